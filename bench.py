@@ -4,17 +4,28 @@ Cityscapes-shaped batches, per-rank batch 8 (train_stage3_cmdline.json), one pro
 RCCL.  A "step" = forward (ResNet-101 + ASPP + SSSR/SISR decoders + feature transformers) + CE/MSE/FA losses + backward +
 gradient reduction + SGD update + the per-iteration loss/NaN readback, exactly what train_or_resume() runs per batch.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed steps, times exactly K steps, writes the outputs of the last timed step if --dump-outputs is
+given, and prints the result line.  Everything else the benchmark measures or checks runs only with --full: the same step under the
+other conv arithmetics, BASELINE config 5's size, the per-kernel rooflines, the CPU baselines and, with N > 1, the collective timings
+and the check that the ranks hold identical parameters (--no-prof / --no-config5 / --no-cpu-baseline drop parts of it).
+
+--dump-outputs DIR writes what the last timed step gave its caller as DIR/<name>.npy: the losses [CE, MSE, FA, total] (float64), and
+in float32 the four network outputs, the parameters after the SGD update and the BatchNorm running statistics; of an array larger than
+DUMP_SAMPLE elements a fixed, seeded sample of that many (sample_index).  The inputs, the initial weights and the dropout keys are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts its own N ranks (python -m torch.distributed.run, one
 per GPU, rendezvous on 127.0.0.1) BEFORE anything touches the GPU and exits with their return code; launched by
 torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE from the environment.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  `value` is measured with the DEFAULT conv arithmetic, the
+Prints ONE JSON line on rank 0.  `value` is measured with the DEFAULT conv arithmetic, the
 fp32-equivalent "f16x3" split (two fp16 terms of the per-tensor scaled operands, three MFMAs per product; fp32 storage, fp32
 accumulation, error vs fp64 equal to exact-product fp32 MFMA: DESIGN.md section 3b); the same step under the other arithmetics -
 "bf16x6" (round 2's fp32-equivalent split), "mixed", exact-product "fp32" MFMA and the reduced-precision "f16x1" (one fp16 MFMA per
-product: what apex O1 / O2 compute) - is timed over the same step counts and listed in `images_per_s_by_conv_arithmetic`.  Extra objects:
+product: what apex O1 / O2 compute) - is timed over the same step counts and listed in `images_per_s_by_conv_arithmetic` (--full).
+Extra objects of --full:
   roofline       - the dominant kernel (the MFMA implicit-GEMM conv family that takes the most device time): achieved in-bounds
                    (algorithmic) TFLOP/s from HIP events recorded by the library around every launch, against the dense MFMA peak
                    of the arithmetic that kernel runs in: 157.3 TFLOP/s for fp32 MFMA, 2516.6/3 for f16x3 / bf16x3 and 2516.6/6 for bf16x6
@@ -54,16 +65,21 @@ ARITH_TEXT = {'fp32': 'exact-product fp32 MFMA', 'bf16x3': 'bf16x3 split, fp32 a
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=100)
-    ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=100, help='timed steps (at least 1)')
+    ap.add_argument('--warmup', type=int, default=20, help='untimed steps before them')
     ap.add_argument('--batch', type=int, default=8, help='per-rank batch (train_stage3_cmdline.json: 8)')
     ap.add_argument('--height', type=int, default=256, help='input height (BASELINE config 5: --height 512 --width 1024)')
     ap.add_argument('--width', type=int, default=512)
     ap.add_argument('--stage', type=int, default=3)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-prof', action='store_true', help='skip the per-kernel roofline passes and the per-arithmetic runs')
-    ap.add_argument('--no-config5', action='store_true', help="skip the bounded BASELINE config-5 run (512x1024 -> 1024x2048, 8 steps) of the default line")
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the outputs of the last timed step to DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true', help='after the headline: per-arithmetic runs, config 5, rooflines, CPU baselines, collective timings')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baselines')
+    ap.add_argument('--no-prof', action='store_true', help='--full without the per-kernel roofline passes and the per-arithmetic runs')
+    ap.add_argument('--no-config5', action='store_true', help="--full without the bounded BASELINE config-5 run (512x1024 -> 1024x2048, 8 steps)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def spawn_ranks(args):
@@ -305,6 +321,41 @@ def hbm_roofline(torch, HF, flat, B, H, W, reps=10):
     return rows
 
 
+# ----------------------------------------------------------------------------------------------------------------- output dump
+DUMP_SAMPLE = 1 << 20           # elements kept of a larger output (4 MB in float32); seven arrays stay far below 64 MB
+
+
+def sample_index(n, k=DUMP_SAMPLE):
+    """Sorted positions of a fixed sample of k of n elements (None: keep all n).  Seeded by n alone, so every run and every build
+    picks the same positions of an array of that size."""
+    import numpy as np
+    if n <= k:
+        return None
+    return np.sort(np.random.RandomState(n % (1 << 32)).randint(0, n, size=k))
+
+
+def dump_outputs(out_dir, losses, outs, params, running_stats):
+    """--dump-outputs: the losses [CE, MSE, FA, total] of the last timed step (float64), its four network outputs, the parameter arena after
+    its SGD update and the BatchNorm running statistics it left (float32).  An array larger than DUMP_SAMPLE elements is sampled on its own
+    device at sample_index() of its logical (NCHW) order; a smaller one keeps its shape."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'losses': np.asarray(losses, dtype=np.float64)}
+    named = dict(zip(('sssr_logits', 'sisr_output', 'sssr_transform', 'sisr_transform'), outs))
+    named.update(params=params, bn_running_stats=running_stats)
+    for name, x in named.items():
+        x = x.detach()
+        idx = sample_index(x.numel())
+        if idx is not None:
+            x = x.reshape(-1)[torch.from_numpy(idx).to(x.device)]         # reshape: logical order whatever the memory format
+        arrays[name] = x.float().cpu().numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return arrays
+
+
 # ----------------------------------------------------------------------------------------------------------------- main
 def main():
     args = parse_args()
@@ -351,16 +402,18 @@ def main():
     data = SyntheticCityscapes(args.batch, (args.height, args.width), dev, rank=rank, length=1)
     (img, org), (tgt, _) = next(iter(data))
     hp = dict(lr=0.006, momentum=0.9, weight_decay=5e-4)        # train_stage3_cmdline.json
-    weights0 = None if (args.no_cpu_baseline or world > 1) else {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    weights0 = None if (not args.full or args.no_cpu_baseline or world > 1) else {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
 
     host_ms = []
     batch_now = [img, org, tgt]             # the batch run() trains on (the config-5 figure swaps in a 512x1024 one)
+    outs_now = [None]                       # the network outputs of the last step run() enqueued (--dump-outputs)
 
     def run(n):
         # train_or_resume()'s loop: iteration k's loss/NaN readback is collected after iteration k+1 has been enqueued
         last = None
         for _ in range(n):
-            step.enqueue(batch_now[0], batch_now[1], batch_now[2], hp['lr'], hp['momentum'], hp['weight_decay'], True)
+            outs_now[0] = None              # released before the next step allocates, as when the outputs are not kept
+            outs_now[0] = step.enqueue(batch_now[0], batch_now[1], batch_now[2], hp['lr'], hp['momentum'], hp['weight_decay'], True)
             host_ms.append(step.host_enqueue_s * 1e3)
             while step.pending() > 1:
                 last = step.collect()
@@ -389,12 +442,15 @@ def main():
             el = float(tt)
         return el, last
 
-    step.time_collectives = world > 1
+    step.time_collectives = world > 1 and args.full
     elapsed, losses = timed(args.warmup, args.steps)
     host_enqueue = sorted(host_ms)[len(host_ms) // 2] if host_ms else 0.0
     replays = step.graph_replays
+    if args.dump_outputs and rank == 0:
+        stats = [b.reshape(-1) for n, b in model.named_buffers() if n.endswith(('running_mean', 'running_var'))]
+        dump_outputs(args.dump_outputs, losses, outs_now[0], flat.p_flat, torch.cat(stats) if stats else torch.zeros(0))
     comm = None
-    if world > 1:
+    if world > 1 and args.full:
         # the collectives of the timed region, from HIP events on the compute stream (rank 0's view): the rank-0 BatchNorm-buffer broadcast in front
         # of the replay, and the part of the gradient all-reduce that is NOT hidden behind the second backward graph (end of that graph ->
         # all collectives complete); plus the ADVICE check that no fused BatchNorm launch gave up at its device-wide barrier beside RCCL
@@ -432,7 +488,7 @@ def main():
         stuck = HF.bn_fused_barrier_timeouts()
         assert stuck == 0, f'{stuck} fused BatchNorm blocks timed out at their device-wide barrier while RCCL shared the device'
         comm['bn_fused_barrier_timeouts'] = stuck
-    if world > 1:
+    if world > 1 and args.full:
         # data-parallel invariant: after K identical-seed steps every rank must hold bit-identical parameters
         chk = torch.stack([flat.p_flat.double().sum(), flat.p_flat.double().abs().sum()])
         lo, hi = chk.clone(), chk.clone()
@@ -442,7 +498,7 @@ def main():
     # the same step under the other conv arithmetics, timed over the SAME warm-up / step counts (every rank takes part)
     by_arith = None
     default_mode = HF.get_conv_precision()
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         gb = args.batch * world
         by_arith = {default_mode: round(gb * args.steps / elapsed, 1)}
         for mode in ('f16x3', 'f16x1', 'bf16x6', 'mixed', 'fp32'):
@@ -453,9 +509,9 @@ def main():
             by_arith[mode] = round(gb * args.steps / el, 1)
         HF.set_conv_precision(None)
 
-    # BASELINE config 5's size (512x1024 -> 1024x2048, per-GPU batch 8) as a bounded extra of the default line: 4 untimed + 8 timed steps
+    # BASELINE config 5's size (512x1024 -> 1024x2048, per-GPU batch 8) as a bounded extra of the --full line: 4 untimed + 8 timed steps
     config5 = None
-    if not args.no_config5 and world == 1 and (args.stage, args.height, args.width, args.batch) == (3, 256, 512, 8):
+    if args.full and not args.no_config5 and world == 1 and (args.stage, args.height, args.width, args.batch) == (3, 256, 512, 8):
         (img5, org5), (tgt5, _) = next(iter(SyntheticCityscapes(args.batch, (512, 1024), dev, rank=rank, length=1)))
         batch_now[:] = [img5, org5, tgt5]
         config5 = {'workload': 'the same stage-3 step at 512x1024 input -> 1024x2048 logits, per-GPU batch 8 (BASELINE.json configs[4] on one GPU), 4 untimed + 8 timed steps',
@@ -494,7 +550,7 @@ def main():
                                      for f in fams}}
 
     roof = None
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         # Per-kernel durations: the timed region replays a hipGraph (no place for per-launch events) and overlaps weight-gradient kernels
         # with the rest of backward, so the roofline comes from a few extra EAGER steps right behind it, every conv launch bracketed by
         # HIP events on its launch stream and the weight-gradient side stream off (a kernel's bracket is then its own execution).
@@ -546,7 +602,7 @@ def main():
             roof['decoder_stack'] = decoder_stack_roofline(torch, HF, args.batch, args.height, args.width)
 
     hbm = None
-    if not args.no_prof and world == 1:
+    if args.full and not args.no_prof and world == 1:
         hbm = hbm_roofline(torch, HF, flat, args.batch, args.height, args.width)
 
     if rank == 0:
