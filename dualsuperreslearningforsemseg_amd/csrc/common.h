@@ -67,10 +67,12 @@ __device__ inline float philox_uniform(uint64_t e, uint64_t seed, uint32_t strea
 // of libm's ~20 (range reduction + polynomial + overflow / denormal cases, none of which a non-positive argument needs); within 2 ulp of expf for
 // x in [-87, 0], 0 below (the hardware flushes the denormal result).  ce_fused_kernel and the ConvTranspose backward that forms the CE gradient
 // itself (convt_dma.hip) both use it: their results are bit-identical.
+// t = -inf (x = -inf: a -inf logit, or v - m overflowing; or x below -2.3e38, where the product overflows) would make r = -inf + inf = NaN:
+// r = 0 there, and the result is 2^-inf = 0 as for expf.  A NaN x fails the comparison too and stays NaN through e0.
 __device__ __forceinline__ float exp_nonpos(float x) {
     constexpr float L2E_HI = 1.44269502162933349609375f, L2E_LO = 1.925963033500011e-08f, LN2 = 0.693147182464599609375f;
     const float t = x * L2E_HI;
-    const float r = fmaf(x, L2E_LO, fmaf(x, L2E_HI, -t));
+    const float r = t > -INFINITY ? fmaf(x, L2E_LO, fmaf(x, L2E_HI, -t)) : 0.f;
     const float e0 = __builtin_amdgcn_exp2f(t);
     return fmaf(e0, r * LN2, e0);
 }

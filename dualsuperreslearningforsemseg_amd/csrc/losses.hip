@@ -34,7 +34,9 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
                 for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
                 float s = 0.f;
                 for (int c = 0; c < C; ++c) s += expf(v[c] - m);
-                loss += (double)(m + logf(s) - v[min(tg, C - 1)]);
+                // a label outside [0, C) that is not ignore_index: torch's CrossEntropyLoss asserts; here it poisons the loss (as ce_fused_kernel does)
+                const float vt = tg < C ? v[tg] : __builtin_nanf("");
+                loss += (double)(m + logf(s) - vt);
                 cnt += 1.0;
             }
         }
@@ -72,7 +74,8 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
                 float s = 0.f;
                 for (int c = 0; c < C; ++c) s += expf(v[c] - m);
                 const float inv = 1.f / s;
-                for (int c = 0; c < C; ++c) v[c] = (expf(v[c] - m) * inv - (c == tg ? 1.f : 0.f)) * scale;
+                const bool bad = tg >= C;             // label outside [0, C), not ignored: a NaN gradient row, as the loss
+                for (int c = 0; c < C; ++c) v[c] = bad ? __builtin_nanf("") : (expf(v[c] - m) * inv - (c == tg ? 1.f : 0.f)) * scale;
             } else {
                 for (int c = 0; c < C; ++c) v[c] = 0.f;
             }

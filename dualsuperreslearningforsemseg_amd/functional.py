@@ -1324,11 +1324,32 @@ class _ConvT2x2(torch.autograd.Function):
         N, Ci, H, W = x.shape
         Co = w.shape[1]
         h = ctx.holder
-        fused = dy is None and h is not None and h.armed
+        hand = None
+        if h is not None and h.armed:           # the loss left d(CE)/d(logits) to this layer: take it over, and disarm the holder whatever happens next
+            hand = (h.y, h.target, int(h.ignore_index), h.count, h.ft)
+            h.armed = False; h.ft = None; h.target = None; h.count = None; h.y = None; h.value = None
+        fused = dy is None and hand is not None
         if dy is None and not fused:
             raise DsrlHipError('conv_transpose2d_k2s2: backward reached without a gradient for the output')
         if not fused:
             dy = pm_dense(dy)
+        if hand is not None and not fused:
+            # another consumer of the logits sent a gradient too (it is not the loss's: fused_losses returned none): d(CE)/d(logits) and the
+            # transformer's term are written as the unfused step writes them (dsrl_ce_fused, dsrl_pointwise_strided_bwd(accumulate = 1)), dy is
+            # added as autograd would add it, and the plain backward below takes the sum
+            y, target, ign, _, ft = hand
+            P = N * 4 * H * W
+            dl = new_cl((N, Co, 2 * H, 2 * W), x)
+            scal = torch.empty(8, device=x.device, dtype=torch.float32)
+            wsc = _ws(cquery('dsrl_ce_fused_workspace_bytes', P), x)
+            call('dsrl_ce_fused', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, dl.data_ptr(), Co, scal.data_ptr(), None, wsc.data_ptr(), wsc.numel(), _stream())
+            if ft is not None:
+                ft_g, ft_w, ft_s = ft
+                dwf = torch.empty(Co, device=x.device, dtype=torch.float32)          # the transformer's weight gradient was delivered by its own backward
+                wsf = _ws(cquery('dsrl_pointwise_strided_bwd_workspace_bytes', N, 2 * H, 2 * W, Co, ft_s), x)
+                call('dsrl_pointwise_strided_bwd', y.data_ptr(), ft_w.data_ptr(), ft_g.data_ptr(), dl.data_ptr(), dwf.data_ptr(), 1,
+                     N, 2 * H, 2 * W, Co, ft_s, wsf.data_ptr(), wsf.numel(), _stream())
+            dy = dl.add_(dy)
         dx = new_cl((N, Ci, H, W), x)
         wsink = _sink_flat(ctx.params[0], w.numel())
         bsink = _sink_flat(ctx.params[1], Co) if ctx.has_bias else None
@@ -1336,11 +1357,11 @@ class _ConvT2x2(torch.autograd.Function):
         db = (bsink if bsink is not None else torch.empty(Co, device=x.device, dtype=torch.float32)) if ctx.has_bias else None
         ws = _ws(cquery('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, Ci, Co), x)
         if fused:
-            ft_g, ft_w, ft_s = h.ft if h.ft is not None else (None, None, 0)
-            call('dsrl_convt2x2_bwd_ce', x.data_ptr(), w.data_ptr(), h.y.data_ptr(), h.target.data_ptr(), int(h.ignore_index), h.count.data_ptr() + 4,
+            y, target, ign, count, ft = hand
+            ft_g, ft_w, ft_s = ft if ft is not None else (None, None, 0)
+            call('dsrl_convt2x2_bwd_ce', x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, count.data_ptr() + 4,
                  None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
                  dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
-            h.armed = False; h.ft = None; h.target = None; h.count = None; h.y = None; h.value = None
         else:
             call('dsrl_convt2x2_bwd', x.data_ptr(), w.data_ptr(), dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(),
                  N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
@@ -1408,8 +1429,9 @@ class _PointwiseStrided(torch.autograd.Function):
         N, Cc, H, W = x.shape
         dy = dy.contiguous()
         # x also feeds the fused loss (fused_losses): that node ran first (it is the root of the backward pass) and published the dense
-        # gradient it returned for x; our contribution lives on the stride grid only (1/64 of the pixels) and is added into that buffer
-        # instead of being materialised as a mostly-zero tensor that autograd would then add with a full pass
+        # gradient it computed for x; our contribution lives on the stride grid only (1/64 of the pixels) and is added into that buffer
+        # instead of being materialised as a mostly-zero tensor that autograd would then add with a full pass.  The loss
+        # left the buffer to us: it goes on to autograd as our gradient of x
         slot = ctx.out_slot
         lg = ctx.logits_grad
         if lg is not None and lg.armed and lg.y is not None and lg.y.data_ptr() == x.data_ptr() and lg.ft is None:
@@ -1436,8 +1458,8 @@ class _PointwiseStrided(torch.autograd.Function):
             slot.closed = True
         if wsink is not None:
             _sunk(ctx.wparam)
-            return (None if acc else dx), None, None, None
-        return (None if acc else dx), _deliver(ctx.wparam, dw.view(ctx.wshape)), None, None
+            return dx, None, None, None
+        return dx, _deliver(ctx.wparam, dw.view(ctx.wshape)), None, None
 
 
 def pointwise_strided(x, weight, stride, out_slot=None):
@@ -1600,11 +1622,15 @@ class _FusedLosses(torch.autograd.Function):
             sb, sc, sh, sw = ft1.stride()
             call('dsrl_fa_bwd', ft1.data_ptr(), ft2.data_ptr(), B, Cf, Hf, Wf, sb, sc, sh, sw, k, 0, gw.data_ptr(), saved.data_ptr(),
                  d1.data_ptr(), d2.data_ptr(), None, 0, _stream())
-        # publish the two dense gradients: the stride-8 feature transformers add their sparse contributions into them (GradSlot protocol)
-        for slot, buf in zip(ctx.slots, (dl, da)):
+        # publish the two dense gradients: the stride-8 feature transformers add their sparse contributions into them (GradSlot protocol) and hand
+        # them on as their own input gradient.  Returned from here, a buffer would be summed with the gradient of any other consumer of the output
+        # that reached autograd first - before the transformer's part is in it, which would then be lost.
+        out = [dl, da]
+        for i, (slot, buf) in enumerate(zip(ctx.slots, (dl, da))):
             if slot is not None and buf is not None and not slot.closed and slot.buf is None:
                 slot.buf = buf
-        return dl, da, d1, d2, None, None, None, None, None, None, None, None
+                out[i] = None
+        return out[0], out[1], d1, d2, None, None, None, None, None, None, None, None
 
 
 _fused_losses_root_checked = False

@@ -617,15 +617,32 @@ def test_convT_backward_lds_dma_vs_oracle_and_register_staged(shape, cap, monkey
         assert torch.equal(a, c)
 
 
-@pytest.mark.parametrize('shape,cap,ft', [((1, 4, 128), 0, 8), ((2, 6, 256), 3, 8), ((2, 9, 384), 2, 0), ((3, 4, 128), 5, 4)])
+CONVT_CE_SHAPES = [((1, 4, 128), 0, 8), ((2, 6, 256), 3, 8), ((2, 9, 384), 2, 0), ((3, 4, 128), 5, 4)]
+
+
+@pytest.mark.parametrize('shape,cap,ft', CONVT_CE_SHAPES)
 def test_convT_backward_with_cross_entropy_inside_bit_identical_to_three_calls(shape, cap, ft, monkeypatch):
     # dsrl_convt2x2_bwd_ce: the ConvTranspose backward that forms d(CE)/d(logits) (+ the stride-s feature transformer's g * w_c) inside the kernel, against
     # the three calls it replaces - dsrl_ce_fused (writes the gradient), dsrl_pointwise_strided_bwd(accumulate = 1), dsrl_convt2x2_bwd - bit for bit:
     # dx, dw, db.  Ignored pixels (10 % + one whole row), block caps that make blocks walk many segments; and the CE gradient
-    # itself against the fp64 oracle through dx.
+    # itself against the fp64 oracle through dx.  The default build: the transform in four waves of its own.
+    _convT_backward_with_cross_entropy_vs_three_calls(shape, cap, ft, None, monkeypatch)
+
+
+@pytest.mark.parametrize('shape,cap,ft', CONVT_CE_SHAPES)
+def test_convT_backward_with_cross_entropy_inside_8_wave_build_bit_identical_to_three_calls(shape, cap, ft, monkeypatch):
+    # the same checks for the build selected by DSRL_CONVT_CE_WAVES=8: the transform inside the eight MFMA waves
+    _convT_backward_with_cross_entropy_vs_three_calls(shape, cap, ft, '8', monkeypatch)
+
+
+def _convT_backward_with_cross_entropy_vs_three_calls(shape, cap, ft, waves, monkeypatch):
     from dualsuperreslearningforsemseg_amd._lib import call, query
     for k in ('DSRL_CONVT_CE', 'DSRL_CONVT_DMA', 'DSRL_CONVT_MFMA'):
         monkeypatch.setenv(k, '1')               # the path under test, whatever the suite's environment says
+    if waves is None:
+        monkeypatch.delenv('DSRL_CONVT_CE_WAVES', raising=False)
+    else:
+        monkeypatch.setenv('DSRL_CONVT_CE_WAVES', waves)
     N, H, W = shape
     C = 19
     rs = np.random.RandomState(N * 1000 + H * 10 + W)
