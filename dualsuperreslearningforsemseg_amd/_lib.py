@@ -129,6 +129,8 @@ PROTOTYPES = {
     'dsrl_fa_bwd': (i32, [fp, fp, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, fp, fp, fp, fp, fp, sz, stream_t]),
     'dsrl_seg_metrics': (i32, [fp, i32, fp, i64, i32, i32, fp, stream_t]),
     'dsrl_prepare_batch': (i32, [fp, fp, fp, C.POINTER(f32), C.POINTER(f32), fp, fp, fp, i32, i32, i32, i32, i32, stream_t]),
+    'dsrl_augment_geometry': (i32, [fp, fp, fp, fp, fp, fp, i32, i32, i32, stream_t]),
+    'dsrl_prepare_batch_augmented': (i32, [fp, fp, fp, C.POINTER(f32), C.POINTER(f32), fp, fp, fp, i32, i32, i32, i32, i32, fp, stream_t]),
     'dsrl_sgd_step': (i32, [fp, fp, fp, i64, f32, f32, f32, f32, stream_t]),
     'dsrl_sgd_step_dev': (i32, [fp, fp, fp, i64, fp, stream_t]),
     'dsrl_sgd_step_dev_segments': (i32, [fp, fp, fp, fp, i64, fp, stream_t]),

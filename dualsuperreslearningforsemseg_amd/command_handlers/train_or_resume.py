@@ -10,8 +10,9 @@ What differs by design:
     arithmetic of the MFMA conv kernels instead: 'O0' = fp32-equivalent f16x3 (the default), 'O1' = bf16x6 forward / bf16x3 gradients, 'O2'/'O3' =
     bf16x3 everywhere (BASELINE config 5's reduced-precision MFMA path).  Storage and accumulation stay fp32 in every mode, so there
     is no loss scaling (nothing can underflow that fp32 training would keep) and `amp_state_dict` is None;
-  * the input pipeline (torchvision Cityscapes + PIL transforms) is out of scope: `dataset` may carry a 'loader_factory'
-    (callable(split, batch_size, device, rank, world) -> iterable of ((input_image, input_org), (target, _))) and
+  * the input pipeline (torchvision Cityscapes + PIL transforms) reads a pre-decoded uint8 cache of the Cityscapes tree and runs the random
+    augmentations as HIP kernels (datasets/Cityscapes/loader.py, models/transforms/augment.py).  `dataset` may instead carry a 'loader_factory'
+    (callable(split, batch_size, device, rank, world) -> iterable of ((input_image, input_org), (target, _))), which is used as given;
     `SyntheticCityscapes` below provides device-resident batches of the Cityscapes shapes.
 """
 import glob
@@ -474,11 +475,14 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     step = TrainStep(model, flat, stage, w1, w2, ds.IGNORE_CLASS_LABEL)
 
     factory = dataset.get('loader_factory')
-    if factory is None:
+    own_loader = factory is None
+    if own_loader:
         os.makedirs(dataset['path'], exist_ok=True)
         if len(os.listdir(dataset['path'])) == 0:
             raise Exception("Cityscapes dataset was not found under '{:s}'.".format(dataset['path']))
-        raise NotImplementedError("the torchvision/PIL input pipeline is out of scope here: pass dataset['loader_factory']")
+        # the Cityscapes tree (or its pre-decoded cache): HIP augmentations on a side stream, datasets/Cityscapes/loader.py
+        from ..datasets.Cityscapes.loader import loader_factory
+        factory = loader_factory(dataset, input_size, settings.RANDOM_SEED, distributed=bool(distributed))
     train_loader = factory('train', batch_size, device_obj, rank, world)
     val_loader = factory('val', batch_size, device_obj, rank, world) if is_master_rank else None
 
@@ -508,6 +512,8 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     try:
         for epoch in range(starting_epoch + 1, epochs + 1):
             lr = polynomial_lr(learning_rate, end_learning_rate, epoch - 1, epochs, poly_power)       # scheduler.step() per epoch, :349
+            if own_loader:
+                train_loader.set_epoch(epoch)     # the sample order and the augmentation draws of this epoch
             means = _do_train_val(True, epoch, model, step, train_loader, lr, momentum, weights_decay, freeze_batch_norm, is_master_rank)
             rec = {'epoch': epoch, 'lr': lr, 'train': means}
             stop = False

@@ -1,6 +1,7 @@
 """Device-side tail of the reference's training input pipeline (models/transforms/): everything after the random PIL
 augmentations is deterministic - label-id remap (JointImageAndLabelTensor.py:9-16), ToTensor + Normalize (JointNormalize.py:11)
-and the dual-scale resize (JointScaledImage.py:27-32) - and runs as one HIP call on decoded uint8 crops."""
+and the dual-scale resize (JointScaledImage.py:27-32) - and runs as one HIP call on decoded uint8 crops.  The random augmentations in front of
+it are DeviceJointAugmentation (augment.py)."""
 import ctypes
 
 import torch
@@ -38,3 +39,6 @@ class DeviceBatchPreparation:
         call('dsrl_prepare_batch', rgb_u8.contiguous().data_ptr(), None if labels_u8 is None else labels_u8.contiguous().data_ptr(), lut.data_ptr(),
              self.mean, self.std, img_in.data_ptr(), img_org.data_ptr(), None if target is None else target.data_ptr(), N, Hs, Ws, H, W, HF._stream())
         return (img_in.permute(0, 3, 1, 2)[:, :3], img_org.permute(0, 3, 1, 2)), (target, labels_u8)
+
+
+from .augment import DeviceJointAugmentation  # noqa: E402,F401  (imports DeviceBatchPreparation from this module)

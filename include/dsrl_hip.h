@@ -435,6 +435,31 @@ int dsrl_seg_metrics(const float* logits, int ld, const uint8_t* target, int64_t
 int dsrl_prepare_batch(const uint8_t* rgb, const uint8_t* labels, const uint8_t* lut /*256*/, const float* mean /*3*/, const float* std /*3*/,
                        float* img_in, float* img_org, uint8_t* target, int N, int Hs, int Ws, int H, int W, dsrl_stream_t stream);
 
+/* Random joint augmentations of the training transform (train_or_resume.py:128-137), one 128-byte row per sample in device memory, drawn and
+ * filled on the host (models/transforms DeviceJointAugmentation).  Samples of one launch may differ in every field. */
+#define DSRL_AUG_HFLIP 1 /* JointHFlip                                   */
+#define DSRL_AUG_BLUR 2  /* JointRandomGaussianBlur(3): blur[] applies    */
+#define DSRL_AUG_GRAY 4  /* JointRandomGrayscale                          */
+typedef struct dsrl_augment_params {
+    double rot[6];      /* PIL Image.rotate's inverse matrix: source = (rot0 x + rot1 y + rot2, rot3 x + rot4 y + rot5) at output pixel centres   */
+    int32_t rot_fix[6]; /* the same in 16.16 fixed point for the nearest path: a0, a1, a2 + half-pixel terms, a3, a4, a5 + half-pixel terms       */
+    int32_t box[4];     /* crop x, y, width, height in the rotated image, resized back to the full size (0, 0, Ws, Hs: no crop)                  */
+    int32_t flags;      /* DSRL_AUG_*                                                                                                              */
+    float blur[9];      /* 3x3 Gaussian weights, row-major (torchvision GaussianBlur: outer product of the normalised 1-D kernel)                 */
+} dsrl_augment_params;
+/* JointRandomRotate (bilinear image, fill 0; nearest labels, fill 255) then JointRandomCrop's resize of the box back to (Ws, Hs) (bilinear image,
+ * nearest labels), Pillow-exact on uint8: rgb (N,Hs,Ws,3) -> rgb_out, labels (N,Hs,Ws) raw ids -> labels_out.  label_src (N x (Ws + Hs) int32,
+ * device) holds per sample the crop-box source column of every output column, then the source row of every output row, of the nearest label
+ * resize: Pillow accumulates them by sequential double additions, which the host repeats.  labels, label_src and labels_out are nullable together.
+ * One pass; the outputs must not alias the inputs. */
+int dsrl_augment_geometry(const uint8_t* rgb, const uint8_t* labels, const dsrl_augment_params* params /*device, N rows*/, const int32_t* label_src,
+                          uint8_t* rgb_out, uint8_t* labels_out, int N, int Hs, int Ws, dsrl_stream_t stream);
+/* dsrl_prepare_batch after JointHFlip, JointRandomGaussianBlur (3x3, reflect padding, evaluated at the taps the resize reads) and
+ * JointRandomGrayscale as each row's flags select; with every flag clear the output is bit-identical to dsrl_prepare_batch.  Hs, Ws >= 2. */
+int dsrl_prepare_batch_augmented(const uint8_t* rgb, const uint8_t* labels, const uint8_t* lut /*256*/, const float* mean /*3*/, const float* std /*3*/,
+                                 float* img_in, float* img_org, uint8_t* target, int N, int Hs, int Ws, int H, int W,
+                                 const dsrl_augment_params* params /*device, N rows*/, dsrl_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * optimiser + bookkeeping on the flat parameter arena (train_or_resume.py:63-66, 445, 426-433)
  * ---------------------------------------------------------------------------------------------- */
