@@ -169,6 +169,20 @@ def load():
     return lib
 
 
+def knob(name, default):
+    """The one way the package reads a DSRL_* environment switch (table: DESIGN.md, "Environment switches"); the library's twin is knob() in
+    csrc/common.h.  The value comes back in the type of `default`: bool ('0' = off, anything else on), int, or the string itself (default a
+    string or None)."""
+    v = os.environ.get(name)
+    if v is None:
+        return default
+    if isinstance(default, bool):
+        return v != '0'
+    if isinstance(default, int):
+        return int(v)
+    return v
+
+
 def check(code, what):
     if code != 0:
         msg = _lib.dsrl_last_error().decode('utf-8', 'replace') if _lib is not None else ''

@@ -88,8 +88,8 @@ class TrainStep:
         self.flag = t.zeros(1, dtype=t.int32, device=dev)
         self.zero = t.zeros((), device=dev)
         self._pending, self._free = [], []           # (pinned host buffer, event) of iterations in flight / reusable
-        self.use_graph = (os.environ.get('DSRL_GRAPH', '1') != '0') if graph is None else bool(graph)
-        self.fused_losses = os.environ.get('DSRL_FUSED_LOSSES', '1') != '0'
+        self.use_graph = HF.knob('DSRL_GRAPH', True) if graph is None else bool(graph)
+        self.fused_losses = True
         self._graphs, self._warm = {}, {}
         self.rng = self.hyper = self._hyper_host = self._hyper_vals = None
         self.host_enqueue_s = 0.0
@@ -105,7 +105,7 @@ class TrainStep:
         # schedule and was rehearsed on one GPU, but it has never run with two GPUs on RCCL, so it stays opt-in until a multi-GPU run has recorded
         # `bn_fused_barrier_timeouts` and the exposed all-reduce time with it.  Default: ONE graph, one all-reduce of the whole
         # 239.5 MB arena behind it (round 2's schedule).
-        self.split = flat.world > 1 and flat.defer_collectives and os.environ.get('DSRL_GRAPH_SPLIT', '0') != '0'
+        self.split = flat.world > 1 and flat.defer_collectives and HF.knob('DSRL_GRAPH_SPLIT', False)
         self.time_collectives = False           # bench.py: bracket the exposed part of the collectives with events
         self.comm_events = []                   # (broadcast start, end, replay end, end of exchange [+ update: one-graph schedule]) per step
 
@@ -149,7 +149,7 @@ class TrainStep:
                     HF.nan_check_(self.flag, *[o for o in outs if o.is_cuda])              # the four NaN asserts, :426-433
                     ce, ms, fa, total = self.losses(outs, input_org, target)
                     vals = t.cat([t.stack([ce, ms, fa, total]).detach().float(), self.flag.float()])
-                if in_graph and os.environ.get('DSRL_GRAPH_FAIL_TEST'):
+                if in_graph and HF.knob('DSRL_GRAPH_FAIL_TEST', ''):
                     raise RuntimeError('DSRL_GRAPH_FAIL_TEST: simulated failure in the middle of a capture')      # tests/test_rccl_gpu.py
                 if do_train:
                     if self.fused_losses:
@@ -226,26 +226,19 @@ class TrainStep:
         bns = [m for m in self.model.modules() if isinstance(m, t.nn.modules.batchnorm._BatchNorm)]
         before = [getattr(m, '_dsrl_batches', 0) for m in bns]
         step_before = HF._rng_state['step']
-        dump_dir = os.environ.get('DSRL_GRAPH_DEBUG_DUMP')          # tools/graph_memset_edges.py: keep the captured hipGraph_t and write it as a DOT file
-        c.graph = t.cuda.CUDAGraph(keep_graph=True) if dump_dir else t.cuda.CUDAGraph()
+        c.graph = t.cuda.CUDAGraph()
         # A forked capture (weight gradients on a side stream) replays slower than a linear one on this runtime: the graph executor
         # pays more for its cross-queue dependencies than the overlap wins (measured 24.2 vs 23.8 ms per step), so the capture is
-        # linear unless DSRL_GRAPH_OVERLAP=1
+        # linear
         overlap_was = HF.overlap_wgrad
-        fused_was = None
-        if os.environ.get('DSRL_GRAPH_OVERLAP', '0') == '0':
-            HF.overlap_wgrad = False
-        else:
-            # a forked capture can place fused BatchNorm nodes on parallel branches: they share ONE device-wide barrier word pair and must
-            # never overlap each other, so that capture takes the three-kernel BatchNorm path
-            fused_was = HF.set_bn_fused_max_blocks(0)
+        HF.overlap_wgrad = False
         c.keep = HF.graph_keepalive = []          # pinned host tables the captured copies read on every replay
         HF.capture_host, HF.capture_host_off = t.empty(2 << 20, dtype=t.uint8, pin_memory=True), 0      # allocated BEFORE the capture starts
         c.keep.append(HF.capture_host)
         if HF.f16_mode():
             c.keep.append(HF.amax_pin(self.flat.device))      # the graph zeroes, maxes into and reads this arena on every replay: it lives as long as the graph
         c.graph_b, c.ready = None, []
-        mode = os.environ.get('DSRL_GRAPH_CAPTURE_MODE', 'thread_local')
+        mode = 'thread_local'
         try:
             if self.split:
                 # two graphs sharing one memory pool: [step start .. backward down to the cut + its weight gradients] and [the rest of backward];
@@ -253,7 +246,7 @@ class TrainStep:
                 with t.cuda.graph(c.graph, capture_error_mode=mode):
                     c.outs, c.vals, cuts = self._phase_a(c.img, c.org, c.tgt, True, True, True)
                 c.ready = self.flat.ready_chunks()
-                c.graph_b = t.cuda.CUDAGraph(keep_graph=True) if dump_dir else t.cuda.CUDAGraph()
+                c.graph_b = t.cuda.CUDAGraph()
                 with t.cuda.graph(c.graph_b, pool=c.graph.pool(), capture_error_mode=mode):
                     self._phase_b(cuts)
                 del cuts
@@ -263,20 +256,8 @@ class TrainStep:
                     self._finish(hp, True)
         finally:
             HF.overlap_wgrad = overlap_was
-            if fused_was is not None:
-                HF.set_bn_fused_max_blocks(fused_was)
             HF.graph_keepalive = None
             HF.capture_host = None
-        if dump_dir:
-            import ctypes
-            os.makedirs(dump_dir, exist_ok=True)
-            hip = ctypes.CDLL('libamdhip64.so')
-            hip.hipGraphDebugDotPrint.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint]
-            for g_, name in ((c.graph, 'graph_a.dot'), (c.graph_b, 'graph_b.dot')):
-                if g_ is not None:
-                    rc = hip.hipGraphDebugDotPrint(ctypes.c_void_p(g_.raw_cuda_graph()), os.path.join(dump_dir, name).encode(), 1)      # 1 = verbose
-                    print(f'[dsrl] hipGraphDebugDotPrint({name}) -> {rc}', flush=True)
-                    g_.instantiate()
         # nothing ran during the capture: take back the host-side bookkeeping of that phantom iteration
         HF._rng_state['step'] = step_before
         c.bns = [m for m, n in zip(bns, before) if getattr(m, '_dsrl_batches', 0) != n]

@@ -1300,14 +1300,11 @@ static SeedArg seed_arg(uint64_t seed) {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     return SeedArg{(unsigned long long)seed, g_rng_dev_key[dev].load()};
 }
-static int env_int_bn(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 // The from-statistics kernels: every block merges the partials of its channel group again, and what that costs is the bytes a CU pulls through its L1
 // (128 partials x 4 blocks of 256 threads per CU: 3.4 us on a 3.7 us launch; 2 blocks of 512: 1.8 us; 1 block of 1024: 0.9 us - but the streaming part
 // of a 1024-thread block is 0.3 us slower on a 4 MB tensor and 1.5 us on a 16 MB one, profiles/round5_bn_prologue_probe.txt).  So: 512 threads, and
-// 1024 where there are many partials over a small tensor.  DSRL_BN_APPLY_THREADS = 256 | 512 | 1024 forces one size.
+// 1024 where there are many partials over a small tensor.
 static int stats_apply_threads(int64_t P, int C, int nparts) {
-    static const int forced = [] { const int v = env_int_bn("DSRL_BN_APPLY_THREADS", 0); return v == 256 || v == 512 || v == 1024 ? v : 0; }();
-    if (forced) return forced;
     return nparts >= 128 && P * C <= (2ll << 20) ? 1024 : 512;
 }
 static int stats_apply_rows(int64_t P, int groups, int threads) {        // rows per slab: ~(4 * 256 * 256 / threads) blocks, at least one pass of rows each
@@ -1321,7 +1318,7 @@ struct FusedPlan { bool ok; int blocks, groups, slabs, rows_per_slab; };
 static FusedPlan fused_plan(int64_t P, int C) {
     FusedPlan f{false, 0, 0, 0, 0};
     int max_blocks = g_fused_max_blocks.load();
-    if (max_blocks < 0) max_blocks = !env_int_bn("DSRL_BN_FUSED", 1) ? 0 : (env_int_bn("DSRL_BN_FUSED_BIG", 1) ? kFusedBlocksBig : kFusedBlocks);
+    if (max_blocks < 0) max_blocks = !knob("DSRL_BN_FUSED", 1) ? 0 : (knob("DSRL_BN_FUSED_BIG", 1) ? kFusedBlocksBig : kFusedBlocks);
     if (max_blocks < kFusedBlocks || C < 32 || C % 32 || P >= (1ll << 30)) return f;
     const int groups = C / 32;
     for (int blocks : {kFusedBlocks, kFusedBlocksBig}) {
@@ -1348,7 +1345,7 @@ static bool fused_stream_ok(hipStream_t st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     unsigned long long id = 0;
     if (hipStreamGetCaptureInfo(st, &cs, &id) == hipSuccess && cs == hipStreamCaptureStatusActive) {
-        // A capture orders only the nodes of ONE stream: a forked capture (DSRL_GRAPH_OVERLAP=1) could place two barrier launches on parallel
+        // A capture orders only the nodes of ONE stream: a forked capture could place two barrier launches on parallel
         // branches that share the word pair.  The first fused launch of a capture pins its stream for that capture; launches the same capture
         // records on another stream take the three-kernel path.
         std::lock_guard<std::mutex> lock(g_fused_mu);
@@ -1654,7 +1651,7 @@ static int dropout_common(const float* x, int ldx, float* y, int ldy, int64_t P,
     hipStream_t st = (hipStream_t)stream;
     if (int e = bind_stream_device(st)) return e;
     const long long total = (long long)P * C;
-    if (ldx == C && ldy == C && total % 4 == 0 && total / 4 < (1ll << 32) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && env_int_bn("DSRL_DROPOUT_FLAT", 1)) {
+    if (ldx == C && ldy == C && total % 4 == 0 && total / 4 < (1ll << 32) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0) {
         hipLaunchKernelGGL(dropout_flat4_kernel, dim3((unsigned)std::min<long long>(ceil_div(total / 4, 256), 8192)), dim3(256), 0, st, reinterpret_cast<const float4*>(x),
                            reinterpret_cast<float4*>(y), (unsigned)(total / 4), p, seed_arg(seed), (unsigned)rng_stream);
         return launch_status("dropout_flat4_kernel");

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
 #include "../../include/dsrl_hip.h"
 
 namespace dsrl {
@@ -29,6 +30,11 @@ int convt_bwd_dma_blocks(long long nseg, int cap);
 int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, hipStream_t st);
 int launch_convt_bwd_dma_ce(const float* x, const float* w, const float* logits, float* dx, float* part, int N, int H, int W, int nblocks,
                             const unsigned char* target, int ignore_index, const float* count, const float* ft_g, const float* ft_w, int ft_s, hipStream_t st);
+
+// The one way the library reads a DSRL_* environment switch (table: DESIGN.md §9).  Read at every call, never cached: tests change switches
+// between calls inside one process.  knob_str: for the one switch whose value is a path (DSRL_PROF_DUMP).
+static inline const char* knob_str(const char* name) { return getenv(name); }
+static inline int knob(const char* name, int dflt) { const char* v = knob_str(name); return v ? atoi(v) : dflt; }
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
@@ -130,8 +136,7 @@ __device__ inline void amax_publish(unsigned m, unsigned* out) {
 int launch_amax(const float* x, int ld, long long P, int C, unsigned* out, hipStream_t st);
 // Zero-fill as a KERNEL launch (conv_igemm.hip), not hipMemsetAsync.  Round 3: with the 2 KiB amax scratch of the stem's weight gradient zeroed by a
 // captured memset node, ~40 % of the replays of the two-graph step produced a NaN there, and replacing that one call by a kernel made it disappear.
-// Round 4 dumped the captured graphs of a build with the memsets restored (DSRL_ZERO_FILL_MEMSET=1, tools/graph_memset_edges.py,
-// profiles/round4_graph_memset_edges.txt): both graphs are pure chains and every memset node has its edge to the kernel that consumes the zeroed
+// Round 4 dumped the captured graphs of a build with the memsets restored (profiles/round4_graph_memset_edges.txt): both graphs are pure chains and every memset node has its edge to the kernel that consumes the zeroed
 // words - the capture did NOT drop a dependency.  Why the replay misbehaved is therefore not established (a runtime fault in how memset nodes execute,
 // or a cause the substitution only perturbed); the kernel fill is kept because it leaves kernel nodes as the only node type of the step's graphs.
 int launch_zero_fill(void* p, size_t bytes, hipStream_t st);

@@ -2,11 +2,8 @@
 // conv_planes.hip: operands as fp16 planes staged by LDS-DMA).
 #pragma once
 #include "common.h"
-#include <stdlib.h>
 
 namespace dsrl {
-
-static inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }   // tuning knobs (tools/sweep_conv.py)
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;

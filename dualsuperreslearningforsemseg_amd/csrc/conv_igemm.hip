@@ -24,13 +24,12 @@ constexpr int BK = 32;
 constexpr int LDS_LD = 36;
 
 // 4 waves per SIMD (<= 128 registers) for the tiles that stage at most 8 rows per thread: 4 blocks of 36.9 KB LDS per CU
-// DBUF: two LDS stages - the next chunk is written while the current one feeds the MFMAs, one barrier per chunk (used when
-// few blocks share a CU); !DBUF: one stage, two barriers, half the LDS (4 blocks per CU on the big grids).
-template <int MR, int NR, int WGM, int WGN, bool DGRAD, int MINW = 2, bool DBUF = false>
+// One LDS stage, two barriers per chunk (a two-stage variant was measured: no gain).  The last parameter is always false (it selected that variant)
+// and stays because it is part of the symbol names the profiles and the spill allow-list record.
+template <int MR, int NR, int WGM, int WGN, bool DGRAD, int MINW = 2, bool = false>
 __global__ __launch_bounds__(256, MINW) void conv_igemm_f32_kernel(const ConvArgs a) {
     constexpr int BM = 32 * MR * WGM, BN = 32 * NR * WGN;
     constexpr int A_IT = BM / 32, B_IT = BN / 32;
-    constexpr int STAGE = (BM + BN) * LDS_LD;                    // floats per LDS stage
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x;
@@ -177,42 +176,22 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_f32_kernel(const ConvArg
         }
     };
     if (q0 < q1) set_tap(tap);
-    if (DBUF) {
-        if (q0 < q1) {
-            issue(ra0, rb0);
-            lds_store(ra0, rb0, smem, smem + BM * LDS_LD);
-            issue(ra0, rb0);
+    float* As = smem;
+    float* Bs = smem + BM * LDS_LD;
+    issue(ra0, rb0);
+    if (PF == 2) issue(ra1, rb1);
+    for (int q = q0; q < q1; q += PF) {
+        lds_store(ra0, rb0, As, Bs);
+        __syncthreads();
+        issue(ra0, rb0);                                  // chunk q+PF
+        compute(As, Bs);
+        __syncthreads();
+        if (PF == 2 && q + 1 < q1) {
+            lds_store(ra1, rb1, As, Bs);
             __syncthreads();
-        }
-        for (int q = q0; q < q1; ++q) {
-            const int cur = (q - q0) & 1;
-            float* nA = smem + (cur ^ 1) * STAGE;
-            if (q + 1 < q1) {
-                lds_store(ra0, rb0, nA, nA + BM * LDS_LD);   // stage q+1 (free since the barrier that ended iteration q-1)
-                issue(ra0, rb0);                              // chunk q+2 flies during this iteration's MFMAs
-            }
-            const float* cA = smem + cur * STAGE;
-            compute(cA, cA + BM * LDS_LD);
-            __syncthreads();
-        }
-    } else {
-        float* As = smem;
-        float* Bs = smem + BM * LDS_LD;
-        issue(ra0, rb0);
-        if (PF == 2) issue(ra1, rb1);
-        for (int q = q0; q < q1; q += PF) {
-            lds_store(ra0, rb0, As, Bs);
-            __syncthreads();
-            issue(ra0, rb0);                                  // chunk q+PF
+            issue(ra1, rb1);                              // chunk q+3
             compute(As, Bs);
             __syncthreads();
-            if (PF == 2 && q + 1 < q1) {
-                lds_store(ra1, rb1, As, Bs);
-                __syncthreads();
-                issue(ra1, rb1);                              // chunk q+3
-                compute(As, Bs);
-                __syncthreads();
-            }
         }
     }
 
@@ -1138,7 +1117,7 @@ static void cfg_dims(TileCfg c, int& bm, int& bn) { bm = kCfgDims[c][0]; bn = kC
 static long long cfg_blocks(TileCfg c, long long M, int N) { return ceil_div(M, kCfgDims[c][0]) * ceil_div(N, kCfgDims[c][1]); }
 static int conv_precision_mode();
 static TileCfg pick_cfg(long long M, int N) {
-    const int forced = env_int("DSRL_FORCE_CFG", -1);
+    const int forced = knob("DSRL_FORCE_CFG", -1);
     if (forced >= 0 && forced < kNumCfg && (forced < kNumCfg4 || conv_precision_mode() >= 4)) return (TileCfg)forced;
     if (N <= 32) return cfg_blocks(T256x32, M, N) >= 3 * kNumCU ? T256x32 : T128x32;
     const int r = N % 128;
@@ -1152,26 +1131,25 @@ static TileCfg pick_cfg(long long M, int N) {
 // wgrad: rows are output channels K, columns input channels C.  Measured on MI355X (tools/sweep_wgrad.py): 128x64 tiles
 // (64x64 when K <= 64) with ~4.5 blocks per CU beat the larger tiles on every layer shape of the step.
 static TileCfg pick_cfg_wgrad(int K, int C) {
-    int forced = env_int("DSRL_FORCE_CFG", -1);
-    if (forced < 0) forced = env_int("DSRL_WGRAD_CFG", -1);
+    const int forced = knob("DSRL_FORCE_CFG", -1);
     if (forced >= 0 && forced < kNumCfg4) return (TileCfg)forced;
     // layers with K >= 128 and C >= 128 (the per-tap grid: 1x1, strided and dilated convs of layers 2-4 and ASPP): 128x128 tiles.  Round 4 measured +-1 % for
     // them; with the 3x3 convs gone to conv_wgrad3_kernel the remaining 1x1 problems gain +0.5 .. 1.0 % step throughput on three boxes (profiles/round5_ab.txt):
-    // an activation chunk is fetched and split once per 128 output columns instead of 64.  DSRL_WGRAD_BIG_CFG=-1: 128x64 as before
-    const int big = env_int("DSRL_WGRAD_BIG_CFG", 0);
-    if (big >= 0 && big < kNumCfg4 && K >= 128 && C >= 128) return (TileCfg)big;
+    // an activation chunk is fetched and split once per 128 output columns instead of 64.
+    if (K >= 128 && C >= 128) return T128x128;
     if (C <= 32) return T128x32;
     return K <= 64 ? T64x64 : T128x64;
 }
+constexpr int kWgradTargetBlocks = 1152;        // ~4.5 blocks per CU (tools/sweep_wgrad.py)
 static int pick_psplits(long long tiles, long long chunks) {
-    const int forced = env_int("DSRL_FORCE_PSPLITS", 0);
+    const int forced = knob("DSRL_FORCE_PSPLITS", 0);
     if (forced > 0) return (int)std::max<long long>(1, std::min<long long>(forced, chunks));
-    long long sp = ceil_div(env_int("DSRL_WGRAD_TARGET_BLOCKS", 1152), std::max<long long>(tiles, 1));
+    long long sp = ceil_div(kWgradTargetBlocks, std::max<long long>(tiles, 1));
     sp = std::min(sp, std::max<long long>(1, chunks / 4));
     return (int)std::max<long long>(1, std::min<long long>(sp, 128));
 }
 static int pick_splits(long long tiles, int nq) {
-    const int forced = env_int("DSRL_FORCE_SPLITS", 0);
+    const int forced = knob("DSRL_FORCE_SPLITS", 0);
     if (forced > 0) return std::max(1, std::min(forced, std::max(1, nq)));
     if (tiles >= 3 * kNumCU) return 1;
     const long long cap = std::min<long long>(8, ceil_div(6 * kNumCU, std::max<long long>(tiles, 1)));
@@ -1190,7 +1168,7 @@ static int pick_splits(long long tiles, int nq) {
 enum ConvPass { PASS_FWD, PASS_DGRAD, PASS_WGRAD };
 static int conv_precision_mode() {
     int prec = g_conv_precision.load();
-    if (prec < 0) prec = env_int("DSRL_CONV_PRECISION", 4);
+    if (prec < 0) prec = knob("DSRL_CONV_PRECISION", 4);
     return prec < 0 ? 0 : (prec > 5 ? 5 : prec);
 }
 static bool conv_f16() { return conv_precision_mode() >= 4; }
@@ -1221,10 +1199,6 @@ int launch_zero_fill(void* p, size_t bytes, hipStream_t st) {
     if ((uintptr_t)p % 16) {                // unaligned head: byte by byte up to the boundary is not worth a kernel of its own - callers pass 16-byte aligned buffers
         set_error("zero_fill: pointer not 16-byte aligned");
         return DSRL_E_BADARG;
-    }
-    if (env_int("DSRL_ZERO_FILL_MEMSET", 0)) {      // diagnosis only (tools/graph_memset_edges.py): the memset node this function replaced in round 3
-        if (hipMemsetAsync(p, 0, bytes, st) != hipSuccess) { set_error("hipMemsetAsync failed"); return DSRL_E_LAUNCH; }
-        return DSRL_OK;
     }
     const long long n16 = (long long)(bytes / 16);
     const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(ceil_div(n16, 256 * 8), 2048));
@@ -1265,7 +1239,7 @@ static int launch_igemm(const ConvArgs& a_in, TileCfg cfg, hipStream_t st) {
     ConvArgs a = a_in;
     a.mtiles = (int)ceil_div(a.M, bm); a.ntiles = (int)ceil_div(a.K, bn);
     make_magic(a.Ho * a.Wo, a.mHW, a.sHW); make_magic(a.Wo, a.mW, a.sW); make_magic(a.ntiles, a.mNT, a.sNT);
-    a.xcd_remap = env_int("DSRL_XCD_REMAP", 1);
+    a.xcd_remap = knob("DSRL_XCD_REMAP", 1);
     // the fast BatchNorm-sum epilogue of the one-group builds parks the block's fp32 tile in LDS (conv_split_kernel.h): fp16 arithmetics, tiles up to 256x128
     if (a.bn_fast && !(DGRAD && conv_f16() && (size_t)bm * bn * 4 <= 128 * 1024)) a.bn_fast = 0;
     if (a.planes) return launch_planes_igemm(a, (int)cfg, DGRAD, st);          // both operands as fp16 planes, staged by LDS-DMA (conv_planes.hip)
@@ -1276,10 +1250,10 @@ static int launch_igemm(const ConvArgs& a_in, TileCfg cfg, hipStream_t st) {
     if (f16 && (a.amax_a == nullptr || a.amax_b == nullptr)) { set_error("conv_igemm_split_kernel<f16x3>: operand magnitudes missing"); return DSRL_E_BADARG; }
     // stride-1 data gradients with pre-split filters run the build without divisibility tests / parity bookkeeping (template STR1; a forward launch
     // passes DGRAD = false in that slot, i.e. the same instantiation as without it)
-    const bool s1 = DGRAD && a.stride == 1 && a.par == 0 && env_int("DSRL_DGRAD_S1", 1);
+    const bool s1 = DGRAD && a.stride == 1 && a.par == 0;
     if (npl) {
         const int kg = a.kg > 1 ? a.kg : 1;
-        const size_t stages = (size_t)2 * (bm + bn) * npl * ((kFullStep && f16) ? 64 : 32);      // two stages per K group: 32-byte rows (a 16-channel half-step), or 64-byte rows (a whole step: fp16 arithmetics)
+        const size_t stages = (size_t)2 * (bm + bn) * npl * (f16 ? 64 : 32);      // two stages per K group: 32-byte rows (a 16-channel half-step), or 64-byte rows (a whole step: fp16 arithmetics)
         if (kg > 1) {
             // K groups (64x64 tiles: 2 or 4 groups, 128x64 / 64x128: 2): block of 256*kg threads, LDS = kg stage pairs or the (kg-1)
             // accumulator sets of the final reduction (all kg of them: every group sums, every group stores a share), whichever is larger (up to 72 KiB)
@@ -1360,26 +1334,14 @@ static int launch_igemm(const ConvArgs& a_in, TileCfg cfg, hipStream_t st) {
         return launch_status(f16 ? (npl == 1 ? "conv_igemm_split_kernel<f16x1>" : "conv_igemm_split_kernel<f16x3>") : (npl == 2 ? "conv_igemm_split_kernel<bf16x3>" : "conv_igemm_split_kernel<bf16x6>"));
     }
     const size_t lds1 = (size_t)(bm + bn) * LDS_LD * sizeof(float);
-    const bool dbuf = env_int("DSRL_IGEMM_DBUF", 0) != 0;     // measured: no gain from the two-stage LDS variant; kept selectable
 #define DSRL_LAUNCH_IGEMM(a_, b_, c_, d_) hipLaunchKernelGGL((conv_igemm_f32_kernel<a_, b_, c_, d_, DGRAD>), grid, dim3(256), lds1, st, a)
-#define DSRL_LAUNCH_IGEMM_DB(a_, b_, c_, d_) hipLaunchKernelGGL((conv_igemm_f32_kernel<a_, b_, c_, d_, DGRAD, 2, true>), grid, dim3(256), 2 * lds1, st, a)
     // 1024+ tiles of 128x128: the <=128-register build keeps 4 blocks per CU resident (one round instead of 1.33)
-    if (cfg == T128x128 && !dbuf && env_int("DSRL_IGEMM_OCC4", nblocks > 3 * kNumCU ? 1 : 0)) {
+    if (cfg == T128x128 && nblocks > 3 * kNumCU) {
         hipLaunchKernelGGL((conv_igemm_f32_kernel<2, 2, 2, 2, DGRAD, 4>), grid, dim3(256), lds1, st, a);
-    } else if (dbuf) {
-        static bool attr_set[2] = {false, false};
-        if (2 * lds1 > 65536 && !attr_set[DGRAD ? 1 : 0]) {       // > 64 KiB of dynamic LDS needs the opt-in attribute (256x64 / 128x128 tiles)
-            hipFuncSetAttribute((const void*)conv_igemm_f32_kernel<2, 2, 2, 2, DGRAD, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
-            hipFuncSetAttribute((const void*)conv_igemm_f32_kernel<2, 2, 4, 1, DGRAD, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
-            hipFuncSetAttribute((const void*)conv_igemm_f32_kernel<2, 1, 4, 1, DGRAD, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 98304);
-            attr_set[DGRAD ? 1 : 0] = true;
-        }
-        DSRL_CFG_SWITCH(cfg, DSRL_LAUNCH_IGEMM_DB)
     } else {
         DSRL_CFG_SWITCH(cfg, DSRL_LAUNCH_IGEMM)
     }
 #undef DSRL_LAUNCH_IGEMM
-#undef DSRL_LAUNCH_IGEMM_DB
     return launch_status("conv_igemm_f32_kernel");
 }
 
@@ -1392,7 +1354,7 @@ static int check_conv(const void* p0, const void* p1, const void* p2, int N, int
     return 0;
 }
 
-static int wgrad_no_ident() { static const int v = [] { const char* e = getenv("DSRL_WGRAD_IDENT"); return (e && atoi(e) == 0) ? 1 : 0; }(); return v; }
+static int wgrad_no_ident() { static const int v = knob("DSRL_WGRAD_IDENT", 1) == 0; return v; }       // read once: WgradArgs::no_ident of a grouped table must not change between plan and launch
 static long long span_bytes(long long pixels, int ld, int c) { return ((pixels - 1) * ld + c) * 4ll; }
 #define DSRL_REQUIRE_31(bytes, what) DSRL_REQUIRE((bytes) > 0 && (bytes) < (1ll << 31), DSRL_E_UNSUPPORTED, what ": tensor of %lld bytes exceeds the 2 GiB buffer-descriptor range", (long long)(bytes))
 struct FwdPlan { int Ho, Wo, M, cchunks, splits, kg; TileCfg cfg; size_t ws; bool coop; };
@@ -1400,7 +1362,7 @@ struct FwdPlan { int Ho, Wo, M, cchunks, splits, kg; TileCfg cfg; size_t ws; boo
 // per CU a block runs 2 or 4 groups of 4 waves over interleaved chunks and sums them in LDS - no slabs, no reduce launch.
 static int pick_kg(long long tiles, int nq, TileCfg cfg, int npl) {
     if (!npl) return 1;
-    const int forced = env_int("DSRL_FORCE_KG", 0);
+    const int forced = knob("DSRL_FORCE_KG", 0);
     const int maxkg = cfg == T64x64 ? 4 : ((cfg == T128x64 || cfg == T64x128 || (cfg == T128x128 && conv_precision_mode() >= 4)) ? 2 : 1);
     if (forced > 0) return std::min(forced >= 4 ? 4 : (forced >= 2 ? 2 : 1), maxkg);
     if (tiles * 2 > 3 * kNumCU) return 1;
@@ -1418,28 +1380,19 @@ static int pick_kg(long long tiles, int nq, TileCfg cfg, int npl) {
 //      CU the forward pass takes 256x256 tiles (cat / SISR 3x3 convs: -8..-17 %), dgrad 256x128 at >= 2 blocks per CU (-4..-7 %; its
 //      256x256 build spills); the dilated ASPP forward convs (M = 4096, 576 chunks) take 256x128 with split-K 8 (-22 %).
 static void pick_split_plan(long long M, int N, int nq, bool dgrad, TileCfg& cfg, int& splits, int& kg) {
-    const bool forced = env_int("DSRL_FORCE_CFG", -1) >= 0 || env_int("DSRL_FORCE_SPLITS", 0) > 0 || env_int("DSRL_FORCE_KG", 0) > 0;
-    if (forced || N <= 32 || !env_int("DSRL_SPLIT_PLAN", 1)) return;
-    if (conv_precision_mode() >= 4 && env_int("DSRL_BIG_TILES", 1) && N >= 192 && nq >= 32) {                                         // d)
+    const bool forced = knob("DSRL_FORCE_CFG", -1) >= 0 || knob("DSRL_FORCE_SPLITS", 0) > 0 || knob("DSRL_FORCE_KG", 0) > 0;
+    if (forced || N <= 32) return;
+    if (conv_precision_mode() >= 4 && N >= 192 && nq >= 32) {                                         // d)
         // 256x256 forward: the LDS-DMA kernel's tile (251 registers, no scratch).  The register-staged two-plane build of that tile spills, so with planes
         // switched off altogether (DSRL_PLANES=0, set by functional when DSRL_PLANES_MODE=off) the f16x3 forward takes 256x128 like dgrad; f16x1 (one plane) fits
-        const bool t256 = conv_precision_mode() == 5 || env_int("DSRL_PLANES", 1) != 0;
+        const bool t256 = conv_precision_mode() == 5 || knob("DSRL_PLANES", 1) != 0;
         if (!dgrad && t256 && cfg_blocks(T256x256, M, N) >= kNumCU) { cfg = T256x256; splits = 1; kg = 1; return; }
         if (!dgrad && !t256 && cfg_blocks(T256x128, M, N) >= 2 * kNumCU) { cfg = T256x128; splits = 1; kg = 1; return; }
         if (dgrad && cfg_blocks(T256x128, M, N) >= 2 * kNumCU) { cfg = T256x128; splits = 1; kg = 1; return; }
         if (!dgrad && nq >= 256 && cfg_blocks(T256x128, M, N) * 8 >= kNumCU && cfg_blocks(T128x128, M, N) < kNumCU) { cfg = T256x128; splits = 8; kg = 1; return; }
     }
-    // e) round 5 (conv_sk.hip, profiles/round5_sk_tiles_ab.txt): exactly half a chip of 128x128 tiles on a long K loop (layer4: M = 4096, N = 512, the 3x3
-    //    conv and the 2048 -> 512 1x1 and its mirror-image dgrad) - two K groups per tile and split-K 2 across workgroups, reduced inside the launch:
-    //    -5 .. -10 % against 128x128 tiles with split-K slabs IN ISOLATION.  In the step the rule came out even when it was introduced and 0.4 % behind
-    //    at the end of the round (once bn3's sums from the next block's dgrad and the decoder links were in: profiles/round5_ab.txt), and the layer3 shapes
-    //    (64 tiles, split-K 4) lose 3 %: the rule is OFF by default.  DSRL_SK_AUTO=1: the layer4 shapes, =2: also the 64-tile shapes (N = 256, nq >= 64).
-    if (conv_precision_mode() >= 4 && N % 128 == 0 && M % 128 == 0) {
-        const int sk = env_int("DSRL_SK_AUTO", 0);
-        const long long t = cfg_blocks(T128x128, M, N);
-        if (sk >= 1 && t == kNumCU / 2 && nq >= 64) { cfg = T128x128; splits = 2; kg = 2; return; }
-        if (sk >= 2 && t == kNumCU / 4 && nq >= 64) { cfg = T128x128; splits = 4; kg = 2; return; }
-    }
+    // (No rule for conv_sk.hip's tiles - 128x128, two K groups, split-K reduced inside the launch: -5 .. -10 % in isolation on the layer4 shapes, but
+    //  0.4 % (layer4) and 3 % (layer3) behind in the step, profiles/round5_ab.txt.  DSRL_FORCE_CFG=0 DSRL_FORCE_KG=2 DSRL_FORCE_SPLITS=n reaches them.)
     const int r = N % 128;
     const bool narrow = N <= 64 || (r > 0 && r <= 64);
     const TileCfg wide[2] = {T128x128, T128x64}, nar[2] = {T256x64, T128x64};
@@ -1461,14 +1414,14 @@ static FwdPlan plan_fwd(int N, int Hin, int Win, int Cin, int Kout, int R, int S
     const long long tiles = ceil_div(p.M, bm) * ceil_div(Kout, bn);
     const int nq = R * S * p.cchunks;
     p.kg = pick_kg(tiles, nq, p.cfg, npl);
-    p.splits = (p.kg > 1 && env_int("DSRL_FORCE_SPLITS", 0) <= 0) ? 1 : pick_splits(tiles, nq);
+    p.splits = (p.kg > 1 && knob("DSRL_FORCE_SPLITS", 0) <= 0) ? 1 : pick_splits(tiles, nq);
     if (npl) pick_split_plan(p.M, Kout, nq, dgrad, p.cfg, p.splits, p.kg);
     // split-K across workgroups with the reduction inside the launch (conv_sk.hip): 128x128 tiles with two K groups, at most kCoopMaxTiles tiles
     // (one arrival ticket per tile in the activation's amax record), partial tiles within one buffer descriptor
     cfg_dims(p.cfg, bm, bn);
     const long long t2 = ceil_div(p.M, bm) * ceil_div(Kout, bn);
-    p.coop = p.splits > 1 && (p.kg == 2 || (p.kg == 1 && env_int("DSRL_SK_COOP1", 1))) && p.cfg == T128x128 && conv_precision_mode() >= 4 && t2 <= kCoopMaxTiles &&
-             (long long)p.splits * t2 * bm * bn * 4 < (1ll << 31) && env_int("DSRL_SK_COOP", 1);
+    p.coop = p.splits > 1 && (p.kg == 2 || (p.kg == 1 && knob("DSRL_SK_COOP1", 1))) && p.cfg == T128x128 && conv_precision_mode() >= 4 && t2 <= kCoopMaxTiles &&
+             (long long)p.splits * t2 * bm * bn * 4 < (1ll << 31) && knob("DSRL_SK_COOP", 1);
     p.ws = p.splits > 1 ? (p.coop ? (size_t)p.splits * t2 * bm * bn * sizeof(float) : (size_t)p.splits * p.M * Kout * sizeof(float)) : 0;
     return p;
 }
@@ -1508,7 +1461,7 @@ extern "C" size_t dsrl_conv2d_fwd_workspace_bytes(int N, int H, int W, int C, in
 // split-K slabs, or more than 256 row blocks)
 constexpr int kMaxStatsParts = 4096;
 static int fwd_stats_parts(const FwdPlan& p, int npl, bool dgrad = false) {
-    if (npl && p.splits > 1 && !p.coop && !dgrad && env_int("DSRL_SPLITK_STATS", 1))      // forward split-K: the slab reduce leaves partials of 64 rows each
+    if (npl && p.splits > 1 && !p.coop && !dgrad)      // forward split-K: the slab reduce leaves partials of 64 rows each
         return ((p.ws / ((size_t)p.splits * p.M * sizeof(float))) % 32 == 0 && ceil_div(p.M, 64) <= 256) ? (int)ceil_div(p.M, 64) : 0;
     if (!npl || (p.splits > 1 && !p.coop)) return 0;
     int bm, bn; cfg_dims(p.cfg, bm, bn);
@@ -1526,7 +1479,7 @@ extern "C" int dsrl_conv2d_fwd_stats_parts(int N, int H, int W, int C, int K, in
 
 // can a launch whose reduction runs over C channels of a [P][ld] activation take its operands as fp16 planes?  (DSRL_PLANES=0: never)
 static bool planes_usable(int C, int ld, const void* a_planes, const void* b_planes) {
-    return C % 8 == 0 && ld % 8 == 0 && ((uintptr_t)a_planes % 16) == 0 && ((uintptr_t)b_planes % 16) == 0 && env_int("DSRL_PLANES", 1) != 0;
+    return C % 8 == 0 && ld % 8 == 0 && ((uintptr_t)a_planes % 16) == 0 && ((uintptr_t)b_planes % 16) == 0 && knob("DSRL_PLANES", 1) != 0;
 }
 static int fwd_impl(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy,
                     int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil,
@@ -1552,7 +1505,7 @@ static int fwd_impl(const float* x, int ldx, const float* w, const float* bias, 
         OperandAmax am{x_amax, w_amax};
         if (int e = resolve_amax(am, x, ldx, (long long)N * H * W, C, w, C, (long long)K * R * S, C, ws, ws_bytes, p.ws, st, "conv2d_fwd")) return e;
         a.amax_a = am.a; a.amax_b = am.b;
-        if (w_split != nullptr && w_amax != nullptr && env_int("DSRL_PRESPLIT", 1)) {      // the split form carries the scale of ITS record
+        if (w_split != nullptr && w_amax != nullptr) {      // the split form carries the scale of ITS record
             DSRL_REQUIRE(((uintptr_t)w_split % 16) == 0, DSRL_E_BADARG, "conv2d_fwd: unaligned pre-split filter");
             a.w = (const float*)w_split; a.w_split = 1;
         }
@@ -1696,7 +1649,7 @@ static int dgrad_impl(const float* dy, int lddy, const float* w, const float* wt
     float* slabs = (float*)((char*)ws + wtb);
     const bool use_planes = conv_f16() && dy_planes != nullptr && wt_planes != nullptr && dy_amax != nullptr && w_amax != nullptr && stride == 1 && K % 8 == 0 &&
                             planes_usable(K, lddy, dy_planes, wt_planes) && planes_cfg_supported((int)p.cfg, p.kg) && !(p.coop && p.splits > 1);    // see fwd_impl
-    const bool use_split = conv_f16() && wt_split != nullptr && w_amax != nullptr && env_int("DSRL_PRESPLIT", 1);
+    const bool use_split = conv_f16() && wt_split != nullptr && w_amax != nullptr;
     if (wt == nullptr && use_planes) wt = (const float*)wt_planes;       // replaced below; no fp32 transpose is built for it
     if (wt == nullptr && use_split) wt = (const float*)wt_split;         // replaced below; no fp32 transpose is built for it
     if (wt == nullptr) {
@@ -1717,7 +1670,7 @@ static int dgrad_impl(const float* dy, int lddy, const float* w, const float* wt
         OperandAmax am{dy_amax, w_amax};
         if (int e = resolve_amax(am, dy, lddy, (long long)N * Ho * Wo, Kp, w, C, (long long)K * R * S, C, ws, ws_bytes, wtb + p.ws, st, "conv2d_dgrad")) return e;
         a.amax_a = am.a; a.amax_b = am.b;
-        if (wt_split != nullptr && w_amax != nullptr && env_int("DSRL_PRESPLIT", 1)) {
+        if (wt_split != nullptr && w_amax != nullptr) {
             DSRL_REQUIRE(((uintptr_t)wt_split % 16) == 0, DSRL_E_BADARG, "conv2d_dgrad: unaligned pre-split filter");
             a.w = (const float*)wt_split; a.w_split = 1;
         }
@@ -1745,7 +1698,7 @@ static int dgrad_impl(const float* dy, int lddy, const float* w, const float* wt
         a.y_bytes = (unsigned)span_bytes(p.M, lddx, C);
     }
     a.y = dx; a.ldy = lddx; a.bias = nullptr; a.accumulate = accumulate;
-    if (stride > 1 && conv_planes(PASS_DGRAD) && H % stride == 0 && W % stride == 0 && (W / stride) % 32 == 0 && env_int("DSRL_DGRAD_PARITY", 1)) {
+    if (stride > 1 && conv_planes(PASS_DGRAD) && H % stride == 0 && W % stride == 0 && (W / stride) % 32 == 0 && knob("DSRL_DGRAD_PARITY", 1)) {
         // rows ordered by parity class (ConvArgs::par): a tile then only runs the taps that divide evenly for its class
         int bm, bn_; cfg_dims(p.cfg, bm, bn_);
         const long long Mc = (long long)N * (H / stride) * (W / stride);
@@ -1755,7 +1708,7 @@ static int dgrad_impl(const float* dy, int lddy, const float* w, const float* wt
         a.bn_x = bn->x; a.bn_y = bn->y; a.bn_mean = bn->mean; a.bn_invstd = bn->invstd; a.bstats = bn->stats; a.bn_ldx = bn->ldx; a.bn_ldy = bn->ldy; a.bn_relu = bn->relu;
         a.bn_gscale = bn->gscale;
         a.bn_fast = a.par == 0 && C % 4 == 0 && bn->ldx % 4 == 0 && (!bn->relu || bn->ldy % 4 == 0) && ((uintptr_t)bn->x % 16) == 0 && (!bn->relu || ((uintptr_t)bn->y % 16) == 0) &&
-                    ((uintptr_t)bn->mean % 16) == 0 && ((uintptr_t)bn->invstd % 16) == 0 && ((uintptr_t)bn->stats % 16) == 0 && env_int("DSRL_BNSTATS_FAST", 1);
+                    ((uintptr_t)bn->mean % 16) == 0 && ((uintptr_t)bn->invstd % 16) == 0 && ((uintptr_t)bn->stats % 16) == 0;
     }
     return launch_igemm<true>(a, p.cfg, st);
 }
@@ -1838,9 +1791,9 @@ namespace dsrl {
 struct WgPlan { int Ho, Wo; long long P; TileCfg cfg; int bm, bn, ktiles, ctiles, psplits; TapList tl; size_t ws; bool w3; };
 // pixel ranges of an all-taps 3x3 launch (conv_wgrad3.hip; one 8-wave block per CU): as many as fit two rounds of blocks, at least 8 chunks each
 static int w3_psplits(long long tiles, long long chunks) {
-    const int forced = env_int("DSRL_FORCE_PSPLITS", 0);
+    const int forced = knob("DSRL_FORCE_PSPLITS", 0);
     if (forced > 0) return (int)std::max<long long>(1, std::min<long long>(forced, chunks));
-    long long sp = std::max<long long>(1, env_int("DSRL_WGRAD3_TARGET_BLOCKS", 2 * kNumCU) / std::max<long long>(tiles, 1));     // rounded down: the blocks fit two rounds of one per CU
+    long long sp = std::max<long long>(1, 2 * kNumCU / std::max<long long>(tiles, 1));     // rounded down: the blocks fit two rounds of one per CU
     sp = std::min(sp, std::max<long long>(1, chunks / 8));
     return (int)std::max<long long>(1, std::min<long long>(sp, 128));
 }
@@ -1910,7 +1863,7 @@ static int wgrad_impl(const float* x, int ldx, const float* dy, int lddy, float*
     if (p.w3) {
         a.psplits = p.psplits; a.kg = 1;
         a.dw = p.psplits > 1 ? (float*)ws : dw;
-        a.kctiles = p.ktiles * p.ctiles; a.xcd_remap = env_int("DSRL_XCD_REMAP", 1);
+        a.kctiles = p.ktiles * p.ctiles; a.xcd_remap = knob("DSRL_XCD_REMAP", 1);
         a.nblocks = a.kctiles * a.psplits;
         make_magic(a.Ho * a.Wo, a.mHW, a.sHW);
         make_magic(a.Wo, a.mW, a.sW);
@@ -1928,10 +1881,10 @@ static int wgrad_impl(const float* x, int ldx, const float* dy, int lddy, float*
     // pixel groups (split kernels): two groups of 4 waves share a block and half of the planned slabs remain.  Measured
     // (tools/wgrad_kg.py): 1x1 convs gain 5-20 %, 3x3 convs lose (each of their taps already has its own blocks), four groups always lose.
     int psplits = p.psplits, kg = 1;
-    if (conv_planes(PASS_WGRAD) && env_int("DSRL_WGRAD_KG", 1)) {
+    if (conv_planes(PASS_WGRAD)) {
         const int npl = conv_planes(PASS_WGRAD);
         const int maxkg = (p.cfg == T64x64 || p.cfg == T128x64 || p.cfg == T64x128 || p.cfg == T128x128) ? 2 : 1;
-        const int forced = env_int("DSRL_FORCE_WGRAD_KG", 0);
+        const int forced = knob("DSRL_FORCE_WGRAD_KG", 0);
         kg = forced > 0 ? std::min(forced, maxkg) : ((RS == 1 && psplits >= 4) ? std::min(2, maxkg) : 1);
         if (kg == 3) kg = 2;
         while (kg > 1 && (size_t)kg * 2 * npl * 16 * ((p.bm * 2 + 64) + (p.bn * 2 + 64)) > 144 * 1024) kg /= 2;      // LDS: kg stage pairs
@@ -1939,7 +1892,7 @@ static int wgrad_impl(const float* x, int ldx, const float* dy, int lddy, float*
     }
     a.psplits = psplits; a.kg = kg;
     a.dw = psplits > 1 ? (float*)ws : dw;
-    a.kctiles = p.ktiles * p.ctiles; a.xcd_remap = env_int("DSRL_XCD_REMAP", 1);
+    a.kctiles = p.ktiles * p.ctiles; a.xcd_remap = knob("DSRL_XCD_REMAP", 1);
     dim3 grid((unsigned)(a.kctiles * p.tl.n * psplits));
     ProfScope prof(prof_family(PASS_WGRAD), 2.0 * (double)dsrl_conv2d_inbounds_macs(N, H, W, C, K, R, S, stride, pad, dil), 4.0 * ((double)N * H * W * C + (double)K * R * S * C + (double)N * out_size(H, R, stride, pad, dil) * out_size(W, S, stride, pad, dil) * K), st);
     prof.shape("wgrad", N, H, W, C, K, R, stride, pad, dil);
@@ -2051,27 +2004,20 @@ struct GroupHeader {
 static size_t group_table_bytes(int n) {
     return align_up(sizeof(GroupHeader), 256) + align_up((size_t)n * sizeof(WgradArgs), 256) + 2 * align_up((size_t)(n + 1) * sizeof(int), 256);
 }
-static int group_target_px() { return std::max(256, env_int("DSRL_WGRAD_GROUP_PX", 4096)); }
+static int group_target_px() { return std::max(256, knob("DSRL_WGRAD_GROUP_PX", 4096)); }
 struct GroupItem { WgradArgs a; TileCfg cfg; int bm, bn; double cost, flops, bytes; size_t slab_bytes; };
-// Pixel ranges of one problem. Default: one range per ~DSRL_WGRAD_GROUP_PX output pixels. A problem that this leaves with fewer than 8 ranges
-// spreads the blocks of a range (taps x tiles) over all 8 XCDs, and every XCD's L2 then fetches the whole of x and dy; with 8 ranges each XCD
-// owns one and fetches an eighth. DSRL_WGRAD_XCD_SPLIT=1 takes 8 ranges where the slab traffic this adds (8 slabs written and read back)
-// is smaller than the operand re-fetches it removes.
-static int group_psplits(long long P, int K, int R, int S, int C, long long x_pixels, int w3_px = 0) {
+// Pixel ranges of one problem: one range per ~DSRL_WGRAD_GROUP_PX output pixels.
+static int group_psplits(long long P, int w3_px = 0) {
     const long long chunks = ceil_div(P, 32);
     if (w3_px > 0) {       // a block takes all nine taps of its pixel range: 9 x the work per pixel; pixels per block chosen for the whole launch (w3_group_px)
-        const int forced3 = env_int("DSRL_FORCE_PSPLITS", 0), px = w3_px;
+        const int forced3 = knob("DSRL_FORCE_PSPLITS", 0), px = w3_px;
         long long sp3 = forced3 > 0 ? forced3 : (P + px / 2) / px;
         sp3 = std::max<long long>(1, std::min<long long>(sp3, std::max<long long>(1, chunks / 8)));
         return (int)std::min<long long>(sp3, 256);
     }
-    const int forced = env_int("DSRL_FORCE_PSPLITS", 0);
+    const int forced = knob("DSRL_FORCE_PSPLITS", 0);
     long long sp = forced > 0 ? forced : (P + group_target_px() / 2) / group_target_px();
     sp = std::max<long long>(1, std::min<long long>(sp, std::max<long long>(1, chunks / 4)));
-    if (forced <= 0 && sp < 8 && chunks >= 64 && env_int("DSRL_WGRAD_XCD_SPLIT", 0)) {
-        const double operands = 4.0 * ((double)x_pixels * C + (double)P * K), slabs = 4.0 * (double)K * R * S * C;
-        if (16.0 * slabs < 7.0 * operands) sp = 8;
-    }
     return (int)std::min<long long>(sp, 256);
 }
 // Pixels per block of the all-taps launches.  Their blocks run one per CU and are dealt in id order to whichever CU is free, so with equal blocks a
@@ -2079,7 +2025,7 @@ static int group_psplits(long long P, int K, int R, int S, int C, long long x_pi
 // 1216: five, 1.07 ms).  Measured over the step's 34 problems (tools/sweep_w3_px.sh; launch + slab reduce, ms): 1536 px 1.59, 2048 1.52, 3072 1.58,
 // 4096 1.61, 8192 1.56, 16384 1.56 - short blocks balance best and their extra slab traffic costs less than the rounding of long ones.  A list-schedule
 // simulation per problem list (block time = chunks + constant, 256 or 240 CUs, slab bytes at 4 TB/s) did not predict the measured order and was dropped.
-static int w3_group_px(const dsrl_wgrad_problem*, int, int) { return std::max(256, env_int("DSRL_WGRAD3_PX", 2048)); }
+static int w3_group_px(const dsrl_wgrad_problem*, int, int) { return std::max(256, knob("DSRL_WGRAD3_PX", 2048)); }
 static int group_item(const dsrl_wgrad_problem& q, int npl, GroupItem& it, const int* w3_px) {
     const int N = q.N, H = q.H, W = q.W, C = q.C, K = q.K, R = q.R, S = q.S, stride = q.stride, pad = q.pad, dil = q.dil;
     if (int e = check_conv(q.x, q.dy, q.dw, N, H, W, C, K, R, S, stride, pad, dil)) return e;
@@ -2095,8 +2041,8 @@ static int group_item(const dsrl_wgrad_problem& q, int npl, GroupItem& it, const
     a.x_bytes = (unsigned)xb; a.dy_bytes = (unsigned)db; a.no_ident = wgrad_no_ident();
     a.ntaps = p.tl.n;
     for (int i = 0; i < p.tl.n; ++i) a.taps[i] = p.tl.taps[i];
-    a.psplits = group_psplits(p.P, K, R, S, C, (long long)N * H * W, p.w3 ? w3_px[dil - 1] : 0);
-    a.kg = 1; a.kctiles = p.ktiles * p.ctiles; a.xcd_remap = env_int("DSRL_XCD_REMAP", 1);
+    a.psplits = group_psplits(p.P, p.w3 ? w3_px[dil - 1] : 0);
+    a.kg = 1; a.kctiles = p.ktiles * p.ctiles; a.xcd_remap = knob("DSRL_XCD_REMAP", 1);
     a.nblocks = p.w3 ? a.kctiles * a.psplits : a.kctiles * a.ntaps * a.psplits;
     a.dw_final = q.dw; a.dw = q.dw;
     a.rblocks = a.psplits > 1 ? (int)ceil_div((long long)K * a.ntaps * (C / 4), 1024) : 0;
@@ -2127,7 +2073,7 @@ extern "C" size_t dsrl_conv2d_wgrad_group_workspace_bytes(const dsrl_wgrad_probl
         if (out_size(q.H, q.R, q.stride, q.pad, q.dil) <= 0 || out_size(q.W, q.S, q.stride, q.pad, q.dil) <= 0) continue;
         const long long P = (long long)q.N * out_size(q.H, q.R, q.stride, q.pad, q.dil) * out_size(q.W, q.S, q.stride, q.pad, q.dil);
         const bool w3 = out_size(q.H, q.R, q.stride, q.pad, q.dil) == q.H && plan_wgrad(q.N, q.H, q.W, q.C, q.K, q.R, q.S, q.stride, q.pad, q.dil).w3;
-        const int sp = dsrl::group_psplits(P, q.K, q.R, q.S, q.C, (long long)q.N * q.H * q.W, w3 ? w3_px[q.dil - 1] : 0);
+        const int sp = dsrl::group_psplits(P, w3 ? w3_px[q.dil - 1] : 0);
         if (sp > 1) total += align_up((size_t)sp * q.K * q.R * q.S * q.C * sizeof(float), 256);
     }
     return total;
@@ -2315,7 +2261,7 @@ extern "C" int dsrl_conv2d_rowfold_wgrad(const float* x, int ldx, const float* d
     a.ntaps = R;
     for (int r = 0; r < R; ++r) a.taps[r] = r;
     a.dw = p.psplits > 1 ? (float*)ws : dw;
-    a.kctiles = p.ktiles * p.ctiles; a.xcd_remap = env_int("DSRL_XCD_REMAP", 1);
+    a.kctiles = p.ktiles * p.ctiles; a.xcd_remap = knob("DSRL_XCD_REMAP", 1);
     dim3 grid((unsigned)(a.kctiles * R * p.psplits));
     if (conv_f16()) {
         OperandAmax am{nullptr, nullptr};
@@ -2360,7 +2306,7 @@ extern "C" int dsrl_prof_read(int family, int64_t* launches, double* total_ms, d
         float t = 0.f;
         hipEventElapsedTime(&t, r.a, r.b);
         ms += t; fl += r.flops; ++n;
-        if (const char* dump = getenv("DSRL_PROF_DUMP")) {          // diagnosis (tools/per_launch.py): one line per bracketed launch
+        if (const char* dump = knob_str("DSRL_PROF_DUMP")) {          // diagnosis (tools/per_launch.py): one line per bracketed launch
             if (FILE* f = fopen(dump, "a")) { fprintf(f, "%d\t%.6f\t%.0f\t%.0f\t%s\n", r.family, (double)t, r.flops, r.bytes, r.tag); fclose(f); }
         }
     }

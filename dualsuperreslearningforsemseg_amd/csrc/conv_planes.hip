@@ -49,8 +49,9 @@ template <> struct PlaneMfma<1> {
 
 // MR x NR 32x32 MFMA tiles per wave, WGM x WGN waves per K group, KG K groups per block (interleaved chunks, accumulators summed through LDS in the
 // order g = 0 .. KG-1), NPL planes per operand (2 = f16x3, 1 = f16x1), R ring slots per group.  DGRAD: stride-1 data gradient (a.x = dy planes,
-// a.w = planes of the transposed filter [C][R][S][K]); strided data gradients stay on conv_igemm_split_kernel.
-template <int MR, int NR, int WGM, int WGN, int KG, int NPL, bool DGRAD, int R, int DBG = 0>
+// a.w = planes of the transposed filter [C][R][S][K]); strided data gradients stay on conv_igemm_split_kernel.  The last parameter is always 0 (it
+// selected timing-only ablations, tools/patches/planes_ablation.diff) and stays because it is part of the symbol names the profiles record.
+template <int MR, int NR, int WGM, int WGN, int KG, int NPL, bool DGRAD, int R, int = 0>
 __global__ __launch_bounds__(64 * WGM * WGN * KG, (64 * WGM * WGN * KG >= 512) ? 1 : 2)
 void conv_planes_kernel(const ConvArgs a) {
     constexpr int NW = WGM * WGN, NT = 64 * NW;
@@ -64,7 +65,6 @@ void conv_planes_kernel(const ConvArgs a) {
     constexpr int SLOT = (BM + BN) * NPL * ROWB;
     static_assert(R >= 2, "ring");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (DBG == 4) return;                                   // fixed-cost dissection: the launch alone
     const unsigned am_a = amax_fetch(a.amax_a), am_b = amax_fetch(a.amax_b);      // consumed in the epilogue (the planes already carry the scales)
     const int grp = KG > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x / NT)) : 0;
     char* const ring = smem + grp * R * SLOT;
@@ -221,7 +221,7 @@ void conv_planes_kernel(const ConvArgs a) {
     constexpr bool ALLFRAGS = MR * NR <= 2;                        // both sub-steps' fragments fit in registers
     auto compute = [&](int slot, int refill) {
         const char* cur = ring + slot * SLOT;
-        if (DBG != 2 && DBG != 3 && DBG != 6) prepare(refill);
+        prepare(refill);
         f16x8 fa[2][MR][NPL], fb[2][NR][NPL];
         auto rd = [&](int sub) {
             // the order the MFMAs need them: last plane of the filter fragments, first plane of the pixel fragments, then the rest
@@ -236,11 +236,8 @@ void conv_planes_kernel(const ConvArgs a) {
                 for (int j = 0; j < NR; ++j) fb[sub][j][0] = *reinterpret_cast<const f16x8*>(cur + (NPL * BM + (wn * NR + j) * 32) * ROWB + u_off[sub]);
             }
         };
-        if (DBG != 2 && DBG != 3 && DBG != 6) {
 #pragma unroll
-            for (int idx = 0; idx < PW; ++idx) piece(idx);
-        }
-        if (DBG == 1 || DBG == 3 || DBG == 6) return;
+        for (int idx = 0; idx < PW; ++idx) piece(idx);
         rd(0);
         if (ALLFRAGS) rd(1);
         __builtin_amdgcn_sched_barrier(0);
@@ -260,10 +257,6 @@ void conv_planes_kernel(const ConvArgs a) {
     };
 
     const int nloc = (q1 - q0 + KG - 1) / KG;   // steps: the same for every group (barriers are block-wide)
-    if (DBG == 5) {                             // fixed-cost dissection: launch + prologue (everything it computed stays live)
-        if (nloc == 0x7fffff && a_off[0] + b_off[0] + u_off[0] + u_off[1] + (unsigned)tap + am_a + am_b == 12345u) a.y[0] = 1.f;
-        return;
-    }
     if (q0 < q1) {
 #pragma unroll
         for (int s = 0; s < R - 1; ++s) issue(s);
@@ -279,7 +272,6 @@ void conv_planes_kernel(const ConvArgs a) {
         }
     }
     s_waitcnt_vm<0>();                              // the zero-filling pieces of the steps past the end still write LDS
-    if (DBG == 6) { if (acc[0][0][0] == 12345.678f) a.y[0] = 1.f; return; }      // fixed-cost dissection: launch + prologue + loop skeleton
     const int sh_a = amax_shift_of(am_a), sh_b = amax_shift_of(am_b);
     constexpr int EPG = 16 / KG;                    // accumulator registers per 32x32 tile that one K group stores in the epilogue
     if constexpr (KG > 1) {
@@ -694,57 +686,27 @@ template <bool DGRAD>
 static int launch_planes_t(const ConvArgs& a, int cfg, hipStream_t st) {
     const dim3 grid((unsigned)(a.mtiles * a.ntiles), 1u, (unsigned)(a.kg > 1 ? 1 : a.splits));
     const int kg = a.kg > 1 ? a.kg : 1;
-    static const int r = env_int("DSRL_PLANES_R", 0);       // ring depth override (tools/planes_bench.py), read once
     switch (cfg) {
         case 3:     // 64x64
-#ifdef DSRL_PLANES_ABLATION      // timing-only builds (wrong results): make CXXFLAGS+=-DDSRL_PLANES_ABLATION, profiles/round4_planes_kernel_ab.txt
-            if (const int dbg = env_int("DSRL_PLANES_DBG", 0)) {         // timing-only ablations (wrong results): 1 = no MFMA / fragment reads, 2 = no DMA, 3 = neither
-                if constexpr (!DGRAD) {
-                    constexpr size_t lds = 128 * 1024;
-                    hipFuncSetAttribute((const void*)conv_planes_kernel<1, 1, 2, 2, 4, 2, false, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    hipFuncSetAttribute((const void*)conv_planes_kernel<1, 1, 2, 2, 4, 2, false, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    hipFuncSetAttribute((const void*)conv_planes_kernel<1, 1, 2, 2, 4, 2, false, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    hipFuncSetAttribute((const void*)conv_planes_kernel<1, 1, 2, 2, 4, 2, false, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    hipFuncSetAttribute((const void*)conv_planes_kernel<1, 1, 2, 2, 4, 2, false, 2, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    hipFuncSetAttribute((const void*)conv_planes_kernel<1, 1, 2, 2, 4, 2, false, 2, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                    if (kg == 4 && dbg == 1) hipLaunchKernelGGL((conv_planes_kernel<1, 1, 2, 2, 4, 2, false, 2, 1>), grid, dim3(1024), lds, st, a);
-                    if (kg == 4 && dbg == 2) hipLaunchKernelGGL((conv_planes_kernel<1, 1, 2, 2, 4, 2, false, 2, 2>), grid, dim3(1024), lds, st, a);
-                    if (kg == 4 && dbg == 3) hipLaunchKernelGGL((conv_planes_kernel<1, 1, 2, 2, 4, 2, false, 2, 3>), grid, dim3(1024), lds, st, a);
-                    if (kg == 4 && dbg == 4) hipLaunchKernelGGL((conv_planes_kernel<1, 1, 2, 2, 4, 2, false, 2, 4>), grid, dim3(1024), lds, st, a);
-                    if (kg == 4 && dbg == 5) hipLaunchKernelGGL((conv_planes_kernel<1, 1, 2, 2, 4, 2, false, 2, 5>), grid, dim3(1024), lds, st, a);
-                    if (kg == 4 && dbg == 6) hipLaunchKernelGGL((conv_planes_kernel<1, 1, 2, 2, 4, 2, false, 2, 6>), grid, dim3(1024), lds, st, a);
-                    if (kg == 4) return launch_status("conv_planes_kernel<debug>");
-                    if (kg == 2 && dbg == 1) {          // DMA only, two K groups, ring depth r
-                        hipFuncSetAttribute((const void*)conv_planes_kernel<1, 1, 2, 2, 2, 2, false, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                        hipFuncSetAttribute((const void*)conv_planes_kernel<1, 1, 2, 2, 2, 2, false, 3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                        hipFuncSetAttribute((const void*)conv_planes_kernel<1, 1, 2, 2, 2, 2, false, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                        if (r == 2) hipLaunchKernelGGL((conv_planes_kernel<1, 1, 2, 2, 2, 2, false, 2, 1>), grid, dim3(512), lds, st, a);
-                        else if (r == 3) hipLaunchKernelGGL((conv_planes_kernel<1, 1, 2, 2, 2, 2, false, 3, 1>), grid, dim3(512), lds, st, a);
-                        else hipLaunchKernelGGL((conv_planes_kernel<1, 1, 2, 2, 2, 2, false, 4, 1>), grid, dim3(512), lds, st, a);
-                        return launch_status("conv_planes_kernel<debug>");
-                    }
-                }
-            }
-#endif
             if (kg == 4) DSRL_PLANES_LAUNCH2(1, 1, 2, 2, 4, 2, 4)
-            if (kg == 2) { if (r == 2) DSRL_PLANES_LAUNCH(1, 1, 2, 2, 2, 2) else if (r == 3) DSRL_PLANES_LAUNCH(1, 1, 2, 2, 2, 3) else DSRL_PLANES_LAUNCH(1, 1, 2, 2, 2, 4) }
-            if (r == 2) DSRL_PLANES_LAUNCH(1, 1, 2, 2, 1, 2) else DSRL_PLANES_LAUNCH(1, 1, 2, 2, 1, 3)
+            if (kg == 2) DSRL_PLANES_LAUNCH(1, 1, 2, 2, 2, 4)
+            DSRL_PLANES_LAUNCH(1, 1, 2, 2, 1, 3)
         case 4:     // 128x64
-            if (kg == 2) { if (r == 2) DSRL_PLANES_LAUNCH(2, 1, 2, 2, 2, 2) else DSRL_PLANES_LAUNCH(2, 1, 2, 2, 2, 3) }
-            if (kg == 1) { if (r == 2) DSRL_PLANES_LAUNCH(2, 1, 2, 2, 1, 2) else DSRL_PLANES_LAUNCH(2, 1, 2, 2, 1, 3) }
+            if (kg == 2) DSRL_PLANES_LAUNCH(2, 1, 2, 2, 2, 3)
+            if (kg == 1) DSRL_PLANES_LAUNCH(2, 1, 2, 2, 1, 3)
             break;
         case 5:     // 64x128
-            if (kg == 2) { if (r == 2) DSRL_PLANES_LAUNCH(1, 2, 2, 2, 2, 2) else DSRL_PLANES_LAUNCH(1, 2, 2, 2, 2, 3) }
-            if (kg == 1) { if (r == 2) DSRL_PLANES_LAUNCH(1, 2, 2, 2, 1, 2) else DSRL_PLANES_LAUNCH(1, 2, 2, 2, 1, 3) }
+            if (kg == 2) DSRL_PLANES_LAUNCH(1, 2, 2, 2, 2, 3)
+            if (kg == 1) DSRL_PLANES_LAUNCH(1, 2, 2, 2, 1, 3)
             break;
         case 0:     // 128x128
-            if (kg == 1) { if (r == 3) DSRL_PLANES_LAUNCH(2, 2, 2, 2, 1, 3) else DSRL_PLANES_LAUNCH2(2, 2, 2, 2, 1, 2, 4) }
+            if (kg == 1) DSRL_PLANES_LAUNCH2(2, 2, 2, 2, 1, 2, 4)
             break;
         case 1:     // 256x64
-            if (kg == 1) { if (r == 3) DSRL_PLANES_LAUNCH(2, 2, 4, 1, 1, 3) else DSRL_PLANES_LAUNCH(2, 2, 4, 1, 1, 2) }
+            if (kg == 1) DSRL_PLANES_LAUNCH(2, 2, 4, 1, 1, 2)
             break;
         case 7:     // 256x128, 8 waves
-            if (kg == 1) { if (r == 2) DSRL_PLANES_LAUNCH(2, 2, 4, 2, 1, 2) else DSRL_PLANES_LAUNCH(2, 2, 4, 2, 1, 3) }
+            if (kg == 1) DSRL_PLANES_LAUNCH(2, 2, 4, 2, 1, 3)
             break;
         case 8:     // 256x256, 8 waves
             if (kg == 1) DSRL_PLANES_LAUNCH2(4, 2, 2, 4, 1, 2, 3)

@@ -27,11 +27,7 @@ namespace dsrl {
 // MR x NR tiles of 32x32, but the block stages 0.75x / 0.5x the bytes of 128x128 tiles per multiply-add, through LDS and from L2).
 // Full-step LDS stages (round 4, fp16 arithmetics): a stage holds a whole 32-channel step (64-byte rows) instead of a 16-channel half, so a K group
 // crosses ONE block barrier per step and the fragment reads of the second half overlap the MFMAs of the first (profiles/round4_staging_ablation.txt:
-// with no operand staging at all the half-step loop still took 27.6 of 30.9 us).  Same MFMAs in the same order.  -DDSRL_FULLSTEP=0: half-step stages.
-#ifndef DSRL_FULLSTEP
-#define DSRL_FULLSTEP 1
-#endif
-constexpr bool kFullStep = DSRL_FULLSTEP != 0;
+// with no operand staging at all the half-step loop still took 27.6 of 30.9 us).  Same MFMAs in the same order.
 // COOP (round 5, conv_sk.hip): split-K across workgroups reduced INSIDE the launch.  The `splits` blocks of a tile each run their share of the
 // (tap, chunk) loop; a block publishes its (unscaled) partial tile with write-through stores, drains them, takes a ticket; the last arriver reads the
 // other partials back (sc1 loads: L2-served, never a stale L1 line), adds them in the fixed order z = 0 .. splits-1 - its own contribution from
@@ -57,7 +53,7 @@ void conv_igemm_split_kernel(const ConvArgs a) {
     constexpr int BM = 32 * MR * WGM, BN = 32 * NR * WGN;
     constexpr int A_IT = (BM + RP - 1) / RP, B_IT = (BN + RP - 1) / RP;
     constexpr int NV = A_IT + B_IT;
-    constexpr bool FS = kFullStep && F16;                            // a stage = a whole 32-channel step
+    constexpr bool FS = F16;                            // a stage = a whole 32-channel step
     constexpr int ROWB = FS ? 64 : 32;
     constexpr int STAGE = (BM + BN) * NPL * ROWB;                     // bytes
     extern __shared__ __attribute__((aligned(16))) float smem[];

@@ -270,10 +270,10 @@ template <typename Kern> int w3_attr(Kern k, size_t lds) {
 }  // namespace
 
 bool wgrad3_eligible(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil, int npl, bool f16) {
-    if (!f16 || (npl != 1 && npl != 2) || !env_int("DSRL_WGRAD3", 1)) return false;
+    if (!f16 || (npl != 1 && npl != 2) || !knob("DSRL_WGRAD3", 1)) return false;
     if (R != 3 || S != 3 || stride != 1 || pad != dil || (dil != 1 && dil != 2)) return false;
     if (W % 32 != 0 || H <= dil || N <= 0) return false;                    // Ho == H, Wo == W: a 32-pixel chunk is a piece of one image row; all nine taps see pixels
-    if (C % 4 != 0 || K < env_int("DSRL_WGRAD3_MIN_K", 64) || C < 32) return false;     // the 64-row tile of out channels is full at least once
+    if (C % 4 != 0 || K < 64 || C < 32) return false;     // the 64-row tile of out channels is full at least once
     return (long long)N * H * W < (1ll << 31);
 }
 void wgrad3_tile(int& bm, int& bn) { bm = 32 * kW3WGM; bn = 32 * kW3WGN; }

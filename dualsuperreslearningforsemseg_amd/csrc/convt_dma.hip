@@ -312,8 +312,7 @@ __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(con
 
 // host side: supported = 19 -> 19 channels, W a multiple of the 128-pixel segment, 16-byte aligned tensors
 bool convt_bwd_dma_supported(const void* x, const void* dy, int W, int Cin, int Cout) {
-    const char* v = getenv("DSRL_CONVT_DMA");
-    if (v && atoi(v) == 0) return false;
+    if (!knob("DSRL_CONVT_DMA", 1)) return false;
     return Cin == 19 && Cout == 19 && W % 128 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0;
 }
 int convt_bwd_dma_blocks(long long nseg, int cap) { return (int)std::min<long long>(std::min(cap, kNumCU), nseg); }
@@ -341,8 +340,7 @@ int launch_convt_bwd_dma_ce(const float* x, const float* w, const float* logits,
     ce.ft_shift = -1;
     for (int b = 0; b < 31; ++b) if (ce.ft_s == (1 << b)) ce.ft_shift = b;
     ce.Hf = (2 * H - 1) / ce.ft_s + 1; ce.Wf = (2 * W - 1) / ce.ft_s + 1;
-    const char* tw = getenv("DSRL_CONVT_CE_WAVES");
-    if (tw && atoi(tw) == 8) return launch_dma<true, false>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);      // the transform inside the MFMA waves
+    if (knob("DSRL_CONVT_CE_WAVES", 12) == 8) return launch_dma<true, false>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);      // the transform inside the MFMA waves
     return launch_dma<true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
 }
 

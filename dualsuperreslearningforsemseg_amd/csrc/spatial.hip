@@ -1128,7 +1128,6 @@ using namespace dsrl;
     hipStream_t st = (hipStream_t)stream;                                           \
     if (int e_ = bind_stream_device(st)) return e_;
 
-static int env_int_sp(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 static float ac_scale(int n_in, int n_out) { return n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f; }
 
 extern "C" int dsrl_bilinear_ac_fwd(const float* x, int ldx, float* y, int ldy, int N, int H, int W, int C, int Ho, int Wo, dsrl_stream_t stream) {
@@ -1138,7 +1137,7 @@ extern "C" int dsrl_bilinear_ac_fwd(const float* x, int ldx, float* y, int ldy, 
         return launch_status("bilinear_fwd4_kernel");
     }
     const int Cg = (C + 3) / 4;           // any width: groups of four channels with 4-byte accesses
-    if ((long long)N * Ho * Wo * C < (1ll << 31) && env_int_sp("DSRL_BILINEAR_G4", 1)) {
+    if ((long long)N * Ho * Wo * C < (1ll << 31) && knob("DSRL_BILINEAR_G4", 1)) {
         hipLaunchKernelGGL(bilinear_fwd4_kernel<false>, dim3(flat_grid((long long)N * Ho * Wo * Cg)), dim3(256), 0, st, x, ldx, y, ldy, N, H, W, C, Cg, Ho, Wo, ac_scale(H, Ho), ac_scale(W, Wo));
         return launch_status("bilinear_fwd4_kernel<any width>");
     }
@@ -1160,7 +1159,7 @@ extern "C" int dsrl_bilinear_ac_bwd(const float* dy, int lddy, float* dx, int ld
         hipLaunchKernelGGL(bilinear_bwd_h4_kernel<true>, dim3(flat_grid((long long)N * H * W * (C / 4))), dim3(256), 0, st, (const float*)ws, dx, lddx, N, H, W, C, C / 4, Ho, ac_scale(H, Ho));
         return launch_status("bilinear_bwd_h4_kernel");
     }
-    if ((long long)N * std::max(H, Ho) * std::max(W, Wo) * C < (1ll << 31) && env_int_sp("DSRL_BILINEAR_G4", 1)) {
+    if ((long long)N * std::max(H, Ho) * std::max(W, Wo) * C < (1ll << 31) && knob("DSRL_BILINEAR_G4", 1)) {
         const int Cg = (C + 3) / 4;
         hipLaunchKernelGGL(bilinear_bwd_w4_kernel<false>, dim3(flat_grid((long long)N * Ho * W * Cg)), dim3(256), 0, st, dy, lddy, (float*)ws, N, W, C, Cg, Ho, Wo, ac_scale(W, Wo));
         if (int e = launch_status("bilinear_bwd_w4_kernel<any width>")) return e;
@@ -1217,15 +1216,14 @@ extern "C" int dsrl_maxpool3x3s2_bwd(const uint8_t* argmax, const float* dy, flo
 
 // DSRL_CONVT_MAX_BLOCKS: test knob - fewer blocks than segments, so that small shapes exercise the grid-stride loop of the segment kernels
 // (prefetch registers and LDS buffers reused across segments)
-static int convt_block_cap(int dflt) { const char* v = getenv("DSRL_CONVT_MAX_BLOCKS"); const int n = v ? atoi(v) : 0; return n > 0 ? std::min(n, dflt) : dflt; }
+static int convt_block_cap(int dflt) { const int n = knob("DSRL_CONVT_MAX_BLOCKS", 0); return n > 0 ? std::min(n, dflt) : dflt; }
 extern "C" int dsrl_convt2x2_fwd(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, dsrl_stream_t stream) {
     DSRL_PROLOGUE(x && w && y && N > 0 && H > 0 && W > 0, "convt2x2_fwd")
     dim3 grid((unsigned)ceil_div(2 * W, 256), (unsigned)(N * H));          // a block writes both output rows of its input row
     {
-        const char* mv = getenv("DSRL_CONVT_MFMA");
         const int nseg_per_row = (int)ceil_div(W, 128);
         const long long nseg = (long long)N * H * nseg_per_row;
-        if ((!mv || atoi(mv) != 0) && W % 4 == 0 && nseg < (1ll << 31) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0) {
+        if (knob("DSRL_CONVT_MFMA", 1) && W % 4 == 0 && nseg < (1ll << 31) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0) {
             const int nb = (int)std::min<long long>(nseg, convt_block_cap(4 * 512));
             DSRL_CONVT_DISPATCH(19, 19, hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<CI, CO>), dim3(nb), dim3(256), 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ConvtFwdCe{}); return launch_status("convt2x2_fwd_mfma_kernel");)
             DSRL_CONVT_DISPATCH(8, 8, hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<CI, CO>), dim3(nb), dim3(256), 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ConvtFwdCe{}); return launch_status("convt2x2_fwd_mfma_kernel");)
@@ -1239,9 +1237,7 @@ extern "C" int dsrl_convt2x2_fwd(const float* x, const float* w, const float* bi
 // ce_finalize_kernel lives in losses.hip
 int launch_ce_finalize(const double* part, int nb, float* loss_out, hipStream_t st);
 extern "C" int dsrl_convt2x2_fwd_ce_supported(const float* x, const float* y, int N, int H, int W, int Cin, int Cout) {
-    const char* v = getenv("DSRL_CONVT_CE");
-    const char* mv = getenv("DSRL_CONVT_MFMA");
-    if ((v && atoi(v) == 0) || (mv && atoi(mv) == 0)) return 0;
+    if (!knob("DSRL_CONVT_CE", 1) || !knob("DSRL_CONVT_MFMA", 1)) return 0;
     return (x && y && N > 0 && H > 0 && W > 0 && Cin == 19 && Cout == 19 && W % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 &&
             (long long)N * H * ceil_div(W, 128) < (1ll << 31)) ? 1 : 0;
 }
@@ -1262,7 +1258,6 @@ extern "C" int dsrl_convt2x2_fwd_ce(const float* x, const float* w, const float*
     if (int e = launch_status("convt2x2_fwd_mfma_kernel")) return e;
     return launch_ce_finalize((const double*)ws, nb, loss_out, st);
 }
-static bool env_flag_convt_fused() { const char* v = getenv("DSRL_CONVT_FUSED_BWD"); return !v || atoi(v) != 0; }   // 0: the separate dx / dw kernels
 static int convt_dw_blocks(int N, int H, int W) { return (int)std::min<long long>(convt_block_cap(1024), (long long)N * H * ceil_div(W, 64)); }
 extern "C" size_t dsrl_convt2x2_bwd_workspace_bytes(int N, int H, int W, int Cin, int Cout) {
     return (size_t)convt_dw_blocks(N, H, W) * (Cin * Cout * 4 + Cout) * sizeof(float);
@@ -1275,9 +1270,8 @@ extern "C" int dsrl_convt2x2_bwd(const float* x, const float* w, const float* dy
     const int nseg_per_row = (int)ceil_div(W, 64);
     const long long nseg = (long long)N * H * nseg_per_row;
     dim3 gdx((unsigned)ceil_div(W, 128), (unsigned)(N * H));
-    const bool fused = W % 4 == 0 && nseg < (1ll << 31) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0 && env_flag_convt_fused();
-    const char* mv = getenv("DSRL_CONVT_MFMA");
-    const bool mfma = fused && (!mv || atoi(mv) != 0);                      // the same pass on the matrix pipe (segments of 128 pixels)
+    const bool fused = W % 4 == 0 && nseg < (1ll << 31) && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0 && knob("DSRL_CONVT_FUSED_BWD", 1);      // 0: the separate dx / dw kernels
+    const bool mfma = fused && knob("DSRL_CONVT_MFMA", 1);                      // the same pass on the matrix pipe (segments of 128 pixels)
     const int nseg_per_row2 = (int)ceil_div(W, 128);
     const long long nseg2 = (long long)N * H * nseg_per_row2;
     const int nb2 = (int)std::min<long long>(nb, nseg2);
@@ -1316,8 +1310,7 @@ extern "C" int dsrl_convt2x2_bwd(const float* x, const float* w, const float* dy
 }
 
 extern "C" int dsrl_convt2x2_bwd_ce_supported(const float* x, const float* logits, const uint8_t* target, int N, int H, int W, int Cin, int Cout) {
-    const char* v = getenv("DSRL_CONVT_CE");
-    if (v && atoi(v) == 0) return 0;
+    if (!knob("DSRL_CONVT_CE", 1)) return 0;
     return (x && logits && target && N > 0 && H > 0 && convt_bwd_dma_supported(x, logits, W, Cin, Cout) && ((uintptr_t)target % 16) == 0 &&
             (long long)N * H * (W / 128) < (1ll << 31) && (long long)N * 4 * H * W * Cout * 4 < (1ll << 32)) ? 1 : 0;
 }

@@ -15,7 +15,6 @@ Replaces what the reference gets from `torch.nn.parallel.DistributedDataParallel
 One process per GPU; `torch.distributed` backend 'nccl' is RCCL on ROCm.  With world size 1 (or no process group) the
 collectives are skipped and only the arena + fused optimiser remain.
 """
-import os
 
 import torch
 import torch.distributed as dist
@@ -92,14 +91,14 @@ class FlatParams:
         self._claimed = set()
         # Round 5: zero_grad() skips the fill of the gradient arena (239.5 MB, 31 us) when every parameter's gradient kernel OVERWROTE its slot in the
         # previous pass (claim: all 354 parameters of the stage-3 step do) - the same kernels will overwrite them again.  settle_grads() checks the
-        # assumption behind the skipped fill after the backward pass and refuses to go on if it did not hold (DSRL_LAZY_ZERO_GRAD=0: always fill).
-        self.lazy_zero = os.environ.get('DSRL_LAZY_ZERO_GRAD', '1') != '0'
+        # assumption behind the skipped fill after the backward pass and refuses to go on if it did not hold (lazy_zero = False: always fill).
+        self.lazy_zero = True
         self._all_claimed_last = False
         self._fill_skipped = False
         for p in self.params:
             p._dsrl_arena = self
         self._build_transposed_filters()
-        if self.world > 1 and self.device.type == 'cuda' and os.environ.get('DSRL_BN_FUSED_BIG') is None:
+        if self.world > 1 and self.device.type == 'cuda' and HF.knob('DSRL_BN_FUSED_BIG', None) is None:
             # RCCL kernels hold CUs while they wait for their peers: a 256-block fused-BN launch (one block on EVERY CU) could stall behind
             # them, the 128-block variant cannot
             HF.set_bn_fused_max_blocks(128)
@@ -270,8 +269,8 @@ class FlatParams:
             self._amax_key = self._params_key()
 
     def _fold_amax(self):
-        return (self.device.type == 'cuda' and self._wt_table is not None and HF.f16_mode() and os.environ.get('DSRL_PRESPLIT', '1') != '0' and
-                os.environ.get('DSRL_FILTER_AMAX_STREAM', '1') != '0' and os.environ.get('DSRL_SGD_AMAX', '1') != '0' and self._split_table is not None)
+        return (self.device.type == 'cuda' and self._wt_table is not None and HF.f16_mode() and HF.knob('DSRL_FILTER_AMAX_STREAM', True) and
+                HF.knob('DSRL_SGD_AMAX', True) and self._split_table is not None)
 
     def _build_plane_filters(self):
         """The filters whose convs take plane operands (channel counts multiples of 8), as fp16 planes, forward [K][R][S][C] and transposed
@@ -307,14 +306,14 @@ class FlatParams:
                    for e in self._split_entries)
 
     def refresh_transposed_filters(self):
-        if self._wt_table is not None and os.environ.get('DSRL_BATCHED_TRANSPOSE', '1') != '0':
-            presplit = HF.f16_mode() and os.environ.get('DSRL_PRESPLIT', '1') != '0'
+        if self._wt_table is not None:
+            presplit = HF.f16_mode()
             if presplit and self._split_table is None:
                 self._build_split_filters()
             # with pre-split filters nothing reads the fp32 transposes: the first launch then only measures (amax records), the second writes both split forms
             if presplit and self._amax_key is not None and self._amax_key == self._params_key() and self._fold_amax():
                 pass            # round 5: the optimiser pass of the previous step left max |w| of every filter it wrote (dsrl_sgd_step_dev_segments)
-            elif presplit and os.environ.get('DSRL_FILTER_AMAX_STREAM', '1') != '0':
+            elif presplit and HF.knob('DSRL_FILTER_AMAX_STREAM', True):
                 self.w_amax.zero_()
                 HF.call('dsrl_conv2d_filters_amax_batched', self._amax_seg_table.data_ptr(), self._amax_segs, HF._stream())
             else:
@@ -357,7 +356,7 @@ class FlatParams:
         if self._fill_skipped and not complete:
             missing = [i for i in range(len(self.params)) if i not in self._claimed]
             raise HF.DsrlHipError(f'{len(missing)} parameter gradients were not written by their kernels in this pass (first: parameter #{missing[0]}) although the '
-                                  'previous pass wrote all of them, and the gradient arena was not zeroed: the graph of the step changed - set DSRL_LAZY_ZERO_GRAD=0')
+                                  'previous pass wrote all of them, and the gradient arena was not zeroed: the graph of the step changed - set lazy_zero = False on this FlatParams')
         self._all_claimed_last = complete
         self._fill_skipped = False
 
@@ -418,12 +417,8 @@ class FlatParams:
         if self.world == 1:
             return
         # nothing overlaps with these collectives, so they are as large as possible (ring all-reduce bandwidth over xGMI grows with the message
-        # size): the whole 239.5 MB arena in pieces of DSRL_REDUCE_ALL_MB (default 256, i.e. one call)
-        per = max(1, int(os.environ.get('DSRL_REDUCE_ALL_MB', '256'))) << 18          # floats
-        works = [dist.all_reduce(self.g_flat[a:min(a + per, self.numel)], op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
-                 for a in range(0, self.numel, per)]
-        for w in works:
-            w.wait()
+        # size): the whole 239.5 MB arena in one call
+        dist.all_reduce(self.g_flat, op=dist.ReduceOp.SUM, group=self.pg, async_op=True).wait()
 
     def reduce_chunked_and_step(self, hyper=None, hp=None, nchunks=None):
         """The default exchange behind a replayed (or deferred eager) backward pass with more than one rank: the gradient arena is cut into
@@ -432,7 +427,7 @@ class FlatParams:
         single 239.5 MB call of round 4 exposed the whole optimiser pass behind the exchange).  Only element-wise kernels touch the ranges, so they
         need no parameter alignment beyond 16 bytes; no barrier kernel is co-resident with RCCL here - those are all inside the graph that has
         finished.  Bit-identical to reduce_all() + one SGD launch (same element-wise arithmetic).  Returns the chunk ranges (tests)."""
-        n = max(1, int(os.environ.get('DSRL_REDUCE_CHUNKS', '4')) if nchunks is None else int(nchunks))
+        n = max(1, HF.knob('DSRL_REDUCE_CHUNKS', 4) if nchunks is None else int(nchunks))
         per = _align(-(-self.numel // n), 1024)
         ranges = [(a, min(a + per, self.numel)) for a in range(0, self.numel, per)]
         works = []

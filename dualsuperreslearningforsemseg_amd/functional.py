@@ -11,7 +11,7 @@ import weakref
 import torch
 
 from . import _lib
-from ._lib import call, query, DsrlHipError
+from ._lib import call, knob, query, DsrlHipError
 
 CL = torch.channels_last
 
@@ -34,10 +34,7 @@ def _stream():
 # only read dy): the small backbone layers do not fill 256 CUs on their own. ddp.FlatParams joins the stream before it
 # reduces / applies the gradients; without an arena the caller's stream waits right away.
 _side = {}
-overlap_wgrad = os.environ.get('DSRL_OVERLAP_WGRAD', '1') != '0'     # measured: +10-13 % step throughput on one MI355X
-# building dgrad's transposed filters during the forward pass on the side stream: measured SLOWER (two-stream allocator / event
-# overhead on the host outweighs the 0.5 ms of transposes it hides) - kept selectable
-pretranspose_filters = os.environ.get('DSRL_PRETRANSPOSE', '0') != '0'
+overlap_wgrad = knob('DSRL_OVERLAP_WGRAD', True)     # measured: +10-13 % step throughput on one MI355X
 
 
 CONV_PRECISION_MODES = {'fp32': 0, 'bf16x3': 1, 'bf16x6': 2, 'mixed': 3, 'f16x3': 4, 'f16x1': 5}
@@ -65,7 +62,7 @@ def _conv_precision_code():
     code = _mode_cache.get('code')
     if code is None:
         prev = int(_lib.load().dsrl_conv_precision(-2))          # out-of-range argument: query only
-        code = prev if prev >= 0 else int(os.environ.get('DSRL_CONV_PRECISION', str(DEFAULT_CONV_PRECISION)))
+        code = prev if prev >= 0 else knob('DSRL_CONV_PRECISION', DEFAULT_CONV_PRECISION)
         code = _mode_cache['code'] = min(max(code, 0), 5)
     return code
 
@@ -231,7 +228,7 @@ def join_side_streams():
 # its weight-gradient problem (x, dy, arena slot); flush() launches all of them as a few grouped grids (dsrl_conv2d_wgrad_group_*).
 # Nothing but the optimiser reads a weight gradient, the small layers do not fill the chip on their own, and a pass-wide grid needs
 # neither the side stream nor per-layer pixel splits.  Off: DSRL_WGRAD_GROUP=0 (per-layer launches, overlapped on the side stream).
-group_wgrad = os.environ.get('DSRL_WGRAD_GROUP', '1') != '0'
+group_wgrad = knob('DSRL_WGRAD_GROUP', True)
 graph_keepalive = None          # a list while a hipGraph capture is in progress: host buffers the captured copies read on every replay
 capture_host, capture_host_off = None, 0      # pinned arena for host tables written during a capture (allocated before it starts)
 
@@ -319,14 +316,7 @@ def new_cl(shape, like):
     return torch.empty(shape, device=like.device, dtype=torch.float32, memory_format=CL)
 
 
-# Workspaces: kernels of one stream run one after the other and each is done with its scratch when the next starts, so ONE
-# growing buffer per (device, stream) serves every call on that stream (saves ~700 allocator round trips per step).
-_ws_pool = {}
-
-
-_use_ws_pool = os.environ.get('DSRL_WS_POOL', '0') != '0'       # measured: no difference; the caching allocator is already cheap
-
-
+# Workspaces come from the caching allocator, one per call: a growing buffer per (device, stream) was measured and made no difference.
 _ws_none = {}
 
 
@@ -337,14 +327,7 @@ def _ws(nbytes, like):
         if buf is None:
             buf = _ws_none[like.device] = torch.empty(256, device=like.device, dtype=torch.uint8)
         return buf
-    nbytes = max(nbytes, 256)
-    if not _use_ws_pool:
-        return torch.empty(nbytes, device=like.device, dtype=torch.uint8)
-    key = (like.device, torch.cuda.current_stream(like.device).cuda_stream)
-    buf = _ws_pool.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = _ws_pool[key] = torch.empty(max(nbytes, 64 << 20) * (2 if buf is not None else 1), device=like.device, dtype=torch.uint8)
-    return buf
+    return torch.empty(max(nbytes, 256), device=like.device, dtype=torch.uint8)
 
 
 _query_cache = {}
@@ -512,14 +495,14 @@ def planes_of(data, ld, amax, nplanes=2):
 # planes yet, 'auto' (default) = the split pass only where it pays by itself (tensors of >= DSRL_PLANES_MIN_ELEMS elements: the 65536-pixel decoder
 # operands; a split launch costs ~6 us on the small ones, more than the planes kernel gains there) - producers that write planes beside their
 # fp32 output are used in every mode but 'off'
-planes_mode = os.environ.get('DSRL_PLANES_MODE', 'auto')
+planes_mode = knob('DSRL_PLANES_MODE', 'auto')
 if planes_mode == 'off':
     os.environ.setdefault('DSRL_PLANES', '0')       # the library's planner then keeps the f16x3 forward off the 256x256 tile, whose register-staged build spills
-planes_min_elems = int(os.environ.get('DSRL_PLANES_MIN_ELEMS', str(8 << 20)))
+planes_min_elems = knob('DSRL_PLANES_MIN_ELEMS', 8 << 20)
 # Round 5: the reduced-precision 'f16x1' arithmetic (apex O1 / O2) takes ONE plane per operand - the conv a 2-byte storage format would run.  A one-plane split
 # pass moves 6 instead of 8 bytes per element and the conv gains more (tools/fp16_slice.py at config 5's shapes: cat_conv.0 forward 593 -> 406 us, dgrad
 # 772 -> 547 us; layer3 3x3 48 -> 35 us), so the pass pays from 2 Mi elements on, and for the data gradients of the >= 8 Mi-element operands as well.
-planes_min_elems_x1 = int(os.environ.get('DSRL_PLANES_MIN_ELEMS_X1', str(2 << 20)))
+planes_min_elems_x1 = knob('DSRL_PLANES_MIN_ELEMS_X1', 2 << 20)
 
 
 def _planes_npl():
@@ -649,9 +632,9 @@ def current_seed():
 # no gradient of its own.  Only sound when EVERY consumer of the tensor takes part, hence fork(): an alias node whose output is
 # consumed inside the block only; other users of the original tensor see one ordinary gradient.  Any case the protocol does not
 # cover falls back to returning a separate gradient (closed slot), which autograd sums as usual.
-grad_slots_enabled = os.environ.get('DSRL_GRAD_SLOTS', '1') != '0'
+grad_slots_enabled = knob('DSRL_GRAD_SLOTS', True)
 # one slot for the three consumers of layer1's output (ResNet101.forward / DSRL.forward_head, round 5)
-outer_grad_slot = os.environ.get('DSRL_OUTER_SLOT', '1') != '0'
+outer_grad_slot = knob('DSRL_OUTER_SLOT', True)
 
 
 class GradSlot:
@@ -667,11 +650,11 @@ class GradSlot:
 # gradient of y in registers and can leave the BatchNorm-backward partial sums with it (dsrl_conv2d_dgrad_bnstats); the BN backward
 # then runs as one streaming kernel (dsrl_bn_bwd_from_stats).  A BNLink carries what the conv needs from the BN's forward and the
 # partials back; the BN only trusts them if the gradient it receives is the very buffer that conv wrote.
-bn_bwd_stats_enabled = os.environ.get('DSRL_BN_BWD_STATS', '1') != '0'
+bn_bwd_stats_enabled = knob('DSRL_BN_BWD_STATS', True)
 # the same for bn3 via the next block's accumulating dgrad.  Rounds 3-4: correct but slower (the wide 1x1 data gradients spent 11-17 us in an epilogue of
 # 4-byte loads of x / y).  Round 5: on since that epilogue reads float4 rows through LDS (conv_split_kernel.h, bn_fast): +0.65 % step throughput, 29 of the 45
 # device-wide-barrier BatchNorm launches become streaming from-sums launches (profiles/round5_ab.txt)
-bn_bwd_stats_shared = os.environ.get('DSRL_BN_BWD_STATS_SHARED', '1') != '0'
+bn_bwd_stats_shared = knob('DSRL_BN_BWD_STATS_SHARED', True)
 
 
 class BNLink:
@@ -746,18 +729,6 @@ class _Conv2d(torch.autograd.Function):
         ctx.has_bias = bias is not None
         ctx.bparam = bias if isinstance(bias, torch.nn.Parameter) else None
         ctx.wparam = w_param if isinstance(w_param, torch.nn.Parameter) else None
-        ctx.wt = None
-        if pretranspose_filters and ctx.needs_input_grad[0]:
-            # the data-gradient kernel reads the filter transposed: build that copy now, on the side stream, off the critical path
-            cur, side = torch.cuda.current_stream(), side_stream(x.device)
-            side.wait_stream(cur)                                   # the weights (last SGD update) are ready on the compute stream
-            with torch.cuda.stream(side):
-                wt = torch.empty(cquery('dsrl_conv2d_transposed_filter_floats', Cc, K, R, S), device=x.device, dtype=torch.float32)
-                call('dsrl_conv2d_transpose_filter', w.data_ptr(), wt.data_ptr(), Cc, K, R, S, side.cuda_stream)
-                ev = torch.cuda.Event()
-                ev.record(side)
-            w.record_stream(side)
-            ctx.wt = (wt, ev)
         if stats is not None:
             ctx.mark_non_differentiable(stats)
             return y, stats
@@ -820,12 +791,7 @@ class _Conv2d(torch.autograd.Function):
                 slot.link.stats = None      # sums left by an earlier contributor do not contain this gradient: that BatchNorm takes its own path
             ws = _ws(cquery('dsrl_conv2d_dgrad_workspace_bytes', *shp), x)
             wt_ptr = None
-            if ctx.wt is not None:
-                wt, ev = ctx.wt
-                torch.cuda.current_stream().wait_event(ev)
-                wt.record_stream(torch.cuda.current_stream())
-                wt_ptr = wt.data_ptr()
-            elif ctx.wparam is not None:
+            if ctx.wparam is not None:
                 # ddp.FlatParams keeps a transposed copy of every filter, refreshed by one batched launch per training step
                 arena, wt = getattr(ctx.wparam, '_dsrl_arena', None), getattr(ctx.wparam, '_dsrl_wt', None)
                 if wt is not None and arena is not None and arena.wt_valid and arena.wt_fp32_valid:
@@ -1047,7 +1013,7 @@ class _BNAct(torch.autograd.Function):
         return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None, dres, None, None, None, None, None
 
 
-bn_res_stats_enabled = os.environ.get('DSRL_BN_RES_STATS', '1') != '0'       # 0: the downsample BatchNorm reduces its own backward sums (until round 5)
+bn_res_stats_enabled = knob('DSRL_BN_RES_STATS', True)      # 0: the downsample BatchNorm reduces its own backward sums (until round 5)
 
 
 def batch_norm_act(x, bn, relu=False, drop_p=0.0, seed=0, rng_stream=0, residual=None, residual_grad_slot=None, stats=None, out_link=None, res_link=None):
@@ -1064,7 +1030,7 @@ def batch_norm_act(x, bn, relu=False, drop_p=0.0, seed=0, rng_stream=0, residual
 
 # BatchNorm statistics from the conv epilogue: the conv that feeds a training-mode BN leaves (n, mean, M2) partials of its output, and
 # the BN becomes one streaming kernel without a statistics pass (dsrl_conv2d_fwd_stats + dsrl_bn_train_fwd_from_stats)
-conv_bn_stats_enabled = os.environ.get('DSRL_CONV_BN_STATS', '1') != '0'
+conv_bn_stats_enabled = knob('DSRL_CONV_BN_STATS', True)
 
 
 def conv2d_bn_act(x, weight, bias, stride, padding, dilation, bn, relu=False, drop_p=0.0, seed=0, rng_stream=0, residual=None,
@@ -1192,7 +1158,7 @@ def max_pool3x3s2(x):
     return _MaxPool3x3s2.apply(x)
 
 
-cat_one_launch = os.environ.get('DSRL_CAT_ONE_LAUNCH', '1') != '0'        # 0: a strided copy per source + a magnitude pass by the consumer (until round 5)
+cat_one_launch = knob('DSRL_CAT_ONE_LAUNCH', True)       # 0: a strided copy per source + a magnitude pass by the consumer (until round 5)
 
 
 class _Cat(torch.autograd.Function):
@@ -1235,7 +1201,7 @@ def cat_channels(xs):
 
 
 # ------------------------------------------------------------------------------------------------ ConvTranspose k2s2 / PixelShuffle / pointwise
-convt_ce_enabled = os.environ.get('DSRL_CONVT_CE', '1') != '0'
+convt_ce_enabled = knob('DSRL_CONVT_CE', True)
 
 
 class LogitsGrad:

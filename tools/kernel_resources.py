@@ -12,18 +12,20 @@ import tempfile
 LLVM = '/opt/rocm/lib/llvm/bin'
 
 
+def code_objects(path, tmp):
+    """Unbundles `path` into `tmp`; the paths of its gfx950 code objects (none: a host-only object, runtime.hip has no kernels)."""
+    local = os.path.join(tmp, 'obj')
+    shutil.copy(path, local)
+    subprocess.run([os.path.join(LLVM, 'llvm-objdump'), '--offloading', local], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=tmp)
+    return [os.path.join(tmp, p) for p in sorted(os.listdir(tmp)) if 'gfx950' in p]
+
+
 def kernels(path):
     """[{name, vgpr, sgpr, scratch, vgpr_spill, sgpr_spill, lds}] of the gfx950 code object bundled in `path`."""
     with tempfile.TemporaryDirectory() as tmp:
-        local = os.path.join(tmp, 'obj')
-        shutil.copy(path, local)
-        subprocess.run([os.path.join(LLVM, 'llvm-objdump'), '--offloading', local], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=tmp)
-        dev = [p for p in os.listdir(tmp) if 'gfx950' in p]
-        if not dev:
-            return []               # host-only object (runtime.hip has no kernels)
         out = []
-        for d in dev:
-            notes = subprocess.run([os.path.join(LLVM, 'llvm-readelf'), '--notes', os.path.join(tmp, d)], check=True, capture_output=True, text=True).stdout
+        for d in code_objects(path, tmp):
+            notes = subprocess.run([os.path.join(LLVM, 'llvm-readelf'), '--notes', d], check=True, capture_output=True, text=True).stdout
             cur = {}
             for ln in notes.splitlines():
                 m = re.match(r'\s*-?\s*\.(\w+):\s+(.*)$', ln)

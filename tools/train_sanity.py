@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """End-to-end sanity: N training steps on ONE fixed synthetic batch (dropout off so that runs are comparable), default fast
-configuration vs the conservative one (exact-product fp32 convs, three-kernel BN, no shared gradient buffers, per-layer filter
-transposes, no K groups).  The loss must fall and the two trajectories must track each other."""
+configuration vs the conservative one (exact-product fp32 convs, three-kernel BN, no shared gradient buffers, no K groups).  The loss must fall and the two trajectories must track each other."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -9,11 +8,11 @@ steps = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 
 
 def run(conservative):
-    for k in ('DSRL_BN_FUSED', 'DSRL_BATCHED_TRANSPOSE', 'DSRL_FORCE_KG', 'DSRL_WGRAD_KG', 'DSRL_SPLIT_PLAN'):
+    for k in ('DSRL_BN_FUSED', 'DSRL_FORCE_KG'):
         os.environ.pop(k, None)
     from dualsuperreslearningforsemseg_amd import functional as HF
     if conservative:
-        os.environ.update(DSRL_BN_FUSED='0', DSRL_BATCHED_TRANSPOSE='0', DSRL_FORCE_KG='1', DSRL_WGRAD_KG='0', DSRL_SPLIT_PLAN='0')
+        os.environ.update(DSRL_BN_FUSED='0', DSRL_FORCE_KG='1')
     HF.set_conv_precision('fp32' if conservative else None)
     HF.grad_slots_enabled = not conservative
     from dualsuperreslearningforsemseg_amd.models import DSRL
