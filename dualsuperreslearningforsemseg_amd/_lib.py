@@ -128,6 +128,9 @@ PROTOTYPES = {
     'dsrl_fa_fwd': (i32, [fp, fp, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, fp, fp, fp, sz, stream_t]),
     'dsrl_fa_bwd': (i32, [fp, fp, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, fp, fp, fp, fp, fp, sz, stream_t]),
     'dsrl_seg_metrics': (i32, [fp, i32, fp, i64, i32, i32, fp, stream_t]),
+    'dsrl_sssr_tail_predict_supported': (i32, [i32] * 6),
+    'dsrl_sssr_tail_predict_workspace_bytes': (sz, [i32] * 3),
+    'dsrl_sssr_tail_predict': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, stream_t]),
     'dsrl_prepare_batch': (i32, [fp, fp, fp, C.POINTER(f32), C.POINTER(f32), fp, fp, fp, i32, i32, i32, i32, i32, stream_t]),
     'dsrl_augment_geometry': (i32, [fp, fp, fp, fp, fp, fp, i32, i32, i32, stream_t]),
     'dsrl_prepare_batch_augmented': (i32, [fp, fp, fp, C.POINTER(f32), C.POINTER(f32), fp, fp, fp, i32, i32, i32, i32, i32, fp, stream_t]),

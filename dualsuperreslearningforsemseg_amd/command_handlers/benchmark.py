@@ -1,0 +1,85 @@
+"""Cross entropy, mIoU and accuracy of a weights file over a dataset split - counterpart of the reference's command_handlers/benchmark.py (same
+`benchmark(...)` signature and figures).
+
+What differs by design: the model runs `DSRL.predict` (the SSSR tail, the arg-max, the metric counters and the loss in one kernel; no logits in
+memory), the batches come through the `loader_factory` protocol of train_or_resume (dataset['loader_factory'] when given, else the Cityscapes cache
+without augmentation, every sample), and the host reads the device ONCE, after the last batch, instead of copying every batch's logits back."""
+import os
+from datetime import datetime
+
+import torch as t
+
+from .. import settings
+from ..metrices import Accuracy, AverageMeter, mIoU
+from ..models import DSRL
+from ..utils import load_checkpoint_or_weights
+from .train_or_resume import isCUDAdevice
+
+NOT_GPU = "this build runs on the MI355X only: use device='gpu' (the reference's --device cpu path is its own)"
+
+
+def load_eval_model(weights, dataset_settings, device_obj):
+    """Stage-1 DSRL in eval mode with the matching entries of the file's state dict (a stage-2/3 file carries more: strict=False, as the reference)."""
+    model = DSRL(stage=1, dataset_settings=dataset_settings).eval()
+    model.load_state_dict(load_checkpoint_or_weights(weights, map_location='cpu')['model_state_dict'], strict=False)
+    return model.to(device_obj).to(memory_format=t.channels_last)
+
+
+def split_loader(dataset, split, batch_size, device_obj, input_size):
+    factory = dataset.get('loader_factory')
+    if factory is None:
+        os.makedirs(dataset['path'], exist_ok=True)
+        if len(os.listdir(dataset['path'])) == 0:
+            raise Exception("Cityscapes dataset was not found under '{:s}'.".format(dataset['path']))
+        from ..datasets.Cityscapes.loader import loader_factory
+        factory = loader_factory(dataset, input_size, settings.RANDOM_SEED)
+    return factory(split, batch_size, device_obj, 0, 1)
+
+
+def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
+    if not isCUDAdevice(device):
+        raise RuntimeError(NOT_GPU)
+    started = datetime.now()
+    input_size = other_args.get('model_input_size', settings.MODEL_INPUT_SIZE)
+    device_obj = t.device('cuda', t.cuda.current_device())
+    ds = dataset['settings']
+    split = dataset.get('split', 'val')
+    model = load_eval_model(weights, ds, device_obj)
+    loader = split_loader(dataset, split, batch_size, device_obj, input_size)
+
+    nan_flag = t.zeros((), dtype=t.int32, device=device_obj)
+    ces, tables = [], []
+    for (input_image, _), (target, _) in loader:
+        _, counts, ce = model.predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag)
+        ces.append(ce)
+        tables.append(counts)
+    if not ces:
+        raise RuntimeError(f"the '{split}' split yielded no batch")
+    # the one device -> host read: losses, NaN flag and counters in a single float64 tensor (counters < 2^53: exact)
+    nb, nc = len(ces), ds.NUM_CLASSES
+    host = t.cat([t.stack(ces).double(), nan_flag.double().reshape(1), t.stack(tables).double().reshape(-1)]).cpu()
+    bits = int(host[nb].item())
+    if bits:
+        raise RuntimeError('benchmark: ' + ' and '.join(m for b, m in ((1, 'NaN in the input or the logits'), (2, 'labels outside the classes')) if bits & b))
+    CE_avg_loss = AverageMeter()
+    miou, accuracy_mean = mIoU(num_classes=nc, ignore_index=ds.IGNORE_CLASS_LABEL), Accuracy(num_classes=nc, ignore_index=ds.IGNORE_CLASS_LABEL)
+    host_tables = host[nb + 1:].reshape(nb, 3 * nc + 2).to(t.int64)
+    for i in range(nb):
+        CE_avg_loss.update(float(host[i]), batch_size)          # weighted by the nominal batch size, the last short batch included, as the reference
+        miou.update_from_counts(host_tables[i])
+        accuracy_mean.update_from_counts(host_tables[i])
+    result = {'CE': CE_avg_loss(), 'mIoU': miou(), 'accuracy': accuracy_mean()}
+
+    lines = ['Avg. Cross Entropy Error: {:.3f}'.format(result['CE']), 'mIoU %: {:.2f}'.format(result['mIoU']),
+             'Mean Accuracy %: {:.2f}'.format(result['accuracy'])]
+    print('-------- RESULTS --------')
+    for ln in lines:
+        print(ln)
+    output_dir = other_args.get('output_dir', 'outputs')
+    os.makedirs(output_dir, exist_ok=True)
+    with open(os.path.join(output_dir, 'benchmark.txt'), 'w') as f:
+        f.write("Benchmarking results on the dataset's {:s} split\n\n".format(split))
+        f.write('On: {:s}\n'.format(started.strftime('%c')))
+        f.write('Weights file: {:s}\n\n'.format(str(weights)))
+        f.write('\n'.join(lines) + '\n')
+    return result

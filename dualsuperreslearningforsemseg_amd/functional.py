@@ -1739,5 +1739,74 @@ def nan_check_(flag, *tensors):
         call('dsrl_nan_check', td.data_ptr(), td.numel(), flag.data_ptr(), st)
 
 
+# ------------------------------------------------------------------------------------------------ inference
+def _bad_label_bit(nan_flag, target, ignore_index, num_classes):
+    """bit 1 of `nan_flag`: a label outside [0, num_classes) that is not the ignore label"""
+    bad = ((target != ignore_index) & (target >= num_classes)).any()
+    nan_flag.bitwise_or_((bad.to(torch.int32) * 2).reshape(nan_flag.shape))
+
+
+def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, counts=None, nan_flag=None):
+    """Eval-mode tail of the SSSR decoder after its bilinear x2 (DSRL.py:55-69): ConvTranspose2d k2 s2 `convt1` -> BatchNorm2d `bn` (running statistics)
+    -> ReLU -> ConvTranspose2d k2 s2 `convt2` -> arg-max, as one launch that writes class indices and never the logits (dsrl_sssr_tail_predict).
+    -> (pred uint8 (N,4H,4W), ce): with `target` (N,4H,4W) `ce` is the 0-d device tensor of nn.CrossEntropyLoss(ignore_index) of the logits and
+    `counts` (int64 [3*classes+2], optional) gets the table of dsrl_seg_metrics ADDED; `nan_flag` (int32 scalar, optional): bit 0 NaN logit, bit 1 a
+    label outside the classes.  Heads the kernel does not implement run the modules one by one and reduce their logits."""
+    with torch.no_grad():
+        x, ldx = pm(x)
+        w1, w2, b2 = convt1.weight, convt2.weight, convt2.bias
+        _need_gpu(w1, w2, b2, bn.weight, bn.bias, bn.running_mean, bn.running_var, target, counts, nan_flag)
+        if bn.training or bn.running_mean is None or bn.running_var is None:
+            raise DsrlHipError('sssr_tail_predict: the BatchNorm must be in eval mode and track running statistics')
+        N, Ci, H, W = x.shape
+        if w1.dim() != 4 or w2.dim() != 4 or w1.shape[0] != Ci or w2.shape[0] != w1.shape[1] or bn.num_features != w1.shape[1]:
+            raise DsrlHipError(f'sssr_tail_predict: {Ci} input channels do not chain through filters {tuple(w1.shape)}, {tuple(w2.shape)}')
+        Cm, Co = w1.shape[1], w2.shape[1]
+        if target is not None:
+            if tuple(target.shape) != (N, 4 * H, 4 * W):
+                raise DsrlHipError(f'sssr_tail_predict: target {tuple(target.shape)} is not {(N, 4 * H, 4 * W)}')
+            if target.dtype != torch.uint8:
+                target = target.to(torch.uint8)
+            target = target.contiguous()
+            if target.data_ptr() % 4:
+                target = target.clone()
+        elif counts is not None:
+            raise DsrlHipError('sssr_tail_predict: counts need a target')
+        if counts is not None and (counts.dtype != torch.int64 or counts.numel() != 3 * Co + 2 or not counts.is_contiguous()):
+            raise DsrlHipError(f'sssr_tail_predict: counts must be a contiguous int64 tensor of {3 * Co + 2} elements')
+        if nan_flag is not None and (nan_flag.dtype != torch.int32 or nan_flag.numel() != 1):
+            raise DsrlHipError('sssr_tail_predict: nan_flag must be an int32 scalar')
+        k2s2 = all(m.kernel_size == (2, 2) and m.stride == (2, 2) and m.padding == (0, 0) and m.output_padding == (0, 0) and m.groups == 1
+                   for m in (convt1, convt2))
+        if k2s2 and convt1.bias is None and cquery('dsrl_sssr_tail_predict_supported', N, H, W, Ci, Cm, Co):
+            st = _stream()
+            invstd = torch.empty(Cm, device=x.device, dtype=torch.float32)
+            call('dsrl_bn_invstd_from_var', bn.running_var.data_ptr(), Cm, float(bn.eps), invstd.data_ptr(), st)
+            pred = torch.empty((N, 4 * H, 4 * W), device=x.device, dtype=torch.uint8)
+            ce = torch.empty(2, device=x.device, dtype=torch.float32) if target is not None else None
+            ws = _ws(cquery('dsrl_sssr_tail_predict_workspace_bytes', N, H, W) if ce is not None else 0, x)
+            gamma = bn.weight if bn.weight is not None else torch.ones_like(invstd)
+            beta = bn.bias if bn.bias is not None else torch.zeros_like(invstd)
+            call('dsrl_sssr_tail_predict', x.data_ptr(), ldx, N, H, W, Ci, Cm, Co, w1.contiguous().data_ptr(), bn.running_mean.data_ptr(),
+                 invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w2.contiguous().data_ptr(), None if b2 is None else b2.data_ptr(),
+                 pred.data_ptr(), None if target is None else target.data_ptr(), int(ignore_index), None if counts is None else counts.data_ptr(),
+                 None if ce is None else ce.data_ptr(), None if nan_flag is None else nan_flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
+            return pred, (None if ce is None else ce[0])
+        # any other head: the modules as the training forward runs them in eval mode, then the reductions over their logits
+        y = batch_norm_act(convt1(x), bn, relu=True)
+        logits = convt2(y)
+        pred = torch.argmax(logits, dim=1).to(torch.uint8)
+        if nan_flag is not None:
+            nan_check_(nan_flag, logits)
+        if target is None:
+            return pred, None
+        if nan_flag is not None:
+            _bad_label_bit(nan_flag, target, int(ignore_index), Co)
+        if counts is not None:
+            lg, ld = pm(logits)
+            call('dsrl_seg_metrics', lg.data_ptr(), ld, target.data_ptr(), N * 16 * H * W, Co, int(ignore_index), counts.data_ptr(), _stream())
+        return pred, cross_entropy(logits, target, int(ignore_index))
+
+
 def conv2d_inbounds_macs(N, H, W, Cc, K, R, S, stride, pad, dil):
     return cquery('dsrl_conv2d_inbounds_macs', N, H, W, Cc, K, R, S, stride, pad, dil)

@@ -46,6 +46,12 @@ class _Counts:
         scores = torch.nn.functional.one_hot(pred.long(), self.num_classes).permute(0, 3, 1, 2).float().contiguous(memory_format=torch.channels_last)
         self.add_logits(scores, tgt)
 
+    def add_counts(self, counts):
+        """a table some kernel already filled for one batch (dsrl_sssr_tail_predict); a host tensor is taken as it is"""
+        if counts.numel() != 3 * self.num_classes + 2:
+            raise ValueError(f'counts of {counts.numel()} elements, expected {3 * self.num_classes + 2}')
+        self.batches.append(counts.reshape(-1).to(torch.int64))
+
     def table(self):
         return torch.stack(self.batches).cpu().double() if self.batches else torch.zeros((0, 3 * self.num_classes + 2), dtype=torch.float64)
 
@@ -67,6 +73,9 @@ class mIoU:
 
     def update_from_logits(self, logits, target):
         self._c.add_logits(logits, target)
+
+    def update_from_counts(self, counts):
+        self._c.add_counts(counts)
 
     def __call__(self):
         t, C = self._c.table(), self.num_classes
@@ -93,6 +102,9 @@ class Accuracy:
 
     def update_from_logits(self, logits, target):
         self._c.add_logits(logits, target)
+
+    def update_from_counts(self, counts):
+        self._c.add_counts(counts)
 
     def __call__(self):
         t, C = self._c.table(), self._c.num_classes

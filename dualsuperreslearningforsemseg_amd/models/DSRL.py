@@ -133,3 +133,44 @@ class DSRL(BaseModel):
             HF.begin_forward(self.training)
             backbone_features, lowlevel_features = self.feature_extractor['backbone'](x)      # DSRL.py:161
             return self.forward_head(backbone_features, lowlevel_features)
+
+    def predict_head(self, backbone_features: t.Tensor, lowlevel_features: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None):
+        """Inference counterpart of forward_head: the SSSR branch in eval mode down to the bilinear x2 of `upsample16_pred`, then its ConvTranspose ->
+        BatchNorm -> ReLU -> ConvTranspose tail and the arg-max as one kernel (functional.sssr_tail_predict) -> (pred uint8 (N,H,W), counts, ce).
+        With `target` (N,H,W): `counts` is the int64 table of dsrl_seg_metrics of this batch (metrices.mIoU / Accuracy.update_from_counts) and `ce` the
+        0-d CrossEntropyLoss(ignore_index); both None otherwise.  `nan_flag` (int32 device scalar) collects bit 0 = NaN logit, bit 1 = label outside
+        the classes; nothing is read back here.  Neither the SISR decoder nor the feature transformers run, whatever the stage."""
+        if self.training:
+            raise HF.DsrlHipError('DSRL.predict* is inference: call model.eval() first')
+        with t.no_grad():
+            fe, dec = self.feature_extractor, self.SSSR_decoder
+            aspp_features = fe['aspp'](backbone_features)
+            h, w = aspp_features.shape[-2:]
+            aspp_features = HF.upsample_bilinear_ac(aspp_features, (4 * h, 4 * w))            # DSRL.py:163
+            cat_features = HF.cat_channels([aspp_features, fe['shortcut_conv'](lowlevel_features)])    # DSRL.py:164-165
+            up = dec['upsample16_pred']
+            y = up[0](dec['cls_conv'](dec['cat_conv'](cat_features)))                          # DSRL.py:168-170 up to the bilinear x2
+            counts = None
+            if target is not None:
+                counts = t.zeros(3 * up[6].out_channels + 2, dtype=t.int64, device=y.device)
+            pred, ce = HF.sssr_tail_predict(y, up[2], up[3], up[6], target=target, ignore_index=ignore_index, counts=counts, nan_flag=nan_flag)
+        return pred, counts, ce
+
+    def predict(self, x: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None):
+        """Class map of a batch: (pred, counts or None, ce or None), see predict_head.  Runs under no_grad and raises in train mode.  Without a
+        `nan_flag` of the caller's the flag is read back here and a NaN logit or an out-of-range label raises; a caller that passes one reads it when
+        it chooses to (command_handlers.benchmark: once, after the last batch)."""
+        if self.training:
+            raise HF.DsrlHipError('DSRL.predict* is inference: call model.eval() first')
+        own = nan_flag is None
+        with t.no_grad():
+            if own:
+                nan_flag = t.zeros((), dtype=t.int32, device=x.device)
+            HF.nan_check_(nan_flag, x)          # a NaN pixel would not reach the logits: the first ReLU (fmaxf) maps it to 0
+            backbone_features, lowlevel_features = self.feature_extractor['backbone'](x)
+            out = self.predict_head(backbone_features, lowlevel_features, target, ignore_index, nan_flag)
+        if own:
+            bits = int(nan_flag.item())
+            if bits:
+                raise HF.DsrlHipError('DSRL.predict: ' + ' and '.join(m for b, m in ((1, 'NaN in the input or the logits'), (2, 'labels outside the classes')) if bits & b))
+        return out

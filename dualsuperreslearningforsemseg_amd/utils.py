@@ -1,0 +1,29 @@
+"""Host-side helpers of the inference commands (the reference keeps theirs in utils.py)."""
+import numpy as np
+import torch as t
+
+
+def load_checkpoint_or_weights(filename, map_location='cpu'):
+    """A `.weights` or `.checkpoint` file written by train_or_resume: a dict with at least 'model_state_dict'."""
+    d = t.load(filename, map_location=map_location)
+    if not isinstance(d, dict) or 'model_state_dict' not in d:
+        raise RuntimeError(f"'{filename}' holds no 'model_state_dict': not a .weights / .checkpoint file of this project")
+    return d
+
+
+def make_input_output_visualization(input_image, output_map, class_rgb_color, blend_factor=0.4):
+    """input_image (3,H,W) uint8, output_map (H,W) of class labels, class_rgb_color {label: (r, g, b)} -> (3,H,3W) uint8:
+    input | class colours | overlay, overlay = uint8(min((1 - blend_factor) * input + blend_factor * colour, 255)) evaluated in float64.
+    Labels the palette does not name are drawn black.  numpy on the host: 6 MB per 1024x2048 image, not a hot path."""
+    input_image = np.asarray(input_image)
+    output_map = np.asarray(output_map)
+    assert input_image.ndim == 3 and output_map.ndim == 2 and input_image.shape[-2:] == output_map.shape, (input_image.shape, output_map.shape)
+    assert 0.0 < blend_factor < 1.0
+    input_image = input_image.astype(np.uint8)
+    palette = np.zeros((256, input_image.shape[0]), dtype=np.uint8)         # one 256-entry look-up table per channel
+    for label, rgb in class_rgb_color.items():
+        palette[int(label) & 0xff] = rgb
+    colours = np.ascontiguousarray(palette[output_map.astype(np.uint8)].transpose(2, 0, 1))
+    blend = (1. - blend_factor) * input_image.astype(np.float64) + blend_factor * colours.astype(np.float64)
+    overlay = np.minimum(blend, 255.).astype(np.uint8)
+    return np.concatenate((input_image, colours, overlay), axis=2)

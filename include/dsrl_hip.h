@@ -489,6 +489,26 @@ int dsrl_prof_read(int family, int64_t* launches, double* total_ms, double* tota
 int dsrl_prof_read_bytes(int family, double* total_bytes);
 const char* dsrl_prof_kernel_name(int family);
 
+/* ------------------------------------------------------------------------------------------------
+ * inference: the eval-mode SSSR tail (DSRL.py:53-69 after the bilinear x2) as one launch that ends in class indices (csrc/predict.hip)
+ *   x (N,H,W,Cin) pixel-major with pixel stride ldx -> ConvTranspose2d k2 s2 w1 (Cin,Cmid,2,2), no bias -> fmaf(v, gamma * invstd, beta - mean * gamma * invstd)
+ *   (the arithmetic of bn_apply) -> ReLU -> ConvTranspose2d k2 s2 w2 (Cmid,Cout,2,2) + bias2 -> pred (N,4H,4W) = lowest index among the maximal logits.
+ *   fp32 products and accumulation whatever the conv precision mode says; neither the mid activations nor the logits are written to memory.
+ *   target (N,4H,4W) given: counts[3*Cout+2] (nullable) gets what a seg_metrics call on the same predictions would ADD (pixels whose target is
+ *   ignore_index or >= Cout excluded; one 64-bit atomic per block and counter), ce_out[2] (nullable) = mean nn.CrossEntropyLoss(ignore_index)
+ *   of the logits and the number of counted pixels, reduced through per-block partials in ws in a fixed order (bit-identical run to run).
+ *   nan_flag (nullable): |= 1 for a NaN logit or a NaN in front of the ReLU (which maps it to 0, as bn_apply does), |= 2 for a label outside [0,Cout) that is not ignore_index (which also makes ce_out NaN).
+ *   pred is written for every pixel.  pred, target and x must be 4-byte aligned; ws 8-byte aligned (only read when ce_out is given).
+ * _supported: 1 for Cin = Cmid = Cout = 19 and any N, H, W >= 1 with N*H*W*16 <= 2^31 - 1 (output pixels are indexed in 32 bits per image batch),
+ *   0 otherwise; pure host code.  _workspace_bytes depends on the shape only and holds for every launch of that shape.
+ * ---------------------------------------------------------------------------------------------- */
+int dsrl_sssr_tail_predict_supported(int N, int H, int W, int Cin, int Cmid, int Cout);
+size_t dsrl_sssr_tail_predict_workspace_bytes(int N, int H, int W);
+int dsrl_sssr_tail_predict(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                           const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2 /*nullable*/,
+                           uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index, unsigned long long* counts /*nullable*/,
+                           float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,165 @@
+#!/usr/bin/env python3
+"""Inference tail, A/B in one process: A = the unfused way to a class map (upsample16_pred[2:] modules in eval mode + torch.argmax; with a target also
+dsrl_seg_metrics + HF.cross_entropy), B = functional.sssr_tail_predict (one launch).  Alternating windows of >= --window seconds of device work each,
+device events around every window, after a warm-up of both sides at that shape.  Bytes and FLOPs are counted from the shapes here; the floor of B is
+the larger of FLOPs / fp32 matrix rate and bytes / HBM rate.  One more table: DSRL.predict against DSRL.forward + arg-max for the whole stage-1 model.
+
+    python tools/predict_bench.py [--out FILE] [--window 0.5] [--rounds 3]
+"""
+import argparse
+import math
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from dualsuperreslearningforsemseg_amd import functional as HF                        # noqa: E402
+from dualsuperreslearningforsemseg_amd.datasets.Cityscapes import settings as CS       # noqa: E402
+from dualsuperreslearningforsemseg_amd.metrices import _Counts                         # noqa: E402
+from dualsuperreslearningforsemseg_amd.models.DSRL import DSRL                         # noqa: E402
+from dualsuperreslearningforsemseg_amd.nn_modules import HipSequential                 # noqa: E402
+
+NC = 19
+HBM_BPS, F32_MATRIX_FLOPS = 6.29e12, 155e12            # measured rates of the MI355X (MFMA f32 16x16x4 / 32x32x2)
+MACS_PER_PIXEL = NC * 4 * NC + 4 * NC * 4 * NC           # 2x2 mid pixels, then 2x2 logits of each: 7220
+
+
+def window(fn, seconds):
+    """-> ms per call over one window of at least `seconds` of device work"""
+    e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    e[0].record()
+    for _ in range(5):
+        fn()
+    e[1].record()
+    torch.cuda.synchronize()
+    n = max(5, int(math.ceil(seconds * 1e3 / max(e[0].elapsed_time(e[1]) / 5, 1e-3))))
+    e[0].record()
+    for _ in range(n):
+        fn()
+    e[1].record()
+    torch.cuda.synchronize()
+    return e[0].elapsed_time(e[1]) / n
+
+
+def peak_bytes(fn):
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    out = fn()
+    torch.cuda.synchronize()
+    rise = torch.cuda.max_memory_allocated() - before
+    del out
+    return rise
+
+
+def ab(a, b, seconds, rounds):
+    for _ in range(3):
+        a(); b()
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    for _ in range(rounds):
+        ta.append(window(a, seconds)); tb.append(window(b, seconds))
+    return ta, tb
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--window', type=float, default=0.5)
+    ap.add_argument('--rounds', type=int, default=3)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), 'predict_bench.py measures on the GPU only'
+    dev = torch.device('cuda:0')
+    lines = []
+
+    def say(s=''):
+        print(s, flush=True)
+        lines.append(s)
+
+    torch.manual_seed(7)
+    up = DSRL._define_SSSR_decoder(256, 48, 256, NC)['upsample16_pred'].to(dev).eval()
+    with torch.no_grad():
+        up[3].running_mean.normal_(0, 0.1); up[3].running_var.uniform_(0.5, 1.5)
+    tail = HipSequential(*list(up)[2:]).eval()
+    say(f'SSSR inference tail, {torch.cuda.get_device_name(0)}: A = ConvT -> BN/ReLU -> ConvT modules + torch.argmax (+ dsrl_seg_metrics + HF.cross_entropy with a target), '
+        f'B = dsrl_sssr_tail_predict')
+    say(f'windows of >= {args.window} s per side, {args.rounds} alternations A B A B ..; times in us per call: mean [each window]; rates of B from the bytes / FLOPs '
+        f'the algorithm needs; floor = max(FLOPs / {F32_MATRIX_FLOPS / 1e12:.0f} TF, bytes / {HBM_BPS / 1e12:.2f} TB/s)')
+    say()
+    losses = []
+    for with_target in (False, True):
+        for (N, H, W) in ((1, 128, 256), (8, 128, 256), (1, 256, 512), (8, 256, 512)):
+            px = N * H * W
+            x = torch.randn(N, NC, H, W, device=dev).contiguous(memory_format=torch.channels_last)
+            target = torch.randint(0, NC, (N, 4 * H, 4 * W), device=dev, dtype=torch.uint8) if with_target else None
+            if with_target:
+                target[torch.rand(target.shape, device=dev) < 0.1] = 255
+            counter = _Counts(NC)
+
+            def a():
+                with torch.no_grad():
+                    logits = tail(x)
+                    pred = torch.argmax(logits, dim=1)
+                    if not with_target:
+                        return pred
+                    counter.batches = []
+                    counter.add_logits(logits, target)
+                    return pred, counter.batches[0], HF.cross_entropy(logits, target, 255)
+
+            def b():
+                if not with_target:
+                    return HF.sssr_tail_predict(x, up[2], up[3], up[6])
+                counts = torch.zeros(3 * NC + 2, dtype=torch.int64, device=dev)
+                return HF.sssr_tail_predict(x, up[2], up[3], up[6], target=target, counts=counts), counts
+
+            ta, tb = ab(a, b, args.window, args.rounds)
+            ma, mb = sum(ta) / len(ta), sum(tb) / len(tb)
+            mem_a, mem_b = peak_bytes(a), peak_bytes(b)
+            logit_b = 16 * px * NC * 4
+            bytes_a = px * NC * 4 + 4 * px * NC * 4 + 2 * 4 * px * NC * 4 + 4 * px * NC * 4 + logit_b + logit_b + 16 * px * 8
+            bytes_b = px * NC * 4 + 16 * px
+            if with_target:
+                bytes_a += 2 * (logit_b + 16 * px)
+                bytes_b += 16 * px
+            flops = 2.0 * MACS_PER_PIXEL * px
+            t_f, t_m = flops / F32_MATRIX_FLOPS, bytes_b / HBM_BPS
+            floor, bound = max(t_f, t_m), 'fp32 matrix rate' if t_f >= t_m else 'HBM'
+            verdict = 'B faster' if mb <= ma else 'B SLOWER'
+            if mb > ma:
+                losses.append((with_target, N, H, W))
+            say(f'(N,H,W)=({N},{H},{W}) target={"yes" if with_target else "no "}:  A {ma * 1e3:8.1f} us [{", ".join(f"{t * 1e3:.1f}" for t in ta)}]   '
+                f'B {mb * 1e3:8.1f} us [{", ".join(f"{t * 1e3:.1f}" for t in tb)}]   A/B {ma / mb:5.2f}  {verdict}')
+            say(f'      bytes A {bytes_a / 1e6:8.1f} MB  B {bytes_b / 1e6:6.1f} MB   FLOPs {flops / 1e9:6.2f} G   B achieves {bytes_b / (mb * 1e-3) / 1e9:7.1f} GB/s, '
+                f'{flops / (mb * 1e-3) / 1e12:6.2f} TFLOP/s   floor {floor * 1e6:6.1f} us ({bound}; {100 * floor / (mb * 1e-3):.0f} % of it reached)   '
+                f'peak memory A {mem_a / 1e6:8.1f} MB  B {mem_b / 1e6:6.2f} MB')
+    say()
+    say('whole model (stage 1, random weights, eval, 256x512 input): A = DSRL.forward + torch.argmax, B = DSRL.predict (caller-owned nan_flag: no readback)')
+    model = DSRL(1, CS).to(dev).to(memory_format=torch.channels_last).eval()
+    flag = torch.zeros((), dtype=torch.int32, device=dev)
+    for N in (1, 8):
+        img = torch.randn(N, 3, 256, 512, device=dev).contiguous(memory_format=torch.channels_last)
+
+        def a():
+            with torch.no_grad():
+                return torch.argmax(model(img)[0], dim=1)
+
+        def b():
+            return model.predict(img, nan_flag=flag)[0]
+
+        ta, tb = ab(a, b, args.window, args.rounds)
+        ma, mb = sum(ta) / len(ta), sum(tb) / len(tb)
+        if mb > ma:
+            losses.append(('model', N, 256, 512))
+        say(f'batch {N}:  A {ma:8.3f} ms [{", ".join(f"{t:.3f}" for t in ta)}]   B {mb:8.3f} ms [{", ".join(f"{t:.3f}" for t in tb)}]   A/B {ma / mb:5.3f}   '
+            f'peak memory A {peak_bytes(a) / 1e6:8.1f} MB  B {peak_bytes(b) / 1e6:8.1f} MB')
+    say()
+    say('rows where B is slower than A: ' + (', '.join(str(r) for r in losses) if losses else 'none'))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()
