@@ -4,5 +4,6 @@ from . import _lib, functional, nn_modules, ddp  # noqa: F401
 from .models import DSRL  # noqa: F401
 from .models.losses import FALoss  # noqa: F401
 from .models.modules import ASPP  # noqa: F401
+from .inference import CompiledPredictor, FrozenOperands, load_compiled_model  # noqa: F401
 
 __version__ = '0.1.0'

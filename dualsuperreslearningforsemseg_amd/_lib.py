@@ -131,6 +131,9 @@ PROTOTYPES = {
     'dsrl_sssr_tail_predict_supported': (i32, [i32] * 6),
     'dsrl_sssr_tail_predict_workspace_bytes': (sz, [i32] * 3),
     'dsrl_sssr_tail_predict': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, stream_t]),
+    'dsrl_fingerprint_segment_words': (i32, []),
+    'dsrl_fingerprint_segments': (i32, [fp, i64, fp, fp, fp, i32, stream_t]),
+    'dsrl_class_map_visualize': (i32, [fp, fp, fp, fp, fp, i32, i32, i32, i32, C.c_double, stream_t]),
     'dsrl_prepare_batch': (i32, [fp, fp, fp, C.POINTER(f32), C.POINTER(f32), fp, fp, fp, i32, i32, i32, i32, i32, stream_t]),
     'dsrl_augment_geometry': (i32, [fp, fp, fp, fp, fp, fp, i32, i32, i32, stream_t]),
     'dsrl_prepare_batch_augmented': (i32, [fp, fp, fp, C.POINTER(f32), C.POINTER(f32), fp, fp, fp, i32, i32, i32, i32, i32, fp, stream_t]),

@@ -3,7 +3,9 @@
 
 What differs by design: the model runs `DSRL.predict` (the SSSR tail, the arg-max, the metric counters and the loss in one kernel; no logits in
 memory), the batches come through the `loader_factory` protocol of train_or_resume (dataset['loader_factory'] when given, else the Cityscapes cache
-without augmentation, every sample), and the host reads the device ONCE, after the last batch, instead of copying every batch's logits back."""
+without augmentation, every sample), and the host reads the device ONCE, after the last batch, instead of copying every batch's logits back.
+`compiled_model=True` in other_args: `weights` names a file of the compile_model command and the batches run through inference.CompiledPredictor (the
+full batch and the last short one are two of its graph keys); the figures are the same."""
 import os
 from datetime import datetime
 
@@ -20,8 +22,11 @@ NOT_GPU = "this build runs on the MI355X only: use device='gpu' (the reference's
 
 def load_eval_model(weights, dataset_settings, device_obj):
     """Stage-1 DSRL in eval mode with the matching entries of the file's state dict (a stage-2/3 file carries more: strict=False, as the reference)."""
+    d = load_checkpoint_or_weights(weights, map_location='cpu')
+    if d.get('format') is not None:
+        raise RuntimeError(f"'{weights}' is a compiled model file (written by the compile_model command): pass compiled_model=True to read it")
     model = DSRL(stage=1, dataset_settings=dataset_settings).eval()
-    model.load_state_dict(load_checkpoint_or_weights(weights, map_location='cpu')['model_state_dict'], strict=False)
+    model.load_state_dict(d['model_state_dict'], strict=False)
     return model.to(device_obj).to(memory_format=t.channels_last)
 
 
@@ -44,20 +49,30 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
     device_obj = t.device('cuda', t.cuda.current_device())
     ds = dataset['settings']
     split = dataset.get('split', 'val')
-    model = load_eval_model(weights, ds, device_obj)
+    predictor = None
+    if other_args.get('compiled_model'):
+        from ..inference import load_compiled_model
+        model, predictor = load_compiled_model(weights, device_obj)          # frozen operands + hipGraph replay: the same class maps, counters and losses
+    else:
+        model = load_eval_model(weights, ds, device_obj)
+    predict = model.predict if predictor is None else predictor
     loader = split_loader(dataset, split, batch_size, device_obj, input_size)
 
     nan_flag = t.zeros((), dtype=t.int32, device=device_obj)
     ces, tables = [], []
-    for (input_image, _), (target, _) in loader:
-        _, counts, ce = model.predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag)
-        ces.append(ce)
-        tables.append(counts)
-    if not ces:
-        raise RuntimeError(f"the '{split}' split yielded no batch")
-    # the one device -> host read: losses, NaN flag and counters in a single float64 tensor (counters < 2^53: exact)
-    nb, nc = len(ces), ds.NUM_CLASSES
-    host = t.cat([t.stack(ces).double(), nan_flag.double().reshape(1), t.stack(tables).double().reshape(-1)]).cpu()
+    try:
+        for (input_image, _), (target, _) in loader:
+            _, counts, ce = predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag)
+            ces.append(ce)
+            tables.append(counts)
+        if not ces:
+            raise RuntimeError(f"the '{split}' split yielded no batch")
+        # the one device -> host read: losses, NaN flag and counters in a single float64 tensor (counters < 2^53: exact)
+        nb, nc = len(ces), ds.NUM_CLASSES
+        host = t.cat([t.stack(ces).double(), nan_flag.double().reshape(1), t.stack(tables).double().reshape(-1)]).cpu()
+    finally:
+        if predictor is not None:
+            predictor.release()             # drops the graphs and restores the conv arithmetic the file selected
     bits = int(host[nb].item())
     if bits:
         raise RuntimeError('benchmark: ' + ' and '.join(m for b, m in ((1, 'NaN in the input or the logits'), (2, 'labels outside the classes')) if bits & b))

@@ -3,7 +3,10 @@ command_handlers/test.py (same `test(...)` signature and file names).
 
 What differs by design: image files are normalised and resized to the model input by dsrl_prepare_batch, the align-corners transform the network
 was trained with (the reference's torchvision Resize here is a different one); the class map comes from `DSRL.predict`; the command is headless
-(no window, no wait for a key) and returns the files it wrote; there is no TorchScript, so `compiled_model` raises."""
+(no window, no wait for a key) and returns the files it wrote.  `compiled_model=True`: `weights` names a file written by the compile_model command
+(data, not TorchScript) and the class maps come from inference.CompiledPredictor - frozen operands and a hipGraph replay, the same bytes.  Either
+way the input | class colours | overlay panels are built on the device (utils.make_input_output_visualization_device): what crosses to the host
+per image is the finished uint8 panel, which PIL encodes."""
 import os
 
 import numpy as np
@@ -11,15 +14,15 @@ import torch as t
 
 from .. import consts, settings
 from ..models.transforms import DeviceBatchPreparation
-from ..utils import make_input_output_visualization
+from ..utils import make_input_output_visualization_device
 from .benchmark import NOT_GPU, load_eval_model, split_loader
 from .train_or_resume import isCUDAdevice
 
 
-def _save_png(chw, filename):
+def _save_png(hwc, filename):
     from PIL import Image
     os.makedirs(os.path.dirname(filename) or '.', exist_ok=True)
-    Image.fromarray(np.ascontiguousarray(chw.transpose(1, 2, 0)), mode='RGB').save(filename, format='PNG')
+    Image.fromarray(np.ascontiguousarray(hwc), mode='RGB').save(filename, format='PNG')
     print('Output image saved as: {0:s}.'.format(filename))
     return filename
 
@@ -28,15 +31,31 @@ def _save_png(chw, filename):
 def test(image_file, images_dir, dataset, output_dir, weights, device, compiled_model, **other_args):
     if not isCUDAdevice(device):
         raise RuntimeError(NOT_GPU)
+    data = None
     if compiled_model:
-        raise RuntimeError('compiled_model: TorchScript models are not supported by this build (the kernels are reached through ctypes)')
+        from ..inference import load_compiled_model, read_compiled_file
+        data = read_compiled_file(weights)                  # format, version and ABI are checked on the host, before any device work
     if not dataset:
         dataset = settings.DATASETS['cityscapes']          # the normalisation constants are not stored with the weights
     ds = dataset['settings']
     input_size = tuple(other_args.get('model_input_size', settings.MODEL_INPUT_SIZE))
     output_size = tuple(2 * v for v in input_size)
     device_obj = t.device('cuda', t.cuda.current_device())
-    model = load_eval_model(weights, ds, device_obj)
+    predictor = None
+    if compiled_model:
+        model, predictor = load_compiled_model(weights, device_obj, data=data)
+        predict = predictor
+    else:
+        model = load_eval_model(weights, ds, device_obj)
+        predict = model.predict
+    try:
+        return _run(predict, image_file, images_dir, dataset, ds, output_dir, device_obj, input_size, output_size)
+    finally:
+        if predictor is not None:
+            predictor.release()
+
+
+def _run(predict, image_file, images_dir, dataset, ds, output_dir, device_obj, input_size, output_size):
     written = []
 
     if image_file or images_dir:
@@ -48,26 +67,30 @@ def test(image_file, images_dir, dataset, output_dir, weights, device, compiled_
             with Image.open(name) as opened:
                 rgb = np.array(ImageOps.exif_transpose(opened).convert('RGB').resize((output_size[1], output_size[0]), resample=Image.BILINEAR),
                                dtype=np.uint8)
-            (input_image, _), _ = prepare(t.from_numpy(rgb).unsqueeze(0).to(device_obj))
-            pred, _, _ = model.predict(input_image)
-            vis = make_input_output_visualization(rgb.transpose(2, 0, 1), pred[0].cpu().numpy(), ds.CLASS_RGB_COLOR)
-            written.append(_save_png(vis, os.path.join(output_dir, os.path.splitext(os.path.basename(name))[0] + '.png')))
+            rgb_dev = t.from_numpy(rgb).unsqueeze(0).to(device_obj)
+            (input_image, _), _ = prepare(rgb_dev)
+            pred, _, _ = predict(input_image)
+            vis = make_input_output_visualization_device(rgb_dev, pred, ds.CLASS_RGB_COLOR)
+            written.append(_save_png(vis[0].cpu().numpy(), os.path.join(output_dir, os.path.splitext(os.path.basename(name))[0] + '.png')))
         return written
 
     loader = split_loader(dataset, dataset['split'], 1, device_obj, input_size)
     first, limit = int(dataset.get('starting_index', 0)), dataset.get('max_images')
-    mean = np.array(ds.MEAN).reshape(consts.NUM_RGB_CHANNELS, 1, 1)
-    std = np.array(ds.STD).reshape(consts.NUM_RGB_CHANNELS, 1, 1)
+    # the shown image, (std * x + mean) * 255 clipped, in float64 as three separately rounded element-wise passes: what numpy evaluated on the host
+    mean = t.tensor(np.array(ds.MEAN), dtype=t.float64, device=device_obj).reshape(1, 1, consts.NUM_RGB_CHANNELS)
+    std = t.tensor(np.array(ds.STD), dtype=t.float64, device=device_obj).reshape(1, 1, consts.NUM_RGB_CHANNELS)
     for i, ((input_image, input_org), (target, _)) in enumerate(loader):
         if i < first:
             continue
         if limit is not None and len(written) >= int(limit):
             break
-        pred, _, _ = model.predict(input_image)
-        shown = np.clip((std * input_org[0].float().cpu().numpy() + mean) * 255., 0., 255.).astype(np.uint8)
-        target_map, pred_map = target[0].cpu().numpy(), pred[0].cpu().numpy()
-        pred_map[target_map == ds.IGNORE_CLASS_LABEL] = ds.IGNORE_CLASS_LABEL
-        vis = np.concatenate((make_input_output_visualization(shown, target_map, ds.CLASS_RGB_COLOR),
-                              make_input_output_visualization(shown, pred_map, ds.CLASS_RGB_COLOR)), axis=1)
-        written.append(_save_png(vis, os.path.join(output_dir, str(i) + '.png')))
+        pred, _, _ = predict(input_image)
+        scaled = std * input_org[0].permute(1, 2, 0).to(t.float64)
+        scaled = (scaled + mean) * 255.
+        shown = t.clamp(scaled, 0., 255.).to(t.uint8)
+        # two panels, target above prediction; in the prediction the pixels the target ignores are drawn as ignored (the mask; a no-op for the target itself)
+        tgt = target[0].to(t.uint8)
+        vis = make_input_output_visualization_device(shown.unsqueeze(0).expand(2, -1, -1, -1), t.stack((tgt, pred[0])), ds.CLASS_RGB_COLOR,
+                                                     mask=t.stack((tgt, tgt)), ignore_index=ds.IGNORE_CLASS_LABEL)
+        written.append(_save_png(vis.reshape(-1, vis.shape[2], 3).cpu().numpy(), os.path.join(output_dir, str(i) + '.png')))
     return written

@@ -213,6 +213,41 @@ __global__ __launch_bounds__(256) void predict_ce_finalize_kernel(const double* 
     }
 }
 
+// Fingerprint of frozen tensors (inference.FrozenOperands): one block per table row {pointer, 32-bit words}, h = sum over the words of
+// (w + 1) * K * (2 i + 1) modulo 2^64 - every single-word change moves it (the factor is odd), and the sum does not depend on the order the threads
+// add in.  With `expect` the block compares instead of (or besides) storing and raises `bit` in `flag` on a difference.
+constexpr int kFingerprintSegWords = 32768;
+__global__ __launch_bounds__(256) void fingerprint_segments_kernel(const long long* __restrict__ table, unsigned long long* __restrict__ out,
+                                                                   const unsigned long long* __restrict__ expect, int* __restrict__ flag, int bit) {
+    __shared__ unsigned long long sh[4];
+    const unsigned* p = reinterpret_cast<const unsigned*>(table[2 * blockIdx.x]);
+    const unsigned n = (unsigned)table[2 * blockIdx.x + 1];
+    constexpr unsigned long long K = 0x9E3779B97F4A7C15ull;
+    unsigned long long h = 0ull;
+    unsigned done = 0u;
+    if ((reinterpret_cast<uintptr_t>(p) & 15u) == 0u) {
+        const unsigned n4 = n >> 2;
+        const uint4* p4 = reinterpret_cast<const uint4*>(p);
+        for (unsigned i = threadIdx.x; i < n4; i += 256u) {
+            const uint4 v = p4[i];
+            const unsigned long long i0 = 8ull * i + 1ull;         // 2 (4 i) + 1
+            h += ((unsigned long long)v.x + 1ull) * (K * i0) + ((unsigned long long)v.y + 1ull) * (K * (i0 + 2ull)) +
+                 ((unsigned long long)v.z + 1ull) * (K * (i0 + 4ull)) + ((unsigned long long)v.w + 1ull) * (K * (i0 + 6ull));
+        }
+        done = n4 << 2;
+    }
+    for (unsigned i = done + threadIdx.x; i < n; i += 256u) h += ((unsigned long long)p[i] + 1ull) * (K * (2ull * i + 1ull));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) h += (unsigned long long)__shfl_xor((long long)h, o, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = h;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        h = sh[0] + sh[1] + sh[2] + sh[3];
+        if (out != nullptr) out[blockIdx.x] = h;
+        if (expect != nullptr && flag != nullptr && expect[blockIdx.x] != h) atomicOr(flag, bit);
+    }
+}
+
 int predict_blocks(long long P) { return (int)std::max<long long>(1, std::min<long long>(kPredMaxBlocks, ceil_div(ceil_div(P, 16), 4))); }
 
 }  // namespace
@@ -263,4 +298,16 @@ extern "C" int dsrl_sssr_tail_predict(const float* x, int ldx, int N, int H, int
         return launch_status("predict_ce_finalize_kernel");
     }
     return DSRL_OK;
+}
+
+extern "C" int dsrl_fingerprint_segment_words(void) { return kFingerprintSegWords; }
+
+extern "C" int dsrl_fingerprint_segments(const int64_t* table, int64_t nseg, uint64_t* out, const uint64_t* expect, int* flag, int bit, dsrl_stream_t stream) {
+    DSRL_REQUIRE(table && nseg > 0 && nseg <= INT_MAX && (out || (expect && flag)), DSRL_E_BADARG,
+                 "fingerprint_segments: null table, no rows, or neither an output nor (expect, flag)");
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    hipLaunchKernelGGL(fingerprint_segments_kernel, dim3((unsigned)nseg), dim3(256), 0, st, (const long long*)table, (unsigned long long*)out,
+                       (const unsigned long long*)expect, flag, bit);
+    return launch_status("fingerprint_segments_kernel");
 }

@@ -149,6 +149,33 @@ def amax_slot(device):
     return slot
 
 
+class amax_private:
+    """with amax_private(arena): ... - every amax record asked for inside the block comes out of `arena`, a step-arena of the caller's own
+    ([tensor from _new_arena, next free slot, generation, pinned]): inference.CompiledPredictor captures each of its graphs inside one, with the
+    arena's zero fill as the graph's first node, so that a replay maxes into records of its own that are zero when it starts.  The step arena of
+    the training steps and the loose arena are neither read nor written; on exit they are what they were."""
+
+    def __init__(self, arena):
+        self.arena = arena
+        self.device = arena[0].device
+
+    def __enter__(self):
+        self.saved = (_amax_arena.get(self.device), self.device in _amax_open)
+        _amax_arena[self.device] = self.arena
+        _amax_open.add(self.device)
+        return self.arena
+
+    def __exit__(self, *exc):
+        prev, was_open = self.saved
+        if prev is None:
+            _amax_arena.pop(self.device, None)
+        else:
+            _amax_arena[self.device] = prev
+        if not was_open:
+            _amax_open.discard(self.device)
+        return False
+
+
 def f16_mode():
     """The conv kernels scale their operands by per-tensor powers of two (amax records): 'f16x3' and 'f16x1'."""
     return _conv_precision_code() >= 4
@@ -945,8 +972,10 @@ class _BNAct(torch.autograd.Function):
                      ws.data_ptr(), ws.numel(), ya_ptr, st)
         else:
             mean = running_mean
-            invstd = torch.empty(Cc, device=x.device, dtype=torch.float32)
-            call('dsrl_bn_invstd_from_var', running_var.data_ptr(), Cc, float(eps), invstd.data_ptr(), st)
+            invstd = frozen_invstd(running_var, eps)
+            if invstd is None:
+                invstd = torch.empty(Cc, device=x.device, dtype=torch.float32)
+                call('dsrl_bn_invstd_from_var', running_var.data_ptr(), Cc, float(eps), invstd.data_ptr(), st)
             call('dsrl_bn_apply', x.data_ptr(), ldx, y.data_ptr(), Cc, P, Cc, mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                  res_ptr, ldr, int(relu), float(drop_p), int(seed), int(rng_stream), ya_ptr, st)
         if ya is not None:
@@ -1016,11 +1045,22 @@ class _BNAct(torch.autograd.Function):
 bn_res_stats_enabled = knob('DSRL_BN_RES_STATS', True)      # 0: the downsample BatchNorm reduces its own backward sums (until round 5)
 
 
+def frozen_invstd(running_var, eps):
+    """1 / sqrt(var + eps) of an eval-mode BatchNorm as inference.FrozenOperands computed it once (by dsrl_bn_invstd_from_var: the same bits), if one
+    is attached to the buffer and still describes it - else None, and the caller launches that kernel itself."""
+    held = getattr(running_var, '_dsrl_invstd', None)
+    if held is not None and held[1] == float(eps) and held[2] == running_var._version and held[0].device == running_var.device:
+        return held[0]
+    return None
+
+
 def batch_norm_act(x, bn, relu=False, drop_p=0.0, seed=0, rng_stream=0, residual=None, residual_grad_slot=None, stats=None, out_link=None, res_link=None):
     """BatchNorm2d `bn` (an nn.BatchNorm2d holding the parameters/buffers) + optional residual add, ReLU, Dropout."""
     training = bn.training or bn.running_mean is None
     if training and bn.running_mean is not None:
         bn._dsrl_batches = getattr(bn, '_dsrl_batches', 0) + 1      # flushed into num_batches_tracked by HipBatchNorm2d.state_dict
+        if getattr(bn.running_var, '_dsrl_invstd', None) is not None:
+            bn.running_var._dsrl_invstd = None                      # the kernel rewrites the statistics through a raw pointer: a frozen invstd is stale
     momentum = 0.1 if bn.momentum is None else bn.momentum
     return _BNAct.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps, relu,
                         drop_p if training or drop_p == 0.0 else 0.0, seed, rng_stream, residual, residual_grad_slot if residual is not None else None,
@@ -1780,8 +1820,10 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
                    for m in (convt1, convt2))
         if k2s2 and convt1.bias is None and cquery('dsrl_sssr_tail_predict_supported', N, H, W, Ci, Cm, Co):
             st = _stream()
-            invstd = torch.empty(Cm, device=x.device, dtype=torch.float32)
-            call('dsrl_bn_invstd_from_var', bn.running_var.data_ptr(), Cm, float(bn.eps), invstd.data_ptr(), st)
+            invstd = frozen_invstd(bn.running_var, bn.eps)
+            if invstd is None:
+                invstd = torch.empty(Cm, device=x.device, dtype=torch.float32)
+                call('dsrl_bn_invstd_from_var', bn.running_var.data_ptr(), Cm, float(bn.eps), invstd.data_ptr(), st)
             pred = torch.empty((N, 4 * H, 4 * W), device=x.device, dtype=torch.uint8)
             ce = torch.empty(2, device=x.device, dtype=torch.float32) if target is not None else None
             ws = _ws(cquery('dsrl_sssr_tail_predict_workspace_bytes', N, H, W) if ce is not None else 0, x)
@@ -1806,6 +1848,50 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
             lg, ld = pm(logits)
             call('dsrl_seg_metrics', lg.data_ptr(), ld, target.data_ptr(), N * 16 * H * W, Co, int(ignore_index), counts.data_ptr(), _stream())
         return pred, cross_entropy(logits, target, int(ignore_index))
+
+
+_palettes = {}
+
+
+def palette_tensor(class_rgb_color, device):
+    """uint8 [256][3] device table label -> colour of a {label: (r, g, b)} dict, labels it does not name black (as utils.make_input_output_visualization
+    builds it on the host); one per (palette, device)."""
+    key = (tuple(sorted((int(k) & 0xff, tuple(int(c) for c in v)) for k, v in class_rgb_color.items())), str(device))
+    tab = _palettes.get(key)
+    if tab is None:
+        host = torch.zeros((256, 3), dtype=torch.uint8)
+        for label, rgb in class_rgb_color.items():
+            host[int(label) & 0xff] = torch.tensor([int(c) for c in rgb], dtype=torch.uint8)
+        tab = _palettes[key] = host.to(device)
+    return tab
+
+
+def class_map_visualize(rgb, classes, palette, mask=None, ignore_index=255, blend_factor=0.4, out=None):
+    """The test command's panel on the device (include/dsrl_hip.h: dsrl_class_map_visualize): rgb uint8 (N,H,W,3), classes uint8 (N,H,W), palette uint8
+    [256][3] (palette_tensor), mask uint8 (N,H,W) or None (where mask == ignore_index the class becomes ignore_index) -> uint8 (N,H,3W,3):
+    input | class colours | overlay, byte for byte utils.make_input_output_visualization."""
+    _need_gpu(rgb, classes, palette, mask)
+    for t_, name in ((rgb, 'rgb'), (classes, 'classes'), (palette, 'palette'), (mask, 'mask')):
+        if t_ is not None and t_.dtype != torch.uint8:
+            raise DsrlHipError(f'class_map_visualize: {name} must be uint8, got {t_.dtype}')
+    if rgb.dim() != 4 or rgb.shape[3] != 3 or classes.dim() != 3 or tuple(classes.shape) != tuple(rgb.shape[:3]):
+        raise DsrlHipError(f'class_map_visualize: rgb {tuple(rgb.shape)} must be (N,H,W,3) and classes {tuple(classes.shape)} (N,H,W)')
+    if mask is not None and tuple(mask.shape) != tuple(classes.shape):
+        raise DsrlHipError(f'class_map_visualize: mask {tuple(mask.shape)} does not match classes {tuple(classes.shape)}')
+    if tuple(palette.shape) != (256, 3):
+        raise DsrlHipError(f'class_map_visualize: palette must be [256][3], got {tuple(palette.shape)}')
+    if not 0.0 < float(blend_factor) < 1.0:
+        raise DsrlHipError('class_map_visualize: 0 < blend_factor < 1')
+    rgb, classes, palette = rgb.contiguous(), classes.contiguous(), palette.contiguous()
+    mask = None if mask is None else mask.contiguous()
+    N, H, W, _ = rgb.shape
+    if out is None:
+        out = torch.empty((N, H, 3 * W, 3), device=rgb.device, dtype=torch.uint8)
+    elif tuple(out.shape) != (N, H, 3 * W, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != rgb.device:
+        raise DsrlHipError('class_map_visualize: out must be a contiguous uint8 (N,H,3W,3) tensor on the same device')
+    call('dsrl_class_map_visualize', rgb.data_ptr(), classes.data_ptr(), None if mask is None else mask.data_ptr(), palette.data_ptr(), out.data_ptr(),
+         N, H, W, int(ignore_index), float(blend_factor), _stream())
+    return out
 
 
 def conv2d_inbounds_macs(N, H, W, Cc, K, R, S, stride, pad, dil):

@@ -1,0 +1,442 @@
+"""Compiled inference: what an eval-mode model can prepare once because its weights are frozen, and its forward pass as a replayed hipGraph.
+
+  * FrozenOperands(model): for every conv filter the kernels take them for, the amax record, the pre-split form and the fp16 planes of the forward layout
+    (the three batched kernels ddp.FlatParams runs once per training step, here once per model), and 1 / sqrt(var + eps) of every eval BatchNorm.
+    functional.py finds them through the hooks it already reads (`w._dsrl_arena`, `_dsrl_wamax`, `_dsrl_wsplit`, `_dsrl_wplanes`;
+    `running_var._dsrl_invstd`), so `model.predict` and `model.forward` launch the same conv kernels on the same values, without the per-call filter
+    measurement, the in-kernel filter split and the ~105 one-block invstd launches.
+  * CompiledPredictor (DSRL.compile_predict): `DSRL.predict` captured per (N, H, W, with target, conv arithmetic) into a hipGraph and replayed - about a
+    thousand eager launches become one hipGraphLaunch.  The contract is bit identity with eager `predict`.
+  * load_compiled_model: the file the compile_model command writes (data only) -> (model, CompiledPredictor).
+"""
+import sys
+
+import torch
+
+from . import functional as HF
+from ._lib import DsrlHipError, call, load as _load_lib, query
+
+FORMAT, FORMAT_VERSION = 'dsrl-hip-compiled', 1
+STALE_BIT = 4           # bit of the NaN flag word the device-side fingerprint check raises (bit 0: NaN, bit 1: label outside the classes)
+_private_gen = [1 << 40]
+
+
+def _align(n, a=4):
+    return (n + a - 1) // a * a
+
+
+class FrozenOperands:
+    """Prepared operands of an eval-mode model on the GPU; see the module docstring.  Inference only: it stands where functional.py expects a
+    ddp.FlatParams arena, and everything a backward pass asks of one raises."""
+
+    def __init__(self, model):
+        from .nn_modules import HipConv2d
+        params = list(model.parameters())
+        if not params or not params[0].is_cuda:
+            raise DsrlHipError('FrozenOperands: the model must be on the HIP device')
+        if model.training or any(m.training for m in model.modules()):
+            raise DsrlHipError('FrozenOperands: inference only - call model.eval() first')
+        for p in params:
+            if getattr(p, '_dsrl_arena', None) is not None:
+                raise DsrlHipError('FrozenOperands: a parameter of this model is bound to a ddp.FlatParams arena or to another FrozenOperands (release() that one first)')
+        self.model, self.device = model, params[0].device
+        self.released = False
+        self.precision = None
+        self.wt_valid = self.wt_fp32_valid = self.split_valid = self.planes_valid = False
+        self._sets = {}             # conv arithmetic -> the operand buffers prepared for it (a captured graph keeps reading the set it was captured with)
+        self._filters = []          # (weight, K, Kp, R*S, C)
+        for m in model.modules():
+            if isinstance(m, HipConv2d):
+                w = m.weight
+                K, C, R, S = w.shape
+                if C % 4 == 0 and HF._is_krsc(w):           # the conditions of ddp.FlatParams: the RGB stem and the C -> 1 transformers have no such operands
+                    self._filters.append((w, K, (K + 3) & ~3, R * S, C))
+        self._bns = [m for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.running_var is not None]
+        # what every call compares: (dict that holds the tensor, its name, address, version counter) of every parameter and buffer
+        self._watch = []
+        for mod in model.modules():
+            for held in (mod._parameters, mod._buffers):
+                for name, t in held.items():
+                    if t is not None:
+                        self._watch.append((held, name, t.data_ptr(), t._version))
+        self._modules = list(model.modules())
+        with torch.no_grad(), torch.cuda.device(self.device):
+            self._freeze_invstd()
+            self._fingerprint()
+            self.attach()
+
+    # ------------------------------------------------------------------ what backward asks of an arena
+    def _inference_only(self, *_a, **_k):
+        raise DsrlHipError('FrozenOperands is inference-only: a backward pass reached a filter whose operands are frozen - call release() '
+                           '(CompiledPredictor.release()) before training this model')
+
+    claim = written = zero_grad = settle_grads = finish_reduction = sgd_step = refresh_transposed_filters = _inference_only
+
+    # ------------------------------------------------------------------ BatchNorm constants
+    def _freeze_invstd(self):
+        total = sum(_align(m.num_features) for m in self._bns)
+        self._invstd = torch.empty(max(total, 4), device=self.device, dtype=torch.float32)
+        off, st = 0, HF._stream()
+        self._invstd_held = []
+        for m in self._bns:
+            rv, C = m.running_var, m.num_features
+            view = self._invstd[off:off + C]
+            off += _align(C)
+            call('dsrl_bn_invstd_from_var', rv.data_ptr(), C, float(m.eps), view.data_ptr(), st)      # the kernel every eval forward runs: the same bits
+            held = (view, float(m.eps), rv._version)
+            rv._dsrl_invstd = held
+            self._invstd_held.append((m, held))
+
+    # ------------------------------------------------------------------ device-side fingerprint of every float parameter and buffer
+    def _fingerprint(self):
+        seg = int(query('dsrl_fingerprint_segment_words'))
+        rows = []
+        for held, name, ptr, _ in self._watch:
+            t = held[name]
+            if t.dtype != torch.float32 or not t.is_cuda or t.numel() == 0:
+                continue
+            if not (t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))):
+                continue                    # dense tensors only (contiguous or channels_last): numel() words from data_ptr()
+            n = t.numel()
+            for a in range(0, n, seg):
+                rows.append([ptr + 4 * a, min(seg, n - a)])
+        self._fp_table = torch.tensor(rows, dtype=torch.int64, device=self.device)
+        self._fp_rows = len(rows)
+        self._fp = torch.empty(len(rows), dtype=torch.int64, device=self.device)
+        call('dsrl_fingerprint_segments', self._fp_table.data_ptr(), self._fp_rows, self._fp.data_ptr(), None, None, 0, HF._stream())
+
+    def check_values(self, flag):
+        """Enqueues the comparison of every float parameter and buffer with its fingerprint at freeze time: bit 2 (value 4) of the int32 device scalar
+        `flag` is raised on a difference.  A write through `.data` or a raw pointer moves neither address nor version counter; this finds it.  One
+        launch that reads the whole model once, so CompiledPredictor runs it only in the form of the call that reads its flag back anyway."""
+        call('dsrl_fingerprint_segments', self._fp_table.data_ptr(), self._fp_rows, None, self._fp.data_ptr(), flag.data_ptr(), STALE_BIT, HF._stream())
+
+    # ------------------------------------------------------------------ filter operands
+    def _prepare(self, precision):
+        """amax records, w_split and w_planes of every filter under the CURRENT conv arithmetic (`precision`), one launch of each batched kernel."""
+        dev, W = self.device, HF.AMAX_WORDS
+        ents = self._filters
+        s = {'amax': torch.zeros(max(len(ents), 1) * W, device=dev, dtype=torch.int32), 'split': None, 'planes': None, 'wsplit': {}, 'wplanes': {}}
+        if not ents:
+            return s
+        s['split'] = torch.empty(sum(_align(w.numel()) for w, *_ in ents), device=dev, dtype=torch.float32)
+        rows_a, rows_s, tiles, off = [], [], 0, 0
+        for i, (w, K, Kp, RS, C) in enumerate(ents):
+            ct = (C + 31) // 32
+            rec = s['amax'].data_ptr() + 4 * W * i
+            wsp = s['split'][off:off + w.numel()]
+            off += _align(w.numel())
+            s['wsplit'][id(w)] = wsp
+            rows_a.append([w.data_ptr(), 0, K, Kp, RS, C, tiles, ct, rec, 0])               # no transposed copy: the launch only measures
+            rows_s.append([w.data_ptr(), 0, K, Kp, RS, C, tiles, ct, rec, wsp.data_ptr()])  # no transposed split form: inference has no data gradients
+            tiles += RS * ct * ((Kp + 31) // 32)
+        st = HF._stream()
+        ta = torch.tensor(rows_a, dtype=torch.int64, device=dev)
+        ts = torch.tensor(rows_s, dtype=torch.int64, device=dev)
+        call('dsrl_conv2d_transpose_filters_batched', ta.data_ptr(), len(rows_a), tiles, st)
+        call('dsrl_conv2d_split_filters_batched', ts.data_ptr(), len(rows_s), tiles, st)
+        # fp16 planes [K][R][S][C] (two for 'f16x3'; 'f16x1' reads the first): channel counts multiples of 8, as ddp.FlatParams / functional.filter_planes
+        pl = [(i, e) for i, e in enumerate(ents) if e[1] % 8 == 0 and e[4] % 8 == 0] if HF.planes_mode != 'off' else []
+        if pl:
+            lo = lambda n: int(HF.cquery('dsrl_planes_lo_offset', n))        # noqa: E731
+            s['planes'] = torch.empty(sum(2 * lo(e[0].numel()) for _, e in pl), device=dev, dtype=torch.uint8)
+            rows_p, ptiles, poff = [], 0, 0
+            for i, (w, K, Kp, RS, C) in pl:
+                nb = 2 * lo(w.numel())
+                wp = s['planes'][poff:poff + nb]
+                poff += nb
+                s['wplanes'][id(w)] = wp
+                ct = (C + 31) // 32
+                rows_p.append([w.data_ptr(), 0, K, K, RS, C, ptiles, ct, s['amax'].data_ptr() + 4 * W * i, wp.data_ptr()])
+                ptiles += RS * ct * ((K + 31) // 32)
+            tp = torch.tensor(rows_p, dtype=torch.int64, device=dev)
+            call('dsrl_conv2d_filter_planes_batched', tp.data_ptr(), len(rows_p), ptiles, st)
+            s['tables'] = (ta, ts, tp)
+        else:
+            s['tables'] = (ta, ts)
+        return s
+
+    def attach(self, precision=None):
+        """Presents the operands of conv arithmetic `precision` (default: the current one) through the hooks of functional.py, preparing them on
+        first use.  Only the arithmetics that scale their operands ('f16x3', 'f16x1') have filter operands; under the others the filters stay as they
+        are and only the BatchNorm constants are shared."""
+        precision = HF.get_conv_precision() if precision is None else precision
+        if precision != HF.get_conv_precision():
+            raise DsrlHipError(f'FrozenOperands.attach({precision!r}) while the conv arithmetic is {HF.get_conv_precision()!r}')
+        scaled = precision in ('f16x3', 'f16x1')
+        s = None
+        if scaled:
+            s = self._sets.get(precision)
+            if s is None:
+                with torch.no_grad(), torch.cuda.device(self.device):
+                    s = self._sets[precision] = self._prepare(precision)
+        for i, (w, *_r) in enumerate(self._filters):
+            for a in ('_dsrl_wamax', '_dsrl_wsplit', '_dsrl_wplanes'):
+                if hasattr(w, a):
+                    delattr(w, a)
+            w._dsrl_arena = self
+            if s is not None:
+                w._dsrl_wamax = s['amax'][i * HF.AMAX_WORDS:(i + 1) * HF.AMAX_WORDS]
+                w._dsrl_wsplit = s['wsplit'][id(w)]
+                wp = s['wplanes'].get(id(w))
+                if wp is not None:
+                    w._dsrl_wplanes = wp
+        self.wt_valid = self.split_valid = s is not None
+        self.planes_valid = s is not None and s['planes'] is not None
+        self.precision = precision
+
+    def nbytes(self):
+        """Bytes of device memory the prepared operands hold (all arithmetics prepared so far, the BatchNorm constants and the fingerprints)."""
+        n = self._invstd.numel() * 4 + self._fp.numel() * 8 + self._fp_table.numel() * 8
+        for s in self._sets.values():
+            n += sum(t.numel() * t.element_size() for t in (s['amax'], s['split'], s['planes']) if t is not None)
+        return n
+
+    # ------------------------------------------------------------------ staleness
+    def stale_reason(self):
+        if self.released:
+            return 'the operands were released'
+        for m in self._modules:
+            if m.training:
+                return f'a {type(m).__name__} of the model is in train mode'
+        for held, name, ptr, ver in self._watch:
+            t = held.get(name)
+            if t is None or t.data_ptr() != ptr:
+                return f"the tensor '{name}' of a module moved (.to(), a ddp.FlatParams arena, a replaced parameter)"
+            if t._version != ver:
+                return f"'{name}' was written in place (an optimiser step, load_state_dict, copy_)"
+        for m, held in self._invstd_held:
+            if getattr(m.running_var, '_dsrl_invstd', None) is not held:
+                return 'a BatchNorm ran in train mode and rewrote its running statistics'
+        for w, *_r in self._filters:
+            if getattr(w, '_dsrl_arena', None) is not self:
+                return 'a filter was bound to another arena (ddp.FlatParams)'
+        return None
+
+    def check(self):
+        """Every call: one Python loop, no device work.  Raises when anything the operands were derived from changed; re-attaches (preparing another
+        set if need be) when the conv arithmetic is not the one the attached operands were prepared for."""
+        why = self.stale_reason()
+        if why is not None:
+            raise DsrlHipError(f'the frozen operands of this model are stale: {why} - call release() and compile_predict() again')
+        if HF.get_conv_precision() != self.precision:
+            self.attach()
+
+    def release(self):
+        """Detaches everything: model.predict and model.forward run as they did before the model was frozen."""
+        if self.released:
+            return
+        for w, *_r in self._filters:
+            if getattr(w, '_dsrl_arena', None) is self:
+                for a in ('_dsrl_arena', '_dsrl_wamax', '_dsrl_wsplit', '_dsrl_wplanes'):
+                    if hasattr(w, a):
+                        delattr(w, a)
+        for m, held in self._invstd_held:
+            rv = m.running_var
+            if rv is not None and getattr(rv, '_dsrl_invstd', None) is held:
+                del rv._dsrl_invstd
+        self._sets, self._invstd_held, self._invstd = {}, [], None
+        self.wt_valid = self.split_valid = self.planes_valid = False
+        self.released = True
+
+
+class _CapturedPredict:
+    __slots__ = ('graph', 'img', 'tgt', 'flag', 'pred', 'counts', 'ce', 'arena', 'keep', 'ignore_index')
+
+
+_FLAG_MESSAGES = ((1, 'NaN in the input or the logits'), (2, 'labels outside the classes'),
+                  (STALE_BIT, 'a parameter or buffer changed since compile_predict() (written through .data or a raw pointer): call release() and compile_predict() again'))
+
+
+class CompiledPredictor:
+    """`pred, counts, ce = compiled(images, target=None, ignore_index=255, nan_flag=None)`: DSRL.predict on frozen operands, replayed from a hipGraph.
+
+    One graph per key (N, H, W, with target, conv arithmetic), captured at the key's first use after GRAPH_WARMUP eager calls (the frozen eager path:
+    the same kernels), at most MAX_GRAPHS keys; further shapes, and every shape when `graph` is False or a capture failed, run the frozen eager path.
+    The graph reads static input buffers (the call copies the batch in) and writes static outputs; the call returns copies of them (the class map is
+    N*H*W bytes), or with copy=False the static tensors themselves, which the next call with the same key overwrites.
+    Without a `nan_flag` the call reads its own flag back once and raises, as DSRL.predict does; that form also compares every parameter and buffer with
+    its fingerprint at compile time on the device (FrozenOperands.check_values).  With a caller's flag nothing synchronises with the host.
+    Activation amax records are the graph's own: a private arena whose zero fill is the graph's first node, so neither an eager predict nor a training
+    step between two replays sees or disturbs them."""
+
+    MAX_GRAPHS = 4
+
+    def __init__(self, model, batch_size=None, input_size=None, graph=True):
+        import time
+        from .command_handlers.train_or_resume import TrainStep
+        t0 = time.perf_counter()
+        self.GRAPH_WARMUP = TrainStep.GRAPH_WARMUP
+        self.model = model
+        self.frozen = FrozenOperands(model)
+        self.device = self.frozen.device
+        self.use_graph = bool(graph)
+        self._graphs, self._warm = {}, {}
+        self._restore_precision = None
+        self.replays = 0
+        if batch_size is not None and input_size is not None:
+            x = torch.zeros((int(batch_size), 3, int(input_size[0]), int(input_size[1])), device=self.device).contiguous(memory_format=HF.CL)
+            flag = torch.zeros((), dtype=torch.int32, device=self.device)
+            for _ in range(self.GRAPH_WARMUP + 1):          # the warm-up calls, then the one that captures and replays
+                self(x, nan_flag=flag)
+        torch.cuda.synchronize(self.device)
+        self.compile_seconds = time.perf_counter() - t0
+
+    @property
+    def num_graphs(self):
+        return len(self._graphs)
+
+    def _key(self, images, target):
+        N, _, H, W = images.shape
+        return (int(N), int(H), int(W), target is not None, HF.get_conv_precision())
+
+    # ------------------------------------------------------------------ capture (after TrainStep._capture / _capture_or_fall_back)
+    def _capture(self, key, images, target, ignore_index):
+        c = _CapturedPredict()
+        c.img = images.clone()
+        c.tgt = None if target is None else target.clone()
+        c.ignore_index = int(ignore_index)
+        c.flag = torch.zeros((), dtype=torch.int32, device=self.device)
+        c.graph = torch.cuda.CUDAGraph()
+        c.keep = HF.graph_keepalive = []            # pinned host tables captured copies would re-read on every replay
+        HF.capture_host, HF.capture_host_off = torch.empty(1 << 16, dtype=torch.uint8, pin_memory=True), 0      # allocated BEFORE the capture starts
+        c.keep.append(HF.capture_host)
+        _private_gen[0] += 1
+        c.arena = [HF._new_arena(self.device), 0, _private_gen[0], True]      # pinned: it can never be replaced while the graph lives
+        try:
+            with HF.amax_private(c.arena):
+                with torch.cuda.graph(c.graph, capture_error_mode='thread_local'):          # linear: one stream, no side streams in an eval forward
+                    c.arena[0].zero_()              # first node: every record a replay maxes into starts at zero
+                    c.flag.zero_()
+                    c.pred, c.counts, c.ce = self.model.predict(c.img, c.tgt, c.ignore_index, c.flag)
+        finally:
+            HF.graph_keepalive = None
+            HF.capture_host = None
+            HF.drop_planes()
+        self._graphs[key] = c
+        return c
+
+    def _capture_or_fall_back(self, key, images, target, ignore_index):
+        try:
+            return self._capture(key, images, target, ignore_index)
+        except Exception as e:          # noqa: BLE001
+            print(f'[dsrl] hipGraph capture of predict failed ({type(e).__name__}: {str(e)[:200]}); this CompiledPredictor continues on the frozen eager path',
+                  file=sys.stderr, flush=True)
+            self.use_graph = False
+            HF.graph_keepalive, HF.capture_host = None, None
+            try:
+                torch.cuda.set_stream(torch.cuda.default_stream(self.device))
+                torch.cuda.synchronize(self.device)
+            except Exception:           # noqa: BLE001
+                pass
+            return None
+
+    # ------------------------------------------------------------------ the call
+    def __call__(self, images, target=None, ignore_index=255, nan_flag=None, copy=True):
+        if self.frozen.released:
+            raise DsrlHipError('this CompiledPredictor was released: call compile_predict() again')
+        self.frozen.check()
+        HF._need_gpu(images, target, nan_flag)
+        if images.dim() != 4:
+            raise DsrlHipError(f'4-D (N,3,H,W) images expected, got shape {tuple(images.shape)}')
+        own = nan_flag is None
+        key = self._key(images, target)
+        c = self._graphs.get(key)
+        if c is not None and target is not None and c.ignore_index != int(ignore_index):
+            c = None                                # the label to ignore is a launch argument of the captured kernels: this call runs eagerly
+        elif (c is None and self.use_graph and len(self._graphs) < self.MAX_GRAPHS and self._warm.get(key, 0) >= self.GRAPH_WARMUP
+              and (target is None or (target.dtype == torch.uint8 and tuple(target.shape) == (images.shape[0], 2 * images.shape[2], 2 * images.shape[3])))):
+            c = self._capture_or_fall_back(key, images, target, ignore_index)
+        with torch.no_grad():
+            if c is None:
+                self._warm[key] = self._warm.get(key, 0) + 1
+                flag = torch.zeros((), dtype=torch.int32, device=images.device) if own else nan_flag
+                out = self.model.predict(images, target, ignore_index, flag)
+                HF.drop_planes()
+            else:
+                if c.img.data_ptr() != images.data_ptr():
+                    c.img.copy_(images, non_blocking=True)
+                if c.tgt is not None and c.tgt.data_ptr() != target.data_ptr():
+                    c.tgt.copy_(target, non_blocking=True)
+                c.graph.replay()
+                self.replays += 1
+                flag = c.flag
+                if not own:
+                    nan_flag.bitwise_or_(flag.reshape(nan_flag.shape))
+                out = (c.pred, c.counts, c.ce)
+                if copy:
+                    out = tuple(None if o is None else o.clone() for o in out)
+            if own:
+                self.frozen.check_values(flag)
+                bits = int(flag.item())             # the one readback of this form of the call
+                if bits:
+                    raise DsrlHipError('CompiledPredictor: ' + ' and '.join(m for b, m in _FLAG_MESSAGES if bits & b))
+        return out
+
+    def release(self):
+        """Drops the graphs and the frozen operands; the model is what it was before compile_predict()."""
+        self._graphs.clear()
+        self.frozen.release()
+        if self._restore_precision is not None:
+            HF.set_conv_precision(self._restore_precision[0])
+            self._restore_precision = None
+
+
+# ------------------------------------------------------------------------------------------------ compiled model files
+class _Settings:
+    """The dataset constants a compiled model file records, with the attribute names of datasets.*.settings."""
+
+    def __init__(self, d):
+        self.NUM_CLASSES, self.IGNORE_CLASS_LABEL = int(d['NUM_CLASSES']), int(d['IGNORE_CLASS_LABEL'])
+        self.MEAN, self.STD = [float(v) for v in d['MEAN']], [float(v) for v in d['STD']]
+        self.CLASS_RGB_COLOR = {int(k): tuple(int(c) for c in v) for k, v in d['CLASS_RGB_COLOR'].items()}
+
+
+def read_compiled_file(filename):
+    """Host-side half of load_compiled_model: reads the file (data only: torch.load(weights_only=True)) and checks format, version and ABI before any
+    device work.  Raises RuntimeError naming the command that writes such files."""
+    import os
+    if not os.path.isfile(filename):
+        raise RuntimeError(f"compiled_model: '{filename}' does not exist (the compile_model command writes compiled model files)")
+    try:
+        d = torch.load(filename, map_location='cpu', weights_only=True)
+    except Exception as e:          # noqa: BLE001
+        raise RuntimeError(f"compiled_model: '{filename}' is not a compiled model file of this project ({type(e).__name__}); write one with the compile_model command") from e
+    if not isinstance(d, dict) or d.get('format') != FORMAT:
+        plain = isinstance(d, dict) and 'model_state_dict' in d
+        raise RuntimeError(f"compiled_model: '{filename}' is {'a plain weights / checkpoint file' if plain else 'not a compiled model file'}: run the compile_model "
+                           'command on the weights first, or call the command without compiled_model')
+    if d.get('format_version') != FORMAT_VERSION:
+        raise RuntimeError(f"compiled_model: '{filename}' has format_version {d.get('format_version')!r}, this build reads {FORMAT_VERSION}: run compile_model again")
+    abi = int(_load_lib().dsrl_version())
+    if d.get('abi_version') != abi:
+        raise RuntimeError(f"compiled_model: '{filename}' was written for library ABI {d.get('abi_version')!r}, libdsrl_hip.so has {abi}: run compile_model again")
+    missing = [k for k in ('model_state_dict', 'model_input_size', 'batch_size', 'conv_precision', 'NUM_CLASSES', 'MEAN', 'STD', 'IGNORE_CLASS_LABEL',
+                           'CLASS_RGB_COLOR') if k not in d]
+    if missing:
+        raise RuntimeError(f"compiled_model: '{filename}' lacks {missing}: run compile_model again")
+    if d['conv_precision'] not in HF.CONV_PRECISION_MODES:
+        raise RuntimeError(f"compiled_model: '{filename}' names the unknown conv arithmetic {d['conv_precision']!r}")
+    return d
+
+
+def load_compiled_model(filename, device_obj, data=None):
+    """-> (model, CompiledPredictor) of a compiled model file: builds the stage-1 model, selects the recorded conv arithmetic for the predictor's
+    lifetime (release() restores the previous one), freezes the operands and captures the recorded (batch size, input size) key."""
+    from .models import DSRL
+    d = read_compiled_file(filename) if data is None else data          # `data`: what read_compiled_file(filename) returned to a caller that checked first
+    info = {k: v for k, v in d.items() if k != 'model_state_dict'}
+    model = DSRL(stage=1, dataset_settings=_Settings(d)).eval()
+    model.load_state_dict(d['model_state_dict'], strict=True)
+    model = model.to(device_obj).to(memory_format=torch.channels_last)
+    prev = HF.set_conv_precision(d['conv_precision'])
+    try:
+        with torch.cuda.device(device_obj):
+            predictor = CompiledPredictor(model, batch_size=int(d['batch_size']), input_size=tuple(int(v) for v in d['model_input_size']))
+    except BaseException:
+        HF.set_conv_precision(None if prev < 0 else prev)
+        raise
+    predictor._restore_precision = (None if prev < 0 else prev,)
+    predictor.info = info
+    predictor.settings = _Settings(d)
+    return model, predictor

@@ -174,3 +174,11 @@ class DSRL(BaseModel):
             if bits:
                 raise HF.DsrlHipError('DSRL.predict: ' + ' and '.join(m for b, m in ((1, 'NaN in the input or the logits'), (2, 'labels outside the classes')) if bits & b))
         return out
+
+    def compile_predict(self, batch_size=None, input_size=None, graph=True):
+        """-> inference.CompiledPredictor: `predict` on operands prepared once (inference.FrozenOperands: filter amax records, pre-split filters, fp16
+        filter planes, BatchNorm 1/std) and replayed from one hipGraph per (N, H, W, with target, conv arithmetic); bit-identical to `predict`.
+        `batch_size` and `input_size` (H, W) given: that key is captured right away.  While the predictor lives the model's weights are frozen: any
+        change makes its calls raise until release() and a new compile_predict(); release() leaves the model exactly as it was."""
+        from ..inference import CompiledPredictor
+        return CompiledPredictor(self, batch_size=batch_size, input_size=input_size, graph=graph)

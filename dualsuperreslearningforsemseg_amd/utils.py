@@ -27,3 +27,12 @@ def make_input_output_visualization(input_image, output_map, class_rgb_color, bl
     blend = (1. - blend_factor) * input_image.astype(np.float64) + blend_factor * colours.astype(np.float64)
     overlay = np.minimum(blend, 255.).astype(np.uint8)
     return np.concatenate((input_image, colours, overlay), axis=2)
+
+
+def make_input_output_visualization_device(rgb_u8, classes, class_rgb_color, mask=None, ignore_index=255, blend_factor=0.4):
+    """The same panels built on the device (functional.class_map_visualize): rgb_u8 (N,H,W,3) uint8, classes (N,H,W) uint8, mask (N,H,W) uint8 or None
+    (where mask == ignore_index the class is drawn as ignore_index), all on the GPU -> device uint8 (N,H,3W,3); `out[n]` holds the bytes of
+    make_input_output_visualization(rgb_u8[n] as (3,H,W), classes[n], class_rgb_color, blend_factor) transposed to (H,3W,3)."""
+    from . import functional as HF
+    return HF.class_map_visualize(rgb_u8, classes, HF.palette_tensor(class_rgb_color, rgb_u8.device), mask=mask, ignore_index=ignore_index,
+                                  blend_factor=blend_factor)

@@ -509,6 +509,30 @@ int dsrl_sssr_tail_predict(const float* x, int ldx, int N, int H, int W, int Cin
                            uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index, unsigned long long* counts /*nullable*/,
                            float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
 
+/* Fingerprint of tensors that must not change while an inference.FrozenOperands holds operands derived from them (a write through `.data` or a
+ * raw pointer moves neither a tensor's address nor its version counter).  table: DEVICE array of nseg rows of 2 int64 {pointer (4-byte aligned),
+ * number of 32-bit words <= dsrl_fingerprint_segment_words()}, one block per row; a tensor is cut into as many rows as it needs.  Row r gets
+ * h = sum_i (word_i + 1) * K * (2 i + 1) modulo 2^64: any change of a single word changes h, and the value does not depend on the order of the
+ * additions (bit-identical run to run).  out (nullable, nseg words): receives h; expect (nullable, nseg words) with flag: *flag |= bit when a row's h
+ * differs from expect[r].  One launch; nothing is read back here. */
+int dsrl_fingerprint_segment_words(void);
+int dsrl_fingerprint_segments(const int64_t* table, int64_t nseg, uint64_t* out /*nullable*/, const uint64_t* expect /*nullable*/, int* flag /*nullable*/,
+                              int bit, dsrl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * inference: the panel of the test command (utils.make_input_output_visualization) on the device (csrc/visualize.hip)
+ *   rgb (N,H,W,3) uint8 pixel-major = the shown input, classes (N,H,W) uint8 = a class map (DSRL.predict's pred), mask (N,H,W) uint8, nullable: where
+ *   mask == ignore_index the class is replaced by ignore_index (test.py's dataset mode: pred_map[target == IGNORE] = IGNORE), palette uint8 [256][3]
+ *   in device memory: label -> colour (labels the palette does not name: black) -> out (N,H,3W,3) uint8 = input | class colours | overlay,
+ *   overlay = uint8(min((1 - blend_factor) * in + blend_factor * colour, 255)) evaluated in double with both products and the sum rounded separately
+ *   and the conversion truncating: byte for byte what numpy gives for that expression in float64, for all 65536 (input byte, colour byte) pairs.
+ *   One streaming launch: a thread owns 16 (W % 16 == 0, pointers 16-byte aligned) or 4 (W % 4 == 0, 4-byte aligned) pixels of one row and moves them
+ *   as 128- or 32-bit words, else one pixel with byte accesses; 32-bit indices (N*H*W*9 < 2^31, DSRL_E_UNSUPPORTED beyond), one division per thread.
+ *   0 < blend_factor < 1, 0 <= ignore_index <= 255.  out must not alias the inputs.
+ * ---------------------------------------------------------------------------------------------- */
+int dsrl_class_map_visualize(const uint8_t* rgb, const uint8_t* classes, const uint8_t* mask /*nullable*/, const uint8_t* palette /*device, 256 x 3*/,
+                             uint8_t* out, int N, int H, int W, int ignore_index, double blend_factor, dsrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
