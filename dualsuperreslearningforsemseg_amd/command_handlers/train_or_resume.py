@@ -79,7 +79,7 @@ class TrainStep:
     is self-resetting, and the batch is copied into static input buffers.  With more than one rank the collectives stay outside the
     graph: BN-buffer broadcast before the replay, chunked gradient all-reduce and the SGD kernel after it."""
 
-    GRAPH_WARMUP = 2          # eager iterations per batch shape before the capture (lazy initialisation, allocator warm-up)
+    GRAPH_WARMUP = HF.GRAPH_WARMUP          # eager iterations per batch shape before the capture
 
     def __init__(self, model, flat, stage, w1, w2, ignore_index, graph=None):
         self.model, self.flat, self.stage, self.w1, self.w2, self.ignore = model, flat, stage, w1, w2, ignore_index
@@ -221,76 +221,52 @@ class TrainStep:
         return (tuple(input_image.shape), tuple(input_org.shape), tuple(target.shape), HF.get_conv_precision(), HF.overlap_wgrad)
 
     def _capture(self, key, input_image, input_org, target, hp):
+        """-> the captured step, or None: a capture that fails (a runtime that refuses something inside it) must not end the training run.  This
+        TrainStep then keeps launching eagerly - the same kernels and, with more than one rank, the same collectives in the same order, so ranks that
+        captured and ranks that did not stay in step.  Nothing of a capture has executed, failed or not: its host-side bookkeeping is rolled back."""
         c = _CapturedStep()
-        c.img, c.org, c.tgt = input_image.clone(), input_org.clone(), target.clone()
         bns = [m for m in self.model.modules() if isinstance(m, t.nn.modules.batchnorm._BatchNorm)]
         before = [getattr(m, '_dsrl_batches', 0) for m in bns]
         step_before = HF._rng_state['step']
-        c.graph = t.cuda.CUDAGraph()
         # A forked capture (weight gradients on a side stream) replays slower than a linear one on this runtime: the graph executor
         # pays more for its cross-queue dependencies than the overlap wins (measured 24.2 vs 23.8 ms per step), so the capture is
         # linear
-        overlap_was = HF.overlap_wgrad
-        HF.overlap_wgrad = False
-        c.keep = HF.graph_keepalive = []          # pinned host tables the captured copies read on every replay
-        HF.capture_host, HF.capture_host_off = t.empty(2 << 20, dtype=t.uint8, pin_memory=True), 0      # allocated BEFORE the capture starts
-        c.keep.append(HF.capture_host)
-        if HF.f16_mode():
-            c.keep.append(HF.amax_pin(self.flat.device))      # the graph zeroes, maxes into and reads this arena on every replay: it lives as long as the graph
-        c.graph_b, c.ready = None, []
-        mode = 'thread_local'
+        overlap_was, HF.overlap_wgrad = HF.overlap_wgrad, False
+        c.graph_b, c.ready, mode = None, [], 'thread_local'
         try:
-            if self.split:
-                # two graphs sharing one memory pool: [step start .. backward down to the cut + its weight gradients] and [the rest of backward];
-                # the chunks complete after the first are recorded - on replay their all-reduce is launched between the two graphs
-                with t.cuda.graph(c.graph, capture_error_mode=mode):
-                    c.outs, c.vals, cuts = self._phase_a(c.img, c.org, c.tgt, True, True, True)
-                c.ready = self.flat.ready_chunks()
-                c.graph_b = t.cuda.CUDAGraph()
-                with t.cuda.graph(c.graph_b, pool=c.graph.pool(), capture_error_mode=mode):
-                    self._phase_b(cuts)
-                del cuts
-            else:
-                with t.cuda.graph(c.graph, capture_error_mode=mode):
-                    c.outs, c.vals, _ = self._phase_a(c.img, c.org, c.tgt, True, True, False)
-                    self._finish(hp, True)
-        finally:
-            HF.overlap_wgrad = overlap_was
-            HF.graph_keepalive = None
-            HF.capture_host = None
-        # nothing ran during the capture: take back the host-side bookkeeping of that phantom iteration
-        HF._rng_state['step'] = step_before
-        c.bns = [m for m, n in zip(bns, before) if getattr(m, '_dsrl_batches', 0) != n]
-        for m, n in zip(bns, before):
-            if hasattr(m, '_dsrl_batches'):
-                m._dsrl_batches = n
-        self._graphs[key] = c
-        return c
-
-    def _capture_or_fall_back(self, key, input_image, input_org, target, hp):
-        """A capture that fails (a runtime that refuses something inside it) must not end the training run: this TrainStep then keeps
-        launching eagerly - the same kernels and, with more than one rank, the same collectives in the same order, so ranks that captured and
-        ranks that did not stay in step.  Nothing of a failed capture has executed; its host-side bookkeeping is rolled back."""
-        import sys
-        bns = [m for m in self.model.modules() if isinstance(m, t.nn.modules.batchnorm._BatchNorm)]
-        before = [getattr(m, '_dsrl_batches', 0) for m in bns]
-        step_before, overlap_was = HF._rng_state['step'], HF.overlap_wgrad
-        try:
-            return self._capture(key, input_image, input_org, target, hp)
+            c.img, c.org, c.tgt = input_image.clone(), input_org.clone(), target.clone()
+            c.graph = t.cuda.CUDAGraph()
+            with HF.capture_scope(2 << 20) as c.keep:
+                if HF.f16_mode():
+                    c.keep.append(HF.amax_pin(self.flat.device))      # the graph zeroes, maxes into and reads this arena on every replay: it lives as long as the graph
+                if self.split:
+                    # two graphs sharing one memory pool: [step start .. backward down to the cut + its weight gradients] and [the rest of backward];
+                    # the chunks complete after the first are recorded - on replay their all-reduce is launched between the two graphs
+                    with t.cuda.graph(c.graph, capture_error_mode=mode):
+                        c.outs, c.vals, cuts = self._phase_a(c.img, c.org, c.tgt, True, True, True)
+                    c.ready = self.flat.ready_chunks()
+                    c.graph_b = t.cuda.CUDAGraph()
+                    with t.cuda.graph(c.graph_b, pool=c.graph.pool(), capture_error_mode=mode):
+                        self._phase_b(cuts)
+                    del cuts
+                else:
+                    with t.cuda.graph(c.graph, capture_error_mode=mode):
+                        c.outs, c.vals, _ = self._phase_a(c.img, c.org, c.tgt, True, True, False)
+                        self._finish(hp, True)
         except Exception as e:          # noqa: BLE001
-            print(f'[dsrl] hipGraph capture failed ({type(e).__name__}: {str(e)[:200]}); this TrainStep continues with eager launches', file=sys.stderr, flush=True)
             self.use_graph = False
-            HF.overlap_wgrad, HF.graph_keepalive, HF.capture_host, HF.wgrad_queue = overlap_was, None, None, None
-            HF._rng_state['step'] = step_before
+            HF.wgrad_queue = None
+            HF.abandon_capture(self.flat.device, e, '', 'this TrainStep continues with eager launches')
+            return None
+        finally:
+            # captured or failed, nothing ran: take back the host-side bookkeeping of that phantom iteration
+            HF.overlap_wgrad, HF._rng_state['step'] = overlap_was, step_before
+            c.bns = [m for m, n in zip(bns, before) if getattr(m, '_dsrl_batches', 0) != n]
             for m, n in zip(bns, before):
                 if hasattr(m, '_dsrl_batches'):
                     m._dsrl_batches = n
-            try:
-                t.cuda.set_stream(t.cuda.default_stream(self.flat.device))
-                t.cuda.synchronize(self.flat.device)
-            except Exception:           # noqa: BLE001
-                pass
-            return None
+        self._graphs[key] = c
+        return c
 
     def _replay(self, c, input_image, input_org, target):
         flat = self.flat
@@ -350,7 +326,7 @@ class TrainStep:
             key = self._graph_key(input_image, input_org, target)
             c = self._graphs.get(key)
             if c is None and self._warm.get(key, 0) >= self.GRAPH_WARMUP:
-                c = self._capture_or_fall_back(key, input_image, input_org, target, hp)
+                c = self._capture(key, input_image, input_org, target, hp)
             if c is None:
                 self._warm[key] = self._warm.get(key, 0) + 1
                 outs, vals = self._body(input_image, input_org, target, hp, True)

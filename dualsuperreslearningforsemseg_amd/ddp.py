@@ -20,10 +20,7 @@ import torch
 import torch.distributed as dist
 
 from . import functional as HF
-
-
-def _align(n, a=4):
-    return (n + a - 1) // a * a
+from .filter_operands import FilterOperands, align as _align, conv_filters, segment_rows
 
 
 class FlatParams:
@@ -97,7 +94,11 @@ class FlatParams:
         self._fill_skipped = False
         for p in self.params:
             p._dsrl_arena = self
-        self._build_transposed_filters()
+        # the conv filters of the arena with their prepared operands: amax records, the [C][R][S][K] transposes the dgrad kernels read, split forms and planes
+        mine = {id(p) for p in self.params}
+        self.filters = FilterOperands([w for w in conv_filters(model) if id(w) in mine] if dev.type == 'cuda' else [], dev, transposed=True)
+        self.filters.attach()
+        self._seg_tables, self._amax_key = {}, None        # segment tables of the optimiser pass by arena range; key under which its filter magnitudes are valid
         if self.world > 1 and self.device.type == 'cuda' and HF.knob('DSRL_BN_FUSED_BIG', None) is None:
             # RCCL kernels hold CUs while they wait for their peers: a 256-block fused-BN launch (one block on EVERY CU) could stall behind
             # them, the 128-block variant cannot
@@ -153,100 +154,24 @@ class FlatParams:
             else:
                 self._works.append(dist.all_reduce(self.g_flat[a:b], op=dist.ReduceOp.SUM, group=self.pg, async_op=True))
 
-    # ------------------------------------------------------------------ transposed conv filters for the data-gradient kernels
-    def _build_transposed_filters(self):
-        """One arena with the [C][R][S][K padded to 4] transpose of every conv filter the dgrad kernel reads, refreshed by ONE
-        launch per training step (dsrl_conv2d_transpose_filters_batched) instead of one launch inside every dgrad call."""
-        from .nn_modules import HipConv2d
-        self.wt_valid, self.wt_fp32_valid, self.split_valid, self._wt_table, self._wt_tiles = False, False, False, None, 0
-        self._split_entries, self._split_table, self._seg_tables, self._amax_key = [], None, {}, None
-        if self.device.type != 'cuda':
-            return
-        mine = {id(p) for p in self.params}
-        entries, floats = [], 0
-        for m in self.model.modules():
-            if not isinstance(m, HipConv2d):
-                continue
-            w = m.weight
-            K, C, R, S = w.shape
-            if id(w) not in mine or C % 4 != 0 or not HF._is_krsc(w):
-                continue            # the RGB stem (C = 3) and the C -> 1 feature transformers never run the implicit-GEMM dgrad
-            Kp = (K + 3) & ~3
-            entries.append((w, K, Kp, R * S, C, floats))
-            floats += _align(C * R * S * Kp)
-        if not entries:
-            return
-        self.wt_flat = torch.empty(floats, device=self.device, dtype=torch.float32)
-        # one magnitude word per filter (max |w| as a bit pattern), re-measured by the same launch: the filter-side operand scale of the
-        # f16x3 conv arithmetic (include/dsrl_hip.h: dsrl_amax)
-        self.w_amax = torch.zeros(len(entries) * HF.AMAX_WORDS, device=self.device, dtype=torch.int32)      # one amax record per filter
-        rows, tiles = [], 0
-        for i, (w, K, Kp, RS, C, off) in enumerate(entries):
-            wt = self.wt_flat[off:off + C * RS * Kp]
-            w._dsrl_wt = wt
-            w._dsrl_wamax = self.w_amax[i * HF.AMAX_WORDS:(i + 1) * HF.AMAX_WORDS]
-            ct = (C + 31) // 32
-            rows.append([w.data_ptr(), wt.data_ptr(), K, Kp, RS, C, tiles, ct, self.w_amax.data_ptr() + 4 * HF.AMAX_WORDS * i, 0])
-            tiles += RS * ct * ((Kp + 31) // 32)
-        self._wt_table = torch.tensor(rows, dtype=torch.int64, device=self.device)
-        self._wt_rows, self._wt_tiles = len(rows), tiles
-        # f16x3 arithmetic: every filter also in pre-split ("plane") form, forward layout and transposed (dsrl_conv2d_split_filters_batched);
-        # the arenas are allocated on first use
-        self._split_entries, self._split_table = entries, None
-        self.planes_valid, self._plane_sets = False, []
-        self._seg_tables, self._amax_key = {}, None        # segment tables of the optimiser pass by arena range; key under which its filter magnitudes are valid
-
-    def _build_split_filters(self):
-        floats_w = sum(_align(w.numel()) for w, *_ in self._split_entries)
-        self.wsplit_flat = torch.empty(floats_w, device=self.device, dtype=torch.float32)
-        self.wtsplit_flat = torch.empty(self.wt_flat.numel(), device=self.device, dtype=torch.float32)
-        rows, off_w = [], 0
-        base = self._wt_table.cpu()
-        for i, (w, K, Kp, RS, C, off) in enumerate(self._split_entries):
-            wsp = self.wsplit_flat[off_w:off_w + w.numel()]
-            wtsp = self.wtsplit_flat[off:off + C * RS * Kp]
-            off_w += _align(w.numel())
-            w._dsrl_wsplit, w._dsrl_wtsplit = wsp, wtsp
-            r = base[i].tolist()
-            rows.append([r[0], wtsp.data_ptr(), K, Kp, RS, C, r[6], r[7], r[8], wsp.data_ptr()])
-        self._split_table = torch.tensor(rows, dtype=torch.int64, device=self.device)
-        amax_only = base.clone()
-        amax_only[:, 1] = 0                     # no transposed fp32 copy
-        self._amax_only_table = amax_only.to(self.device)
-        # the records alone, by a streaming launch over segments of every filter's contiguous storage (dsrl_conv2d_filters_amax_batched)
-        seg = int(HF.query('dsrl_conv2d_filters_amax_segment_floats'))
-        segs = []
-        for i, (w, K, Kp, RS, C, off) in enumerate(self._split_entries):
-            n, rec = w.numel(), self.w_amax.data_ptr() + 4 * HF.AMAX_WORDS * i
-            for a in range(0, n, seg):
-                segs.append([w.data_ptr() + 4 * a, min(seg, n - a), rec])
-        self._amax_seg_table = torch.tensor(segs, dtype=torch.int64, device=self.device)
-        self._amax_segs = len(segs)
-
     # ------------------------------------------------------------------ optimiser pass that also measures the filters (round 5)
     def _params_key(self):
         """Changes whenever torch code writes a filter or the arena (load_state_dict, copy_, fill_ ...): the magnitudes the optimiser kernel left are
         trusted only while it is unchanged - the kernels themselves write through raw pointers and do not move it."""
-        return (self.p_flat._version, sum(e[0]._version for e in self._split_entries))
+        return (self.p_flat._version, sum(w._version for w in self.filters.filters))
 
     def _segments(self, a, b):
         """Device table {first float, floats, amax record address or 0} covering arena range [a, b) (multiples of 4) with segments of at most 32768
-        floats, each inside one parameter; the filters of _split_entries carry their record (dsrl_sgd_step_dev_segments)."""
+        floats, each inside one parameter; the filters with prepared operands carry their record (dsrl_sgd_step_dev_segments)."""
         key = (a, b)
         tab = self._seg_tables.get(key)
         if tab is not None:
             return tab
         seg = int(HF.query('dsrl_conv2d_filters_amax_segment_floats'))
-        rec_of = {id(w): self.w_amax.data_ptr() + 4 * HF.AMAX_WORDS * i for i, (w, *_r) in enumerate(self._split_entries)}
         rows = []
         for p_, o in zip(self.params, self.offsets):
             lo, hi = max(o, a), min(o + _align(p_.numel()), b)
-            rec = rec_of.get(id(p_), 0)
-            x = lo
-            while x < hi:
-                n = min(seg, hi - x)
-                rows.append([x, n, rec])
-                x += n
+            rows += segment_rows(lo, hi - lo, self.filters.record_ptr_of.get(id(p_), 0), seg)
         tab = self._seg_tables[key] = (torch.tensor(rows, dtype=torch.int64, device=self.device), len(rows))
         return tab
 
@@ -264,70 +189,37 @@ class FlatParams:
         """In front of a REPLAYED step: a graph captured while the optimiser's magnitudes were valid contains no measuring sweep and relies on the
         previous replay's optimiser pass.  If torch code wrote parameters since (a restored state, load_state_dict), measure eagerly once."""
         if self._fold_amax() and self._amax_key != self._params_key():
-            self.w_amax.zero_()
-            HF.call('dsrl_conv2d_filters_amax_batched', self._amax_seg_table.data_ptr(), self._amax_segs, HF._stream())
+            self.filters.amax.zero_()
+            self.filters.measure(streaming=True)
             self._amax_key = self._params_key()
 
     def _fold_amax(self):
-        return (self.device.type == 'cuda' and self._wt_table is not None and HF.f16_mode() and HF.knob('DSRL_FILTER_AMAX_STREAM', True) and
-                HF.knob('DSRL_SGD_AMAX', True) and self._split_table is not None)
+        return (self.device.type == 'cuda' and self.filters.rows and HF.f16_mode() and HF.knob('DSRL_FILTER_AMAX_STREAM', True) and
+                HF.knob('DSRL_SGD_AMAX', True) and self.filters.wsplit_flat is not None)
 
-    def _build_plane_filters(self):
-        """The filters whose convs take plane operands (channel counts multiples of 8), as fp16 planes, forward [K][R][S][C] and transposed
-        [C][R][S][K]: the filter operand of conv_planes_kernel (dsrl_conv2d_filter_planes_batched), scaled by the same amax records as the split forms.
-        'auto': only the filters whose convs asked for planes in an earlier step (functional._Conv2d marks them: operands large enough for the split pass
-        to pay); 'all': every eligible filter.  Sets are only ever ADDED: a captured graph keeps launching the table it was captured with and reading the
-        arenas of that table (another batch shape may want more filters later - they get a set of their own; nothing a graph references is replaced)."""
-        have = {id(w) for st in self._plane_sets for w in st['filters']}
-        ents = [(i, e) for i, e in enumerate(self._split_entries) if e[1] % 8 == 0 and e[4] % 8 == 0 and id(e[0]) not in have and
-                (HF.planes_mode == 'all' or getattr(e[0], '_dsrl_want_planes', False))]
-        if not ents:
-            return
-        lo = lambda n: int(HF.cquery('dsrl_planes_lo_offset', n))        # noqa: E731
-        total = sum(2 * lo(w.numel()) for _, (w, *_r) in ents)
-        wplanes = torch.empty(total, device=self.device, dtype=torch.uint8)
-        wtplanes = torch.empty(total, device=self.device, dtype=torch.uint8)
-        rows, off, tiles = [], 0, 0
-        for i, (w, K, Kp, RS, C, _off) in ents:
-            nb = 2 * lo(w.numel())
-            wp, wtp = wplanes[off:off + nb], wtplanes[off:off + nb]
-            off += nb
-            w._dsrl_wplanes, w._dsrl_wtplanes = wp, wtp
-            ct = (C + 31) // 32
-            rows.append([w.data_ptr(), wtp.data_ptr(), K, K, RS, C, tiles, ct, self.w_amax.data_ptr() + 4 * HF.AMAX_WORDS * i, wp.data_ptr()])
-            tiles += RS * ct * ((K + 31) // 32)
-        self._plane_sets.append({'table': torch.tensor(rows, dtype=torch.int64, device=self.device), 'rows': len(rows), 'tiles': tiles,
-                                 'arenas': (wplanes, wtplanes), 'filters': [e[0] for _, e in ents]})
-
-    def _planes_pending(self):
-        """Does a filter want planes that no set holds yet?  (host-side check, two attribute reads per filter)"""
-        have = {id(w) for st in self._plane_sets for w in st['filters']}
-        return any(e[1] % 8 == 0 and e[4] % 8 == 0 and id(e[0]) not in have and (HF.planes_mode == 'all' or getattr(e[0], '_dsrl_want_planes', False))
-                   for e in self._split_entries)
-
+    # ------------------------------------------------------------------ the per-step filter pass
     def refresh_transposed_filters(self):
-        if self._wt_table is not None:
-            presplit = HF.f16_mode()
-            if presplit and self._split_table is None:
-                self._build_split_filters()
-            # with pre-split filters nothing reads the fp32 transposes: the first launch then only measures (amax records), the second writes both split forms
-            if presplit and self._amax_key is not None and self._amax_key == self._params_key() and self._fold_amax():
-                pass            # round 5: the optimiser pass of the previous step left max |w| of every filter it wrote (dsrl_sgd_step_dev_segments)
-            elif presplit and HF.knob('DSRL_FILTER_AMAX_STREAM', True):
-                self.w_amax.zero_()
-                HF.call('dsrl_conv2d_filters_amax_batched', self._amax_seg_table.data_ptr(), self._amax_segs, HF._stream())
-            else:
-                self.w_amax.zero_()
-                HF.call('dsrl_conv2d_transpose_filters_batched', (self._amax_only_table if presplit else self._wt_table).data_ptr(), self._wt_rows, self._wt_tiles, HF._stream())
-            if presplit:
-                HF.call('dsrl_conv2d_split_filters_batched', self._split_table.data_ptr(), self._wt_rows, self._wt_tiles, HF._stream())
-            planes = presplit and HF.planes_mode != 'off' and HF.get_conv_precision() in ('f16x3', 'f16x1')      # f16x1 reads the first plane only
-            if planes:
-                if HF.graph_keepalive is None and self._planes_pending():
-                    self._build_plane_filters()         # first use, or more filters asked for planes since the last set was built (never inside a capture)
-                for st in self._plane_sets:
-                    HF.call('dsrl_conv2d_filter_planes_batched', st['table'].data_ptr(), st['rows'], st['tiles'], HF._stream())
-            self.wt_valid, self.wt_fp32_valid, self.split_valid, self.planes_valid = True, not presplit, presplit, planes
+        """What the convs of this step read of every filter (filter_operands.FilterOperands runs the launches): under the f16 arithmetics the amax
+        records, both split forms and - for the filters whose convs asked for them - the planes; else the records and the fp32 transposes."""
+        ops = self.filters
+        if not ops.rows:
+            return
+        if not HF.f16_mode():
+            ops.amax.zero_()
+            ops.transpose()
+            return
+        # with pre-split filters nothing reads the fp32 transposes: the first launch only measures (amax records) - round 5: unless the optimiser pass of
+        # the previous step left max |w| of every filter it wrote (dsrl_sgd_step_dev_segments) -, the second writes both split forms
+        if not (self._amax_key is not None and self._amax_key == self._params_key() and self._fold_amax()):
+            ops.amax.zero_()
+            ops.measure(HF.knob('DSRL_FILTER_AMAX_STREAM', True))
+        ops.write_split()
+        if HF.planes_mode != 'off' and HF.get_conv_precision() in ('f16x3', 'f16x1'):      # f16x1 reads the first plane only
+            if HF.graph_keepalive is None:
+                # 'auto': the filters whose convs asked for planes in an earlier step (functional._Conv2d marks them: operands large enough for the split
+                # pass to pay); 'all': every eligible filter.  First use, or more filters asked since the last set was built - never inside a capture
+                ops.add_plane_set(lambda w: HF.planes_mode == 'all' or getattr(w, '_dsrl_want_planes', False))
+            ops.write_planes()
 
     def zero_grad(self):
         self._fill_skipped = self.lazy_zero and self._all_claimed_last
@@ -433,18 +325,8 @@ class FlatParams:
         works = []
         if self.world > 1:
             works = [dist.all_reduce(self.g_flat[a:b], op=dist.ReduceOp.SUM, group=self.pg, async_op=True) for a, b in ranges]
-        fold = hyper is not None and self._fold_amax()
-        if fold:
-            self.w_amax.zero_()
-        for i, (a, b) in enumerate(ranges):
-            if works:
-                works[i].wait()             # stream-ordered for RCCL: the compute stream waits for this range only
-            self._sgd_range(a, b, hyper, hp)
-        self._amax_key = self._params_key() if fold else None
+        self._update(ranges, works, hyper, hp)
         self._pending = [0] * len(self.chunks)
-        if self.device.type == 'cuda':
-            HF.amax_end_step(self.device)
-        self.wt_valid = self.wt_fp32_valid = self.split_valid = self.planes_valid = False
         return ranges
 
     def sync_buffers(self):
@@ -458,14 +340,21 @@ class FlatParams:
         three host values."""
         if reduce:
             self.finish_reduction()
+        self._update([(0, self.numel)], [], hyper, (lr, momentum, weight_decay))
+
+    def _update(self, ranges, works, hyper, hp):
+        """SGD over `ranges` of the arena, range k as soon as works[k] (its all-reduce, if any) is done; then the step is over."""
         fold = hyper is not None and self._fold_amax()
         if fold:
-            self.w_amax.zero_()
-        self._sgd_range(0, self.numel, hyper, (lr, momentum, weight_decay))
+            self.filters.amax.zero_()
+        for i, (a, b) in enumerate(ranges):
+            if works:
+                works[i].wait()             # stream-ordered for RCCL: the compute stream waits for this range only
+            self._sgd_range(a, b, hyper, hp)
         self._amax_key = self._params_key() if fold else None
         if self.device.type == 'cuda':
             HF.amax_end_step(self.device)       # records asked for between steps (validation) come from the loose arena, not from the step's
-        self.wt_valid = self.wt_fp32_valid = self.split_valid = self.planes_valid = False       # the filters changed: transposed / split copies and amax records are stale until the next refresh
+        self.filters.invalidate()       # the filters changed: transposed / split copies and amax records are stale until the next refresh
 
     def _trainable_in_model_order(self):
         return [p for p in self.model.parameters() if p.requires_grad]

@@ -4,8 +4,10 @@ Tensors keep the reference's logical NCHW shapes; physically they are torch.chan
 [P][ld] for the kernels), which the wrappers enforce with at most one strided copy at the boundary.  Every op
 raises if its tensors are not on a HIP device: there is no CPU / stock-ATen fallback in this package.
 """
+import contextlib
 import ctypes
 import os
+import sys
 import weakref
 
 import torch
@@ -258,6 +260,33 @@ def join_side_streams():
 group_wgrad = knob('DSRL_WGRAD_GROUP', True)
 graph_keepalive = None          # a list while a hipGraph capture is in progress: host buffers the captured copies read on every replay
 capture_host, capture_host_off = None, 0      # pinned arena for host tables written during a capture (allocated before it starts)
+GRAPH_WARMUP = 2                # eager calls per graph key before its capture (lazy initialisation, allocator warm-up)
+
+
+@contextlib.contextmanager
+def capture_scope(table_bytes):
+    """The host state of a hipGraph capture: the pinned arena of `table_bytes` for host tables, allocated BEFORE the capture starts (hipHostMalloc
+    is not capturable), and the keep-alive list, which it yields: the caller keeps it as long as the graph - captured copies re-read those buffers."""
+    global graph_keepalive, capture_host, capture_host_off
+    capture_host, capture_host_off = torch.empty(table_bytes, dtype=torch.uint8, pin_memory=True), 0
+    keep = graph_keepalive = [capture_host]
+    try:
+        yield keep
+    finally:
+        graph_keepalive = capture_host = None
+
+
+def abandon_capture(device, e, what, then):
+    """After a failed capture (nothing of it has executed): one line on stderr, then back to the default stream and an idle device; the caller goes on
+    with eager launches."""
+    global graph_keepalive, capture_host
+    print(f'[dsrl] hipGraph capture{what} failed ({type(e).__name__}: {str(e)[:200]}); {then}', file=sys.stderr, flush=True)
+    graph_keepalive = capture_host = None
+    try:
+        torch.cuda.set_stream(torch.cuda.default_stream(device))
+        torch.cuda.synchronize(device)
+    except Exception:           # noqa: BLE001
+        pass
 
 
 class WgradQueue:
@@ -472,37 +501,35 @@ def _deliver(param, grad):
 
 
 def _weight_amax(w):
-    """Magnitude slot of a conv filter that ddp.FlatParams keeps (measured by the batched filter transpose of this step), or None."""
-    arena, slot = getattr(w, '_dsrl_arena', None), getattr(w, '_dsrl_wamax', None)
-    if slot is not None and arena is not None and arena.wt_valid:
-        return slot
-    return None
+    """The amax record its FilterOperands (filter_operands.py) keeps for a conv filter - measured in this step, or once for a frozen model - or None."""
+    h = getattr(w, '_dsrl_operands', None)
+    return None if h is None else h[0].record(h[1])
 
 
-def _weight_split(w, attr):
-    """The pre-split form of a conv filter that ddp.FlatParams wrote in this step (attr: '_dsrl_wsplit' forward layout, '_dsrl_wtsplit' transposed), or None."""
-    arena = getattr(w, '_dsrl_arena', None)
-    return getattr(w, attr, None) if (arena is not None and arena.split_valid) else None
+def _weight_split(w, transposed=False):
+    """The pre-split form of a conv filter written in this step (forward layout, or transposed), or None."""
+    h = getattr(w, '_dsrl_operands', None)
+    return None if h is None else h[0].split(h[1], transposed)
 
 
-def _weight_planes(w, attr):
-    """The fp16 planes of a conv filter that ddp.FlatParams wrote in this step (attr: '_dsrl_wplanes' [K][R][S][C], '_dsrl_wtplanes' [C][R][S][K]), or None."""
-    arena = getattr(w, '_dsrl_arena', None)
-    return getattr(w, attr, None) if (arena is not None and getattr(arena, 'planes_valid', False)) else None
+def _weight_planes(w, transposed=False):
+    """The fp16 planes of a conv filter written in this step ([K][R][S][C], or transposed [C][R][S][K]), or None."""
+    h = getattr(w, '_dsrl_operands', None)
+    return None if h is None else h[0].planes(h[1], transposed)
 
 
 def split_filter(w):
-    """(amax record, w_split, wt_split) of one [K][R][S][C] filter for the f16x3 kernels: what ddp.FlatParams prepares for every filter of a
-    model once per step (dsrl_conv2d_transpose_filters_batched + dsrl_conv2d_split_filters_batched), here for a single tensor."""
+    """(amax record, w_split, wt_split) of one [K][R][S][C] filter for the f16x3 kernels: what filter_operands.FilterOperands prepares for every
+    filter of a model (dsrl_conv2d_transpose_filters_batched + dsrl_conv2d_split_filters_batched), here for a single tensor."""
+    from .filter_operands import table_row, wt_floats           # that module sits above this one
     w = w_cl(w)
     K, C, R, S = w.shape
-    Kp, RS, ct = (K + 3) & ~3, R * S, (C + 31) // 32
-    tiles = RS * ct * ((Kp + 31) // 32)
     rec = amax_slot(w.device)
-    wt = torch.empty(C * RS * Kp, device=w.device, dtype=torch.float32)
-    wsp, wtsp = torch.empty(K * RS * C, device=w.device, dtype=torch.float32), torch.empty_like(wt)
-    t1 = torch.tensor([[w.data_ptr(), wt.data_ptr(), K, Kp, RS, C, 0, ct, rec.data_ptr(), 0]], dtype=torch.int64, device=w.device)
-    t2 = torch.tensor([[w.data_ptr(), wtsp.data_ptr(), K, Kp, RS, C, 0, ct, rec.data_ptr(), wsp.data_ptr()]], dtype=torch.int64, device=w.device)
+    wt = torch.empty(wt_floats(K, R * S, C), device=w.device, dtype=torch.float32)
+    wsp, wtsp = torch.empty(K * R * S * C, device=w.device, dtype=torch.float32), torch.empty_like(wt)
+    r1, tiles = table_row(w.data_ptr(), K, R * S, C, 0, rec.data_ptr(), wt.data_ptr())
+    r2, _ = table_row(w.data_ptr(), K, R * S, C, 0, rec.data_ptr(), wtsp.data_ptr(), wsp.data_ptr())
+    t1, t2 = (torch.tensor([r], dtype=torch.int64, device=w.device) for r in (r1, r2))
     call('dsrl_conv2d_transpose_filters_batched', t1.data_ptr(), 1, tiles, _stream())
     call('dsrl_conv2d_split_filters_batched', t2.data_ptr(), 1, tiles, _stream())
     return rec, wsp, wtsp, wt
@@ -591,16 +618,16 @@ def drop_planes():
 
 
 def filter_planes(w, rec):
-    """(w_planes [K][R][S][C], wt_planes [C][R][S][K]) of one filter, scaled by its amax record `rec`: what ddp.FlatParams prepares for every
-    filter once per step (dsrl_conv2d_filter_planes_batched), here for a single tensor.  K and C must be multiples of 8."""
+    """(w_planes [K][R][S][C], wt_planes [C][R][S][K]) of one filter, scaled by its amax record `rec`: what filter_operands.FilterOperands prepares
+    for the filters of a plane set (dsrl_conv2d_filter_planes_batched), here for a single tensor.  K and C must be multiples of 8."""
+    from .filter_operands import table_row
     w = w_cl(w)
     K, C, R, S = w.shape
-    RS, ct = R * S, (C + 31) // 32
-    tiles = RS * ct * ((K + 31) // 32)
-    nbytes = int(cquery('dsrl_planes_bytes', K * RS * C, 2))
+    nbytes = int(cquery('dsrl_planes_bytes', K * R * S * C, 2))
     wp = torch.empty(nbytes, device=w.device, dtype=torch.uint8)
     wtp = torch.empty(nbytes, device=w.device, dtype=torch.uint8)
-    t = torch.tensor([[w.data_ptr(), wtp.data_ptr(), K, K, RS, C, 0, ct, rec.data_ptr(), wp.data_ptr()]], dtype=torch.int64, device=w.device)
+    row, tiles = table_row(w.data_ptr(), K, R * S, C, 0, rec.data_ptr(), wtp.data_ptr(), wp.data_ptr(), pad_k=False)
+    t = torch.tensor([row], dtype=torch.int64, device=w.device)
     call('dsrl_conv2d_filter_planes_batched', t.data_ptr(), 1, tiles, _stream())
     return wp, wtp
 
@@ -742,10 +769,10 @@ class _Conv2d(torch.autograd.Function):
         ctx.amax = (xa, wa)
         if stats_parts > 0:         # BatchNorm partials of y from the conv epilogue (include/dsrl_hip.h: dsrl_conv2d_fwd_stats)
             stats = torch.empty(cquery('dsrl_bn_stats_floats', 3, int(stats_parts), K), device=x.device, dtype=torch.float32)
-        wsp = _weight_split(w_param, '_dsrl_wsplit') if wa is not None else None        # the filter pre-split by ddp.FlatParams (same step, same record)
-        wpl = _weight_planes(w_param, '_dsrl_wplanes') if wa is not None else None       # ... and as fp16 planes; with planes of x the launch stages by LDS-DMA
+        wsp = _weight_split(w_param) if wa is not None else None        # the filter pre-split by its FilterOperands (same step, same record)
+        wpl = _weight_planes(w_param) if wa is not None else None       # ... and as fp16 planes; with planes of x the launch stages by LDS-DMA
         if wpl is None and wa is not None and planes_wanted(x, ldx, Cc, K, R * S):
-            w_param._dsrl_want_planes = True            # ddp.FlatParams writes this filter's planes from the next step on
+            w_param._dsrl_want_planes = True            # ddp.FlatParams adds this filter to a plane set at the next step
         xp = planes_for(x_in, x, ldx, xa, R * S) if wpl is not None else None
         call('dsrl_conv2d_fwd_planes', x.data_ptr(), ldx, None if xa is None else xa.data_ptr(), None if xp is None else xp.data_ptr(), w.data_ptr(),
              None if wa is None else wa.data_ptr(), None if wsp is None else wsp.data_ptr(), None if wpl is None else wpl.data_ptr(),
@@ -779,11 +806,11 @@ class _Conv2d(torch.autograd.Function):
             dya = amax_for(dy_in, dy, lddy)          # one measurement for the data and the weight gradient
             if xa is None:
                 xa = amax_for(x, x, ldx)
-            if wa is not None and ctx.wparam is not None and not getattr(getattr(ctx.wparam, '_dsrl_arena', None), 'wt_valid', False):
+            if wa is not None and ctx.wparam is not None and _weight_amax(ctx.wparam) is None:
                 wa = None                             # the filter changed since its magnitude was taken
         p_ = lambda t_: None if t_ is None else t_.data_ptr()       # noqa: E731
-        wtsp = _weight_split(ctx.wparam, '_dsrl_wtsplit') if (wa is not None and ctx.wparam is not None) else None
-        wtpl = _weight_planes(ctx.wparam, '_dsrl_wtplanes') if (wa is not None and ctx.wparam is not None) else None
+        wtsp = _weight_split(ctx.wparam, True) if (wa is not None and ctx.wparam is not None) else None
+        wtpl = _weight_planes(ctx.wparam, True) if (wa is not None and ctx.wparam is not None) else None
         # 'auto' never pays a split pass for a gradient (measured: the data-gradient launches gain less than the pass costs); planes a producer left are used
         # f16x1 (round 5): the one-plane split of a large gradient does pay (cat_conv.0 dgrad 772 -> 547 us at config 5's size for a ~60 us pass)
         dy_split_ok = planes_mode == 'all' or (_planes_npl() == 1 and dy.shape[0] * dy.shape[1] * dy.shape[2] * dy.shape[3] >= planes_min_elems)
@@ -820,8 +847,9 @@ class _Conv2d(torch.autograd.Function):
             wt_ptr = None
             if ctx.wparam is not None:
                 # ddp.FlatParams keeps a transposed copy of every filter, refreshed by one batched launch per training step
-                arena, wt = getattr(ctx.wparam, '_dsrl_arena', None), getattr(ctx.wparam, '_dsrl_wt', None)
-                if wt is not None and arena is not None and arena.wt_valid and arena.wt_fp32_valid:
+                h = getattr(ctx.wparam, '_dsrl_operands', None)
+                wt = None if h is None else h[0].fp32_transpose(h[1])
+                if wt is not None:
                     wt_ptr = wt.data_ptr()
             link = ctx.in_link
             parts = 0

@@ -1,36 +1,30 @@
 """Compiled inference: what an eval-mode model can prepare once because its weights are frozen, and its forward pass as a replayed hipGraph.
 
   * FrozenOperands(model): for every conv filter the kernels take them for, the amax record, the pre-split form and the fp16 planes of the forward layout
-    (the three batched kernels ddp.FlatParams runs once per training step, here once per model), and 1 / sqrt(var + eps) of every eval BatchNorm.
-    functional.py finds them through the hooks it already reads (`w._dsrl_arena`, `_dsrl_wamax`, `_dsrl_wsplit`, `_dsrl_wplanes`;
+    (a forward-only filter_operands.FilterOperands: the launches ddp.FlatParams runs once per training step, here once per model), and
+    1 / sqrt(var + eps) of every eval BatchNorm.  functional.py finds them through the hooks it already reads (`w._dsrl_operands`;
     `running_var._dsrl_invstd`), so `model.predict` and `model.forward` launch the same conv kernels on the same values, without the per-call filter
     measurement, the in-kernel filter split and the ~105 one-block invstd launches.
   * CompiledPredictor (DSRL.compile_predict): `DSRL.predict` captured per (N, H, W, with target, conv arithmetic) into a hipGraph and replayed - about a
     thousand eager launches become one hipGraphLaunch.  The contract is bit identity with eager `predict`.
   * load_compiled_model: the file the compile_model command writes (data only) -> (model, CompiledPredictor).
 """
-import sys
-
 import torch
 
 from . import functional as HF
 from ._lib import DsrlHipError, call, load as _load_lib, query
+from .filter_operands import FilterOperands, align as _align, conv_filters
 
 FORMAT, FORMAT_VERSION = 'dsrl-hip-compiled', 1
 STALE_BIT = 4           # bit of the NaN flag word the device-side fingerprint check raises (bit 0: NaN, bit 1: label outside the classes)
 _private_gen = [1 << 40]
 
 
-def _align(n, a=4):
-    return (n + a - 1) // a * a
-
-
 class FrozenOperands:
-    """Prepared operands of an eval-mode model on the GPU; see the module docstring.  Inference only: it stands where functional.py expects a
-    ddp.FlatParams arena, and everything a backward pass asks of one raises."""
+    """Prepared operands of an eval-mode model on the GPU; see the module docstring.  Inference only: it is the gradient sink (`_dsrl_arena`) of the
+    filters it froze, and a backward pass that asks it for a slot raises."""
 
     def __init__(self, model):
-        from .nn_modules import HipConv2d
         params = list(model.parameters())
         if not params or not params[0].is_cuda:
             raise DsrlHipError('FrozenOperands: the model must be on the HIP device')
@@ -42,15 +36,8 @@ class FrozenOperands:
         self.model, self.device = model, params[0].device
         self.released = False
         self.precision = None
-        self.wt_valid = self.wt_fp32_valid = self.split_valid = self.planes_valid = False
-        self._sets = {}             # conv arithmetic -> the operand buffers prepared for it (a captured graph keeps reading the set it was captured with)
-        self._filters = []          # (weight, K, Kp, R*S, C)
-        for m in model.modules():
-            if isinstance(m, HipConv2d):
-                w = m.weight
-                K, C, R, S = w.shape
-                if C % 4 == 0 and HF._is_krsc(w):           # the conditions of ddp.FlatParams: the RGB stem and the C -> 1 transformers have no such operands
-                    self._filters.append((w, K, (K + 3) & ~3, R * S, C))
+        self._sets = {}             # conv arithmetic -> its FilterOperands (a captured graph keeps reading the set it was captured with)
+        self._filters = conv_filters(model)          # the RGB stem and the C -> 1 transformers have no such operands
         self._bns = [m for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.running_var is not None]
         # what every call compares: (dict that holds the tensor, its name, address, version counter) of every parameter and buffer
         self._watch = []
@@ -65,12 +52,10 @@ class FrozenOperands:
             self._fingerprint()
             self.attach()
 
-    # ------------------------------------------------------------------ what backward asks of an arena
-    def _inference_only(self, *_a, **_k):
+    # ------------------------------------------------------------------ what backward asks of a gradient sink first
+    def claim(self, _p):
         raise DsrlHipError('FrozenOperands is inference-only: a backward pass reached a filter whose operands are frozen - call release() '
                            '(CompiledPredictor.release()) before training this model')
-
-    claim = written = zero_grad = settle_grads = finish_reduction = sgd_step = refresh_transposed_filters = _inference_only
 
     # ------------------------------------------------------------------ BatchNorm constants
     def _freeze_invstd(self):
@@ -112,49 +97,17 @@ class FrozenOperands:
         call('dsrl_fingerprint_segments', self._fp_table.data_ptr(), self._fp_rows, None, self._fp.data_ptr(), flag.data_ptr(), STALE_BIT, HF._stream())
 
     # ------------------------------------------------------------------ filter operands
-    def _prepare(self, precision):
-        """amax records, w_split and w_planes of every filter under the CURRENT conv arithmetic (`precision`), one launch of each batched kernel."""
-        dev, W = self.device, HF.AMAX_WORDS
-        ents = self._filters
-        s = {'amax': torch.zeros(max(len(ents), 1) * W, device=dev, dtype=torch.int32), 'split': None, 'planes': None, 'wsplit': {}, 'wplanes': {}}
-        if not ents:
-            return s
-        s['split'] = torch.empty(sum(_align(w.numel()) for w, *_ in ents), device=dev, dtype=torch.float32)
-        rows_a, rows_s, tiles, off = [], [], 0, 0
-        for i, (w, K, Kp, RS, C) in enumerate(ents):
-            ct = (C + 31) // 32
-            rec = s['amax'].data_ptr() + 4 * W * i
-            wsp = s['split'][off:off + w.numel()]
-            off += _align(w.numel())
-            s['wsplit'][id(w)] = wsp
-            rows_a.append([w.data_ptr(), 0, K, Kp, RS, C, tiles, ct, rec, 0])               # no transposed copy: the launch only measures
-            rows_s.append([w.data_ptr(), 0, K, Kp, RS, C, tiles, ct, rec, wsp.data_ptr()])  # no transposed split form: inference has no data gradients
-            tiles += RS * ct * ((Kp + 31) // 32)
-        st = HF._stream()
-        ta = torch.tensor(rows_a, dtype=torch.int64, device=dev)
-        ts = torch.tensor(rows_s, dtype=torch.int64, device=dev)
-        call('dsrl_conv2d_transpose_filters_batched', ta.data_ptr(), len(rows_a), tiles, st)
-        call('dsrl_conv2d_split_filters_batched', ts.data_ptr(), len(rows_s), tiles, st)
-        # fp16 planes [K][R][S][C] (two for 'f16x3'; 'f16x1' reads the first): channel counts multiples of 8, as ddp.FlatParams / functional.filter_planes
-        pl = [(i, e) for i, e in enumerate(ents) if e[1] % 8 == 0 and e[4] % 8 == 0] if HF.planes_mode != 'off' else []
-        if pl:
-            lo = lambda n: int(HF.cquery('dsrl_planes_lo_offset', n))        # noqa: E731
-            s['planes'] = torch.empty(sum(2 * lo(e[0].numel()) for _, e in pl), device=dev, dtype=torch.uint8)
-            rows_p, ptiles, poff = [], 0, 0
-            for i, (w, K, Kp, RS, C) in pl:
-                nb = 2 * lo(w.numel())
-                wp = s['planes'][poff:poff + nb]
-                poff += nb
-                s['wplanes'][id(w)] = wp
-                ct = (C + 31) // 32
-                rows_p.append([w.data_ptr(), 0, K, K, RS, C, ptiles, ct, s['amax'].data_ptr() + 4 * W * i, wp.data_ptr()])
-                ptiles += RS * ct * ((K + 31) // 32)
-            tp = torch.tensor(rows_p, dtype=torch.int64, device=dev)
-            call('dsrl_conv2d_filter_planes_batched', tp.data_ptr(), len(rows_p), ptiles, st)
-            s['tables'] = (ta, ts, tp)
-        else:
-            s['tables'] = (ta, ts)
-        return s
+    def _prepare(self):
+        """amax records, w_split and w_planes of every filter under the CURRENT conv arithmetic, one launch of each batched kernel."""
+        ops = FilterOperands(self._filters, self.device, transposed=False)          # no transposed forms: inference has no data gradients
+        if ops.rows:
+            ops.measure(streaming=False)
+            ops.write_split()
+            # fp16 planes [K][R][S][C] (two for 'f16x3'; 'f16x1' reads the first) of every eligible filter
+            if HF.planes_mode != 'off':
+                ops.add_plane_set()
+                ops.write_planes()
+        return ops
 
     def attach(self, precision=None):
         """Presents the operands of conv arithmetic `precision` (default: the current one) through the hooks of functional.py, preparing them on
@@ -163,34 +116,21 @@ class FrozenOperands:
         precision = HF.get_conv_precision() if precision is None else precision
         if precision != HF.get_conv_precision():
             raise DsrlHipError(f'FrozenOperands.attach({precision!r}) while the conv arithmetic is {HF.get_conv_precision()!r}')
-        scaled = precision in ('f16x3', 'f16x1')
-        s = None
-        if scaled:
-            s = self._sets.get(precision)
-            if s is None:
-                with torch.no_grad(), torch.cuda.device(self.device):
-                    s = self._sets[precision] = self._prepare(precision)
-        for i, (w, *_r) in enumerate(self._filters):
-            for a in ('_dsrl_wamax', '_dsrl_wsplit', '_dsrl_wplanes'):
-                if hasattr(w, a):
-                    delattr(w, a)
+        for ops in self._sets.values():
+            ops.detach()
+        for w in self._filters:
             w._dsrl_arena = self
-            if s is not None:
-                w._dsrl_wamax = s['amax'][i * HF.AMAX_WORDS:(i + 1) * HF.AMAX_WORDS]
-                w._dsrl_wsplit = s['wsplit'][id(w)]
-                wp = s['wplanes'].get(id(w))
-                if wp is not None:
-                    w._dsrl_wplanes = wp
-        self.wt_valid = self.split_valid = s is not None
-        self.planes_valid = s is not None and s['planes'] is not None
+        if precision in ('f16x3', 'f16x1'):
+            if precision not in self._sets:
+                with torch.no_grad(), torch.cuda.device(self.device):
+                    self._sets[precision] = self._prepare()
+            self._sets[precision].attach()
         self.precision = precision
 
     def nbytes(self):
         """Bytes of device memory the prepared operands hold (all arithmetics prepared so far, the BatchNorm constants and the fingerprints)."""
         n = self._invstd.numel() * 4 + self._fp.numel() * 8 + self._fp_table.numel() * 8
-        for s in self._sets.values():
-            n += sum(t.numel() * t.element_size() for t in (s['amax'], s['split'], s['planes']) if t is not None)
-        return n
+        return n + sum(ops.nbytes() for ops in self._sets.values())
 
     # ------------------------------------------------------------------ staleness
     def stale_reason(self):
@@ -208,7 +148,7 @@ class FrozenOperands:
         for m, held in self._invstd_held:
             if getattr(m.running_var, '_dsrl_invstd', None) is not held:
                 return 'a BatchNorm ran in train mode and rewrote its running statistics'
-        for w, *_r in self._filters:
+        for w in self._filters:
             if getattr(w, '_dsrl_arena', None) is not self:
                 return 'a filter was bound to another arena (ddp.FlatParams)'
         return None
@@ -226,17 +166,16 @@ class FrozenOperands:
         """Detaches everything: model.predict and model.forward run as they did before the model was frozen."""
         if self.released:
             return
-        for w, *_r in self._filters:
+        for ops in self._sets.values():
+            ops.detach()
+        for w in self._filters:
             if getattr(w, '_dsrl_arena', None) is self:
-                for a in ('_dsrl_arena', '_dsrl_wamax', '_dsrl_wsplit', '_dsrl_wplanes'):
-                    if hasattr(w, a):
-                        delattr(w, a)
+                del w._dsrl_arena
         for m, held in self._invstd_held:
             rv = m.running_var
             if rv is not None and getattr(rv, '_dsrl_invstd', None) is held:
                 del rv._dsrl_invstd
         self._sets, self._invstd_held, self._invstd = {}, [], None
-        self.wt_valid = self.split_valid = self.planes_valid = False
         self.released = True
 
 
@@ -261,12 +200,11 @@ class CompiledPredictor:
     step between two replays sees or disturbs them."""
 
     MAX_GRAPHS = 4
+    GRAPH_WARMUP = HF.GRAPH_WARMUP
 
     def __init__(self, model, batch_size=None, input_size=None, graph=True):
         import time
-        from .command_handlers.train_or_resume import TrainStep
         t0 = time.perf_counter()
-        self.GRAPH_WARMUP = TrainStep.GRAPH_WARMUP
         self.model = model
         self.frozen = FrozenOperands(model)
         self.device = self.frozen.device
@@ -290,46 +228,31 @@ class CompiledPredictor:
         N, _, H, W = images.shape
         return (int(N), int(H), int(W), target is not None, HF.get_conv_precision())
 
-    # ------------------------------------------------------------------ capture (after TrainStep._capture / _capture_or_fall_back)
+    # ------------------------------------------------------------------ capture
     def _capture(self, key, images, target, ignore_index):
+        """-> the captured call; after a capture that failed None, and this predictor stays on the frozen eager path."""
         c = _CapturedPredict()
-        c.img = images.clone()
-        c.tgt = None if target is None else target.clone()
-        c.ignore_index = int(ignore_index)
-        c.flag = torch.zeros((), dtype=torch.int32, device=self.device)
-        c.graph = torch.cuda.CUDAGraph()
-        c.keep = HF.graph_keepalive = []            # pinned host tables captured copies would re-read on every replay
-        HF.capture_host, HF.capture_host_off = torch.empty(1 << 16, dtype=torch.uint8, pin_memory=True), 0      # allocated BEFORE the capture starts
-        c.keep.append(HF.capture_host)
-        _private_gen[0] += 1
-        c.arena = [HF._new_arena(self.device), 0, _private_gen[0], True]      # pinned: it can never be replaced while the graph lives
         try:
-            with HF.amax_private(c.arena):
+            c.img = images.clone()
+            c.tgt = None if target is None else target.clone()
+            c.ignore_index = int(ignore_index)
+            c.flag = torch.zeros((), dtype=torch.int32, device=self.device)
+            c.graph = torch.cuda.CUDAGraph()
+            _private_gen[0] += 1
+            c.arena = [HF._new_arena(self.device), 0, _private_gen[0], True]      # pinned: it can never be replaced while the graph lives
+            with HF.capture_scope(1 << 16) as c.keep, HF.amax_private(c.arena):
                 with torch.cuda.graph(c.graph, capture_error_mode='thread_local'):          # linear: one stream, no side streams in an eval forward
                     c.arena[0].zero_()              # first node: every record a replay maxes into starts at zero
                     c.flag.zero_()
                     c.pred, c.counts, c.ce = self.model.predict(c.img, c.tgt, c.ignore_index, c.flag)
+        except Exception as e:          # noqa: BLE001
+            self.use_graph = False
+            HF.abandon_capture(self.device, e, ' of predict', 'this CompiledPredictor continues on the frozen eager path')
+            return None
         finally:
-            HF.graph_keepalive = None
-            HF.capture_host = None
             HF.drop_planes()
         self._graphs[key] = c
         return c
-
-    def _capture_or_fall_back(self, key, images, target, ignore_index):
-        try:
-            return self._capture(key, images, target, ignore_index)
-        except Exception as e:          # noqa: BLE001
-            print(f'[dsrl] hipGraph capture of predict failed ({type(e).__name__}: {str(e)[:200]}); this CompiledPredictor continues on the frozen eager path',
-                  file=sys.stderr, flush=True)
-            self.use_graph = False
-            HF.graph_keepalive, HF.capture_host = None, None
-            try:
-                torch.cuda.set_stream(torch.cuda.default_stream(self.device))
-                torch.cuda.synchronize(self.device)
-            except Exception:           # noqa: BLE001
-                pass
-            return None
 
     # ------------------------------------------------------------------ the call
     def __call__(self, images, target=None, ignore_index=255, nan_flag=None, copy=True):
@@ -346,7 +269,7 @@ class CompiledPredictor:
             c = None                                # the label to ignore is a launch argument of the captured kernels: this call runs eagerly
         elif (c is None and self.use_graph and len(self._graphs) < self.MAX_GRAPHS and self._warm.get(key, 0) >= self.GRAPH_WARMUP
               and (target is None or (target.dtype == torch.uint8 and tuple(target.shape) == (images.shape[0], 2 * images.shape[2], 2 * images.shape[3])))):
-            c = self._capture_or_fall_back(key, images, target, ignore_index)
+            c = self._capture(key, images, target, ignore_index)
         with torch.no_grad():
             if c is None:
                 self._warm[key] = self._warm.get(key, 0) + 1

@@ -216,6 +216,7 @@ def test_stale_operands_raise_and_release_restores(model):
             bias.copy_(saved)
         cp.release()
     assert not hasattr(model.SSSR_decoder['cls_conv'].weight, '_dsrl_arena') and not hasattr(model.SSSR_decoder['cat_conv'][1].running_var, '_dsrl_invstd')
+    assert not any(hasattr(p, '_dsrl_operands') for p in model.parameters())
     assert _same(_host(model.predict(x, tgt)), want)
     with torch.no_grad():
         for a, b in zip(forward_before, model(x)):
@@ -366,3 +367,58 @@ def test_commands_on_a_compiled_file(model, tmp_path):
         benchmark(weights, bench_ds, 'gpu', 0, 2, model_input_size=(64, 128), output_dir=str(tmp_path / 'x'), compiled_model=True)
     with pytest.raises(RuntimeError, match='compiled_model=True'):
         benchmark(compiled, bench_ds, 'gpu', 0, 2, model_input_size=(64, 128), output_dir=str(tmp_path / 'x'))
+
+
+# ---------------------------------------------------------------------------------------------- 8. one preparer for training and inference
+@pytest.mark.parametrize('precision', ['f16x3', 'f16x1'])
+def test_frozen_operands_equal_the_training_steps(precision):
+    """What inference.FrozenOperands prepares for an eval head and what ddp.FlatParams leaves after zero_grad() + refresh_transposed_filters() on a
+    train-mode twin with the same weights come from the same kernels on the same values through tables built by the same code: the magnitude of every
+    amax record (the maximum over its 16 shards; also max |w| itself), the forward split form and the forward planes are byte-equal, filter by filter.
+    planes_mode 'all' so that both sides hold planes for the same filters (the training side otherwise waits for its convs to ask)."""
+    import gen
+    from hip_helpers import host, make_head
+    from dualsuperreslearningforsemseg_amd import functional as HF
+    from dualsuperreslearningforsemseg_amd.ddp import FlatParams
+    from dualsuperreslearningforsemseg_amd.filter_operands import PLANES
+    from dualsuperreslearningforsemseg_amd.inference import FrozenOperands
+    HF.set_conv_precision(precision)
+    mode_was, HF.planes_mode = HF.planes_mode, 'all'
+    frozen = None
+    try:
+        head, _ = make_head(gen.SMALL, 1, 77, False)
+        twin, _ = make_head(gen.SMALL, 1, 77, True)
+        frozen = FrozenOperands(head)
+        flat = FlatParams(twin)
+        flat.zero_grad()
+        flat.refresh_transposed_filters()
+        torch.cuda.synchronize()
+        a, b = frozen._sets[precision], flat.filters
+        assert a.state == b.state == PLANES and not a.transposed and b.transposed
+        names_a = {id(p): k for k, p in head.named_parameters()}
+        names_b = {id(p): k for k, p in twin.named_parameters()}
+        ia = {names_a[id(w)]: i for i, w in enumerate(a.filters)}
+        ib = {names_b[id(w)]: i for i, w in enumerate(b.filters)}
+        assert set(ia) == set(ib) and len(ia) >= 8
+        mag = lambda ops: ops.amax.view(-1, 16, 16)[:, :, 0].max(dim=1).values.cpu().numpy()       # noqa: E731
+        ma, mb = mag(a), mag(b)
+        with_planes = 0
+        for k in sorted(ia):
+            i, j = ia[k], ib[k]
+            want = np.abs(host(a.filters[i])).max().astype(np.float32).view(np.int32)
+            assert ma[i] == mb[j] == want, (k, int(ma[i]), int(mb[j]), int(want))
+            assert torch.equal(a.split(i).view(torch.int32), b.split(j).view(torch.int32)), k
+            assert a.split(i, True) is None and b.split(j, True) is not None, k
+            pa, pb = a.planes(i), b.planes(j)
+            assert (pa is None) == (pb is None), k
+            if pa is not None:
+                with_planes += 1
+                assert torch.equal(pa, pb), k
+                assert a.planes(i, True) is None and b.planes(j, True) is not None, k
+        assert 1 <= with_planes < len(ia)           # the 19-class cls_conv (K = 19) has no planes on either side
+    finally:
+        if frozen is not None:
+            frozen.release()
+        HF.amax_end_step(torch.device(DEV))
+        HF.wgrad_queue = None
+        HF.planes_mode = mode_was

@@ -1642,6 +1642,7 @@ def test_gradient_sink_matches_autograd_accumulation():
         hip_losses(outs, dev(target), dev(org), 3)[3].backward()
         if flat is not None:
             flat.finish_reduction()              # joins the side stream the weight-gradient kernels ran on
+            HF.amax_end_step(flat.device)        # no optimiser pass ends this step: close its amax arena, or every later test draws its records from it
             assert len(flat._claimed) >= 30
         grads.append({k: host(p.grad) for k, p in head.named_parameters()})
     # BN gradients: the same kernels either way - bit-identical.  Conv weight gradients: the arena path defers them into the grouped launch
@@ -1659,16 +1660,17 @@ def test_batched_filter_transposes_match_per_layer_path():
     model) feeds the dgrad kernels the same transposed filters as the per-call transpose: bit-identical gradients; the copies
     are marked stale by the SGD update."""
     from dualsuperreslearningforsemseg_amd.ddp import FlatParams
+    from dualsuperreslearningforsemseg_amd.filter_operands import STALE
     x16, x4, target, org = gen.make_head_inputs(202, 2, 2, 4, gen.SMALL)
     grads = []
     for batched in (False, True):
         head, _ = make_head(gen.SMALL, 3, 101, True)
         flat = FlatParams(head)
-        assert flat._wt_rows >= 10 and not flat.wt_valid
+        assert flat.filters.rows >= 10 and flat.filters.state == STALE
         flat.zero_grad()
         if batched:
             flat.refresh_transposed_filters()
-            assert flat.wt_valid
+            assert flat.filters.state != STALE
         a = dev(x16).requires_grad_(True); b = dev(x4).requires_grad_(True)
         outs = head(a, b)
         hip_losses(outs, dev(target), dev(org), 3)[3].backward()
@@ -1677,7 +1679,7 @@ def test_batched_filter_transposes_match_per_layer_path():
         g['x16'], g['x4'] = host(a.grad), host(b.grad)
         grads.append(g)
         flat.sgd_step(0.01, 0.9, 5e-4)
-        assert not flat.wt_valid
+        assert flat.filters.state == STALE
     bad = {k: float(np.abs(grads[0][k] - grads[1][k]).max()) for k in grads[0] if not np.array_equal(grads[0][k], grads[1][k])}
     assert not bad, bad
 
@@ -1691,12 +1693,12 @@ def test_streaming_filter_amax_equals_transposing_pass(monkeypatch):
     vals = {}
     for stream in ('1', '0'):
         monkeypatch.setenv('DSRL_FILTER_AMAX_STREAM', stream)
-        flat.wt_valid = False
+        flat.filters.invalidate()
         flat.refresh_transposed_filters()
         torch.cuda.synchronize()
-        vals[stream] = flat.w_amax.view(-1, HF.AMAX_WORDS).max(dim=1).values.cpu().numpy().copy()
-    assert flat._amax_segs > flat._wt_rows and np.array_equal(vals['1'], vals['0'])
-    expect = np.array([np.abs(host(w)).max() for w, *_ in flat._split_entries], dtype=np.float32).view(np.int32)
+        vals[stream] = flat.filters.amax.view(-1, HF.AMAX_WORDS).max(dim=1).values.cpu().numpy().copy()
+    assert flat.filters.amax_segs > flat.filters.rows and np.array_equal(vals['1'], vals['0'])
+    expect = np.array([np.abs(host(w)).max() for w in flat.filters.filters], dtype=np.float32).view(np.int32)
     assert np.array_equal(vals['1'].astype(np.int32), expect)
 
 

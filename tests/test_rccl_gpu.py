@@ -212,12 +212,12 @@ def test_graph_amax_arena_outlives_evaluation_passes():
             model.train()
             assert HF._amax_arena[dev_][0] is arena and arena.data_ptr() == ptr and HF._amax_arena[dev_][1] < HF._AMAX_SLOTS
             # a larger batch shape in between wants plane operands for MORE filters (threshold lowered for this test): their planes come as an additional
-            # set - the table and arenas the first graph was captured with stay where they are (ddp.FlatParams._build_plane_filters)
-            sets_before = [(st['table'].data_ptr(), st['arenas'][0].data_ptr()) for st in flat._plane_sets]
+            # set - the table and arenas the first graph was captured with stay where they are (filter_operands.FilterOperands.add_plane_set)
+            sets_before = [(st['table'].data_ptr(), st['arenas'][0].data_ptr()) for st in flat.filters.plane_sets]
             big = list(SyntheticCityscapes(2, (128, 256), torch.device(DEV), length=3, distinct=1))
             hist += [step(img_, org_, tgt_, 0.006, 0.9, 5e-4, True)[0] for (img_, org_), (tgt_, _) in big]
-            assert [(st['table'].data_ptr(), st['arenas'][0].data_ptr()) for st in flat._plane_sets][:len(sets_before)] == sets_before
-            assert len(flat._plane_sets) > len(sets_before) >= 1
+            assert [(st['table'].data_ptr(), st['arenas'][0].data_ptr()) for st in flat.filters.plane_sets][:len(sets_before)] == sets_before
+            assert len(flat.filters.plane_sets) > len(sets_before) >= 1
             hist += [step(img, org, tgt, 0.006, 0.9, 5e-4, True)[0] for (img, org), (tgt, _) in batches]
         finally:
             HF.overlap_wgrad = was
@@ -281,7 +281,7 @@ def test_optimiser_pass_leaves_the_filter_magnitudes(graph, monkeypatch):
         flat.refresh_transposed_filters()       # fold: keeps the optimiser's records; else: measures the current weights - the same numbers
         torch.cuda.synchronize()
         # a record = 16 shards (which shard a block maxes into depends on its block index): the magnitude is the maximum over the shards
-        res[fold] = (hist + more, flat.p_flat.clone(), flat.w_amax.view(-1, 16, 16)[:, :, 0].max(dim=1).values.clone(), flat.wsplit_flat.clone())
+        res[fold] = (hist + more, flat.p_flat.clone(), flat.filters.amax.view(-1, 16, 16)[:, :, 0].max(dim=1).values.clone(), flat.filters.wsplit_flat.clone())
         step.release()
     assert res['1'][0] == res['0'][0], (res['1'][0][-1], res['0'][0][-1])
     for a, b in zip(res['1'][1:], res['0'][1:]):

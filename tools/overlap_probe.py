@@ -66,12 +66,8 @@ def graphed(f):
     prep()
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
-    HF.graph_keepalive = []
-    try:
-        with torch.cuda.graph(g):
-            out = f()
-    finally:
-        keep, HF.graph_keepalive = HF.graph_keepalive, None
+    with HF.capture_scope(1 << 16) as keep, torch.cuda.graph(g):
+        out = f()
     g._keep = (keep, out)
     return g.replay
 
