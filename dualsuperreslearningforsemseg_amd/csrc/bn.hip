@@ -769,13 +769,16 @@ constexpr int kMergeRows = 4;      // partial rows a thread requests at once in 
 // statistics pass and the device-wide barrier of bn_fused_fwd_kernel disappear: a block = (32-channel group) x (row slab) merges
 // the <= 256 partials of its own 32 channels (fp64, fixed order: every block of a group gets bit-identical statistics) and streams
 // x -> y once.  Any number of blocks; slab-0 blocks publish mean / invstd and update the running statistics.
-template <int THREADS>
+// MASK: the launch also leaves the sign mask of the stored y (the pointer is null and unused without it: the kernel of dsrl_bn_train_fwd_from_stats,
+// 113 / 102 / 102 VGPRs for 1024 / 512 / 256 threads as before the mask existed; with MASK 114 / 102 / 102, no scratch: tools/kernel_resources.py)
+template <int THREADS, bool MASK = false>
 __global__ __launch_bounds__(THREADS) void bn_stats_apply_kernel(const float* __restrict__ x, int ldx, float* __restrict__ y, int ldy, int P, int C,
                                                               int groups, int rows_per_slab, float eps, float momentum,
                                                               float* __restrict__ mean_out, float* __restrict__ invstd_out, float* __restrict__ rm, float* __restrict__ rv,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
                                                               const float* __restrict__ res, int ldr, int relu, float drop_p, SeedArg seed_arg, unsigned rng_stream,
-                                                              const float* __restrict__ part, int nparts, unsigned* __restrict__ y_amax) {
+                                                              const float* __restrict__ part, int nparts, unsigned* __restrict__ y_amax,
+                                                              unsigned* __restrict__ mask) {
     const unsigned long long seed = seed_arg.dev ? *seed_arg.dev : seed_arg.value;     // device-resident key: replayable from a graph
     constexpr int KG = THREADS / 32, RP = THREADS / 8;      // row groups of the merge, tensor rows per pass
     __shared__ double shm[KG][3][32];
@@ -870,10 +873,41 @@ __global__ __launch_bounds__(THREADS) void bn_stats_apply_kernel(const float* __
         }
         ST4(y, p, ldy, q) = make_float4(v[0], v[1], v[2], v[3]);
         am = abs_bits4(am, v[0], v[1], v[2], v[3]);
+        if constexpr (MASK) {
+            // sign mask of the stored row, mask[grp][p]: bit j = (y[p][32 grp + j] > 0).  The 8 lanes of a row (all in or all out of this call) hold
+            // one nibble each; a wave's 8 rows are 8 consecutive words.  The backward kernels read the bit instead of y (relu == 2).
+            unsigned w = ((v[0] > 0.f ? 1u : 0u) | (v[1] > 0.f ? 2u : 0u) | (v[2] > 0.f ? 4u : 0u) | (v[3] > 0.f ? 8u : 0u)) << (4 * l8);
+            w |= __shfl_xor(w, 1); w |= __shfl_xor(w, 2); w |= __shfl_xor(w, 4);
+            if (l8 == 0) mask[(long long)grp * P + p] = w;
+        }
     };
     if (p0 < row1) row(p0, xv0, rv0);
+    if constexpr (!MASK) {
 #pragma unroll 4
-    for (int p = p0 + RP; p < row1; p += RP) {
+        for (int p = p0 + RP; p < row1; p += RP) {
+            const float4 xv = LD4(x, p, ldx, q);
+            float4 r = xv;
+            if (res) r = LD4(res, p, ldr, q);
+            row(p, xv, r);
+        }
+        amax_publish(am, y_amax);
+        return;
+    }
+    // with the mask: four rows in flight written out by hand - hipcc refuses `#pragma unroll 4` on a loop of unknown trip count that holds the
+    // lane exchange (a convergent operation; -Wpass-failed "loop not unrolled"), and the rolled loop would keep one row of loads in flight
+    int p = p0 + RP;
+    for (; p + 3 * RP < row1; p += 4 * RP) {
+        float4 xv[4], r[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            xv[u] = LD4(x, p + u * RP, ldx, q);
+            r[u] = xv[u];
+            if (res) r[u] = LD4(res, p + u * RP, ldr, q);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) row(p + u * RP, xv[u], r[u]);
+    }
+    for (; p < row1; p += RP) {
         const float4 xv = LD4(x, p, ldx, q);
         float4 r = xv;
         if (res) r = LD4(res, p, ldr, q);
@@ -978,9 +1012,17 @@ __global__ __launch_bounds__(THREADS) void bn_bwd_stats_apply_kernel(const float
     // first row and per-channel constants requested before the merge (see bn_stats_apply_kernel)
     const int row0 = slab * rows_per_slab, row1 = min(P, row0 + rows_per_slab), p0 = row0 + rr;
     float4 dv0 = make_float4(0.f, 0.f, 0.f, 0.f), xv0 = dv0, yv0 = make_float4(1.f, 1.f, 1.f, 1.f), x2v0 = dv0;
+    // relu == 2: y addresses the sign mask [C / 32][ldy] the forward left (bn_stats_apply_kernel); a thread's four channels are nibble l8 of word
+    // (grp, p), and the row's "y" is 1 where the bit is set and 0 where not - the same y > 0 for masked_grad
+    const unsigned* __restrict__ mrow = reinterpret_cast<const unsigned*>(y) + (relu == 2 ? (long long)grp * ldy : 0ll);
+    auto mask_row = [&](int p) {
+        const unsigned w = mrow[p] >> (4 * l8);
+        return make_float4((w & 1u) ? 1.f : 0.f, (w & 2u) ? 1.f : 0.f, (w & 4u) ? 1.f : 0.f, (w & 8u) ? 1.f : 0.f);
+    };
     if (p0 < row1) {
         dv0 = LD4(dy, p0, lddy, q); xv0 = LD4(x, p0, ldx, q);
-        if (relu) yv0 = LD4(y, p0, ldy, q);
+        if (relu == 2) yv0 = mask_row(p0);
+        else if (relu) yv0 = LD4(y, p0, ldy, q);
         if constexpr (RES2) x2v0 = LD4(r2.x, p0, r2.ldx, q);
     }
     float mu2[4] = {0.f, 0.f, 0.f, 0.f}, is2[4] = {0.f, 0.f, 0.f, 0.f}, sg2[4] = {0.f, 0.f, 0.f, 0.f}, sgx2[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1061,7 +1103,8 @@ __global__ __launch_bounds__(THREADS) void bn_bwd_stats_apply_kernel(const float
     for (int p = p0 + RP; p < row1; p += RP) {
         const float4 dv = LD4(dy, p, lddy, q), xv = LD4(x, p, ldx, q);
         float4 yv = make_float4(1.f, 1.f, 1.f, 1.f);
-        if (relu) yv = LD4(y, p, ldy, q);
+        if (relu == 2) yv = mask_row(p);
+        else if (relu) yv = LD4(y, p, ldy, q);
         float4 x2v = xv;
         if constexpr (RES2) x2v = LD4(r2.x, p, r2.ldx, q);
         row(p, dv, xv, yv, x2v);
@@ -1453,10 +1496,22 @@ extern "C" int dsrl_bn_train_fwd(const float* x, int ldx, float* y, int ldy, int
     return dsrl_bn_apply(x, ldx, y, ldy, P, C, mean, invstd, gamma, beta, residual, ldr, relu, drop_p, seed, rng_stream, y_amax, stream);
 }
 
+extern "C" size_t dsrl_bn_mask_words(int64_t P, int C) { return (P > 0 && C > 0 && C % 32 == 0) ? (size_t)(C / 32) * (size_t)P : 0; }
+
 extern "C" int dsrl_bn_train_fwd_from_stats(const float* x, int ldx, float* y, int ldy, int64_t P, int C, float eps, float momentum, float* mean, float* invstd,
                                             float* running_mean, float* running_var, const float* gamma, const float* beta, const float* residual, int ldr,
                                             int relu, float drop_p, uint64_t seed, uint32_t rng_stream, float* stats, int stats_parts, uint32_t* y_amax,
                                             dsrl_stream_t stream) {
+    return dsrl_bn_train_fwd_from_stats_mask(x, ldx, y, ldy, P, C, eps, momentum, mean, invstd, running_mean, running_var, gamma, beta, residual, ldr, relu, drop_p, seed,
+                                             rng_stream, stats, stats_parts, y_amax, nullptr, stream);
+}
+// ... and the sign mask of the stored y with it: mask [C / 32][P] words (dsrl_bn_mask_words), bit j of word (g, p) = (y[p][32 g + j] > 0) - what a backward
+// pass needs of y behind a ReLU (dsrl_bn_bwd_from_stats*, dsrl_conv2d_dgrad_*: relu == 2).  mask == null: the launch above.
+extern "C" int dsrl_bn_train_fwd_from_stats_mask(const float* x, int ldx, float* y, int ldy, int64_t P, int C, float eps, float momentum, float* mean, float* invstd,
+                                                 float* running_mean, float* running_var, const float* gamma, const float* beta, const float* residual, int ldr,
+                                                 int relu, float drop_p, uint64_t seed, uint32_t rng_stream, float* stats, int stats_parts, uint32_t* y_amax,
+                                                 uint32_t* mask, dsrl_stream_t stream) {
+    DSRL_REQUIRE(((uintptr_t)mask % 4) == 0, DSRL_E_BADARG, "bn_train_fwd_from_stats: unaligned mask");
     DSRL_REQUIRE(x && y && mean && invstd && gamma && beta && stats && P > 0 && P < (1ll << 31) && C > 0 && ldx >= C && ldy >= C, DSRL_E_BADARG, "bn_train_fwd_from_stats: bad arguments");
     DSRL_REQUIRE(stats_parts > 0 && stats_parts <= 4096, DSRL_E_BADARG, "bn_train_fwd_from_stats: %d row blocks of partials (1..4096)", stats_parts);
     DSRL_REQUIRE(C % 32 == 0 && vec4_ok(C, {ldx, ldy, residual ? ldr : 0}, {x, y, residual}), DSRL_E_UNSUPPORTED,
@@ -1474,9 +1529,11 @@ extern "C" int dsrl_bn_train_fwd_from_stats(const float* x, int ldx, float* y, i
     const int T = stats_apply_threads(P, C, stats_parts), rows_per_slab = stats_apply_rows(P, groups, T), slabs = (int)ceil_div(P, (int64_t)rows_per_slab);
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3((unsigned)(groups * slabs)), dim3(T), 0, st, x, ldx, y, ldy, (int)P, C, groups, rows_per_slab, eps, momentum,
-                           mean, invstd, running_mean, running_var, gamma, beta, residual, ldr, relu, drop_p, seed_arg(seed), (unsigned)rng_stream, stats, stats_parts, y_amax);
+                           mean, invstd, running_mean, running_var, gamma, beta, residual, ldr, relu, drop_p, seed_arg(seed), (unsigned)rng_stream, stats, stats_parts, y_amax,
+                           (unsigned*)mask);
     };
-    if (T == 1024) go(bn_stats_apply_kernel<1024>); else if (T == 512) go(bn_stats_apply_kernel<512>); else go(bn_stats_apply_kernel<256>);
+    if (mask) { if (T == 1024) go(bn_stats_apply_kernel<1024, true>); else if (T == 512) go(bn_stats_apply_kernel<512, true>); else go(bn_stats_apply_kernel<256, true>); }
+    else if (T == 1024) go(bn_stats_apply_kernel<1024>); else if (T == 512) go(bn_stats_apply_kernel<512>); else go(bn_stats_apply_kernel<256>);
     return launch_status("bn_stats_apply_kernel");
 }
 
@@ -1569,7 +1626,10 @@ static int bn_bwd_from_stats_impl(const float* x, int ldx, const float* y, int l
     DSRL_REQUIRE(x && dy && dx && mean && invstd && gamma && stats && P > 0 && P < (1ll << 31) && C > 0, DSRL_E_BADARG, "bn_bwd_from_stats: bad arguments");
     DSRL_REQUIRE(y || !relu, DSRL_E_BADARG, "bn_bwd_from_stats: forward output needed for the relu mask");
     DSRL_REQUIRE(stats_parts > 0 && stats_parts <= 4096, DSRL_E_BADARG, "bn_bwd_from_stats: %d row blocks of partials (1..4096)", stats_parts);
-    DSRL_REQUIRE(C % 32 == 0 && vec4_ok(C, {ldx, y ? ldy : 0, lddy, lddx, dresidual ? lddr : 0}, {x, y, dy, dx, dresidual}), DSRL_E_UNSUPPORTED,
+    const bool bits = relu == 2;        // y is the sign mask [C / 32][ldy] of dsrl_bn_train_fwd_from_stats_mask
+    DSRL_REQUIRE(relu == 0 || relu == 1 || bits, DSRL_E_BADARG, "bn_bwd_from_stats: relu = %d (0, 1, or 2 = y is the sign mask)", relu);
+    DSRL_REQUIRE(!bits || (ldy >= P && ((uintptr_t)y % 4) == 0), DSRL_E_BADARG, "bn_bwd_from_stats: sign mask with rows of %d words for %lld pixels, or unaligned", ldy, (long long)P);
+    DSRL_REQUIRE(C % 32 == 0 && vec4_ok(C, {ldx, (y && !bits) ? ldy : 0, lddy, lddx, dresidual ? lddr : 0}, {x, bits ? nullptr : y, dy, dx, dresidual}), DSRL_E_UNSUPPORTED,
                  "bn_bwd_from_stats: C (%d) must be a multiple of 32, strides multiples of 4, pointers 16-byte aligned", C);
     hipStream_t st = (hipStream_t)stream;
     if (int e = bind_stream_device(st)) return e;

@@ -84,7 +84,7 @@ struct ConvArgs {
     // split kernels, dgrad: the output is the gradient w.r.t. the output y = relu(bn(x)) of a BatchNorm; the epilogue leaves the
     // partial sums of g = dy * [y > 0] and g * xhat per (row block, channel) in bstats [2][parts][K] (null: off)
     const float* bn_x; const float* bn_y; const float* bn_mean; const float* bn_invstd; float* bstats;
-    int bn_ldx, bn_ldy, bn_relu;
+    int bn_ldx, bn_ldy, bn_relu;          // bn_relu == 2: bn_y addresses the sign mask uint32 [K / 32][bn_ldy] of that output (bn.hip: bn_stats_apply_kernel), not y itself
     float bn_gscale;                      // factor on the masked gradient: 1 / (1 - p) when a Dropout sits behind the BatchNorm's ReLU (round 5), else 1
     int bn_fast;                          // KG == 1 builds: the BatchNorm-backward sums through LDS with 16-byte loads of x / y (host: alignment, K % 4 == 0, no parity order)
     // split kernels, dgrad of a strided conv (par = stride > 1, else 0): the GEMM rows are ordered by parity class - M-tile t (pbm rows) holds
@@ -118,6 +118,12 @@ __device__ __forceinline__ int dgrad_pix(const ConvArgs& a, int m) {        // r
     const int ph = c / a.par, pw = c - ph * a.par;
     return (n * a.Ho + hh * a.par + ph) * a.Wo + wh * a.par + pw;
 }
+
+// bn_relu == 2: the word of the sign mask that holds channel k of pixel px (bit k % 32 = y > 0), and a nibble of it as the "y" of four channels (1 or 0)
+__device__ __forceinline__ unsigned bn_mask_word(const ConvArgs& a, int k, long long px) {
+    return reinterpret_cast<const unsigned*>(a.bn_y)[(long long)(k >> 5) * a.bn_ldy + px];
+}
+__device__ __forceinline__ float4 bn_mask4(unsigned w) { return make_float4((w & 1u) ? 1.f : 0.f, (w & 2u) ? 1.f : 0.f, (w & 4u) ? 1.f : 0.f, (w & 8u) ? 1.f : 0.f); }
 
 // Blocks are dealt round-robin over the 8 XCDs (private L2 each). Remap the linear block id so that every XCD works on a contiguous
 // range of tile ids (bijective for any count): tiles that share input rows then hit the same L2. Speed only, never correctness.

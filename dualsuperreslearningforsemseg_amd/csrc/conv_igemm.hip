@@ -1629,6 +1629,11 @@ extern "C" int dsrl_conv2d_filters_amax_batched(const int64_t* table, int64_t ns
 }
 
 struct DgradBn { const float* x; const float* y; const float* mean; const float* invstd; float* stats; int ldx, ldy, relu; float gscale = 1.f; };
+// relu: 0 none, 1 y is the BatchNorm's output [N*H*W][ldy >= C], 2 y is its sign mask, uint32 [C / 32][ldy >= N*H*W] (dsrl_bn_train_fwd_from_stats_mask)
+static bool bn_y_ok(const float* y, int ldy, int relu, int N, int H, int W, int C) {
+    if (relu == 2) return y != nullptr && C % 32 == 0 && (long long)ldy >= (long long)N * H * W && ((uintptr_t)y % 4) == 0;
+    return relu == 0 || (relu == 1 && y != nullptr && ldy >= C);
+}
 static int dgrad_impl(const float* dy, int lddy, const float* w, const float* wt_in, float* dx, int lddx,
                       int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil,
                       void* ws, size_t ws_bytes, dsrl_stream_t stream, int accumulate, const DgradBn* bn = nullptr,
@@ -1707,7 +1712,8 @@ static int dgrad_impl(const float* dy, int lddy, const float* w, const float* wt
     if (bn) {
         a.bn_x = bn->x; a.bn_y = bn->y; a.bn_mean = bn->mean; a.bn_invstd = bn->invstd; a.bstats = bn->stats; a.bn_ldx = bn->ldx; a.bn_ldy = bn->ldy; a.bn_relu = bn->relu;
         a.bn_gscale = bn->gscale;
-        a.bn_fast = a.par == 0 && C % 4 == 0 && bn->ldx % 4 == 0 && (!bn->relu || bn->ldy % 4 == 0) && ((uintptr_t)bn->x % 16) == 0 && (!bn->relu || ((uintptr_t)bn->y % 16) == 0) &&
+        const bool y4 = bn->relu != 1 || (bn->ldy % 4 == 0 && ((uintptr_t)bn->y % 16) == 0);        // float4 rows of y (the sign mask is read by words)
+        a.bn_fast = a.par == 0 && C % 4 == 0 && bn->ldx % 4 == 0 && y4 && ((uintptr_t)bn->x % 16) == 0 &&
                     ((uintptr_t)bn->mean % 16) == 0 && ((uintptr_t)bn->invstd % 16) == 0 && ((uintptr_t)bn->stats % 16) == 0;
     }
     return launch_igemm<true>(a, p.cfg, st);
@@ -1730,7 +1736,7 @@ extern "C" int dsrl_conv2d_dgrad_bnstats(const float* dy, int lddy, const float*
                                          void* ws, size_t ws_bytes, const float* bn_x, int bn_ldx, const float* bn_y, int bn_ldy,
                                          const float* bn_mean, const float* bn_invstd, int bn_relu, float* bstats, int stats_parts, int accumulate,
                                          dsrl_stream_t stream) {
-    DSRL_REQUIRE(bn_x && bn_mean && bn_invstd && bstats && (bn_y || !bn_relu) && bn_ldx >= C && (!bn_relu || bn_ldy >= C), DSRL_E_BADARG, "conv2d_dgrad_bnstats: bad BatchNorm arguments");
+    DSRL_REQUIRE(bn_x && bn_mean && bn_invstd && bstats && bn_ldx >= C && bn_y_ok(bn_y, bn_ldy, bn_relu, N, H, W, C), DSRL_E_BADARG, "conv2d_dgrad_bnstats: bad BatchNorm arguments");
     DSRL_REQUIRE(dsrl_conv2d_dgrad_stats_parts(N, H, W, C, K, R, S, stride, pad, dil) == stats_parts && stats_parts > 0, DSRL_E_BADARG,
                  "conv2d_dgrad_bnstats: this launch writes %d row blocks of partials, the caller expects %d",
                  dsrl_conv2d_dgrad_stats_parts(N, H, W, C, K, R, S, stride, pad, dil), stats_parts);
@@ -1934,7 +1940,7 @@ extern "C" int dsrl_conv2d_dgrad_amax(const float* dy, int lddy, const uint32_t*
                                       dsrl_stream_t stream) {
     if (bstats == nullptr)
         return dgrad_impl(dy, lddy, w, wt_in, dx, lddx, N, H, W, C, K, R, S, stride, pad, dil, ws, ws_bytes, stream, accumulate ? 1 : 0, nullptr, dy_amax, w_amax, wt_split);
-    DSRL_REQUIRE(bn_x && bn_mean && bn_invstd && (bn_y || !bn_relu) && bn_ldx >= C && (!bn_relu || bn_ldy >= C), DSRL_E_BADARG, "conv2d_dgrad_amax: bad BatchNorm arguments");
+    DSRL_REQUIRE(bn_x && bn_mean && bn_invstd && bn_ldx >= C && bn_y_ok(bn_y, bn_ldy, bn_relu, N, H, W, C), DSRL_E_BADARG, "conv2d_dgrad_amax: bad BatchNorm arguments");
     DSRL_REQUIRE(dsrl_conv2d_dgrad_stats_parts(N, H, W, C, K, R, S, stride, pad, dil) == stats_parts && stats_parts > 0, DSRL_E_BADARG,
                  "conv2d_dgrad_amax: this launch writes %d row blocks of partials, the caller expects %d",
                  dsrl_conv2d_dgrad_stats_parts(N, H, W, C, K, R, S, stride, pad, dil), stats_parts);
@@ -1968,7 +1974,7 @@ extern "C" int dsrl_conv2d_dgrad_planes_drop(const float* dy, int lddy, const ui
     if (bstats == nullptr)
         return dgrad_impl(dy, lddy, w, wt_in, dx, lddx, N, H, W, C, K, R, S, stride, pad, dil, ws, ws_bytes, stream, accumulate ? 1 : 0, nullptr, dy_amax, w_amax, wt_split,
                           dy_planes, wt_planes);
-    DSRL_REQUIRE(bn_x && bn_mean && bn_invstd && (bn_y || !bn_relu) && bn_ldx >= C && (!bn_relu || bn_ldy >= C), DSRL_E_BADARG, "conv2d_dgrad_planes: bad BatchNorm arguments");
+    DSRL_REQUIRE(bn_x && bn_mean && bn_invstd && bn_ldx >= C && bn_y_ok(bn_y, bn_ldy, bn_relu, N, H, W, C), DSRL_E_BADARG, "conv2d_dgrad_planes: bad BatchNorm arguments");
     DSRL_REQUIRE(dsrl_conv2d_dgrad_stats_parts(N, H, W, C, K, R, S, stride, pad, dil) == stats_parts && stats_parts > 0, DSRL_E_BADARG,
                  "conv2d_dgrad_planes: this launch writes %d row blocks of partials, the caller expects %d",
                  dsrl_conv2d_dgrad_stats_parts(N, H, W, C, K, R, S, stride, pad, dil), stats_parts);

@@ -390,7 +390,8 @@ void conv_planes_kernel(const ConvArgs a) {
                     const int m = mrow0 + r0_ + RSTEP * (b0 + u);
                     const bool ok = kok4 && m < a.M;
                     xv[u] = ok ? *reinterpret_cast<const float4*>(a.bn_x + (long long)m * a.bn_ldx + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    yv[u] = (ok && a.bn_relu) ? *reinterpret_cast<const float4*>(a.bn_y + (long long)m * a.bn_ldy + kk) : make_float4(1.f, 1.f, 1.f, 1.f);
+                    if (a.bn_relu == 2) yv[u] = bn_mask4(ok ? bn_mask_word(a, kk, m) >> (kk & 31) : 15u);         // the lane's four channels: one nibble of the sign mask
+                    else yv[u] = (ok && a.bn_relu) ? *reinterpret_cast<const float4*>(a.bn_y + (long long)m * a.bn_ldy + kk) : make_float4(1.f, 1.f, 1.f, 1.f);
                 }
 #pragma unroll
                 for (int u = 0; u < NB; ++u) {
@@ -441,7 +442,8 @@ void conv_planes_kernel(const ConvArgs a) {
                     const bool ok = kok && m < a.M;
                     const long long px = m;
                     xv[e] = ok ? a.bn_x[px * a.bn_ldx + k] : 0.f;
-                    yv[e] = (ok && a.bn_relu) ? a.bn_y[px * a.bn_ldy + k] : 1.f;
+                    if (a.bn_relu == 2) yv[e] = (!ok || ((bn_mask_word(a, k, px) >> (k & 31)) & 1u)) ? 1.f : 0.f;     // one bit of the sign mask
+                    else yv[e] = (ok && a.bn_relu) ? a.bn_y[px * a.bn_ldy + k] : 1.f;
                 }
 #pragma unroll
                 for (int e = 0; e < EPG; ++e) {

@@ -709,10 +709,14 @@ bn_bwd_stats_enabled = knob('DSRL_BN_BWD_STATS', True)
 # 4-byte loads of x / y).  Round 5: on since that epilogue reads float4 rows through LDS (conv_split_kernel.h, bn_fast): +0.65 % step throughput, 29 of the 45
 # device-wide-barrier BatchNorm launches become streaming from-sums launches (profiles/round5_ab.txt)
 bn_bwd_stats_shared = knob('DSRL_BN_BWD_STATS_SHARED', True)
+# Backward needs y = relu(bn(x)) only for the test y > 0.  The from-statistics forward leaves that bit per element (uint32 [C / 32][P], dsrl_bn_train_fwd_from_stats_mask)
+# and the from-statistics backward and the linked data-gradient epilogues read it instead of y (relu == 2): a 32nd of the bytes, the same gradients bit for bit.
+# 0: no mask is allocated and backward reads y.
+bn_mask_enabled = knob('DSRL_BN_MASK', True)
 
 
 class BNLink:
-    __slots__ = ('x', 'y_ptr', 'y_shape', 'mean', 'invstd', 'relu', 'valid', 'stats', 'parts', 'dx_ptr', 'shared', 'drop_p')
+    __slots__ = ('x', 'y_ptr', 'y_shape', 'mean', 'invstd', 'relu', 'valid', 'stats', 'parts', 'dx_ptr', 'shared', 'drop_p', 'mask')
 
     def __init__(self, shared=False):
         self.x = self.mean = self.invstd = self.stats = None      # the BN output itself is NOT kept (it may carry this link: no cycles)
@@ -720,6 +724,8 @@ class BNLink:
         self.relu, self.valid, self.parts, self.dx_ptr = False, False, 0, 0
         self.shared = shared        # y feeds the two consumers of a GradSlot: the accumulating (= last) dgrad completes its gradient
         self.drop_p = 0.0           # a Dropout(p) behind the BN's ReLU (round 5): y is the tensor behind it, its zeros are the combined mask
+        self.mask = None            # the sign mask of y the forward left (bn_mask_enabled), or None: the data gradient reads y; P * C / 8 bytes kept
+                                    # alive until the next forward overwrites the link
 
 
 class _Fork(torch.autograd.Function):
@@ -862,8 +868,10 @@ class _Conv2d(torch.autograd.Function):
                 # x is y = relu(bn(.)) of a BatchNorm that feeds only this conv: leave its backward partial sums with the data gradient
                 bstats = torch.empty(cquery('dsrl_bn_stats_floats', 2, parts, Cc), device=x.device, dtype=torch.float32)
                 _, bld = pm(link.x)
+                # the BatchNorm's ReLU mask: its sign bits when the forward left them (relu == 2: pointer and row length of the mask), else y itself
+                ym = (link.mask.data_ptr(), N * H * W, 2) if (link.mask is not None and link.relu) else (x.data_ptr(), ldx, int(link.relu))
                 call('dsrl_conv2d_dgrad_planes_drop', dy.data_ptr(), lddy, p_(dya), p_(dyp), w.data_ptr(), wt_ptr, p_(wa), p_(wtsp), p_(wtpl), dx.data_ptr(), Cc, *shp,
-                     ws.data_ptr(), ws.numel(), link.x.data_ptr(), bld, x.data_ptr(), ldx, link.mean.data_ptr(), link.invstd.data_ptr(), int(link.relu),
+                     ws.data_ptr(), ws.numel(), link.x.data_ptr(), bld, ym[0], ym[1], link.mean.data_ptr(), link.invstd.data_ptr(), ym[2],
                      float(link.drop_p), bstats.data_ptr(), parts, int(acc), st)
                 link.stats, link.parts, link.dx_ptr = bstats, parts, dx.data_ptr()
             else:
@@ -982,6 +990,7 @@ class _BNAct(torch.autograd.Function):
         if residual is not None:
             residual, ldr = pm(residual)
             res_ptr = residual.data_ptr()
+        mask = None                 # sign bits of y, left by the from-statistics forward behind a ReLU (bn_mask_enabled)
         if training:
             if P <= 1:
                 raise ValueError(f'Expected more than 1 value per channel when training, got input size {tuple(x.shape)}')
@@ -989,10 +998,13 @@ class _BNAct(torch.autograd.Function):
             mean = torch.empty(Cc, device=x.device, dtype=torch.float32)
             invstd = torch.empty_like(mean)
             if stats is not None and stats_parts > 0:
-                call('dsrl_bn_train_fwd_from_stats', x.data_ptr(), ldx, y.data_ptr(), Cc, P, Cc, float(eps), float(momentum), mean.data_ptr(), invstd.data_ptr(),
+                if relu and bn_mask_enabled and Cc % 32 == 0:
+                    mask = torch.empty(cquery('dsrl_bn_mask_words', P, Cc), device=x.device, dtype=torch.int32)
+                call('dsrl_bn_train_fwd_from_stats' if mask is None else 'dsrl_bn_train_fwd_from_stats_mask', x.data_ptr(), ldx, y.data_ptr(), Cc, P, Cc,
+                     float(eps), float(momentum), mean.data_ptr(), invstd.data_ptr(),
                      None if running_mean is None else running_mean.data_ptr(), None if running_var is None else running_var.data_ptr(),
                      gamma.data_ptr(), beta.data_ptr(), res_ptr, ldr, int(relu), float(drop_p), int(seed), int(rng_stream),
-                     stats.data_ptr(), int(stats_parts), ya_ptr, st)
+                     stats.data_ptr(), int(stats_parts), ya_ptr, *(() if mask is None else (mask.data_ptr(),)), st)
             else:
                 call('dsrl_bn_train_fwd', x.data_ptr(), ldx, y.data_ptr(), Cc, P, Cc, float(eps), float(momentum), mean.data_ptr(), invstd.data_ptr(),
                      None if running_mean is None else running_mean.data_ptr(), None if running_var is None else running_var.data_ptr(),
@@ -1009,8 +1021,10 @@ class _BNAct(torch.autograd.Function):
         if ya is not None:
             set_amax(y, ya)
         ctx.save_for_backward(x, y, mean, invstd, gamma)
+        ctx.mask = mask
         if out_link is not None and (drop_p == 0.0 or relu) and Cc % 32 == 0 and ldx == Cc:
             out_link.x, out_link.mean, out_link.invstd, out_link.relu, out_link.valid = x, mean, invstd, bool(relu), True
+            out_link.mask = mask
             out_link.y_ptr, out_link.y_shape, out_link.drop_p = y.data_ptr(), tuple(y.shape), float(drop_p)
         ctx.cfg = (bool(training), bool(relu), float(drop_p), residual is not None)
         ctx.gb = (gamma, beta) if isinstance(gamma, torch.nn.Parameter) and isinstance(beta, torch.nn.Parameter) else None
@@ -1038,19 +1052,20 @@ class _BNAct(torch.autograd.Function):
         if link is not None and link.stats is not None and link.dx_ptr == dy.data_ptr() and lddy == Cc and (drop_p == 0.0 or relu):
             # the gradient we received is the buffer the consuming conv's dgrad wrote, and it left our two per-channel sums with it
             rl = ctx.res_link
+            ym = (ctx.mask.data_ptr(), P, 2) if (ctx.mask is not None and relu) else (y.data_ptr(), Cc, int(relu))       # relu == 2: the sign mask and its row length in y's place
             rparts = int(query('dsrl_bn_bwd_from_stats_res_parts', P, Cc, int(link.parts))) if (rl is not None and dres is not None and bn_res_stats_enabled) else 0
             if rparts > 0:
                 # ... and the masked gradient we write to dres is the output gradient of the downsample branch's BatchNorm: leave its sums as well
                 rstats = torch.empty(cquery('dsrl_bn_stats_floats', 2, rparts, Cc), device=x.device, dtype=torch.float32)
                 _, rld = pm(rl.x)
-                call('dsrl_bn_bwd_from_stats_res', x.data_ptr(), ldx, y.data_ptr(), Cc, dy.data_ptr(), lddy, dx.data_ptr(), Cc, dres.data_ptr(), Cc, P, Cc,
-                     mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), int(relu), float(drop_p), int(training),
+                call('dsrl_bn_bwd_from_stats_res', x.data_ptr(), ldx, ym[0], ym[1], dy.data_ptr(), lddy, dx.data_ptr(), Cc, dres.data_ptr(), Cc, P, Cc,
+                     mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ym[2], float(drop_p), int(training),
                      link.stats.data_ptr(), int(link.parts), dxa_ptr, rl.x.data_ptr(), rld, rl.mean.data_ptr(), rl.invstd.data_ptr(), rstats.data_ptr(), rparts, _stream())
                 rl.stats, rl.parts, rl.dx_ptr = rstats, rparts, dres.data_ptr()
             else:
-                call('dsrl_bn_bwd_from_stats_drop', x.data_ptr(), ldx, y.data_ptr(), Cc, dy.data_ptr(), lddy, dx.data_ptr(), Cc,
+                call('dsrl_bn_bwd_from_stats_drop', x.data_ptr(), ldx, ym[0], ym[1], dy.data_ptr(), lddy, dx.data_ptr(), Cc,
                      None if dres is None else dres.data_ptr(), Cc, P, Cc, mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(),
-                     dgamma.data_ptr(), dbeta.data_ptr(), int(relu), float(drop_p), int(training), link.stats.data_ptr(), int(link.parts), dxa_ptr, _stream())
+                     dgamma.data_ptr(), dbeta.data_ptr(), ym[2], float(drop_p), int(training), link.stats.data_ptr(), int(link.parts), dxa_ptr, _stream())
         else:
             ws = _ws(cquery('dsrl_bn_workspace_bytes', P, Cc), x)
             call('dsrl_bn_bwd', x.data_ptr(), ldx, y.data_ptr(), Cc, dy.data_ptr(), lddy, dx.data_ptr(), Cc,

@@ -255,6 +255,17 @@ int dsrl_bn_train_fwd_from_stats(const float* x, int ldx, float* y, int ldy, int
                                  float* running_mean /*nullable*/, float* running_var /*nullable*/, const float* gamma, const float* beta,
                                  const float* residual /*nullable*/, int ldr, int relu, float drop_p, uint64_t seed, uint32_t rng_stream,
                                  float* stats, int stats_parts, uint32_t* y_amax /*nullable*/, dsrl_stream_t stream);
+/* ... that also leaves the sign mask of the stored y (behind residual add, ReLU and Dropout): mask [C / 32][P] 32-bit words, dsrl_bn_mask_words(P, C)
+ * of them (0 when C is no multiple of 32), bit j of word (g, p) set iff y[p][32 g + j] > 0.  y, mean, invstd, the running statistics and y_amax are
+ * those of dsrl_bn_train_fwd_from_stats; mask == NULL is that call.  Readers take the mask in place of y: relu (bn_relu) == 2 in
+ * dsrl_bn_bwd_from_stats / _drop / _res and in dsrl_conv2d_dgrad_bnstats / _amax / _planes / _planes_drop means that the y (bn_y) pointer addresses
+ * the mask and ldy (bn_ldy) is its row length P - one bit instead of four bytes per element, the same gradients bit for bit.  In those calls relu
+ * (bn_relu) must be 0, 1 (y is the output) or 2 (y is the mask); any other value is DSRL_E_BADARG. */
+size_t dsrl_bn_mask_words(int64_t P, int C);
+int dsrl_bn_train_fwd_from_stats_mask(const float* x, int ldx, float* y, int ldy, int64_t P, int C, float eps, float momentum, float* mean, float* invstd,
+                                      float* running_mean /*nullable*/, float* running_var /*nullable*/, const float* gamma, const float* beta,
+                                      const float* residual /*nullable*/, int ldr, int relu, float drop_p, uint64_t seed, uint32_t rng_stream,
+                                      float* stats, int stats_parts, uint32_t* y_amax /*nullable*/, uint32_t* mask /*nullable*/, dsrl_stream_t stream);
 /* The fused small-tensor BN kernels (dsrl_bn_train_fwd / dsrl_bn_bwd) cross a device-wide barrier: all blocks of a launch (128, or
  * 256 for tensors of 4.2-8.4 M elements; one 512-thread block per CU) must become resident together, so they assume that the process
  * has the GPU to itself apart from its own streams. dsrl_bn_fused_max_blocks: 0 = never use them, 128 = the 128-block variant only (what
