@@ -139,6 +139,9 @@ PROTOTYPES = {
     'dsrl_prepare_batch': (i32, [fp, fp, fp, C.POINTER(f32), C.POINTER(f32), fp, fp, fp, i32, i32, i32, i32, i32, stream_t]),
     'dsrl_augment_geometry': (i32, [fp, fp, fp, fp, fp, fp, i32, i32, i32, stream_t]),
     'dsrl_prepare_batch_augmented': (i32, [fp, fp, fp, C.POINTER(f32), C.POINTER(f32), fp, fp, fp, i32, i32, i32, i32, i32, fp, stream_t]),
+    'dsrl_colour_jitter_workspace_bytes': (sz, [i32, i32, i32]),
+    'dsrl_colour_jitter_means': (i32, [fp, fp, fp, fp, sz, i32, i32, i32, stream_t]),
+    'dsrl_prepare_batch_jittered': (i32, [fp, fp, fp, C.POINTER(f32), C.POINTER(f32), fp, fp, fp, i32, i32, i32, i32, i32, fp, fp, fp, stream_t]),
     'dsrl_sgd_step': (i32, [fp, fp, fp, i64, f32, f32, f32, f32, stream_t]),
     'dsrl_sgd_step_dev': (i32, [fp, fp, fp, i64, fp, stream_t]),
     'dsrl_sgd_step_dev_segments': (i32, [fp, fp, fp, fp, i64, fp, stream_t]),

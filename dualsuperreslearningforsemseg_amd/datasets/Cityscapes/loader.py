@@ -134,13 +134,15 @@ class _Slot:
 class CityscapesLoader:
     """Device batches ((input_image, input_org), (target, _)) of one split from the cache.
 
-    train: per-epoch permutation partitioned across ranks, drop_last, DeviceJointAugmentation (parameters drawn per (seed, epoch, sample index));
+    train: per-epoch permutation partitioned across ranks, drop_last, DeviceJointAugmentation (parameters drawn per (seed, epoch, sample index);
+           with dataset['color_jitter'] its colour jitter as well);
     val:   file order, every sample (drop_last=False), DeviceBatchPreparation only."""
 
     def __init__(self, cache, batch_size, device, transform, rank=0, world=1, train=True, seed=0, prefetch=2):
         self.cache, self.bs, self.device, self.transform = cache, int(batch_size), torch.device(device), transform
         self.rank, self.world, self.train, self.seed = rank, world, train, seed
         self.augment = isinstance(transform, DeviceJointAugmentation)
+        self.jitter = self.augment and transform.jitter          # the batch table then carries the colour-jitter rows as a third section
         self.prefetch = max(1, int(prefetch))
         self.epoch = 0
         self._slots = None
@@ -170,7 +172,7 @@ class CityscapesLoader:
             rgb[j] = c.rgb[i]
             lab[j] = c.labels[i]
         if self.augment:
-            rows = pack_table(self.transform.draw(epoch, ids, (c.height, c.width)), c.width, c.height)
+            rows = pack_table(self.transform.draw(epoch, ids, (c.height, c.width)), c.width, c.height, self.jitter)
             slot.table.numpy()[:rows.size] = rows
 
     def _worker(self, batches, epoch, free, ready, stop):
@@ -197,7 +199,7 @@ class CityscapesLoader:
         with torch.cuda.stream(self._stream):
             rgb = slot.rgb[:n].to(dev, non_blocking=True)
             lab = slot.labels[:n].to(dev, non_blocking=True)
-            table = slot.table[:table_bytes(n, self.cache.width, self.cache.height)].to(dev, non_blocking=True) if self.augment else None
+            table = slot.table[:table_bytes(n, self.cache.width, self.cache.height, self.jitter)].to(dev, non_blocking=True) if self.augment else None
             slot.copied = torch.cuda.Event()
             slot.copied.record(self._stream)
             if self.augment:
@@ -218,7 +220,7 @@ class CityscapesLoader:
         c = self.cache
         if self._slots is None:
             self._stream = torch.cuda.Stream(self.device)
-            self._slots = [_Slot(self.bs, c.height, c.width, table_bytes(self.bs, c.width, c.height)) for _ in range(self.prefetch + 2)]
+            self._slots = [_Slot(self.bs, c.height, c.width, table_bytes(self.bs, c.width, c.height, self.jitter)) for _ in range(self.prefetch + 2)]
         free, ready, stop = queue.Queue(), queue.Queue(), threading.Event()
         for s in self._slots:
             free.put(s)
@@ -276,7 +278,8 @@ def loader_factory(dataset, model_input_size, seed, distributed=False):
     def factory(split, batch_size, device, rank, world):
         cache = CityscapesCache(cache_dir, split)
         if split == 'train':
-            tf = DeviceJointAugmentation(ds.LABEL_MAPPING_DICT, ds.MEAN, ds.STD, model_input_size, ds.IGNORE_CLASS_LABEL, seed=seed)
+            tf = DeviceJointAugmentation(ds.LABEL_MAPPING_DICT, ds.MEAN, ds.STD, model_input_size, ds.IGNORE_CLASS_LABEL, seed=seed,
+                                         color_jitter=dataset.get('color_jitter'))
             return CityscapesLoader(cache, batch_size, device, tf, rank, world, train=True, seed=seed)
         tf = DeviceBatchPreparation(ds.LABEL_MAPPING_DICT, ds.MEAN, ds.STD, model_input_size, ds.IGNORE_CLASS_LABEL)
         return CityscapesLoader(cache, batch_size, device, tf, 0, 1, train=False, seed=seed)

@@ -471,6 +471,35 @@ int dsrl_prepare_batch_augmented(const uint8_t* rgb, const uint8_t* labels, cons
                                  float* img_in, float* img_org, uint8_t* target, int N, int Hs, int Ws, int H, int W,
                                  const dsrl_augment_params* params /*device, N rows*/, dsrl_stream_t stream);
 
+/* JointColorJitter (models/transforms/JointColorJitter.py), opt-in: one 64-byte row per sample in device memory beside the dsrl_augment_params rows.
+ * On the float image x in [0, 1] (the geometry output / 255, before flip, blur and grayscale) the enabled operations run in the order of
+ * order[], each followed by a clamp to [0, 1]; gray(x) = 0.2989 R + 0.587 G + 0.114 B (torchvision 0.8.1 functional_tensor):
+ *   brightness  x <- b x;   contrast  x <- c x + (1 - c) m, m = mean of gray(x) over the sample as x is at that point;
+ *   saturation  x <- s x + (1 - s) gray(x);   hue  out[j] = sum_i x[i] hue[3 i + j] (the reference's rotation matrix for hue_factor * 2 pi). */
+#define DSRL_JITTER_BRIGHTNESS 0
+#define DSRL_JITTER_CONTRAST 1
+#define DSRL_JITTER_SATURATION 2
+#define DSRL_JITTER_HUE 3
+typedef struct dsrl_colour_jitter_params {
+    int32_t order[4];                      /* DSRL_JITTER_* in application order; -1: a disabled slot; any other value is skipped */
+    float brightness, contrast, saturation; /* factors b, c, s                                                                     */
+    float hue[9];                          /* row-major 3x3 M, computed on the host in double                                     */
+} dsrl_colour_jitter_params;
+/* Bytes of workspace dsrl_colour_jitter_means needs for N samples of Hs x Ws: a function of these three alone. */
+size_t dsrl_colour_jitter_workspace_bytes(int N, int Hs, int Ws);
+/* means[n] = contrast's m (0..1 scale) of sample n of rgb (N,Hs,Ws,3) uint8: the mean over the sample of gray after the operations in front of
+ * contrast in that sample's order.  Double partial sums per block, then one wave per sample in a fixed order: no atomics, the same bits on every
+ * call with the same buffers.  The entry of a sample without an enabled contrast is left untouched (nothing reads it).  jitter, means 4-byte and
+ * ws 8-byte aligned; ws_bytes >= the query (DSRL_E_WORKSPACE otherwise). */
+int dsrl_colour_jitter_means(const uint8_t* rgb, const dsrl_colour_jitter_params* jitter /*device, N rows*/, float* means /*device, N*/, void* ws,
+                             size_t ws_bytes, int N, int Hs, int Ws, dsrl_stream_t stream);
+/* dsrl_prepare_batch_augmented with the colour jitter applied to every uint8 pixel a tap reads (so the blur's nine taps read jittered pixels and no
+ * float copy of the full-size image exists); means from dsrl_colour_jitter_means on the same rgb and rows.  jitter and means must not be null. */
+int dsrl_prepare_batch_jittered(const uint8_t* rgb, const uint8_t* labels, const uint8_t* lut /*256*/, const float* mean /*3*/, const float* std /*3*/,
+                                float* img_in, float* img_org, uint8_t* target, int N, int Hs, int Ws, int H, int W,
+                                const dsrl_augment_params* params /*device, N rows*/, const dsrl_colour_jitter_params* jitter /*device, N rows*/,
+                                const float* means /*device, N*/, dsrl_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * optimiser + bookkeeping on the flat parameter arena (train_or_resume.py:63-66, 445, 426-433)
  * ---------------------------------------------------------------------------------------------- */

@@ -5,7 +5,10 @@
 2. TrainStep images/s fed by CityscapesLoader (synthetic full-size uint8 cache written to --cache, augmentation on the side stream) against
    SyntheticCityscapes device batches, in the same process, alternating A/B/A/B.
 
-Usage: python tools/augment_bench.py [--reps 100] [--steps 30] [--images 48] [--cache DIR]"""
+With --color-jitter B C S H (JointColorJitter's arguments; the reference's commented-out values are 0.4 0.4 0.4 0.4) the colour-jitter kernels are
+timed too and the loader runs once without and once with jitter in every round (profiles/augment_colour_jitter.txt).
+
+Usage: python tools/augment_bench.py [--reps 100] [--steps 30] [--images 48] [--cache DIR] [--color-jitter 0.4 0.4 0.4 0.4]"""
 import argparse
 import json
 import os
@@ -64,6 +67,7 @@ def main():
     ap.add_argument('--images', type=int, default=48)
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--cache', default=None)
+    ap.add_argument('--color-jitter', type=float, nargs=4, default=None, metavar=('B', 'C', 'S', 'H'))
     args = ap.parse_args()
     import dualsuperreslearningforsemseg_amd as D
     from dualsuperreslearningforsemseg_amd import settings
@@ -90,6 +94,19 @@ def main():
     res['prepare_augmented_ms'] = event_median(lambda: aug.prepare(g_rgb, g_lab, table), args.reps)
     res['prepare_batch_ms'] = event_median(lambda: prep(g_rgb, g_lab), args.reps)
     res['augment_call_ms (table upload + both kernels)'] = event_median(lambda: aug(rgb, lab, table), args.reps)
+    augj = None
+    if args.color_jitter is not None:
+        from dualsuperreslearningforsemseg_amd.models.transforms.augment import jitter_offset
+        augj = DeviceJointAugmentation(cs.LABEL_MAPPING_DICT, cs.MEAN, cs.STD, size, cs.IGNORE_CLASS_LABEL, seed=settings.RANDOM_SEED,
+                                       color_jitter=tuple(args.color_jitter))
+        psj = augj.draw(0, range(B), (Hs, Ws))
+        assert [p[:7] for p in psj] == [p[:7] for p in ps]
+        tablej = augj.table(psj, Ws, Hs, dev)
+        rows = tablej.data_ptr() + jitter_offset(B, Ws, Hs)
+        means = augj.jitter_means(g_rgb, rows)
+        res['colour_jitter_means_ms'] = event_median(lambda: augj.jitter_means(g_rgb, rows), args.reps)
+        res['prepare_jittered_ms (means given)'] = event_median(lambda: augj._prepare(g_rgb, g_lab, tablej, means), args.reps)
+        res['augment_call_ms, jitter (geometry + means + jittered)'] = event_median(lambda: augj(rgb, lab, tablej), args.reps)
     t0 = time.perf_counter()
     for e in range(20):
         aug.draw(e, range(B), (Hs, Ws))
@@ -100,6 +117,8 @@ def main():
         pack_table(ps, Ws, Hs)
     res['host_pack_ms_per_batch'] = (time.perf_counter() - t0) / 20 * 1e3
     flags = {k: sum(getattr(p, k) for p in ps) for k in ('flip', 'blur', 'gray')}
+    if augj is not None:
+        print(f'colour jitter {augj.color_jitter}; contrast enabled in {sum(p.jitter.contrast is not None for p in psj)} of {B} samples')
     print(f'kernels, B={B}, {Hs}x{Ws} -> {size[0]}x{size[1]} / {2 * size[0]}x{2 * size[1]} (median, min of {args.reps} runs, HIP events; drawn flags {flags}):')
     for k, v in res.items():
         print(f'  {k:48s} ' + (f'{v[0]:.4f} ms (min {v[1]:.4f})' if isinstance(v, tuple) else f'{v:.4f} ms'))
@@ -126,6 +145,9 @@ def main():
     step = TrainStep(model, flat, 3, 0.1, 1.0, cs.IGNORE_CLASS_LABEL)
     synth = SyntheticCityscapes(B, size, dev, length=args.steps)
     loader = L.CityscapesLoader(L.CityscapesCache(cache, 'train'), B, dev, aug, train=True, seed=settings.RANDOM_SEED)
+    loaders = {'loader': loader}
+    if augj is not None:
+        loaders['loader+jitter'] = L.CityscapesLoader(L.CityscapesCache(cache, 'train'), B, dev, augj, train=True, seed=settings.RANDOM_SEED)
     hp = (0.006, 0.9, 5e-4)
 
     def run(it, n):
@@ -143,21 +165,22 @@ def main():
         torch.cuda.synchronize()
         return k, time.perf_counter() - t0
 
-    def loader_batches(n):
+    def loader_batches(ld):
         while True:
-            for b in loader:
+            for b in ld:
                 yield b
 
     run(synth, 6)
-    warm = loader_batches(6)
-    run(warm, 6)
-    warm.close()
-    rates = {'synthetic': [], 'loader': []}
+    for ld in loaders.values():
+        warm = loader_batches(ld)
+        run(warm, 6)
+        warm.close()
+    rates = {name: [] for name in ('synthetic', *loaders)}
     for r in range(args.rounds):
-        for name in ('synthetic', 'loader'):
-            it = iter(synth) if name == 'synthetic' else loader_batches(args.steps)
+        for name in rates:
+            it = iter(synth) if name == 'synthetic' else loader_batches(loaders[name])
             k, el = run(it, args.steps)
-            if name == 'loader':
+            if name != 'synthetic':
                 it.close()               # stops the loader's reader thread before the next run starts one
             rates[name].append(k * B / el)
     s, l_ = statistics.median(rates['synthetic']), statistics.median(rates['loader'])
@@ -165,6 +188,10 @@ def main():
     print(f'  SyntheticCityscapes   {s:8.1f} img/s   runs {[round(v, 1) for v in rates["synthetic"]]}')
     print(f'  CityscapesLoader      {l_:8.1f} img/s   runs {[round(v, 1) for v in rates["loader"]]}')
     print(f'  loader / synthetic    {100 * l_ / s:8.1f} %')
+    if augj is not None:
+        j_ = statistics.median(rates['loader+jitter'])
+        print(f'  CityscapesLoader, colour jitter {j_:8.1f} img/s   runs {[round(v, 1) for v in rates["loader+jitter"]]}')
+        print(f'  loader+jitter / synthetic {100 * j_ / s:8.1f} %')
     step.release()
     if tmp is not None:
         tmp.cleanup()
