@@ -5,7 +5,9 @@ What differs by design: the model runs `DSRL.predict` (the SSSR tail, the arg-ma
 memory), the batches come through the `loader_factory` protocol of train_or_resume (dataset['loader_factory'] when given, else the Cityscapes cache
 without augmentation, every sample), and the host reads the device ONCE, after the last batch, instead of copying every batch's logits back.
 `compiled_model=True` in other_args: `weights` names a file of the compile_model command and the batches run through inference.CompiledPredictor (the
-full batch and the last short one are two of its graph keys); the figures are the same."""
+full batch and the last short one are two of its graph keys); the figures are the same.
+`flip=True` in other_args: every batch is evaluated as the horizontal-flip ensemble (`DSRL.predict(flip=True)`: the image and its mirror image, class
+probabilities averaged); benchmark.txt then says so."""
 import os
 from datetime import datetime
 
@@ -56,13 +58,14 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
     else:
         model = load_eval_model(weights, ds, device_obj)
     predict = model.predict if predictor is None else predictor
+    flip = bool(other_args.get('flip'))
     loader = split_loader(dataset, split, batch_size, device_obj, input_size)
 
     nan_flag = t.zeros((), dtype=t.int32, device=device_obj)
     ces, tables = [], []
     try:
         for (input_image, _), (target, _) in loader:
-            _, counts, ce = predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag)
+            _, counts, ce = predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag, flip=flip)
             ces.append(ce)
             tables.append(counts)
         if not ces:
@@ -95,6 +98,9 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
     with open(os.path.join(output_dir, 'benchmark.txt'), 'w') as f:
         f.write("Benchmarking results on the dataset's {:s} split\n\n".format(split))
         f.write('On: {:s}\n'.format(started.strftime('%c')))
-        f.write('Weights file: {:s}\n\n'.format(str(weights)))
+        f.write('Weights file: {:s}\n'.format(str(weights)))
+        if flip:
+            f.write('Horizontal-flip ensemble: class probabilities of the image and its mirror image averaged\n')
+        f.write('\n')
         f.write('\n'.join(lines) + '\n')
     return result

@@ -6,7 +6,9 @@ was trained with (the reference's torchvision Resize here is a different one); t
 (no window, no wait for a key) and returns the files it wrote.  `compiled_model=True`: `weights` names a file written by the compile_model command
 (data, not TorchScript) and the class maps come from inference.CompiledPredictor - frozen operands and a hipGraph replay, the same bytes.  Either
 way the input | class colours | overlay panels are built on the device (utils.make_input_output_visualization_device): what crosses to the host
-per image is the finished uint8 panel, which PIL encodes."""
+per image is the finished uint8 panel, which PIL encodes.  `flip=True` in other_args: the class maps are those of the horizontal-flip ensemble
+(`DSRL.predict(flip=True)`)."""
+import functools
 import os
 
 import numpy as np
@@ -49,6 +51,8 @@ def test(image_file, images_dir, dataset, output_dir, weights, device, compiled_
         model = load_eval_model(weights, ds, device_obj)
         predict = model.predict
     try:
+        if other_args.get('flip'):
+            predict = functools.partial(predict, flip=True)
         return _run(predict, image_file, images_dir, dataset, ds, output_dir, device_obj, input_size, output_size)
     finally:
         if predictor is not None:

@@ -196,6 +196,237 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
     }
 }
 
+// Horizontal-flip ensemble of the same tail: x holds 2 N images, image N + n is the tail input of the MIRRORED image n, still in the mirrored frame.
+// The lane of pixel p = (n, h, w) also loads pixel (N + n, h, W - 1 - w), whose 4x4 patch is the same patch of the class map mirrored left to right:
+// its output pixel (tap1 = (i1, j1), tap2 = (i2, j2)) in the un-mirrored frame is view b's ((i1, 1 - j1), (i2, 1 - j2)).  Tap indices are 2 i + j, so
+// stage-2 step T feeds view b's mid[.][T ^ 1] to a second set of stage-2 fragments built with tap2 ^ 1 (a2b), and the lane that holds the 19 logits of an
+// output pixel of view a then holds the 19 logits of view b for the SAME pixel.  Per view: max, exp(v - max), sum; the class is the first maximum of
+// ea_c / sa + eb_c / sb, the loss -(logaddexp(la_t, lb_t) - ln 2) of the two log-softmax values in log space (finite where the averaged probability
+// underflows).  View a is reduced to its 19 probabilities before view b's accumulators are formed, so only one set of accumulators is live at a time.
+// Counters, partials, NaN flag and the byte assembly are those of sssr_tail_predict_kernel.
+template <bool TGT, bool CE>
+__global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w1,
+                                                                         const float* __restrict__ bn_mean, const float* __restrict__ bn_invstd,
+                                                                         const float* __restrict__ bn_gamma, const float* __restrict__ bn_beta,
+                                                                         const float* __restrict__ w2, const float* __restrict__ bias2,
+                                                                         unsigned char* __restrict__ pred, const unsigned char* __restrict__ target,
+                                                                         int ignore_index, unsigned long long* __restrict__ counts, double* __restrict__ part,
+                                                                         int* __restrict__ nan_flag, int H, int W, long long P, int ntiles) {
+    __shared__ unsigned hist[3 * kPC + 2];
+    __shared__ double shd[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int px = lane & 15, g = lane >> 4;
+    if (TGT) {
+        for (int t = tid; t < 3 * kPC + 2; t += 256) hist[t] = 0u;
+        __syncthreads();
+    }
+    // Stage-2 fragments stay in registers (two sets: a2 for view a, a2b with tap2 ^ 1 for view b).  The stage-1 fragments do not fit beside them and
+    // both views' mid pixels: they are re-read per tile (w1 is 5.8 KB, cache-resident; 25 loads against 250 MFMAs) through an offset the compiler
+    // cannot see through, so that it does not hoist them back out of the tile loop.  Padding rows / k-steps read a clamped address and are zeroed.
+    float a2[kPT][kPT], a2b[kPT][kPT];
+#pragma unroll
+    for (int t = 0; t < kPT; ++t)
+#pragma unroll
+        for (int s = 0; s < kPT; ++s) {
+            const int k = 4 * s + g;
+            const int tap2 = px >> 2, cls = 4 * t + (px & 3);
+            a2[t][s] = (k < kPC && cls < kPC) ? w2[(k * kPC + cls) * 4 + tap2] : 0.f;
+            a2b[t][s] = (k < kPC && cls < kPC) ? w2[(k * kPC + cls) * 4 + (tap2 ^ 1)] : 0.f;
+        }
+    // a1[t][s] = w1[((4 s + g) * 19 + 4 t + (px >> 2)) * 4 + (px & 3)]: one lane offset plus 304 s + 16 t; s = 4 needs g < 3, t = 4 needs (px >> 2) < 3
+    const bool k_ok = g < 3, cm_ok = (px >> 2) < 3;
+    const int gc = k_ok ? g : 0, qc = cm_ok ? (px >> 2) : 0;
+    const int w1off[2][2] = {{(g * kPC + (px >> 2)) * 4 + (px & 3), (gc * kPC + (px >> 2)) * 4 + (px & 3)},
+                             {(g * kPC + qc) * 4 + (px & 3), (gc * kPC + qc) * 4 + (px & 3)}};
+    auto a1load = [&](float (&a1)[kPT][kPT]) {
+        int o[2][2] = {{w1off[0][0], w1off[0][1]}, {w1off[1][0], w1off[1][1]}};
+        asm volatile("" : "+v"(o[0][0]), "+v"(o[0][1]), "+v"(o[1][0]), "+v"(o[1][1]));
+#pragma unroll
+        for (int t = 0; t < kPT; ++t)
+#pragma unroll
+            for (int s = 0; s < kPT; ++s) {
+                const float v = w1[o[t == 4][s == 4] + 304 * s + 16 * t];
+                a1[t][s] = ((s < 4 || k_ok) && (t < 4 || cm_ok)) ? v : 0.f;
+            }
+    };
+    float sc[kPT], sh[kPT];
+#pragma unroll
+    for (int t = 0; t < kPT; ++t) {
+        const int cm = 4 * t + g;
+        sc[t] = cm < kPC ? bn_gamma[cm] * bn_invstd[cm] : 0.f;
+        sh[t] = cm < kPC ? bn_beta[cm] - bn_mean[cm] * sc[t] : 0.f;
+    }
+    float bv[4 * kPT];
+#pragma unroll
+    for (int c = 0; c < 4 * kPT; ++c) bv[c] = (bias2 != nullptr && c < kPC) ? bias2[c] : 0.f;
+
+    const int i2 = g >> 1, j2 = g & 1;
+    const long long HW = (long long)H * W;
+    const int Wo = 4 * W;
+    double ce_loss = 0.0, ce_cnt = 0.0;
+    bool bad = false, bad_label = false;
+    unsigned nanbits = 0u;
+
+    // view a: pixel p; view b: the pixel of image N + n at column W - 1 - w, i.e. p + P + (W - 1 - 2 w)
+    auto xload = [&](int tile, float (&xa)[kPT], float (&xb)[kPT]) {
+        const long long p = (long long)tile * 16 + px;
+        const bool in = tile < ntiles && p < P;
+        const long long q = in ? p + P + (W - 1 - 2 * ((int)p % W)) : 0;           // p < P <= INT_MAX / 16
+#pragma unroll
+        for (int s = 0; s < kPT; ++s) {
+            const bool ld = in && 4 * s + g < kPC;
+            xa[s] = ld ? x[p * ldx + 4 * s + g] : 0.f;
+            xb[s] = ld ? x[q * ldx + 4 * s + g] : 0.f;
+        }
+    };
+    // stage 1 of one view: the 2x2 mid pixels after BatchNorm and ReLU
+    auto stage1 = [&](const float (&a1)[kPT][kPT], const float (&xv)[kPT], f32x4_p (&mid)[kPT]) {
+#pragma unroll
+        for (int t = 0; t < kPT; ++t) mid[t] = f32x4_p{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < kPT; ++s)
+#pragma unroll
+            for (int t = 0; t < kPT; ++t) mid[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[t][s], xv[s], mid[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < kPT; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float z = fmaf(mid[t][r], sc[t], sh[t]);
+                nanbits = max(nanbits, abs_bits(z));        // the ReLU would hide a NaN of the input from the logits (lanes past the end hold zeros)
+                mid[t][r] = fmaxf(z, 0.f);
+            }
+    };
+    // stage 2 of one view for one mid pixel, reduced to what the ensemble needs: v[c] <- exp(v[c] - max) / sum; returns log_softmax(v)[ts]
+    auto softmax_of = [&](const float (&aw)[kPT][kPT], const f32x4_p (&mid)[kPT], int T, int ts, const float (&b0)[4 * kPT], float (&v)[kPC]) {
+        f32x4_p acc[kPT];
+#pragma unroll
+        for (int t = 0; t < kPT; ++t) acc[t] = f32x4_p{b0[4 * t], b0[4 * t + 1], b0[4 * t + 2], b0[4 * t + 3]};
+#pragma unroll
+        for (int s = 0; s < kPT; ++s)
+#pragma unroll
+            for (int t = 0; t < kPT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[t][s], mid[s][T], acc[t], 0, 0, 0);
+#pragma unroll
+        for (int c = 0; c < kPC; ++c) v[c] = acc[c >> 2][c & 3];
+        float m = v[0], vt = v[0];
+#pragma unroll
+        for (int c = 1; c < kPC; ++c) {
+            m = fmaxf(m, v[c]);
+            if (CE) vt = (c == ts) ? v[c] : vt;
+        }
+        float sum = 0.f;
+#pragma unroll
+        for (int c = 0; c < kPC; ++c) { v[c] = exp_nonpos(v[c] - m); sum += v[c]; }
+        bad |= !(sum == sum);               // any NaN logit poisons the sum (fmaxf alone would skip it)
+        const float inv = 1.f / sum;
+#pragma unroll
+        for (int c = 0; c < kPC; ++c) v[c] *= inv;
+        return CE ? (vt - m) - logf(sum) : 0.f;
+    };
+
+    const int stride = (int)gridDim.x * 4;
+    int tile = (int)blockIdx.x * 4 + wv;
+    float xa[kPT], xb[kPT];
+    xload(tile, xa, xb);
+    for (; tile < ntiles; tile += stride) {
+        float a1[kPT][kPT];
+        a1load(a1);
+        const long long p = (long long)tile * 16 + px;
+        const bool valid = p < P;
+        const long long pc = valid ? p : P - 1;
+        const int n = (int)(pc / HW);
+        const int rem = (int)(pc - (long long)n * HW);
+        const int h = rem / W, w = rem - h * W;
+        const long long obase = ((long long)n * 4 * H + 4 * h) * Wo + 4 * w;        // first byte of the pixel's 4x4 patch
+        unsigned tw[2] = {0u, 0u};
+        if (TGT && valid) {
+            tw[0] = *reinterpret_cast<const unsigned*>(target + obase + (long long)i2 * Wo);
+            tw[1] = *reinterpret_cast<const unsigned*>(target + obase + (long long)(2 + i2) * Wo);
+        }
+        f32x4_p mid_a[kPT], mid_b[kPT];
+        stage1(a1, xa, mid_a);
+        stage1(a1, xb, mid_b);
+        xload(tile + stride, xa, xb);               // the next tile's pixels are in flight while stage 2 of this one is computed
+        unsigned packed = 0u;
+#pragma unroll
+        for (int T = 0; T < 4; ++T) {
+            int tg = 0, ts = 0;
+            if (TGT) {
+                tg = (int)((tw[T >> 1] >> (8 * (2 * (T & 1) + j2))) & 0xffu);
+                ts = min(tg == ignore_index ? 0 : tg, kPC - 1);
+            }
+            float pa[kPC], pb[kPC];
+            // One set of accumulators at a time.  Left alone the compiler issues the MFMAs of both views, and of the next output pixel, ahead of the
+            // softmax arithmetic and spills.  Empty asm statements keep their order: each set of accumulators starts from bias values that pass through
+            // one, behind a statement that needs what the previous set was reduced to (the class byte of the pixel before; view a's pa[]).
+            float ba[4 * kPT], bb[4 * kPT];
+#pragma unroll
+            for (int c = 0; c < 4 * kPT; ++c) ba[c] = bb[c] = bv[c];
+            asm volatile("" : "+v"(packed), "+v"(ba[0]), "+v"(ba[1]), "+v"(ba[2]), "+v"(ba[3]), "+v"(ba[4]), "+v"(ba[5]), "+v"(ba[6]), "+v"(ba[7]), "+v"(ba[8]),
+                         "+v"(ba[9]), "+v"(ba[10]), "+v"(ba[11]), "+v"(ba[12]), "+v"(ba[13]), "+v"(ba[14]), "+v"(ba[15]), "+v"(ba[16]), "+v"(ba[17]), "+v"(ba[18]),
+                         "+v"(ba[19]));
+            const float la = softmax_of(a2, mid_a, T, ts, ba, pa);
+            asm volatile("" : "+v"(pa[0]), "+v"(pa[1]), "+v"(pa[2]), "+v"(pa[3]), "+v"(pa[4]), "+v"(pa[5]), "+v"(pa[6]), "+v"(pa[7]), "+v"(pa[8]), "+v"(pa[9]),
+                         "+v"(pa[10]), "+v"(pa[11]), "+v"(pa[12]), "+v"(pa[13]), "+v"(pa[14]), "+v"(pa[15]), "+v"(pa[16]), "+v"(pa[17]), "+v"(pa[18]));
+            asm volatile("" : "+v"(bb[0]), "+v"(bb[1]), "+v"(bb[2]), "+v"(bb[3]), "+v"(bb[4]), "+v"(bb[5]), "+v"(bb[6]), "+v"(bb[7]), "+v"(bb[8]), "+v"(bb[9]),
+                         "+v"(bb[10]), "+v"(bb[11]), "+v"(bb[12]), "+v"(bb[13]), "+v"(bb[14]), "+v"(bb[15]), "+v"(bb[16]), "+v"(bb[17]), "+v"(bb[18]), "+v"(bb[19]));
+            const float lb = softmax_of(a2b, mid_b, T ^ 1, ts, bb, pb);
+            int best = 0;
+            float bestv = pa[0] + pb[0];
+#pragma unroll
+            for (int c = 1; c < kPC; ++c) {
+                const float e = pa[c] + pb[c];
+                if (e > bestv) { bestv = e; best = c; }                 // first maximum, as seg_metrics_kernel and torch.argmax
+            }
+            packed |= (unsigned)best << (8 * T);
+            if (TGT) {
+                const bool lab_bad = valid && tg != ignore_index && tg >= kPC;
+                bad_label |= lab_bad;
+                if (counts != nullptr && valid && tg != ignore_index && tg < kPC) {
+                    atomicAdd(&hist[best], 1u);
+                    atomicAdd(&hist[2 * kPC + tg], 1u);
+                    atomicAdd(&hist[3 * kPC + 1], 1u);
+                    if (best == tg) { atomicAdd(&hist[kPC + tg], 1u); atomicAdd(&hist[3 * kPC], 1u); }
+                }
+                if (CE && valid && tg != ignore_index) {
+                    // log(0.5 (pa_t + pb_t)) = logaddexp(la, lb) - ln 2, in log space
+                    constexpr float LN2 = 0.693147182464599609375f;
+                    const float e = fmaxf(la, lb) + log1pf(exp_nonpos(-fabsf(la - lb))) - LN2;
+                    ce_loss -= (double)e;
+                    ce_cnt += 1.0;
+                }
+            }
+        }
+        // row 2 i1 + i2 of the patch, columns 2 j1 + j2: this lane has j2, the lane 16 further on has the other one; lane j2 writes row i1 = j2
+        const unsigned other = (unsigned)__shfl_xor((int)packed, 16, 64);
+        const unsigned b0 = j2 ? (other >> 16) & 0xffu : packed & 0xffu;
+        const unsigned b1 = j2 ? (packed >> 16) & 0xffu : other & 0xffu;
+        const unsigned b2 = j2 ? (other >> 24) & 0xffu : (packed >> 8) & 0xffu;
+        const unsigned b3 = j2 ? (packed >> 24) & 0xffu : (other >> 8) & 0xffu;
+        if (valid) *reinterpret_cast<unsigned*>(pred + obase + (long long)(2 * j2 + i2) * Wo) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+    }
+    bad |= nanbits > 0x7f800000u;
+    if (nan_flag != nullptr && __any(bad) && lane == 0) atomicOr(nan_flag, 1);
+    if (TGT && nan_flag != nullptr && __any(bad_label) && lane == 0) atomicOr(nan_flag, 2);
+    if (TGT) {
+        __syncthreads();
+        if (counts != nullptr)
+            for (int t = tid; t < 3 * kPC + 2; t += 256)
+                if (hist[t]) atomicAdd(&counts[t], (unsigned long long)hist[t]);
+    }
+    if (CE) {
+        if (bad_label) ce_loss = __builtin_nan("");     // as sssr_tail_predict_kernel
+        double l = wave_sum_d(ce_loss), c = wave_sum_d(ce_cnt);
+        if (lane == 0) shd[wv] = l;
+        __syncthreads();
+        l = shd[0] + shd[1] + shd[2] + shd[3];
+        __syncthreads();
+        if (lane == 0) shd[wv] = c;
+        __syncthreads();
+        c = shd[0] + shd[1] + shd[2] + shd[3];
+        if (tid == 0) { part[2 * blockIdx.x] = l; part[2 * blockIdx.x + 1] = c; }
+    }
+}
+
 // the per-block partials in block order: the same value whatever order the blocks ran in
 __global__ __launch_bounds__(256) void predict_ce_finalize_kernel(const double* __restrict__ part, int nb, float* __restrict__ out) {
     __shared__ double sl[256], sn[256];
@@ -266,10 +497,13 @@ extern "C" size_t dsrl_sssr_tail_predict_workspace_bytes(int N, int H, int W) {
     return (size_t)2 * predict_blocks((long long)N * H * W) * sizeof(double);
 }
 
-extern "C" int dsrl_sssr_tail_predict(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
-                                      const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2, uint8_t* pred,
-                                      const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag, void* ws,
-                                      size_t ws_bytes, dsrl_stream_t stream) {
+namespace {
+
+// both entry points: `flip` selects the two-view kernel, whose x holds 2 N images for N class maps
+int tail_predict_launch(bool flip, const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                        const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2, uint8_t* pred,
+                        const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag, void* ws, size_t ws_bytes,
+                        dsrl_stream_t stream) {
     DSRL_REQUIRE(x && w1 && bn_mean && bn_invstd && bn_gamma && bn_beta && w2 && pred && N > 0 && H > 0 && W > 0, DSRL_E_BADARG,
                  "sssr_tail_predict: null pointer or empty shape");
     DSRL_REQUIRE(dsrl_sssr_tail_predict_supported(N, H, W, Cin, Cmid, Cout), DSRL_E_UNSUPPORTED,
@@ -285,19 +519,43 @@ extern "C" int dsrl_sssr_tail_predict(const float* x, int ldx, int N, int H, int
     if (int e = bind_stream_device(st)) return e;
     const int ntiles = (int)ceil_div(P, 16);
     double* part = (double*)ws;
-#define DSRL_PREDICT_LAUNCH(TGT, CE)                                                                                                                   \
-    hipLaunchKernelGGL((sssr_tail_predict_kernel<TGT, CE>), dim3(nb), dim3(256), 0, st, x, ldx, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, \
-                       pred, target, ignore_index, counts, part, nan_flag, H, W, P, ntiles)
-    if (!target) DSRL_PREDICT_LAUNCH(false, false);
-    else if (!ce_out) DSRL_PREDICT_LAUNCH(true, false);
-    else DSRL_PREDICT_LAUNCH(true, true);
+#define DSRL_PREDICT_LAUNCH(KERNEL, TGT, CE)                                                                                                           \
+    hipLaunchKernelGGL((KERNEL<TGT, CE>), dim3(nb), dim3(256), 0, st, x, ldx, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target,     \
+                       ignore_index, counts, part, nan_flag, H, W, P, ntiles)
+    if (flip) {
+        if (!target) DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, false, false);
+        else if (!ce_out) DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, true, false);
+        else DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, true, true);
+    } else {
+        if (!target) DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, false, false);
+        else if (!ce_out) DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, true, false);
+        else DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, true, true);
+    }
 #undef DSRL_PREDICT_LAUNCH
-    if (int e = launch_status("sssr_tail_predict_kernel")) return e;
+    if (int e = launch_status(flip ? "sssr_tail_predict_flip_kernel" : "sssr_tail_predict_kernel")) return e;
     if (ce_out) {
         hipLaunchKernelGGL(predict_ce_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nb, ce_out);
         return launch_status("predict_ce_finalize_kernel");
     }
     return DSRL_OK;
+}
+
+}  // namespace
+
+extern "C" int dsrl_sssr_tail_predict(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                                      const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2, uint8_t* pred,
+                                      const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag, void* ws,
+                                      size_t ws_bytes, dsrl_stream_t stream) {
+    return tail_predict_launch(false, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
+                               counts, ce_out, nan_flag, ws, ws_bytes, stream);
+}
+
+extern "C" int dsrl_sssr_tail_predict_flip(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                                           const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2,
+                                           uint8_t* pred, const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag,
+                                           void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    return tail_predict_launch(true, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
+                               counts, ce_out, nan_flag, ws, ws_bytes, stream);
 }
 
 extern "C" int dsrl_fingerprint_segment_words(void) { return kFingerprintSegWords; }

@@ -6,6 +6,7 @@ raises if its tensors are not on a HIP device: there is no CPU / stock-ATen fall
 """
 import contextlib
 import ctypes
+import math
 import os
 import sys
 import weakref
@@ -1829,12 +1830,24 @@ def _bad_label_bit(nan_flag, target, ignore_index, num_classes):
     nan_flag.bitwise_or_((bad.to(torch.int32) * 2).reshape(nan_flag.shape))
 
 
-def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, counts=None, nan_flag=None):
+def _flip_ensemble(logits):
+    """logits (2N,C,H,W), the second half computed from the mirrored images -> E (N,C,H,W) = logaddexp of the two views' log-softmax - ln 2 with the
+    second view mirrored back: the log of the averaged class probabilities (include/dsrl_hip.h: dsrl_sssr_tail_predict_flip)"""
+    N = logits.shape[0] // 2
+    la = torch.log_softmax(logits[:N], dim=1)
+    lb = torch.log_softmax(logits[N:], dim=1).flip(3)
+    return torch.logaddexp(la, lb) - math.log(2.0)
+
+
+def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, counts=None, nan_flag=None, flip=False):
     """Eval-mode tail of the SSSR decoder after its bilinear x2 (DSRL.py:55-69): ConvTranspose2d k2 s2 `convt1` -> BatchNorm2d `bn` (running statistics)
     -> ReLU -> ConvTranspose2d k2 s2 `convt2` -> arg-max, as one launch that writes class indices and never the logits (dsrl_sssr_tail_predict).
     -> (pred uint8 (N,4H,4W), ce): with `target` (N,4H,4W) `ce` is the 0-d device tensor of nn.CrossEntropyLoss(ignore_index) of the logits and
     `counts` (int64 [3*classes+2], optional) gets the table of dsrl_seg_metrics ADDED; `nan_flag` (int32 scalar, optional): bit 0 NaN logit, bit 1 a
-    label outside the classes.  Heads the kernel does not implement run the modules one by one and reduce their logits."""
+    label outside the classes.  Heads the kernel does not implement run the modules one by one and reduce their logits.
+    `flip=True`: the horizontal-flip ensemble.  `x` is (2N,...): image N + n is the tail input computed from the MIRRORED image n, still in the mirrored
+    frame.  -> N class maps: the arg-max of the two views' averaged class probabilities (the second view mirrored back), `ce` the loss of their
+    logarithm, `target` (N,4H,4W); the same single launch (dsrl_sssr_tail_predict_flip), still no logits in memory."""
     with torch.no_grad():
         x, ldx = pm(x)
         w1, w2, b2 = convt1.weight, convt2.weight, convt2.bias
@@ -1842,6 +1855,10 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
         if bn.training or bn.running_mean is None or bn.running_var is None:
             raise DsrlHipError('sssr_tail_predict: the BatchNorm must be in eval mode and track running statistics')
         N, Ci, H, W = x.shape
+        if flip:
+            if N % 2:
+                raise DsrlHipError(f'sssr_tail_predict: flip=True takes the two views of every image, got an odd batch of {N}')
+            N //= 2
         if w1.dim() != 4 or w2.dim() != 4 or w1.shape[0] != Ci or w2.shape[0] != w1.shape[1] or bn.num_features != w1.shape[1]:
             raise DsrlHipError(f'sssr_tail_predict: {Ci} input channels do not chain through filters {tuple(w1.shape)}, {tuple(w2.shape)}')
         Cm, Co = w1.shape[1], w2.shape[1]
@@ -1872,7 +1889,7 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
             ws = _ws(cquery('dsrl_sssr_tail_predict_workspace_bytes', N, H, W) if ce is not None else 0, x)
             gamma = bn.weight if bn.weight is not None else torch.ones_like(invstd)
             beta = bn.bias if bn.bias is not None else torch.zeros_like(invstd)
-            call('dsrl_sssr_tail_predict', x.data_ptr(), ldx, N, H, W, Ci, Cm, Co, w1.contiguous().data_ptr(), bn.running_mean.data_ptr(),
+            call('dsrl_sssr_tail_predict_flip' if flip else 'dsrl_sssr_tail_predict', x.data_ptr(), ldx, N, H, W, Ci, Cm, Co, w1.contiguous().data_ptr(), bn.running_mean.data_ptr(),
                  invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w2.contiguous().data_ptr(), None if b2 is None else b2.data_ptr(),
                  pred.data_ptr(), None if target is None else target.data_ptr(), int(ignore_index), None if counts is None else counts.data_ptr(),
                  None if ce is None else ce.data_ptr(), None if nan_flag is None else nan_flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
@@ -1880,9 +1897,11 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
         # any other head: the modules as the training forward runs them in eval mode, then the reductions over their logits
         y = batch_norm_act(convt1(x), bn, relu=True)
         logits = convt2(y)
-        pred = torch.argmax(logits, dim=1).to(torch.uint8)
         if nan_flag is not None:
             nan_check_(nan_flag, logits)
+        if flip:
+            logits = _flip_ensemble(logits)         # the scores of the ensemble stand in for the logits: log_softmax(E) = E
+        pred = torch.argmax(logits, dim=1).to(torch.uint8)
         if target is None:
             return pred, None
         if nan_flag is not None:

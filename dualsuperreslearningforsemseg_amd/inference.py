@@ -5,7 +5,7 @@
     1 / sqrt(var + eps) of every eval BatchNorm.  functional.py finds them through the hooks it already reads (`w._dsrl_operands`;
     `running_var._dsrl_invstd`), so `model.predict` and `model.forward` launch the same conv kernels on the same values, without the per-call filter
     measurement, the in-kernel filter split and the ~105 one-block invstd launches.
-  * CompiledPredictor (DSRL.compile_predict): `DSRL.predict` captured per (N, H, W, with target, conv arithmetic) into a hipGraph and replayed - about a
+  * CompiledPredictor (DSRL.compile_predict): `DSRL.predict` captured per (N, H, W, with target, conv arithmetic, flip) into a hipGraph and replayed - about a
     thousand eager launches become one hipGraphLaunch.  The contract is bit identity with eager `predict`.
   * load_compiled_model: the file the compile_model command writes (data only) -> (model, CompiledPredictor).
 """
@@ -188,9 +188,10 @@ _FLAG_MESSAGES = ((1, 'NaN in the input or the logits'), (2, 'labels outside the
 
 
 class CompiledPredictor:
-    """`pred, counts, ce = compiled(images, target=None, ignore_index=255, nan_flag=None)`: DSRL.predict on frozen operands, replayed from a hipGraph.
+    """`pred, counts, ce = compiled(images, target=None, ignore_index=255, nan_flag=None, flip=False)`: DSRL.predict on frozen operands, replayed from a
+    hipGraph.  `flip` is a call-time option (DSRL.predict(flip=True): the horizontal-flip ensemble), not a property of a compiled model file.
 
-    One graph per key (N, H, W, with target, conv arithmetic), captured at the key's first use after GRAPH_WARMUP eager calls (the frozen eager path:
+    One graph per key (N, H, W, with target, conv arithmetic, flip), captured at the key's first use after GRAPH_WARMUP eager calls (the frozen eager path:
     the same kernels), at most MAX_GRAPHS keys; further shapes, and every shape when `graph` is False or a capture failed, run the frozen eager path.
     The graph reads static input buffers (the call copies the batch in) and writes static outputs; the call returns copies of them (the class map is
     N*H*W bytes), or with copy=False the static tensors themselves, which the next call with the same key overwrites.
@@ -224,12 +225,12 @@ class CompiledPredictor:
     def num_graphs(self):
         return len(self._graphs)
 
-    def _key(self, images, target):
+    def _key(self, images, target, flip=False):
         N, _, H, W = images.shape
-        return (int(N), int(H), int(W), target is not None, HF.get_conv_precision())
+        return (int(N), int(H), int(W), target is not None, HF.get_conv_precision(), bool(flip))
 
     # ------------------------------------------------------------------ capture
-    def _capture(self, key, images, target, ignore_index):
+    def _capture(self, key, images, target, ignore_index, flip=False):
         """-> the captured call; after a capture that failed None, and this predictor stays on the frozen eager path."""
         c = _CapturedPredict()
         try:
@@ -244,7 +245,7 @@ class CompiledPredictor:
                 with torch.cuda.graph(c.graph, capture_error_mode='thread_local'):          # linear: one stream, no side streams in an eval forward
                     c.arena[0].zero_()              # first node: every record a replay maxes into starts at zero
                     c.flag.zero_()
-                    c.pred, c.counts, c.ce = self.model.predict(c.img, c.tgt, c.ignore_index, c.flag)
+                    c.pred, c.counts, c.ce = self.model.predict(c.img, c.tgt, c.ignore_index, c.flag, flip)
         except Exception as e:          # noqa: BLE001
             self.use_graph = False
             HF.abandon_capture(self.device, e, ' of predict', 'this CompiledPredictor continues on the frozen eager path')
@@ -255,7 +256,7 @@ class CompiledPredictor:
         return c
 
     # ------------------------------------------------------------------ the call
-    def __call__(self, images, target=None, ignore_index=255, nan_flag=None, copy=True):
+    def __call__(self, images, target=None, ignore_index=255, nan_flag=None, copy=True, flip=False):
         if self.frozen.released:
             raise DsrlHipError('this CompiledPredictor was released: call compile_predict() again')
         self.frozen.check()
@@ -263,18 +264,18 @@ class CompiledPredictor:
         if images.dim() != 4:
             raise DsrlHipError(f'4-D (N,3,H,W) images expected, got shape {tuple(images.shape)}')
         own = nan_flag is None
-        key = self._key(images, target)
+        key = self._key(images, target, flip)
         c = self._graphs.get(key)
         if c is not None and target is not None and c.ignore_index != int(ignore_index):
             c = None                                # the label to ignore is a launch argument of the captured kernels: this call runs eagerly
         elif (c is None and self.use_graph and len(self._graphs) < self.MAX_GRAPHS and self._warm.get(key, 0) >= self.GRAPH_WARMUP
               and (target is None or (target.dtype == torch.uint8 and tuple(target.shape) == (images.shape[0], 2 * images.shape[2], 2 * images.shape[3])))):
-            c = self._capture(key, images, target, ignore_index)
+            c = self._capture(key, images, target, ignore_index, flip)
         with torch.no_grad():
             if c is None:
                 self._warm[key] = self._warm.get(key, 0) + 1
                 flag = torch.zeros((), dtype=torch.int32, device=images.device) if own else nan_flag
-                out = self.model.predict(images, target, ignore_index, flag)
+                out = self.model.predict(images, target, ignore_index, flag, flip)
                 HF.drop_planes()
             else:
                 if c.img.data_ptr() != images.data_ptr():

@@ -134,12 +134,15 @@ class DSRL(BaseModel):
             backbone_features, lowlevel_features = self.feature_extractor['backbone'](x)      # DSRL.py:161
             return self.forward_head(backbone_features, lowlevel_features)
 
-    def predict_head(self, backbone_features: t.Tensor, lowlevel_features: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None):
+    def predict_head(self, backbone_features: t.Tensor, lowlevel_features: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None,
+                     flip: bool = False):
         """Inference counterpart of forward_head: the SSSR branch in eval mode down to the bilinear x2 of `upsample16_pred`, then its ConvTranspose ->
         BatchNorm -> ReLU -> ConvTranspose tail and the arg-max as one kernel (functional.sssr_tail_predict) -> (pred uint8 (N,H,W), counts, ce).
         With `target` (N,H,W): `counts` is the int64 table of dsrl_seg_metrics of this batch (metrices.mIoU / Accuracy.update_from_counts) and `ce` the
         0-d CrossEntropyLoss(ignore_index); both None otherwise.  `nan_flag` (int32 device scalar) collects bit 0 = NaN logit, bit 1 = label outside
-        the classes; nothing is read back here.  Neither the SISR decoder nor the feature transformers run, whatever the stage."""
+        the classes; nothing is read back here.  Neither the SISR decoder nor the feature transformers run, whatever the stage.
+        `flip=True`: the features are those of 2N images, the second half from the horizontally mirrored images; the tail kernel mirrors that half back
+        and averages the two views' class probabilities -> N class maps (functional.sssr_tail_predict(flip=True)), `target` (N,H,W)."""
         if self.training:
             raise HF.DsrlHipError('DSRL.predict* is inference: call model.eval() first')
         with t.no_grad():
@@ -153,13 +156,15 @@ class DSRL(BaseModel):
             counts = None
             if target is not None:
                 counts = t.zeros(3 * up[6].out_channels + 2, dtype=t.int64, device=y.device)
-            pred, ce = HF.sssr_tail_predict(y, up[2], up[3], up[6], target=target, ignore_index=ignore_index, counts=counts, nan_flag=nan_flag)
+            pred, ce = HF.sssr_tail_predict(y, up[2], up[3], up[6], target=target, ignore_index=ignore_index, counts=counts, nan_flag=nan_flag, flip=flip)
         return pred, counts, ce
 
-    def predict(self, x: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None):
+    def predict(self, x: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None, flip: bool = False):
         """Class map of a batch: (pred, counts or None, ce or None), see predict_head.  Runs under no_grad and raises in train mode.  Without a
         `nan_flag` of the caller's the flag is read back here and a NaN logit or an out-of-range label raises; a caller that passes one reads it when
-        it chooses to (command_handlers.benchmark: once, after the last batch)."""
+        it chooses to (command_handlers.benchmark: once, after the last batch).
+        `flip=True`: the horizontal-flip ensemble.  The trunk runs once on cat([x, x.flip(3)]) (2N images) and the tail kernel forms the ensemble:
+        N class maps, counters and the loss of the averaged class probabilities."""
         if self.training:
             raise HF.DsrlHipError('DSRL.predict* is inference: call model.eval() first')
         own = nan_flag is None
@@ -167,8 +172,13 @@ class DSRL(BaseModel):
             if own:
                 nan_flag = t.zeros((), dtype=t.int32, device=x.device)
             HF.nan_check_(nan_flag, x)          # a NaN pixel would not reach the logits: the first ReLU (fmaxf) maps it to 0
+            if flip:
+                both = t.empty((2 * x.shape[0],) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device, memory_format=t.channels_last)
+                both[:x.shape[0]].copy_(x)
+                both[x.shape[0]:].copy_(x.flip(3))          # 3 channels at input size: torch ops
+                x = both
             backbone_features, lowlevel_features = self.feature_extractor['backbone'](x)
-            out = self.predict_head(backbone_features, lowlevel_features, target, ignore_index, nan_flag)
+            out = self.predict_head(backbone_features, lowlevel_features, target, ignore_index, nan_flag, flip)
         if own:
             bits = int(nan_flag.item())
             if bits:

@@ -548,6 +548,16 @@ int dsrl_sssr_tail_predict(const float* x, int ldx, int N, int H, int W, int Cin
                            const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2 /*nullable*/,
                            uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index, unsigned long long* counts /*nullable*/,
                            float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+/* Horizontal-flip ensemble of the same tail in the same single launch.  x holds 2 N images: image n is the plain view, image N + n the tail input
+ * computed from the MIRRORED image n, still in the mirrored frame (the kernel un-mirrors it).  With La the logits of the plain view and Lb those of
+ * the mirrored view mirrored back along W: E = logaddexp(log_softmax(La), log_softmax(Lb)) - ln 2 over the classes; pred (N,4H,4W) = lowest index
+ * among the maxima of softmax(La) + softmax(Lb); ce_out = mean of -E[target] over the counted pixels, evaluated in log space; counts, nan_flag
+ * (bit 0: a NaN in either view), target, ws and the alignment rules as above.  N is the number of class maps: _supported(N, ...) and
+ * _workspace_bytes(N, H, W) answer for this launch too. */
+int dsrl_sssr_tail_predict_flip(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                                const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2 /*nullable*/,
+                                uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index, unsigned long long* counts /*nullable*/,
+                                float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
 
 /* Fingerprint of tensors that must not change while an inference.FrozenOperands holds operands derived from them (a write through `.data` or a
  * raw pointer moves neither a tensor's address nor its version counter).  table: DEVICE array of nseg rows of 2 int64 {pointer (4-byte aligned),

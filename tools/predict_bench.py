@@ -5,6 +5,16 @@ device events around every window, after a warm-up of both sides at that shape. 
 the larger of FLOPs / fp32 matrix rate and bytes / HBM rate.  One more table: DSRL.predict against DSRL.forward + arg-max for the whole stage-1 model.
 
     python tools/predict_bench.py [--out FILE] [--window 0.5] [--rounds 3]
+
+--flip measures the horizontal-flip ensemble instead (profiles/predict_flip.txt), at tail input 256x512, batch 1 and 8:
+  (a) the two-view tail (dsrl_sssr_tail_predict_flip) against the unfused composition on the same 2N tail input (modules, two sets of logits, torch
+      log_softmax / flip / logaddexp / argmax, with a target also dsrl_seg_metrics and the loss),
+  (b) the two-view tail on N class maps against the single-view tail on 2N images: the same input bytes and MFMAs, so the ratio is the price of the two
+      softmaxes per output pixel,
+  (c) DSRL.predict(flip=True) on N images against DSRL.predict on 2N: eager, on frozen operands, and replayed from the hipGraph,
+and lists the registers of the tail kernels (tools/kernel_resources.py on the built library).
+
+    python tools/predict_bench.py --flip [--out profiles/predict_flip.txt]
 """
 import argparse
 import math
@@ -13,6 +23,7 @@ import sys
 
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dualsuperreslearningforsemseg_amd import functional as HF                        # noqa: E402
 from dualsuperreslearningforsemseg_amd.datasets.Cityscapes import settings as CS       # noqa: E402
@@ -63,13 +74,128 @@ def ab(a, b, seconds, rounds):
     return ta, tb
 
 
+def _row(say, label, ta, tb, unit_scale=1e3, unit='us', extra=''):
+    ma, mb = sum(ta) / len(ta), sum(tb) / len(tb)
+    d = 1 if unit == 'us' else 3
+    say(f'{label}:  A {ma * unit_scale:9.{d}f} {unit} [{", ".join(f"{t * unit_scale:.{d}f}" for t in ta)}]   B {mb * unit_scale:9.{d}f} {unit} '
+        f'[{", ".join(f"{t * unit_scale:.{d}f}" for t in tb)}]   A/B {ma / mb:5.3f}{extra}')
+    return ma, mb
+
+
+def flip_main(args):
+    import kernel_resources as KR
+    from dualsuperreslearningforsemseg_amd import _lib
+    dev = torch.device('cuda:0')
+    lines = []
+
+    def say(s=''):
+        print(s, flush=True)
+        lines.append(s)
+
+    torch.manual_seed(7)
+    up = DSRL._define_SSSR_decoder(256, 48, 256, NC)['upsample16_pred'].to(dev).eval()
+    with torch.no_grad():
+        up[3].running_mean.normal_(0, 0.1); up[3].running_var.uniform_(0.5, 1.5)
+    tail = HipSequential(*list(up)[2:]).eval()
+    H, W = 256, 512
+    say(f'Horizontal-flip ensemble, {torch.cuda.get_device_name(0)}, tail input {H}x{W}; windows of >= {args.window} s per side, {args.rounds} alternations '
+        f'A B A B ..; mean [each window]')
+    say()
+    say('(a) A = unfused composition on the 2N tail input (modules -> two sets of logits -> torch log_softmax, flip, logaddexp, argmax; with a target also '
+        'dsrl_seg_metrics + HF.cross_entropy of the scores), B = dsrl_sssr_tail_predict_flip')
+    slower = []
+    for with_target in (False, True):
+        for N in (1, 8):
+            x = torch.randn(2 * N, NC, H, W, device=dev).contiguous(memory_format=torch.channels_last)
+            target = torch.randint(0, NC, (N, 4 * H, 4 * W), device=dev, dtype=torch.uint8) if with_target else None
+            if with_target:
+                target[torch.rand(target.shape, device=dev) < 0.1] = 255
+            counter = _Counts(NC)
+
+            def a():
+                with torch.no_grad():
+                    scores = HF._flip_ensemble(tail(x))
+                    pred = torch.argmax(scores, dim=1)
+                    if not with_target:
+                        return pred
+                    counter.batches = []
+                    counter.add_logits(scores, target)
+                    return pred, counter.batches[0], HF.cross_entropy(scores, target, 255)
+
+            def b():
+                if not with_target:
+                    return HF.sssr_tail_predict(x, up[2], up[3], up[6], flip=True)
+                counts = torch.zeros(3 * NC + 2, dtype=torch.int64, device=dev)
+                return HF.sssr_tail_predict(x, up[2], up[3], up[6], target=target, counts=counts, flip=True), counts
+
+            ta, tb = ab(a, b, args.window, args.rounds)
+            mem_a, mem_b = peak_bytes(a), peak_bytes(b)
+            ma, mb = _row(say, f'N={N} target={"yes" if with_target else "no "}', ta, tb,
+                          extra=f'   peak memory A {mem_a / 1e6:8.1f} MB  B {mem_b / 1e6:6.2f} MB')
+            if mb > ma:
+                slower.append(('a', N, with_target))
+    say()
+    say('(b) A = dsrl_sssr_tail_predict on 2N images (2N class maps), B = dsrl_sssr_tail_predict_flip on the same 2N images (N class maps): '
+        'the same input bytes and MFMAs; B/A is the price of the two softmaxes per output pixel')
+    for with_target in (False, True):
+        for N in (1, 8):
+            x = torch.randn(2 * N, NC, H, W, device=dev).contiguous(memory_format=torch.channels_last)
+            t2 = torch.randint(0, NC, (2 * N, 4 * H, 4 * W), device=dev, dtype=torch.uint8) if with_target else None
+            t1 = t2[:N].contiguous() if with_target else None
+
+            def a():
+                return HF.sssr_tail_predict(x, up[2], up[3], up[6], target=t2)
+
+            def b():
+                return HF.sssr_tail_predict(x, up[2], up[3], up[6], target=t1, flip=True)
+
+            ta, tb = ab(a, b, args.window, args.rounds)
+            ma, mb = _row(say, f'N={N} target={"yes" if with_target else "no "}', ta, tb)
+            px = 2 * N * H * W
+            say(f'      B/A {mb / ma:5.2f};  B: {2.0 * MACS_PER_PIXEL * px / (mb * 1e-3) / 1e12:6.2f} TFLOP/s of MFMA work, {38 * 8 * px / (mb * 1e-3) / 1e9:7.1f} G exp/s '
+                f'(floor of the MFMAs at {F32_MATRIX_FLOPS / 1e12:.0f} TF: {2.0 * MACS_PER_PIXEL * px / F32_MATRIX_FLOPS * 1e6:6.1f} us)')
+    say()
+    say('(c) whole model (stage 1, random weights, eval, 256x512 input, caller-owned nan_flag: no readback): A = predict on 2N images, B = predict(flip=True) on N')
+    model = DSRL(1, CS).to(dev).to(memory_format=torch.channels_last).eval()
+    flag = torch.zeros((), dtype=torch.int32, device=dev)
+    for N in (1, 8):
+        img = torch.randn(N, 3, 256, 512, device=dev).contiguous(memory_format=torch.channels_last)
+        img2 = torch.cat([img, img.flip(3)]).contiguous(memory_format=torch.channels_last)
+        ta, tb = ab(lambda: model.predict(img2, nan_flag=flag)[0], lambda: model.predict(img, nan_flag=flag, flip=True)[0], args.window, args.rounds)
+        _row(say, f'batch {N} eager ', ta, tb, 1.0, 'ms', f'   peak memory A {peak_bytes(lambda: model.predict(img2, nan_flag=flag)[0]) / 1e6:8.1f} MB  '
+             f'B {peak_bytes(lambda: model.predict(img, nan_flag=flag, flip=True)[0]) / 1e6:8.1f} MB')
+        for graph, name in ((False, 'frozen'), (True, 'replay')):
+            cp = model.compile_predict(graph=graph)
+            try:
+                ta, tb = ab(lambda: cp(img2, nan_flag=flag, copy=False)[0], lambda: cp(img, nan_flag=flag, copy=False, flip=True)[0], args.window, args.rounds)
+                _row(say, f'batch {N} {name} ', ta, tb, 1.0, 'ms', f'   graphs {cp.num_graphs}')
+            finally:
+                cp.release()
+    say()
+    say('rows of (a) where B is slower than A: ' + (', '.join(str(r) for r in slower) if slower else 'none'))
+    say()
+    say('kernel resources (tools/kernel_resources.py on libdsrl_hip.so):')
+    ks = KR.kernels(_lib.LIB_PATH)
+    for k, n in zip(ks, KR.demangle([k['name'] for k in ks])):
+        if 'sssr_tail_predict' in n:
+            say(f"vgpr {k.get('vgpr', 0):3d} agpr {k.get('agpr', 0):3d} sgpr {k.get('sgpr', 0):3d} scratch {k.get('scratch', 0):5d} B  spills v{k.get('vgpr_spill', 0)} "
+                f"s{k.get('sgpr_spill', 0)}  lds {k.get('lds', 0):6d}  {n[:110]}")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
     ap.add_argument('--window', type=float, default=0.5)
     ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--flip', action='store_true', help='measure the horizontal-flip ensemble (profiles/predict_flip.txt)')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'predict_bench.py measures on the GPU only'
+    if args.flip:
+        return flip_main(args)
     dev = torch.device('cuda:0')
     lines = []
 
