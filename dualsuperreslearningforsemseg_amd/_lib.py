@@ -124,6 +124,17 @@ PROTOTYPES = {
     'dsrl_ce_fused_workspace_bytes': (sz, [i64]),
     'dsrl_ce_fused': (i32, [fp, i32, fp, i64, i32, i32, fp, i32, fp, fp, fp, sz, stream_t]),
     'dsrl_mse_fused': (i32, [fp, fp, i64, f32, fp, fp, fp, fp, sz, stream_t]),
+    'dsrl_ce_weight_sum_workspace_bytes': (sz, []),
+    'dsrl_ce_weight_sum': (i32, [fp, i64, i32, i32, fp, fp, fp, sz, stream_t]),
+    'dsrl_ce_w_workspace_bytes': (sz, [i64]),
+    'dsrl_ce_fwd_w': (i32, [fp, i32, fp, i64, i32, i32, fp, fp, fp, sz, stream_t]),
+    'dsrl_ce_bwd_w': (i32, [fp, i32, fp, i64, i32, i32, fp, fp, fp, fp, i32, stream_t]),
+    'dsrl_ce_fused_w_workspace_bytes': (sz, [i64]),
+    'dsrl_ce_fused_w': (i32, [fp, i32, fp, i64, i32, i32, fp, fp, i32, fp, fp, fp, sz, stream_t]),
+    'dsrl_convt2x2_fwd_ce_w_workspace_bytes': (sz, [i32, i32, i32]),
+    'dsrl_convt2x2_fwd_ce_w': (i32, [fp, fp, fp, fp, i32, i32, i32, i32, i32, fp, i32, fp, fp, fp, fp, sz, stream_t]),
+    'dsrl_convt2x2_bwd_ce_w': (i32, [fp, fp, fp, fp, i32, fp, fp, fp, fp, i32, fp, fp, fp, i32, i32, i32, i32, i32, fp, sz, stream_t]),
+    'dsrl_class_histogram': (i32, [fp, i64, fp, fp, stream_t]),
     'dsrl_loss_mix': (i32, [fp, fp, fp, f32, f32, fp, fp, stream_t]),
     'dsrl_fa_saved_floats': (sz, [i32] * 5),
     'dsrl_fa_workspace_bytes': (sz, [i32] * 5),

@@ -77,12 +77,17 @@ class TrainStep:
     become one hipGraphLaunch, so the host no longer paces the device.  What makes the capture replayable: the dropout key and the
     optimiser hyper-parameters are read from device memory (functional.DeviceRng, dsrl_sgd_step_dev), the fused BatchNorm barrier
     is self-resetting, and the batch is copied into static input buffers.  With more than one rank the collectives stay outside the
-    graph: BN-buffer broadcast before the replay, chunked gradient all-reduce and the SGD kernel after it."""
+    graph: BN-buffer broadcast before the replay, chunked gradient all-reduce and the SGD kernel after it.
+
+    `class_weights` (None, or one number per class): nn.CrossEntropyLoss(weight=) for the CE term of every path of the step - fused and unfused
+    losses, eager and captured, training and `do_train=False` (the reference shares one `loss_funcs` between training and validation).  With more
+    than one rank each rank normalises by the weight sum of its own batch and the gradients are averaged, as DDP with a weighted loss does."""
 
     GRAPH_WARMUP = HF.GRAPH_WARMUP          # eager iterations per batch shape before the capture
 
-    def __init__(self, model, flat, stage, w1, w2, ignore_index, graph=None):
+    def __init__(self, model, flat, stage, w1, w2, ignore_index, graph=None, class_weights=None):
         self.model, self.flat, self.stage, self.w1, self.w2, self.ignore = model, flat, stage, w1, w2, ignore_index
+        self.class_weight = None if class_weights is None else HF.class_weight_table(class_weights, flat.device)     # ValueError on bad weights
         self.fa = FALoss()
         dev = flat.device
         self.flag = t.zeros(1, dtype=t.int32, device=dev)
@@ -111,7 +116,7 @@ class TrainStep:
 
     def losses(self, outs, input_org, target):
         SSSR, SISR, SSSR_ft, SISR_ft = outs
-        ce = HF.cross_entropy(SSSR, target, self.ignore)                                   # train_or_resume.py:435
+        ce = HF.cross_entropy(SSSR, target, self.ignore, self.class_weight)                # train_or_resume.py:435
         ms = self.w1 * HF.mse_loss(SISR, input_org) if self.stage > 1 else self.zero       # :436
         fa = self.w2 * self.fa(SSSR_ft, SISR_ft) if self.stage > 2 else self.zero          # :437
         return ce, ms, fa, ce + ms + fa                                                    # :438
@@ -137,13 +142,15 @@ class TrainStep:
             with t.set_grad_enabled(do_train):
                 if self.fused_losses and do_train:
                     # the layer that produces the logits evaluates the CE value in its own forward kernel (HF.logits_target), :435
-                    with HF.logits_target(target if target.dtype == t.uint8 and target.is_contiguous() else None, self.ignore, self.flag):
+                    with HF.logits_target(target if target.dtype == t.uint8 and target.is_contiguous() else None, self.ignore, self.flag,
+                                          self.class_weight):
                         outs = self.model(input_image)                                     # :420
                 else:
                     outs = self.model(input_image)                                         # :420
                 if self.fused_losses:
                     # CE + MSE + FA, their gradients, the NaN asserts (:426-433) and the loss mix (:435-438) in one launch set
-                    vals = HF.fused_losses(outs, target, input_org, self.ignore, self.w1, self.w2, self.stage, self.flag, self.fa.subsample_factor)
+                    vals = HF.fused_losses(outs, target, input_org, self.ignore, self.w1, self.w2, self.stage, self.flag, self.fa.subsample_factor,
+                                           self.class_weight)
                     total = vals[3]
                 else:
                     HF.nan_check_(self.flag, *[o for o in outs if o.is_cuda])              # the four NaN asserts, :426-433
@@ -381,6 +388,25 @@ def _get_state_dict(model):
     return model.state_dict()
 
 
+def check_class_weights(dataset, num_classes):
+    """dataset['class_weights']: absent / None, a sequence of `num_classes` finite numbers >= 0, or 'enet'.  -> None, a float32 numpy array, or
+    'enet'; ValueError otherwise.  Touches no device: called before anything is set up.  'enet' (w_c = 1 / ln(1.02 + f_c) from the class
+    frequencies of the training split) needs the pre-decoded cache of the project's own loader to count from."""
+    cw = dataset.get('class_weights')
+    if cw is None:
+        return None
+    if isinstance(cw, str):
+        if cw != 'enet':
+            raise ValueError(f"dataset['class_weights'] = {cw!r}: expected None, {num_classes} numbers or 'enet'")
+        if dataset.get('loader_factory') is not None:
+            from ..datasets.Cityscapes.loader import cache_dir_of, has_cache
+            if not (dataset.get('cache_path') or dataset.get('path')) or not has_cache(cache_dir_of(dataset)):
+                raise ValueError("dataset['class_weights'] = 'enet' counts the classes of the pre-decoded Cityscapes cache: with a caller's "
+                                 "'loader_factory' there is none (set dataset['cache_path'] to one, or pass the weights as numbers)")
+        return 'enet'
+    return HF.class_weight_table(cw, 'cpu', num_classes)[:num_classes].numpy()
+
+
 def train_or_resume(is_resuming_training, device, distributed, mixed_precision, disable_cudnn_benchmark, num_workers, dataset, val_interval,
                     checkpoint_interval, checkpoint_history, init_weights, batch_size, epochs, learning_rate, end_learning_rate, momentum,
                     weights_decay, poly_power, stage, w1, w2, freeze_batch_norm, experiment_id, description, early_stopping, dry_run=False, **other_args):
@@ -390,6 +416,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
         raise RuntimeError(f"mixed_precision={mixed_precision!r}: expected one of {sorted(k for k in settings.MIXED_PRECISION_TO_CONV_ARITHMETIC if k)} "
                            '(apex itself is not used: the opt level selects the MFMA conv arithmetic)')
     conv_arith = settings.MIXED_PRECISION_TO_CONV_ARITHMETIC[mixed_precision]
+    class_weights = check_class_weights(dataset, dataset['settings'].NUM_CLASSES)
     input_size = other_args.get('model_input_size', settings.MODEL_INPUT_SIZE)
     if distributed:
         t.manual_seed(settings.RANDOM_SEED)                                                # identical init on all ranks, :31
@@ -429,8 +456,6 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     flat = FlatParams(model)                                                               # DDP wrap, :105-106
     if is_resuming_training and 'optimizer_state_dict' in other_args:
         flat.load_state_dict(other_args['optimizer_state_dict'])
-    step = TrainStep(model, flat, stage, w1, w2, ds.IGNORE_CLASS_LABEL)
-
     factory = dataset.get('loader_factory')
     own_loader = factory is None
     if own_loader:
@@ -440,6 +465,13 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
         # the Cityscapes tree (or its pre-decoded cache): HIP augmentations on a side stream, datasets/Cityscapes/loader.py
         from ..datasets.Cityscapes.loader import loader_factory
         factory = loader_factory(dataset, input_size, settings.RANDOM_SEED, distributed=bool(distributed))
+    if isinstance(class_weights, str):          # 'enet': from the class counts of the cached training labels (counted once, kept beside the cache)
+        from ..datasets.Cityscapes.class_weights import class_counts, enet_weights
+        from ..datasets.Cityscapes.loader import cache_dir_of
+        from ..models.transforms import DeviceBatchPreparation
+        lut = DeviceBatchPreparation(ds.LABEL_MAPPING_DICT, ds.MEAN, ds.STD, input_size, ds.IGNORE_CLASS_LABEL).lut_host
+        class_weights = enet_weights(class_counts(cache_dir_of(dataset), 'train', lut, device_obj)[:ds.NUM_CLASSES])
+    step = TrainStep(model, flat, stage, w1, w2, ds.IGNORE_CLASS_LABEL, class_weights=class_weights)
     train_loader = factory('train', batch_size, device_obj, rank, world)
     val_loader = factory('val', batch_size, device_obj, rank, world) if is_master_rank else None
 

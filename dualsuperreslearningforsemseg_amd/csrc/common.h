@@ -29,7 +29,8 @@ bool convt_bwd_dma_supported(const void* x, const void* dy, int W, int Cin, int 
 int convt_bwd_dma_blocks(long long nseg, int cap);
 int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, hipStream_t st);
 int launch_convt_bwd_dma_ce(const float* x, const float* w, const float* logits, float* dx, float* part, int N, int H, int W, int nblocks,
-                            const unsigned char* target, int ignore_index, const float* count, const float* ft_g, const float* ft_w, int ft_s, hipStream_t st);
+                            const unsigned char* target, int ignore_index, const float* count, const float* ft_g, const float* ft_w, int ft_s,
+                            const float* wtab /*null: unweighted; else the 256-float class-weight table and `count` points to D*/, hipStream_t st);
 
 // The one way the library reads a DSRL_* environment switch (table: DESIGN.md §9).  Read at every call, never cached: tests change switches
 // between calls inside one process.  knob_str: for the one switch whose value is a path (DSRL_PROF_DUMP).

@@ -38,12 +38,18 @@ struct ConvtCeArgs {
     const float* ft_g;              // (N, Hf, Wf) incoming gradient of the stride-s 1x1 conv on the logits, or null
     const float* ft_w;              // its CO weights
     int ignore_index, ft_s, ft_shift, Hf, Wf;     // ft_shift = log2(ft_s) when ft_s is a power of two, else -1
+    const float* wtab;              // CW: the 256-float class-weight table, and `count` points to D
 };
 
-template <int CI, int CO, bool CE, bool TW = false>
+// CW = true (dsrl_convt2x2_bwd_ce_w): nn.CrossEntropyLoss(weight=).  ce.count points to D = sum n_c w_c and the only change is in transform(): the
+// per-pixel sc = wtab[target] * (1 / D) stands where `scale` stands, as in ce_fused_body<true> (losses.hip).  The 256-float table sits in LDS, already
+// multiplied by 1 / D (indexed by the label byte: entries >= CO are zero).  A template parameter, so that the CW = false instantiations compile to the
+// code they were.
+template <int CI, int CO, bool CE, bool TW = false, bool CW = false>
 __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ dy,
                                                                  float* __restrict__ dx, float* __restrict__ part, int N, int H, int W,
                                                                  int nseg_per_row, int nseg, ConvtCeArgs ce) {
+    static_assert(CE || !CW, "class weights belong to the CE build");
     constexpr int TP = 128, COLS = 4 * CO, NK = COLS / 2, NJ = (COLS + 31) / 32, NOUT = CI * COLS;
     constexpr int XB = TP * CI * 4, XP = (XB + 1023) / 1024;               // bytes / 1 KB pieces of an x segment
     constexpr int GB = 2 * TP * CO * 4, GP = GB / 1024;                    // of one dy row segment
@@ -101,6 +107,12 @@ __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(con
         scale = 1.f / ce.count[0];
         if (tid < 32) ftw_s[tid] = (ce.ft_g && tid < CO) ? ce.ft_w[tid] : 0.f;          // visible after the first barrier below
     }
+    __shared__ float wt_s[CW ? 256 : 1];
+    if (CW) {
+        if (tid < 256) wt_s[tid] = ce.wtab[tid] * scale;                     // sc of a pixel with label tid
+        // block_barrier() is a bare s_barrier: it does not wait for this wave's ds_write, so drain the LDS counter before the barrier that publishes the table
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
     auto transform = [&](int seg, int slot) {                              // TW: wave wq of the tw waves takes 128 output pixels, two per lane; else every wave 64
         const int r = TW ? wq >> 1 : (is_dw ? 1 : 0);                       // output row 2h + r of the segment
         // the transformer's gradient g of this lane's pixels, fetched FIRST: the softmax arithmetic covers its latency (fetched where it is used it
@@ -148,9 +160,23 @@ __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(con
             // roundings of ce_fused_kernel and pointwise_bwd_kernel.  Everything stays in registers between the 19 reads and the 19 writes: a
             // read-modify-write of the target word in LDS instead of the 19 selects measured +11 us
             const bool live = tg != ce.ignore_index;
-            const float inv = scale / s;
+            if (CW) {
+                // sc = table[target] is per lane where `scale` is uniform: held across the 19 operations beside inv it is one VGPR more than the
+                // 768-thread build has (168, 2 spilled).  So it is read twice: for inv, and again - through a copy of the index the compiler cannot
+                // match - once inv is dead.  Same operations and roundings: (e * inv) - sc
+                const float inv = wt_s[tg] / s;
 #pragma unroll
-            for (int c = 0; c < CO; ++c) e[c] = live ? e[c] * inv - (c == tg ? scale : 0.f) : 0.f;
+                for (int c = 0; c < CO; ++c) e[c] *= inv;
+                int tg2 = tg;
+                asm volatile("" : "+v"(tg2));
+                const float sc = wt_s[tg2];
+#pragma unroll
+                for (int c = 0; c < CO; ++c) e[c] = live ? e[c] - (c == tg ? sc : 0.f) : 0.f;
+            } else {
+                const float inv = scale / s;
+#pragma unroll
+                for (int c = 0; c < CO; ++c) e[c] = live ? e[c] * inv - (c == tg ? scale : 0.f) : 0.f;
+            }
             if (any_grid) {                                                 // wave-uniform: every eighth lane of every fourth row at stride 8
 #pragma unroll
                 for (int c = 0; c < CO; ++c) e[c] = on_u ? e[c] + g_u * ftw_s[c] : e[c];
@@ -317,30 +343,35 @@ bool convt_bwd_dma_supported(const void* x, const void* dy, int W, int Cin, int 
 }
 int convt_bwd_dma_blocks(long long nseg, int cap) { return (int)std::min<long long>(std::min(cap, kNumCU), nseg); }
 
-template <bool CE, bool TW>
+template <bool CE, bool TW, bool CW = false>
 static int launch_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, const ConvtCeArgs& ce, hipStream_t st) {
     constexpr int CI = 19, CO = 19;
     constexpr int kLds = 3 * ((128 * CI * 4 + 1023) / 1024 + 2 * (2 * 128 * CO * 4 / 1024) + (CE ? 2 : 0)) * 1024;
-    static const hipError_t attr = hipFuncSetAttribute((const void*)convt2x2_bwd_dma_kernel<CI, CO, CE, TW>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+    static_assert(kLds + (CW ? 1024 : 0) + 128 <= 160 * 1024, "the ring, the transformer's weights and the class-weight table in LDS");
+    static const hipError_t attr = hipFuncSetAttribute((const void*)convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     if (attr != hipSuccess) { set_error("convt2x2_bwd_dma_kernel: %d bytes of LDS refused (%s)", kLds, hipGetErrorString(attr)); return DSRL_E_LAUNCH; }
     const int nseg_per_row = W / 128;
     const long long nseg = (long long)N * H * nseg_per_row;
     if ((long long)N * 4 * H * W * CO * 4 >= (1ll << 32)) { set_error("convt2x2_bwd_dma_kernel: output gradient of 4 GB or more"); return DSRL_E_UNSUPPORTED; }
     if (nseg >= (1ll << 31) || nblocks < 1 || nblocks > nseg) { set_error("convt2x2_bwd_dma_kernel: %lld segments, %d blocks", nseg, nblocks); return DSRL_E_BADARG; }
-    hipLaunchKernelGGL((convt2x2_bwd_dma_kernel<CI, CO, CE, TW>), dim3(nblocks), dim3(TW ? 768 : 512), kLds, st, x, w, dy, dx, part, N, H, W, nseg_per_row, (int)nseg, ce);
+    hipLaunchKernelGGL((convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW>), dim3(nblocks), dim3(TW ? 768 : 512), kLds, st, x, w, dy, dx, part, N, H, W, nseg_per_row, (int)nseg, ce);
     return launch_status("convt2x2_bwd_dma_kernel");
 }
 int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, hipStream_t st) {
     return launch_dma<false, false>(x, w, dy, dx, part, N, H, W, nblocks, ConvtCeArgs{}, st);
 }
 int launch_convt_bwd_dma_ce(const float* x, const float* w, const float* logits, float* dx, float* part, int N, int H, int W, int nblocks,
-                            const unsigned char* target, int ignore_index, const float* count, const float* ft_g, const float* ft_w, int ft_s, hipStream_t st) {
+                            const unsigned char* target, int ignore_index, const float* count, const float* ft_g, const float* ft_w, int ft_s,
+                            const float* wtab, hipStream_t st) {
     ConvtCeArgs ce{};
     ce.target = target; ce.count = count; ce.ft_g = ft_g; ce.ft_w = ft_w; ce.ignore_index = ignore_index; ce.ft_s = ft_s > 0 ? ft_s : 1;
-    ce.ft_shift = -1;
+    ce.ft_shift = -1; ce.wtab = wtab;
     for (int b = 0; b < 31; ++b) if (ce.ft_s == (1 << b)) ce.ft_shift = b;
     ce.Hf = (2 * H - 1) / ce.ft_s + 1; ce.Wf = (2 * W - 1) / ce.ft_s + 1;
-    if (knob("DSRL_CONVT_CE_WAVES", 12) == 8) return launch_dma<true, false>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);      // the transform inside the MFMA waves
+    const bool w8 = knob("DSRL_CONVT_CE_WAVES", 12) == 8;                  // the transform inside the MFMA waves
+    if (wtab) return w8 ? launch_dma<true, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st)
+                        : launch_dma<true, true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
+    if (w8) return launch_dma<true, false>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
     return launch_dma<true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
 }
 

@@ -16,8 +16,12 @@ __device__ inline double block_sum_d(double v, double* sh) {     // sh: 4 double
 
 // ---------------------------------------------------------------------------------------------- cross entropy
 // A block stages 256 pixels x C logits through LDS (contiguous global reads), one thread per pixel.
-__global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
-                                                      int ignore_index, double* __restrict__ part) {
+// CW = true (the *_w_kernel entry of each body below): nn.CrossEntropyLoss(weight=): `wtab` is the 256-float class-weight table indexed by the label byte
+// (entries >= C are zero, so no label can index past it), a pixel's term is (double)w[t] * (double)nll and the mean's denominator is D = sum n_c w_c,
+// left by ce_weight_sum_kernel where the unweighted kernels leave the pixel count.  The CW = false bodies are the kernels as they were.
+template <bool CW>
+__device__ __forceinline__ void ce_fwd_body(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                            int ignore_index, const float* __restrict__ wtab, double* __restrict__ part) {
     extern __shared__ float tile[];         // [256][C]
     __shared__ double shd[4];
     double loss = 0.0, cnt = 0.0;
@@ -36,7 +40,8 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
                 for (int c = 0; c < C; ++c) s += expf(v[c] - m);
                 // a label outside [0, C) that is not ignore_index: torch's CrossEntropyLoss asserts; here it poisons the loss (as ce_fused_kernel does)
                 const float vt = tg < C ? v[tg] : __builtin_nanf("");
-                loss += (double)(m + logf(s) - vt);
+                if (CW) loss += (double)wtab[tg] * (double)(m + logf(s) - vt);
+                else loss += (double)(m + logf(s) - vt);
                 cnt += 1.0;
             }
         }
@@ -44,6 +49,14 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
     const double l = block_sum_d(loss, shd);
     const double n = block_sum_d(cnt, shd);
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = l; part[2 * blockIdx.x + 1] = n; }
+}
+__global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                      int ignore_index, double* __restrict__ part) {
+    ce_fwd_body<false>(logits, ld, target, P, C, ignore_index, nullptr, part);
+}
+__global__ __launch_bounds__(256) void ce_fwd_w_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                        int ignore_index, const float* __restrict__ wtab, double* __restrict__ part) {
+    ce_fwd_body<true>(logits, ld, target, P, C, ignore_index, wtab, part);
 }
 __global__ __launch_bounds__(256) void ce_finalize_kernel(const double* __restrict__ part, int nb, float* __restrict__ out) {
     __shared__ double shd[4];
@@ -55,9 +68,18 @@ __global__ __launch_bounds__(256) void ce_finalize_kernel(const double* __restri
         out[1] = (float)n;
     }
 }
-__global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
-                                                      int ignore_index, const float* __restrict__ loss_out, const float* __restrict__ grad_out,
-                                                      float* __restrict__ dl, int lddl) {
+// weighted: out[1] already holds D (ce_weight_sum_kernel); out[0] = sum w nll / D, 0/0 = NaN when every live pixel has weight 0, as torch
+__global__ __launch_bounds__(256) void ce_finalize_w_kernel(const double* __restrict__ part, int nb, float* __restrict__ out) {
+    __shared__ double shd[4];
+    double l = 0;
+    for (int i = threadIdx.x; i < nb; i += 256) l += part[2 * i];
+    l = block_sum_d(l, shd);
+    if (threadIdx.x == 0) out[0] = (float)(l / (double)out[1]);
+}
+template <bool CW>
+__device__ __forceinline__ void ce_bwd_body(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                            int ignore_index, const float* __restrict__ wtab, const float* __restrict__ loss_out,
+                                            const float* __restrict__ grad_out, float* __restrict__ dl, int lddl) {
     extern __shared__ float tile[];
     const float scale = grad_out[0] / loss_out[1];
     for (long long p0 = (long long)blockIdx.x * 256; p0 < P; p0 += (long long)gridDim.x * 256) {
@@ -75,7 +97,8 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
                 for (int c = 0; c < C; ++c) s += expf(v[c] - m);
                 const float inv = 1.f / s;
                 const bool bad = tg >= C;             // label outside [0, C), not ignored: a NaN gradient row, as the loss
-                for (int c = 0; c < C; ++c) v[c] = bad ? __builtin_nanf("") : (expf(v[c] - m) * inv - (c == tg ? 1.f : 0.f)) * scale;
+                const float sc = CW ? wtab[tg] * scale : scale;
+                for (int c = 0; c < C; ++c) v[c] = bad ? __builtin_nanf("") : (expf(v[c] - m) * inv - (c == tg ? 1.f : 0.f)) * sc;
             } else {
                 for (int c = 0; c < C; ++c) v[c] = 0.f;
             }
@@ -83,6 +106,16 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
         __syncthreads();
         for (int t = threadIdx.x; t < np * C; t += 256) { const int r = t / C, c = t - r * C; dl[(p0 + r) * lddl + c] = tile[t]; }
     }
+}
+__global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                      int ignore_index, const float* __restrict__ loss_out, const float* __restrict__ grad_out,
+                                                      float* __restrict__ dl, int lddl) {
+    ce_bwd_body<false>(logits, ld, target, P, C, ignore_index, nullptr, loss_out, grad_out, dl, lddl);
+}
+__global__ __launch_bounds__(256) void ce_bwd_w_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                        int ignore_index, const float* __restrict__ wtab, const float* __restrict__ loss_out,
+                                                        const float* __restrict__ grad_out, float* __restrict__ dl, int lddl) {
+    ce_bwd_body<true>(logits, ld, target, P, C, ignore_index, wtab, loss_out, grad_out, dl, lddl);
 }
 
 // ---------------------------------------------------------------------------------------------- fused loss pass
@@ -118,19 +151,71 @@ __global__ __launch_bounds__(256) void count_valid_kernel(const unsigned char* _
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
 }
-__global__ __launch_bounds__(256) void ce_fused_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
-                                                        int ignore_index, const unsigned* __restrict__ cnt_part, float* __restrict__ dl, int lddl,
-                                                        double* __restrict__ part, int* __restrict__ nan_flag, int vec_in, int vec_out) {
+// ---------------------------------------------------------------------------------------------- class histogram, weighted denominator
+// Labels (through `lut` when given) -> 256 bins.  16 labels per load, per-wave LDS bins (a road-heavy label map sends most lanes of a wave to one
+// bin; four sets keep the waves of a block apart), the head up to the first 16-byte boundary and the tail byte by byte by block 0.  The bins leave as
+// 64-bit atomics into `counts` (accumulated: dsrl_class_histogram) or as the block's own row of `part` [gridDim.x][256] (nothing to zero, merged in
+// integers by ce_weight_sum_kernel) - exact and independent of the block order either way.
+constexpr int kHistBlocks = 256;
+__global__ __launch_bounds__(256) void class_hist_kernel(const unsigned char* __restrict__ labels, long long P, const unsigned char* __restrict__ lut,
+                                                          unsigned long long* __restrict__ counts, unsigned* __restrict__ part) {
+    __shared__ unsigned hist[4][256];
+    __shared__ unsigned char slut[256];
+    for (int t = threadIdx.x; t < 4 * 256; t += 256) (&hist[0][0])[t] = 0u;
+    slut[threadIdx.x] = lut ? lut[threadIdx.x] : (unsigned char)threadIdx.x;
+    __syncthreads();
+    unsigned* h = hist[threadIdx.x >> 6];
+    const long long head = min(P, (long long)((16 - ((uintptr_t)labels & 15)) & 15));
+    const long long nv = (P - head) >> 4;
+    const uint4* v = reinterpret_cast<const uint4*>(labels + head);
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < nv; e += (long long)gridDim.x * 256) {
+        const uint4 q = v[e];
+        const unsigned w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) atomicAdd(&h[slut[(w[u] >> (8 * b)) & 0xffu]], 1u);
+    }
+    if (blockIdx.x == 0) {
+        for (long long e = threadIdx.x; e < head; e += 256) atomicAdd(&h[slut[labels[e]]], 1u);
+        for (long long e = head + (nv << 4) + threadIdx.x; e < P; e += 256) atomicAdd(&h[slut[labels[e]]], 1u);
+    }
+    __syncthreads();
+    const unsigned n = hist[0][threadIdx.x] + hist[1][threadIdx.x] + hist[2][threadIdx.x] + hist[3][threadIdx.x];
+    if (part) part[(long long)blockIdx.x * 256 + threadIdx.x] = n;
+    else if (n) atomicAdd(&counts[threadIdx.x], (unsigned long long)n);
+}
+// D = fp32(sum over c ascending of (double)n_c * (double)w_c), n_c the pixels of class c that are not ignore_index: integer counts, one rounding.
+// Classes [0, C) only: whatever a caller's table holds from C on cannot change D.
+__global__ __launch_bounds__(256) void ce_weight_sum_kernel(const unsigned* __restrict__ part, int nb, int C, int ignore_index, const float* __restrict__ wtab,
+                                                             float* __restrict__ d_out) {
+    __shared__ double term[256];
+    unsigned long long n = 0;
+    for (int b = 0; b < nb; ++b) n += part[b * 256 + threadIdx.x];
+    term[threadIdx.x] = ((int)threadIdx.x == ignore_index || (int)threadIdx.x >= C) ? 0.0 : (double)n * (double)wtab[threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double d = 0.0;
+        for (int c = 0; c < C; ++c) d += term[c];
+        d_out[0] = (float)d;
+    }
+}
+
+template <bool CW>
+__device__ __forceinline__ void ce_fused_body(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                              int ignore_index, const unsigned* __restrict__ cnt_part, const float* __restrict__ wtab,
+                                              const float* __restrict__ wsum, float* __restrict__ dl, int lddl,
+                                              double* __restrict__ part, int* __restrict__ nan_flag, int vec_in, int vec_out) {
     extern __shared__ __attribute__((aligned(16))) float tile[];         // [256][C]
     __shared__ double shd[4];
     __shared__ float sh_scale;
-    {
+    if (!CW) {
         static_assert(kCountBlocks == 256, "one partial count per thread");
         const double n = block_sum_d((double)cnt_part[threadIdx.x], shd);       // exact: counts < 2^53
         if (threadIdx.x == 0) sh_scale = 1.f / (float)n;        // n = 0: every pixel ignored, the loss is 0/0 = NaN as in torch and no gradient element uses the scale
     }
     __syncthreads();
-    const float scale = sh_scale;
+    const float scale = CW ? 1.f / wsum[0] : sh_scale;      // CW: 1 / D; per pixel sc = w[t] * (1 / D)
     double loss = 0.0, cnt = 0.0;
     bool bad = false, bad_label = false;
     for (long long p0 = (long long)blockIdx.x * 256; p0 < P; p0 += (long long)gridDim.x * 256) {
@@ -156,11 +241,14 @@ __global__ __launch_bounds__(256) void ce_fused_kernel(const float* __restrict__
             for (int c = 0; c < C; ++c) { const float e = exp_nonpos(v[c] - m); s += e; v[c] = e; }       // the tile keeps exp(v - m): one exp per logit
             bad |= !(s == s);                   // any NaN logit poisons the sum (fmaxf alone would skip it)
             if (tg != ignore_index) {
-                loss += (double)(m + logf(s) - vt);
+                const float wt = CW ? wtab[tg] : 1.f;
+                if (CW) loss += (double)wt * (double)(m + logf(s) - vt);
+                else loss += (double)(m + logf(s) - vt);
                 cnt += 1.0;
                 if (dl) {
-                    const float inv = scale / s;
-                    for (int c = 0; c < C; ++c) v[c] = v[c] * inv - (c == tg ? scale : 0.f);
+                    const float sc = CW ? wt * scale : scale;
+                    const float inv = sc / s;
+                    for (int c = 0; c < C; ++c) v[c] = v[c] * inv - (c == tg ? sc : 0.f);
                 }
             } else if (dl) {
                 for (int c = 0; c < C; ++c) v[c] = 0.f;
@@ -183,6 +271,17 @@ __global__ __launch_bounds__(256) void ce_fused_kernel(const float* __restrict__
     if (threadIdx.x == 0) { part[2 * blockIdx.x] = l; part[2 * blockIdx.x + 1] = n; }
     if (nan_flag && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(nan_flag, 1);
     if (nan_flag && __any(bad_label) && (threadIdx.x & 63) == 0) atomicOr(nan_flag, 2);
+}
+__global__ __launch_bounds__(256) void ce_fused_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                        int ignore_index, const unsigned* __restrict__ cnt_part, float* __restrict__ dl, int lddl,
+                                                        double* __restrict__ part, int* __restrict__ nan_flag, int vec_in, int vec_out) {
+    ce_fused_body<false>(logits, ld, target, P, C, ignore_index, cnt_part, nullptr, nullptr, dl, lddl, part, nan_flag, vec_in, vec_out);
+}
+__global__ __launch_bounds__(256) void ce_fused_w_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                          int ignore_index, const float* __restrict__ wtab, const float* __restrict__ wsum,
+                                                          float* __restrict__ dl, int lddl, double* __restrict__ part, int* __restrict__ nan_flag,
+                                                          int vec_in, int vec_out) {
+    ce_fused_body<true>(logits, ld, target, P, C, ignore_index, nullptr, wtab, wsum, dl, lddl, part, nan_flag, vec_in, vec_out);
 }
 // MSE forward and backward in one pass: partial sums of (a-b)^2 and da = (a-b) * 2 * grad_scale / n; NaN check of `a`
 __global__ __launch_bounds__(256) void mse_fused_kernel(const float* __restrict__ a, const float* __restrict__ b, long long n, float sc, float* __restrict__ da,
@@ -689,6 +788,80 @@ extern "C" int dsrl_ce_fused(const float* logits, int ld, const uint8_t* target,
     if (int e = launch_status("ce_fused_kernel")) return e;
     hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nb, loss_out);
     return launch_status("ce_finalize_kernel");
+}
+// ---- class-weighted cross entropy: nn.CrossEntropyLoss(weight, ignore_index).  Every weighted entry point starts with the same pre-pass (per-block
+// integer histograms of the labels, then D in one block), so D is the same bits in all of them.
+static int hist_blocks(long long P) { return (int)std::max<long long>(1, std::min<long long>(kHistBlocks, ceil_div(P, 4096))); }
+static constexpr size_t kWeightSumBytes = (size_t)kHistBlocks * 256 * sizeof(unsigned);
+int launch_ce_weight_sum(const unsigned char* target, long long P, int C, int ignore_index, const float* weights, float* d_out, void* ws, hipStream_t st) {
+    const int nb = hist_blocks(P);
+    hipLaunchKernelGGL(class_hist_kernel, dim3(nb), dim3(256), 0, st, target, P, (const unsigned char*)nullptr, (unsigned long long*)nullptr, (unsigned*)ws);
+    if (int e = launch_status("class_hist_kernel")) return e;
+    hipLaunchKernelGGL(ce_weight_sum_kernel, dim3(1), dim3(256), 0, st, (const unsigned*)ws, nb, C, ignore_index, weights, d_out);
+    return launch_status("ce_weight_sum_kernel");
+}
+int launch_ce_finalize_w(const double* part, int nb, float* loss_out, hipStream_t st) {      // for dsrl_convt2x2_fwd_ce_w (spatial.hip)
+    hipLaunchKernelGGL(ce_finalize_w_kernel, dim3(1), dim3(256), 0, st, part, nb, loss_out);
+    return launch_status("ce_finalize_w_kernel");
+}
+size_t ce_weight_sum_bytes() { return kWeightSumBytes; }
+extern "C" int dsrl_class_histogram(const uint8_t* labels, int64_t P, const uint8_t* lut, unsigned long long* counts, dsrl_stream_t stream) {
+    DSRL_REQUIRE(labels && counts && P > 0, DSRL_E_BADARG, "class_histogram: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    hipLaunchKernelGGL(class_hist_kernel, dim3(hist_blocks(P)), dim3(256), 0, st, labels, (long long)P, lut, counts, (unsigned*)nullptr);
+    return launch_status("class_hist_kernel");
+}
+extern "C" size_t dsrl_ce_weight_sum_workspace_bytes(void) { return kWeightSumBytes; }
+extern "C" int dsrl_ce_weight_sum(const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float* d_out,
+                                  void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_REQUIRE(target && weights && d_out && ws && P > 0 && C > 0 && C <= 256, DSRL_E_BADARG, "ce_weight_sum: bad arguments (C=%d)", C);
+    DSRL_REQUIRE(ws_bytes >= kWeightSumBytes && ((uintptr_t)ws % 4) == 0, DSRL_E_WORKSPACE, "ce_weight_sum: workspace too small or misaligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    return launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, d_out, ws, st);
+}
+extern "C" size_t dsrl_ce_w_workspace_bytes(int64_t P) { return dsrl_ce_workspace_bytes(P) + kWeightSumBytes; }
+extern "C" int dsrl_ce_fwd_w(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float* loss_out,
+                             void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_REQUIRE(logits && target && weights && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C, DSRL_E_BADARG, "ce_fwd_w: bad arguments (C=%d)", C);
+    DSRL_REQUIRE(ws_bytes >= dsrl_ce_w_workspace_bytes(P) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fwd_w: workspace too small or misaligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    const int nb = loss_blocks(P);
+    double* part = (double*)ws;
+    if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, loss_out + 1, part + 2 * nb, st)) return e;
+    hipLaunchKernelGGL(ce_fwd_w_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index, weights, part);
+    if (int e = launch_status("ce_fwd_w_kernel")) return e;
+    return launch_ce_finalize_w(part, nb, loss_out, st);
+}
+extern "C" int dsrl_ce_bwd_w(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, const float* loss_out,
+                             const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
+    DSRL_REQUIRE(logits && target && weights && loss_out && grad_out && dlogits && P > 0 && C > 0 && C <= 60 && ld >= C && lddl >= C, DSRL_E_BADARG,
+                 "ce_bwd_w: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    hipLaunchKernelGGL(ce_bwd_w_kernel, dim3((unsigned)std::min<long long>(ceil_div(P, 256), 8192)), dim3(256), (size_t)256 * C * sizeof(float), st,
+                       logits, ld, target, (long long)P, C, ignore_index, weights, loss_out, grad_out, dlogits, lddl);
+    return launch_status("ce_bwd_w_kernel");
+}
+extern "C" size_t dsrl_ce_fused_w_workspace_bytes(int64_t P) { return (size_t)2 * loss_blocks(P) * sizeof(double) + kWeightSumBytes; }
+extern "C" int dsrl_ce_fused_w(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights,
+                               float* dlogits, int lddl, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_REQUIRE(logits && target && weights && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C && (!dlogits || lddl >= C), DSRL_E_BADARG,
+                 "ce_fused_w: bad arguments (C=%d)", C);
+    DSRL_REQUIRE(ws_bytes >= dsrl_ce_fused_w_workspace_bytes(P) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fused_w: workspace too small or misaligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    const int nb = loss_blocks(P);
+    double* part = (double*)ws;
+    if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, loss_out + 1, part + 2 * nb, st)) return e;
+    const int vec_in = (ld == C && ((uintptr_t)logits % 16) == 0) ? 1 : 0;
+    const int vec_out = (dlogits && lddl == C && ((uintptr_t)dlogits % 16) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(ce_fused_w_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index,
+                       weights, (const float*)(loss_out + 1), dlogits, lddl, part, nan_flag, vec_in, vec_out);
+    if (int e = launch_status("ce_fused_w_kernel")) return e;
+    return launch_ce_finalize_w(part, nb, loss_out, st);
 }
 extern "C" int dsrl_mse_fused(const float* a, const float* b, int64_t n, float grad_scale, float* da, float* loss_out, int* nan_flag,
                               void* ws, size_t ws_bytes, dsrl_stream_t stream) {

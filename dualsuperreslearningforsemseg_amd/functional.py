@@ -11,6 +11,8 @@ import os
 import sys
 import weakref
 
+import numpy as np
+
 import torch
 
 from . import _lib
@@ -1294,12 +1296,13 @@ class LogitsGrad:
     leaves `target`, `count` (device pointer holder) here and reports no gradient; the stride-8 feature transformer leaves its incoming gradient and
     weights; the ConvTranspose backward then forms d(CE)/d(logits) (+ the transformer's rank-one term) inside its own kernel
     (dsrl_convt2x2_bwd_ce): the 319 MB gradient of the 256x512 step is neither written nor read."""
-    __slots__ = ('y', 'xshape', 'x_ptr', 'armed', 'target', 'ignore_index', 'count', 'ft', 'value', 'value_key')
+    __slots__ = ('y', 'xshape', 'x_ptr', 'armed', 'target', 'ignore_index', 'count', 'ft', 'value', 'value_key', 'weight')
 
     def __init__(self):
         self.y = None; self.xshape = None; self.x_ptr = 0; self.armed = False; self.target = None; self.ignore_index = 255; self.count = None; self.ft = None
         self.value = None           # [CE, pixel count, ...] when the producing layer already evaluated the loss (logits_target), and for which
-        self.value_key = None       # (target pointer, ignore_index, NaN flag pointer)
+        self.value_key = None       # (target pointer, ignore_index, NaN flag pointer, class-weight table pointer or 0)
+        self.weight = None          # the 256-float class-weight table of a weighted loss (class_weight_table); `count` then holds D = sum n_c w_c
 
     def usable(self, logits, target):
         """Can the loss leave the gradient to the producer?  logits must be exactly the producer's output buffer."""
@@ -1310,6 +1313,52 @@ class LogitsGrad:
 
 
 
+def class_weight_table(weights, device, num_classes=None):
+    """Per-class loss weights (nn.CrossEntropyLoss(weight=)) -> the 256-float table the weighted kernels index by the label byte: entries
+    [0, len(weights)) hold the weights as fp32, the rest are zero.  Negative, NaN or infinite weights (also after rounding to fp32), an empty or
+    over-long sequence, or a length other than `num_classes` when that is given, raise ValueError.  Zero weights are allowed.  Equal weights on one
+    device ('cuda' means the current device) give the SAME tensor, so that the hand-over of the CE value keyed by its pointer
+    (LogitsGrad.value_key) engages however the caller passes them.  A table returned by this function is recognised as that object and passed
+    through without a host read; any other tensor (a clone or a copy of a table included) is validated on the host, which a graph capture does
+    not allow: under capture pass the table itself, as TrainStep does."""
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    if isinstance(weights, torch.Tensor):
+        made = _weight_tables_made.get(id(weights)) if weights.device == dev else None
+        if made is not None and made[0]() is weights:
+            if num_classes is not None and made[1] != int(num_classes):
+                raise ValueError(f'class weights: table of {made[1]} classes, the logits have {int(num_classes)}')
+            return weights
+        weights = weights.detach().cpu().numpy()
+    try:
+        w = np.asarray(weights, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f'class weights: not a sequence of numbers ({e})')
+    if w.ndim != 1 or w.size == 0 or w.size > 256:
+        raise ValueError(f'class weights: expected a sequence of 1..256 numbers, got shape {w.shape}')
+    if num_classes is not None and w.size != int(num_classes):
+        raise ValueError(f'class weights: {w.size} weights for {int(num_classes)} classes')
+    with np.errstate(over='ignore'):
+        w32 = w.astype(np.float32)
+    if not np.isfinite(w32).all() or (w32 < 0).any():
+        raise ValueError('class weights must be finite and >= 0')
+    key = (w32.tobytes(), dev)
+    tab = _weight_tables.get(key)
+    if tab is None:
+        while len(_weight_tables) >= _WEIGHT_TABLES_MAX:                # oldest first (dicts keep insertion order)
+            _weight_tables.pop(next(iter(_weight_tables)))              # (a table somebody still holds stays recognised: the registry below is weak)
+        full = np.zeros(256, np.float32); full[:w32.size] = w32
+        tab = torch.from_numpy(full).to(dev)
+        _weight_tables[key] = tab
+        ident = id(tab)
+        _weight_tables_made[ident] = (weakref.ref(tab, lambda _, ident=ident: _weight_tables_made.pop(ident, None)), int(w32.size))
+    return tab
+
+
+_WEIGHT_TABLES_MAX = 32
+_weight_tables = {}             # (fp32 weight bytes, device) -> table
+_weight_tables_made = {}        # id(table) -> (weak reference, number of classes): how a table made here is recognised for as long as it lives
 _logits_target = None
 
 
@@ -1317,12 +1366,15 @@ class logits_target:
     """with logits_target(target, ignore_index, flag): ... model(x) ... - tells the layer that produces the logits (HipConvTranspose2d.logits_layer) what
     they will be compared with, so that its forward kernel evaluates nn.CrossEntropyLoss while the output tile is on chip (dsrl_convt2x2_fwd_ce) and
     fused_losses finds the value ready (LogitsGrad.value) instead of reading the logits again.  target: (N,H,W) uint8, contiguous; flag: the int32 NaN
-    flag fused_losses will be given.  Outside the block, or when the shape does not qualify, nothing changes."""
+    flag fused_losses will be given; weight: the class weights fused_losses will be given (None: unweighted).  Outside the block, or when the shape
+    does not qualify, nothing changes."""
 
-    def __init__(self, target, ignore_index, flag):
+    def __init__(self, target, ignore_index, flag, weight=None):
         ok = (convt_ce_enabled and target is not None and target.is_cuda and target.dtype == torch.uint8 and target.is_contiguous() and target.dim() == 3
               and flag is not None and flag.dtype == torch.int32)
-        self.new = (target, int(ignore_index), flag) if ok else None
+        if weight is not None and target is not None:
+            weight = class_weight_table(weight, target.device)
+        self.new = (target, int(ignore_index), flag, weight) if ok else None
 
     def __enter__(self):
         global _logits_target
@@ -1352,12 +1404,18 @@ class _ConvT2x2(torch.autograd.Function):
         lt = _logits_target if holder is not None else None
         if (lt is not None and tuple(lt[0].shape) == (N, 2 * H, 2 * W) and lt[0].device == x.device
                 and query('dsrl_convt2x2_fwd_ce_supported', x.data_ptr(), y.data_ptr(), N, H, W, Ci, Co)):       # (pointer arguments: not memoised)
-            tgt, ign, flag = lt
+            tgt, ign, flag, wt = lt
             holder.value = torch.empty(8, device=x.device, dtype=torch.float32)
-            holder.value_key = (tgt.data_ptr(), ign, flag.data_ptr())
-            ws = _ws(cquery('dsrl_convt2x2_fwd_ce_workspace_bytes', N, H, W), x)
-            call('dsrl_convt2x2_fwd_ce', x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co,
-                 tgt.data_ptr(), ign, holder.value.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+            holder.value_key = (tgt.data_ptr(), ign, flag.data_ptr(), 0 if wt is None else wt.data_ptr())
+            if wt is None:
+                ws = _ws(cquery('dsrl_convt2x2_fwd_ce_workspace_bytes', N, H, W), x)
+                call('dsrl_convt2x2_fwd_ce', x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co,
+                     tgt.data_ptr(), ign, holder.value.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+            else:
+                wt = class_weight_table(wt, x.device, Co)
+                ws = _ws(cquery('dsrl_convt2x2_fwd_ce_w_workspace_bytes', N, H, W), x)
+                call('dsrl_convt2x2_fwd_ce_w', x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co,
+                     tgt.data_ptr(), ign, wt.data_ptr(), holder.value.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
         else:
             call('dsrl_convt2x2_fwd', x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co, _stream())
         ctx.save_for_backward(x, w)
@@ -1376,8 +1434,8 @@ class _ConvT2x2(torch.autograd.Function):
         h = ctx.holder
         hand = None
         if h is not None and h.armed:           # the loss left d(CE)/d(logits) to this layer: take it over, and disarm the holder whatever happens next
-            hand = (h.y, h.target, int(h.ignore_index), h.count, h.ft)
-            h.armed = False; h.ft = None; h.target = None; h.count = None; h.y = None; h.value = None
+            hand = (h.y, h.target, int(h.ignore_index), h.count, h.ft, h.weight)
+            h.armed = False; h.ft = None; h.target = None; h.count = None; h.y = None; h.value = None; h.weight = None
         fused = dy is None and hand is not None
         if dy is None and not fused:
             raise DsrlHipError('conv_transpose2d_k2s2: backward reached without a gradient for the output')
@@ -1387,12 +1445,17 @@ class _ConvT2x2(torch.autograd.Function):
             # another consumer of the logits sent a gradient too (it is not the loss's: fused_losses returned none): d(CE)/d(logits) and the
             # transformer's term are written as the unfused step writes them (dsrl_ce_fused, dsrl_pointwise_strided_bwd(accumulate = 1)), dy is
             # added as autograd would add it, and the plain backward below takes the sum
-            y, target, ign, _, ft = hand
+            y, target, ign, _, ft, wt = hand
             P = N * 4 * H * W
             dl = new_cl((N, Co, 2 * H, 2 * W), x)
             scal = torch.empty(8, device=x.device, dtype=torch.float32)
-            wsc = _ws(cquery('dsrl_ce_fused_workspace_bytes', P), x)
-            call('dsrl_ce_fused', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, dl.data_ptr(), Co, scal.data_ptr(), None, wsc.data_ptr(), wsc.numel(), _stream())
+            if wt is None:
+                wsc = _ws(cquery('dsrl_ce_fused_workspace_bytes', P), x)
+                call('dsrl_ce_fused', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, dl.data_ptr(), Co, scal.data_ptr(), None, wsc.data_ptr(), wsc.numel(), _stream())
+            else:
+                wsc = _ws(cquery('dsrl_ce_fused_w_workspace_bytes', P), x)
+                call('dsrl_ce_fused_w', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, wt.data_ptr(), dl.data_ptr(), Co, scal.data_ptr(), None,
+                     wsc.data_ptr(), wsc.numel(), _stream())
             if ft is not None:
                 ft_g, ft_w, ft_s = ft
                 dwf = torch.empty(Co, device=x.device, dtype=torch.float32)          # the transformer's weight gradient was delivered by its own backward
@@ -1407,11 +1470,16 @@ class _ConvT2x2(torch.autograd.Function):
         db = (bsink if bsink is not None else torch.empty(Co, device=x.device, dtype=torch.float32)) if ctx.has_bias else None
         ws = _ws(cquery('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, Ci, Co), x)
         if fused:
-            y, target, ign, count, ft = hand
+            y, target, ign, count, ft, wt = hand
             ft_g, ft_w, ft_s = ft if ft is not None else (None, None, 0)
-            call('dsrl_convt2x2_bwd_ce', x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, count.data_ptr() + 4,
-                 None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
-                 dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
+            if wt is None:
+                call('dsrl_convt2x2_bwd_ce', x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, count.data_ptr() + 4,
+                     None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
+                     dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
+            else:
+                call('dsrl_convt2x2_bwd_ce_w', x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, wt.data_ptr(), count.data_ptr() + 4,
+                     None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
+                     dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
         else:
             call('dsrl_convt2x2_bwd', x.data_ptr(), w.data_ptr(), dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(),
                  N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
@@ -1519,7 +1587,7 @@ def pointwise_strided(x, weight, stride, out_slot=None):
 # ------------------------------------------------------------------------------------------------ losses
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, ignore_index):
+    def forward(ctx, logits, target, ignore_index, weight=None):
         logits, ld = pm(logits)
         _need_gpu(target)
         if target.dtype != torch.uint8:
@@ -1530,10 +1598,16 @@ class _CrossEntropy(torch.autograd.Function):
         if target.numel() != P:
             raise DsrlHipError(f'cross_entropy: target has {target.numel()} pixels, logits {P}')
         out = torch.empty(2, device=logits.device, dtype=torch.float32)
-        ws = _ws(cquery('dsrl_ce_workspace_bytes', P), logits)
-        call('dsrl_ce_fwd', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        if weight is None:
+            ws = _ws(cquery('dsrl_ce_workspace_bytes', P), logits)
+            call('dsrl_ce_fwd', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        else:
+            ws = _ws(cquery('dsrl_ce_w_workspace_bytes', P), logits)
+            call('dsrl_ce_fwd_w', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(), out.data_ptr(),
+                 ws.data_ptr(), ws.numel(), _stream())
         ctx.save_for_backward(logits, target, out)
         ctx.ignore_index = int(ignore_index)
+        ctx.weight = weight
         return out[0].clone()
 
     @staticmethod
@@ -1543,14 +1617,21 @@ class _CrossEntropy(torch.autograd.Function):
         N, Cc, H, W = logits.shape
         g = g.reshape(1).contiguous().float()
         dl = new_cl((N, Cc, H, W), logits)
-        call('dsrl_ce_bwd', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, out.data_ptr(), g.data_ptr(),
-             dl.data_ptr(), Cc, _stream())
-        return dl, None, None
+        if ctx.weight is None:
+            call('dsrl_ce_bwd', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, out.data_ptr(), g.data_ptr(),
+                 dl.data_ptr(), Cc, _stream())
+        else:
+            call('dsrl_ce_bwd_w', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, ctx.weight.data_ptr(), out.data_ptr(),
+                 g.data_ptr(), dl.data_ptr(), Cc, _stream())
+        return dl, None, None, None
 
 
-def cross_entropy(logits, target, ignore_index=255):
-    """nn.CrossEntropyLoss(ignore_index) with mean reduction; target (N,H,W) uint8/long."""
-    return _CrossEntropy.apply(logits, target, ignore_index)
+def cross_entropy(logits, target, ignore_index=255, weight=None):
+    """nn.CrossEntropyLoss(weight, ignore_index) with mean reduction; target (N,H,W) uint8/long; weight: None, one number per class, or a
+    class_weight_table."""
+    if weight is not None:
+        weight = class_weight_table(weight, logits.device, logits.shape[1])
+    return _CrossEntropy.apply(logits, target, ignore_index, weight)
 
 
 class _MSE(torch.autograd.Function):
@@ -1587,7 +1668,7 @@ class _FusedLosses(torch.autograd.Function):
     its incoming gradient is 1 (TrainStep calls vals[3].backward()); the stored gradients are returned as they are."""
 
     @staticmethod
-    def forward(ctx, sssr, sisr, ft1, ft2, target, org, ignore_index, w1, w2, stage, flag, k):
+    def forward(ctx, sssr, sisr, ft1, ft2, target, org, ignore_index, w1, w2, stage, flag, k, weight=None):
         want = bool(ctx.needs_input_grad[0])          # forward-only (validation, no_grad): no gradient buffers are written
         logits, ld = pm(sssr)
         _need_gpu(target)
@@ -1606,12 +1687,17 @@ class _FusedLosses(torch.autograd.Function):
         if lg is not None and not (ld == Cc and lg.usable(logits, target)):
             lg = None
         dl = new_cl((N, Cc, H, W), logits) if (want and lg is None) else None      # lg: the producer of the logits forms this gradient in its own backward
-        if lg is not None and lg.value is not None and lg.value_key == (target.data_ptr(), int(ignore_index), flag.data_ptr()):
+        if lg is not None and lg.value is not None and lg.value_key == (target.data_ptr(), int(ignore_index), flag.data_ptr(),
+                                                                        0 if weight is None else weight.data_ptr()):
             scal = lg.value                                             # the producer's forward kernel evaluated the loss (logits_target)
-        else:
+        elif weight is None:
             ws = _ws(cquery('dsrl_ce_fused_workspace_bytes', P), logits)
             call('dsrl_ce_fused', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), None if dl is None else dl.data_ptr(), Cc,
                  scal.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        else:
+            ws = _ws(cquery('dsrl_ce_fused_w_workspace_bytes', P), logits)
+            call('dsrl_ce_fused_w', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(),
+                 None if dl is None else dl.data_ptr(), Cc, scal.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
         da = None
         mse_ptr = fa_ptr = None
         ctx.fa = None
@@ -1640,7 +1726,7 @@ class _FusedLosses(torch.autograd.Function):
             ctx.fa = (ft1, ft2, saved, k, fa_out)
         call('dsrl_loss_mix', scal.data_ptr(), mse_ptr, fa_ptr, float(w1), float(w2), flag.data_ptr(), vals.data_ptr(), st)
         if lg is not None:
-            lg.target = target; lg.ignore_index = int(ignore_index); lg.count = scal; lg.ft = None; lg.armed = True
+            lg.target = target; lg.ignore_index = int(ignore_index); lg.count = scal; lg.ft = None; lg.weight = weight; lg.armed = True
         ctx.lg = lg
         ctx.grads = (dl, da)
         ctx.w2 = float(w2)
@@ -1680,7 +1766,7 @@ class _FusedLosses(torch.autograd.Function):
             if slot is not None and buf is not None and not slot.closed and slot.buf is None:
                 slot.buf = buf
                 out[i] = None
-        return out[0], out[1], d1, d2, None, None, None, None, None, None, None, None
+        return out[0], out[1], d1, d2, None, None, None, None, None, None, None, None, None
 
 
 _fused_losses_root_checked = False
@@ -1712,13 +1798,16 @@ def fused_losses_backward(vals):
     torch.autograd.backward([vals], [e3])
 
 
-def fused_losses(outs, target, input_org, ignore_index, w1, w2, stage, flag, subsample_factor=8):
+def fused_losses(outs, target, input_org, ignore_index, w1, w2, stage, flag, subsample_factor=8, weight=None):
     """-> 5-float device tensor [CE, w1*MSE, w2*FA, total, NaN flag]; `outs` = DSRL.forward's 4-tuple.  vals[3].backward() is the only
-    supported backward (the function is the root of the pass); `flag` is the int32 NaN flag the fused kernels OR into."""
+    supported backward (the function is the root of the pass); `flag` is the int32 NaN flag the fused kernels OR into.  weight: per-class CE
+    weights (None, one number per class, or a class_weight_table): nn.CrossEntropyLoss(weight=)."""
     sssr, sisr, ft1, ft2 = outs
+    if weight is not None:
+        weight = class_weight_table(weight, sssr.device, sssr.shape[1])
     dummy = _const1(0.0, sssr.device)            # stands in for the outputs a lower stage does not have (a cached constant: no fill launch per step)
     return _FusedLosses.apply(sssr, sisr if stage > 1 else dummy, ft1 if stage > 2 else dummy, ft2 if stage > 2 else dummy, target,
-                              input_org if stage > 1 else dummy, int(ignore_index), float(w1), float(w2), int(stage), flag, int(subsample_factor))
+                              input_org if stage > 1 else dummy, int(ignore_index), float(w1), float(w2), int(stage), flag, int(subsample_factor), weight)
 
 
 _RED = {'mean': 0, 'sum': 1, 'none': 2}

@@ -418,6 +418,43 @@ int dsrl_mse_fused(const float* a, const float* b, int64_t n, float grad_scale, 
 int dsrl_loss_mix(const float* ce, const float* mse /*nullable*/, const float* fa /*nullable*/, float w1, float w2, const int* nan_flag /*nullable*/,
                   float* vals /*[5]*/, dsrl_stream_t stream);
 
+/* Class-weighted cross entropy: nn.CrossEntropyLoss(weight, ignore_index, reduction='mean').  `weights` is a device table of 256 floats indexed
+ * directly by the label byte: entries [0, C) hold the class weights (finite, >= 0), entries >= C are zero, so a label outside the classes never
+ * reads out of bounds (it still makes the loss NaN and raises flag bit 1).  With nll_i = m_i + log s_i - v_i[t_i]:
+ *     n_c  = pixels with t_i == c and t_i != ignore_index                         (exact integers: per-block histograms merged in integers)
+ *     D    = fp32(sum over c ascending of (double)n_c * (double)w_c)             (rounded once; identical in every entry point)
+ *     loss = (sum_i (double)w[t_i] * (double)nll_i) / D                           (0/0 = NaN when every live pixel has weight 0, as torch)
+ *     dl_ic = sc_i * e_ic / s_i - (c == t_i ? sc_i : 0),  sc_i = w[t_i] * (1 / D);  ignored pixel: zeros
+ * D takes the place of the pixel count: loss_out[1] = D, and dsrl_convt2x2_bwd_ce_w reads it there.  Everything runs on the stream (no host read),
+ * so the calls can be captured.  All-ones weights give the bits of the unweighted entry points while the pixel count is below 2^24.
+ * dsrl_ce_weight_sum is the pre-pass alone (d_out[0] = D, summed over the classes [0, C) only); each *_w entry point below runs it first.  The _w forms otherwise keep the contracts
+ * of dsrl_ce_fwd / dsrl_ce_bwd / dsrl_ce_fused / dsrl_convt2x2_fwd_ce / dsrl_convt2x2_bwd_ce; the weighted dsrl_convt2x2_bwd_ce_w is bit-identical to
+ * dsrl_ce_fused_w -> dsrl_pointwise_strided_bwd(accumulate = 1) -> dsrl_convt2x2_bwd. */
+size_t dsrl_ce_weight_sum_workspace_bytes(void);
+int dsrl_ce_weight_sum(const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights /*[256]*/, float* d_out,
+                       void* ws, size_t ws_bytes, dsrl_stream_t stream);
+size_t dsrl_ce_w_workspace_bytes(int64_t P);
+int dsrl_ce_fwd_w(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights /*[256]*/,
+                  float* loss_out /*[2]*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+int dsrl_ce_bwd_w(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights /*[256]*/,
+                  const float* loss_out, const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream);
+size_t dsrl_ce_fused_w_workspace_bytes(int64_t P);
+int dsrl_ce_fused_w(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights /*[256]*/,
+                    float* dlogits /*nullable*/, int lddl, float* loss_out /*[2]*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes,
+                    dsrl_stream_t stream);
+size_t dsrl_convt2x2_fwd_ce_w_workspace_bytes(int N, int H, int W);
+int dsrl_convt2x2_fwd_ce_w(const float* x, const float* w, const float* bias /*nullable*/, float* y, int N, int H, int W, int Cin, int Cout,
+                           const uint8_t* target, int ignore_index, const float* weights /*[256]*/, float* loss_out, int* nan_flag /*nullable*/,
+                           void* ws, size_t ws_bytes, dsrl_stream_t stream);
+int dsrl_convt2x2_bwd_ce_w(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* weights /*[256]*/,
+                           const float* ce_wsum /*D: loss_out + 1*/, const float* ft_g /*nullable*/, const float* ft_w /*nullable*/, int ft_stride,
+                           float* dx, float* dw, float* dbias /*nullable*/, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes,
+                           dsrl_stream_t stream);
+/* counts[lut ? lut[label] : label] += 1 for each of the P label bytes (counts: 256 accumulated 64-bit counters; 64-bit integer atomics, exact and
+ * order independent, like dsrl_seg_metrics).  The label buffer may start at any byte. */
+int dsrl_class_histogram(const uint8_t* labels, int64_t P, const uint8_t* lut /*nullable, [256]*/, unsigned long long* counts /*[256]*/,
+                         dsrl_stream_t stream);
+
 /* FALoss (models/losses/FALoss.py:8-34). fm1/fm2 are (B,C,H,W) with element strides (sb,sc,sh,sw).
  * reduction: 0 mean, 1 sum, 2 none (out has B*C*n*n floats, n = (W/k)^2).
  * `saved` (>= dsrl_fa_saved_floats) carries S1,S2,sigma,u1,v1 to the backward. */
