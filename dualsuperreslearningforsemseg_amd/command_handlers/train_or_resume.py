@@ -81,12 +81,16 @@ class TrainStep:
 
     `class_weights` (None, or one number per class): nn.CrossEntropyLoss(weight=) for the CE term of every path of the step - fused and unfused
     losses, eager and captured, training and `do_train=False` (the reference shares one `loss_funcs` between training and validation).  With more
-    than one rank each rank normalises by the weight sum of its own batch and the gradients are averaged, as DDP with a weighted loss does."""
+    than one rank each rank normalises by the weight sum of its own batch and the gradients are averaged, as DDP with a weighted loss does.
+
+    `focal_gamma` (a finite number >= 0; 0: off): the CE term becomes the focal loss sum w[t] (1 - p_t)^gamma (-log p_t) / sum w[t] on the same paths,
+    `do_train=False` included (early stopping compares the two).  It runs on the weighted kernels: without `class_weights` the weights are all ones."""
 
     GRAPH_WARMUP = HF.GRAPH_WARMUP          # eager iterations per batch shape before the capture
 
-    def __init__(self, model, flat, stage, w1, w2, ignore_index, graph=None, class_weights=None):
+    def __init__(self, model, flat, stage, w1, w2, ignore_index, graph=None, class_weights=None, focal_gamma=0.0):
         self.model, self.flat, self.stage, self.w1, self.w2, self.ignore = model, flat, stage, w1, w2, ignore_index
+        self.focal_gamma = HF.focal_gamma_value(focal_gamma)                                                          # ValueError on a bad gamma
         self.class_weight = None if class_weights is None else HF.class_weight_table(class_weights, flat.device)     # ValueError on bad weights
         self.fa = FALoss()
         dev = flat.device
@@ -116,7 +120,7 @@ class TrainStep:
 
     def losses(self, outs, input_org, target):
         SSSR, SISR, SSSR_ft, SISR_ft = outs
-        ce = HF.cross_entropy(SSSR, target, self.ignore, self.class_weight)                # train_or_resume.py:435
+        ce = HF.cross_entropy(SSSR, target, self.ignore, self.class_weight, self.focal_gamma)      # train_or_resume.py:435
         ms = self.w1 * HF.mse_loss(SISR, input_org) if self.stage > 1 else self.zero       # :436
         fa = self.w2 * self.fa(SSSR_ft, SISR_ft) if self.stage > 2 else self.zero          # :437
         return ce, ms, fa, ce + ms + fa                                                    # :438
@@ -143,14 +147,14 @@ class TrainStep:
                 if self.fused_losses and do_train:
                     # the layer that produces the logits evaluates the CE value in its own forward kernel (HF.logits_target), :435
                     with HF.logits_target(target if target.dtype == t.uint8 and target.is_contiguous() else None, self.ignore, self.flag,
-                                          self.class_weight):
+                                          self.class_weight, self.focal_gamma):
                         outs = self.model(input_image)                                     # :420
                 else:
                     outs = self.model(input_image)                                         # :420
                 if self.fused_losses:
                     # CE + MSE + FA, their gradients, the NaN asserts (:426-433) and the loss mix (:435-438) in one launch set
                     vals = HF.fused_losses(outs, target, input_org, self.ignore, self.w1, self.w2, self.stage, self.flag, self.fa.subsample_factor,
-                                           self.class_weight)
+                                           self.class_weight, self.focal_gamma)
                     total = vals[3]
                 else:
                     HF.nan_check_(self.flag, *[o for o in outs if o.is_cuda])              # the four NaN asserts, :426-433
@@ -407,6 +411,12 @@ def check_class_weights(dataset, num_classes):
     return HF.class_weight_table(cw, 'cpu', num_classes)[:num_classes].numpy()
 
 
+def check_focal_gamma(dataset):
+    """dataset['focal_gamma']: absent, None or 0 -> 0.0 (off); a finite number > 0 -> that float; ValueError otherwise.  Touches no device."""
+    g = dataset.get('focal_gamma')
+    return 0.0 if g is None else HF.focal_gamma_value(g)
+
+
 def train_or_resume(is_resuming_training, device, distributed, mixed_precision, disable_cudnn_benchmark, num_workers, dataset, val_interval,
                     checkpoint_interval, checkpoint_history, init_weights, batch_size, epochs, learning_rate, end_learning_rate, momentum,
                     weights_decay, poly_power, stage, w1, w2, freeze_batch_norm, experiment_id, description, early_stopping, dry_run=False, **other_args):
@@ -417,6 +427,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
                            '(apex itself is not used: the opt level selects the MFMA conv arithmetic)')
     conv_arith = settings.MIXED_PRECISION_TO_CONV_ARITHMETIC[mixed_precision]
     class_weights = check_class_weights(dataset, dataset['settings'].NUM_CLASSES)
+    focal_gamma = check_focal_gamma(dataset)
     input_size = other_args.get('model_input_size', settings.MODEL_INPUT_SIZE)
     if distributed:
         t.manual_seed(settings.RANDOM_SEED)                                                # identical init on all ranks, :31
@@ -471,7 +482,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
         from ..models.transforms import DeviceBatchPreparation
         lut = DeviceBatchPreparation(ds.LABEL_MAPPING_DICT, ds.MEAN, ds.STD, input_size, ds.IGNORE_CLASS_LABEL).lut_host
         class_weights = enet_weights(class_counts(cache_dir_of(dataset), 'train', lut, device_obj)[:ds.NUM_CLASSES])
-    step = TrainStep(model, flat, stage, w1, w2, ds.IGNORE_CLASS_LABEL, class_weights=class_weights)
+    step = TrainStep(model, flat, stage, w1, w2, ds.IGNORE_CLASS_LABEL, class_weights=class_weights, focal_gamma=focal_gamma)
     train_loader = factory('train', batch_size, device_obj, rank, world)
     val_loader = factory('val', batch_size, device_obj, rank, world) if is_master_rank else None
 

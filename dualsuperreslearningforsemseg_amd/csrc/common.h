@@ -21,6 +21,10 @@ int launch_status(const char* what);
         }                                    \
     } while (0)
 
+// the focal entry points (dsrl_*_f) check their gamma before anything else: finite and >= 0 (a NaN fails the comparison)
+#define DSRL_FOCAL_GAMMA(gamma, what) \
+    DSRL_REQUIRE((gamma) >= 0.f && (gamma) <= 3.402823466e+38f, DSRL_E_BADARG, what ": gamma = %g is not a finite number >= 0", (double)(gamma))
+
 // Binds the calling thread to the device that owns `stream` (autograd runs backward on its own thread).
 int bind_stream_device(hipStream_t s);
 
@@ -30,7 +34,8 @@ int convt_bwd_dma_blocks(long long nseg, int cap);
 int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, hipStream_t st);
 int launch_convt_bwd_dma_ce(const float* x, const float* w, const float* logits, float* dx, float* part, int N, int H, int W, int nblocks,
                             const unsigned char* target, int ignore_index, const float* count, const float* ft_g, const float* ft_w, int ft_s,
-                            const float* wtab /*null: unweighted; else the 256-float class-weight table and `count` points to D*/, hipStream_t st);
+                            const float* wtab /*null: unweighted; else the 256-float class-weight table and `count` points to D*/,
+                            float gamma /*> 0 (with wtab): focal*/, hipStream_t st);
 
 // The one way the library reads a DSRL_* environment switch (table: DESIGN.md §9).  Read at every call, never cached: tests change switches
 // between calls inside one process.  knob_str: for the one switch whose value is a path (DSRL_PROF_DUMP).
@@ -82,6 +87,31 @@ __device__ __forceinline__ float exp_nonpos(float x) {
     const float r = t > -INFINITY ? fmaf(x, L2E_LO, fmaf(x, L2E_HI, -t)) : 0.f;
     const float e0 = __builtin_amdgcn_exp2f(t);
     return fmaf(e0, r * LN2, e0);
+}
+
+// ---------------------------------------------------------------- focal cross entropy, the arithmetic of one live pixel
+// term_i = w[t] q^g nll, d loss / d v_c = (w[t] / D) mod (softmax_c - [c == t]), mod = q^(g-1) (q + g p nll), with q = 1 - p_t.  The caller passes
+//     m = max_c v_c, vt = v_t, et = exp_nonpos(vt - m), s = sum_c e_c and so = sum_{c != t} e_c (both with c ascending, e_t taken as 0 in `so`)
+// and gets fl = q^g nll and mod; the weight, 1 / D and the double accumulation stay with the kernel.  Every focal kernel (losses.hip, spatial.hip,
+// convt_dma.hip) goes through this one function, so that the fused and the unfused paths round alike (the library is built with -ffp-contract=off).
+//   q = so / s, never 1 - p: a confident pixel would lose all of q, and q^g with it, to cancellation.
+//   nll = (m - vt) + log s, not m + log s - vt: at logits near 1e4 the latter costs an ulp(1e4), which the modulator does not tolerate.
+//   q^g = 2^(g log2 q) on v_log_f32 / v_exp_f32 (1 ulp each): the error of the exponent, g |log2 q| 2^-23 relative, is weighted by q^g |log q|
+//   <= 1 / (e g) in the value and in the gradient alike, i.e. below an ulp of their bounds.
+//   Limits: q == 0 -> fl = 0, mod = 0 for every g > 0 (also a q below the smallest normal number, which v_log_f32 does not read: q^g underflows
+//   there for g >= 1 and is below 1.1e-19 for g = 1/2); p == 0 -> p nll taken as 0, so that mod = 1 at q = 1 even where nll overflows.
+__device__ __forceinline__ void focal_pixel(float m, float vt, float et, float s, float so, float gamma, float& fl, float& mod) {
+    const float d = m - vt;
+    const float nll = d + logf(s);
+    const float q = so / s;
+    const float p = et / s;
+    const float l2 = __builtin_amdgcn_logf(q);                              // log2 q <= 0
+    const float qg = __builtin_amdgcn_exp2f(gamma * l2);                    // q^g
+    const float qg1 = __builtin_amdgcn_exp2f((gamma - 1.f) * l2);           // q^(g-1)
+    const float pn = p == 0.f ? 0.f : p * nll;
+    const bool zero = q < 1.17549435e-38f;                                  // (a NaN q compares false and goes through)
+    fl = zero ? 0.f : qg * nll;
+    mod = zero ? 0.f : qg1 * (q + gamma * pn);
 }
 
 // ---------------------------------------------------------------- wave / block reductions

@@ -39,17 +39,22 @@ struct ConvtCeArgs {
     const float* ft_w;              // its CO weights
     int ignore_index, ft_s, ft_shift, Hf, Wf;     // ft_shift = log2(ft_s) when ft_s is a power of two, else -1
     const float* wtab;              // CW: the 256-float class-weight table, and `count` points to D
+    float gamma;                    // FL: the focal exponent (> 0)
 };
 
 // CW = true (dsrl_convt2x2_bwd_ce_w): nn.CrossEntropyLoss(weight=).  ce.count points to D = sum n_c w_c and the only change is in transform(): the
 // per-pixel sc = wtab[target] * (1 / D) stands where `scale` stands, as in ce_fused_body<true> (losses.hip).  The 256-float table sits in LDS, already
 // multiplied by 1 / D (indexed by the label byte: entries >= CO are zero).  A template parameter, so that the CW = false instantiations compile to the
 // code they were.
-template <int CI, int CO, bool CE, bool TW = false, bool CW = false>
+// FL = true (dsrl_convt2x2_bwd_ce_f): focal cross entropy.  transform() also forms so = sum_{c != t} e_c beside s and reads v_t once more from the
+// stage (the raw logits are still there), focal_pixel (common.h) gives mod from them, and sc = (w[t] * mod) * (1 / D) as in ce_fused_body<true, true>:
+// the table in LDS holds the raw weights here, so that the product rounds as it does there.  Everything after sc is the weighted code.
+template <int CI, int CO, bool CE, bool TW = false, bool CW = false, bool FL = false>
 __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ dy,
                                                                  float* __restrict__ dx, float* __restrict__ part, int N, int H, int W,
                                                                  int nseg_per_row, int nseg, ConvtCeArgs ce) {
     static_assert(CE || !CW, "class weights belong to the CE build");
+    static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
     constexpr int TP = 128, COLS = 4 * CO, NK = COLS / 2, NJ = (COLS + 31) / 32, NOUT = CI * COLS;
     constexpr int XB = TP * CI * 4, XP = (XB + 1023) / 1024;               // bytes / 1 KB pieces of an x segment
     constexpr int GB = 2 * TP * CO * 4, GP = GB / 1024;                    // of one dy row segment
@@ -109,7 +114,7 @@ __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(con
     }
     __shared__ float wt_s[CW ? 256 : 1];
     if (CW) {
-        if (tid < 256) wt_s[tid] = ce.wtab[tid] * scale;                     // sc of a pixel with label tid
+        if (tid < 256) wt_s[tid] = FL ? ce.wtab[tid] : ce.wtab[tid] * scale;   // sc of a pixel with label tid (FL: its weight, sc needs the pixel's mod)
         // block_barrier() is a bare s_barrier: it does not wait for this wave's ds_write, so drain the LDS counter before the barrier that publishes the table
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
@@ -153,14 +158,22 @@ __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(con
             float m = e[0];
 #pragma unroll
             for (int c = 1; c < CO; ++c) m = fmaxf(m, e[c]);
-            float s = 0.f;
+            float s = 0.f, so = 0.f;
 #pragma unroll
-            for (int c = 0; c < CO; ++c) { e[c] = exp_nonpos(e[c] - m); s += e[c]; }
+            for (int c = 0; c < CO; ++c) { e[c] = exp_nonpos(e[c] - m); s += e[c]; if (FL) so += c == tg ? 0.f : e[c]; }
             // e_c * inv - (c == tg ? scale : 0), zeros for an ignored pixel; then the feature transformer's term: ((e * inv) - scale) + g * w, the
             // roundings of ce_fused_kernel and pointwise_bwd_kernel.  Everything stays in registers between the 19 reads and the 19 writes: a
             // read-modify-write of the target word in LDS instead of the 19 selects measured +11 us
             const bool live = tg != ce.ignore_index;
-            if (CW) {
+            if (FL) {
+                const float vt = v[min(live ? tg : 0, CO - 1)];              // as ce_fused_body reads it; e_t = exp_nonpos(vt - m) has the bits of e[t]
+                float fl, mod;
+                focal_pixel(m, vt, exp_nonpos(vt - m), s, so, ce.gamma, fl, mod);
+                const float sc = (wt_s[tg] * mod) * scale;
+                const float inv = sc / s;
+#pragma unroll
+                for (int c = 0; c < CO; ++c) e[c] = live ? e[c] * inv - (c == tg ? sc : 0.f) : 0.f;
+            } else if (CW) {
                 // sc = table[target] is per lane where `scale` is uniform: held across the 19 operations beside inv it is one VGPR more than the
                 // 768-thread build has (168, 2 spilled).  So it is read twice: for inv, and again - through a copy of the index the compiler cannot
                 // match - once inv is dead.  Same operations and roundings: (e * inv) - sc
@@ -343,18 +356,18 @@ bool convt_bwd_dma_supported(const void* x, const void* dy, int W, int Cin, int 
 }
 int convt_bwd_dma_blocks(long long nseg, int cap) { return (int)std::min<long long>(std::min(cap, kNumCU), nseg); }
 
-template <bool CE, bool TW, bool CW = false>
+template <bool CE, bool TW, bool CW = false, bool FL = false>
 static int launch_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, const ConvtCeArgs& ce, hipStream_t st) {
     constexpr int CI = 19, CO = 19;
     constexpr int kLds = 3 * ((128 * CI * 4 + 1023) / 1024 + 2 * (2 * 128 * CO * 4 / 1024) + (CE ? 2 : 0)) * 1024;
     static_assert(kLds + (CW ? 1024 : 0) + 128 <= 160 * 1024, "the ring, the transformer's weights and the class-weight table in LDS");
-    static const hipError_t attr = hipFuncSetAttribute((const void*)convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+    static const hipError_t attr = hipFuncSetAttribute((const void*)convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     if (attr != hipSuccess) { set_error("convt2x2_bwd_dma_kernel: %d bytes of LDS refused (%s)", kLds, hipGetErrorString(attr)); return DSRL_E_LAUNCH; }
     const int nseg_per_row = W / 128;
     const long long nseg = (long long)N * H * nseg_per_row;
     if ((long long)N * 4 * H * W * CO * 4 >= (1ll << 32)) { set_error("convt2x2_bwd_dma_kernel: output gradient of 4 GB or more"); return DSRL_E_UNSUPPORTED; }
     if (nseg >= (1ll << 31) || nblocks < 1 || nblocks > nseg) { set_error("convt2x2_bwd_dma_kernel: %lld segments, %d blocks", nseg, nblocks); return DSRL_E_BADARG; }
-    hipLaunchKernelGGL((convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW>), dim3(nblocks), dim3(TW ? 768 : 512), kLds, st, x, w, dy, dx, part, N, H, W, nseg_per_row, (int)nseg, ce);
+    hipLaunchKernelGGL((convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL>), dim3(nblocks), dim3(TW ? 768 : 512), kLds, st, x, w, dy, dx, part, N, H, W, nseg_per_row, (int)nseg, ce);
     return launch_status("convt2x2_bwd_dma_kernel");
 }
 int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, hipStream_t st) {
@@ -362,13 +375,16 @@ int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float*
 }
 int launch_convt_bwd_dma_ce(const float* x, const float* w, const float* logits, float* dx, float* part, int N, int H, int W, int nblocks,
                             const unsigned char* target, int ignore_index, const float* count, const float* ft_g, const float* ft_w, int ft_s,
-                            const float* wtab, hipStream_t st) {
+                            const float* wtab, float gamma, hipStream_t st) {
     ConvtCeArgs ce{};
     ce.target = target; ce.count = count; ce.ft_g = ft_g; ce.ft_w = ft_w; ce.ignore_index = ignore_index; ce.ft_s = ft_s > 0 ? ft_s : 1;
-    ce.ft_shift = -1; ce.wtab = wtab;
+    ce.ft_shift = -1; ce.wtab = wtab; ce.gamma = gamma;
     for (int b = 0; b < 31; ++b) if (ce.ft_s == (1 << b)) ce.ft_shift = b;
     ce.Hf = (2 * H - 1) / ce.ft_s + 1; ce.Wf = (2 * W - 1) / ce.ft_s + 1;
     const bool w8 = knob("DSRL_CONVT_CE_WAVES", 12) == 8;                  // the transform inside the MFMA waves
+    // focal: the 8-wave build whatever DSRL_CONVT_CE_WAVES says.  focal_pixel's log and two divisions beside the 19 terms need 172 VGPRs in the
+    // 12-wave build, which has 168 (4 spilled, 20 B of scratch); the 8-wave build has 256 and takes 212
+    if (wtab && gamma > 0.f) return launch_dma<true, false, true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
     if (wtab) return w8 ? launch_dma<true, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st)
                         : launch_dma<true, true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
     if (w8) return launch_dma<true, false>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);

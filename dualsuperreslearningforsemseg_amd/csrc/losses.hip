@@ -19,9 +19,12 @@ __device__ inline double block_sum_d(double v, double* sh) {     // sh: 4 double
 // CW = true (the *_w_kernel entry of each body below): nn.CrossEntropyLoss(weight=): `wtab` is the 256-float class-weight table indexed by the label byte
 // (entries >= C are zero, so no label can index past it), a pixel's term is (double)w[t] * (double)nll and the mean's denominator is D = sum n_c w_c,
 // left by ce_weight_sum_kernel where the unweighted kernels leave the pixel count.  The CW = false bodies are the kernels as they were.
-template <bool CW>
+// FL = true (the *_f_kernel entries): focal cross entropy, a pixel's term is (double)w[t] * (double)(q^gamma nll) and its gradient scale
+// (w[t] * mod) * (1 / D), both from focal_pixel (common.h) on exp_nonpos terms; D, the flags and the staging are those of the weighted bodies.
+template <bool CW, bool FL = false>
 __device__ __forceinline__ void ce_fwd_body(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
-                                            int ignore_index, const float* __restrict__ wtab, double* __restrict__ part) {
+                                            int ignore_index, const float* __restrict__ wtab, double* __restrict__ part, float gamma = 0.f) {
+    static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
     extern __shared__ float tile[];         // [256][C]
     __shared__ double shd[4];
     double loss = 0.0, cnt = 0.0;
@@ -36,12 +39,21 @@ __device__ __forceinline__ void ce_fwd_body(const float* __restrict__ logits, in
                 const float* v = tile + threadIdx.x * C;
                 float m = v[0];
                 for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
-                float s = 0.f;
-                for (int c = 0; c < C; ++c) s += expf(v[c] - m);
-                // a label outside [0, C) that is not ignore_index: torch's CrossEntropyLoss asserts; here it poisons the loss (as ce_fused_kernel does)
-                const float vt = tg < C ? v[tg] : __builtin_nanf("");
-                if (CW) loss += (double)wtab[tg] * (double)(m + logf(s) - vt);
-                else loss += (double)(m + logf(s) - vt);
+                if (FL) {
+                    float s = 0.f, so = 0.f;
+                    for (int c = 0; c < C; ++c) { const float e = exp_nonpos(v[c] - m); s += e; so += c == tg ? 0.f : e; }
+                    const float vt = v[min(tg, C - 1)];
+                    float fl, mod;
+                    focal_pixel(m, vt, exp_nonpos(vt - m), s, so, gamma, fl, mod);
+                    loss += (double)wtab[tg] * (double)(tg < C ? fl : __builtin_nanf(""));
+                } else {
+                    float s = 0.f;
+                    for (int c = 0; c < C; ++c) s += expf(v[c] - m);
+                    // a label outside [0, C) that is not ignore_index: torch's CrossEntropyLoss asserts; here it poisons the loss (as ce_fused_kernel does)
+                    const float vt = tg < C ? v[tg] : __builtin_nanf("");
+                    if (CW) loss += (double)wtab[tg] * (double)(m + logf(s) - vt);
+                    else loss += (double)(m + logf(s) - vt);
+                }
                 cnt += 1.0;
             }
         }
@@ -57,6 +69,10 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
 __global__ __launch_bounds__(256) void ce_fwd_w_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
                                                         int ignore_index, const float* __restrict__ wtab, double* __restrict__ part) {
     ce_fwd_body<true>(logits, ld, target, P, C, ignore_index, wtab, part);
+}
+__global__ __launch_bounds__(256) void ce_fwd_f_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                        int ignore_index, const float* __restrict__ wtab, float gamma, double* __restrict__ part) {
+    ce_fwd_body<true, true>(logits, ld, target, P, C, ignore_index, wtab, part, gamma);
 }
 __global__ __launch_bounds__(256) void ce_finalize_kernel(const double* __restrict__ part, int nb, float* __restrict__ out) {
     __shared__ double shd[4];
@@ -76,10 +92,11 @@ __global__ __launch_bounds__(256) void ce_finalize_w_kernel(const double* __rest
     l = block_sum_d(l, shd);
     if (threadIdx.x == 0) out[0] = (float)(l / (double)out[1]);
 }
-template <bool CW>
+template <bool CW, bool FL = false>
 __device__ __forceinline__ void ce_bwd_body(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
                                             int ignore_index, const float* __restrict__ wtab, const float* __restrict__ loss_out,
-                                            const float* __restrict__ grad_out, float* __restrict__ dl, int lddl) {
+                                            const float* __restrict__ grad_out, float* __restrict__ dl, int lddl, float gamma = 0.f) {
+    static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
     extern __shared__ float tile[];
     const float scale = grad_out[0] / loss_out[1];
     for (long long p0 = (long long)blockIdx.x * 256; p0 < P; p0 += (long long)gridDim.x * 256) {
@@ -93,12 +110,23 @@ __device__ __forceinline__ void ce_bwd_body(const float* __restrict__ logits, in
             if (tg != ignore_index) {
                 float m = v[0];
                 for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
-                float s = 0.f;
-                for (int c = 0; c < C; ++c) s += expf(v[c] - m);
-                const float inv = 1.f / s;
                 const bool bad = tg >= C;             // label outside [0, C), not ignored: a NaN gradient row, as the loss
-                const float sc = CW ? wtab[tg] * scale : scale;
-                for (int c = 0; c < C; ++c) v[c] = bad ? __builtin_nanf("") : (expf(v[c] - m) * inv - (c == tg ? 1.f : 0.f)) * sc;
+                if (FL) {
+                    const float vt = v[min(tg, C - 1)];
+                    float s = 0.f, so = 0.f;
+                    for (int c = 0; c < C; ++c) { const float e = exp_nonpos(v[c] - m); s += e; so += c == tg ? 0.f : e; v[c] = e; }
+                    float fl, mod;
+                    focal_pixel(m, vt, exp_nonpos(vt - m), s, so, gamma, fl, mod);
+                    const float sc = (wtab[tg] * mod) * scale;
+                    const float inv = 1.f / s;
+                    for (int c = 0; c < C; ++c) v[c] = bad ? __builtin_nanf("") : (v[c] * inv - (c == tg ? 1.f : 0.f)) * sc;
+                } else {
+                    float s = 0.f;
+                    for (int c = 0; c < C; ++c) s += expf(v[c] - m);
+                    const float inv = 1.f / s;
+                    const float sc = CW ? wtab[tg] * scale : scale;
+                    for (int c = 0; c < C; ++c) v[c] = bad ? __builtin_nanf("") : (expf(v[c] - m) * inv - (c == tg ? 1.f : 0.f)) * sc;
+                }
             } else {
                 for (int c = 0; c < C; ++c) v[c] = 0.f;
             }
@@ -116,6 +144,11 @@ __global__ __launch_bounds__(256) void ce_bwd_w_kernel(const float* __restrict__
                                                         int ignore_index, const float* __restrict__ wtab, const float* __restrict__ loss_out,
                                                         const float* __restrict__ grad_out, float* __restrict__ dl, int lddl) {
     ce_bwd_body<true>(logits, ld, target, P, C, ignore_index, wtab, loss_out, grad_out, dl, lddl);
+}
+__global__ __launch_bounds__(256) void ce_bwd_f_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                        int ignore_index, const float* __restrict__ wtab, float gamma, const float* __restrict__ loss_out,
+                                                        const float* __restrict__ grad_out, float* __restrict__ dl, int lddl) {
+    ce_bwd_body<true, true>(logits, ld, target, P, C, ignore_index, wtab, loss_out, grad_out, dl, lddl, gamma);
 }
 
 // ---------------------------------------------------------------------------------------------- fused loss pass
@@ -201,11 +234,12 @@ __global__ __launch_bounds__(256) void ce_weight_sum_kernel(const unsigned* __re
     }
 }
 
-template <bool CW>
+template <bool CW, bool FL = false>
 __device__ __forceinline__ void ce_fused_body(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
                                               int ignore_index, const unsigned* __restrict__ cnt_part, const float* __restrict__ wtab,
                                               const float* __restrict__ wsum, float* __restrict__ dl, int lddl,
-                                              double* __restrict__ part, int* __restrict__ nan_flag, int vec_in, int vec_out) {
+                                              double* __restrict__ part, int* __restrict__ nan_flag, int vec_in, int vec_out, float gamma = 0.f) {
+    static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
     extern __shared__ __attribute__((aligned(16))) float tile[];         // [256][C]
     __shared__ double shd[4];
     __shared__ float sh_scale;
@@ -237,16 +271,26 @@ __device__ __forceinline__ void ce_fused_body(const float* __restrict__ logits, 
             float m = v[0];
             for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
             const float vt = v[max(min(tg == ignore_index ? 0 : tg, C - 1), 0)];
-            float s = 0.f;
-            for (int c = 0; c < C; ++c) { const float e = exp_nonpos(v[c] - m); s += e; v[c] = e; }       // the tile keeps exp(v - m): one exp per logit
+            float s = 0.f, so = 0.f;
+            if (FL) {                           // so: the sum without the target's term, in the same order
+                for (int c = 0; c < C; ++c) { const float e = exp_nonpos(v[c] - m); s += e; so += c == tg ? 0.f : e; v[c] = e; }
+            } else {
+                for (int c = 0; c < C; ++c) { const float e = exp_nonpos(v[c] - m); s += e; v[c] = e; }   // the tile keeps exp(v - m): one exp per logit
+            }
             bad |= !(s == s);                   // any NaN logit poisons the sum (fmaxf alone would skip it)
             if (tg != ignore_index) {
                 const float wt = CW ? wtab[tg] : 1.f;
-                if (CW) loss += (double)wt * (double)(m + logf(s) - vt);
+                float mod = 1.f;
+                if (FL) {
+                    float fl;
+                    focal_pixel(m, vt, exp_nonpos(vt - m), s, so, gamma, fl, mod);
+                    loss += (double)wt * (double)fl;
+                }
+                else if (CW) loss += (double)wt * (double)(m + logf(s) - vt);
                 else loss += (double)(m + logf(s) - vt);
                 cnt += 1.0;
                 if (dl) {
-                    const float sc = CW ? wt * scale : scale;
+                    const float sc = FL ? (wt * mod) * scale : CW ? wt * scale : scale;
                     const float inv = sc / s;
                     for (int c = 0; c < C; ++c) v[c] = v[c] * inv - (c == tg ? sc : 0.f);
                 }
@@ -282,6 +326,12 @@ __global__ __launch_bounds__(256) void ce_fused_w_kernel(const float* __restrict
                                                           float* __restrict__ dl, int lddl, double* __restrict__ part, int* __restrict__ nan_flag,
                                                           int vec_in, int vec_out) {
     ce_fused_body<true>(logits, ld, target, P, C, ignore_index, nullptr, wtab, wsum, dl, lddl, part, nan_flag, vec_in, vec_out);
+}
+__global__ __launch_bounds__(256) void ce_fused_f_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                          int ignore_index, const float* __restrict__ wtab, float gamma, const float* __restrict__ wsum,
+                                                          float* __restrict__ dl, int lddl, double* __restrict__ part, int* __restrict__ nan_flag,
+                                                          int vec_in, int vec_out) {
+    ce_fused_body<true, true>(logits, ld, target, P, C, ignore_index, nullptr, wtab, wsum, dl, lddl, part, nan_flag, vec_in, vec_out, gamma);
 }
 // MSE forward and backward in one pass: partial sums of (a-b)^2 and da = (a-b) * 2 * grad_scale / n; NaN check of `a`
 __global__ __launch_bounds__(256) void mse_fused_kernel(const float* __restrict__ a, const float* __restrict__ b, long long n, float sc, float* __restrict__ da,
@@ -861,6 +911,57 @@ extern "C" int dsrl_ce_fused_w(const float* logits, int ld, const uint8_t* targe
     hipLaunchKernelGGL(ce_fused_w_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index,
                        weights, (const float*)(loss_out + 1), dlogits, lddl, part, nan_flag, vec_in, vec_out);
     if (int e = launch_status("ce_fused_w_kernel")) return e;
+    return launch_ce_finalize_w(part, nb, loss_out, st);
+}
+// ---- focal cross entropy: the weighted entry points with one more per-pixel factor (focal_pixel, common.h).  Same pre-pass, same D, same workspaces.
+// gamma == 0 is the weighted loss itself and goes to the _w entry point: no focal kernel runs with it.
+extern "C" size_t dsrl_ce_f_workspace_bytes(int64_t P) { return dsrl_ce_w_workspace_bytes(P); }
+extern "C" int dsrl_ce_fwd_f(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float gamma,
+                             float* loss_out, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_FOCAL_GAMMA(gamma, "ce_fwd_f");
+    if (gamma == 0.f) return dsrl_ce_fwd_w(logits, ld, target, P, C, ignore_index, weights, loss_out, ws, ws_bytes, stream);
+    DSRL_REQUIRE(logits && target && weights && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C, DSRL_E_BADARG, "ce_fwd_f: bad arguments (C=%d)", C);
+    DSRL_REQUIRE(ws_bytes >= dsrl_ce_f_workspace_bytes(P) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fwd_f: workspace too small or misaligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    const int nb = loss_blocks(P);
+    double* part = (double*)ws;
+    if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, loss_out + 1, part + 2 * nb, st)) return e;
+    hipLaunchKernelGGL(ce_fwd_f_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index, weights,
+                       gamma, part);
+    if (int e = launch_status("ce_fwd_f_kernel")) return e;
+    return launch_ce_finalize_w(part, nb, loss_out, st);
+}
+extern "C" int dsrl_ce_bwd_f(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float gamma,
+                             const float* loss_out, const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
+    DSRL_FOCAL_GAMMA(gamma, "ce_bwd_f");
+    if (gamma == 0.f) return dsrl_ce_bwd_w(logits, ld, target, P, C, ignore_index, weights, loss_out, grad_out, dlogits, lddl, stream);
+    DSRL_REQUIRE(logits && target && weights && loss_out && grad_out && dlogits && P > 0 && C > 0 && C <= 60 && ld >= C && lddl >= C, DSRL_E_BADARG,
+                 "ce_bwd_f: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    hipLaunchKernelGGL(ce_bwd_f_kernel, dim3((unsigned)std::min<long long>(ceil_div(P, 256), 8192)), dim3(256), (size_t)256 * C * sizeof(float), st,
+                       logits, ld, target, (long long)P, C, ignore_index, weights, gamma, loss_out, grad_out, dlogits, lddl);
+    return launch_status("ce_bwd_f_kernel");
+}
+extern "C" size_t dsrl_ce_fused_f_workspace_bytes(int64_t P) { return dsrl_ce_fused_w_workspace_bytes(P); }
+extern "C" int dsrl_ce_fused_f(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float gamma,
+                               float* dlogits, int lddl, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_FOCAL_GAMMA(gamma, "ce_fused_f");
+    if (gamma == 0.f) return dsrl_ce_fused_w(logits, ld, target, P, C, ignore_index, weights, dlogits, lddl, loss_out, nan_flag, ws, ws_bytes, stream);
+    DSRL_REQUIRE(logits && target && weights && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C && (!dlogits || lddl >= C), DSRL_E_BADARG,
+                 "ce_fused_f: bad arguments (C=%d)", C);
+    DSRL_REQUIRE(ws_bytes >= dsrl_ce_fused_f_workspace_bytes(P) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fused_f: workspace too small or misaligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    const int nb = loss_blocks(P);
+    double* part = (double*)ws;
+    if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, loss_out + 1, part + 2 * nb, st)) return e;
+    const int vec_in = (ld == C && ((uintptr_t)logits % 16) == 0) ? 1 : 0;
+    const int vec_out = (dlogits && lddl == C && ((uintptr_t)dlogits % 16) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(ce_fused_f_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index,
+                       weights, gamma, (const float*)(loss_out + 1), dlogits, lddl, part, nan_flag, vec_in, vec_out);
+    if (int e = launch_status("ce_fused_f_kernel")) return e;
     return launch_ce_finalize_w(part, nb, loss_out, st);
 }
 extern "C" int dsrl_mse_fused(const float* a, const float* b, int64_t n, float grad_scale, float* da, float* loss_out, int* nan_flag,

@@ -1296,13 +1296,14 @@ class LogitsGrad:
     leaves `target`, `count` (device pointer holder) here and reports no gradient; the stride-8 feature transformer leaves its incoming gradient and
     weights; the ConvTranspose backward then forms d(CE)/d(logits) (+ the transformer's rank-one term) inside its own kernel
     (dsrl_convt2x2_bwd_ce): the 319 MB gradient of the 256x512 step is neither written nor read."""
-    __slots__ = ('y', 'xshape', 'x_ptr', 'armed', 'target', 'ignore_index', 'count', 'ft', 'value', 'value_key', 'weight')
+    __slots__ = ('y', 'xshape', 'x_ptr', 'armed', 'target', 'ignore_index', 'count', 'ft', 'value', 'value_key', 'weight', 'gamma')
 
     def __init__(self):
         self.y = None; self.xshape = None; self.x_ptr = 0; self.armed = False; self.target = None; self.ignore_index = 255; self.count = None; self.ft = None
         self.value = None           # [CE, pixel count, ...] when the producing layer already evaluated the loss (logits_target), and for which
-        self.value_key = None       # (target pointer, ignore_index, NaN flag pointer, class-weight table pointer or 0)
+        self.value_key = None       # (target pointer, ignore_index, NaN flag pointer, class-weight table pointer or 0, focal gamma)
         self.weight = None          # the 256-float class-weight table of a weighted loss (class_weight_table); `count` then holds D = sum n_c w_c
+        self.gamma = 0.0            # > 0: the focal loss (always with a table: all ones when the caller gave no weights)
 
     def usable(self, logits, target):
         """Can the loss leave the gradient to the producer?  logits must be exactly the producer's output buffer."""
@@ -1356,6 +1357,28 @@ def class_weight_table(weights, device, num_classes=None):
     return tab
 
 
+def focal_gamma_value(x):
+    """The focal exponent as a float: any finite number >= 0 (0: the focal factor is off).  ValueError on a bool, on anything that is not a
+    number, on NaN, infinity and negatives.  Touches no device."""
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+        raise ValueError(f'focal_gamma = {x!r}: expected a finite number >= 0')
+    g = float(x)
+    if not math.isfinite(g) or g < 0.0 or g > 3.4028234663852886e38:          # (the kernels take it as fp32)
+        raise ValueError(f'focal_gamma = {x!r}: expected a finite number >= 0')
+    return g
+
+
+def _focal_args(weight, gamma, device, num_classes):
+    """(class-weight table or None, gamma) of a CE call: the focal loss runs on the weighted kernels, so gamma > 0 without weights takes the
+    all-ones table of `num_classes` classes."""
+    gamma = focal_gamma_value(gamma)
+    if weight is not None:
+        weight = class_weight_table(weight, device, num_classes)
+    elif gamma > 0.0:
+        weight = class_weight_table(np.ones(int(num_classes), np.float32), device, num_classes)
+    return weight, gamma
+
+
 _WEIGHT_TABLES_MAX = 32
 _weight_tables = {}             # (fp32 weight bytes, device) -> table
 _weight_tables_made = {}        # id(table) -> (weak reference, number of classes): how a table made here is recognised for as long as it lives
@@ -1366,15 +1389,16 @@ class logits_target:
     """with logits_target(target, ignore_index, flag): ... model(x) ... - tells the layer that produces the logits (HipConvTranspose2d.logits_layer) what
     they will be compared with, so that its forward kernel evaluates nn.CrossEntropyLoss while the output tile is on chip (dsrl_convt2x2_fwd_ce) and
     fused_losses finds the value ready (LogitsGrad.value) instead of reading the logits again.  target: (N,H,W) uint8, contiguous; flag: the int32 NaN
-    flag fused_losses will be given; weight: the class weights fused_losses will be given (None: unweighted).  Outside the block, or when the shape
-    does not qualify, nothing changes."""
+    flag fused_losses will be given; weight: the class weights fused_losses will be given (None: unweighted); focal_gamma: its focal exponent
+    (0: none).  Outside the block, or when the shape does not qualify, nothing changes."""
 
-    def __init__(self, target, ignore_index, flag, weight=None):
+    def __init__(self, target, ignore_index, flag, weight=None, focal_gamma=0.0):
+        focal_gamma = focal_gamma_value(focal_gamma)
         ok = (convt_ce_enabled and target is not None and target.is_cuda and target.dtype == torch.uint8 and target.is_contiguous() and target.dim() == 3
               and flag is not None and flag.dtype == torch.int32)
         if weight is not None and target is not None:
             weight = class_weight_table(weight, target.device)
-        self.new = (target, int(ignore_index), flag, weight) if ok else None
+        self.new = (target, int(ignore_index), flag, weight, focal_gamma) if ok else None
 
     def __enter__(self):
         global _logits_target
@@ -1404,10 +1428,16 @@ class _ConvT2x2(torch.autograd.Function):
         lt = _logits_target if holder is not None else None
         if (lt is not None and tuple(lt[0].shape) == (N, 2 * H, 2 * W) and lt[0].device == x.device
                 and query('dsrl_convt2x2_fwd_ce_supported', x.data_ptr(), y.data_ptr(), N, H, W, Ci, Co)):       # (pointer arguments: not memoised)
-            tgt, ign, flag, wt = lt
+            tgt, ign, flag, wt, gamma = lt
+            if gamma > 0.0:
+                wt = _focal_args(wt, gamma, x.device, Co)[0]
             holder.value = torch.empty(8, device=x.device, dtype=torch.float32)
-            holder.value_key = (tgt.data_ptr(), ign, flag.data_ptr(), 0 if wt is None else wt.data_ptr())
-            if wt is None:
+            holder.value_key = (tgt.data_ptr(), ign, flag.data_ptr(), 0 if wt is None else wt.data_ptr(), gamma)
+            if gamma > 0.0:
+                ws = _ws(cquery('dsrl_convt2x2_fwd_ce_f_workspace_bytes', N, H, W), x)
+                call('dsrl_convt2x2_fwd_ce_f', x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co,
+                     tgt.data_ptr(), ign, wt.data_ptr(), gamma, holder.value.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+            elif wt is None:
                 ws = _ws(cquery('dsrl_convt2x2_fwd_ce_workspace_bytes', N, H, W), x)
                 call('dsrl_convt2x2_fwd_ce', x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co,
                      tgt.data_ptr(), ign, holder.value.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
@@ -1434,8 +1464,8 @@ class _ConvT2x2(torch.autograd.Function):
         h = ctx.holder
         hand = None
         if h is not None and h.armed:           # the loss left d(CE)/d(logits) to this layer: take it over, and disarm the holder whatever happens next
-            hand = (h.y, h.target, int(h.ignore_index), h.count, h.ft, h.weight)
-            h.armed = False; h.ft = None; h.target = None; h.count = None; h.y = None; h.value = None; h.weight = None
+            hand = (h.y, h.target, int(h.ignore_index), h.count, h.ft, h.weight, h.gamma)
+            h.armed = False; h.ft = None; h.target = None; h.count = None; h.y = None; h.value = None; h.weight = None; h.gamma = 0.0
         fused = dy is None and hand is not None
         if dy is None and not fused:
             raise DsrlHipError('conv_transpose2d_k2s2: backward reached without a gradient for the output')
@@ -1445,11 +1475,15 @@ class _ConvT2x2(torch.autograd.Function):
             # another consumer of the logits sent a gradient too (it is not the loss's: fused_losses returned none): d(CE)/d(logits) and the
             # transformer's term are written as the unfused step writes them (dsrl_ce_fused, dsrl_pointwise_strided_bwd(accumulate = 1)), dy is
             # added as autograd would add it, and the plain backward below takes the sum
-            y, target, ign, _, ft, wt = hand
+            y, target, ign, _, ft, wt, gamma = hand
             P = N * 4 * H * W
             dl = new_cl((N, Co, 2 * H, 2 * W), x)
             scal = torch.empty(8, device=x.device, dtype=torch.float32)
-            if wt is None:
+            if gamma > 0.0:
+                wsc = _ws(cquery('dsrl_ce_fused_f_workspace_bytes', P), x)
+                call('dsrl_ce_fused_f', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, wt.data_ptr(), gamma, dl.data_ptr(), Co, scal.data_ptr(), None,
+                     wsc.data_ptr(), wsc.numel(), _stream())
+            elif wt is None:
                 wsc = _ws(cquery('dsrl_ce_fused_workspace_bytes', P), x)
                 call('dsrl_ce_fused', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, dl.data_ptr(), Co, scal.data_ptr(), None, wsc.data_ptr(), wsc.numel(), _stream())
             else:
@@ -1470,9 +1504,13 @@ class _ConvT2x2(torch.autograd.Function):
         db = (bsink if bsink is not None else torch.empty(Co, device=x.device, dtype=torch.float32)) if ctx.has_bias else None
         ws = _ws(cquery('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, Ci, Co), x)
         if fused:
-            y, target, ign, count, ft, wt = hand
+            y, target, ign, count, ft, wt, gamma = hand
             ft_g, ft_w, ft_s = ft if ft is not None else (None, None, 0)
-            if wt is None:
+            if gamma > 0.0:
+                call('dsrl_convt2x2_bwd_ce_f', x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, wt.data_ptr(), gamma, count.data_ptr() + 4,
+                     None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
+                     dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
+            elif wt is None:
                 call('dsrl_convt2x2_bwd_ce', x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, count.data_ptr() + 4,
                      None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
                      dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
@@ -1587,7 +1625,7 @@ def pointwise_strided(x, weight, stride, out_slot=None):
 # ------------------------------------------------------------------------------------------------ losses
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, ignore_index, weight=None):
+    def forward(ctx, logits, target, ignore_index, weight=None, gamma=0.0):
         logits, ld = pm(logits)
         _need_gpu(target)
         if target.dtype != torch.uint8:
@@ -1598,7 +1636,11 @@ class _CrossEntropy(torch.autograd.Function):
         if target.numel() != P:
             raise DsrlHipError(f'cross_entropy: target has {target.numel()} pixels, logits {P}')
         out = torch.empty(2, device=logits.device, dtype=torch.float32)
-        if weight is None:
+        if gamma > 0.0:
+            ws = _ws(cquery('dsrl_ce_f_workspace_bytes', P), logits)
+            call('dsrl_ce_fwd_f', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(), gamma, out.data_ptr(),
+                 ws.data_ptr(), ws.numel(), _stream())
+        elif weight is None:
             ws = _ws(cquery('dsrl_ce_workspace_bytes', P), logits)
             call('dsrl_ce_fwd', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
         else:
@@ -1608,6 +1650,7 @@ class _CrossEntropy(torch.autograd.Function):
         ctx.save_for_backward(logits, target, out)
         ctx.ignore_index = int(ignore_index)
         ctx.weight = weight
+        ctx.gamma = gamma
         return out[0].clone()
 
     @staticmethod
@@ -1617,21 +1660,23 @@ class _CrossEntropy(torch.autograd.Function):
         N, Cc, H, W = logits.shape
         g = g.reshape(1).contiguous().float()
         dl = new_cl((N, Cc, H, W), logits)
-        if ctx.weight is None:
+        if ctx.gamma > 0.0:
+            call('dsrl_ce_bwd_f', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, ctx.weight.data_ptr(), ctx.gamma,
+                 out.data_ptr(), g.data_ptr(), dl.data_ptr(), Cc, _stream())
+        elif ctx.weight is None:
             call('dsrl_ce_bwd', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, out.data_ptr(), g.data_ptr(),
                  dl.data_ptr(), Cc, _stream())
         else:
             call('dsrl_ce_bwd_w', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, ctx.weight.data_ptr(), out.data_ptr(),
                  g.data_ptr(), dl.data_ptr(), Cc, _stream())
-        return dl, None, None, None
+        return dl, None, None, None, None
 
 
-def cross_entropy(logits, target, ignore_index=255, weight=None):
+def cross_entropy(logits, target, ignore_index=255, weight=None, focal_gamma=0.0):
     """nn.CrossEntropyLoss(weight, ignore_index) with mean reduction; target (N,H,W) uint8/long; weight: None, one number per class, or a
-    class_weight_table."""
-    if weight is not None:
-        weight = class_weight_table(weight, logits.device, logits.shape[1])
-    return _CrossEntropy.apply(logits, target, ignore_index, weight)
+    class_weight_table.  focal_gamma > 0: the focal loss sum w[t] (1 - p_t)^gamma (-log p_t) / sum w[t]; 0 changes nothing."""
+    weight, focal_gamma = _focal_args(weight, focal_gamma, logits.device, logits.shape[1])
+    return _CrossEntropy.apply(logits, target, ignore_index, weight, focal_gamma)
 
 
 class _MSE(torch.autograd.Function):
@@ -1668,7 +1713,7 @@ class _FusedLosses(torch.autograd.Function):
     its incoming gradient is 1 (TrainStep calls vals[3].backward()); the stored gradients are returned as they are."""
 
     @staticmethod
-    def forward(ctx, sssr, sisr, ft1, ft2, target, org, ignore_index, w1, w2, stage, flag, k, weight=None):
+    def forward(ctx, sssr, sisr, ft1, ft2, target, org, ignore_index, w1, w2, stage, flag, k, weight=None, gamma=0.0):
         want = bool(ctx.needs_input_grad[0])          # forward-only (validation, no_grad): no gradient buffers are written
         logits, ld = pm(sssr)
         _need_gpu(target)
@@ -1688,8 +1733,12 @@ class _FusedLosses(torch.autograd.Function):
             lg = None
         dl = new_cl((N, Cc, H, W), logits) if (want and lg is None) else None      # lg: the producer of the logits forms this gradient in its own backward
         if lg is not None and lg.value is not None and lg.value_key == (target.data_ptr(), int(ignore_index), flag.data_ptr(),
-                                                                        0 if weight is None else weight.data_ptr()):
+                                                                        0 if weight is None else weight.data_ptr(), gamma):
             scal = lg.value                                             # the producer's forward kernel evaluated the loss (logits_target)
+        elif gamma > 0.0:
+            ws = _ws(cquery('dsrl_ce_fused_f_workspace_bytes', P), logits)
+            call('dsrl_ce_fused_f', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(), gamma,
+                 None if dl is None else dl.data_ptr(), Cc, scal.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
         elif weight is None:
             ws = _ws(cquery('dsrl_ce_fused_workspace_bytes', P), logits)
             call('dsrl_ce_fused', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), None if dl is None else dl.data_ptr(), Cc,
@@ -1726,7 +1775,7 @@ class _FusedLosses(torch.autograd.Function):
             ctx.fa = (ft1, ft2, saved, k, fa_out)
         call('dsrl_loss_mix', scal.data_ptr(), mse_ptr, fa_ptr, float(w1), float(w2), flag.data_ptr(), vals.data_ptr(), st)
         if lg is not None:
-            lg.target = target; lg.ignore_index = int(ignore_index); lg.count = scal; lg.ft = None; lg.weight = weight; lg.armed = True
+            lg.target = target; lg.ignore_index = int(ignore_index); lg.count = scal; lg.ft = None; lg.weight = weight; lg.gamma = gamma; lg.armed = True
         ctx.lg = lg
         ctx.grads = (dl, da)
         ctx.w2 = float(w2)
@@ -1766,7 +1815,7 @@ class _FusedLosses(torch.autograd.Function):
             if slot is not None and buf is not None and not slot.closed and slot.buf is None:
                 slot.buf = buf
                 out[i] = None
-        return out[0], out[1], d1, d2, None, None, None, None, None, None, None, None, None
+        return out[0], out[1], d1, d2, None, None, None, None, None, None, None, None, None, None
 
 
 _fused_losses_root_checked = False
@@ -1798,16 +1847,17 @@ def fused_losses_backward(vals):
     torch.autograd.backward([vals], [e3])
 
 
-def fused_losses(outs, target, input_org, ignore_index, w1, w2, stage, flag, subsample_factor=8, weight=None):
+def fused_losses(outs, target, input_org, ignore_index, w1, w2, stage, flag, subsample_factor=8, weight=None, focal_gamma=0.0):
     """-> 5-float device tensor [CE, w1*MSE, w2*FA, total, NaN flag]; `outs` = DSRL.forward's 4-tuple.  vals[3].backward() is the only
     supported backward (the function is the root of the pass); `flag` is the int32 NaN flag the fused kernels OR into.  weight: per-class CE
-    weights (None, one number per class, or a class_weight_table): nn.CrossEntropyLoss(weight=)."""
+    weights (None, one number per class, or a class_weight_table): nn.CrossEntropyLoss(weight=).  focal_gamma > 0 makes the CE term the focal loss
+    (as cross_entropy); 0 changes nothing."""
     sssr, sisr, ft1, ft2 = outs
-    if weight is not None:
-        weight = class_weight_table(weight, sssr.device, sssr.shape[1])
+    weight, focal_gamma = _focal_args(weight, focal_gamma, sssr.device, sssr.shape[1])
     dummy = _const1(0.0, sssr.device)            # stands in for the outputs a lower stage does not have (a cached constant: no fill launch per step)
     return _FusedLosses.apply(sssr, sisr if stage > 1 else dummy, ft1 if stage > 2 else dummy, ft2 if stage > 2 else dummy, target,
-                              input_org if stage > 1 else dummy, int(ignore_index), float(w1), float(w2), int(stage), flag, int(subsample_factor), weight)
+                              input_org if stage > 1 else dummy, int(ignore_index), float(w1), float(w2), int(stage), flag, int(subsample_factor), weight,
+                              focal_gamma)
 
 
 _RED = {'mean': 0, 'sum': 1, 'none': 2}

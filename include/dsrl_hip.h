@@ -455,6 +455,33 @@ int dsrl_convt2x2_bwd_ce_w(const float* x, const float* w, const float* logits, 
 int dsrl_class_histogram(const uint8_t* labels, int64_t P, const uint8_t* lut /*nullable, [256]*/, unsigned long long* counts /*[256]*/,
                          dsrl_stream_t stream);
 
+/* Focal cross entropy (Lin et al.): the weighted loss above with one more per-pixel factor.  For a live pixel with p = softmax(v)[t], q = 1 - p,
+ * nll = -log p:
+ *     term_i = w[t_i] * q^gamma * nll,   loss = (sum_i term_i) / D,   D as above (the same pre-pass, the same bits)
+ *     dl_ic  = sc_i * e_ic / s_i - (c == t_i ? sc_i : 0),  sc_i = (w[t_i] * mod_i) * (1 / D),  mod = q^(gamma-1) * (q + gamma * p * nll)
+ * with q = (sum_{c != t} e_c) / s (never 1 - p), nll = (m - v_t) + log s, and the limits q == 0 -> term = 0, mod = 0; p == 0 -> p * nll = 0.
+ * `gamma` must be finite and >= 0, else DSRL_E_BADARG and nothing is launched; gamma == 0 runs the _w entry point itself.  Each _f entry point is
+ * its _w sibling with `float gamma` after `weights` (all-ones weights for an unweighted focal loss): same contracts, flags and workspaces (the
+ * _f size queries are those of the _w siblings), and dsrl_convt2x2_bwd_ce_f is bit-identical to
+ * dsrl_ce_fused_f -> dsrl_pointwise_strided_bwd(accumulate = 1) -> dsrl_convt2x2_bwd. */
+size_t dsrl_ce_f_workspace_bytes(int64_t P);
+int dsrl_ce_fwd_f(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights /*[256]*/, float gamma,
+                  float* loss_out /*[2]*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+int dsrl_ce_bwd_f(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights /*[256]*/, float gamma,
+                  const float* loss_out, const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream);
+size_t dsrl_ce_fused_f_workspace_bytes(int64_t P);
+int dsrl_ce_fused_f(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights /*[256]*/, float gamma,
+                    float* dlogits /*nullable*/, int lddl, float* loss_out /*[2]*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes,
+                    dsrl_stream_t stream);
+size_t dsrl_convt2x2_fwd_ce_f_workspace_bytes(int N, int H, int W);
+int dsrl_convt2x2_fwd_ce_f(const float* x, const float* w, const float* bias /*nullable*/, float* y, int N, int H, int W, int Cin, int Cout,
+                           const uint8_t* target, int ignore_index, const float* weights /*[256]*/, float gamma, float* loss_out,
+                           int* nan_flag /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+int dsrl_convt2x2_bwd_ce_f(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* weights /*[256]*/,
+                           float gamma, const float* ce_wsum /*D: loss_out + 1*/, const float* ft_g /*nullable*/, const float* ft_w /*nullable*/,
+                           int ft_stride, float* dx, float* dw, float* dbias /*nullable*/, int N, int H, int W, int Cin, int Cout, void* ws,
+                           size_t ws_bytes, dsrl_stream_t stream);
+
 /* FALoss (models/losses/FALoss.py:8-34). fm1/fm2 are (B,C,H,W) with element strides (sb,sc,sh,sw).
  * reduction: 0 mean, 1 sum, 2 none (out has B*C*n*n floats, n = (W/k)^2).
  * `saved` (>= dsrl_fa_saved_floats) carries S1,S2,sigma,u1,v1 to the backward. */
