@@ -143,6 +143,14 @@ PROTOTYPES = {
     'dsrl_convt2x2_fwd_ce_f_workspace_bytes': (sz, [i32, i32, i32]),
     'dsrl_convt2x2_fwd_ce_f': (i32, [fp, fp, fp, fp, i32, i32, i32, i32, i32, fp, i32, fp, f32, fp, fp, fp, sz, stream_t]),
     'dsrl_convt2x2_bwd_ce_f': (i32, [fp, fp, fp, fp, i32, fp, f32, fp, fp, fp, i32, fp, fp, fp, i32, i32, i32, i32, i32, fp, sz, stream_t]),
+    'dsrl_ce_s_workspace_bytes': (sz, [i64]),
+    'dsrl_ce_fwd_s': (i32, [fp, i32, fp, i64, i32, i32, fp, f32, fp, fp, sz, stream_t]),
+    'dsrl_ce_bwd_s': (i32, [fp, i32, fp, i64, i32, i32, fp, f32, fp, fp, fp, i32, stream_t]),
+    'dsrl_ce_fused_s_workspace_bytes': (sz, [i64]),
+    'dsrl_ce_fused_s': (i32, [fp, i32, fp, i64, i32, i32, fp, f32, fp, i32, fp, fp, fp, sz, stream_t]),
+    'dsrl_convt2x2_fwd_ce_s_workspace_bytes': (sz, [i32, i32, i32]),
+    'dsrl_convt2x2_fwd_ce_s': (i32, [fp, fp, fp, fp, i32, i32, i32, i32, i32, fp, i32, fp, f32, fp, fp, fp, sz, stream_t]),
+    'dsrl_convt2x2_bwd_ce_s': (i32, [fp, fp, fp, fp, i32, fp, f32, fp, fp, fp, i32, fp, fp, fp, i32, i32, i32, i32, i32, fp, sz, stream_t]),
     'dsrl_loss_mix': (i32, [fp, fp, fp, f32, f32, fp, fp, stream_t]),
     'dsrl_fa_saved_floats': (sz, [i32] * 5),
     'dsrl_fa_workspace_bytes': (sz, [i32] * 5),

@@ -84,13 +84,20 @@ class TrainStep:
     than one rank each rank normalises by the weight sum of its own batch and the gradients are averaged, as DDP with a weighted loss does.
 
     `focal_gamma` (a finite number >= 0; 0: off): the CE term becomes the focal loss sum w[t] (1 - p_t)^gamma (-log p_t) / sum w[t] on the same paths,
-    `do_train=False` included (early stopping compares the two).  It runs on the weighted kernels: without `class_weights` the weights are all ones."""
+    `do_train=False` included (early stopping compares the two).  It runs on the weighted kernels: without `class_weights` the weights are all ones.
+
+    `label_smoothing` (a number in [0, 1]; 0: off): nn.CrossEntropyLoss(label_smoothing=) for the CE term on the same paths, training and
+    `do_train=False` alike, also on the weighted kernels.  Together with `focal_gamma` > 0: ValueError.  The value is fixed for the life of the
+    step, as `focal_gamma` is, so every graph this step captures was captured with it."""
 
     GRAPH_WARMUP = HF.GRAPH_WARMUP          # eager iterations per batch shape before the capture
 
-    def __init__(self, model, flat, stage, w1, w2, ignore_index, graph=None, class_weights=None, focal_gamma=0.0):
+    def __init__(self, model, flat, stage, w1, w2, ignore_index, graph=None, class_weights=None, focal_gamma=0.0, label_smoothing=0.0):
         self.model, self.flat, self.stage, self.w1, self.w2, self.ignore = model, flat, stage, w1, w2, ignore_index
         self.focal_gamma = HF.focal_gamma_value(focal_gamma)                                                          # ValueError on a bad gamma
+        self.label_smoothing = HF.label_smoothing_value(label_smoothing)                                              # ValueError on a bad eps
+        if self.focal_gamma > 0.0 and self.label_smoothing > 0.0:
+            raise ValueError(f'label_smoothing = {label_smoothing!r} together with focal_gamma = {focal_gamma!r}: the combination is not defined')
         self.class_weight = None if class_weights is None else HF.class_weight_table(class_weights, flat.device)     # ValueError on bad weights
         self.fa = FALoss()
         dev = flat.device
@@ -120,7 +127,7 @@ class TrainStep:
 
     def losses(self, outs, input_org, target):
         SSSR, SISR, SSSR_ft, SISR_ft = outs
-        ce = HF.cross_entropy(SSSR, target, self.ignore, self.class_weight, self.focal_gamma)      # train_or_resume.py:435
+        ce = HF.cross_entropy(SSSR, target, self.ignore, self.class_weight, self.focal_gamma, self.label_smoothing)      # train_or_resume.py:435
         ms = self.w1 * HF.mse_loss(SISR, input_org) if self.stage > 1 else self.zero       # :436
         fa = self.w2 * self.fa(SSSR_ft, SISR_ft) if self.stage > 2 else self.zero          # :437
         return ce, ms, fa, ce + ms + fa                                                    # :438
@@ -147,14 +154,14 @@ class TrainStep:
                 if self.fused_losses and do_train:
                     # the layer that produces the logits evaluates the CE value in its own forward kernel (HF.logits_target), :435
                     with HF.logits_target(target if target.dtype == t.uint8 and target.is_contiguous() else None, self.ignore, self.flag,
-                                          self.class_weight, self.focal_gamma):
+                                          self.class_weight, self.focal_gamma, self.label_smoothing):
                         outs = self.model(input_image)                                     # :420
                 else:
                     outs = self.model(input_image)                                         # :420
                 if self.fused_losses:
                     # CE + MSE + FA, their gradients, the NaN asserts (:426-433) and the loss mix (:435-438) in one launch set
                     vals = HF.fused_losses(outs, target, input_org, self.ignore, self.w1, self.w2, self.stage, self.flag, self.fa.subsample_factor,
-                                           self.class_weight, self.focal_gamma)
+                                           self.class_weight, self.focal_gamma, self.label_smoothing)
                     total = vals[3]
                 else:
                     HF.nan_check_(self.flag, *[o for o in outs if o.is_cuda])              # the four NaN asserts, :426-433
@@ -229,7 +236,8 @@ class TrainStep:
             self._hyper_vals = vals
 
     def _graph_key(self, input_image, input_org, target):
-        return (tuple(input_image.shape), tuple(input_org.shape), tuple(target.shape), HF.get_conv_precision(), HF.overlap_wgrad)
+        return (tuple(input_image.shape), tuple(input_org.shape), tuple(target.shape), HF.get_conv_precision(), HF.overlap_wgrad,
+                self.focal_gamma, self.label_smoothing)
 
     def _capture(self, key, input_image, input_org, target, hp):
         """-> the captured step, or None: a capture that fails (a runtime that refuses something inside it) must not end the training run.  This
@@ -417,6 +425,16 @@ def check_focal_gamma(dataset):
     return 0.0 if g is None else HF.focal_gamma_value(g)
 
 
+def check_label_smoothing(dataset):
+    """dataset['label_smoothing']: absent, None or 0 -> 0.0 (off); a number in (0, 1] -> that float; ValueError otherwise, and on a value > 0
+    together with dataset['focal_gamma'] > 0 (the combination has no definition).  Touches no device."""
+    e = dataset.get('label_smoothing')
+    e = 0.0 if e is None else HF.label_smoothing_value(e)
+    if e > 0.0 and check_focal_gamma(dataset) > 0.0:
+        raise ValueError(f"label_smoothing = {e!r} together with focal_gamma = {dataset.get('focal_gamma')!r}: the combination is not defined")
+    return e
+
+
 def train_or_resume(is_resuming_training, device, distributed, mixed_precision, disable_cudnn_benchmark, num_workers, dataset, val_interval,
                     checkpoint_interval, checkpoint_history, init_weights, batch_size, epochs, learning_rate, end_learning_rate, momentum,
                     weights_decay, poly_power, stage, w1, w2, freeze_batch_norm, experiment_id, description, early_stopping, dry_run=False, **other_args):
@@ -428,6 +446,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     conv_arith = settings.MIXED_PRECISION_TO_CONV_ARITHMETIC[mixed_precision]
     class_weights = check_class_weights(dataset, dataset['settings'].NUM_CLASSES)
     focal_gamma = check_focal_gamma(dataset)
+    label_smoothing = check_label_smoothing(dataset)
     input_size = other_args.get('model_input_size', settings.MODEL_INPUT_SIZE)
     if distributed:
         t.manual_seed(settings.RANDOM_SEED)                                                # identical init on all ranks, :31
@@ -482,7 +501,8 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
         from ..models.transforms import DeviceBatchPreparation
         lut = DeviceBatchPreparation(ds.LABEL_MAPPING_DICT, ds.MEAN, ds.STD, input_size, ds.IGNORE_CLASS_LABEL).lut_host
         class_weights = enet_weights(class_counts(cache_dir_of(dataset), 'train', lut, device_obj)[:ds.NUM_CLASSES])
-    step = TrainStep(model, flat, stage, w1, w2, ds.IGNORE_CLASS_LABEL, class_weights=class_weights, focal_gamma=focal_gamma)
+    step = TrainStep(model, flat, stage, w1, w2, ds.IGNORE_CLASS_LABEL, class_weights=class_weights, focal_gamma=focal_gamma,
+                     label_smoothing=label_smoothing)
     train_loader = factory('train', batch_size, device_obj, rank, world)
     val_loader = factory('val', batch_size, device_obj, rank, world) if is_master_rank else None
 

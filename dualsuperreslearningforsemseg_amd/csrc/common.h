@@ -25,6 +25,10 @@ int launch_status(const char* what);
 #define DSRL_FOCAL_GAMMA(gamma, what) \
     DSRL_REQUIRE((gamma) >= 0.f && (gamma) <= 3.402823466e+38f, DSRL_E_BADARG, what ": gamma = %g is not a finite number >= 0", (double)(gamma))
 
+// the label-smoothing entry points (dsrl_*_s) check their eps before anything else: 0 <= eps <= 1 (a NaN fails the comparison)
+#define DSRL_LABEL_SMOOTHING(eps, what) \
+    DSRL_REQUIRE((eps) >= 0.f && (eps) <= 1.f, DSRL_E_BADARG, what ": eps = %g is not a number in [0, 1]", (double)(eps))
+
 // Binds the calling thread to the device that owns `stream` (autograd runs backward on its own thread).
 int bind_stream_device(hipStream_t s);
 
@@ -35,7 +39,7 @@ int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float*
 int launch_convt_bwd_dma_ce(const float* x, const float* w, const float* logits, float* dx, float* part, int N, int H, int W, int nblocks,
                             const unsigned char* target, int ignore_index, const float* count, const float* ft_g, const float* ft_w, int ft_s,
                             const float* wtab /*null: unweighted; else the 256-float class-weight table and `count` points to D*/,
-                            float gamma /*> 0 (with wtab): focal*/, hipStream_t st);
+                            float gamma /*> 0 (with wtab): focal*/, float eps /*> 0 (with wtab, gamma == 0): label smoothing*/, hipStream_t st);
 
 // The one way the library reads a DSRL_* environment switch (table: DESIGN.md §9).  Read at every call, never cached: tests change switches
 // between calls inside one process.  knob_str: for the one switch whose value is a path (DSRL_PROF_DUMP).
@@ -113,6 +117,43 @@ __device__ __forceinline__ void focal_pixel(float m, float vt, float et, float s
     fl = zero ? 0.f : qg * nll;
     mod = zero ? 0.f : qg1 * (q + gamma * pn);
 }
+
+// ---------------------------------------------------------------- label-smoothed cross entropy, the arithmetic of one live pixel
+// With nl_c = (m - v_c) + log s, W = sum_{c < C} w_c and D = sum_i w[t_i]:
+//     term_i = (1 - eps) w[t] nl_t + (eps / C) sum_{c < C, w_c > 0} w_c nl_c
+//     d loss / d v_c = ((1 - eps) w[t] (p_c - [c == t]) + (eps / C) (p_c W - w_c)) / D = e_c inv - sub_c,
+//     inv = (((1 - eps) w[t] + (eps / C) W) scale) / s,   sub_c = (([c == t] ? (1 - eps) w[t] : 0) + (eps / C) w_c) scale,   scale = 1 / D
+// sub_c of a class that is not the target is ((eps / C) w_c) scale (0 + x is x) and the same for every pixel: smooth_sub, which the gradient kernels
+// keep as a C-entry table in LDS, made once per block; the target's own sub_t = ((1 - eps) w[t] + (eps / C) w[t]) scale comes from smooth_pixel.
+// The caller passes the pixel's C raw logits `v`, the weights `w` (the table: w[t] is read at the label byte, so a label >= C has weight 0),
+// m = max_c v_c, s = sum_c exp_nonpos(v_c - m) (c ascending) and W (summed once per block, c ascending); it gets the value term (VAL builds only:
+// a backward needs no log), sub_t and inv.  smooth_grad is one element of the gradient row.  Each nl_c is fp32; the products with the
+// weights and their sum over the classes are double, as the accumulation over pixels is in every CE kernel (w_c nl_c of a logit near -3e38 times a
+// weight above 1 leaves fp32 while the loss does not).  The accumulation over pixels and 1 / D stay with the kernel.  Every smoothing kernel
+// (losses.hip, spatial.hip, convt_dma.hip) goes through these functions, so that the fused and the unfused paths round alike (the library is
+// built with -ffp-contract=off).
+//   nl = (m - v) + log s, never m + log s - v: m - v is exact or rounds at its own size, the other order rounds at ulp(m) in every one of C terms.
+//   The sum over the classes runs in ascending c.  A class of weight 0 adds nothing to it, even where nl_c is +inf (torch forms 0 * inf = NaN there);
+//   with a positive weight such a class makes the value +inf, as it is.  The target's own term is the plain product, as in the weighted kernels.
+template <bool VAL>
+__device__ __forceinline__ void smooth_pixel(const float* v, const float* w, int C, int tg, float m, float s, float eps, float Wsum, float scale,
+                                             double& val, float& sub_t, float& inv) {
+    const float epsC = eps / (float)C;
+    const float omw = (1.f - eps) * w[tg];
+    inv = ((omw + epsC * Wsum) * scale) / s;
+    sub_t = (omw + epsC * w[tg]) * scale;
+    if (VAL) {
+        const float ls = logf(s);
+        double sm = 0.0;
+        for (int c = 0; c < C; ++c) { const float wc = w[c]; const float nl = (m - v[c]) + ls; sm += wc > 0.f ? (double)wc * (double)nl : 0.0; }
+        const float nlt = (m - v[min(tg, C - 1)]) + ls;
+        val = (double)omw * (double)nlt + (double)epsC * sm;
+    } else {
+        val = 0.0;
+    }
+}
+__device__ __forceinline__ float smooth_sub(float eps, int C, float wc, float scale) { return ((eps / (float)C) * wc) * scale; }
+__device__ __forceinline__ float smooth_grad(float e, float inv, bool hit, float sub_t, float sub_c) { return e * inv - (hit ? sub_t : sub_c); }
 
 // ---------------------------------------------------------------- wave / block reductions
 __device__ inline float wave_sum(float v) {

@@ -40,6 +40,7 @@ struct ConvtCeArgs {
     int ignore_index, ft_s, ft_shift, Hf, Wf;     // ft_shift = log2(ft_s) when ft_s is a power of two, else -1
     const float* wtab;              // CW: the 256-float class-weight table, and `count` points to D
     float gamma;                    // FL: the focal exponent (> 0)
+    float eps;                      // SM: the label smoothing (0 < eps <= 1)
 };
 
 // CW = true (dsrl_convt2x2_bwd_ce_w): nn.CrossEntropyLoss(weight=).  ce.count points to D = sum n_c w_c and the only change is in transform(): the
@@ -49,12 +50,16 @@ struct ConvtCeArgs {
 // FL = true (dsrl_convt2x2_bwd_ce_f): focal cross entropy.  transform() also forms so = sum_{c != t} e_c beside s and reads v_t once more from the
 // stage (the raw logits are still there), focal_pixel (common.h) gives mod from them, and sc = (w[t] * mod) * (1 / D) as in ce_fused_body<true, true>:
 // the table in LDS holds the raw weights here, so that the product rounds as it does there.  Everything after sc is the weighted code.
-template <int CI, int CO, bool CE, bool TW = false, bool CW = false, bool FL = false>
+// SM = true (dsrl_convt2x2_bwd_ce_s): label-smoothed cross entropy.  The table in LDS holds the raw weights (its first CO entries are the per-class w_c
+// of the smoothing term), W = sum_c w_c is summed from it once per block, a second table holds smooth_sub of every class, and the row is smooth_pixel /
+// smooth_grad (common.h) on the e_c in registers, as ce_fused_body<true, false, true> forms it from its tile.  A backward needs no value, hence no log.
+template <int CI, int CO, bool CE, bool TW = false, bool CW = false, bool FL = false, bool SM = false>
 __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ dy,
                                                                  float* __restrict__ dx, float* __restrict__ part, int N, int H, int W,
                                                                  int nseg_per_row, int nseg, ConvtCeArgs ce) {
     static_assert(CE || !CW, "class weights belong to the CE build");
     static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
+    static_assert(!SM || (CW && !FL), "label smoothing runs on the weighted machinery and has no focal form");
     constexpr int TP = 128, COLS = 4 * CO, NK = COLS / 2, NJ = (COLS + 31) / 32, NOUT = CI * COLS;
     constexpr int XB = TP * CI * 4, XP = (XB + 1023) / 1024;               // bytes / 1 KB pieces of an x segment
     constexpr int GB = 2 * TP * CO * 4, GP = GB / 1024;                    // of one dy row segment
@@ -113,11 +118,14 @@ __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(con
         if (tid < 32) ftw_s[tid] = (ce.ft_g && tid < CO) ? ce.ft_w[tid] : 0.f;          // visible after the first barrier below
     }
     __shared__ float wt_s[CW ? 256 : 1];
+    __shared__ float sub_s[SM ? 32 : 1];                                   // SM: ((eps / C) w_c) scale of every class, published with wt_s
+    if (SM && tid < 32) sub_s[tid] = tid < CO ? smooth_sub(ce.eps, CO, ce.wtab[tid], scale) : 0.f;
     if (CW) {
-        if (tid < 256) wt_s[tid] = FL ? ce.wtab[tid] : ce.wtab[tid] * scale;   // sc of a pixel with label tid (FL: its weight, sc needs the pixel's mod)
+        if (tid < 256) wt_s[tid] = (FL || SM) ? ce.wtab[tid] : ce.wtab[tid] * scale;   // sc of a pixel with label tid (FL, SM: its weight; sc is formed per pixel)
         // block_barrier() is a bare s_barrier: it does not wait for this wave's ds_write, so drain the LDS counter before the barrier that publishes the table
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
+    float Wsum = 0.f;                                                      // SM: sum_c w_c
     auto transform = [&](int seg, int slot) {                              // TW: wave wq of the tw waves takes 128 output pixels, two per lane; else every wave 64
         const int r = TW ? wq >> 1 : (is_dw ? 1 : 0);                       // output row 2h + r of the segment
         // the transformer's gradient g of this lane's pixels, fetched FIRST: the softmax arithmetic covers its latency (fetched where it is used it
@@ -165,7 +173,12 @@ __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(con
             // roundings of ce_fused_kernel and pointwise_bwd_kernel.  Everything stays in registers between the 19 reads and the 19 writes: a
             // read-modify-write of the target word in LDS instead of the 19 selects measured +11 us
             const bool live = tg != ce.ignore_index;
-            if (FL) {
+            if (SM) {
+                double val; float sub_t, inv;
+                smooth_pixel<false>(v, wt_s, CO, tg, m, s, ce.eps, Wsum, scale, val, sub_t, inv);
+#pragma unroll
+                for (int c = 0; c < CO; ++c) e[c] = live ? smooth_grad(e[c], inv, c == tg, sub_t, sub_s[c]) : 0.f;
+            } else if (FL) {
                 const float vt = v[min(live ? tg : 0, CO - 1)];              // as ce_fused_body reads it; e_t = exp_nonpos(vt - m) has the bits of e[t]
                 float fl, mod;
                 focal_pixel(m, vt, exp_nonpos(vt - m), s, so, ce.gamma, fl, mod);
@@ -230,6 +243,10 @@ __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(con
     if (CE) {
         if (is_dw) s_waitcnt_vm<0>();
         block_barrier();
+        if (SM) {                                                          // the table is published: W, once per block, c ascending
+#pragma unroll
+            for (int c = 0; c < CO; ++c) Wsum += wt_s[c];
+        }
         if ((is_tw || !TW) && seg < nseg) transform(seg, 0);
     }
     if (is_dw && seg + grid < nseg) issue(seg + grid, 1);
@@ -356,18 +373,18 @@ bool convt_bwd_dma_supported(const void* x, const void* dy, int W, int Cin, int 
 }
 int convt_bwd_dma_blocks(long long nseg, int cap) { return (int)std::min<long long>(std::min(cap, kNumCU), nseg); }
 
-template <bool CE, bool TW, bool CW = false, bool FL = false>
+template <bool CE, bool TW, bool CW = false, bool FL = false, bool SM = false>
 static int launch_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, const ConvtCeArgs& ce, hipStream_t st) {
     constexpr int CI = 19, CO = 19;
     constexpr int kLds = 3 * ((128 * CI * 4 + 1023) / 1024 + 2 * (2 * 128 * CO * 4 / 1024) + (CE ? 2 : 0)) * 1024;
-    static_assert(kLds + (CW ? 1024 : 0) + 128 <= 160 * 1024, "the ring, the transformer's weights and the class-weight table in LDS");
-    static const hipError_t attr = hipFuncSetAttribute((const void*)convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+    static_assert(kLds + (CW ? 1024 : 0) + (SM ? 128 : 0) + 128 <= 160 * 1024, "the ring, the transformer's weights and the class-weight tables in LDS");
+    static const hipError_t attr = hipFuncSetAttribute((const void*)convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     if (attr != hipSuccess) { set_error("convt2x2_bwd_dma_kernel: %d bytes of LDS refused (%s)", kLds, hipGetErrorString(attr)); return DSRL_E_LAUNCH; }
     const int nseg_per_row = W / 128;
     const long long nseg = (long long)N * H * nseg_per_row;
     if ((long long)N * 4 * H * W * CO * 4 >= (1ll << 32)) { set_error("convt2x2_bwd_dma_kernel: output gradient of 4 GB or more"); return DSRL_E_UNSUPPORTED; }
     if (nseg >= (1ll << 31) || nblocks < 1 || nblocks > nseg) { set_error("convt2x2_bwd_dma_kernel: %lld segments, %d blocks", nseg, nblocks); return DSRL_E_BADARG; }
-    hipLaunchKernelGGL((convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL>), dim3(nblocks), dim3(TW ? 768 : 512), kLds, st, x, w, dy, dx, part, N, H, W, nseg_per_row, (int)nseg, ce);
+    hipLaunchKernelGGL((convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM>), dim3(nblocks), dim3(TW ? 768 : 512), kLds, st, x, w, dy, dx, part, N, H, W, nseg_per_row, (int)nseg, ce);
     return launch_status("convt2x2_bwd_dma_kernel");
 }
 int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, hipStream_t st) {
@@ -375,16 +392,18 @@ int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float*
 }
 int launch_convt_bwd_dma_ce(const float* x, const float* w, const float* logits, float* dx, float* part, int N, int H, int W, int nblocks,
                             const unsigned char* target, int ignore_index, const float* count, const float* ft_g, const float* ft_w, int ft_s,
-                            const float* wtab, float gamma, hipStream_t st) {
+                            const float* wtab, float gamma, float eps, hipStream_t st) {
     ConvtCeArgs ce{};
     ce.target = target; ce.count = count; ce.ft_g = ft_g; ce.ft_w = ft_w; ce.ignore_index = ignore_index; ce.ft_s = ft_s > 0 ? ft_s : 1;
-    ce.ft_shift = -1; ce.wtab = wtab; ce.gamma = gamma;
+    ce.ft_shift = -1; ce.wtab = wtab; ce.gamma = gamma; ce.eps = eps;
     for (int b = 0; b < 31; ++b) if (ce.ft_s == (1 << b)) ce.ft_shift = b;
     ce.Hf = (2 * H - 1) / ce.ft_s + 1; ce.Wf = (2 * W - 1) / ce.ft_s + 1;
     const bool w8 = knob("DSRL_CONVT_CE_WAVES", 12) == 8;                  // the transform inside the MFMA waves
     // focal: the 8-wave build whatever DSRL_CONVT_CE_WAVES says.  focal_pixel's log and two divisions beside the 19 terms need 172 VGPRs in the
     // 12-wave build, which has 168 (4 spilled, 20 B of scratch); the 8-wave build has 256 and takes 212
     if (wtab && gamma > 0.f) return launch_dma<true, false, true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
+    // label smoothing: one wave build, the 8-wave one, as focal has
+    if (wtab && eps > 0.f) return launch_dma<true, false, true, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
     if (wtab) return w8 ? launch_dma<true, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st)
                         : launch_dma<true, true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
     if (w8) return launch_dma<true, false>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);

@@ -21,13 +21,18 @@ __device__ inline double block_sum_d(double v, double* sh) {     // sh: 4 double
 // left by ce_weight_sum_kernel where the unweighted kernels leave the pixel count.  The CW = false bodies are the kernels as they were.
 // FL = true (the *_f_kernel entries): focal cross entropy, a pixel's term is (double)w[t] * (double)(q^gamma nll) and its gradient scale
 // (w[t] * mod) * (1 / D), both from focal_pixel (common.h) on exp_nonpos terms; D, the flags and the staging are those of the weighted bodies.
-template <bool CW, bool FL = false>
+// SM = true (the *_s_kernel entries): label-smoothed cross entropy, a pixel's term and its gradient row come from smooth_pixel / smooth_grad (common.h),
+// which read all C logits and all C weights of the pixel; W = sum_{c < C} w_c is summed once per block, c ascending, before the pixel loop.
+template <bool CW, bool FL = false, bool SM = false>
 __device__ __forceinline__ void ce_fwd_body(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
-                                            int ignore_index, const float* __restrict__ wtab, double* __restrict__ part, float gamma = 0.f) {
+                                            int ignore_index, const float* __restrict__ wtab, double* __restrict__ part, float gamma = 0.f, float eps = 0.f) {
     static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
+    static_assert(!SM || (CW && !FL), "label smoothing runs on the weighted machinery and has no focal form");
     extern __shared__ float tile[];         // [256][C]
     __shared__ double shd[4];
     double loss = 0.0, cnt = 0.0;
+    float Wsum = 0.f;
+    if (SM) for (int c = 0; c < C; ++c) Wsum += wtab[c];
     for (long long p0 = (long long)blockIdx.x * 256; p0 < P; p0 += (long long)gridDim.x * 256) {
         const int np = (int)min(256ll, P - p0);
         __syncthreads();
@@ -39,7 +44,13 @@ __device__ __forceinline__ void ce_fwd_body(const float* __restrict__ logits, in
                 const float* v = tile + threadIdx.x * C;
                 float m = v[0];
                 for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
-                if (FL) {
+                if (SM) {
+                    float s = 0.f;
+                    for (int c = 0; c < C; ++c) s += exp_nonpos(v[c] - m);
+                    double val; float sub_t, inv;
+                    smooth_pixel<true>(v, wtab, C, tg, m, s, eps, Wsum, 0.f, val, sub_t, inv);
+                    loss += tg < C ? val : __builtin_nan("");
+                } else if (FL) {
                     float s = 0.f, so = 0.f;
                     for (int c = 0; c < C; ++c) { const float e = exp_nonpos(v[c] - m); s += e; so += c == tg ? 0.f : e; }
                     const float vt = v[min(tg, C - 1)];
@@ -74,6 +85,10 @@ __global__ __launch_bounds__(256) void ce_fwd_f_kernel(const float* __restrict__
                                                         int ignore_index, const float* __restrict__ wtab, float gamma, double* __restrict__ part) {
     ce_fwd_body<true, true>(logits, ld, target, P, C, ignore_index, wtab, part, gamma);
 }
+__global__ __launch_bounds__(256) void ce_fwd_s_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                        int ignore_index, const float* __restrict__ wtab, float eps, double* __restrict__ part) {
+    ce_fwd_body<true, false, true>(logits, ld, target, P, C, ignore_index, wtab, part, 0.f, eps);
+}
 __global__ __launch_bounds__(256) void ce_finalize_kernel(const double* __restrict__ part, int nb, float* __restrict__ out) {
     __shared__ double shd[4];
     double l = 0, n = 0;
@@ -92,13 +107,20 @@ __global__ __launch_bounds__(256) void ce_finalize_w_kernel(const double* __rest
     l = block_sum_d(l, shd);
     if (threadIdx.x == 0) out[0] = (float)(l / (double)out[1]);
 }
-template <bool CW, bool FL = false>
+template <bool CW, bool FL = false, bool SM = false>
 __device__ __forceinline__ void ce_bwd_body(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
                                             int ignore_index, const float* __restrict__ wtab, const float* __restrict__ loss_out,
-                                            const float* __restrict__ grad_out, float* __restrict__ dl, int lddl, float gamma = 0.f) {
+                                            const float* __restrict__ grad_out, float* __restrict__ dl, int lddl, float gamma = 0.f, float eps = 0.f) {
     static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
+    static_assert(!SM || (CW && !FL), "label smoothing runs on the weighted machinery and has no focal form");
     extern __shared__ float tile[];
     const float scale = grad_out[0] / loss_out[1];
+    float Wsum = 0.f;
+    __shared__ float sub_s[SM ? 64 : 1];    // SM: smooth_sub of every class (C <= 60), published by the first barrier of the pixel loop
+    if (SM) {
+        for (int c = 0; c < C; ++c) Wsum += wtab[c];
+        if ((int)threadIdx.x < C) sub_s[threadIdx.x] = smooth_sub(eps, C, wtab[threadIdx.x], scale);
+    }
     for (long long p0 = (long long)blockIdx.x * 256; p0 < P; p0 += (long long)gridDim.x * 256) {
         const int np = (int)min(256ll, P - p0);
         __syncthreads();
@@ -111,7 +133,13 @@ __device__ __forceinline__ void ce_bwd_body(const float* __restrict__ logits, in
                 float m = v[0];
                 for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
                 const bool bad = tg >= C;             // label outside [0, C), not ignored: a NaN gradient row, as the loss
-                if (FL) {
+                if (SM) {
+                    float s = 0.f;
+                    for (int c = 0; c < C; ++c) s += exp_nonpos(v[c] - m);
+                    double val; float sub_t, inv;
+                    smooth_pixel<false>(v, wtab, C, tg, m, s, eps, Wsum, scale, val, sub_t, inv);
+                    for (int c = 0; c < C; ++c) v[c] = bad ? __builtin_nanf("") : smooth_grad(exp_nonpos(v[c] - m), inv, c == tg, sub_t, sub_s[c]);
+                } else if (FL) {
                     const float vt = v[min(tg, C - 1)];
                     float s = 0.f, so = 0.f;
                     for (int c = 0; c < C; ++c) { const float e = exp_nonpos(v[c] - m); s += e; so += c == tg ? 0.f : e; v[c] = e; }
@@ -149,6 +177,11 @@ __global__ __launch_bounds__(256) void ce_bwd_f_kernel(const float* __restrict__
                                                         int ignore_index, const float* __restrict__ wtab, float gamma, const float* __restrict__ loss_out,
                                                         const float* __restrict__ grad_out, float* __restrict__ dl, int lddl) {
     ce_bwd_body<true, true>(logits, ld, target, P, C, ignore_index, wtab, loss_out, grad_out, dl, lddl, gamma);
+}
+__global__ __launch_bounds__(256) void ce_bwd_s_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                        int ignore_index, const float* __restrict__ wtab, float eps, const float* __restrict__ loss_out,
+                                                        const float* __restrict__ grad_out, float* __restrict__ dl, int lddl) {
+    ce_bwd_body<true, false, true>(logits, ld, target, P, C, ignore_index, wtab, loss_out, grad_out, dl, lddl, 0.f, eps);
 }
 
 // ---------------------------------------------------------------------------------------------- fused loss pass
@@ -234,12 +267,14 @@ __global__ __launch_bounds__(256) void ce_weight_sum_kernel(const unsigned* __re
     }
 }
 
-template <bool CW, bool FL = false>
+template <bool CW, bool FL = false, bool SM = false>
 __device__ __forceinline__ void ce_fused_body(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
                                               int ignore_index, const unsigned* __restrict__ cnt_part, const float* __restrict__ wtab,
                                               const float* __restrict__ wsum, float* __restrict__ dl, int lddl,
-                                              double* __restrict__ part, int* __restrict__ nan_flag, int vec_in, int vec_out, float gamma = 0.f) {
+                                              double* __restrict__ part, int* __restrict__ nan_flag, int vec_in, int vec_out, float gamma = 0.f,
+                                              float eps = 0.f) {
     static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
+    static_assert(!SM || (CW && !FL), "label smoothing runs on the weighted machinery and has no focal form");
     extern __shared__ __attribute__((aligned(16))) float tile[];         // [256][C]
     __shared__ double shd[4];
     __shared__ float sh_scale;
@@ -252,6 +287,12 @@ __device__ __forceinline__ void ce_fused_body(const float* __restrict__ logits, 
     const float scale = CW ? 1.f / wsum[0] : sh_scale;      // CW: 1 / D; per pixel sc = w[t] * (1 / D)
     double loss = 0.0, cnt = 0.0;
     bool bad = false, bad_label = false;
+    float Wsum = 0.f;
+    __shared__ float sub_s[SM ? 64 : 1];    // SM: smooth_sub of every class (C <= 60), published by the first barrier of the pixel loop
+    if (SM) {
+        for (int c = 0; c < C; ++c) Wsum += wtab[c];
+        if ((int)threadIdx.x < C) sub_s[threadIdx.x] = smooth_sub(eps, C, wtab[threadIdx.x], scale);
+    }
     for (long long p0 = (long long)blockIdx.x * 256; p0 < P; p0 += (long long)gridDim.x * 256) {
         const int np = (int)min(256ll, P - p0);
         const int nf = np * C;
@@ -272,13 +313,26 @@ __device__ __forceinline__ void ce_fused_body(const float* __restrict__ logits, 
             for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
             const float vt = v[max(min(tg == ignore_index ? 0 : tg, C - 1), 0)];
             float s = 0.f, so = 0.f;
-            if (FL) {                           // so: the sum without the target's term, in the same order
+            if (SM) {                           // the tile keeps the logits: smooth_pixel reads every one of them once s is known
+                for (int c = 0; c < C; ++c) s += exp_nonpos(v[c] - m);
+            } else if (FL) {                    // so: the sum without the target's term, in the same order
                 for (int c = 0; c < C; ++c) { const float e = exp_nonpos(v[c] - m); s += e; so += c == tg ? 0.f : e; v[c] = e; }
             } else {
                 for (int c = 0; c < C; ++c) { const float e = exp_nonpos(v[c] - m); s += e; v[c] = e; }   // the tile keeps exp(v - m): one exp per logit
             }
             bad |= !(s == s);                   // any NaN logit poisons the sum (fmaxf alone would skip it)
-            if (tg != ignore_index) {
+            if (SM) {
+                if (tg != ignore_index) {
+                    double val; float sub_t, inv;
+                    smooth_pixel<true>(v, wtab, C, tg, m, s, eps, Wsum, scale, val, sub_t, inv);
+                    loss += val;
+                    cnt += 1.0;
+                    // the second exp_nonpos of a logit has the bits of the first: the row equals the one convt2x2_bwd_dma_kernel forms from registers
+                    if (dl) for (int c = 0; c < C; ++c) v[c] = smooth_grad(exp_nonpos(v[c] - m), inv, c == tg, sub_t, sub_s[c]);
+                } else if (dl) {
+                    for (int c = 0; c < C; ++c) v[c] = 0.f;
+                }
+            } else if (tg != ignore_index) {
                 const float wt = CW ? wtab[tg] : 1.f;
                 float mod = 1.f;
                 if (FL) {
@@ -332,6 +386,12 @@ __global__ __launch_bounds__(256) void ce_fused_f_kernel(const float* __restrict
                                                           float* __restrict__ dl, int lddl, double* __restrict__ part, int* __restrict__ nan_flag,
                                                           int vec_in, int vec_out) {
     ce_fused_body<true, true>(logits, ld, target, P, C, ignore_index, nullptr, wtab, wsum, dl, lddl, part, nan_flag, vec_in, vec_out, gamma);
+}
+__global__ __launch_bounds__(256) void ce_fused_s_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                          int ignore_index, const float* __restrict__ wtab, float eps, const float* __restrict__ wsum,
+                                                          float* __restrict__ dl, int lddl, double* __restrict__ part, int* __restrict__ nan_flag,
+                                                          int vec_in, int vec_out) {
+    ce_fused_body<true, false, true>(logits, ld, target, P, C, ignore_index, nullptr, wtab, wsum, dl, lddl, part, nan_flag, vec_in, vec_out, 0.f, eps);
 }
 // MSE forward and backward in one pass: partial sums of (a-b)^2 and da = (a-b) * 2 * grad_scale / n; NaN check of `a`
 __global__ __launch_bounds__(256) void mse_fused_kernel(const float* __restrict__ a, const float* __restrict__ b, long long n, float sc, float* __restrict__ da,
@@ -962,6 +1022,57 @@ extern "C" int dsrl_ce_fused_f(const float* logits, int ld, const uint8_t* targe
     hipLaunchKernelGGL(ce_fused_f_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index,
                        weights, gamma, (const float*)(loss_out + 1), dlogits, lddl, part, nan_flag, vec_in, vec_out);
     if (int e = launch_status("ce_fused_f_kernel")) return e;
+    return launch_ce_finalize_w(part, nb, loss_out, st);
+}
+// ---- label-smoothed cross entropy: the weighted entry points plus the smoothing term over all classes (smooth_pixel, common.h).  Same pre-pass, same D,
+// same workspaces.  eps == 0 is the weighted loss itself and goes to the _w entry point: no smoothing kernel runs with it.
+extern "C" size_t dsrl_ce_s_workspace_bytes(int64_t P) { return dsrl_ce_w_workspace_bytes(P); }
+extern "C" int dsrl_ce_fwd_s(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float eps,
+                             float* loss_out, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_LABEL_SMOOTHING(eps, "ce_fwd_s");
+    if (eps == 0.f) return dsrl_ce_fwd_w(logits, ld, target, P, C, ignore_index, weights, loss_out, ws, ws_bytes, stream);
+    DSRL_REQUIRE(logits && target && weights && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C, DSRL_E_BADARG, "ce_fwd_s: bad arguments (C=%d)", C);
+    DSRL_REQUIRE(ws_bytes >= dsrl_ce_s_workspace_bytes(P) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fwd_s: workspace too small or misaligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    const int nb = loss_blocks(P);
+    double* part = (double*)ws;
+    if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, loss_out + 1, part + 2 * nb, st)) return e;
+    hipLaunchKernelGGL(ce_fwd_s_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index, weights,
+                       eps, part);
+    if (int e = launch_status("ce_fwd_s_kernel")) return e;
+    return launch_ce_finalize_w(part, nb, loss_out, st);
+}
+extern "C" int dsrl_ce_bwd_s(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float eps,
+                             const float* loss_out, const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
+    DSRL_LABEL_SMOOTHING(eps, "ce_bwd_s");
+    if (eps == 0.f) return dsrl_ce_bwd_w(logits, ld, target, P, C, ignore_index, weights, loss_out, grad_out, dlogits, lddl, stream);
+    DSRL_REQUIRE(logits && target && weights && loss_out && grad_out && dlogits && P > 0 && C > 0 && C <= 60 && ld >= C && lddl >= C, DSRL_E_BADARG,
+                 "ce_bwd_s: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    hipLaunchKernelGGL(ce_bwd_s_kernel, dim3((unsigned)std::min<long long>(ceil_div(P, 256), 8192)), dim3(256), (size_t)256 * C * sizeof(float), st,
+                       logits, ld, target, (long long)P, C, ignore_index, weights, eps, loss_out, grad_out, dlogits, lddl);
+    return launch_status("ce_bwd_s_kernel");
+}
+extern "C" size_t dsrl_ce_fused_s_workspace_bytes(int64_t P) { return dsrl_ce_fused_w_workspace_bytes(P); }
+extern "C" int dsrl_ce_fused_s(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float eps,
+                               float* dlogits, int lddl, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_LABEL_SMOOTHING(eps, "ce_fused_s");
+    if (eps == 0.f) return dsrl_ce_fused_w(logits, ld, target, P, C, ignore_index, weights, dlogits, lddl, loss_out, nan_flag, ws, ws_bytes, stream);
+    DSRL_REQUIRE(logits && target && weights && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C && (!dlogits || lddl >= C), DSRL_E_BADARG,
+                 "ce_fused_s: bad arguments (C=%d)", C);
+    DSRL_REQUIRE(ws_bytes >= dsrl_ce_fused_s_workspace_bytes(P) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fused_s: workspace too small or misaligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    const int nb = loss_blocks(P);
+    double* part = (double*)ws;
+    if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, loss_out + 1, part + 2 * nb, st)) return e;
+    const int vec_in = (ld == C && ((uintptr_t)logits % 16) == 0) ? 1 : 0;
+    const int vec_out = (dlogits && lddl == C && ((uintptr_t)dlogits % 16) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(ce_fused_s_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index,
+                       weights, eps, (const float*)(loss_out + 1), dlogits, lddl, part, nan_flag, vec_in, vec_out);
+    if (int e = launch_status("ce_fused_s_kernel")) return e;
     return launch_ce_finalize_w(part, nb, loss_out, st);
 }
 extern "C" int dsrl_mse_fused(const float* a, const float* b, int64_t n, float grad_scale, float* da, float* loss_out, int* nan_flag,

@@ -384,17 +384,20 @@ __global__ __launch_bounds__(256) void convt2x2_fwd_kernel(const float* __restri
 // loss of two output pixels from the tile in LDS (max, exp, sum, log in ce_fused_kernel's arithmetic; NaN logit -> flag bit 0, label outside
 // [0, CO) -> NaN loss + flag bit 1) while the tile is being stored: the 319 MB read of a loss pass of its own disappears.  Per-block partials
 // (sum of the pixel losses, number of pixels that count) as two doubles in ce.part; ce_finalize_kernel merges them.
-struct ConvtFwdCe { const unsigned char* target; double* part; int* nan_flag; int ignore_index; const float* wtab; float gamma; };
+struct ConvtFwdCe { const unsigned char* target; double* part; int* nan_flag; int ignore_index; const float* wtab; float gamma; float eps; };
 using f32x16_f = __attribute__((ext_vector_type(16))) float;
 // CW = true (dsrl_convt2x2_fwd_ce_w): nn.CrossEntropyLoss(weight=): a pixel's term is (double)ce.wtab[target] * (double)nll, wtab the 256-float
 // class-weight table (ce_fwd_body in losses.hip).  A template parameter, so that the CW = false instantiations compile to the code they were.
 // FL = true (dsrl_convt2x2_fwd_ce_f): focal cross entropy, the term is (double)wtab[target] * (double)(q^gamma nll) from focal_pixel (common.h): one
 // more pass over the pixel's 19 words in LDS for the sum without the target's term.
-template <int CI, int CO, bool CE = false, bool CW = false, bool FL = false>
+// SM = true (dsrl_convt2x2_fwd_ce_s): label-smoothed cross entropy, the term comes from smooth_pixel (common.h), which reads the pixel's 19 words in LDS
+// once more and all 19 weights; W = sum_c w_c is summed once per block.
+template <int CI, int CO, bool CE = false, bool CW = false, bool FL = false, bool SM = false>
 __global__ __launch_bounds__(256, 2) void convt2x2_fwd_mfma_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                                  float* __restrict__ y, int N, int H, int W, int nseg_per_row, int nseg, ConvtFwdCe ce) {
     static_assert(CE || !CW, "class weights belong to the CE build");
     static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
+    static_assert(!SM || (CW && !FL), "label smoothing runs on the weighted machinery and has no focal form");
     constexpr int TP = 128, COLS = 4 * CO, GS = COLS + 1, NK = (CI + 2) / 2, XS = 2 * NK, NJ = (COLS + 31) / 32;
     static_assert(CI + 1 <= XS && NJ <= 3 && (TP * CI) % 4 == 0 && (2 * TP * CO) % 4 == 0, "tile does not fit");
     constexpr int XV = TP * CI / 4, DV = 2 * TP * CO / 4;                   // float4 per x segment / per output row segment
@@ -429,6 +432,11 @@ __global__ __launch_bounds__(256, 2) void convt2x2_fwd_mfma_kernel(const float* 
     const int px0 = 32 * wv;
     double ce_loss = 0.0, ce_cnt = 0.0;
     bool ce_bad = false, ce_bad_label = false;
+    float Wsum = 0.f;
+    if (SM) {
+#pragma unroll
+        for (int c = 0; c < CO; ++c) Wsum += ce.wtab[c];
+    }
     int seg = (int)blockIdx.x;
     if (seg < nseg) gload(seg);
     for (; seg < nseg; seg += (int)gridDim.x) {
@@ -486,7 +494,12 @@ __global__ __launch_bounds__(256, 2) void convt2x2_fwd_mfma_kernel(const float* 
                 for (int c = 0; c < CO; ++c) sum += exp_nonpos(v[c] - m);
                 ce_bad |= !(sum == sum);            // any NaN logit poisons the sum (fmaxf alone would skip it)
                 if (tg != ce.ignore_index) {
-                    if (FL) {
+                    if (SM) {
+                        double val; float sub_t, inv;
+                        smooth_pixel<true>(v, ce.wtab, CO, tg, m, sum, ce.eps, Wsum, 0.f, val, sub_t, inv);
+                        ce_loss += val;
+                    }
+                    else if (FL) {
                         float so = 0.f, fl, mod;
 #pragma unroll
                         for (int c = 0; c < CO; ++c) so += c == tg ? 0.f : exp_nonpos(v[c] - m);
@@ -1270,7 +1283,7 @@ extern "C" int dsrl_convt2x2_fwd_ce(const float* x, const float* w, const float*
     const int nseg_per_row = (int)ceil_div(W, 128);
     const long long nseg = (long long)N * H * nseg_per_row;
     const int nb = (int)std::min<long long>(nseg, convt_block_cap(4 * 512));
-    ConvtFwdCe ce{target, (double*)ws, nan_flag, ignore_index, nullptr, 0.f};
+    ConvtFwdCe ce{target, (double*)ws, nan_flag, ignore_index, nullptr, 0.f, 0.f};
     hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true>), dim3(nb), dim3(256), 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce);
     if (int e = launch_status("convt2x2_fwd_mfma_kernel")) return e;
     return launch_ce_finalize((const double*)ws, nb, loss_out, st);
@@ -1291,7 +1304,7 @@ extern "C" int dsrl_convt2x2_fwd_ce_w(const float* x, const float* w, const floa
     const long long nseg = (long long)N * H * nseg_per_row;
     const int nb = (int)std::min<long long>(nseg, convt_block_cap(4 * 512));
     if (int e = launch_ce_weight_sum(target, (long long)N * 4 * H * W, Cout, ignore_index, weights, loss_out + 1, (double*)ws + 2 * nb, st)) return e;
-    ConvtFwdCe ce{target, (double*)ws, nan_flag, ignore_index, weights, 0.f};
+    ConvtFwdCe ce{target, (double*)ws, nan_flag, ignore_index, weights, 0.f, 0.f};
     hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true, true>), dim3(nb), dim3(256), 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce);
     if (int e = launch_status("convt2x2_fwd_mfma_kernel")) return e;
     return launch_ce_finalize_w((const double*)ws, nb, loss_out, st);
@@ -1311,8 +1324,28 @@ extern "C" int dsrl_convt2x2_fwd_ce_f(const float* x, const float* w, const floa
     const long long nseg = (long long)N * H * nseg_per_row;
     const int nb = (int)std::min<long long>(nseg, convt_block_cap(4 * 512));
     if (int e = launch_ce_weight_sum(target, (long long)N * 4 * H * W, Cout, ignore_index, weights, loss_out + 1, (double*)ws + 2 * nb, st)) return e;
-    ConvtFwdCe ce{target, (double*)ws, nan_flag, ignore_index, weights, gamma};
+    ConvtFwdCe ce{target, (double*)ws, nan_flag, ignore_index, weights, gamma, 0.f};
     hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true, true, true>), dim3(nb), dim3(256), 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce);
+    if (int e = launch_status("convt2x2_fwd_mfma_kernel")) return e;
+    return launch_ce_finalize_w((const double*)ws, nb, loss_out, st);
+}
+// the label-smoothing forms: the weighted forms plus eps (eps == 0 IS the weighted form)
+extern "C" size_t dsrl_convt2x2_fwd_ce_s_workspace_bytes(int N, int H, int W) { return dsrl_convt2x2_fwd_ce_w_workspace_bytes(N, H, W); }
+extern "C" int dsrl_convt2x2_fwd_ce_s(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                                      const uint8_t* target, int ignore_index, const float* weights, float eps, float* loss_out, int* nan_flag,
+                                      void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_LABEL_SMOOTHING(eps, "convt2x2_fwd_ce_s");
+    if (eps == 0.f) return dsrl_convt2x2_fwd_ce_w(x, w, bias, y, N, H, W, Cin, Cout, target, ignore_index, weights, loss_out, nan_flag, ws, ws_bytes, stream);
+    DSRL_PROLOGUE(x && w && y && target && weights && loss_out && ws && N > 0 && H > 0 && W > 0 && ((uintptr_t)ws % 8) == 0, "convt2x2_fwd_ce_s")
+    DSRL_REQUIRE(dsrl_convt2x2_fwd_ce_supported(x, y, N, H, W, Cin, Cout), DSRL_E_UNSUPPORTED,
+                 "convt2x2_fwd_ce_s: needs 19 -> 19 channels, W %% 4 == 0, 16-byte aligned tensors (got %d -> %d, W = %d) and DSRL_CONVT_MFMA / DSRL_CONVT_CE not 0", Cin, Cout, W);
+    DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_fwd_ce_s_workspace_bytes(N, H, W), DSRL_E_WORKSPACE, "convt2x2_fwd_ce_s: workspace too small");
+    const int nseg_per_row = (int)ceil_div(W, 128);
+    const long long nseg = (long long)N * H * nseg_per_row;
+    const int nb = (int)std::min<long long>(nseg, convt_block_cap(4 * 512));
+    if (int e = launch_ce_weight_sum(target, (long long)N * 4 * H * W, Cout, ignore_index, weights, loss_out + 1, (double*)ws + 2 * nb, st)) return e;
+    ConvtFwdCe ce{target, (double*)ws, nan_flag, ignore_index, weights, 0.f, eps};
+    hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true, true, false, true>), dim3(nb), dim3(256), 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce);
     if (int e = launch_status("convt2x2_fwd_mfma_kernel")) return e;
     return launch_ce_finalize_w((const double*)ws, nb, loss_out, st);
 }
@@ -1381,7 +1414,7 @@ extern "C" int dsrl_convt2x2_bwd_ce(const float* x, const float* w, const float*
     DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_bwd_workspace_bytes(N, H, W, Cin, Cout), DSRL_E_WORKSPACE, "convt2x2_bwd_ce: workspace too small");
     const long long nseg = (long long)N * H * (W / 128);
     const int nb3 = convt_bwd_dma_blocks(nseg, convt_dw_blocks(N, H, W));
-    if (int e = launch_convt_bwd_dma_ce(x, w, logits, dx, (float*)ws, N, H, W, nb3, target, ignore_index, ce_count, ft_g, ft_w, ft_stride, nullptr, 0.f, st)) return e;
+    if (int e = launch_convt_bwd_dma_ce(x, w, logits, dx, (float*)ws, N, H, W, nb3, target, ignore_index, ce_count, ft_g, ft_w, ft_stride, nullptr, 0.f, 0.f, st)) return e;
     hipLaunchKernelGGL((convt2x2_dw_finalize_kernel<19, 19>), dim3((unsigned)ceil_div(19 * 19 * 4 + 19, 32)), dim3(256), 0, st, (const float*)ws, nb3, dw, dbias);
     return launch_status("convt2x2_dw_finalize_kernel");
 }
@@ -1395,7 +1428,7 @@ extern "C" int dsrl_convt2x2_bwd_ce_w(const float* x, const float* w, const floa
     DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_bwd_workspace_bytes(N, H, W, Cin, Cout), DSRL_E_WORKSPACE, "convt2x2_bwd_ce_w: workspace too small");
     const long long nseg = (long long)N * H * (W / 128);
     const int nb3 = convt_bwd_dma_blocks(nseg, convt_dw_blocks(N, H, W));
-    if (int e = launch_convt_bwd_dma_ce(x, w, logits, dx, (float*)ws, N, H, W, nb3, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, weights, 0.f, st)) return e;
+    if (int e = launch_convt_bwd_dma_ce(x, w, logits, dx, (float*)ws, N, H, W, nb3, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, weights, 0.f, 0.f, st)) return e;
     hipLaunchKernelGGL((convt2x2_dw_finalize_kernel<19, 19>), dim3((unsigned)ceil_div(19 * 19 * 4 + 19, 32)), dim3(256), 0, st, (const float*)ws, nb3, dw, dbias);
     return launch_status("convt2x2_dw_finalize_kernel");
 }
@@ -1412,7 +1445,24 @@ extern "C" int dsrl_convt2x2_bwd_ce_f(const float* x, const float* w, const floa
     DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_bwd_workspace_bytes(N, H, W, Cin, Cout), DSRL_E_WORKSPACE, "convt2x2_bwd_ce_f: workspace too small");
     const long long nseg = (long long)N * H * (W / 128);
     const int nb3 = convt_bwd_dma_blocks(nseg, convt_dw_blocks(N, H, W));
-    if (int e = launch_convt_bwd_dma_ce(x, w, logits, dx, (float*)ws, N, H, W, nb3, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, weights, gamma, st)) return e;
+    if (int e = launch_convt_bwd_dma_ce(x, w, logits, dx, (float*)ws, N, H, W, nb3, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, weights, gamma, 0.f, st)) return e;
+    hipLaunchKernelGGL((convt2x2_dw_finalize_kernel<19, 19>), dim3((unsigned)ceil_div(19 * 19 * 4 + 19, 32)), dim3(256), 0, st, (const float*)ws, nb3, dw, dbias);
+    return launch_status("convt2x2_dw_finalize_kernel");
+}
+
+extern "C" int dsrl_convt2x2_bwd_ce_s(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* weights,
+                                      float eps, const float* ce_wsum, const float* ft_g, const float* ft_w, int ft_stride, float* dx, float* dw, float* dbias,
+                                      int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_LABEL_SMOOTHING(eps, "convt2x2_bwd_ce_s");
+    if (eps == 0.f) return dsrl_convt2x2_bwd_ce_w(x, w, logits, target, ignore_index, weights, ce_wsum, ft_g, ft_w, ft_stride, dx, dw, dbias, N, H, W, Cin, Cout,
+                                                  ws, ws_bytes, stream);
+    DSRL_PROLOGUE(x && w && logits && target && weights && ce_wsum && dx && dw && ws && N > 0 && H > 0 && W > 0 && (!ft_g || (ft_w && ft_stride > 0)), "convt2x2_bwd_ce_s")
+    DSRL_REQUIRE(dsrl_convt2x2_bwd_ce_supported(x, logits, target, N, H, W, Cin, Cout), DSRL_E_UNSUPPORTED,
+                 "convt2x2_bwd_ce_s: needs 19 -> 19 channels, W %% 128 == 0, 16-byte aligned tensors (got %d -> %d, W = %d) and DSRL_CONVT_DMA / DSRL_CONVT_CE not 0", Cin, Cout, W);
+    DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_bwd_workspace_bytes(N, H, W, Cin, Cout), DSRL_E_WORKSPACE, "convt2x2_bwd_ce_s: workspace too small");
+    const long long nseg = (long long)N * H * (W / 128);
+    const int nb3 = convt_bwd_dma_blocks(nseg, convt_dw_blocks(N, H, W));
+    if (int e = launch_convt_bwd_dma_ce(x, w, logits, dx, (float*)ws, N, H, W, nb3, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, weights, 0.f, eps, st)) return e;
     hipLaunchKernelGGL((convt2x2_dw_finalize_kernel<19, 19>), dim3((unsigned)ceil_div(19 * 19 * 4 + 19, 32)), dim3(256), 0, st, (const float*)ws, nb3, dw, dbias);
     return launch_status("convt2x2_dw_finalize_kernel");
 }

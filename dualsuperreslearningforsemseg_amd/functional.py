@@ -1296,14 +1296,15 @@ class LogitsGrad:
     leaves `target`, `count` (device pointer holder) here and reports no gradient; the stride-8 feature transformer leaves its incoming gradient and
     weights; the ConvTranspose backward then forms d(CE)/d(logits) (+ the transformer's rank-one term) inside its own kernel
     (dsrl_convt2x2_bwd_ce): the 319 MB gradient of the 256x512 step is neither written nor read."""
-    __slots__ = ('y', 'xshape', 'x_ptr', 'armed', 'target', 'ignore_index', 'count', 'ft', 'value', 'value_key', 'weight', 'gamma')
+    __slots__ = ('y', 'xshape', 'x_ptr', 'armed', 'target', 'ignore_index', 'count', 'ft', 'value', 'value_key', 'weight', 'gamma', 'eps')
 
     def __init__(self):
         self.y = None; self.xshape = None; self.x_ptr = 0; self.armed = False; self.target = None; self.ignore_index = 255; self.count = None; self.ft = None
         self.value = None           # [CE, pixel count, ...] when the producing layer already evaluated the loss (logits_target), and for which
-        self.value_key = None       # (target pointer, ignore_index, NaN flag pointer, class-weight table pointer or 0, focal gamma)
+        self.value_key = None       # (target pointer, ignore_index, NaN flag pointer, class-weight table pointer or 0, label smoothing, focal gamma)
         self.weight = None          # the 256-float class-weight table of a weighted loss (class_weight_table); `count` then holds D = sum n_c w_c
         self.gamma = 0.0            # > 0: the focal loss (always with a table: all ones when the caller gave no weights)
+        self.eps = 0.0              # > 0: label smoothing (likewise always with a table; never together with gamma > 0)
 
     def usable(self, logits, target):
         """Can the loss leave the gradient to the producer?  logits must be exactly the producer's output buffer."""
@@ -1368,15 +1369,30 @@ def focal_gamma_value(x):
     return g
 
 
-def _focal_args(weight, gamma, device, num_classes):
-    """(class-weight table or None, gamma) of a CE call: the focal loss runs on the weighted kernels, so gamma > 0 without weights takes the
-    all-ones table of `num_classes` classes."""
+def label_smoothing_value(x):
+    """nn.CrossEntropyLoss's label_smoothing as a float: a finite number in [0, 1] (0: off).  ValueError on a bool, on anything that is not a
+    number, on NaN, infinity and anything outside [0, 1] (-1e-30 and 1.0000001 included).  Touches no device."""
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+        raise ValueError(f'label_smoothing = {x!r}: expected a number in [0, 1]')
+    e = float(x)
+    if not (0.0 <= e <= 1.0) or float(np.float32(e)) > 1.0:                    # (a NaN fails the comparison; the kernels take it as fp32)
+        raise ValueError(f'label_smoothing = {x!r}: expected a number in [0, 1]')
+    return e
+
+
+def _focal_args(weight, gamma, device, num_classes, eps=0.0):
+    """(class-weight table or None, gamma, eps) of a CE call: the focal and the label-smoothed loss run on the weighted kernels, so gamma > 0 or
+    eps > 0 without weights takes the all-ones table of `num_classes` classes.  Both at once: ValueError (the combination has no agreed
+    definition and no kernel)."""
     gamma = focal_gamma_value(gamma)
+    eps = label_smoothing_value(eps)
+    if gamma > 0.0 and eps > 0.0:
+        raise ValueError(f'label_smoothing = {eps!r} together with focal_gamma = {gamma!r}: the combination is not defined')
     if weight is not None:
         weight = class_weight_table(weight, device, num_classes)
-    elif gamma > 0.0:
+    elif gamma > 0.0 or eps > 0.0:
         weight = class_weight_table(np.ones(int(num_classes), np.float32), device, num_classes)
-    return weight, gamma
+    return weight, gamma, eps
 
 
 _WEIGHT_TABLES_MAX = 32
@@ -1390,15 +1406,19 @@ class logits_target:
     they will be compared with, so that its forward kernel evaluates nn.CrossEntropyLoss while the output tile is on chip (dsrl_convt2x2_fwd_ce) and
     fused_losses finds the value ready (LogitsGrad.value) instead of reading the logits again.  target: (N,H,W) uint8, contiguous; flag: the int32 NaN
     flag fused_losses will be given; weight: the class weights fused_losses will be given (None: unweighted); focal_gamma: its focal exponent
-    (0: none).  Outside the block, or when the shape does not qualify, nothing changes."""
+    (0: none); label_smoothing: its label smoothing (0: none; not together with focal_gamma > 0).  Outside the block, or when the shape does not
+    qualify, nothing changes."""
 
-    def __init__(self, target, ignore_index, flag, weight=None, focal_gamma=0.0):
+    def __init__(self, target, ignore_index, flag, weight=None, focal_gamma=0.0, label_smoothing=0.0):
         focal_gamma = focal_gamma_value(focal_gamma)
+        label_smoothing = label_smoothing_value(label_smoothing)
+        if focal_gamma > 0.0 and label_smoothing > 0.0:
+            raise ValueError(f'label_smoothing = {label_smoothing!r} together with focal_gamma = {focal_gamma!r}: the combination is not defined')
         ok = (convt_ce_enabled and target is not None and target.is_cuda and target.dtype == torch.uint8 and target.is_contiguous() and target.dim() == 3
               and flag is not None and flag.dtype == torch.int32)
         if weight is not None and target is not None:
             weight = class_weight_table(weight, target.device)
-        self.new = (target, int(ignore_index), flag, weight, focal_gamma) if ok else None
+        self.new = (target, int(ignore_index), flag, weight, focal_gamma, label_smoothing) if ok else None
 
     def __enter__(self):
         global _logits_target
@@ -1428,12 +1448,16 @@ class _ConvT2x2(torch.autograd.Function):
         lt = _logits_target if holder is not None else None
         if (lt is not None and tuple(lt[0].shape) == (N, 2 * H, 2 * W) and lt[0].device == x.device
                 and query('dsrl_convt2x2_fwd_ce_supported', x.data_ptr(), y.data_ptr(), N, H, W, Ci, Co)):       # (pointer arguments: not memoised)
-            tgt, ign, flag, wt, gamma = lt
-            if gamma > 0.0:
-                wt = _focal_args(wt, gamma, x.device, Co)[0]
+            tgt, ign, flag, wt, gamma, eps = lt
+            if gamma > 0.0 or eps > 0.0:
+                wt = _focal_args(wt, gamma, x.device, Co, eps)[0]
             holder.value = torch.empty(8, device=x.device, dtype=torch.float32)
-            holder.value_key = (tgt.data_ptr(), ign, flag.data_ptr(), 0 if wt is None else wt.data_ptr(), gamma)
-            if gamma > 0.0:
+            holder.value_key = (tgt.data_ptr(), ign, flag.data_ptr(), 0 if wt is None else wt.data_ptr(), eps, gamma)
+            if eps > 0.0:
+                ws = _ws(cquery('dsrl_convt2x2_fwd_ce_s_workspace_bytes', N, H, W), x)
+                call('dsrl_convt2x2_fwd_ce_s', x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co,
+                     tgt.data_ptr(), ign, wt.data_ptr(), eps, holder.value.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+            elif gamma > 0.0:
                 ws = _ws(cquery('dsrl_convt2x2_fwd_ce_f_workspace_bytes', N, H, W), x)
                 call('dsrl_convt2x2_fwd_ce_f', x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co,
                      tgt.data_ptr(), ign, wt.data_ptr(), gamma, holder.value.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
@@ -1464,8 +1488,8 @@ class _ConvT2x2(torch.autograd.Function):
         h = ctx.holder
         hand = None
         if h is not None and h.armed:           # the loss left d(CE)/d(logits) to this layer: take it over, and disarm the holder whatever happens next
-            hand = (h.y, h.target, int(h.ignore_index), h.count, h.ft, h.weight, h.gamma)
-            h.armed = False; h.ft = None; h.target = None; h.count = None; h.y = None; h.value = None; h.weight = None; h.gamma = 0.0
+            hand = (h.y, h.target, int(h.ignore_index), h.count, h.ft, h.weight, h.gamma, h.eps)
+            h.armed = False; h.ft = None; h.target = None; h.count = None; h.y = None; h.value = None; h.weight = None; h.gamma = 0.0; h.eps = 0.0
         fused = dy is None and hand is not None
         if dy is None and not fused:
             raise DsrlHipError('conv_transpose2d_k2s2: backward reached without a gradient for the output')
@@ -1475,11 +1499,15 @@ class _ConvT2x2(torch.autograd.Function):
             # another consumer of the logits sent a gradient too (it is not the loss's: fused_losses returned none): d(CE)/d(logits) and the
             # transformer's term are written as the unfused step writes them (dsrl_ce_fused, dsrl_pointwise_strided_bwd(accumulate = 1)), dy is
             # added as autograd would add it, and the plain backward below takes the sum
-            y, target, ign, _, ft, wt, gamma = hand
+            y, target, ign, _, ft, wt, gamma, eps = hand
             P = N * 4 * H * W
             dl = new_cl((N, Co, 2 * H, 2 * W), x)
             scal = torch.empty(8, device=x.device, dtype=torch.float32)
-            if gamma > 0.0:
+            if eps > 0.0:
+                wsc = _ws(cquery('dsrl_ce_fused_s_workspace_bytes', P), x)
+                call('dsrl_ce_fused_s', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, wt.data_ptr(), eps, dl.data_ptr(), Co, scal.data_ptr(), None,
+                     wsc.data_ptr(), wsc.numel(), _stream())
+            elif gamma > 0.0:
                 wsc = _ws(cquery('dsrl_ce_fused_f_workspace_bytes', P), x)
                 call('dsrl_ce_fused_f', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, wt.data_ptr(), gamma, dl.data_ptr(), Co, scal.data_ptr(), None,
                      wsc.data_ptr(), wsc.numel(), _stream())
@@ -1504,9 +1532,13 @@ class _ConvT2x2(torch.autograd.Function):
         db = (bsink if bsink is not None else torch.empty(Co, device=x.device, dtype=torch.float32)) if ctx.has_bias else None
         ws = _ws(cquery('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, Ci, Co), x)
         if fused:
-            y, target, ign, count, ft, wt, gamma = hand
+            y, target, ign, count, ft, wt, gamma, eps = hand
             ft_g, ft_w, ft_s = ft if ft is not None else (None, None, 0)
-            if gamma > 0.0:
+            if eps > 0.0:
+                call('dsrl_convt2x2_bwd_ce_s', x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, wt.data_ptr(), eps, count.data_ptr() + 4,
+                     None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
+                     dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
+            elif gamma > 0.0:
                 call('dsrl_convt2x2_bwd_ce_f', x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, wt.data_ptr(), gamma, count.data_ptr() + 4,
                      None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
                      dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
@@ -1625,7 +1657,7 @@ def pointwise_strided(x, weight, stride, out_slot=None):
 # ------------------------------------------------------------------------------------------------ losses
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, ignore_index, weight=None, gamma=0.0):
+    def forward(ctx, logits, target, ignore_index, weight=None, gamma=0.0, eps=0.0):
         logits, ld = pm(logits)
         _need_gpu(target)
         if target.dtype != torch.uint8:
@@ -1636,7 +1668,11 @@ class _CrossEntropy(torch.autograd.Function):
         if target.numel() != P:
             raise DsrlHipError(f'cross_entropy: target has {target.numel()} pixels, logits {P}')
         out = torch.empty(2, device=logits.device, dtype=torch.float32)
-        if gamma > 0.0:
+        if eps > 0.0:
+            ws = _ws(cquery('dsrl_ce_s_workspace_bytes', P), logits)
+            call('dsrl_ce_fwd_s', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(), eps, out.data_ptr(),
+                 ws.data_ptr(), ws.numel(), _stream())
+        elif gamma > 0.0:
             ws = _ws(cquery('dsrl_ce_f_workspace_bytes', P), logits)
             call('dsrl_ce_fwd_f', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(), gamma, out.data_ptr(),
                  ws.data_ptr(), ws.numel(), _stream())
@@ -1651,6 +1687,7 @@ class _CrossEntropy(torch.autograd.Function):
         ctx.ignore_index = int(ignore_index)
         ctx.weight = weight
         ctx.gamma = gamma
+        ctx.eps = eps
         return out[0].clone()
 
     @staticmethod
@@ -1660,7 +1697,10 @@ class _CrossEntropy(torch.autograd.Function):
         N, Cc, H, W = logits.shape
         g = g.reshape(1).contiguous().float()
         dl = new_cl((N, Cc, H, W), logits)
-        if ctx.gamma > 0.0:
+        if ctx.eps > 0.0:
+            call('dsrl_ce_bwd_s', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, ctx.weight.data_ptr(), ctx.eps,
+                 out.data_ptr(), g.data_ptr(), dl.data_ptr(), Cc, _stream())
+        elif ctx.gamma > 0.0:
             call('dsrl_ce_bwd_f', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, ctx.weight.data_ptr(), ctx.gamma,
                  out.data_ptr(), g.data_ptr(), dl.data_ptr(), Cc, _stream())
         elif ctx.weight is None:
@@ -1669,14 +1709,16 @@ class _CrossEntropy(torch.autograd.Function):
         else:
             call('dsrl_ce_bwd_w', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, ctx.weight.data_ptr(), out.data_ptr(),
                  g.data_ptr(), dl.data_ptr(), Cc, _stream())
-        return dl, None, None, None, None
+        return dl, None, None, None, None, None
 
 
-def cross_entropy(logits, target, ignore_index=255, weight=None, focal_gamma=0.0):
-    """nn.CrossEntropyLoss(weight, ignore_index) with mean reduction; target (N,H,W) uint8/long; weight: None, one number per class, or a
-    class_weight_table.  focal_gamma > 0: the focal loss sum w[t] (1 - p_t)^gamma (-log p_t) / sum w[t]; 0 changes nothing."""
-    weight, focal_gamma = _focal_args(weight, focal_gamma, logits.device, logits.shape[1])
-    return _CrossEntropy.apply(logits, target, ignore_index, weight, focal_gamma)
+def cross_entropy(logits, target, ignore_index=255, weight=None, focal_gamma=0.0, label_smoothing=0.0):
+    """nn.CrossEntropyLoss(weight, ignore_index, label_smoothing=) with mean reduction; target (N,H,W) uint8/long; weight: None, one number per
+    class, or a class_weight_table.  focal_gamma > 0: the focal loss sum w[t] (1 - p_t)^gamma (-log p_t) / sum w[t]; 0 changes
+    nothing.  label_smoothing in (0, 1]: torch's smoothed loss, with one deviation: a class of weight 0 adds nothing to the
+    smoothing sum even where its -log p is +inf (torch forms 0 * inf = NaN there); 0 changes nothing; together with focal_gamma > 0: ValueError."""
+    weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, logits.device, logits.shape[1], label_smoothing)
+    return _CrossEntropy.apply(logits, target, ignore_index, weight, focal_gamma, label_smoothing)
 
 
 class _MSE(torch.autograd.Function):
@@ -1713,7 +1755,7 @@ class _FusedLosses(torch.autograd.Function):
     its incoming gradient is 1 (TrainStep calls vals[3].backward()); the stored gradients are returned as they are."""
 
     @staticmethod
-    def forward(ctx, sssr, sisr, ft1, ft2, target, org, ignore_index, w1, w2, stage, flag, k, weight=None, gamma=0.0):
+    def forward(ctx, sssr, sisr, ft1, ft2, target, org, ignore_index, w1, w2, stage, flag, k, weight=None, gamma=0.0, eps=0.0):
         want = bool(ctx.needs_input_grad[0])          # forward-only (validation, no_grad): no gradient buffers are written
         logits, ld = pm(sssr)
         _need_gpu(target)
@@ -1733,8 +1775,12 @@ class _FusedLosses(torch.autograd.Function):
             lg = None
         dl = new_cl((N, Cc, H, W), logits) if (want and lg is None) else None      # lg: the producer of the logits forms this gradient in its own backward
         if lg is not None and lg.value is not None and lg.value_key == (target.data_ptr(), int(ignore_index), flag.data_ptr(),
-                                                                        0 if weight is None else weight.data_ptr(), gamma):
+                                                                        0 if weight is None else weight.data_ptr(), eps, gamma):
             scal = lg.value                                             # the producer's forward kernel evaluated the loss (logits_target)
+        elif eps > 0.0:
+            ws = _ws(cquery('dsrl_ce_fused_s_workspace_bytes', P), logits)
+            call('dsrl_ce_fused_s', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(), eps,
+                 None if dl is None else dl.data_ptr(), Cc, scal.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
         elif gamma > 0.0:
             ws = _ws(cquery('dsrl_ce_fused_f_workspace_bytes', P), logits)
             call('dsrl_ce_fused_f', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(), gamma,
@@ -1775,7 +1821,7 @@ class _FusedLosses(torch.autograd.Function):
             ctx.fa = (ft1, ft2, saved, k, fa_out)
         call('dsrl_loss_mix', scal.data_ptr(), mse_ptr, fa_ptr, float(w1), float(w2), flag.data_ptr(), vals.data_ptr(), st)
         if lg is not None:
-            lg.target = target; lg.ignore_index = int(ignore_index); lg.count = scal; lg.ft = None; lg.weight = weight; lg.gamma = gamma; lg.armed = True
+            lg.target = target; lg.ignore_index = int(ignore_index); lg.count = scal; lg.ft = None; lg.weight = weight; lg.gamma = gamma; lg.eps = eps; lg.armed = True
         ctx.lg = lg
         ctx.grads = (dl, da)
         ctx.w2 = float(w2)
@@ -1815,7 +1861,7 @@ class _FusedLosses(torch.autograd.Function):
             if slot is not None and buf is not None and not slot.closed and slot.buf is None:
                 slot.buf = buf
                 out[i] = None
-        return out[0], out[1], d1, d2, None, None, None, None, None, None, None, None, None, None
+        return out[0], out[1], d1, d2, None, None, None, None, None, None, None, None, None, None, None
 
 
 _fused_losses_root_checked = False
@@ -1847,17 +1893,17 @@ def fused_losses_backward(vals):
     torch.autograd.backward([vals], [e3])
 
 
-def fused_losses(outs, target, input_org, ignore_index, w1, w2, stage, flag, subsample_factor=8, weight=None, focal_gamma=0.0):
+def fused_losses(outs, target, input_org, ignore_index, w1, w2, stage, flag, subsample_factor=8, weight=None, focal_gamma=0.0, label_smoothing=0.0):
     """-> 5-float device tensor [CE, w1*MSE, w2*FA, total, NaN flag]; `outs` = DSRL.forward's 4-tuple.  vals[3].backward() is the only
     supported backward (the function is the root of the pass); `flag` is the int32 NaN flag the fused kernels OR into.  weight: per-class CE
     weights (None, one number per class, or a class_weight_table): nn.CrossEntropyLoss(weight=).  focal_gamma > 0 makes the CE term the focal loss
-    (as cross_entropy); 0 changes nothing."""
+    (as cross_entropy); 0 changes nothing.  label_smoothing in (0, 1] makes it torch's label-smoothed loss (as cross_entropy); 0 changes nothing."""
     sssr, sisr, ft1, ft2 = outs
-    weight, focal_gamma = _focal_args(weight, focal_gamma, sssr.device, sssr.shape[1])
+    weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, sssr.device, sssr.shape[1], label_smoothing)
     dummy = _const1(0.0, sssr.device)            # stands in for the outputs a lower stage does not have (a cached constant: no fill launch per step)
     return _FusedLosses.apply(sssr, sisr if stage > 1 else dummy, ft1 if stage > 2 else dummy, ft2 if stage > 2 else dummy, target,
                               input_org if stage > 1 else dummy, int(ignore_index), float(w1), float(w2), int(stage), flag, int(subsample_factor), weight,
-                              focal_gamma)
+                              focal_gamma, label_smoothing)
 
 
 _RED = {'mean': 0, 'sum': 1, 'none': 2}

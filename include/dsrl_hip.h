@@ -482,6 +482,34 @@ int dsrl_convt2x2_bwd_ce_f(const float* x, const float* w, const float* logits, 
                            int ft_stride, float* dx, float* dw, float* dbias /*nullable*/, int N, int H, int W, int Cin, int Cout, void* ws,
                            size_t ws_bytes, dsrl_stream_t stream);
 
+/* Label-smoothed cross entropy: nn.CrossEntropyLoss(weight=, ignore_index=, label_smoothing=eps).  With C classes, nl_ic = (m_i - v_ic) + log s_i,
+ * W = sum_{c < C} w_c and D as above (the same pre-pass, the same bits), over the pixels i whose label is not ignore_index:
+ *     loss  = ((1 - eps) sum_i w[t_i] nl_i,t_i + (eps / C) sum_i sum_{c < C, w_c > 0} w_c nl_ic) / D
+ *     dl_ic = ((1 - eps) w[t_i] (p_ic - [c == t_i]) + (eps / C) (p_ic W - w_c)) / D,   zeros for an ignored pixel
+ * One deviation from torch: a class of weight 0 adds nothing to the smoothing sum even where nl_ic is +inf (torch forms 0 * inf = NaN).  A live pixel
+ * whose target has weight 0 still contributes its smoothing term; D == 0 gives what IEEE division gives.  `eps` must satisfy 0 <= eps <= 1 (a NaN
+ * does not), else DSRL_E_BADARG and nothing is launched or written; eps == 0 runs the _w entry point itself.  Each _s entry point is its _w sibling
+ * with `float eps` after `weights` (all-ones weights for an unweighted smoothed loss): same contracts, flags and workspaces (the _s size queries
+ * are those of the _w siblings), and dsrl_convt2x2_bwd_ce_s is bit-identical to
+ * dsrl_ce_fused_s -> dsrl_pointwise_strided_bwd(accumulate = 1) -> dsrl_convt2x2_bwd.  There is no smoothed focal loss. */
+size_t dsrl_ce_s_workspace_bytes(int64_t P);
+int dsrl_ce_fwd_s(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights /*[256]*/, float eps,
+                  float* loss_out /*[2]*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+int dsrl_ce_bwd_s(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights /*[256]*/, float eps,
+                  const float* loss_out, const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream);
+size_t dsrl_ce_fused_s_workspace_bytes(int64_t P);
+int dsrl_ce_fused_s(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights /*[256]*/, float eps,
+                    float* dlogits /*nullable*/, int lddl, float* loss_out /*[2]*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes,
+                    dsrl_stream_t stream);
+size_t dsrl_convt2x2_fwd_ce_s_workspace_bytes(int N, int H, int W);
+int dsrl_convt2x2_fwd_ce_s(const float* x, const float* w, const float* bias /*nullable*/, float* y, int N, int H, int W, int Cin, int Cout,
+                           const uint8_t* target, int ignore_index, const float* weights /*[256]*/, float eps, float* loss_out,
+                           int* nan_flag /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+int dsrl_convt2x2_bwd_ce_s(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* weights /*[256]*/,
+                           float eps, const float* ce_wsum /*D: loss_out + 1*/, const float* ft_g /*nullable*/, const float* ft_w /*nullable*/,
+                           int ft_stride, float* dx, float* dw, float* dbias /*nullable*/, int N, int H, int W, int Cin, int Cout, void* ws,
+                           size_t ws_bytes, dsrl_stream_t stream);
+
 /* FALoss (models/losses/FALoss.py:8-34). fm1/fm2 are (B,C,H,W) with element strides (sb,sc,sh,sw).
  * reduction: 0 mean, 1 sum, 2 none (out has B*C*n*n floats, n = (W/k)^2).
  * `saved` (>= dsrl_fa_saved_floats) carries S1,S2,sigma,u1,v1 to the backward. */
