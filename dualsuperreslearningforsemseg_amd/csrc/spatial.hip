@@ -224,7 +224,9 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restric
         long long pix = e / C;
         const int wo = (int)(pix % Wo); pix /= Wo;
         const int ho = (int)(pix % Ho); const int n = (int)(pix / Ho);
-        float best = -INFINITY; int bi = 0;
+        // the scan starts at the window's first in-bounds tap (row 1 / column 1 on the top / left border), as torch's does: a window whose
+        // in-bounds values are all -inf records that tap, never a padding position the backward pass would drop
+        float best = -INFINITY; int bi = (ho == 0 ? 3 : 0) + (wo == 0 ? 1 : 0);
         for (int r = 0; r < 3; ++r) {
             const int h = 2 * ho - 1 + r;
             if (h < 0 || h >= H) continue;
@@ -267,7 +269,8 @@ __global__ __launch_bounds__(256) void maxpool_fwd4_kernel(const float* __restri
         const unsigned q = e % C4; unsigned pix = e / C4;
         const int wo = (int)(pix % Wo); pix /= Wo;
         const int ho = (int)(pix % Ho), n = (int)(pix / Ho);
-        float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}; unsigned bi[4] = {0u, 0u, 0u, 0u};
+        const unsigned b0 = (ho == 0 ? 3u : 0u) + (wo == 0 ? 1u : 0u);        // first in-bounds tap, as in the scalar kernel
+        float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}; unsigned bi[4] = {b0, b0, b0, b0};
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             const int h = 2 * ho - 1 + r;

@@ -336,7 +336,9 @@ int dsrl_bilinear_ac_bwd(const float* dy, int lddy, float* dx, int lddx, int N, 
 int dsrl_global_avgpool_fwd(const float* x, int ldx, float* y, int N, int HW, int C, dsrl_stream_t stream);
 int dsrl_global_avgpool_bwd(const float* dy, float* dx, int lddx, int N, int HW, int C, dsrl_stream_t stream);
 /* nn.MaxPool2d(3, stride 2, pad 1) (ResNet101.py:32) */
-/* argmax (nullable in fwd): per output element the winning tap r*3+s (first maximum in scan order), consumed by the backward */
+/* argmax (nullable in fwd): per output element the winning tap r*3+s (first maximum in scan order), consumed by the backward.
+ * torch's scan: it starts at the first in-bounds tap and a tap replaces the best on `v > best || isnan(v)`, so the tap is always an
+ * in-bounds one (an all -inf window: its first in-bounds element) and the last of several NaNs wins. */
 int dsrl_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* argmax, int N, int H, int W, int C, dsrl_stream_t stream);
 int dsrl_maxpool3x3s2_bwd(const uint8_t* argmax, const float* dy, float* dx, int N, int H, int W, int C, dsrl_stream_t stream);
 

@@ -230,9 +230,21 @@ def max_pool3x3s2(x):
     N, C, H, W = x.shape
     Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
     xp = np.pad(x, ((0, 0), (0, 0), (1, 1), (1, 1)), constant_values=-np.inf)
-    wins = np.stack([xp[:, :, r: r + 2 * (Ho - 1) + 1: 2, s: s + 2 * (Wo - 1) + 1: 2] for r in range(3) for s in range(3)], axis=0)
-    arg = wins.argmax(axis=0)
-    return wins.max(axis=0), arg
+    # torch's scan (max_pool2d on the CPU): row-major over the in-bounds taps, starting AT the first of them, a later tap replacing the best on
+    # `v > best or isnan(v)`.  So an all -inf window records its first in-bounds tap (never the padding) and the last of several NaNs wins;
+    # an argmax over the -inf padded window has neither property.
+    hp, wp = 2 * np.arange(Ho)[:, None], 2 * np.arange(Wo)[None, :]
+    best = np.full((N, C, Ho, Wo), -np.inf, dtype=x.dtype)
+    arg = np.full((N, C, Ho, Wo), -1, dtype=np.int64)
+    for t in range(9):
+        r, s = divmod(t, 3)
+        v = xp[:, :, r: r + 2 * (Ho - 1) + 1: 2, s: s + 2 * (Wo - 1) + 1: 2]
+        inb = (hp + r >= 1) & (hp + r <= H) & (wp + s >= 1) & (wp + s <= W)
+        with np.errstate(invalid='ignore'):
+            take = inb & ((arg < 0) | (v > best) | np.isnan(v))
+        best = np.where(take, v, best)
+        arg = np.where(take, t, arg)
+    return best, arg
 
 
 def max_pool3x3s2_bwd(in_hw, arg, dy):
