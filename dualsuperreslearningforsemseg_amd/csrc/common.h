@@ -36,10 +36,33 @@ int bind_stream_device(hipStream_t s);
 bool convt_bwd_dma_supported(const void* x, const void* dy, int W, int Cin, int Cout);
 int convt_bwd_dma_blocks(long long nseg, int cap);
 int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, hipStream_t st);
+
+// Which cross entropy a host call asks for: plain, class-weighted, focal or label-smoothed.  The dsrl_*_w / _f / _s entry points make theirs with
+// weighted() / focal() / smoothed(), and these hold the one normalisation rule: gamma == 0 or eps == 0 IS the weighted form, in every respect
+// (kernels, messages).  Everything below the entry points takes this value and decides by kind.
+struct CeVariant {
+    enum Kind { kPlain, kWeighted, kFocal, kSmoothed };
+    const float* weights = nullptr;     // the 256-float class-weight table; the plain form has none
+    float gamma = 0.f;                  // > 0: kFocal
+    float eps = 0.f;                    // > 0: kSmoothed
+    Kind kind = kPlain;
+    static CeVariant weighted(const float* w) { return CeVariant{w, 0.f, 0.f, kWeighted}; }
+    static CeVariant focal(const float* w, float gamma) { return gamma == 0.f ? weighted(w) : CeVariant{w, gamma, 0.f, kFocal}; }
+    static CeVariant smoothed(const float* w, float eps) { return eps == 0.f ? weighted(w) : CeVariant{w, 0.f, eps, kSmoothed}; }
+    bool plain() const { return kind == kPlain; }
+    bool table_ok() const { return plain() || weights != nullptr; }         // part of every entry point's argument check
+    const char* suffix() const { return plain() ? "" : kind == kWeighted ? "_w" : kind == kFocal ? "_f" : "_s"; }       // of the entry point, for its messages
+};
+// losses.hip, for the ConvTranspose forms in spatial.hip: the pre-pass of every kind but plain (D = sum n_c w_c into d_out, through `ws` of
+// ce_weight_sum_bytes()) and the finalize (plain: loss / pixel count; the others: loss / D, D read from loss_out[1])
+int launch_ce_weight_sum(const unsigned char* target, long long P, int C, int ignore_index, const float* weights, float* d_out, void* ws, hipStream_t st);
+size_t ce_weight_sum_bytes();
+int launch_ce_finalize(CeVariant::Kind kind, const double* part, int nb, float* loss_out, hipStream_t st);
+
+// `count`: the pixel count of the plain form, D of the others
 int launch_convt_bwd_dma_ce(const float* x, const float* w, const float* logits, float* dx, float* part, int N, int H, int W, int nblocks,
                             const unsigned char* target, int ignore_index, const float* count, const float* ft_g, const float* ft_w, int ft_s,
-                            const float* wtab /*null: unweighted; else the 256-float class-weight table and `count` points to D*/,
-                            float gamma /*> 0 (with wtab): focal*/, float eps /*> 0 (with wtab, gamma == 0): label smoothing*/, hipStream_t st);
+                            const CeVariant& v, hipStream_t st);
 
 // The one way the library reads a DSRL_* environment switch (table: DESIGN.md §9).  Read at every call, never cached: tests change switches
 // between calls inside one process.  knob_str: for the one switch whose value is a path (DSRL_PROF_DUMP).

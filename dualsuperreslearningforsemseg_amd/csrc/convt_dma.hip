@@ -392,19 +392,19 @@ int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float*
 }
 int launch_convt_bwd_dma_ce(const float* x, const float* w, const float* logits, float* dx, float* part, int N, int H, int W, int nblocks,
                             const unsigned char* target, int ignore_index, const float* count, const float* ft_g, const float* ft_w, int ft_s,
-                            const float* wtab, float gamma, float eps, hipStream_t st) {
+                            const CeVariant& v, hipStream_t st) {
     ConvtCeArgs ce{};
     ce.target = target; ce.count = count; ce.ft_g = ft_g; ce.ft_w = ft_w; ce.ignore_index = ignore_index; ce.ft_s = ft_s > 0 ? ft_s : 1;
-    ce.ft_shift = -1; ce.wtab = wtab; ce.gamma = gamma; ce.eps = eps;
+    ce.ft_shift = -1; ce.wtab = v.weights; ce.gamma = v.gamma; ce.eps = v.eps;
     for (int b = 0; b < 31; ++b) if (ce.ft_s == (1 << b)) ce.ft_shift = b;
     ce.Hf = (2 * H - 1) / ce.ft_s + 1; ce.Wf = (2 * W - 1) / ce.ft_s + 1;
     const bool w8 = knob("DSRL_CONVT_CE_WAVES", 12) == 8;                  // the transform inside the MFMA waves
     // focal: the 8-wave build whatever DSRL_CONVT_CE_WAVES says.  focal_pixel's log and two divisions beside the 19 terms need 172 VGPRs in the
     // 12-wave build, which has 168 (4 spilled, 20 B of scratch); the 8-wave build has 256 and takes 212
-    if (wtab && gamma > 0.f) return launch_dma<true, false, true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
+    if (v.kind == CeVariant::kFocal) return launch_dma<true, false, true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
     // label smoothing: one wave build, the 8-wave one, as focal has
-    if (wtab && eps > 0.f) return launch_dma<true, false, true, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
-    if (wtab) return w8 ? launch_dma<true, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st)
+    if (v.kind == CeVariant::kSmoothed) return launch_dma<true, false, true, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
+    if (v.kind == CeVariant::kWeighted) return w8 ? launch_dma<true, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st)
                         : launch_dma<true, true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
     if (w8) return launch_dma<true, false>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
     return launch_dma<true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);

@@ -832,29 +832,6 @@ static int loss_blocks(long long work) { return (int)std::max<long long>(1, std:
 }  // namespace dsrl
 using namespace dsrl;
 
-extern "C" size_t dsrl_ce_workspace_bytes(int64_t P) { return (size_t)2 * loss_blocks(P) * sizeof(double); }
-extern "C" int dsrl_ce_fwd(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float* loss_out,
-                           void* ws, size_t ws_bytes, dsrl_stream_t stream) {
-    DSRL_REQUIRE(logits && target && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C, DSRL_E_BADARG, "ce_fwd: bad arguments (C=%d)", C);
-    DSRL_REQUIRE(ws_bytes >= dsrl_ce_workspace_bytes(P), DSRL_E_WORKSPACE, "ce_fwd: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = bind_stream_device(st)) return e;
-    const int nb = loss_blocks(P);
-    hipLaunchKernelGGL(ce_fwd_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index, (double*)ws);
-    if (int e = launch_status("ce_fwd_kernel")) return e;
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, nb, loss_out);
-    return launch_status("ce_finalize_kernel");
-}
-extern "C" int dsrl_ce_bwd(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* loss_out,
-                           const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
-    DSRL_REQUIRE(logits && target && loss_out && grad_out && dlogits && P > 0 && C > 0 && C <= 60 && ld >= C && lddl >= C, DSRL_E_BADARG, "ce_bwd: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = bind_stream_device(st)) return e;
-    hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)std::min<long long>(ceil_div(P, 256), 8192)), dim3(256), (size_t)256 * C * sizeof(float), st,
-                       logits, ld, target, (long long)P, C, ignore_index, loss_out, grad_out, dlogits, lddl);
-    return launch_status("ce_bwd_kernel");
-}
-
 extern "C" size_t dsrl_mse_workspace_bytes(int64_t n) { return (size_t)loss_blocks(n / 4 + 1) * sizeof(double); }
 extern "C" int dsrl_mse_fwd(const float* a, const float* b, int64_t n, float* loss_out, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     DSRL_REQUIRE(a && b && loss_out && ws && n > 0, DSRL_E_BADARG, "mse_fwd: bad arguments");
@@ -875,46 +852,196 @@ extern "C" int dsrl_mse_bwd(const float* a, const float* b, int64_t n, const flo
     return launch_status("mse_bwd_kernel");
 }
 
-int launch_ce_finalize(const double* part, int nb, float* loss_out, hipStream_t st) {       // for dsrl_convt2x2_fwd_ce (spatial.hip)
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, part, nb, loss_out);
-    return launch_status("ce_finalize_kernel");
-}
-extern "C" size_t dsrl_ce_fused_workspace_bytes(int64_t P) { return (size_t)2 * loss_blocks(P) * sizeof(double) + kCountBlocks * sizeof(unsigned); }
-extern "C" int dsrl_ce_fused(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float* dlogits, int lddl,
-                             float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
-    DSRL_REQUIRE(logits && target && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C && (!dlogits || lddl >= C), DSRL_E_BADARG, "ce_fused: bad arguments (C=%d)", C);
-    DSRL_REQUIRE(ws_bytes >= dsrl_ce_fused_workspace_bytes(P) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fused: workspace too small or misaligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = bind_stream_device(st)) return e;
-    const int nb = loss_blocks(P);
-    double* part = (double*)ws;
-    unsigned* cnt = (unsigned*)(part + 2 * nb);
-    hipLaunchKernelGGL(count_valid_kernel, dim3(kCountBlocks), dim3(256), 0, st, target, (long long)P, ignore_index, cnt);
-    if (int e = launch_status("count_valid_kernel")) return e;
-    const int vec_in = (ld == C && ((uintptr_t)logits % 16) == 0) ? 1 : 0;          // 256 * C floats per tile: every tile starts 16-byte aligned
-    const int vec_out = (dlogits && lddl == C && ((uintptr_t)dlogits % 16) == 0) ? 1 : 0;
-    hipLaunchKernelGGL(ce_fused_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index,
-                       (const unsigned*)cnt, dlogits, lddl, part, nan_flag, vec_in, vec_out);
-    if (int e = launch_status("ce_fused_kernel")) return e;
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nb, loss_out);
-    return launch_status("ce_finalize_kernel");
-}
-// ---- class-weighted cross entropy: nn.CrossEntropyLoss(weight, ignore_index).  Every weighted entry point starts with the same pre-pass (per-block
-// integer histograms of the labels, then D in one block), so D is the same bits in all of them.
+// ---- cross entropy: nn.CrossEntropyLoss(weight, ignore_index, label_smoothing=) and the focal loss.  Four kinds (CeVariant, common.h): plain,
+// class-weighted, focal = weighted with one more per-pixel factor (focal_pixel), label-smoothed = weighted plus the smoothing term over all
+// classes (smooth_pixel).  The twelve entry points check their gamma or eps, make their CeVariant and hand over to ONE host body per family
+// (ce_fwd_any, ce_bwd_any, ce_fused_any): every check, workspace layout and launch decision is written once.
+// Every kind but plain starts with the same pre-pass (per-block integer histograms of the labels, then D = sum n_c w_c in one block, left in
+// loss_out[1]), so D is the same bits in all of them, and ends with the finalize that divides by D.
 static int hist_blocks(long long P) { return (int)std::max<long long>(1, std::min<long long>(kHistBlocks, ceil_div(P, 4096))); }
 static constexpr size_t kWeightSumBytes = (size_t)kHistBlocks * 256 * sizeof(unsigned);
-int launch_ce_weight_sum(const unsigned char* target, long long P, int C, int ignore_index, const float* weights, float* d_out, void* ws, hipStream_t st) {
+size_t dsrl::ce_weight_sum_bytes() { return kWeightSumBytes; }
+int dsrl::launch_ce_weight_sum(const unsigned char* target, long long P, int C, int ignore_index, const float* weights, float* d_out, void* ws, hipStream_t st) {
     const int nb = hist_blocks(P);
     hipLaunchKernelGGL(class_hist_kernel, dim3(nb), dim3(256), 0, st, target, P, (const unsigned char*)nullptr, (unsigned long long*)nullptr, (unsigned*)ws);
     if (int e = launch_status("class_hist_kernel")) return e;
     hipLaunchKernelGGL(ce_weight_sum_kernel, dim3(1), dim3(256), 0, st, (const unsigned*)ws, nb, C, ignore_index, weights, d_out);
     return launch_status("ce_weight_sum_kernel");
 }
-int launch_ce_finalize_w(const double* part, int nb, float* loss_out, hipStream_t st) {      // for dsrl_convt2x2_fwd_ce_w (spatial.hip)
+int dsrl::launch_ce_finalize(CeVariant::Kind kind, const double* part, int nb, float* loss_out, hipStream_t st) {
+    if (kind == CeVariant::kPlain) {
+        hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, part, nb, loss_out);
+        return launch_status("ce_finalize_kernel");
+    }
     hipLaunchKernelGGL(ce_finalize_w_kernel, dim3(1), dim3(256), 0, st, part, nb, loss_out);
     return launch_status("ce_finalize_w_kernel");
 }
-size_t ce_weight_sum_bytes() { return kWeightSumBytes; }
+// workspaces: two doubles per loss block, then the histograms of the pre-pass (every kind but plain) or, for the plain fused pass, the pixel
+// counts of count_valid_kernel
+static size_t ce_ws_bytes(int64_t P, bool plain) { return (size_t)2 * loss_blocks(P) * sizeof(double) + (plain ? 0 : kWeightSumBytes); }
+static size_t ce_fused_ws_bytes(int64_t P, bool plain) {
+    return (size_t)2 * loss_blocks(P) * sizeof(double) + (plain ? kCountBlocks * sizeof(unsigned) : kWeightSumBytes);
+}
+extern "C" size_t dsrl_ce_workspace_bytes(int64_t P) { return ce_ws_bytes(P, true); }
+extern "C" size_t dsrl_ce_w_workspace_bytes(int64_t P) { return ce_ws_bytes(P, false); }
+extern "C" size_t dsrl_ce_f_workspace_bytes(int64_t P) { return ce_ws_bytes(P, false); }
+extern "C" size_t dsrl_ce_s_workspace_bytes(int64_t P) { return ce_ws_bytes(P, false); }
+extern "C" size_t dsrl_ce_fused_workspace_bytes(int64_t P) { return ce_fused_ws_bytes(P, true); }
+extern "C" size_t dsrl_ce_fused_w_workspace_bytes(int64_t P) { return ce_fused_ws_bytes(P, false); }
+extern "C" size_t dsrl_ce_fused_f_workspace_bytes(int64_t P) { return ce_fused_ws_bytes(P, false); }
+extern "C" size_t dsrl_ce_fused_s_workspace_bytes(int64_t P) { return ce_fused_ws_bytes(P, false); }
+
+static int ce_fwd_any(const CeVariant& v, const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float* loss_out,
+                      void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    const char* sfx = v.suffix();
+    DSRL_REQUIRE(logits && target && v.table_ok() && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C, DSRL_E_BADARG,
+                 "ce_fwd%s: bad arguments (C=%d)", sfx, C);
+    if (v.plain()) DSRL_REQUIRE(ws_bytes >= ce_ws_bytes(P, true), DSRL_E_WORKSPACE, "ce_fwd: workspace too small");
+    else DSRL_REQUIRE(ws_bytes >= ce_ws_bytes(P, false) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fwd%s: workspace too small or misaligned", sfx);
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    const int nb = loss_blocks(P);
+    double* part = (double*)ws;
+    if (!v.plain())
+        if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, v.weights, loss_out + 1, part + 2 * nb, st)) return e;
+    const dim3 grid(nb), block(256);
+    const size_t lds = (size_t)256 * C * sizeof(float);
+    switch (v.kind) {
+    case CeVariant::kPlain: hipLaunchKernelGGL(ce_fwd_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, part); break;
+    case CeVariant::kWeighted: hipLaunchKernelGGL(ce_fwd_w_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, part); break;
+    case CeVariant::kFocal: hipLaunchKernelGGL(ce_fwd_f_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, v.gamma, part); break;
+    case CeVariant::kSmoothed: hipLaunchKernelGGL(ce_fwd_s_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, v.eps, part); break;
+    }
+    static const char* const kernel[] = {"ce_fwd_kernel", "ce_fwd_w_kernel", "ce_fwd_f_kernel", "ce_fwd_s_kernel"};
+    if (int e = launch_status(kernel[v.kind])) return e;
+    return launch_ce_finalize(v.kind, part, nb, loss_out, st);
+}
+static int ce_bwd_any(const CeVariant& v, const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* loss_out,
+                      const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
+    DSRL_REQUIRE(logits && target && v.table_ok() && loss_out && grad_out && dlogits && P > 0 && C > 0 && C <= 60 && ld >= C && lddl >= C, DSRL_E_BADARG,
+                 "ce_bwd%s: bad arguments", v.suffix());
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    const dim3 grid((unsigned)std::min<long long>(ceil_div(P, 256), 8192)), block(256);
+    const size_t lds = (size_t)256 * C * sizeof(float);
+    switch (v.kind) {
+    case CeVariant::kPlain:
+        hipLaunchKernelGGL(ce_bwd_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, loss_out, grad_out, dlogits, lddl);
+        break;
+    case CeVariant::kWeighted:
+        hipLaunchKernelGGL(ce_bwd_w_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, loss_out, grad_out, dlogits, lddl);
+        break;
+    case CeVariant::kFocal:
+        hipLaunchKernelGGL(ce_bwd_f_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, v.gamma, loss_out, grad_out,
+                           dlogits, lddl);
+        break;
+    case CeVariant::kSmoothed:
+        hipLaunchKernelGGL(ce_bwd_s_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, v.eps, loss_out, grad_out,
+                           dlogits, lddl);
+        break;
+    }
+    static const char* const kernel[] = {"ce_bwd_kernel", "ce_bwd_w_kernel", "ce_bwd_f_kernel", "ce_bwd_s_kernel"};
+    return launch_status(kernel[v.kind]);
+}
+static int ce_fused_any(const CeVariant& v, const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float* dlogits, int lddl,
+                        float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    const char* sfx = v.suffix();
+    DSRL_REQUIRE(logits && target && v.table_ok() && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C && (!dlogits || lddl >= C), DSRL_E_BADARG,
+                 "ce_fused%s: bad arguments (C=%d)", sfx, C);
+    DSRL_REQUIRE(ws_bytes >= ce_fused_ws_bytes(P, v.plain()) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fused%s: workspace too small or misaligned", sfx);
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    const int nb = loss_blocks(P);
+    double* part = (double*)ws;
+    unsigned* cnt = (unsigned*)(part + 2 * nb);         // plain: the pixel counts; the others: the histograms, and D lands in loss_out[1]
+    const float* wsum = loss_out + 1;
+    if (v.plain()) {
+        hipLaunchKernelGGL(count_valid_kernel, dim3(kCountBlocks), dim3(256), 0, st, target, (long long)P, ignore_index, cnt);
+        if (int e = launch_status("count_valid_kernel")) return e;
+    } else if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, v.weights, loss_out + 1, cnt, st)) return e;
+    const int vec_in = (ld == C && ((uintptr_t)logits % 16) == 0) ? 1 : 0;          // 256 * C floats per tile: every tile starts 16-byte aligned
+    const int vec_out = (dlogits && lddl == C && ((uintptr_t)dlogits % 16) == 0) ? 1 : 0;
+    const dim3 grid(nb), block(256);
+    const size_t lds = (size_t)256 * C * sizeof(float);
+    switch (v.kind) {
+    case CeVariant::kPlain:
+        hipLaunchKernelGGL(ce_fused_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, (const unsigned*)cnt, dlogits, lddl, part,
+                           nan_flag, vec_in, vec_out);
+        break;
+    case CeVariant::kWeighted:
+        hipLaunchKernelGGL(ce_fused_w_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, wsum, dlogits, lddl, part,
+                           nan_flag, vec_in, vec_out);
+        break;
+    case CeVariant::kFocal:
+        hipLaunchKernelGGL(ce_fused_f_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, v.gamma, wsum, dlogits, lddl,
+                           part, nan_flag, vec_in, vec_out);
+        break;
+    case CeVariant::kSmoothed:
+        hipLaunchKernelGGL(ce_fused_s_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, v.eps, wsum, dlogits, lddl,
+                           part, nan_flag, vec_in, vec_out);
+        break;
+    }
+    static const char* const kernel[] = {"ce_fused_kernel", "ce_fused_w_kernel", "ce_fused_f_kernel", "ce_fused_s_kernel"};
+    if (int e = launch_status(kernel[v.kind])) return e;
+    return launch_ce_finalize(v.kind, part, nb, loss_out, st);
+}
+
+// the entry points: gamma or eps first (DSRL_FOCAL_GAMMA, DSRL_LABEL_SMOOTHING), then everything else in the shared body
+extern "C" int dsrl_ce_fwd(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float* loss_out,
+                           void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    return ce_fwd_any(CeVariant{}, logits, ld, target, P, C, ignore_index, loss_out, ws, ws_bytes, stream);
+}
+extern "C" int dsrl_ce_fwd_w(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float* loss_out,
+                             void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    return ce_fwd_any(CeVariant::weighted(weights), logits, ld, target, P, C, ignore_index, loss_out, ws, ws_bytes, stream);
+}
+extern "C" int dsrl_ce_fwd_f(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float gamma,
+                             float* loss_out, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_FOCAL_GAMMA(gamma, "ce_fwd_f");
+    return ce_fwd_any(CeVariant::focal(weights, gamma), logits, ld, target, P, C, ignore_index, loss_out, ws, ws_bytes, stream);
+}
+extern "C" int dsrl_ce_fwd_s(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float eps,
+                             float* loss_out, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_LABEL_SMOOTHING(eps, "ce_fwd_s");
+    return ce_fwd_any(CeVariant::smoothed(weights, eps), logits, ld, target, P, C, ignore_index, loss_out, ws, ws_bytes, stream);
+}
+extern "C" int dsrl_ce_bwd(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* loss_out,
+                           const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
+    return ce_bwd_any(CeVariant{}, logits, ld, target, P, C, ignore_index, loss_out, grad_out, dlogits, lddl, stream);
+}
+extern "C" int dsrl_ce_bwd_w(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, const float* loss_out,
+                             const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
+    return ce_bwd_any(CeVariant::weighted(weights), logits, ld, target, P, C, ignore_index, loss_out, grad_out, dlogits, lddl, stream);
+}
+extern "C" int dsrl_ce_bwd_f(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float gamma,
+                             const float* loss_out, const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
+    DSRL_FOCAL_GAMMA(gamma, "ce_bwd_f");
+    return ce_bwd_any(CeVariant::focal(weights, gamma), logits, ld, target, P, C, ignore_index, loss_out, grad_out, dlogits, lddl, stream);
+}
+extern "C" int dsrl_ce_bwd_s(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float eps,
+                             const float* loss_out, const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
+    DSRL_LABEL_SMOOTHING(eps, "ce_bwd_s");
+    return ce_bwd_any(CeVariant::smoothed(weights, eps), logits, ld, target, P, C, ignore_index, loss_out, grad_out, dlogits, lddl, stream);
+}
+extern "C" int dsrl_ce_fused(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float* dlogits, int lddl,
+                             float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    return ce_fused_any(CeVariant{}, logits, ld, target, P, C, ignore_index, dlogits, lddl, loss_out, nan_flag, ws, ws_bytes, stream);
+}
+extern "C" int dsrl_ce_fused_w(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights,
+                               float* dlogits, int lddl, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    return ce_fused_any(CeVariant::weighted(weights), logits, ld, target, P, C, ignore_index, dlogits, lddl, loss_out, nan_flag, ws, ws_bytes, stream);
+}
+extern "C" int dsrl_ce_fused_f(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float gamma,
+                               float* dlogits, int lddl, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_FOCAL_GAMMA(gamma, "ce_fused_f");
+    return ce_fused_any(CeVariant::focal(weights, gamma), logits, ld, target, P, C, ignore_index, dlogits, lddl, loss_out, nan_flag, ws, ws_bytes, stream);
+}
+extern "C" int dsrl_ce_fused_s(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float eps,
+                               float* dlogits, int lddl, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_LABEL_SMOOTHING(eps, "ce_fused_s");
+    return ce_fused_any(CeVariant::smoothed(weights, eps), logits, ld, target, P, C, ignore_index, dlogits, lddl, loss_out, nan_flag, ws, ws_bytes, stream);
+}
+
 extern "C" int dsrl_class_histogram(const uint8_t* labels, int64_t P, const uint8_t* lut, unsigned long long* counts, dsrl_stream_t stream) {
     DSRL_REQUIRE(labels && counts && P > 0, DSRL_E_BADARG, "class_histogram: bad arguments");
     hipStream_t st = (hipStream_t)stream;
@@ -930,150 +1057,6 @@ extern "C" int dsrl_ce_weight_sum(const uint8_t* target, int64_t P, int C, int i
     hipStream_t st = (hipStream_t)stream;
     if (int e = bind_stream_device(st)) return e;
     return launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, d_out, ws, st);
-}
-extern "C" size_t dsrl_ce_w_workspace_bytes(int64_t P) { return dsrl_ce_workspace_bytes(P) + kWeightSumBytes; }
-extern "C" int dsrl_ce_fwd_w(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float* loss_out,
-                             void* ws, size_t ws_bytes, dsrl_stream_t stream) {
-    DSRL_REQUIRE(logits && target && weights && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C, DSRL_E_BADARG, "ce_fwd_w: bad arguments (C=%d)", C);
-    DSRL_REQUIRE(ws_bytes >= dsrl_ce_w_workspace_bytes(P) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fwd_w: workspace too small or misaligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = bind_stream_device(st)) return e;
-    const int nb = loss_blocks(P);
-    double* part = (double*)ws;
-    if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, loss_out + 1, part + 2 * nb, st)) return e;
-    hipLaunchKernelGGL(ce_fwd_w_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index, weights, part);
-    if (int e = launch_status("ce_fwd_w_kernel")) return e;
-    return launch_ce_finalize_w(part, nb, loss_out, st);
-}
-extern "C" int dsrl_ce_bwd_w(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, const float* loss_out,
-                             const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
-    DSRL_REQUIRE(logits && target && weights && loss_out && grad_out && dlogits && P > 0 && C > 0 && C <= 60 && ld >= C && lddl >= C, DSRL_E_BADARG,
-                 "ce_bwd_w: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = bind_stream_device(st)) return e;
-    hipLaunchKernelGGL(ce_bwd_w_kernel, dim3((unsigned)std::min<long long>(ceil_div(P, 256), 8192)), dim3(256), (size_t)256 * C * sizeof(float), st,
-                       logits, ld, target, (long long)P, C, ignore_index, weights, loss_out, grad_out, dlogits, lddl);
-    return launch_status("ce_bwd_w_kernel");
-}
-extern "C" size_t dsrl_ce_fused_w_workspace_bytes(int64_t P) { return (size_t)2 * loss_blocks(P) * sizeof(double) + kWeightSumBytes; }
-extern "C" int dsrl_ce_fused_w(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights,
-                               float* dlogits, int lddl, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
-    DSRL_REQUIRE(logits && target && weights && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C && (!dlogits || lddl >= C), DSRL_E_BADARG,
-                 "ce_fused_w: bad arguments (C=%d)", C);
-    DSRL_REQUIRE(ws_bytes >= dsrl_ce_fused_w_workspace_bytes(P) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fused_w: workspace too small or misaligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = bind_stream_device(st)) return e;
-    const int nb = loss_blocks(P);
-    double* part = (double*)ws;
-    if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, loss_out + 1, part + 2 * nb, st)) return e;
-    const int vec_in = (ld == C && ((uintptr_t)logits % 16) == 0) ? 1 : 0;
-    const int vec_out = (dlogits && lddl == C && ((uintptr_t)dlogits % 16) == 0) ? 1 : 0;
-    hipLaunchKernelGGL(ce_fused_w_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index,
-                       weights, (const float*)(loss_out + 1), dlogits, lddl, part, nan_flag, vec_in, vec_out);
-    if (int e = launch_status("ce_fused_w_kernel")) return e;
-    return launch_ce_finalize_w(part, nb, loss_out, st);
-}
-// ---- focal cross entropy: the weighted entry points with one more per-pixel factor (focal_pixel, common.h).  Same pre-pass, same D, same workspaces.
-// gamma == 0 is the weighted loss itself and goes to the _w entry point: no focal kernel runs with it.
-extern "C" size_t dsrl_ce_f_workspace_bytes(int64_t P) { return dsrl_ce_w_workspace_bytes(P); }
-extern "C" int dsrl_ce_fwd_f(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float gamma,
-                             float* loss_out, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
-    DSRL_FOCAL_GAMMA(gamma, "ce_fwd_f");
-    if (gamma == 0.f) return dsrl_ce_fwd_w(logits, ld, target, P, C, ignore_index, weights, loss_out, ws, ws_bytes, stream);
-    DSRL_REQUIRE(logits && target && weights && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C, DSRL_E_BADARG, "ce_fwd_f: bad arguments (C=%d)", C);
-    DSRL_REQUIRE(ws_bytes >= dsrl_ce_f_workspace_bytes(P) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fwd_f: workspace too small or misaligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = bind_stream_device(st)) return e;
-    const int nb = loss_blocks(P);
-    double* part = (double*)ws;
-    if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, loss_out + 1, part + 2 * nb, st)) return e;
-    hipLaunchKernelGGL(ce_fwd_f_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index, weights,
-                       gamma, part);
-    if (int e = launch_status("ce_fwd_f_kernel")) return e;
-    return launch_ce_finalize_w(part, nb, loss_out, st);
-}
-extern "C" int dsrl_ce_bwd_f(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float gamma,
-                             const float* loss_out, const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
-    DSRL_FOCAL_GAMMA(gamma, "ce_bwd_f");
-    if (gamma == 0.f) return dsrl_ce_bwd_w(logits, ld, target, P, C, ignore_index, weights, loss_out, grad_out, dlogits, lddl, stream);
-    DSRL_REQUIRE(logits && target && weights && loss_out && grad_out && dlogits && P > 0 && C > 0 && C <= 60 && ld >= C && lddl >= C, DSRL_E_BADARG,
-                 "ce_bwd_f: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = bind_stream_device(st)) return e;
-    hipLaunchKernelGGL(ce_bwd_f_kernel, dim3((unsigned)std::min<long long>(ceil_div(P, 256), 8192)), dim3(256), (size_t)256 * C * sizeof(float), st,
-                       logits, ld, target, (long long)P, C, ignore_index, weights, gamma, loss_out, grad_out, dlogits, lddl);
-    return launch_status("ce_bwd_f_kernel");
-}
-extern "C" size_t dsrl_ce_fused_f_workspace_bytes(int64_t P) { return dsrl_ce_fused_w_workspace_bytes(P); }
-extern "C" int dsrl_ce_fused_f(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float gamma,
-                               float* dlogits, int lddl, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
-    DSRL_FOCAL_GAMMA(gamma, "ce_fused_f");
-    if (gamma == 0.f) return dsrl_ce_fused_w(logits, ld, target, P, C, ignore_index, weights, dlogits, lddl, loss_out, nan_flag, ws, ws_bytes, stream);
-    DSRL_REQUIRE(logits && target && weights && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C && (!dlogits || lddl >= C), DSRL_E_BADARG,
-                 "ce_fused_f: bad arguments (C=%d)", C);
-    DSRL_REQUIRE(ws_bytes >= dsrl_ce_fused_f_workspace_bytes(P) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fused_f: workspace too small or misaligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = bind_stream_device(st)) return e;
-    const int nb = loss_blocks(P);
-    double* part = (double*)ws;
-    if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, loss_out + 1, part + 2 * nb, st)) return e;
-    const int vec_in = (ld == C && ((uintptr_t)logits % 16) == 0) ? 1 : 0;
-    const int vec_out = (dlogits && lddl == C && ((uintptr_t)dlogits % 16) == 0) ? 1 : 0;
-    hipLaunchKernelGGL(ce_fused_f_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index,
-                       weights, gamma, (const float*)(loss_out + 1), dlogits, lddl, part, nan_flag, vec_in, vec_out);
-    if (int e = launch_status("ce_fused_f_kernel")) return e;
-    return launch_ce_finalize_w(part, nb, loss_out, st);
-}
-// ---- label-smoothed cross entropy: the weighted entry points plus the smoothing term over all classes (smooth_pixel, common.h).  Same pre-pass, same D,
-// same workspaces.  eps == 0 is the weighted loss itself and goes to the _w entry point: no smoothing kernel runs with it.
-extern "C" size_t dsrl_ce_s_workspace_bytes(int64_t P) { return dsrl_ce_w_workspace_bytes(P); }
-extern "C" int dsrl_ce_fwd_s(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float eps,
-                             float* loss_out, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
-    DSRL_LABEL_SMOOTHING(eps, "ce_fwd_s");
-    if (eps == 0.f) return dsrl_ce_fwd_w(logits, ld, target, P, C, ignore_index, weights, loss_out, ws, ws_bytes, stream);
-    DSRL_REQUIRE(logits && target && weights && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C, DSRL_E_BADARG, "ce_fwd_s: bad arguments (C=%d)", C);
-    DSRL_REQUIRE(ws_bytes >= dsrl_ce_s_workspace_bytes(P) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fwd_s: workspace too small or misaligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = bind_stream_device(st)) return e;
-    const int nb = loss_blocks(P);
-    double* part = (double*)ws;
-    if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, loss_out + 1, part + 2 * nb, st)) return e;
-    hipLaunchKernelGGL(ce_fwd_s_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index, weights,
-                       eps, part);
-    if (int e = launch_status("ce_fwd_s_kernel")) return e;
-    return launch_ce_finalize_w(part, nb, loss_out, st);
-}
-extern "C" int dsrl_ce_bwd_s(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float eps,
-                             const float* loss_out, const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
-    DSRL_LABEL_SMOOTHING(eps, "ce_bwd_s");
-    if (eps == 0.f) return dsrl_ce_bwd_w(logits, ld, target, P, C, ignore_index, weights, loss_out, grad_out, dlogits, lddl, stream);
-    DSRL_REQUIRE(logits && target && weights && loss_out && grad_out && dlogits && P > 0 && C > 0 && C <= 60 && ld >= C && lddl >= C, DSRL_E_BADARG,
-                 "ce_bwd_s: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = bind_stream_device(st)) return e;
-    hipLaunchKernelGGL(ce_bwd_s_kernel, dim3((unsigned)std::min<long long>(ceil_div(P, 256), 8192)), dim3(256), (size_t)256 * C * sizeof(float), st,
-                       logits, ld, target, (long long)P, C, ignore_index, weights, eps, loss_out, grad_out, dlogits, lddl);
-    return launch_status("ce_bwd_s_kernel");
-}
-extern "C" size_t dsrl_ce_fused_s_workspace_bytes(int64_t P) { return dsrl_ce_fused_w_workspace_bytes(P); }
-extern "C" int dsrl_ce_fused_s(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, float eps,
-                               float* dlogits, int lddl, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
-    DSRL_LABEL_SMOOTHING(eps, "ce_fused_s");
-    if (eps == 0.f) return dsrl_ce_fused_w(logits, ld, target, P, C, ignore_index, weights, dlogits, lddl, loss_out, nan_flag, ws, ws_bytes, stream);
-    DSRL_REQUIRE(logits && target && weights && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C && (!dlogits || lddl >= C), DSRL_E_BADARG,
-                 "ce_fused_s: bad arguments (C=%d)", C);
-    DSRL_REQUIRE(ws_bytes >= dsrl_ce_fused_s_workspace_bytes(P) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fused_s: workspace too small or misaligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (int e = bind_stream_device(st)) return e;
-    const int nb = loss_blocks(P);
-    double* part = (double*)ws;
-    if (int e = launch_ce_weight_sum(target, (long long)P, C, ignore_index, weights, loss_out + 1, part + 2 * nb, st)) return e;
-    const int vec_in = (ld == C && ((uintptr_t)logits % 16) == 0) ? 1 : 0;
-    const int vec_out = (dlogits && lddl == C && ((uintptr_t)dlogits % 16) == 0) ? 1 : 0;
-    hipLaunchKernelGGL(ce_fused_s_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index,
-                       weights, eps, (const float*)(loss_out + 1), dlogits, lddl, part, nan_flag, vec_in, vec_out);
-    if (int e = launch_status("ce_fused_s_kernel")) return e;
-    return launch_ce_finalize_w(part, nb, loss_out, st);
 }
 extern "C" int dsrl_mse_fused(const float* a, const float* b, int64_t n, float grad_scale, float* da, float* loss_out, int* nan_flag,
                               void* ws, size_t ws_bytes, dsrl_stream_t stream) {

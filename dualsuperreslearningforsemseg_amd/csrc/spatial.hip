@@ -1267,8 +1267,6 @@ extern "C" int dsrl_convt2x2_fwd(const float* x, const float* w, const float* bi
     set_error("convt2x2_fwd: channel counts %d->%d not instantiated (19->19, 8->8)", Cin, Cout);
     return DSRL_E_UNSUPPORTED;
 }
-// ce_finalize_kernel lives in losses.hip
-int launch_ce_finalize(const double* part, int nb, float* loss_out, hipStream_t st);
 extern "C" int dsrl_convt2x2_fwd_ce_supported(const float* x, const float* y, int N, int H, int W, int Cin, int Cout) {
     if (!knob("DSRL_CONVT_CE", 1) || !knob("DSRL_CONVT_MFMA", 1)) return 0;
     return (x && y && N > 0 && H > 0 && W > 0 && Cin == 19 && Cout == 19 && W % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 &&
@@ -1277,80 +1275,59 @@ extern "C" int dsrl_convt2x2_fwd_ce_supported(const float* x, const float* y, in
 extern "C" size_t dsrl_convt2x2_fwd_ce_workspace_bytes(int N, int H, int W) {
     return (size_t)std::min<long long>((long long)N * H * ceil_div(W, 128), convt_block_cap(4 * 512)) * 2 * sizeof(double);
 }
-extern "C" int dsrl_convt2x2_fwd_ce(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
-                                    const uint8_t* target, int ignore_index, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
-    DSRL_PROLOGUE(x && w && y && target && loss_out && ws && N > 0 && H > 0 && W > 0 && ((uintptr_t)ws % 8) == 0, "convt2x2_fwd_ce")
+// every kind but plain: plus the histograms of the pre-pass that leaves D in loss_out[1] (losses.hip; its finalize divides by D)
+extern "C" size_t dsrl_convt2x2_fwd_ce_w_workspace_bytes(int N, int H, int W) { return dsrl_convt2x2_fwd_ce_workspace_bytes(N, H, W) + ce_weight_sum_bytes(); }
+extern "C" size_t dsrl_convt2x2_fwd_ce_f_workspace_bytes(int N, int H, int W) { return dsrl_convt2x2_fwd_ce_w_workspace_bytes(N, H, W); }
+extern "C" size_t dsrl_convt2x2_fwd_ce_s_workspace_bytes(int N, int H, int W) { return dsrl_convt2x2_fwd_ce_w_workspace_bytes(N, H, W); }
+// the one host body of dsrl_convt2x2_fwd_ce, _w, _f and _s (CeVariant, common.h: focal and smoothed are the weighted form plus gamma or eps)
+static int convt_fwd_ce_any(const CeVariant& v, const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                            const uint8_t* target, int ignore_index, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    const char* sfx = v.suffix();
+    DSRL_REQUIRE(x && w && y && target && v.table_ok() && loss_out && ws && N > 0 && H > 0 && W > 0 && ((uintptr_t)ws % 8) == 0, DSRL_E_BADARG,
+                 "convt2x2_fwd_ce%s: bad arguments", sfx);
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
     DSRL_REQUIRE(dsrl_convt2x2_fwd_ce_supported(x, y, N, H, W, Cin, Cout), DSRL_E_UNSUPPORTED,
-                 "convt2x2_fwd_ce: needs 19 -> 19 channels, W %% 4 == 0, 16-byte aligned tensors (got %d -> %d, W = %d) and DSRL_CONVT_MFMA / DSRL_CONVT_CE not 0", Cin, Cout, W);
-    DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_fwd_ce_workspace_bytes(N, H, W), DSRL_E_WORKSPACE, "convt2x2_fwd_ce: workspace too small");
+                 "convt2x2_fwd_ce%s: needs 19 -> 19 channels, W %% 4 == 0, 16-byte aligned tensors (got %d -> %d, W = %d) and DSRL_CONVT_MFMA / DSRL_CONVT_CE not 0",
+                 sfx, Cin, Cout, W);
+    DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_fwd_ce_workspace_bytes(N, H, W) + (v.plain() ? 0 : ce_weight_sum_bytes()), DSRL_E_WORKSPACE,
+                 "convt2x2_fwd_ce%s: workspace too small", sfx);
     const int nseg_per_row = (int)ceil_div(W, 128);
     const long long nseg = (long long)N * H * nseg_per_row;
     const int nb = (int)std::min<long long>(nseg, convt_block_cap(4 * 512));
-    ConvtFwdCe ce{target, (double*)ws, nan_flag, ignore_index, nullptr, 0.f, 0.f};
-    hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true>), dim3(nb), dim3(256), 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce);
+    if (!v.plain())
+        if (int e = launch_ce_weight_sum(target, (long long)N * 4 * H * W, Cout, ignore_index, v.weights, loss_out + 1, (double*)ws + 2 * nb, st)) return e;
+    ConvtFwdCe ce{target, (double*)ws, nan_flag, ignore_index, v.weights, v.gamma, v.eps};
+    const dim3 grid(nb), block(256);
+    switch (v.kind) {
+    case CeVariant::kPlain: hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true>), grid, block, 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce); break;
+    case CeVariant::kWeighted: hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true, true>), grid, block, 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce); break;
+    case CeVariant::kFocal: hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true, true, true>), grid, block, 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce); break;
+    case CeVariant::kSmoothed: hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true, true, false, true>), grid, block, 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce); break;
+    }
     if (int e = launch_status("convt2x2_fwd_mfma_kernel")) return e;
-    return launch_ce_finalize((const double*)ws, nb, loss_out, st);
+    return launch_ce_finalize(v.kind, (const double*)ws, nb, loss_out, st);
 }
-// the weighted forms (losses.hip holds the pre-pass that leaves D in loss_out[1] and the finalize that divides by it)
-int launch_ce_weight_sum(const unsigned char* target, long long P, int C, int ignore_index, const float* weights, float* d_out, void* ws, hipStream_t st);
-int launch_ce_finalize_w(const double* part, int nb, float* loss_out, hipStream_t st);
-size_t ce_weight_sum_bytes();
-extern "C" size_t dsrl_convt2x2_fwd_ce_w_workspace_bytes(int N, int H, int W) { return dsrl_convt2x2_fwd_ce_workspace_bytes(N, H, W) + ce_weight_sum_bytes(); }
+extern "C" int dsrl_convt2x2_fwd_ce(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                                    const uint8_t* target, int ignore_index, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    return convt_fwd_ce_any(CeVariant{}, x, w, bias, y, N, H, W, Cin, Cout, target, ignore_index, loss_out, nan_flag, ws, ws_bytes, stream);
+}
 extern "C" int dsrl_convt2x2_fwd_ce_w(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
                                       const uint8_t* target, int ignore_index, const float* weights, float* loss_out, int* nan_flag,
                                       void* ws, size_t ws_bytes, dsrl_stream_t stream) {
-    DSRL_PROLOGUE(x && w && y && target && weights && loss_out && ws && N > 0 && H > 0 && W > 0 && ((uintptr_t)ws % 8) == 0, "convt2x2_fwd_ce_w")
-    DSRL_REQUIRE(dsrl_convt2x2_fwd_ce_supported(x, y, N, H, W, Cin, Cout), DSRL_E_UNSUPPORTED,
-                 "convt2x2_fwd_ce_w: needs 19 -> 19 channels, W %% 4 == 0, 16-byte aligned tensors (got %d -> %d, W = %d) and DSRL_CONVT_MFMA / DSRL_CONVT_CE not 0", Cin, Cout, W);
-    DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_fwd_ce_w_workspace_bytes(N, H, W), DSRL_E_WORKSPACE, "convt2x2_fwd_ce_w: workspace too small");
-    const int nseg_per_row = (int)ceil_div(W, 128);
-    const long long nseg = (long long)N * H * nseg_per_row;
-    const int nb = (int)std::min<long long>(nseg, convt_block_cap(4 * 512));
-    if (int e = launch_ce_weight_sum(target, (long long)N * 4 * H * W, Cout, ignore_index, weights, loss_out + 1, (double*)ws + 2 * nb, st)) return e;
-    ConvtFwdCe ce{target, (double*)ws, nan_flag, ignore_index, weights, 0.f, 0.f};
-    hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true, true>), dim3(nb), dim3(256), 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce);
-    if (int e = launch_status("convt2x2_fwd_mfma_kernel")) return e;
-    return launch_ce_finalize_w((const double*)ws, nb, loss_out, st);
+    return convt_fwd_ce_any(CeVariant::weighted(weights), x, w, bias, y, N, H, W, Cin, Cout, target, ignore_index, loss_out, nan_flag, ws, ws_bytes, stream);
 }
-// the focal forms: the weighted forms plus gamma (gamma == 0 IS the weighted form)
-extern "C" size_t dsrl_convt2x2_fwd_ce_f_workspace_bytes(int N, int H, int W) { return dsrl_convt2x2_fwd_ce_w_workspace_bytes(N, H, W); }
 extern "C" int dsrl_convt2x2_fwd_ce_f(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
                                       const uint8_t* target, int ignore_index, const float* weights, float gamma, float* loss_out, int* nan_flag,
                                       void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     DSRL_FOCAL_GAMMA(gamma, "convt2x2_fwd_ce_f");
-    if (gamma == 0.f) return dsrl_convt2x2_fwd_ce_w(x, w, bias, y, N, H, W, Cin, Cout, target, ignore_index, weights, loss_out, nan_flag, ws, ws_bytes, stream);
-    DSRL_PROLOGUE(x && w && y && target && weights && loss_out && ws && N > 0 && H > 0 && W > 0 && ((uintptr_t)ws % 8) == 0, "convt2x2_fwd_ce_f")
-    DSRL_REQUIRE(dsrl_convt2x2_fwd_ce_supported(x, y, N, H, W, Cin, Cout), DSRL_E_UNSUPPORTED,
-                 "convt2x2_fwd_ce_f: needs 19 -> 19 channels, W %% 4 == 0, 16-byte aligned tensors (got %d -> %d, W = %d) and DSRL_CONVT_MFMA / DSRL_CONVT_CE not 0", Cin, Cout, W);
-    DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_fwd_ce_f_workspace_bytes(N, H, W), DSRL_E_WORKSPACE, "convt2x2_fwd_ce_f: workspace too small");
-    const int nseg_per_row = (int)ceil_div(W, 128);
-    const long long nseg = (long long)N * H * nseg_per_row;
-    const int nb = (int)std::min<long long>(nseg, convt_block_cap(4 * 512));
-    if (int e = launch_ce_weight_sum(target, (long long)N * 4 * H * W, Cout, ignore_index, weights, loss_out + 1, (double*)ws + 2 * nb, st)) return e;
-    ConvtFwdCe ce{target, (double*)ws, nan_flag, ignore_index, weights, gamma, 0.f};
-    hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true, true, true>), dim3(nb), dim3(256), 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce);
-    if (int e = launch_status("convt2x2_fwd_mfma_kernel")) return e;
-    return launch_ce_finalize_w((const double*)ws, nb, loss_out, st);
+    return convt_fwd_ce_any(CeVariant::focal(weights, gamma), x, w, bias, y, N, H, W, Cin, Cout, target, ignore_index, loss_out, nan_flag, ws, ws_bytes, stream);
 }
-// the label-smoothing forms: the weighted forms plus eps (eps == 0 IS the weighted form)
-extern "C" size_t dsrl_convt2x2_fwd_ce_s_workspace_bytes(int N, int H, int W) { return dsrl_convt2x2_fwd_ce_w_workspace_bytes(N, H, W); }
 extern "C" int dsrl_convt2x2_fwd_ce_s(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
                                       const uint8_t* target, int ignore_index, const float* weights, float eps, float* loss_out, int* nan_flag,
                                       void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     DSRL_LABEL_SMOOTHING(eps, "convt2x2_fwd_ce_s");
-    if (eps == 0.f) return dsrl_convt2x2_fwd_ce_w(x, w, bias, y, N, H, W, Cin, Cout, target, ignore_index, weights, loss_out, nan_flag, ws, ws_bytes, stream);
-    DSRL_PROLOGUE(x && w && y && target && weights && loss_out && ws && N > 0 && H > 0 && W > 0 && ((uintptr_t)ws % 8) == 0, "convt2x2_fwd_ce_s")
-    DSRL_REQUIRE(dsrl_convt2x2_fwd_ce_supported(x, y, N, H, W, Cin, Cout), DSRL_E_UNSUPPORTED,
-                 "convt2x2_fwd_ce_s: needs 19 -> 19 channels, W %% 4 == 0, 16-byte aligned tensors (got %d -> %d, W = %d) and DSRL_CONVT_MFMA / DSRL_CONVT_CE not 0", Cin, Cout, W);
-    DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_fwd_ce_s_workspace_bytes(N, H, W), DSRL_E_WORKSPACE, "convt2x2_fwd_ce_s: workspace too small");
-    const int nseg_per_row = (int)ceil_div(W, 128);
-    const long long nseg = (long long)N * H * nseg_per_row;
-    const int nb = (int)std::min<long long>(nseg, convt_block_cap(4 * 512));
-    if (int e = launch_ce_weight_sum(target, (long long)N * 4 * H * W, Cout, ignore_index, weights, loss_out + 1, (double*)ws + 2 * nb, st)) return e;
-    ConvtFwdCe ce{target, (double*)ws, nan_flag, ignore_index, weights, 0.f, eps};
-    hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true, true, false, true>), dim3(nb), dim3(256), 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce);
-    if (int e = launch_status("convt2x2_fwd_mfma_kernel")) return e;
-    return launch_ce_finalize_w((const double*)ws, nb, loss_out, st);
+    return convt_fwd_ce_any(CeVariant::smoothed(weights, eps), x, w, bias, y, N, H, W, Cin, Cout, target, ignore_index, loss_out, nan_flag, ws, ws_bytes, stream);
 }
 static int convt_dw_blocks(int N, int H, int W) { return (int)std::min<long long>(convt_block_cap(1024), (long long)N * H * ceil_div(W, 64)); }
 extern "C" size_t dsrl_convt2x2_bwd_workspace_bytes(int N, int H, int W, int Cin, int Cout) {
@@ -1408,66 +1385,49 @@ extern "C" int dsrl_convt2x2_bwd_ce_supported(const float* x, const float* logit
     return (x && logits && target && N > 0 && H > 0 && convt_bwd_dma_supported(x, logits, W, Cin, Cout) && ((uintptr_t)target % 16) == 0 &&
             (long long)N * H * (W / 128) < (1ll << 31) && (long long)N * 4 * H * W * Cout * 4 < (1ll << 32)) ? 1 : 0;
 }
+// the one host body of dsrl_convt2x2_bwd_ce, _w, _f and _s; `count`: the pixel count of the plain form, D of the others
+static int convt_bwd_ce_any(const CeVariant& v, const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* count,
+                            const float* ft_g, const float* ft_w, int ft_stride, float* dx, float* dw, float* dbias,
+                            int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    const char* sfx = v.suffix();
+    DSRL_REQUIRE(x && w && logits && target && v.table_ok() && count && dx && dw && ws && N > 0 && H > 0 && W > 0 && (!ft_g || (ft_w && ft_stride > 0)), DSRL_E_BADARG,
+                 "convt2x2_bwd_ce%s: bad arguments", sfx);
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    DSRL_REQUIRE(dsrl_convt2x2_bwd_ce_supported(x, logits, target, N, H, W, Cin, Cout), DSRL_E_UNSUPPORTED,
+                 "convt2x2_bwd_ce%s: needs 19 -> 19 channels, W %% 128 == 0, 16-byte aligned tensors (got %d -> %d, W = %d) and DSRL_CONVT_DMA / DSRL_CONVT_CE not 0",
+                 sfx, Cin, Cout, W);
+    DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_bwd_workspace_bytes(N, H, W, Cin, Cout), DSRL_E_WORKSPACE, "convt2x2_bwd_ce%s: workspace too small", sfx);
+    const long long nseg = (long long)N * H * (W / 128);
+    const int nb3 = convt_bwd_dma_blocks(nseg, convt_dw_blocks(N, H, W));
+    if (int e = launch_convt_bwd_dma_ce(x, w, logits, dx, (float*)ws, N, H, W, nb3, target, ignore_index, count, ft_g, ft_w, ft_stride, v, st)) return e;
+    hipLaunchKernelGGL((convt2x2_dw_finalize_kernel<19, 19>), dim3((unsigned)ceil_div(19 * 19 * 4 + 19, 32)), dim3(256), 0, st, (const float*)ws, nb3, dw, dbias);
+    return launch_status("convt2x2_dw_finalize_kernel");
+}
 extern "C" int dsrl_convt2x2_bwd_ce(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* ce_count,
                                     const float* ft_g, const float* ft_w, int ft_stride, float* dx, float* dw, float* dbias,
                                     int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
-    DSRL_PROLOGUE(x && w && logits && target && ce_count && dx && dw && ws && N > 0 && H > 0 && W > 0 && (!ft_g || (ft_w && ft_stride > 0)), "convt2x2_bwd_ce")
-    DSRL_REQUIRE(dsrl_convt2x2_bwd_ce_supported(x, logits, target, N, H, W, Cin, Cout), DSRL_E_UNSUPPORTED,
-                 "convt2x2_bwd_ce: needs 19 -> 19 channels, W %% 128 == 0, 16-byte aligned tensors (got %d -> %d, W = %d) and DSRL_CONVT_DMA / DSRL_CONVT_CE not 0", Cin, Cout, W);
-    DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_bwd_workspace_bytes(N, H, W, Cin, Cout), DSRL_E_WORKSPACE, "convt2x2_bwd_ce: workspace too small");
-    const long long nseg = (long long)N * H * (W / 128);
-    const int nb3 = convt_bwd_dma_blocks(nseg, convt_dw_blocks(N, H, W));
-    if (int e = launch_convt_bwd_dma_ce(x, w, logits, dx, (float*)ws, N, H, W, nb3, target, ignore_index, ce_count, ft_g, ft_w, ft_stride, nullptr, 0.f, 0.f, st)) return e;
-    hipLaunchKernelGGL((convt2x2_dw_finalize_kernel<19, 19>), dim3((unsigned)ceil_div(19 * 19 * 4 + 19, 32)), dim3(256), 0, st, (const float*)ws, nb3, dw, dbias);
-    return launch_status("convt2x2_dw_finalize_kernel");
+    return convt_bwd_ce_any(CeVariant{}, x, w, logits, target, ignore_index, ce_count, ft_g, ft_w, ft_stride, dx, dw, dbias, N, H, W, Cin, Cout, ws, ws_bytes, stream);
 }
-
 extern "C" int dsrl_convt2x2_bwd_ce_w(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* weights,
                                       const float* ce_wsum, const float* ft_g, const float* ft_w, int ft_stride, float* dx, float* dw, float* dbias,
                                       int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
-    DSRL_PROLOGUE(x && w && logits && target && weights && ce_wsum && dx && dw && ws && N > 0 && H > 0 && W > 0 && (!ft_g || (ft_w && ft_stride > 0)), "convt2x2_bwd_ce_w")
-    DSRL_REQUIRE(dsrl_convt2x2_bwd_ce_supported(x, logits, target, N, H, W, Cin, Cout), DSRL_E_UNSUPPORTED,
-                 "convt2x2_bwd_ce_w: needs 19 -> 19 channels, W %% 128 == 0, 16-byte aligned tensors (got %d -> %d, W = %d) and DSRL_CONVT_DMA / DSRL_CONVT_CE not 0", Cin, Cout, W);
-    DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_bwd_workspace_bytes(N, H, W, Cin, Cout), DSRL_E_WORKSPACE, "convt2x2_bwd_ce_w: workspace too small");
-    const long long nseg = (long long)N * H * (W / 128);
-    const int nb3 = convt_bwd_dma_blocks(nseg, convt_dw_blocks(N, H, W));
-    if (int e = launch_convt_bwd_dma_ce(x, w, logits, dx, (float*)ws, N, H, W, nb3, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, weights, 0.f, 0.f, st)) return e;
-    hipLaunchKernelGGL((convt2x2_dw_finalize_kernel<19, 19>), dim3((unsigned)ceil_div(19 * 19 * 4 + 19, 32)), dim3(256), 0, st, (const float*)ws, nb3, dw, dbias);
-    return launch_status("convt2x2_dw_finalize_kernel");
+    return convt_bwd_ce_any(CeVariant::weighted(weights), x, w, logits, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, dx, dw, dbias, N, H, W, Cin, Cout,
+                            ws, ws_bytes, stream);
 }
-
 extern "C" int dsrl_convt2x2_bwd_ce_f(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* weights,
                                       float gamma, const float* ce_wsum, const float* ft_g, const float* ft_w, int ft_stride, float* dx, float* dw, float* dbias,
                                       int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     DSRL_FOCAL_GAMMA(gamma, "convt2x2_bwd_ce_f");
-    if (gamma == 0.f) return dsrl_convt2x2_bwd_ce_w(x, w, logits, target, ignore_index, weights, ce_wsum, ft_g, ft_w, ft_stride, dx, dw, dbias, N, H, W, Cin, Cout,
-                                                    ws, ws_bytes, stream);
-    DSRL_PROLOGUE(x && w && logits && target && weights && ce_wsum && dx && dw && ws && N > 0 && H > 0 && W > 0 && (!ft_g || (ft_w && ft_stride > 0)), "convt2x2_bwd_ce_f")
-    DSRL_REQUIRE(dsrl_convt2x2_bwd_ce_supported(x, logits, target, N, H, W, Cin, Cout), DSRL_E_UNSUPPORTED,
-                 "convt2x2_bwd_ce_f: needs 19 -> 19 channels, W %% 128 == 0, 16-byte aligned tensors (got %d -> %d, W = %d) and DSRL_CONVT_DMA / DSRL_CONVT_CE not 0", Cin, Cout, W);
-    DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_bwd_workspace_bytes(N, H, W, Cin, Cout), DSRL_E_WORKSPACE, "convt2x2_bwd_ce_f: workspace too small");
-    const long long nseg = (long long)N * H * (W / 128);
-    const int nb3 = convt_bwd_dma_blocks(nseg, convt_dw_blocks(N, H, W));
-    if (int e = launch_convt_bwd_dma_ce(x, w, logits, dx, (float*)ws, N, H, W, nb3, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, weights, gamma, 0.f, st)) return e;
-    hipLaunchKernelGGL((convt2x2_dw_finalize_kernel<19, 19>), dim3((unsigned)ceil_div(19 * 19 * 4 + 19, 32)), dim3(256), 0, st, (const float*)ws, nb3, dw, dbias);
-    return launch_status("convt2x2_dw_finalize_kernel");
+    return convt_bwd_ce_any(CeVariant::focal(weights, gamma), x, w, logits, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, dx, dw, dbias, N, H, W, Cin, Cout,
+                            ws, ws_bytes, stream);
 }
-
 extern "C" int dsrl_convt2x2_bwd_ce_s(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* weights,
                                       float eps, const float* ce_wsum, const float* ft_g, const float* ft_w, int ft_stride, float* dx, float* dw, float* dbias,
                                       int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     DSRL_LABEL_SMOOTHING(eps, "convt2x2_bwd_ce_s");
-    if (eps == 0.f) return dsrl_convt2x2_bwd_ce_w(x, w, logits, target, ignore_index, weights, ce_wsum, ft_g, ft_w, ft_stride, dx, dw, dbias, N, H, W, Cin, Cout,
-                                                  ws, ws_bytes, stream);
-    DSRL_PROLOGUE(x && w && logits && target && weights && ce_wsum && dx && dw && ws && N > 0 && H > 0 && W > 0 && (!ft_g || (ft_w && ft_stride > 0)), "convt2x2_bwd_ce_s")
-    DSRL_REQUIRE(dsrl_convt2x2_bwd_ce_supported(x, logits, target, N, H, W, Cin, Cout), DSRL_E_UNSUPPORTED,
-                 "convt2x2_bwd_ce_s: needs 19 -> 19 channels, W %% 128 == 0, 16-byte aligned tensors (got %d -> %d, W = %d) and DSRL_CONVT_DMA / DSRL_CONVT_CE not 0", Cin, Cout, W);
-    DSRL_REQUIRE(ws_bytes >= dsrl_convt2x2_bwd_workspace_bytes(N, H, W, Cin, Cout), DSRL_E_WORKSPACE, "convt2x2_bwd_ce_s: workspace too small");
-    const long long nseg = (long long)N * H * (W / 128);
-    const int nb3 = convt_bwd_dma_blocks(nseg, convt_dw_blocks(N, H, W));
-    if (int e = launch_convt_bwd_dma_ce(x, w, logits, dx, (float*)ws, N, H, W, nb3, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, weights, 0.f, eps, st)) return e;
-    hipLaunchKernelGGL((convt2x2_dw_finalize_kernel<19, 19>), dim3((unsigned)ceil_div(19 * 19 * 4 + 19, 32)), dim3(256), 0, st, (const float*)ws, nb3, dw, dbias);
-    return launch_status("convt2x2_dw_finalize_kernel");
+    return convt_bwd_ce_any(CeVariant::smoothed(weights, eps), x, w, logits, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, dx, dw, dbias, N, H, W, Cin, Cout,
+                            ws, ws_bytes, stream);
 }
 
 static size_t pixel_shuffle_tile_bytes(int c, int r) { return (size_t)kPsTile * c * (r * r + 1) * sizeof(float); }

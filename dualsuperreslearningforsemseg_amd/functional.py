@@ -1395,6 +1395,19 @@ def _focal_args(weight, gamma, device, num_classes, eps=0.0):
     return weight, gamma, eps
 
 
+def _ce_variant(weight, gamma, eps):
+    """(suffix of the entry point, the arguments that follow ignore_index in its call) of a CE call whose (class-weight table, gamma, eps) went
+    through _focal_args: '' plain, '_w' class-weighted, '_f' focal, '_s' label-smoothed.  Every family (dsrl_ce_fwd, dsrl_ce_bwd, dsrl_ce_fused,
+    dsrl_convt2x2_fwd_ce, dsrl_convt2x2_bwd_ce) and every workspace query names its four forms with these suffixes."""
+    if eps > 0.0:
+        return '_s', (weight.data_ptr(), eps)
+    if gamma > 0.0:
+        return '_f', (weight.data_ptr(), gamma)
+    if weight is None:
+        return '', ()
+    return '_w', (weight.data_ptr(),)
+
+
 _WEIGHT_TABLES_MAX = 32
 _weight_tables = {}             # (fp32 weight bytes, device) -> table
 _weight_tables_made = {}        # id(table) -> (weak reference, number of classes): how a table made here is recognised for as long as it lives
@@ -1449,27 +1462,14 @@ class _ConvT2x2(torch.autograd.Function):
         if (lt is not None and tuple(lt[0].shape) == (N, 2 * H, 2 * W) and lt[0].device == x.device
                 and query('dsrl_convt2x2_fwd_ce_supported', x.data_ptr(), y.data_ptr(), N, H, W, Ci, Co)):       # (pointer arguments: not memoised)
             tgt, ign, flag, wt, gamma, eps = lt
-            if gamma > 0.0 or eps > 0.0:
-                wt = _focal_args(wt, gamma, x.device, Co, eps)[0]
+            if wt is not None or gamma > 0.0 or eps > 0.0:
+                wt = _focal_args(wt, gamma, x.device, Co, eps)[0]           # (a table of another class count: ValueError)
+            sfx, extra = _ce_variant(wt, gamma, eps)
             holder.value = torch.empty(8, device=x.device, dtype=torch.float32)
             holder.value_key = (tgt.data_ptr(), ign, flag.data_ptr(), 0 if wt is None else wt.data_ptr(), eps, gamma)
-            if eps > 0.0:
-                ws = _ws(cquery('dsrl_convt2x2_fwd_ce_s_workspace_bytes', N, H, W), x)
-                call('dsrl_convt2x2_fwd_ce_s', x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co,
-                     tgt.data_ptr(), ign, wt.data_ptr(), eps, holder.value.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-            elif gamma > 0.0:
-                ws = _ws(cquery('dsrl_convt2x2_fwd_ce_f_workspace_bytes', N, H, W), x)
-                call('dsrl_convt2x2_fwd_ce_f', x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co,
-                     tgt.data_ptr(), ign, wt.data_ptr(), gamma, holder.value.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-            elif wt is None:
-                ws = _ws(cquery('dsrl_convt2x2_fwd_ce_workspace_bytes', N, H, W), x)
-                call('dsrl_convt2x2_fwd_ce', x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co,
-                     tgt.data_ptr(), ign, holder.value.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-            else:
-                wt = class_weight_table(wt, x.device, Co)
-                ws = _ws(cquery('dsrl_convt2x2_fwd_ce_w_workspace_bytes', N, H, W), x)
-                call('dsrl_convt2x2_fwd_ce_w', x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co,
-                     tgt.data_ptr(), ign, wt.data_ptr(), holder.value.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+            ws = _ws(cquery(f'dsrl_convt2x2_fwd_ce{sfx}_workspace_bytes', N, H, W), x)
+            call('dsrl_convt2x2_fwd_ce' + sfx, x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co,
+                 tgt.data_ptr(), ign, *extra, holder.value.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
         else:
             call('dsrl_convt2x2_fwd', x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co, _stream())
         ctx.save_for_backward(x, w)
@@ -1503,21 +1503,10 @@ class _ConvT2x2(torch.autograd.Function):
             P = N * 4 * H * W
             dl = new_cl((N, Co, 2 * H, 2 * W), x)
             scal = torch.empty(8, device=x.device, dtype=torch.float32)
-            if eps > 0.0:
-                wsc = _ws(cquery('dsrl_ce_fused_s_workspace_bytes', P), x)
-                call('dsrl_ce_fused_s', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, wt.data_ptr(), eps, dl.data_ptr(), Co, scal.data_ptr(), None,
-                     wsc.data_ptr(), wsc.numel(), _stream())
-            elif gamma > 0.0:
-                wsc = _ws(cquery('dsrl_ce_fused_f_workspace_bytes', P), x)
-                call('dsrl_ce_fused_f', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, wt.data_ptr(), gamma, dl.data_ptr(), Co, scal.data_ptr(), None,
-                     wsc.data_ptr(), wsc.numel(), _stream())
-            elif wt is None:
-                wsc = _ws(cquery('dsrl_ce_fused_workspace_bytes', P), x)
-                call('dsrl_ce_fused', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, dl.data_ptr(), Co, scal.data_ptr(), None, wsc.data_ptr(), wsc.numel(), _stream())
-            else:
-                wsc = _ws(cquery('dsrl_ce_fused_w_workspace_bytes', P), x)
-                call('dsrl_ce_fused_w', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, wt.data_ptr(), dl.data_ptr(), Co, scal.data_ptr(), None,
-                     wsc.data_ptr(), wsc.numel(), _stream())
+            sfx, extra = _ce_variant(wt, gamma, eps)
+            wsc = _ws(cquery(f'dsrl_ce_fused{sfx}_workspace_bytes', P), x)
+            call('dsrl_ce_fused' + sfx, y.data_ptr(), Co, target.data_ptr(), P, Co, ign, *extra, dl.data_ptr(), Co, scal.data_ptr(), None,
+                 wsc.data_ptr(), wsc.numel(), _stream())
             if ft is not None:
                 ft_g, ft_w, ft_s = ft
                 dwf = torch.empty(Co, device=x.device, dtype=torch.float32)          # the transformer's weight gradient was delivered by its own backward
@@ -1534,22 +1523,10 @@ class _ConvT2x2(torch.autograd.Function):
         if fused:
             y, target, ign, count, ft, wt, gamma, eps = hand
             ft_g, ft_w, ft_s = ft if ft is not None else (None, None, 0)
-            if eps > 0.0:
-                call('dsrl_convt2x2_bwd_ce_s', x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, wt.data_ptr(), eps, count.data_ptr() + 4,
-                     None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
-                     dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
-            elif gamma > 0.0:
-                call('dsrl_convt2x2_bwd_ce_f', x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, wt.data_ptr(), gamma, count.data_ptr() + 4,
-                     None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
-                     dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
-            elif wt is None:
-                call('dsrl_convt2x2_bwd_ce', x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, count.data_ptr() + 4,
-                     None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
-                     dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
-            else:
-                call('dsrl_convt2x2_bwd_ce_w', x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, wt.data_ptr(), count.data_ptr() + 4,
-                     None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
-                     dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
+            sfx, extra = _ce_variant(wt, gamma, eps)
+            call('dsrl_convt2x2_bwd_ce' + sfx, x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, *extra, count.data_ptr() + 4,
+                 None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
+                 dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
         else:
             call('dsrl_convt2x2_bwd', x.data_ptr(), w.data_ptr(), dy.data_ptr(), dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(),
                  N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
@@ -1668,21 +1645,10 @@ class _CrossEntropy(torch.autograd.Function):
         if target.numel() != P:
             raise DsrlHipError(f'cross_entropy: target has {target.numel()} pixels, logits {P}')
         out = torch.empty(2, device=logits.device, dtype=torch.float32)
-        if eps > 0.0:
-            ws = _ws(cquery('dsrl_ce_s_workspace_bytes', P), logits)
-            call('dsrl_ce_fwd_s', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(), eps, out.data_ptr(),
-                 ws.data_ptr(), ws.numel(), _stream())
-        elif gamma > 0.0:
-            ws = _ws(cquery('dsrl_ce_f_workspace_bytes', P), logits)
-            call('dsrl_ce_fwd_f', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(), gamma, out.data_ptr(),
-                 ws.data_ptr(), ws.numel(), _stream())
-        elif weight is None:
-            ws = _ws(cquery('dsrl_ce_workspace_bytes', P), logits)
-            call('dsrl_ce_fwd', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-        else:
-            ws = _ws(cquery('dsrl_ce_w_workspace_bytes', P), logits)
-            call('dsrl_ce_fwd_w', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(), out.data_ptr(),
-                 ws.data_ptr(), ws.numel(), _stream())
+        sfx, extra = _ce_variant(weight, gamma, eps)
+        ws = _ws(cquery(f'dsrl_ce{sfx}_workspace_bytes', P), logits)
+        call('dsrl_ce_fwd' + sfx, logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), *extra, out.data_ptr(),
+             ws.data_ptr(), ws.numel(), _stream())
         ctx.save_for_backward(logits, target, out)
         ctx.ignore_index = int(ignore_index)
         ctx.weight = weight
@@ -1697,18 +1663,9 @@ class _CrossEntropy(torch.autograd.Function):
         N, Cc, H, W = logits.shape
         g = g.reshape(1).contiguous().float()
         dl = new_cl((N, Cc, H, W), logits)
-        if ctx.eps > 0.0:
-            call('dsrl_ce_bwd_s', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, ctx.weight.data_ptr(), ctx.eps,
-                 out.data_ptr(), g.data_ptr(), dl.data_ptr(), Cc, _stream())
-        elif ctx.gamma > 0.0:
-            call('dsrl_ce_bwd_f', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, ctx.weight.data_ptr(), ctx.gamma,
-                 out.data_ptr(), g.data_ptr(), dl.data_ptr(), Cc, _stream())
-        elif ctx.weight is None:
-            call('dsrl_ce_bwd', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, out.data_ptr(), g.data_ptr(),
-                 dl.data_ptr(), Cc, _stream())
-        else:
-            call('dsrl_ce_bwd_w', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, ctx.weight.data_ptr(), out.data_ptr(),
-                 g.data_ptr(), dl.data_ptr(), Cc, _stream())
+        sfx, extra = _ce_variant(ctx.weight, ctx.gamma, ctx.eps)
+        call('dsrl_ce_bwd' + sfx, logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, *extra, out.data_ptr(), g.data_ptr(),
+             dl.data_ptr(), Cc, _stream())
         return dl, None, None, None, None, None
 
 
@@ -1777,21 +1734,10 @@ class _FusedLosses(torch.autograd.Function):
         if lg is not None and lg.value is not None and lg.value_key == (target.data_ptr(), int(ignore_index), flag.data_ptr(),
                                                                         0 if weight is None else weight.data_ptr(), eps, gamma):
             scal = lg.value                                             # the producer's forward kernel evaluated the loss (logits_target)
-        elif eps > 0.0:
-            ws = _ws(cquery('dsrl_ce_fused_s_workspace_bytes', P), logits)
-            call('dsrl_ce_fused_s', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(), eps,
-                 None if dl is None else dl.data_ptr(), Cc, scal.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        elif gamma > 0.0:
-            ws = _ws(cquery('dsrl_ce_fused_f_workspace_bytes', P), logits)
-            call('dsrl_ce_fused_f', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(), gamma,
-                 None if dl is None else dl.data_ptr(), Cc, scal.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        elif weight is None:
-            ws = _ws(cquery('dsrl_ce_fused_workspace_bytes', P), logits)
-            call('dsrl_ce_fused', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), None if dl is None else dl.data_ptr(), Cc,
-                 scal.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
         else:
-            ws = _ws(cquery('dsrl_ce_fused_w_workspace_bytes', P), logits)
-            call('dsrl_ce_fused_w', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), weight.data_ptr(),
+            sfx, extra = _ce_variant(weight, gamma, eps)
+            ws = _ws(cquery(f'dsrl_ce_fused{sfx}_workspace_bytes', P), logits)
+            call('dsrl_ce_fused' + sfx, logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), *extra,
                  None if dl is None else dl.data_ptr(), Cc, scal.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
         da = None
         mse_ptr = fa_ptr = None

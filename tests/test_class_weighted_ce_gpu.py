@@ -31,6 +31,7 @@ pytestmark = pytest.mark.gpu
 import gen                     # noqa: E402
 import oracle as O             # noqa: E402
 from hip_helpers import DEV, HF, check, dev, host, make_head   # noqa: E402
+from ce_variant_runners import _place, table, run_A_w as run_A, run_B_w as run_B, run_C_w as run_C, run_D_w as run_D   # noqa: E402,F401
 from test_cross_entropy_edges import check_loss, make_case     # noqa: E402
 
 import dualsuperreslearningforsemseg_amd as D                  # noqa: E402
@@ -49,10 +50,6 @@ def make_weights(C, rs, zero=None):
     w = rs.uniform(0.25, 8.0, C).astype(np.float32)
     w[rs.randint(C) if zero is None else zero] = 0.0
     return w
-
-
-def table(w):
-    return HF.class_weight_table(w, DEV)
 
 
 def case_for(case, P, C, rs, ii):
@@ -109,62 +106,6 @@ def check_against_reference(L, Dgot, g, lg, tg, ii, w, case, name):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ paths A and B
-def _place(lg, layout):
-    P, C = lg.shape
-    if layout == 'slice':                       # the logits a channel slice of a wider tensor: ld = C + 5, 8 bytes past the base (scalar loads)
-        buf = torch.full((P, C + 5), 7.0, device=DEV); buf[:, 2:2 + C] = torch.tensor(lg, device=DEV)
-        return buf, buf.data_ptr() + 8, C + 5
-    buf = torch.tensor(lg, device=DEV)
-    return buf, buf.data_ptr(), C
-
-
-def run_A(lg, tg, ii, w, layout='dense'):
-    """dsrl_ce_fwd_w + dsrl_ce_bwd_w (w None: the unweighted pair) -> (loss, D or count, gradient)"""
-    call, query = _lib()
-    P, C = lg.shape
-    buf, ptr, ld = _place(lg, layout)
-    target = torch.tensor(tg, device=DEV)
-    out = torch.full((2,), 7.0, device=DEV); one = torch.ones(1, device=DEV)
-    dl = torch.full((P, C), 7.0, device=DEV)
-    st = HF._stream()
-    if w is None:
-        ws = torch.empty(query('dsrl_ce_workspace_bytes', P), dtype=torch.uint8, device=DEV)
-        call('dsrl_ce_fwd', ptr, ld, target.data_ptr(), P, C, ii, out.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        call('dsrl_ce_bwd', ptr, ld, target.data_ptr(), P, C, ii, out.data_ptr(), one.data_ptr(), dl.data_ptr(), C, st)
-    else:
-        wt = table(w)
-        ws = torch.empty(query('dsrl_ce_w_workspace_bytes', P), dtype=torch.uint8, device=DEV)
-        call('dsrl_ce_fwd_w', ptr, ld, target.data_ptr(), P, C, ii, wt.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        call('dsrl_ce_bwd_w', ptr, ld, target.data_ptr(), P, C, ii, wt.data_ptr(), out.data_ptr(), one.data_ptr(), dl.data_ptr(), C, st)
-    torch.cuda.synchronize()
-    o = host(out)
-    return o[0], o[1], host(dl)
-
-
-def run_B(lg, tg, ii, w, layout='dense', want_grad=True):
-    """dsrl_ce_fused_w (w None: dsrl_ce_fused) -> (loss, D or count, flag, gradient)"""
-    call, query = _lib()
-    P, C = lg.shape
-    buf, ptr, ld = _place(lg, layout)
-    target = torch.tensor(tg, device=DEV)
-    scal = torch.full((8,), 7.0, device=DEV)
-    flag = torch.zeros(1, dtype=torch.int32, device=DEV)
-    dl = torch.full((P, C), 7.0, device=DEV) if want_grad else None
-    dlp = None if dl is None else dl.data_ptr()
-    st = HF._stream()
-    if w is None:
-        ws = torch.empty(query('dsrl_ce_fused_workspace_bytes', P), dtype=torch.uint8, device=DEV)
-        call('dsrl_ce_fused', ptr, ld, target.data_ptr(), P, C, ii, dlp, C, scal.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
-    else:
-        ws = torch.empty(query('dsrl_ce_fused_w_workspace_bytes', P), dtype=torch.uint8, device=DEV)
-        call('dsrl_ce_fused_w', ptr, ld, target.data_ptr(), P, C, ii, table(w).data_ptr(), dlp, C, scal.data_ptr(), flag.data_ptr(),
-             ws.data_ptr(), ws.numel(), st)
-    torch.cuda.synchronize()
-    s = host(scal)
-    assert np.all(s[2:] == 7.0), 'wrote past loss_out[2]'
-    return s[0], s[1], int(flag), None if dl is None else host(dl)
-
-
 @pytest.mark.parametrize('C', [19, 3])
 @pytest.mark.parametrize('case', CASES)
 def test_paths_A_and_B_weighted(case, C):
@@ -243,27 +184,6 @@ def test_all_ones_weights_are_the_unweighted_bits_and_runs_repeat(case, C, layou
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ path C
-def run_C(x, wgt, b, tg, ii, w):
-    call, query = _lib()
-    N, H, W, C = x.shape
-    xt = torch.tensor(x, device=DEV); wt = torch.tensor(wgt, device=DEV); bt = torch.tensor(b, device=DEV); target = torch.tensor(tg, device=DEV)
-    y = torch.full((N, 2 * H, 2 * W, C), 7.0, device=DEV)
-    s = torch.full((8,), 7.0, device=DEV); f = torch.zeros(1, dtype=torch.int32, device=DEV)
-    st = HF._stream()
-    if w is None:
-        ws = torch.empty(query('dsrl_convt2x2_fwd_ce_workspace_bytes', N, H, W), dtype=torch.uint8, device=DEV)
-        call('dsrl_convt2x2_fwd_ce', xt.data_ptr(), wt.data_ptr(), bt.data_ptr(), y.data_ptr(), N, H, W, C, C, target.data_ptr(), ii, s.data_ptr(),
-             f.data_ptr(), ws.data_ptr(), ws.numel(), st)
-    else:
-        ws = torch.empty(query('dsrl_convt2x2_fwd_ce_w_workspace_bytes', N, H, W), dtype=torch.uint8, device=DEV)
-        call('dsrl_convt2x2_fwd_ce_w', xt.data_ptr(), wt.data_ptr(), bt.data_ptr(), y.data_ptr(), N, H, W, C, C, target.data_ptr(), ii,
-             table(w).data_ptr(), s.data_ptr(), f.data_ptr(), ws.data_ptr(), ws.numel(), st)
-    torch.cuda.synchronize()
-    sh = host(s)
-    assert np.all(sh[2:] == 7.0)
-    return y, sh[0], sh[1], int(f)
-
-
 @pytest.mark.parametrize('case,ii', [(c, 255) for c in ('randn', 'spread', 'offset_1e4', 'onehot', 'bad_label')] + [('randn', ii) for ii in (0, 18, -1)])
 def test_path_C_weighted_value_inside_the_convT_forward(case, ii, monkeypatch):
     call, query = _lib()
@@ -313,44 +233,6 @@ def test_path_C_weighted_value_inside_the_convT_forward(case, ii, monkeypatch):
 # ------------------------------------------------------------------------------------------------------------------------------ path D
 def _bits_equal(a, b):
     return torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
-def run_D(x, wgt, logits, target, ii, w, ftg, ftw, ft):
-    """-> (three-call results (dx, dw, db, dl of the loss alone, flag), one-call results (dx, dw, db)); w None: the unweighted entry points"""
-    call, query = _lib()
-    N, H, W, C = x.shape
-    P = N * 4 * H * W
-    st = HF._stream()
-    flag = torch.zeros(1, dtype=torch.int32, device=DEV)
-    wsb = torch.empty(query('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, C, C), dtype=torch.uint8, device=DEV)
-    assert query('dsrl_convt2x2_bwd_ce_supported', x.data_ptr(), logits.data_ptr(), target.data_ptr(), N, H, W, C, C) == 1
-    scal = torch.zeros(8, device=DEV); dl = torch.empty_like(logits)
-    if w is None:
-        ws = torch.empty(query('dsrl_ce_fused_workspace_bytes', P), dtype=torch.uint8, device=DEV)
-        call('dsrl_ce_fused', logits.data_ptr(), C, target.data_ptr(), P, C, ii, dl.data_ptr(), C, scal.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
-    else:
-        wt = table(w)
-        ws = torch.empty(query('dsrl_ce_fused_w_workspace_bytes', P), dtype=torch.uint8, device=DEV)
-        call('dsrl_ce_fused_w', logits.data_ptr(), C, target.data_ptr(), P, C, ii, wt.data_ptr(), dl.data_ptr(), C, scal.data_ptr(), flag.data_ptr(),
-             ws.data_ptr(), ws.numel(), st)
-    dl_ce = dl.clone()
-    if ft:
-        dwf = torch.empty(C, device=DEV)
-        wsf = torch.empty(query('dsrl_pointwise_strided_bwd_workspace_bytes', N, 2 * H, 2 * W, C, ft), dtype=torch.uint8, device=DEV)
-        call('dsrl_pointwise_strided_bwd', logits.data_ptr(), ftw.data_ptr(), ftg.data_ptr(), dl.data_ptr(), dwf.data_ptr(), 1, N, 2 * H, 2 * W, C, ft,
-             wsf.data_ptr(), wsf.numel(), st)
-    dx = torch.empty_like(x); dw = torch.empty_like(wgt); db = torch.empty(C, device=DEV)
-    call('dsrl_convt2x2_bwd', x.data_ptr(), wgt.data_ptr(), dl.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), N, H, W, C, C, wsb.data_ptr(), wsb.numel(), st)
-    dx2 = torch.full_like(x, 7.0); dw2 = torch.full_like(wgt, 7.0); db2 = torch.full((C,), 7.0, device=DEV)
-    ftp = (None, None) if not ft else (ftg.data_ptr(), ftw.data_ptr())
-    if w is None:
-        call('dsrl_convt2x2_bwd_ce', x.data_ptr(), wgt.data_ptr(), logits.data_ptr(), target.data_ptr(), ii, scal.data_ptr() + 4, ftp[0], ftp[1], ft,
-             dx2.data_ptr(), dw2.data_ptr(), db2.data_ptr(), N, H, W, C, C, wsb.data_ptr(), wsb.numel(), st)
-    else:
-        call('dsrl_convt2x2_bwd_ce_w', x.data_ptr(), wgt.data_ptr(), logits.data_ptr(), target.data_ptr(), ii, wt.data_ptr(), scal.data_ptr() + 4,
-             ftp[0], ftp[1], ft, dx2.data_ptr(), dw2.data_ptr(), db2.data_ptr(), N, H, W, C, C, wsb.data_ptr(), wsb.numel(), st)
-    torch.cuda.synchronize()
-    return (dx, dw, db, dl_ce, int(flag)), (dx2, dw2, db2)
 
 
 @pytest.mark.parametrize('ft', [8, 0])

@@ -34,6 +34,7 @@ import gen                     # noqa: E402
 import label_smoothing_ref as SR   # noqa: E402
 import oracle as O             # noqa: E402
 from hip_helpers import DEV, HF, check, dev, host, make_head   # noqa: E402
+from ce_variant_runners import run_A_s as run_A, run_B_s as run_B, run_C_s as run_C, run_D_s as run_D, run_D_one_s as run_D_one   # noqa: E402
 from test_class_weighted_ce_gpu import (_bits, _bits_equal, _five, _place, case_for, expected_D, make_weights, reference, table)   # noqa: E402
 from test_cross_entropy_edges import make_case     # noqa: E402
 from test_focal_ce_gpu import _convt_inputs        # noqa: E402
@@ -130,56 +131,6 @@ def check_against_reference(L, Dgot, g, lg, tg, ii, w, eps, case, name):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ paths A and B
-def run_A(lg, tg, ii, w, eps, layout='dense', expect_error=False):
-    """dsrl_ce_fwd_s + dsrl_ce_bwd_s -> (loss, D, gradient)"""
-    call, query = _lib()
-    P, C = lg.shape
-    buf, ptr, ld = _place(lg, layout)
-    target = torch.tensor(tg, device=DEV)
-    out = torch.full((2,), 7.0, device=DEV); one = torch.ones(1, device=DEV)
-    dl = torch.full((P, C), 7.0, device=DEV)
-    st = HF._stream()
-    wt = table(w)
-    ws = torch.empty(query('dsrl_ce_s_workspace_bytes', P), dtype=torch.uint8, device=DEV)
-    assert ws.numel() == query('dsrl_ce_w_workspace_bytes', P)
-    if expect_error:
-        with pytest.raises(DsrlHipError):
-            call('dsrl_ce_fwd_s', ptr, ld, target.data_ptr(), P, C, ii, wt.data_ptr(), eps, out.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        with pytest.raises(DsrlHipError):
-            call('dsrl_ce_bwd_s', ptr, ld, target.data_ptr(), P, C, ii, wt.data_ptr(), eps, out.data_ptr(), one.data_ptr(), dl.data_ptr(), C, st)
-    else:
-        call('dsrl_ce_fwd_s', ptr, ld, target.data_ptr(), P, C, ii, wt.data_ptr(), eps, out.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        call('dsrl_ce_bwd_s', ptr, ld, target.data_ptr(), P, C, ii, wt.data_ptr(), eps, out.data_ptr(), one.data_ptr(), dl.data_ptr(), C, st)
-    torch.cuda.synchronize()
-    o = host(out)
-    return o[0], o[1], host(dl)
-
-
-def run_B(lg, tg, ii, w, eps, layout='dense', want_grad=True, expect_error=False):
-    """dsrl_ce_fused_s -> (loss, D, flag, gradient)"""
-    call, query = _lib()
-    P, C = lg.shape
-    buf, ptr, ld = _place(lg, layout)
-    target = torch.tensor(tg, device=DEV)
-    scal = torch.full((8,), 7.0, device=DEV)
-    flag = torch.zeros(1, dtype=torch.int32, device=DEV)
-    dl = torch.full((P, C), 7.0, device=DEV) if want_grad else None
-    dlp = None if dl is None else dl.data_ptr()
-    st = HF._stream()
-    ws = torch.empty(query('dsrl_ce_fused_s_workspace_bytes', P), dtype=torch.uint8, device=DEV)
-    assert ws.numel() == query('dsrl_ce_fused_w_workspace_bytes', P)
-    args = (ptr, ld, target.data_ptr(), P, C, ii, table(w).data_ptr(), eps, dlp, C, scal.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
-    if expect_error:
-        with pytest.raises(DsrlHipError):
-            call('dsrl_ce_fused_s', *args)
-    else:
-        call('dsrl_ce_fused_s', *args)
-    torch.cuda.synchronize()
-    s = host(scal)
-    assert np.all(s[2:] == 7.0), 'wrote past loss_out[2]'
-    return s[0], s[1], int(flag), None if dl is None else host(dl)
-
-
 def assert_eps_matters(lg, tg, ii, w, eps, name):
     """near-uniform predictions (an untrained net) move little under smoothing: the weighted CE must still lie far outside the bound around the
     smoothed reference, so that a kernel that ignores eps fails the value check"""
@@ -301,27 +252,6 @@ def test_a_bad_eps_is_an_error_and_writes_nothing(eps, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ path C
-def run_C(x, wgt, b, tg, ii, w, eps, expect_error=False):
-    call, query = _lib()
-    N, H, W, C = x.shape
-    xt = torch.tensor(x, device=DEV); wt = torch.tensor(wgt, device=DEV); bt = torch.tensor(b, device=DEV); target = torch.tensor(tg, device=DEV)
-    y = torch.full((N, 2 * H, 2 * W, C), 7.0, device=DEV)
-    s = torch.full((8,), 7.0, device=DEV); f = torch.zeros(1, dtype=torch.int32, device=DEV)
-    ws = torch.empty(query('dsrl_convt2x2_fwd_ce_s_workspace_bytes', N, H, W), dtype=torch.uint8, device=DEV)
-    assert ws.numel() == query('dsrl_convt2x2_fwd_ce_w_workspace_bytes', N, H, W)
-    args = (xt.data_ptr(), wt.data_ptr(), bt.data_ptr(), y.data_ptr(), N, H, W, C, C, target.data_ptr(), ii, table(w).data_ptr(), eps, s.data_ptr(),
-            f.data_ptr(), ws.data_ptr(), ws.numel(), HF._stream())
-    if expect_error:
-        with pytest.raises(DsrlHipError):
-            call('dsrl_convt2x2_fwd_ce_s', *args)
-    else:
-        call('dsrl_convt2x2_fwd_ce_s', *args)
-    torch.cuda.synchronize()
-    sh = host(s)
-    assert np.all(sh[2:] == 7.0)
-    return y, sh[0], sh[1], int(f)
-
-
 @pytest.mark.parametrize('case,ii,zero', [(c, 255, None) for c in CASES] + [('spread', 255, 4)] + [('randn', ii, None) for ii in (0, 18, -1)])
 def test_path_C_smoothed_value_inside_the_convT_forward(case, ii, zero, monkeypatch):
     call, query = _lib()
@@ -353,49 +283,6 @@ def test_path_C_smoothed_value_inside_the_convT_forward(case, ii, zero, monkeypa
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ path D
-def run_D_one(x, wgt, logits, target, ii, w, eps, scal, ftg, ftw, ft, expect_error=False):
-    """dsrl_convt2x2_bwd_ce_s alone -> (dx, dw, db), pre-filled with 7"""
-    call, query = _lib()
-    N, H, W, C = x.shape
-    wsb = torch.empty(query('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, C, C), dtype=torch.uint8, device=DEV)
-    dx2 = torch.full_like(x, 7.0); dw2 = torch.full_like(wgt, 7.0); db2 = torch.full((C,), 7.0, device=DEV)
-    ftp = (None, None) if not ft else (ftg.data_ptr(), ftw.data_ptr())
-    args = (x.data_ptr(), wgt.data_ptr(), logits.data_ptr(), target.data_ptr(), ii, table(w).data_ptr(), eps, scal.data_ptr() + 4, ftp[0], ftp[1], ft,
-            dx2.data_ptr(), dw2.data_ptr(), db2.data_ptr(), N, H, W, C, C, wsb.data_ptr(), wsb.numel(), HF._stream())
-    if expect_error:
-        with pytest.raises(DsrlHipError):
-            call('dsrl_convt2x2_bwd_ce_s', *args)
-    else:
-        call('dsrl_convt2x2_bwd_ce_s', *args)
-    torch.cuda.synchronize()
-    return dx2, dw2, db2
-
-
-def run_D(x, wgt, logits, target, ii, w, eps, ftg, ftw, ft):
-    """-> (three-call results (dx, dw, db, dl of the loss alone, flag), one-call results (dx, dw, db))"""
-    call, query = _lib()
-    N, H, W, C = x.shape
-    P = N * 4 * H * W
-    st = HF._stream()
-    flag = torch.zeros(1, dtype=torch.int32, device=DEV)
-    wsb = torch.empty(query('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, C, C), dtype=torch.uint8, device=DEV)
-    assert query('dsrl_convt2x2_bwd_ce_supported', x.data_ptr(), logits.data_ptr(), target.data_ptr(), N, H, W, C, C) == 1
-    scal = torch.zeros(8, device=DEV); dl = torch.empty_like(logits)
-    ws = torch.empty(query('dsrl_ce_fused_s_workspace_bytes', P), dtype=torch.uint8, device=DEV)
-    call('dsrl_ce_fused_s', logits.data_ptr(), C, target.data_ptr(), P, C, ii, table(w).data_ptr(), eps, dl.data_ptr(), C, scal.data_ptr(), flag.data_ptr(),
-         ws.data_ptr(), ws.numel(), st)
-    dl_ce = dl.clone()
-    if ft:
-        dwf = torch.empty(C, device=DEV)
-        wsf = torch.empty(query('dsrl_pointwise_strided_bwd_workspace_bytes', N, 2 * H, 2 * W, C, ft), dtype=torch.uint8, device=DEV)
-        call('dsrl_pointwise_strided_bwd', logits.data_ptr(), ftw.data_ptr(), ftg.data_ptr(), dl.data_ptr(), dwf.data_ptr(), 1, N, 2 * H, 2 * W, C, ft,
-             wsf.data_ptr(), wsf.numel(), st)
-    dx = torch.empty_like(x); dw = torch.empty_like(wgt); db = torch.empty(C, device=DEV)
-    call('dsrl_convt2x2_bwd', x.data_ptr(), wgt.data_ptr(), dl.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), N, H, W, C, C, wsb.data_ptr(), wsb.numel(), st)
-    one = run_D_one(x, wgt, logits, target, ii, w, eps, scal, ftg, ftw, ft)
-    return (dx, dw, db, dl_ce, int(flag)), one
-
-
 @pytest.mark.parametrize('ft', [8, 0])
 @pytest.mark.parametrize('case,ii', [(c, 255) for c in ('randn', 'graded', 'spread', 'onehot', 'bad_label')] + [('randn', ii) for ii in (0, 18, -1)])
 def test_path_D_smoothed_gradient_inside_the_convT_backward(case, ii, ft, monkeypatch):

@@ -1,0 +1,197 @@
+#!/usr/bin/env python3
+"""Cost of one cross-entropy variant at the step's shape (N = 8, tail input 256 x 512, 19 -> 19), written to profiles/<variant>_ce.txt
+(class_weighted_ce.txt, focal_ce.txt, label_smoothing_ce.txt):
+  * kernel-only times through the C ABI, HIP events around back-to-back launches, the variant's entry points against their base:
+      weighted   dsrl_convt2x2_fwd_ce_w, dsrl_convt2x2_bwd_ce_w and dsrl_ce_fused_w against the unweighted calls, and the D pre-pass alone
+                 (dsrl_ce_weight_sum: label histogram + weight sum);
+      focal      dsrl_ce_fwd_f + dsrl_ce_bwd_f, dsrl_ce_fused_f, dsrl_convt2x2_fwd_ce_f, dsrl_convt2x2_bwd_ce_f against their _w siblings, gamma = 2;
+      smoothed   the same four _s paths against their _w siblings, eps = 0.1;
+  * the replayed training step (stage 3, batch 8, 256 x 512 input, hipGraph): default, class weights and (focal, smoothed) class weights + gamma
+    or eps, alternating in one process.
+Everything in that file from the line '## recorded beside the tool' on is kept as it is.
+Usage: python tools/ce_variant_bench.py weighted|focal|smoothed [--steps K] [--no-step] [VAR=value ...]"""
+import os
+import sys
+import time
+
+args = [a for a in sys.argv[1:] if '=' not in a]
+for kv in sys.argv[1:]:
+    if '=' in kv:
+        k, v = kv.split('=', 1); os.environ[k] = v
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np                                                                                    # noqa: E402
+import torch                                                                                          # noqa: E402
+from dualsuperreslearningforsemseg_amd import functional as HF                                        # noqa: E402
+from dualsuperreslearningforsemseg_amd._lib import call, query                                        # noqa: E402
+
+# variant -> (entry-point suffix, suffix of the base it is measured against, gamma or eps, its name in the output, what it is called there,
+#             the TrainStep keyword of the parameter, output file)
+VARIANTS = {'weighted': ('_w', '', None, None, 'weighted', None, 'class_weighted_ce.txt'),
+            'focal': ('_f', '_w', 2.0, 'gamma', 'focal', 'focal_gamma', 'focal_ce.txt'),
+            'smoothed': ('_s', '_w', 0.1, 'eps', 'smoothed', 'label_smoothing', 'label_smoothing_ce.txt')}
+if not args or args[0] not in VARIANTS:
+    sys.exit(__doc__)
+VARIANT = args[0]
+SFX, BASE, PARAM, PNAME, WORD, STEP_KW, OUT = VARIANTS[VARIANT]
+dev = 'cuda:0'
+STEPS = int(args[args.index('--steps') + 1]) if '--steps' in args else 30
+lines = []
+
+
+def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+
+def timeit(f, reps=20):
+    for _ in range(3):
+        f()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        f()
+    b.record(); torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps * 1e3
+
+
+def kernels():
+    N, H, W, C = 8, 256, 512, 19
+    P = N * 4 * H * W
+    rs = np.random.RandomState(1)
+    x = torch.randn(N, H, W, C, device=dev); w = torch.randn(C, C, 2, 2, device=dev) * 0.2; b = torch.randn(C, device=dev)
+    y = torch.empty(N, 2 * H, 2 * W, C, device=dev)
+    tg = torch.randint(0, C, (N, 2 * H, 2 * W), device=dev, dtype=torch.uint8)
+    tg[torch.rand(tg.shape, device=dev) < 0.1] = 255
+    wt = HF.class_weight_table(rs.uniform(0.25, 8.0, C), dev)
+    dx = torch.empty_like(x); dw = torch.empty_like(w); db = torch.empty(C, device=dev); dl = torch.empty_like(y)
+    scal = torch.zeros(8, device=dev); flag = torch.zeros(1, dtype=torch.int32, device=dev); one = torch.ones(1, device=dev)
+    ftg = torch.randn(N, H // 4, W // 4, device=dev); ftw = torch.randn(C, device=dev)
+    st = HF._stream()
+    wb = torch.empty(query('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, C, C), dtype=torch.uint8, device=dev)
+    extra = {'': (), '_w': (wt.data_ptr(),), SFX: (wt.data_ptr(),) + (() if PARAM is None else (PARAM,))}      # what follows ignore_index
+    wsp = {}
+
+    def ws(name, *a):
+        if (name, a) not in wsp:
+            wsp[name, a] = torch.empty(query(name, *a), dtype=torch.uint8, device=dev)
+        return wsp[name, a].data_ptr(), wsp[name, a].numel()
+
+    def ce_fwd(s):
+        call('dsrl_ce_fwd' + s, y.data_ptr(), C, tg.data_ptr(), P, C, 255, *extra[s], scal.data_ptr(), *ws(f'dsrl_ce{s}_workspace_bytes', P), st)
+
+    def ce_bwd(s):
+        call('dsrl_ce_bwd' + s, y.data_ptr(), C, tg.data_ptr(), P, C, 255, *extra[s], scal.data_ptr(), one.data_ptr(), dl.data_ptr(), C, st)
+
+    def ce_fused(s):
+        call('dsrl_ce_fused' + s, y.data_ptr(), C, tg.data_ptr(), P, C, 255, *extra[s], dl.data_ptr(), C, scal.data_ptr(), flag.data_ptr(),
+             *ws(f'dsrl_ce_fused{s}_workspace_bytes', P), st)
+
+    def fwd_ce(s):
+        call('dsrl_convt2x2_fwd_ce' + s, x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), N, H, W, C, C, tg.data_ptr(), 255, *extra[s],
+             scal.data_ptr(), flag.data_ptr(), *ws(f'dsrl_convt2x2_fwd_ce{s}_workspace_bytes', N, H, W), st)
+
+    def bwd_ce(s):
+        call('dsrl_convt2x2_bwd_ce' + s, x.data_ptr(), w.data_ptr(), y.data_ptr(), tg.data_ptr(), 255, *extra[s], scal.data_ptr() + 4,
+             ftg.data_ptr(), ftw.data_ptr(), 8, dx.data_ptr(), dw.data_ptr(), db.data_ptr(), N, H, W, C, C, wb.data_ptr(), wb.numel(), st)
+
+    t = {}
+    for s in (BASE, SFX):
+        t['fwd_ce' + s] = timeit(lambda: fwd_ce(s))
+    for waves in ('12', '8'):                   # the focal and the smoothed backward are the 8-wave build under either setting
+        os.environ['DSRL_CONVT_CE_WAVES'] = waves
+        for s in (BASE, SFX):
+            fwd_ce(s)                           # its pixel count or D in scal[1]
+            t[f'bwd_ce{s}/{waves}'] = timeit(lambda: bwd_ce(s))
+    os.environ.pop('DSRL_CONVT_CE_WAVES')
+    for s in (BASE, SFX):
+        t['ce_fused' + s] = timeit(lambda: ce_fused(s))
+    if VARIANT == 'weighted':
+        wd = ws('dsrl_ce_weight_sum_workspace_bytes')
+        t['D pre-pass'] = timeit(lambda: call('dsrl_ce_weight_sum', tg.data_ptr(), P, C, 255, wt.data_ptr(), scal.data_ptr() + 4, *wd, st))
+        say(f'kernel-only, us per call (N = {N}, tail input {H} x {W}, {P} labels = {P / 1e6:.1f} MB; mean of 20 back-to-back calls):')
+        say(f"  dsrl_convt2x2_fwd_ce      {t['fwd_ce']:7.1f}   weighted {t['fwd_ce_w']:7.1f}   (+{t['fwd_ce_w'] - t['fwd_ce']:.1f}; the weighted call holds the D pre-pass)")
+        for waves in ('12', '8'):
+            a, bb = t[f'bwd_ce/{waves}'], t[f'bwd_ce_w/{waves}']
+            say(f'  dsrl_convt2x2_bwd_ce ({waves:>2} waves) {a:7.1f}   weighted {bb:7.1f}   ({bb - a:+.1f})')
+        say(f"  dsrl_ce_fused             {t['ce_fused']:7.1f}   weighted {t['ce_fused_w']:7.1f}   ({t['ce_fused_w'] - t['ce_fused']:+.1f}; count pre-pass -> D pre-pass)")
+        say(f"  D pre-pass alone (class_hist_kernel + ce_weight_sum_kernel) {t['D pre-pass']:.1f}")
+        return
+    for key, f in (('ce_fwd', ce_fwd), ('ce_bwd', ce_bwd)):
+        for s in (BASE, SFX):
+            t[key + s] = timeit(lambda: f(s))
+    say(f'kernel-only, us per call (N = {N}, tail input {H} x {W}, {P} pixels; {PNAME} = {PARAM}; mean of 20 back-to-back calls; every call but ce_bwd and')
+    say('convt2x2_bwd_ce holds the D pre-pass):')
+    for path, label, key in (('A', 'dsrl_ce_fwd', 'ce_fwd'), ('A', 'dsrl_ce_bwd', 'ce_bwd'), ('B', 'dsrl_ce_fused', 'ce_fused'), ('C', 'dsrl_convt2x2_fwd_ce', 'fwd_ce')):
+        a, bb = t[key + BASE], t[key + SFX]
+        say(f'  {path}  {label:<22} weighted {a:7.1f}   {WORD} {bb:7.1f}   ({bb - a:+.1f})')
+    for waves in ('12', '8'):
+        a, bb = t[f'bwd_ce{BASE}/{waves}'], t[f'bwd_ce{SFX}/{waves}']
+        say(f'  D  dsrl_convt2x2_bwd_ce   weighted {a:7.1f} ({waves:>2} waves)   {WORD} {bb:7.1f} (8 waves, DSRL_CONVT_CE_WAVES={waves})   ({bb - a:+.1f})')
+
+
+def replayed_step():
+    import dualsuperreslearningforsemseg_amd as D
+    from dualsuperreslearningforsemseg_amd import settings
+    from dualsuperreslearningforsemseg_amd.command_handlers.train_or_resume import SyntheticCityscapes, TrainStep
+    from dualsuperreslearningforsemseg_amd.datasets.Cityscapes import settings as cs
+    from dualsuperreslearningforsemseg_amd.ddp import FlatParams
+    torch.manual_seed(settings.RANDOM_SEED)
+    model = D.DSRL(3, cs)
+    with torch.no_grad():
+        for m in model.modules():
+            if hasattr(m, 'bn3'):
+                m.bn3.weight.fill_(0.5)
+    model = model.to(dev).to(memory_format=torch.channels_last).train()
+    flat = FlatParams(model)
+    (img, org), (tgt, _) = next(iter(SyntheticCityscapes(8, (256, 512), torch.device(dev), length=1)))
+    w = np.random.RandomState(2).uniform(0.25, 8.0, cs.NUM_CLASSES)
+
+    def run(step, n):
+        for _ in range(n):
+            step.enqueue(img, org, tgt, 0.0, 0.9, 0.0, True)      # lr 0: every step trains the same parameters
+            while step.pending() > 1:
+                step.collect()
+        while step.pending():
+            step.collect()
+    if VARIANT == 'weighted':
+        kinds = {'unweighted': {}, 'weighted': {'class_weights': w}}
+    else:
+        kinds = {'default': {}, 'weighted': {'class_weights': w}, WORD: {'class_weights': w, STEP_KW: PARAM}}
+    res, replays = {k: [] for k in kinds}, {}
+    for _ in range(2):                          # one captured step at a time (the device-resident dropout key has one binding): build, warm, time, release
+        for k, kw in kinds.items():
+            s = TrainStep(model, flat, 3, 0.1, 1.0, cs.IGNORE_CLASS_LABEL, **kw)
+            run(s, s.GRAPH_WARMUP + 6)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(s, STEPS)
+            torch.cuda.synchronize()
+            res[k].append((time.perf_counter() - t0) / STEPS * 1e3)
+            replays[k] = s.graph_replays
+            s.release()
+    say(f'replayed step (stage 3, batch 8, 256 x 512, {STEPS} steps per figure, two alternating rounds in one process), ms per step:')
+    width = 11 if VARIANT == 'weighted' else 9
+    for k in res:
+        say(f'  {k:<{width}} ' + '  '.join(f'{v:.3f}' for v in res[k]) + f'   min {min(res[k]):.3f}  (replays {replays[k]})')
+    if VARIANT == 'weighted':
+        say(f"  weighted - unweighted (min): {(min(res['weighted']) - min(res['unweighted'])) * 1e3:+.0f} us")
+    else:
+        say(f"  {WORD} - weighted (min): {(min(res[WORD]) - min(res['weighted'])) * 1e3:+.0f} us;  {WORD} - default (min): "
+            f"{(min(res[WORD]) - min(res['default'])) * 1e3:+.0f} us")
+
+
+kernels()
+if '--no-step' not in args:
+    replayed_step()
+out = os.path.join(ROOT, 'profiles', OUT)
+os.makedirs(os.path.dirname(out), exist_ok=True)
+KEEP = '## recorded beside the tool'            # the same-box A/B against the parent commit and the kernel resource tables: kept across runs
+tail = ''
+if os.path.isfile(out):
+    old = open(out).read()
+    if KEEP in old:
+        tail = old[old.index(KEEP):]
+with open(out, 'w') as f:
+    f.write('\n'.join(lines) + '\n' + tail)
