@@ -157,10 +157,16 @@ PROTOTYPES = {
     'dsrl_fa_fwd': (i32, [fp, fp, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, fp, fp, fp, sz, stream_t]),
     'dsrl_fa_bwd': (i32, [fp, fp, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, fp, fp, fp, fp, fp, sz, stream_t]),
     'dsrl_seg_metrics': (i32, [fp, i32, fp, i64, i32, i32, fp, stream_t]),
+    'dsrl_seg_metrics_cm_max_classes': (i32, []),
+    'dsrl_seg_metrics_cm': (i32, [fp, i32, fp, i64, i32, i32, fp, fp, stream_t]),
+    'dsrl_confusion_matrix_max_classes': (i32, []),
+    'dsrl_confusion_matrix': (i32, [fp, fp, i64, i32, i32, fp, fp, stream_t]),
     'dsrl_sssr_tail_predict_supported': (i32, [i32] * 6),
     'dsrl_sssr_tail_predict_workspace_bytes': (sz, [i32] * 3),
     'dsrl_sssr_tail_predict': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, stream_t]),
     'dsrl_sssr_tail_predict_flip': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, stream_t]),
+    'dsrl_sssr_tail_predict_cm': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, fp, stream_t]),
+    'dsrl_sssr_tail_predict_flip_cm': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, fp, stream_t]),
     'dsrl_fingerprint_segment_words': (i32, []),
     'dsrl_fingerprint_segments': (i32, [fp, i64, fp, fp, fp, i32, stream_t]),
     'dsrl_class_map_visualize': (i32, [fp, fp, fp, fp, fp, i32, i32, i32, i32, C.c_double, stream_t]),

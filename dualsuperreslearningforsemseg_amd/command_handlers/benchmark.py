@@ -7,14 +7,19 @@ without augmentation, every sample), and the host reads the device ONCE, after t
 `compiled_model=True` in other_args: `weights` names a file of the compile_model command and the batches run through inference.CompiledPredictor (the
 full batch and the last short one are two of its graph keys); the figures are the same.
 `flip=True` in other_args: every batch is evaluated as the horizontal-flip ensemble (`DSRL.predict(flip=True)`: the image and its mirror image, class
-probabilities averaged); benchmark.txt then says so."""
+probabilities averaged); benchmark.txt then says so.
+Beside the reference's per-batch figures the command accumulates ONE confusion matrix over the split on the device (the kernel that writes the
+class map fills it; it comes back in the same single read) and reports the dataset-level figures from it - intersections and unions summed over the
+split, then IoU per class, then the mean over the classes, as Cityscapes results are published - with a per-class table in benchmark.txt and the
+matrix itself in confusion_matrix.npy."""
 import os
 from datetime import datetime
 
+import numpy as np
 import torch as t
 
 from .. import settings
-from ..metrices import Accuracy, AverageMeter, mIoU
+from ..metrices import Accuracy, AverageMeter, ConfusionMatrix, mIoU
 from ..models import DSRL
 from ..utils import load_checkpoint_or_weights
 from .train_or_resume import isCUDAdevice
@@ -63,16 +68,18 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
 
     nan_flag = t.zeros((), dtype=t.int32, device=device_obj)
     ces, tables = [], []
+    nc = ds.NUM_CLASSES
+    confusion = t.zeros(nc * nc, dtype=t.int64, device=device_obj)
     try:
         for (input_image, _), (target, _) in loader:
-            _, counts, ce = predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag, flip=flip)
+            _, counts, ce = predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag, flip=flip, confusion=confusion)
             ces.append(ce)
             tables.append(counts)
         if not ces:
             raise RuntimeError(f"the '{split}' split yielded no batch")
-        # the one device -> host read: losses, NaN flag and counters in a single float64 tensor (counters < 2^53: exact)
-        nb, nc = len(ces), ds.NUM_CLASSES
-        host = t.cat([t.stack(ces).double(), nan_flag.double().reshape(1), t.stack(tables).double().reshape(-1)]).cpu()
+        # the one device -> host read: losses, NaN flag, counters and the confusion matrix in a single float64 tensor (counters < 2^53: exact)
+        nb = len(ces)
+        host = t.cat([t.stack(ces).double(), nan_flag.double().reshape(1), t.stack(tables).double().reshape(-1), confusion.double()]).cpu()
     finally:
         if predictor is not None:
             predictor.release()             # drops the graphs and restores the conv arithmetic the file selected
@@ -81,15 +88,28 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
         raise RuntimeError('benchmark: ' + ' and '.join(m for b, m in ((1, 'NaN in the input or the logits'), (2, 'labels outside the classes')) if bits & b))
     CE_avg_loss = AverageMeter()
     miou, accuracy_mean = mIoU(num_classes=nc, ignore_index=ds.IGNORE_CLASS_LABEL), Accuracy(num_classes=nc, ignore_index=ds.IGNORE_CLASS_LABEL)
-    host_tables = host[nb + 1:].reshape(nb, 3 * nc + 2).to(t.int64)
+    host_tables = host[nb + 1:nb + 1 + nb * (3 * nc + 2)].reshape(nb, 3 * nc + 2).to(t.int64)
     for i in range(nb):
         CE_avg_loss.update(float(host[i]), batch_size)          # weighted by the nominal batch size, the last short batch included, as the reference
         miou.update_from_counts(host_tables[i])
         accuracy_mean.update_from_counts(host_tables[i])
     result = {'CE': CE_avg_loss(), 'mIoU': miou(), 'accuracy': accuracy_mean()}
+    whole = ConfusionMatrix(nc, ds.IGNORE_CLASS_LABEL)
+    whole.merge(host[nb + 1 + nb * (3 * nc + 2):].to(t.int64))
+    fig = whole.result()
+    result.update({'mIoU_dataset': fig['mIoU'], 'IoU_per_class': [float(v) for v in fig['IoU']], 'pixel_accuracy': fig['pixel_accuracy'],
+                   'mean_class_accuracy': fig['mean_class_accuracy'], 'fwIoU': fig['fwIoU'], 'confusion_matrix': fig['matrix'].tolist()})
 
     lines = ['Avg. Cross Entropy Error: {:.3f}'.format(result['CE']), 'mIoU %: {:.2f}'.format(result['mIoU']),
              'Mean Accuracy %: {:.2f}'.format(result['accuracy'])]
+    names = list(getattr(ds, 'CLASS_NAMES', ()))
+    names = [names[k] if k < len(names) else 'class {:d}'.format(k) for k in range(nc)]
+    width = max(len(n) for n in names)
+    lines += ['', 'Dataset-level mIoU %: {:.2f}'.format(result['mIoU_dataset']),
+              'Dataset-level pixel accuracy %: {:.2f}, mean class accuracy %: {:.2f}, frequency-weighted IoU %: {:.2f}'.format(
+                  result['pixel_accuracy'], result['mean_class_accuracy'], result['fwIoU']),
+              '', '{:<{w}s}  {:>7s}  {:>8s}'.format('class', 'IoU %', 'recall %', w=width)]
+    lines += ['{:<{w}s}  {:>7.2f}  {:>8.2f}'.format(n, i, r, w=width) for n, i, r in zip(names, fig['IoU'], fig['class_accuracy'])]
     print('-------- RESULTS --------')
     for ln in lines:
         print(ln)
@@ -103,4 +123,5 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
             f.write('Horizontal-flip ensemble: class probabilities of the image and its mirror image averaged\n')
         f.write('\n')
         f.write('\n'.join(lines) + '\n')
+    np.save(os.path.join(output_dir, 'confusion_matrix.npy'), fig['matrix'])
     return result

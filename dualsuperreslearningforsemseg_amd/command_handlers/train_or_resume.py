@@ -547,7 +547,9 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
                         if os.path.isfile(stale):
                             os.remove(stale)
                 if val_loader is not None and epoch % val_interval == 0:                                            # :294
-                    rec['val'] = _do_train_val(False, epoch, model, step, val_loader, lr, momentum, weights_decay, False, True)
+                    details = {}
+                    rec['val'] = _do_train_val(False, epoch, model, step, val_loader, lr, momentum, weights_decay, False, True, details)
+                    rec['val_mIoU_dataset'], rec['val_IoU_per_class'] = rec['val'][6], details['IoU_per_class']
                     CE_val_avg_loss, MSE_val_avg_loss, FA_val_avg_loss, Avg_val_loss, val_mIoU = rec['val'][:5]
                     if val_mIoU > best_validation_dict['best_miou_percent']:                                        # :318-337
                         best_validation_dict = {'epoch': epoch, 'best_miou_percent': val_mIoU, 'loss': Avg_val_loss}
@@ -580,18 +582,22 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     return history
 
 
-def _do_train_val(do_train, epoch, model, step, data_loader, lr, momentum, weights_decay, freeze_batch_norm, is_master_rank):
+def _do_train_val(do_train, epoch, model, step, data_loader, lr, momentum, weights_decay, freeze_batch_norm, is_master_rank, details=None):
     """train_or_resume.py:373-533 without the progress-bar / TensorBoard plumbing. Returns the running means
-    (CE, MSE, FA, Total, mIoU %, accuracy %); the last two only for validation."""
+    (CE, MSE, FA, Total, mIoU %, accuracy %) and, as a last element, the dataset-level mIoU % (metrices.ConfusionMatrix over the whole loader);
+    the last three only for validation.  Everything decided from a validation - best checkpoint, early stopping - uses the reference's per-batch
+    mIoU.  `details` (a dict, optional) receives 'IoU_per_class' of the dataset-level figure."""
     model.train(mode=do_train)
     if do_train and freeze_batch_norm:
         for m in model.modules():
             if isinstance(m, t.nn.modules.batchnorm._BatchNorm):
                 m.eval()                                                                   # :379-382
-    from ..metrices import Accuracy, AverageMeter, mIoU
+    from ..metrices import Accuracy, AverageMeter, ConfusionMatrix, mIoU
     meters = [AverageMeter() for _ in range(4)]                                            # CE, MSE, FA, Total (:385-388)
     nc = model.SSSR_decoder['cls_conv'].out_channels
     miou, mean_accuracy = mIoU(num_classes=nc, ignore_index=step.ignore), Accuracy(num_classes=nc, ignore_index=step.ignore)
+    whole = ConfusionMatrix(num_classes=nc, ignore_index=step.ignore)
+    whole_fits = nc <= ConfusionMatrix.max_classes_from_logits()        # beyond it the one-pass kernel has no room for the matrix: the figure is NaN
     sizes = []
 
     def drain(keep):
@@ -606,7 +612,12 @@ def _do_train_val(do_train, epoch, model, step, data_loader, lr, momentum, weigh
         if not do_train and is_master_rank:
             miou.update_from_logits(outs[0], target)                                       # argmax + histograms on the device (:476-480)
             mean_accuracy.update_from_logits(outs[0], target)
+            if whole_fits:
+                whole.update_from_logits(outs[0], target)
         drain(1)              # the losses of iteration k are read while iteration k+1 is already queued
     drain(0)
-    return [m() for m in meters] + [miou() if not do_train else 0.0, mean_accuracy() if not do_train else 0.0]
+    fig = whole.result() if not do_train else None
+    if details is not None and fig is not None:
+        details['IoU_per_class'] = [float(v) for v in fig['IoU']]
+    return [m() for m in meters] + [miou() if not do_train else 0.0, mean_accuracy() if not do_train else 0.0, fig['mIoU'] if fig is not None else 0.0]
 

@@ -764,11 +764,18 @@ __global__ __launch_bounds__(256) void nan_check_kernel(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------- validation metrics
+// CM: the confusion matrix cmh[t * C + p] beside the table, in dynamic LDS behind the staged logits (C <= kSegMetricsCmMaxC keeps both under 64 KB);
+// `counts` may then be null.
+constexpr int kSegMetricsCmMaxC = 48;
+template <bool CM>
 __global__ __launch_bounds__(256) void seg_metrics_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
-                                                           int ignore_index, unsigned long long* __restrict__ counts) {
-    extern __shared__ float tile[];                     // [256][C] logits, then 3*C+2 unsigned counters
+                                                           int ignore_index, unsigned long long* __restrict__ counts, unsigned long long* __restrict__ cm) {
+    extern __shared__ float tile[];                     // [256][C] logits; CM: then [C][C] unsigned bins
     __shared__ unsigned hist[3 * 64 + 2];
+    unsigned* cmh = reinterpret_cast<unsigned*>(tile + 256 * C);
     for (int t = threadIdx.x; t < 3 * C + 2; t += 256) hist[t] = 0u;
+    if (CM)
+        for (int t = threadIdx.x; t < C * C; t += 256) cmh[t] = 0u;
     for (long long p0 = (long long)blockIdx.x * 256; p0 < P; p0 += (long long)gridDim.x * 256) {
         const int np = (int)min(256ll, P - p0);
         __syncthreads();
@@ -784,11 +791,90 @@ __global__ __launch_bounds__(256) void seg_metrics_kernel(const float* __restric
                 atomicAdd(&hist[2 * C + tg], 1u);
                 atomicAdd(&hist[3 * C + 1], 1u);
                 if (best == tg) { atomicAdd(&hist[C + tg], 1u); atomicAdd(&hist[3 * C], 1u); }
+                if (CM) atomicAdd(&cmh[tg * C + best], 1u);
             }
         }
     }
     __syncthreads();
-    for (int t = threadIdx.x; t < 3 * C + 2; t += 256) if (hist[t]) atomicAdd(&counts[t], (unsigned long long)hist[t]);
+    if (!CM || counts != nullptr)
+        for (int t = threadIdx.x; t < 3 * C + 2; t += 256) if (hist[t]) atomicAdd(&counts[t], (unsigned long long)hist[t]);
+    if (CM)
+        for (int t = threadIdx.x; t < C * C; t += 256) if (cmh[t]) atomicAdd(&cm[t], (unsigned long long)cmh[t]);
+}
+
+// ---------------------------------------------------------------------------------------------- confusion matrix of two class maps
+// cm[t * C + p] += 1 for every pixel whose target t is counted (t != ignore_index, t < C) and whose predicted class p is < C; a p >= C on a counted
+// pixel raises bit 1 of nan_flag instead.  16 pixels of each map per iteration in 16-byte loads, whatever byte either map starts at (block 0 takes
+// the head up to the target's first 16-byte boundary and the tail byte by byte).  LDS bins per wave
+// (kCmCopies sets when C * C <= kCmCopyBins, else one), merged and flushed once per block as 64-bit atomics: exact and order independent.
+constexpr int kCmBlocks = 512;
+constexpr int kCmMaxC = 64;
+constexpr int kCmCopyBins = 1024, kCmCopies = 4;
+constexpr long long kCmLaunchPixels = 1ll << 40;        // per block <= 2^31 + 2^12 pixels: no 32-bit LDS bin can wrap
+// A lane's 16 pixels are consecutive: a run of equal (t, p) pairs leaves as ONE LDS atomic of its length, so a map that is one class over most pixels
+// does not serialise a wave on one bin.  k < 0: a pixel that is not counted.
+struct CmRun {
+    int key = -1;
+    unsigned n = 0u;
+    __device__ __forceinline__ void flush(unsigned* h) { if (n) atomicAdd(&h[key], n); n = 0u; }
+    __device__ __forceinline__ void add(unsigned* h, int k) {
+        if (k != key) { flush(h); key = k; }
+        n += k >= 0 ? 1u : 0u;
+    }
+};
+__device__ __forceinline__ int cm_key(unsigned t, unsigned p, int C, int ignore_index, bool& bad) {
+    const bool live = (int)t != ignore_index && (int)t < C;
+    bad |= live && (int)p >= C;
+    return (live && (int)p < C) ? (int)t * C + (int)p : -1;
+}
+__global__ __launch_bounds__(256) void confusion_matrix_kernel(const unsigned char* __restrict__ pred, const unsigned char* __restrict__ target, long long P, int C,
+                                                                int ignore_index, int copies, unsigned long long* __restrict__ cm, int* __restrict__ nan_flag) {
+    extern __shared__ unsigned cmbins[];                // [copies][C * C]
+    const int bins = C * C;
+    for (int t = threadIdx.x; t < copies * bins; t += 256) cmbins[t] = 0u;
+    __syncthreads();
+    unsigned* h = cmbins + (copies > 1 ? (int)(threadIdx.x >> 6) * bins : 0);
+    bool bad = false;
+    CmRun run;
+    // The body starts at the target's first 16-byte boundary.  pred + head is `m` bytes past a boundary of its own: its 16 pixels come from the two
+    // aligned quads that hold them (both hold a pixel of the map, so neither load leaves the 16-byte granules the map occupies), shifted together.
+    const long long head = min(P, (long long)((16 - ((uintptr_t)target & 15)) & 15));
+    const long long nv = (P - head) >> 4;
+    const int m = (int)((uintptr_t)(pred + head) & 15), q = m >> 2, r = m & 3;
+    const uint4* pv = reinterpret_cast<const uint4*>(pred + head - m);
+    const uint4* tv = reinterpret_cast<const uint4*>(target + head);
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < nv; e += (long long)gridDim.x * 256) {
+        const uint4 qt = tv[e], lo = pv[e];
+        unsigned wp[4] = {lo.x, lo.y, lo.z, lo.w};
+        if (m) {
+            const uint4 hi = pv[e + 1];
+            const unsigned w[9] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w, 0u};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const unsigned a = q == 0 ? w[u] : q == 1 ? w[u + 1] : q == 2 ? w[u + 2] : w[u + 3];
+                const unsigned b = q == 0 ? w[u + 1] : q == 1 ? w[u + 2] : q == 2 ? w[u + 3] : w[u + 4];
+                wp[u] = __builtin_amdgcn_alignbyte(b, a, (unsigned)r);          // bytes r .. r + 3 of {b : a}
+            }
+        }
+        const unsigned wt[4] = {qt.x, qt.y, qt.z, qt.w};
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) run.add(h, cm_key((wt[u] >> (8 * b)) & 0xffu, (wp[u] >> (8 * b)) & 0xffu, C, ignore_index, bad));
+    }
+    run.flush(h);
+    if (blockIdx.x == 0) {          // scalar head and tail
+        for (long long e = threadIdx.x; e < head; e += 256) run.add(h, cm_key(target[e], pred[e], C, ignore_index, bad));
+        for (long long e = head + (nv << 4) + threadIdx.x; e < P; e += 256) run.add(h, cm_key(target[e], pred[e], C, ignore_index, bad));
+    }
+    run.flush(h);
+    if (nan_flag != nullptr && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(nan_flag, 2);
+    __syncthreads();
+    for (int t = threadIdx.x; t < bins; t += 256) {
+        unsigned n = cmbins[t];
+        for (int c = 1; c < copies; ++c) n += cmbins[c * bins + t];
+        if (n) atomicAdd(&cm[t], (unsigned long long)n);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------- batch preparation
@@ -1162,8 +1248,38 @@ extern "C" int dsrl_seg_metrics(const float* logits, int ld, const uint8_t* targ
     DSRL_REQUIRE(logits && target && counts && P > 0 && C > 0 && C <= 60 && ld >= C, DSRL_E_BADARG, "seg_metrics: bad arguments (C=%d)", C);
     hipStream_t st = (hipStream_t)stream;
     if (int e = bind_stream_device(st)) return e;
-    hipLaunchKernelGGL(seg_metrics_kernel, dim3(loss_blocks(P)), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C, ignore_index, counts);
+    hipLaunchKernelGGL(seg_metrics_kernel<false>, dim3(loss_blocks(P)), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, (long long)P, C,
+                       ignore_index, counts, (unsigned long long*)nullptr);
     return launch_status("seg_metrics_kernel");
+}
+extern "C" int dsrl_seg_metrics_cm_max_classes(void) { return kSegMetricsCmMaxC; }
+extern "C" int dsrl_seg_metrics_cm(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, unsigned long long* counts,
+                                   unsigned long long* cm, dsrl_stream_t stream) {
+    DSRL_REQUIRE(logits && target && cm && P > 0 && C > 0 && ld >= C, DSRL_E_BADARG, "seg_metrics_cm: bad arguments (C=%d)", C);
+    DSRL_REQUIRE(C <= kSegMetricsCmMaxC, DSRL_E_UNSUPPORTED, "seg_metrics_cm: %d classes, the staged logits and the matrix fit the LDS up to %d", C,
+                 kSegMetricsCmMaxC);
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    hipLaunchKernelGGL(seg_metrics_kernel<true>, dim3(loss_blocks(P)), dim3(256), ((size_t)256 * C + (size_t)C * C) * sizeof(float), st, logits, ld, target,
+                       (long long)P, C, ignore_index, counts, cm);
+    return launch_status("seg_metrics_kernel");
+}
+extern "C" int dsrl_confusion_matrix_max_classes(void) { return kCmMaxC; }
+extern "C" int dsrl_confusion_matrix(const uint8_t* pred, const uint8_t* target, int64_t P, int C, int ignore_index, unsigned long long* cm, int* nan_flag,
+                                     dsrl_stream_t stream) {
+    DSRL_REQUIRE(pred && target && cm && P > 0 && C > 0, DSRL_E_BADARG, "confusion_matrix: bad arguments (C=%d)", C);
+    DSRL_REQUIRE(C <= kCmMaxC, DSRL_E_UNSUPPORTED, "confusion_matrix: %d classes, the LDS bins hold up to %d", C, kCmMaxC);
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = bind_stream_device(st)) return e;
+    const int copies = C * C <= kCmCopyBins ? kCmCopies : 1;
+    for (int64_t done = 0; done < P; done += kCmLaunchPixels) {
+        const long long n = std::min<long long>(kCmLaunchPixels, P - done);
+        const int nb = (int)std::max<long long>(1, std::min<long long>(kCmBlocks, ceil_div(n, 4096)));
+        hipLaunchKernelGGL(confusion_matrix_kernel, dim3(nb), dim3(256), (size_t)copies * C * C * sizeof(unsigned), st, pred + done, target + done, n, C,
+                           ignore_index, copies, cm, nan_flag);
+        if (int e = launch_status("confusion_matrix_kernel")) return e;
+    }
+    return DSRL_OK;
 }
 
 extern "C" int dsrl_prepare_batch(const uint8_t* rgb, const uint8_t* labels, const uint8_t* lut, const float* mean, const float* std_,

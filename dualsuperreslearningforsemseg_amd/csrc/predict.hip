@@ -26,20 +26,24 @@ constexpr int kPT = 5;                  // M tiles of 16 rows (80 >= 76) = k-ste
 constexpr int kPredMaxBlocks = 512;     // two blocks of 4 waves per CU
 using f32x4_p = __attribute__((ext_vector_type(4))) float;
 
-template <bool TGT, bool CE>
+template <bool TGT, bool CE, bool CM>
 __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w1,
                                                                     const float* __restrict__ bn_mean, const float* __restrict__ bn_invstd,
                                                                     const float* __restrict__ bn_gamma, const float* __restrict__ bn_beta,
                                                                     const float* __restrict__ w2, const float* __restrict__ bias2,
                                                                     unsigned char* __restrict__ pred, const unsigned char* __restrict__ target, int ignore_index,
                                                                     unsigned long long* __restrict__ counts, double* __restrict__ part, int* __restrict__ nan_flag,
-                                                                    int H, int W, long long P, int ntiles) {
+                                                                    int H, int W, long long P, int ntiles, unsigned long long* __restrict__ cm) {
+    static_assert(!CM || TGT, "the confusion matrix needs a target");
     __shared__ unsigned hist[3 * kPC + 2];
+    __shared__ unsigned cmh[CM ? kPC * kPC : 1];           // CM: cmh[t * kPC + p], per block at most what hist[3 * kPC + 1] receives
     __shared__ double shd[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int px = lane & 15, g = lane >> 4;
     if (TGT) {
         for (int t = tid; t < 3 * kPC + 2; t += 256) hist[t] = 0u;
+        if (CM)
+            for (int t = tid; t < kPC * kPC; t += 256) cmh[t] = 0u;
         __syncthreads();
     }
     // A fragments: A[i = l & 15][k = 4 s + (l >> 4)] of M-tile t
@@ -146,6 +150,7 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
                     atomicAdd(&hist[3 * kPC + 1], 1u);
                     if (best == tg) { atomicAdd(&hist[kPC + tg], 1u); atomicAdd(&hist[3 * kPC], 1u); }
                 }
+                if (CM && valid && tg != ignore_index && tg < kPC) atomicAdd(&cmh[tg * kPC + best], 1u);
                 if (CE && valid) {
                     // ce_fused_kernel's arithmetic: max, exp(v - max), sum, log
                     float m = v[0];
@@ -181,6 +186,9 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
         if (counts != nullptr)
             for (int t = tid; t < 3 * kPC + 2; t += 256)
                 if (hist[t]) atomicAdd(&counts[t], (unsigned long long)hist[t]);
+        if (CM)
+            for (int t = tid; t < kPC * kPC; t += 256)
+                if (cmh[t]) atomicAdd(&cm[t], (unsigned long long)cmh[t]);
     }
     if (CE) {
         if (bad_label) ce_loss = __builtin_nan("");     // torch asserts on such a label; here it poisons the loss, as ce_fused_kernel does
@@ -204,20 +212,25 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
 // ea_c / sa + eb_c / sb, the loss -(logaddexp(la_t, lb_t) - ln 2) of the two log-softmax values in log space (finite where the averaged probability
 // underflows).  View a is reduced to its 19 probabilities before view b's accumulators are formed, so only one set of accumulators is live at a time.
 // Counters, partials, NaN flag and the byte assembly are those of sssr_tail_predict_kernel.
-template <bool TGT, bool CE>
+template <bool TGT, bool CE, bool CM>
 __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w1,
                                                                          const float* __restrict__ bn_mean, const float* __restrict__ bn_invstd,
                                                                          const float* __restrict__ bn_gamma, const float* __restrict__ bn_beta,
                                                                          const float* __restrict__ w2, const float* __restrict__ bias2,
                                                                          unsigned char* __restrict__ pred, const unsigned char* __restrict__ target,
                                                                          int ignore_index, unsigned long long* __restrict__ counts, double* __restrict__ part,
-                                                                         int* __restrict__ nan_flag, int H, int W, long long P, int ntiles) {
+                                                                         int* __restrict__ nan_flag, int H, int W, long long P, int ntiles,
+                                                                         unsigned long long* __restrict__ cm) {
+    static_assert(!CM || TGT, "the confusion matrix needs a target");
     __shared__ unsigned hist[3 * kPC + 2];
+    __shared__ unsigned cmh[CM ? kPC * kPC : 1];           // as sssr_tail_predict_kernel
     __shared__ double shd[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int px = lane & 15, g = lane >> 4;
     if (TGT) {
         for (int t = tid; t < 3 * kPC + 2; t += 256) hist[t] = 0u;
+        if (CM)
+            for (int t = tid; t < kPC * kPC; t += 256) cmh[t] = 0u;
         __syncthreads();
     }
     // Stage-2 fragments stay in registers (two sets: a2 for view a, a2b with tap2 ^ 1 for view b).  The stage-1 fragments do not fit beside them and
@@ -387,6 +400,7 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const fl
                     atomicAdd(&hist[3 * kPC + 1], 1u);
                     if (best == tg) { atomicAdd(&hist[kPC + tg], 1u); atomicAdd(&hist[3 * kPC], 1u); }
                 }
+                if (CM && valid && tg != ignore_index && tg < kPC) atomicAdd(&cmh[tg * kPC + best], 1u);
                 if (CE && valid && tg != ignore_index) {
                     // log(0.5 (pa_t + pb_t)) = logaddexp(la, lb) - ln 2, in log space
                     constexpr float LN2 = 0.693147182464599609375f;
@@ -412,6 +426,9 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const fl
         if (counts != nullptr)
             for (int t = tid; t < 3 * kPC + 2; t += 256)
                 if (hist[t]) atomicAdd(&counts[t], (unsigned long long)hist[t]);
+        if (CM)
+            for (int t = tid; t < kPC * kPC; t += 256)
+                if (cmh[t]) atomicAdd(&cm[t], (unsigned long long)cmh[t]);
     }
     if (CE) {
         if (bad_label) ce_loss = __builtin_nan("");     // as sssr_tail_predict_kernel
@@ -503,14 +520,14 @@ namespace {
 int tail_predict_launch(bool flip, const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
                         const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2, uint8_t* pred,
                         const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag, void* ws, size_t ws_bytes,
-                        dsrl_stream_t stream) {
+                        unsigned long long* cm, dsrl_stream_t stream) {
     DSRL_REQUIRE(x && w1 && bn_mean && bn_invstd && bn_gamma && bn_beta && w2 && pred && N > 0 && H > 0 && W > 0, DSRL_E_BADARG,
                  "sssr_tail_predict: null pointer or empty shape");
     DSRL_REQUIRE(dsrl_sssr_tail_predict_supported(N, H, W, Cin, Cmid, Cout), DSRL_E_UNSUPPORTED,
                  "sssr_tail_predict: needs 19 -> 19 -> 19 channels and N*H*W*16 < 2^31 (got %d -> %d -> %d, %d x %d x %d)", Cin, Cmid, Cout, N, H, W);
     DSRL_REQUIRE(ldx >= Cin && ((uintptr_t)x % 4) == 0 && ((uintptr_t)pred % 4) == 0 && ((uintptr_t)target % 4) == 0, DSRL_E_BADARG,
                  "sssr_tail_predict: ldx < Cin, or x / pred / target not 4-byte aligned");
-    DSRL_REQUIRE(target || (!counts && !ce_out), DSRL_E_BADARG, "sssr_tail_predict: counts / ce_out need a target");
+    DSRL_REQUIRE(target || (!counts && !ce_out && !cm), DSRL_E_BADARG, "sssr_tail_predict: counts / ce_out / cm need a target");
     const long long P = (long long)N * H * W;
     const int nb = predict_blocks(P);
     DSRL_REQUIRE(!ce_out || (ws && ws_bytes >= dsrl_sssr_tail_predict_workspace_bytes(N, H, W) && ((uintptr_t)ws % 8) == 0), DSRL_E_WORKSPACE,
@@ -519,17 +536,21 @@ int tail_predict_launch(bool flip, const float* x, int ldx, int N, int H, int W,
     if (int e = bind_stream_device(st)) return e;
     const int ntiles = (int)ceil_div(P, 16);
     double* part = (double*)ws;
-#define DSRL_PREDICT_LAUNCH(KERNEL, TGT, CE)                                                                                                           \
-    hipLaunchKernelGGL((KERNEL<TGT, CE>), dim3(nb), dim3(256), 0, st, x, ldx, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target,     \
-                       ignore_index, counts, part, nan_flag, H, W, P, ntiles)
+#define DSRL_PREDICT_LAUNCH(KERNEL, TGT, CE, CM)                                                                                                       \
+    hipLaunchKernelGGL((KERNEL<TGT, CE, CM>), dim3(nb), dim3(256), 0, st, x, ldx, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, \
+                       ignore_index, counts, part, nan_flag, H, W, P, ntiles, cm)
     if (flip) {
-        if (!target) DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, false, false);
-        else if (!ce_out) DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, true, false);
-        else DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, true, true);
+        if (!target) DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, false, false, false);
+        else if (cm && !ce_out) DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, true, false, true);
+        else if (cm) DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, true, true, true);
+        else if (!ce_out) DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, true, false, false);
+        else DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, true, true, false);
     } else {
-        if (!target) DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, false, false);
-        else if (!ce_out) DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, true, false);
-        else DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, true, true);
+        if (!target) DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, false, false, false);
+        else if (cm && !ce_out) DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, true, false, true);
+        else if (cm) DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, true, true, true);
+        else if (!ce_out) DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, true, false, false);
+        else DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, true, true, false);
     }
 #undef DSRL_PREDICT_LAUNCH
     if (int e = launch_status(flip ? "sssr_tail_predict_flip_kernel" : "sssr_tail_predict_kernel")) return e;
@@ -547,7 +568,7 @@ extern "C" int dsrl_sssr_tail_predict(const float* x, int ldx, int N, int H, int
                                       const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag, void* ws,
                                       size_t ws_bytes, dsrl_stream_t stream) {
     return tail_predict_launch(false, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
-                               counts, ce_out, nan_flag, ws, ws_bytes, stream);
+                               counts, ce_out, nan_flag, ws, ws_bytes, nullptr, stream);
 }
 
 extern "C" int dsrl_sssr_tail_predict_flip(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
@@ -555,7 +576,24 @@ extern "C" int dsrl_sssr_tail_predict_flip(const float* x, int ldx, int N, int H
                                            uint8_t* pred, const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag,
                                            void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     return tail_predict_launch(true, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
-                               counts, ce_out, nan_flag, ws, ws_bytes, stream);
+                               counts, ce_out, nan_flag, ws, ws_bytes, nullptr, stream);
+}
+
+// the same launches with the confusion matrix beside the counters: cm[t * Cout + p] += pixels with target t and predicted class p
+extern "C" int dsrl_sssr_tail_predict_cm(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                                         const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2, uint8_t* pred,
+                                         const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag, void* ws,
+                                         size_t ws_bytes, unsigned long long* cm, dsrl_stream_t stream) {
+    return tail_predict_launch(false, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
+                               counts, ce_out, nan_flag, ws, ws_bytes, cm, stream);
+}
+
+extern "C" int dsrl_sssr_tail_predict_flip_cm(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                                              const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2,
+                                              uint8_t* pred, const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag,
+                                              void* ws, size_t ws_bytes, unsigned long long* cm, dsrl_stream_t stream) {
+    return tail_predict_launch(true, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
+                               counts, ce_out, nan_flag, ws, ws_bytes, cm, stream);
 }
 
 extern "C" int dsrl_fingerprint_segment_words(void) { return kFingerprintSegWords; }

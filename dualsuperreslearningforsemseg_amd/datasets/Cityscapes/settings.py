@@ -32,3 +32,6 @@ CLASS_RGB_COLOR = {
     18: (119, 11, 32),      # bicycle
     IGNORE_CLASS_LABEL: (0, 0, 0),
 }
+# train-id names in train-id order (the same public label table)
+CLASS_NAMES = ('road', 'sidewalk', 'building', 'wall', 'fence', 'pole', 'traffic light', 'traffic sign', 'vegetation', 'terrain', 'sky', 'person',
+               'rider', 'car', 'truck', 'bus', 'train', 'motorcycle', 'bicycle')

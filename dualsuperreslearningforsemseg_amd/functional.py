@@ -1970,7 +1970,36 @@ def _flip_ensemble(logits):
     return torch.logaddexp(la, lb) - math.log(2.0)
 
 
-def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, counts=None, nan_flag=None, flip=False):
+def check_confusion(confusion, num_classes, device, what='sssr_tail_predict'):
+    """`confusion` as every producer wants it: a contiguous int64 tensor of num_classes^2 elements on `device`"""
+    if confusion.dtype != torch.int64 or confusion.numel() != num_classes * num_classes or not confusion.is_contiguous():
+        raise DsrlHipError(f'{what}: confusion must be a contiguous int64 tensor of {num_classes * num_classes} elements '
+                           f'(got {confusion.dtype}, {confusion.numel()} elements)')
+    _need_gpu(confusion)
+    if confusion.device != device:
+        raise DsrlHipError(f'{what}: confusion is on {confusion.device}, the batch on {device}')
+
+
+def confusion_matrix_(confusion, pred, target, num_classes, ignore_index=255, nan_flag=None):
+    """confusion[t * num_classes + p] += pixels with target t and predicted class p, from two class maps of the same shape (dsrl_confusion_matrix):
+    targets equal to `ignore_index` or >= num_classes are not counted; a predicted class >= num_classes on a counted pixel raises bit 1 of `nan_flag`
+    (int32 device scalar, optional) and is not counted.  `confusion`: int64, num_classes^2 elements, accumulated."""
+    with torch.no_grad():
+        _need_gpu(pred, target, nan_flag)
+        check_confusion(confusion, int(num_classes), pred.device, 'confusion_matrix_')
+        if tuple(pred.shape) != tuple(target.shape):
+            raise DsrlHipError(f'confusion_matrix_: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape')
+        if nan_flag is not None and (nan_flag.dtype != torch.int32 or nan_flag.numel() != 1):
+            raise DsrlHipError('confusion_matrix_: nan_flag must be an int32 scalar')
+        pred = (pred if pred.dtype == torch.uint8 else pred.to(torch.uint8)).contiguous()
+        target = (target if target.dtype == torch.uint8 else target.to(torch.uint8)).contiguous()
+        if pred.numel():
+            call('dsrl_confusion_matrix', pred.data_ptr(), target.data_ptr(), pred.numel(), int(num_classes), int(ignore_index), confusion.data_ptr(),
+                 None if nan_flag is None else nan_flag.data_ptr(), _stream())
+    return confusion
+
+
+def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, counts=None, nan_flag=None, flip=False, confusion=None):
     """Eval-mode tail of the SSSR decoder after its bilinear x2 (DSRL.py:55-69): ConvTranspose2d k2 s2 `convt1` -> BatchNorm2d `bn` (running statistics)
     -> ReLU -> ConvTranspose2d k2 s2 `convt2` -> arg-max, as one launch that writes class indices and never the logits (dsrl_sssr_tail_predict).
     -> (pred uint8 (N,4H,4W), ce): with `target` (N,4H,4W) `ce` is the 0-d device tensor of nn.CrossEntropyLoss(ignore_index) of the logits and
@@ -1978,11 +2007,16 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
     label outside the classes.  Heads the kernel does not implement run the modules one by one and reduce their logits.
     `flip=True`: the horizontal-flip ensemble.  `x` is (2N,...): image N + n is the tail input computed from the MIRRORED image n, still in the mirrored
     frame.  -> N class maps: the arg-max of the two views' averaged class probabilities (the second view mirrored back), `ce` the loss of their
-    logarithm, `target` (N,4H,4W); the same single launch (dsrl_sssr_tail_predict_flip), still no logits in memory."""
+    logarithm, `target` (N,4H,4W); the same single launch (dsrl_sssr_tail_predict_flip), still no logits in memory.
+    `confusion` (int64 [classes^2], optional, needs a target) gets the confusion matrix of the returned class map ADDED: confusion[t * classes + p] =
+    pixels with target t and predicted class p, by the same launch (dsrl_sssr_tail_predict_cm / _flip_cm); heads the kernel does not implement
+    count it from `pred` (dsrl_confusion_matrix).  Without it the launches are those of a call that does not know the argument."""
+    if confusion is not None and target is None:
+        raise DsrlHipError('sssr_tail_predict: confusion needs a target')
     with torch.no_grad():
         x, ldx = pm(x)
         w1, w2, b2 = convt1.weight, convt2.weight, convt2.bias
-        _need_gpu(w1, w2, b2, bn.weight, bn.bias, bn.running_mean, bn.running_var, target, counts, nan_flag)
+        _need_gpu(w1, w2, b2, bn.weight, bn.bias, bn.running_mean, bn.running_var, target, counts, nan_flag, confusion)
         if bn.training or bn.running_mean is None or bn.running_var is None:
             raise DsrlHipError('sssr_tail_predict: the BatchNorm must be in eval mode and track running statistics')
         N, Ci, H, W = x.shape
@@ -2001,8 +2035,10 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
             target = target.contiguous()
             if target.data_ptr() % 4:
                 target = target.clone()
-        elif counts is not None:
-            raise DsrlHipError('sssr_tail_predict: counts need a target')
+        elif counts is not None or confusion is not None:
+            raise DsrlHipError('sssr_tail_predict: counts and confusion need a target')
+        if confusion is not None:
+            check_confusion(confusion, Co, x.device)
         if counts is not None and (counts.dtype != torch.int64 or counts.numel() != 3 * Co + 2 or not counts.is_contiguous()):
             raise DsrlHipError(f'sssr_tail_predict: counts must be a contiguous int64 tensor of {3 * Co + 2} elements')
         if nan_flag is not None and (nan_flag.dtype != torch.int32 or nan_flag.numel() != 1):
@@ -2020,10 +2056,12 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
             ws = _ws(cquery('dsrl_sssr_tail_predict_workspace_bytes', N, H, W) if ce is not None else 0, x)
             gamma = bn.weight if bn.weight is not None else torch.ones_like(invstd)
             beta = bn.bias if bn.bias is not None else torch.zeros_like(invstd)
-            call('dsrl_sssr_tail_predict_flip' if flip else 'dsrl_sssr_tail_predict', x.data_ptr(), ldx, N, H, W, Ci, Cm, Co, w1.contiguous().data_ptr(), bn.running_mean.data_ptr(),
+            name = ('dsrl_sssr_tail_predict_flip' if flip else 'dsrl_sssr_tail_predict') + ('' if confusion is None else '_cm')
+            call(name, x.data_ptr(), ldx, N, H, W, Ci, Cm, Co, w1.contiguous().data_ptr(), bn.running_mean.data_ptr(),
                  invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w2.contiguous().data_ptr(), None if b2 is None else b2.data_ptr(),
                  pred.data_ptr(), None if target is None else target.data_ptr(), int(ignore_index), None if counts is None else counts.data_ptr(),
-                 None if ce is None else ce.data_ptr(), None if nan_flag is None else nan_flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
+                 None if ce is None else ce.data_ptr(), None if nan_flag is None else nan_flag.data_ptr(), ws.data_ptr(), ws.numel(),
+                 *(() if confusion is None else (confusion.data_ptr(),)), st)
             return pred, (None if ce is None else ce[0])
         # any other head: the modules as the training forward runs them in eval mode, then the reductions over their logits
         y = batch_norm_act(convt1(x), bn, relu=True)
@@ -2040,6 +2078,8 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
         if counts is not None:
             lg, ld = pm(logits)
             call('dsrl_seg_metrics', lg.data_ptr(), ld, target.data_ptr(), N * 16 * H * W, Co, int(ignore_index), counts.data_ptr(), _stream())
+        if confusion is not None:
+            confusion_matrix_(confusion, pred, target, Co, int(ignore_index))
         return pred, cross_entropy(logits, target, int(ignore_index))
 
 

@@ -180,7 +180,7 @@ class FrozenOperands:
 
 
 class _CapturedPredict:
-    __slots__ = ('graph', 'img', 'tgt', 'flag', 'pred', 'counts', 'ce', 'arena', 'keep', 'ignore_index')
+    __slots__ = ('graph', 'img', 'tgt', 'flag', 'pred', 'counts', 'ce', 'cm', 'arena', 'keep', 'ignore_index')
 
 
 _FLAG_MESSAGES = ((1, 'NaN in the input or the logits'), (2, 'labels outside the classes'),
@@ -188,10 +188,13 @@ _FLAG_MESSAGES = ((1, 'NaN in the input or the logits'), (2, 'labels outside the
 
 
 class CompiledPredictor:
-    """`pred, counts, ce = compiled(images, target=None, ignore_index=255, nan_flag=None, flip=False)`: DSRL.predict on frozen operands, replayed from a
-    hipGraph.  `flip` is a call-time option (DSRL.predict(flip=True): the horizontal-flip ensemble), not a property of a compiled model file.
+    """`pred, counts, ce = compiled(images, target=None, ignore_index=255, nan_flag=None, flip=False, confusion=None)`: DSRL.predict on frozen operands,
+    replayed from a hipGraph.  `flip` is a call-time option (DSRL.predict(flip=True): the horizontal-flip ensemble), not a property of a compiled model file.
+    `confusion` (DSRL.predict_head): the caller's matrix gets exactly this batch's counts added, replayed or eager.  A graph never holds the caller's
+    pointer: it fills a static matrix of its own, zeroed by a node of the graph, which the call then adds to the tensor it was given - successive
+    calls may pass different tensors.
 
-    One graph per key (N, H, W, with target, conv arithmetic, flip), captured at the key's first use after GRAPH_WARMUP eager calls (the frozen eager path:
+    One graph per key (N, H, W, with target, conv arithmetic, flip, with confusion), captured at the key's first use after GRAPH_WARMUP eager calls (the frozen eager path:
     the same kernels), at most MAX_GRAPHS keys; further shapes, and every shape when `graph` is False or a capture failed, run the frozen eager path.
     The graph reads static input buffers (the call copies the batch in) and writes static outputs; the call returns copies of them (the class map is
     N*H*W bytes), or with copy=False the static tensors themselves, which the next call with the same key overwrites.
@@ -225,12 +228,12 @@ class CompiledPredictor:
     def num_graphs(self):
         return len(self._graphs)
 
-    def _key(self, images, target, flip=False):
+    def _key(self, images, target, flip=False, confusion=None):
         N, _, H, W = images.shape
-        return (int(N), int(H), int(W), target is not None, HF.get_conv_precision(), bool(flip))
+        return (int(N), int(H), int(W), target is not None, HF.get_conv_precision(), bool(flip), confusion is not None)
 
     # ------------------------------------------------------------------ capture
-    def _capture(self, key, images, target, ignore_index, flip=False):
+    def _capture(self, key, images, target, ignore_index, flip=False, confusion=None):
         """-> the captured call; after a capture that failed None, and this predictor stays on the frozen eager path."""
         c = _CapturedPredict()
         try:
@@ -238,6 +241,7 @@ class CompiledPredictor:
             c.tgt = None if target is None else target.clone()
             c.ignore_index = int(ignore_index)
             c.flag = torch.zeros((), dtype=torch.int32, device=self.device)
+            c.cm = None if confusion is None else torch.zeros_like(confusion)
             c.graph = torch.cuda.CUDAGraph()
             _private_gen[0] += 1
             c.arena = [HF._new_arena(self.device), 0, _private_gen[0], True]      # pinned: it can never be replaced while the graph lives
@@ -245,7 +249,9 @@ class CompiledPredictor:
                 with torch.cuda.graph(c.graph, capture_error_mode='thread_local'):          # linear: one stream, no side streams in an eval forward
                     c.arena[0].zero_()              # first node: every record a replay maxes into starts at zero
                     c.flag.zero_()
-                    c.pred, c.counts, c.ce = self.model.predict(c.img, c.tgt, c.ignore_index, c.flag, flip)
+                    if c.cm is not None:
+                        c.cm.zero_()                # a replay leaves exactly its batch's matrix
+                    c.pred, c.counts, c.ce = self.model.predict(c.img, c.tgt, c.ignore_index, c.flag, flip, c.cm)
         except Exception as e:          # noqa: BLE001
             self.use_graph = False
             HF.abandon_capture(self.device, e, ' of predict', 'this CompiledPredictor continues on the frozen eager path')
@@ -256,26 +262,30 @@ class CompiledPredictor:
         return c
 
     # ------------------------------------------------------------------ the call
-    def __call__(self, images, target=None, ignore_index=255, nan_flag=None, copy=True, flip=False):
+    def __call__(self, images, target=None, ignore_index=255, nan_flag=None, copy=True, flip=False, confusion=None):
         if self.frozen.released:
             raise DsrlHipError('this CompiledPredictor was released: call compile_predict() again')
         self.frozen.check()
         HF._need_gpu(images, target, nan_flag)
         if images.dim() != 4:
             raise DsrlHipError(f'4-D (N,3,H,W) images expected, got shape {tuple(images.shape)}')
+        if confusion is not None:
+            if target is None:
+                raise DsrlHipError('CompiledPredictor: confusion needs a target')
+            HF.check_confusion(confusion, self.model.SSSR_decoder['upsample16_pred'][6].out_channels, images.device, 'CompiledPredictor')
         own = nan_flag is None
-        key = self._key(images, target, flip)
+        key = self._key(images, target, flip, confusion)
         c = self._graphs.get(key)
         if c is not None and target is not None and c.ignore_index != int(ignore_index):
             c = None                                # the label to ignore is a launch argument of the captured kernels: this call runs eagerly
         elif (c is None and self.use_graph and len(self._graphs) < self.MAX_GRAPHS and self._warm.get(key, 0) >= self.GRAPH_WARMUP
               and (target is None or (target.dtype == torch.uint8 and tuple(target.shape) == (images.shape[0], 2 * images.shape[2], 2 * images.shape[3])))):
-            c = self._capture(key, images, target, ignore_index, flip)
+            c = self._capture(key, images, target, ignore_index, flip, confusion)
         with torch.no_grad():
             if c is None:
                 self._warm[key] = self._warm.get(key, 0) + 1
                 flag = torch.zeros((), dtype=torch.int32, device=images.device) if own else nan_flag
-                out = self.model.predict(images, target, ignore_index, flag, flip)
+                out = self.model.predict(images, target, ignore_index, flag, flip, confusion)
                 HF.drop_planes()
             else:
                 if c.img.data_ptr() != images.data_ptr():
@@ -287,6 +297,8 @@ class CompiledPredictor:
                 flag = c.flag
                 if not own:
                     nan_flag.bitwise_or_(flag.reshape(nan_flag.shape))
+                if c.cm is not None:
+                    confusion.add_(c.cm.view_as(confusion))
                 out = (c.pred, c.counts, c.ce)
                 if copy:
                     out = tuple(None if o is None else o.clone() for o in out)

@@ -1,8 +1,10 @@
-"""On-device counterparts of the reference's metrices/ package (AverageMeter.py:16-27, mIoU.py:15-41, Accuracy.py:13-30)."""
+"""On-device counterparts of the reference's metrices/ package (AverageMeter.py:16-27, mIoU.py:15-41, Accuracy.py:13-30), and the dataset-level
+ConfusionMatrix the reference has no counterpart of."""
+import numpy as np
 import torch
 
 from .. import functional as HF
-from .._lib import call
+from .._lib import call, query
 
 
 class AverageMeter:
@@ -111,3 +113,98 @@ class Accuracy:
         if t.shape[0] == 0:
             return 0.0
         return float((t[:, 3 * C] / t[:, 3 * C + 1]).mean() * 100.)
+
+
+class ConfusionMatrix:
+    """Dataset-level evaluation: one C x C matrix summed over a whole split, matrix[t, p] = pixels with target t and predicted class p (targets equal
+    to `ignore_index` or >= C are not counted: the rule of the per-batch counters).  The figures are the published kind - intersections and unions
+    summed over the split, then IoU per class, then the mean over the classes - where mIoU above is the reference's mean over batches of per-batch means.
+
+    `.matrix` is the int64 (C, C) buffer, allocated on first use on the device of what it is fed; every producer adds to it and none clears it, so it
+    can be handed to `DSRL.predict(confusion=cm.matrix)` batch after batch and read once."""
+
+    def __init__(self, num_classes, ignore_index=255):
+        self.num_classes, self.ignore_index = int(num_classes), int(ignore_index)
+        self._matrix = None
+
+    def _on(self, device):
+        if self._matrix is None:
+            self._matrix = torch.zeros((self.num_classes, self.num_classes), dtype=torch.int64, device=device)
+        elif self._matrix.device != torch.device(device):
+            raise ValueError(f'ConfusionMatrix lives on {self._matrix.device}, fed from {device}')
+        return self._matrix
+
+    @property
+    def matrix(self):
+        if self._matrix is None:
+            raise ValueError('ConfusionMatrix.matrix before first use: call on(device), update*() or merge() first')
+        return self._matrix
+
+    def on(self, device):
+        """-> .matrix, allocated on `device` if nothing has been fed yet"""
+        return self._on(torch.device(device))
+
+    def reset(self):
+        if self._matrix is not None:
+            self._matrix.zero_()
+
+    def update(self, pred, target, valid_labels_mask=None):
+        """reference call shape: class maps (B, H, W) and a boolean mask of the pixels that count (device tensors) -> dsrl_confusion_matrix"""
+        assert pred.shape == target.shape, "BUG CHECK: 'pred' and 'target' must be of the same shape of (B, H, W)."
+        HF._need_gpu(pred, target, valid_labels_mask)
+        if valid_labels_mask is not None:
+            target = torch.where(valid_labels_mask.bool(), target.long(), torch.full_like(target.long(), self.ignore_index))
+        HF.confusion_matrix_(self._on(pred.device), pred, target, self.num_classes, self.ignore_index)
+
+    def update_from_logits(self, logits, target):
+        """logits (N, C, H, W): the arg-max and the matrix in one pass over them (dsrl_seg_metrics_cm), no class map in memory"""
+        HF._need_gpu(logits, target)
+        logits, ld = HF.pm(logits)
+        N, C, H, W = logits.shape
+        if C != self.num_classes:
+            raise ValueError(f'logits of {C} classes, expected {self.num_classes}')
+        if target.dtype != torch.uint8:
+            target = target.to(torch.uint8)
+        target = target.contiguous()
+        cm = self._on(logits.device)
+        call('dsrl_seg_metrics_cm', logits.data_ptr(), ld, target.data_ptr(), N * H * W, C, self.ignore_index, None, cm.data_ptr(), HF._stream())
+
+    @staticmethod
+    def max_classes_from_logits():
+        """the largest class count update_from_logits takes (dsrl_seg_metrics_cm_max_classes)"""
+        return int(query('dsrl_seg_metrics_cm_max_classes'))
+
+    def merge(self, other):
+        """adds another ConfusionMatrix or an int64 tensor of C*C elements; a host tensor is taken as it is (and so is its device)"""
+        m = other.matrix if isinstance(other, ConfusionMatrix) else other
+        if m.dtype != torch.int64 or m.numel() != self.num_classes ** 2:
+            raise ValueError(f'merge: an int64 tensor of {self.num_classes ** 2} elements expected, got {m.dtype} of {m.numel()}')
+        self._on(m.device).add_(m.reshape(self.num_classes, self.num_classes))
+
+    def result(self):
+        """The one device read -> dict of float64 figures (percent): IoU and class_accuracy (recall) per class, NaN where a class has no pixels to
+        judge it by; mIoU and mean_class_accuracy their nan-means; pixel_accuracy = trace / total; fwIoU the frequency-weighted IoU; matrix the int64
+        array.  An empty matrix gives NaN figures."""
+        C = self.num_classes
+        m = np.zeros((C, C), np.int64) if self._matrix is None else self._matrix.cpu().numpy().astype(np.int64)
+        return figures(m)
+
+
+def _nanmean(v):
+    ok = ~np.isnan(v)
+    return float(v[ok].mean()) if ok.any() else float('nan')
+
+
+def figures(m):
+    """The figures of ConfusionMatrix.result() from an int64 (C, C) array."""
+    m = np.asarray(m, np.int64)
+    inter = np.diag(m).astype(np.float64)
+    tgt, prd = m.sum(axis=1).astype(np.float64), m.sum(axis=0).astype(np.float64)
+    union, total = tgt + prd - inter, float(m.sum())
+    with np.errstate(divide='ignore', invalid='ignore'):
+        iou = np.where(union > 0, inter / union, np.nan)
+        recall = np.where(tgt > 0, inter / tgt, np.nan)
+        pixel = inter.sum() / total if total > 0 else float('nan')
+        fw = float(np.nansum(tgt * iou) / total) if total > 0 else float('nan')
+    return {'IoU': 100. * iou, 'mIoU': 100. * _nanmean(iou), 'class_accuracy': 100. * recall, 'mean_class_accuracy': 100. * _nanmean(recall),
+            'pixel_accuracy': 100. * float(pixel), 'fwIoU': 100. * fw, 'matrix': m}

@@ -135,11 +135,13 @@ class DSRL(BaseModel):
             return self.forward_head(backbone_features, lowlevel_features)
 
     def predict_head(self, backbone_features: t.Tensor, lowlevel_features: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None,
-                     flip: bool = False):
+                     flip: bool = False, confusion: t.Tensor = None):
         """Inference counterpart of forward_head: the SSSR branch in eval mode down to the bilinear x2 of `upsample16_pred`, then its ConvTranspose ->
         BatchNorm -> ReLU -> ConvTranspose tail and the arg-max as one kernel (functional.sssr_tail_predict) -> (pred uint8 (N,H,W), counts, ce).
-        With `target` (N,H,W): `counts` is the int64 table of dsrl_seg_metrics of this batch (metrices.mIoU / Accuracy.update_from_counts) and `ce` the
-        0-d CrossEntropyLoss(ignore_index); both None otherwise.  `nan_flag` (int32 device scalar) collects bit 0 = NaN logit, bit 1 = label outside
+        With `target` (N,H,W): `counts` is the int64 table of dsrl_seg_metrics of this batch (metrices.mIoU / Accuracy.update_from_counts), a fresh
+        tensor per call, and `ce` the 0-d CrossEntropyLoss(ignore_index); both None otherwise.  `confusion` (int64 device tensor of classes^2 elements,
+        needs a target; metrices.ConfusionMatrix.matrix) gets this batch's confusion matrix [target, predicted] ADDED by the same kernel and is never
+        cleared here: one buffer collects a whole split.  `nan_flag` (int32 device scalar) collects bit 0 = NaN logit, bit 1 = label outside
         the classes; nothing is read back here.  Neither the SISR decoder nor the feature transformers run, whatever the stage.
         `flip=True`: the features are those of 2N images, the second half from the horizontally mirrored images; the tail kernel mirrors that half back
         and averages the two views' class probabilities -> N class maps (functional.sssr_tail_predict(flip=True)), `target` (N,H,W)."""
@@ -156,17 +158,22 @@ class DSRL(BaseModel):
             counts = None
             if target is not None:
                 counts = t.zeros(3 * up[6].out_channels + 2, dtype=t.int64, device=y.device)
-            pred, ce = HF.sssr_tail_predict(y, up[2], up[3], up[6], target=target, ignore_index=ignore_index, counts=counts, nan_flag=nan_flag, flip=flip)
+            pred, ce = HF.sssr_tail_predict(y, up[2], up[3], up[6], target=target, ignore_index=ignore_index, counts=counts, nan_flag=nan_flag, flip=flip,
+                                            confusion=confusion)
         return pred, counts, ce
 
-    def predict(self, x: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None, flip: bool = False):
+    def predict(self, x: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None, flip: bool = False,
+                confusion: t.Tensor = None):
         """Class map of a batch: (pred, counts or None, ce or None), see predict_head.  Runs under no_grad and raises in train mode.  Without a
         `nan_flag` of the caller's the flag is read back here and a NaN logit or an out-of-range label raises; a caller that passes one reads it when
         it chooses to (command_handlers.benchmark: once, after the last batch).
         `flip=True`: the horizontal-flip ensemble.  The trunk runs once on cat([x, x.flip(3)]) (2N images) and the tail kernel forms the ensemble:
-        N class maps, counters and the loss of the averaged class probabilities."""
+        N class maps, counters and the loss of the averaged class probabilities.
+        `confusion`: see predict_head; with `flip` it is the matrix of the ensemble's class map."""
         if self.training:
             raise HF.DsrlHipError('DSRL.predict* is inference: call model.eval() first')
+        if confusion is not None and target is None:
+            raise HF.DsrlHipError('DSRL.predict: confusion needs a target')
         own = nan_flag is None
         with t.no_grad():
             if own:
@@ -178,7 +185,7 @@ class DSRL(BaseModel):
                 both[x.shape[0]:].copy_(x.flip(3))          # 3 channels at input size: torch ops
                 x = both
             backbone_features, lowlevel_features = self.feature_extractor['backbone'](x)
-            out = self.predict_head(backbone_features, lowlevel_features, target, ignore_index, nan_flag, flip)
+            out = self.predict_head(backbone_features, lowlevel_features, target, ignore_index, nan_flag, flip, confusion)
         if own:
             bits = int(nan_flag.item())
             if bits:

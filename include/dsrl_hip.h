@@ -532,6 +532,22 @@ int dsrl_fa_bwd(const float* fm1, const float* fm2, int B, int C, int H, int W, 
  * (pixels whose target is the ignore label are excluded everywhere). 64-bit integer atomics: exact and order independent. */
 int dsrl_seg_metrics(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index,
                      unsigned long long* counts, dsrl_stream_t stream);
+/* Confusion matrix, one convention for every producer: cm is C*C accumulated 64-bit counters, cm[t*C + p] += pixels with target t and predicted
+ * class p, counted under the rule of the table above (target != ignore_index && target < C).  Producers ADD and never clear, so one buffer collects a
+ * whole split; 64-bit integer atomics, exact and order independent.  On zeroed buffers: row sums = area_target, column sums = area_pred, diagonal =
+ * area_inter, total = valid, trace = correct.
+ * dsrl_seg_metrics_cm: dsrl_seg_metrics' single pass over the logits (staged, first maximum) with the matrix beside the table; counts is nullable.
+ *   C <= dsrl_seg_metrics_cm_max_classes() = 48 (256*C staged floats and C*C bins share the default 64 KB of LDS; dsrl_seg_metrics itself goes to 60):
+ *   DSRL_E_UNSUPPORTED above, nothing is launched.
+ * dsrl_confusion_matrix: from two class maps of P bytes each; either may start at any byte (aligned 16-byte loads, scalar head and tail; the loads
+ *   stay inside the 16-byte granules the maps occupy).  A predicted class >= C on a counted pixel is not counted and raises bit 1 (|= 2) of nan_flag (nullable).
+ *   C <= dsrl_confusion_matrix_max_classes() = 64, DSRL_E_UNSUPPORTED above; any P > 0 (launched in spans that keep every 32-bit LDS bin from wrapping). */
+int dsrl_seg_metrics_cm_max_classes(void);
+int dsrl_seg_metrics_cm(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index,
+                        unsigned long long* counts /*nullable*/, unsigned long long* cm /*[C*C]*/, dsrl_stream_t stream);
+int dsrl_confusion_matrix_max_classes(void);
+int dsrl_confusion_matrix(const uint8_t* pred, const uint8_t* target, int64_t P, int C, int ignore_index, unsigned long long* cm /*[C*C]*/,
+                          int* nan_flag /*nullable*/, dsrl_stream_t stream);
 /* Deterministic tail of the training input pipeline (JointImageAndLabelTensor.py:9-16 label remap, JointNormalize.py:11,
  * JointScaledImage.py:27-32): from a decoded RGB uint8 crop (N,Hs,Ws,3) and its label-id map (N,Hs,Ws):
  *   img_in  (N,H,W,4)   = align-corners bilinear resize of ((u8/255 - mean)/std) to the model input size, 4th channel 0
@@ -652,6 +668,19 @@ int dsrl_sssr_tail_predict_flip(const float* x, int ldx, int N, int H, int W, in
                                 const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2 /*nullable*/,
                                 uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index, unsigned long long* counts /*nullable*/,
                                 float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+/* The two launches above with the confusion matrix of the class map they write (the ensemble's with _flip) against target: cm[t*Cout + p] as
+ * dsrl_seg_metrics_cm defines it, ADDED (an LDS matrix per block, one 64-bit atomic per block and non-zero bin).  cm needs a target and neither counts
+ * nor ce_out; with cm null these are dsrl_sssr_tail_predict / _flip themselves.  pred, counts and ce_out are bit-identical to those of the plain entry points. */
+int dsrl_sssr_tail_predict_cm(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                              const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2 /*nullable*/,
+                              uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index, unsigned long long* counts /*nullable*/,
+                              float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes,
+                              unsigned long long* cm /*nullable, [Cout*Cout]*/, dsrl_stream_t stream);
+int dsrl_sssr_tail_predict_flip_cm(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                                   const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2 /*nullable*/,
+                                   uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index, unsigned long long* counts /*nullable*/,
+                                   float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes,
+                                   unsigned long long* cm /*nullable, [Cout*Cout]*/, dsrl_stream_t stream);
 
 /* Fingerprint of tensors that must not change while an inference.FrozenOperands holds operands derived from them (a write through `.data` or a
  * raw pointer moves neither a tensor's address nor its version counter).  table: DEVICE array of nseg rows of 2 int64 {pointer (4-byte aligned),

@@ -15,6 +15,15 @@ the larger of FLOPs / fp32 matrix rate and bytes / HBM rate.  One more table: DS
 and lists the registers of the tail kernels (tools/kernel_resources.py on the built library).
 
     python tools/predict_bench.py --flip [--out profiles/predict_flip.txt]
+
+--confusion measures the device confusion matrix (profiles/predict_confusion.txt), at tail input 256x512, batch 1 and 8, plain and flip, with a target,
+on uniform labels and on labels / predictions that are class 0 on ~90 % of the pixels:
+  (a) the tail with counters and loss and no `confusion` (with --baseline only this: the form that also runs on a tree without the feature),
+  (b) the same call with `confusion`, (c) the two-launch composition: (a), then dsrl_confusion_matrix on its class map,
+  (d) dsrl_confusion_matrix alone on 8x1024x2048 pixels against the time 2 bytes per pixel take at the HBM rate,
+  (e) dsrl_seg_metrics_cm against dsrl_seg_metrics on 8x19x512x1024 logits.
+
+    python tools/predict_bench.py --confusion [--baseline] [--out profiles/predict_confusion.txt]
 """
 import argparse
 import math
@@ -186,14 +195,127 @@ def flip_main(args):
             f.write('\n'.join(lines) + '\n')
 
 
+def _spread(ts):
+    return (max(ts) - min(ts)) / (sum(ts) / len(ts))
+
+
+def confusion_main(args):
+    dev = torch.device('cuda:0')
+    lines = []
+
+    def say(s=''):
+        print(s, flush=True)
+        lines.append(s)
+
+    def windows(fns):
+        """alternating windows over `fns` -> one list of ms per call for each"""
+        for f in fns:
+            for _ in range(3):
+                f()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(args.rounds):
+            for i, f in enumerate(fns):
+                ts[i].append(window(f, args.window))
+        return ts
+
+    def fmt(ts):
+        return f'{sum(ts) / len(ts) * 1e3:8.1f} us [{", ".join(f"{t * 1e3:.1f}" for t in ts)}] spread {100 * _spread(ts):4.1f} %'
+
+    torch.manual_seed(7)
+    up = DSRL._define_SSSR_decoder(256, 48, 256, NC)['upsample16_pred'].to(dev).eval()
+    with torch.no_grad():
+        up[3].running_mean.normal_(0, 0.1); up[3].running_var.uniform_(0.5, 1.5)
+    torch.manual_seed(7)
+    skew = DSRL._define_SSSR_decoder(256, 48, 256, NC)['upsample16_pred'].to(dev).eval()         # the same tail, class 0 pushed up: ~all predictions 0
+    with torch.no_grad():
+        skew[3].running_mean.copy_(up[3].running_mean); skew[3].running_var.copy_(up[3].running_var)
+        skew[6].bias[0] += 20.0
+    H, W = 256, 512
+    say(f'Device confusion matrix, {torch.cuda.get_device_name(0)}, tail input {H}x{W} with a target; windows of >= {args.window} s per side, {args.rounds} '
+        f'alternations; us per call: mean [each window], spread = (max - min) / mean of the windows')
+    say()
+    say('(a) tail with counters and loss, no confusion' + ('' if args.baseline else
+        ';  (b) the same launch with confusion;  (c) (a) followed by dsrl_confusion_matrix on its class map'))
+    for labels, head in (('uniform', up), ('90 % class 0', skew)):
+        for flip in (False, True):
+            for N in (1, 8):
+                x = torch.randn((2 if flip else 1) * N, NC, H, W, device=dev).contiguous(memory_format=torch.channels_last)
+                target = torch.randint(0, NC, (N, 4 * H, 4 * W), device=dev, dtype=torch.uint8)
+                if labels != 'uniform':
+                    target[torch.rand(target.shape, device=dev) < 0.9] = 0
+                target[torch.rand(target.shape, device=dev) < 0.1] = 255
+                counts = torch.zeros(3 * NC + 2, dtype=torch.int64, device=dev)
+                cm = torch.zeros(NC * NC, dtype=torch.int64, device=dev)
+                mods = (head[2], head[3], head[6])
+
+                def a():
+                    return HF.sssr_tail_predict(x, *mods, target=target, counts=counts, flip=flip)
+
+                def b():
+                    return HF.sssr_tail_predict(x, *mods, target=target, counts=counts, flip=flip, confusion=cm)
+
+                def c():
+                    out = HF.sssr_tail_predict(x, *mods, target=target, counts=counts, flip=flip)
+                    HF.confusion_matrix_(cm, out[0], target, NC)
+                    return out
+
+                label = f'{labels:13s} {"flip " if flip else "plain"} N={N}'
+                if args.baseline:
+                    say(f'{label}:  (a) {fmt(windows([a])[0])}')
+                    continue
+                ta, tb, tc = windows([a, b, c])
+                ma, mb, mc = (sum(t) / len(t) for t in (ta, tb, tc))
+                say(f'{label}:  (a) {fmt(ta)}')
+                say(f'{"":25s}  (b) {fmt(tb)}   (b) - (a) {(mb - ma) * 1e3:+7.1f} us ({100 * (mb - ma) / ma:+5.1f} %)')
+                say(f'{"":25s}  (c) {fmt(tc)}   (c) - (b) {(mc - mb) * 1e3:+7.1f} us: the fusion {"pays" if mb <= mc else "DOES NOT PAY"}')
+    if not args.baseline:
+        say()
+        P = 8 * 1024 * 2048
+        floor = 2.0 * P / HBM_BPS
+        say(f'(d) dsrl_confusion_matrix alone, {P} pixels; 2 bytes per pixel at {HBM_BPS / 1e12:.2f} TB/s: {floor * 1e6:.1f} us')
+        cm = torch.zeros(NC * NC, dtype=torch.int64, device=dev)
+        for labels in ('uniform', '90 % class 0'):
+            tg = torch.randint(0, NC, (P,), device=dev, dtype=torch.uint8)
+            pr = torch.where(torch.rand(P, device=dev) < 0.7, tg, torch.randint(0, NC, (P,), device=dev, dtype=torch.uint8))
+            if labels != 'uniform':
+                m = torch.rand(P, device=dev) < 0.9
+                tg[m] = 0; pr[m] = 0
+            tg[torch.rand(P, device=dev) < 0.1] = 255
+            (td,) = windows([lambda: HF.confusion_matrix_(cm, pr, tg, NC)])
+            md = sum(td) / len(td)
+            say(f'{labels:13s}:  {fmt(td)}   {2.0 * P / (md * 1e-3) / 1e12:5.2f} TB/s, {100 * floor / (md * 1e-3):.0f} % of the HBM rate')
+        say()
+        say('(e) A = dsrl_seg_metrics, B = dsrl_seg_metrics_cm (counts and matrix) on 8x19x512x1024 logits')
+        from dualsuperreslearningforsemseg_amd._lib import call
+        logits = torch.randn(8, NC, 512, 1024, device=dev).contiguous(memory_format=torch.channels_last)
+        tg = torch.randint(0, NC, (8, 512, 1024), device=dev, dtype=torch.uint8)
+        tg[torch.rand(tg.shape, device=dev) < 0.1] = 255
+        counts = torch.zeros(3 * NC + 2, dtype=torch.int64, device=dev)
+        Pl = 8 * 512 * 1024
+        ta, tb = windows([lambda: call('dsrl_seg_metrics', logits.data_ptr(), NC, tg.data_ptr(), Pl, NC, 255, counts.data_ptr(), HF._stream()),
+                          lambda: call('dsrl_seg_metrics_cm', logits.data_ptr(), NC, tg.data_ptr(), Pl, NC, 255, counts.data_ptr(), cm.data_ptr(), HF._stream())])
+        ma, mb = sum(ta) / len(ta), sum(tb) / len(tb)
+        say(f'A {fmt(ta)}')
+        say(f'B {fmt(tb)}   B - A {(mb - ma) * 1e3:+7.1f} us ({100 * (mb - ma) / ma:+5.1f} %)')
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
     ap.add_argument('--window', type=float, default=0.5)
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--flip', action='store_true', help='measure the horizontal-flip ensemble (profiles/predict_flip.txt)')
+    ap.add_argument('--confusion', action='store_true', help='measure the device confusion matrix (profiles/predict_confusion.txt)')
+    ap.add_argument('--baseline', action='store_true', help='with --confusion: only (a), the calls a tree without the feature also has')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'predict_bench.py measures on the GPU only'
+    if args.confusion:
+        return confusion_main(args)
     if args.flip:
         return flip_main(args)
     dev = torch.device('cuda:0')
