@@ -1166,7 +1166,8 @@ extern "C" int dsrl_loss_mix(const float* ce, const float* mse, const float* fa,
 }
 
 static int fa_dims(int H, int W, int k, int& hp, int& wp) {
-    DSRL_REQUIRE(k > 0 && H >= k && W >= k, DSRL_E_BADARG, "fa_loss: subsample factor %d larger than the %dx%d map", k, H, W);
+    DSRL_REQUIRE(k > 0, DSRL_E_BADARG, "fa_loss: subsample factor %d must be positive", k);
+    DSRL_REQUIRE(H >= k && W >= k, DSRL_E_BADARG, "fa_loss: subsample factor %d larger than the %dx%d map", k, H, W);
     hp = H / k; wp = W / k;
     DSRL_REQUIRE(hp <= FA_MAXH && wp <= FA_MAXW, DSRL_E_UNSUPPORTED, "fa_loss: pooled map %dx%d exceeds %dx%d", hp, wp, FA_MAXH, FA_MAXW);
     return DSRL_OK;
@@ -1180,9 +1181,9 @@ extern "C" size_t dsrl_fa_workspace_bytes(int B, int C, int H, int W, int k) { (
 
 extern "C" int dsrl_fa_fwd(const float* fm1, const float* fm2, int B, int C, int H, int W, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
                            int k, int reduction, float* out, float* saved, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
-    DSRL_REQUIRE(fm1 && fm2 && out && saved && ws && B > 0 && C > 0 && reduction >= 0 && reduction <= 2, DSRL_E_BADARG, "fa_fwd: bad arguments");
     int hp, wp;
-    if (int e = fa_dims(H, W, k, hp, wp)) return e;
+    if (int e = fa_dims(H, W, k, hp, wp)) return e;         // first: k > W leaves a 'none' output of no elements, whose null pointer is not the reason
+    DSRL_REQUIRE(fm1 && fm2 && out && saved && ws && B > 0 && C > 0 && reduction >= 0 && reduction <= 2, DSRL_E_BADARG, "fa_fwd: bad arguments");
     DSRL_REQUIRE(ws_bytes >= dsrl_fa_workspace_bytes(B, C, H, W, k), DSRL_E_WORKSPACE, "fa_fwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     if (int e = bind_stream_device(st)) return e;

@@ -1863,6 +1863,8 @@ class _FALoss(torch.autograd.Function):
             fm1, fm2 = fm1.contiguous(), fm2.contiguous()
         B, Cc, H, W = fm1.shape
         red = _RED[reduction]
+        if k <= 0:                  # the library refuses it too, but the size of 'none' below divides by k first
+            raise DsrlHipError(f'fa_loss: subsample factor {k} must be positive')
         n = (W // k) ** 2
         out = torch.empty((B, Cc, n * n) if red == 2 else (1,), device=fm1.device, dtype=torch.float32)
         saved = torch.empty(cquery('dsrl_fa_saved_floats', B, Cc, H, W, k), device=fm1.device, dtype=torch.float32)
