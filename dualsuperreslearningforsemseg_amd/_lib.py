@@ -167,6 +167,11 @@ PROTOTYPES = {
     'dsrl_sssr_tail_predict_flip': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, stream_t]),
     'dsrl_sssr_tail_predict_cm': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, fp, stream_t]),
     'dsrl_sssr_tail_predict_flip_cm': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, fp, stream_t]),
+    'dsrl_prob_merge_supported': (i32, [i32] * 6),
+    'dsrl_prob_merge_acc_bytes': (sz, [i32] * 4),
+    'dsrl_prob_merge_workspace_bytes': (sz, [i32] * 3),
+    'dsrl_prob_merge': (i32, [fp, i32] + [i32] * 5 + [fp, i32, i32, i32, stream_t]),
+    'dsrl_prob_merge_finish': (i32, [fp, i32] + [i32] * 5 + [fp, i32, i32, i32, fp, fp, i32, fp, fp, fp, fp, sz, fp, stream_t]),
     'dsrl_fingerprint_segment_words': (i32, []),
     'dsrl_fingerprint_segments': (i32, [fp, i64, fp, fp, fp, i32, stream_t]),
     'dsrl_class_map_visualize': (i32, [fp, fp, fp, fp, fp, i32, i32, i32, i32, C.c_double, stream_t]),

@@ -8,10 +8,14 @@ without augmentation, every sample), and the host reads the device ONCE, after t
 full batch and the last short one are two of its graph keys); the figures are the same.
 `flip=True` in other_args: every batch is evaluated as the horizontal-flip ensemble (`DSRL.predict(flip=True)`: the image and its mirror image, class
 probabilities averaged); benchmark.txt then says so.
+`scales=(0.5, 0.75, ...)` in other_args: every batch is evaluated as the multi-scale ensemble (`DSRL.predict(scales=...)`; combines with `flip`);
+the value is validated before any device work, benchmark.txt names the scales and the view sizes, and with `compiled_model` the command raises
+before it loads anything (graph replay of the multi-scale path is not built).
 Beside the reference's per-batch figures the command accumulates ONE confusion matrix over the split on the device (the kernel that writes the
 class map fills it; it comes back in the same single read) and reports the dataset-level figures from it - intersections and unions summed over the
 split, then IoU per class, then the mean over the classes, as Cityscapes results are published - with a per-class table in benchmark.txt and the
 matrix itself in confusion_matrix.npy."""
+import functools
 import os
 from datetime import datetime
 
@@ -19,6 +23,8 @@ import numpy as np
 import torch as t
 
 from .. import settings
+from .._lib import DsrlHipError
+from ..functional import multiscale_scales_value, multiscale_sizes
 from ..metrices import Accuracy, AverageMeter, ConfusionMatrix, mIoU
 from ..models import DSRL
 from ..utils import load_checkpoint_or_weights
@@ -49,8 +55,12 @@ def split_loader(dataset, split, batch_size, device_obj, input_size):
 
 
 def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
+    scales = multiscale_scales_value(other_args.get('scales'))          # ValueError on a bad value, before any device work
     if not isCUDAdevice(device):
         raise RuntimeError(NOT_GPU)
+    if scales is not None and other_args.get('compiled_model'):
+        from ..inference import MULTISCALE_NOT_COMPILED
+        raise DsrlHipError(MULTISCALE_NOT_COMPILED)
     started = datetime.now()
     input_size = other_args.get('model_input_size', settings.MODEL_INPUT_SIZE)
     device_obj = t.device('cuda', t.cuda.current_device())
@@ -64,6 +74,8 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
         model = load_eval_model(weights, ds, device_obj)
     predict = model.predict if predictor is None else predictor
     flip = bool(other_args.get('flip'))
+    if scales is not None:
+        predict = functools.partial(predict, scales=scales)
     loader = split_loader(dataset, split, batch_size, device_obj, input_size)
 
     nan_flag = t.zeros((), dtype=t.int32, device=device_obj)
@@ -121,6 +133,10 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
         f.write('Weights file: {:s}\n'.format(str(weights)))
         if flip:
             f.write('Horizontal-flip ensemble: class probabilities of the image and its mirror image averaged\n')
+        if scales is not None:
+            f.write('Multi-scale ensemble: scales {:s} of the {:d} x {:d} input -> views of {:s}\n'.format(
+                ', '.join('{:g}'.format(s) for s in scales), int(input_size[0]), int(input_size[1]),
+                ', '.join('{:d} x {:d}'.format(h, w) for h, w in multiscale_sizes(input_size[0], input_size[1], scales))))
         f.write('\n')
         f.write('\n'.join(lines) + '\n')
     np.save(os.path.join(output_dir, 'confusion_matrix.npy'), fig['matrix'])

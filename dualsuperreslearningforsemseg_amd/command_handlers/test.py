@@ -7,7 +7,8 @@ was trained with (the reference's torchvision Resize here is a different one); t
 (data, not TorchScript) and the class maps come from inference.CompiledPredictor - frozen operands and a hipGraph replay, the same bytes.  Either
 way the input | class colours | overlay panels are built on the device (utils.make_input_output_visualization_device): what crosses to the host
 per image is the finished uint8 panel, which PIL encodes.  `flip=True` in other_args: the class maps are those of the horizontal-flip ensemble
-(`DSRL.predict(flip=True)`)."""
+(`DSRL.predict(flip=True)`).  `scales=(...)` in other_args: those of the multi-scale ensemble (`DSRL.predict(scales=...)`; combines with `flip`);
+the value is validated before any device work, and with `compiled_model` the command raises before it reads the file."""
 import functools
 import os
 
@@ -15,6 +16,8 @@ import numpy as np
 import torch as t
 
 from .. import consts, settings
+from .._lib import DsrlHipError
+from ..functional import multiscale_scales_value
 from ..models.transforms import DeviceBatchPreparation
 from ..utils import make_input_output_visualization_device
 from .benchmark import NOT_GPU, load_eval_model, split_loader
@@ -31,9 +34,13 @@ def _save_png(hwc, filename):
 
 @t.no_grad()
 def test(image_file, images_dir, dataset, output_dir, weights, device, compiled_model, **other_args):
+    scales = multiscale_scales_value(other_args.get('scales'))          # ValueError on a bad value, before any device work
     if not isCUDAdevice(device):
         raise RuntimeError(NOT_GPU)
     data = None
+    if compiled_model and scales is not None:
+        from ..inference import MULTISCALE_NOT_COMPILED
+        raise DsrlHipError(MULTISCALE_NOT_COMPILED)
     if compiled_model:
         from ..inference import load_compiled_model, read_compiled_file
         data = read_compiled_file(weights)                  # format, version and ABI are checked on the host, before any device work
@@ -53,6 +60,8 @@ def test(image_file, images_dir, dataset, output_dir, weights, device, compiled_
     try:
         if other_args.get('flip'):
             predict = functools.partial(predict, flip=True)
+        if scales is not None:
+            predict = functools.partial(predict, scales=scales)
         return _run(predict, image_file, images_dir, dataset, ds, output_dir, device_obj, input_size, output_size)
     finally:
         if predictor is not None:

@@ -2085,6 +2085,211 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
         return pred, cross_entropy(logits, target, int(ignore_index))
 
 
+# ------------------------------------------------------------------------------------------------ multi-scale inference
+MULTISCALE_MAX_SCALES = 16
+
+
+def multiscale_scales_value(scales):
+    """The scales of the multi-scale ensemble as a tuple of floats, or None for "off": None, () and (1.0,) are the single-scale path.  ValueError on
+    anything that is not a sequence of numbers, on bools, NaN, infinity, values <= 0 and more than 16 entries.  Touches no device."""
+    if scales is None:
+        return None
+    what = f'scales = {scales!r}: expected at most {MULTISCALE_MAX_SCALES} finite numbers > 0'
+    if isinstance(scales, (str, bytes, torch.Tensor)):
+        raise ValueError(what)
+    try:
+        seq = tuple(scales)
+    except TypeError:
+        raise ValueError(what) from None
+    if len(seq) > MULTISCALE_MAX_SCALES:
+        raise ValueError(what)
+    out = []
+    for s in seq:
+        if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, float, np.integer, np.floating)):
+            raise ValueError(what)
+        v = float(s)
+        if not math.isfinite(v) or v <= 0.0:
+            raise ValueError(what)
+        out.append(v)
+    out = tuple(out)
+    return None if out in ((), (1.0,)) else out
+
+
+def multiscale_sizes(H, W, scales):
+    """[(H_k, W_k)] of the views of an (H, W) input: every side is the multiple of 16 nearest to scale * side, at least 16 (the head concatenates the
+    4x upsampled OS16 features with the OS4 features).  ValueError when two scales round to the same size.  Pure host code."""
+    sizes = []
+    for s in scales:
+        size = tuple(16 * max(1, int(math.floor(float(s) * v / 16.0 + 0.5))) for v in (int(H), int(W)))
+        if size in sizes:
+            raise ValueError(f'scales = {tuple(scales)!r}: two of them give the same {size[0]} x {size[1]} view of a {H} x {W} input')
+        sizes.append(size)
+    return sizes
+
+
+def resize_image_ac(x, size):
+    """The input of a view: the align-corners bilinear resize of the images `x` (N,3,H,W) to `size` (dsrl_bilinear_ac_fwd, the convention of every
+    interpolation of the model and its input pipeline); `x` itself when the size is its own."""
+    _need_gpu(x)
+    size = (int(size[0]), int(size[1]))
+    if tuple(x.shape[2:]) == size:
+        return x
+    with torch.no_grad():
+        return upsample_bilinear_ac(x, size)
+
+
+def _resample_exact(logits, mirrored, Ho, Wo):
+    """the resampling rule of dsrl_prob_merge in torch ops (class counts the kernel refuses)"""
+    if mirrored:
+        logits = logits.flip(3)
+
+    def axis(S, O):
+        o = torch.arange(O, device=logits.device, dtype=torch.int64)
+        n = o * (S - 1)
+        i0 = n // max(O - 1, 1)
+        frac = (n - i0 * max(O - 1, 1)).to(torch.float32) / float(max(O - 1, 1))
+        return i0, torch.clamp(i0 + 1, max=S - 1), frac
+
+    y0, y1, fy = axis(logits.shape[2], Ho)
+    x0, x1, fx = axis(logits.shape[3], Wo)
+    fy, fx = fy.view(1, 1, Ho, 1), fx.view(1, 1, 1, Wo)
+    r0, r1 = logits.index_select(2, y0), logits.index_select(2, y1)
+    top = (1.0 - fx) * r0.index_select(3, x0) + fx * r0.index_select(3, x1)
+    bot = (1.0 - fx) * r1.index_select(3, x0) + fx * r1.index_select(3, x1)
+    return (1.0 - fy) * top + fy * bot
+
+
+class ProbMerge:
+    """The multi-scale ensemble one view at a time (include/dsrl_hip.h, "multi-scale ensemble"): `add(logits, mirrored)` for each of `views` views in
+    turn; the call with the last view returns (pred, ce), every earlier one None.  All but the last view go through dsrl_prob_merge into one
+    accumulator, the last through dsrl_prob_merge_finish.  A view's logits may be freed as soon as its `add` returns: the launch is enqueued on the
+    current stream and nothing else refers to them.  Shapes dsrl_prob_merge_supported refuses for the whole batch are launched image by image; class
+    counts it refuses are composed from torch ops under the same definition."""
+
+    def __init__(self, views, N, C, out_size, device, target=None, ignore_index=255, counts=None, nan_flag=None, confusion=None):
+        self.V, self.N, self.C = int(views), int(N), int(C)
+        self.Ho, self.Wo = int(out_size[0]), int(out_size[1])
+        self.device, self.ignore_index = device, int(ignore_index)
+        if self.V < 1 or self.N < 1 or self.C < 1 or self.Ho < 1 or self.Wo < 1:
+            raise DsrlHipError(f'multiscale_merge: {self.V} views of {self.N} x {self.C} x {self.Ho} x {self.Wo}: every count must be at least 1')
+        _need_gpu(target, counts, nan_flag, confusion)
+        if target is not None:
+            if tuple(target.shape) != (self.N, self.Ho, self.Wo):
+                raise DsrlHipError(f'multiscale_merge: target {tuple(target.shape)} is not {(self.N, self.Ho, self.Wo)}')
+            if target.dtype != torch.uint8:
+                target = target.to(torch.uint8)
+            target = target.contiguous()
+        elif counts is not None or confusion is not None:
+            raise DsrlHipError('multiscale_merge: counts and confusion need a target')
+        if confusion is not None:
+            check_confusion(confusion, self.C, device, 'multiscale_merge')
+        if counts is not None and (counts.dtype != torch.int64 or counts.numel() != 3 * self.C + 2 or not counts.is_contiguous()):
+            raise DsrlHipError(f'multiscale_merge: counts must be a contiguous int64 tensor of {3 * self.C + 2} elements')
+        if nan_flag is not None and (nan_flag.dtype != torch.int32 or nan_flag.numel() != 1):
+            raise DsrlHipError('multiscale_merge: nan_flag must be an int32 scalar')
+        self.target, self.counts, self.nan_flag, self.confusion = target, counts, nan_flag, confusion
+        self.kernel = bool(cquery('dsrl_prob_merge_supported', 1, 1, 1, 1, 1, self.C))
+        self.acc = None             # the kernels' accumulator (or, without the kernels, the sum of the views' probabilities)
+        self.done = 0
+
+    def _chunk(self, h, w, ld):
+        """images per launch: the batch, or one where the batch's indices leave 32 bits"""
+        for n in (self.N, 1):
+            if cquery('dsrl_prob_merge_supported', n, h, w, self.Ho, self.Wo, self.C) and n * h * w * ld < 2 ** 31:
+                return n
+        raise DsrlHipError(f'multiscale_merge: a single {self.C} x {h} x {w} image on a {self.Ho} x {self.Wo} grid is beyond the 32-bit indices of '
+                           'dsrl_prob_merge')
+
+    def add(self, logits, mirrored=False):
+        if self.done >= self.V:
+            raise DsrlHipError(f'multiscale_merge: all {self.V} views were merged already')
+        with torch.no_grad():
+            logits, ld = pm(logits)
+            if logits.shape[0] != self.N or logits.shape[1] != self.C or logits.device != self.device:
+                raise DsrlHipError(f'multiscale_merge: view {self.done} is {tuple(logits.shape)} on {logits.device}, expected ({self.N}, {self.C}, h, w) '
+                                   f'on {self.device}')
+            self.done += 1
+            last = self.done == self.V
+            if not self.kernel:
+                return self._add_torch(logits, mirrored, last)
+            h, w = int(logits.shape[2]), int(logits.shape[3])
+            n, st = self._chunk(h, w, ld), _stream()
+            C, Ho, Wo = self.C, self.Ho, self.Wo
+            if self.acc is None and not last:
+                self.acc = torch.empty(self.N * (cquery('dsrl_prob_merge_acc_bytes', 1, Ho, Wo, C) // 4), device=self.device, dtype=torch.float32)
+            acc_step = C * Ho * Wo * 4          # bytes per image (dsrl_prob_merge_acc_bytes is linear in N)
+            if not last:
+                for i in range(0, self.N, n):
+                    call('dsrl_prob_merge', logits.data_ptr() + i * h * w * ld * 4, ld, n, h, w, C, int(bool(mirrored)), self.acc.data_ptr() + i * acc_step,
+                         Ho, Wo, int(self.done == 1), st)
+                return None
+            tgt = self.target
+            pred = torch.empty((self.N, Ho, Wo), device=self.device, dtype=torch.uint8)
+            ce = torch.empty((self.N // n, 2), device=self.device, dtype=torch.float32) if tgt is not None else None
+            ws = _ws(cquery('dsrl_prob_merge_workspace_bytes', n, Ho, Wo) if ce is not None else 0, logits)
+            for k, i in enumerate(range(0, self.N, n)):
+                call('dsrl_prob_merge_finish', logits.data_ptr() + i * h * w * ld * 4, ld, n, h, w, C, int(bool(mirrored)),
+                     None if self.acc is None else self.acc.data_ptr() + i * acc_step, Ho, Wo, self.V, pred.data_ptr() + i * Ho * Wo,
+                     None if tgt is None else tgt.data_ptr() + i * Ho * Wo, self.ignore_index, None if self.counts is None else self.counts.data_ptr(),
+                     None if ce is None else ce.data_ptr() + 8 * k, None if self.nan_flag is None else self.nan_flag.data_ptr(), ws.data_ptr(), ws.numel(),
+                     None if self.confusion is None else self.confusion.data_ptr(), st)
+            self.acc = None
+            if ce is None:
+                return pred, None
+            if ce.shape[0] == 1:
+                return pred, ce[0, 0]
+            mean, cnt = ce[:, 0].double(), ce[:, 1].double()            # per image: a mean over no pixel (NaN) carries no weight
+            return pred, (torch.where(cnt > 0, mean * cnt, torch.zeros_like(mean)).sum() / cnt.sum()).float()
+
+    def _add_torch(self, logits, mirrored, last):
+        p = torch.softmax(_resample_exact(logits, mirrored, self.Ho, self.Wo), dim=1)
+        self.acc = p if self.acc is None else self.acc.add_(p)
+        if not last:
+            return None
+        tot, self.acc = self.acc, None
+        if self.nan_flag is not None:
+            nan_check_(self.nan_flag, tot)
+        pred = torch.argmax(tot, dim=1).to(torch.uint8)
+        tgt = self.target
+        if tgt is None:
+            return pred, None
+        if self.nan_flag is not None:
+            _bad_label_bit(self.nan_flag, tgt, self.ignore_index, self.C)
+        if self.counts is not None:
+            lg, ld = pm(tot)
+            call('dsrl_seg_metrics', lg.data_ptr(), ld, tgt.data_ptr(), tgt.numel(), self.C, self.ignore_index, self.counts.data_ptr(), _stream())
+        if self.confusion is not None:
+            confusion_matrix_(self.confusion, pred, tgt, self.C, self.ignore_index)
+        counted = tgt != self.ignore_index
+        picked = (tot / float(self.V)).gather(1, tgt.long().clamp(max=self.C - 1).unsqueeze(1))[:, 0]
+        ce = (-torch.log(picked))[counted].mean()
+        bad = (counted & (tgt >= self.C)).any()
+        return pred, torch.where(bad, torch.full_like(ce, float('nan')), ce)
+
+
+def multiscale_merge(views, out_size, target=None, ignore_index=255, counts=None, nan_flag=None, confusion=None):
+    """The multi-scale (and flip) ensemble of given logits: `views` is a list of (logits (N,C,h,w), mirrored) - the logits of one scale each, in the
+    horizontally mirrored frame where `mirrored` is true; sizes may differ from view to view.  Every view is resampled onto the `out_size` = (Ho, Wo)
+    grid by align-corners bilinear interpolation of the logits (a mirrored one mirrored back first), its softmax taken and the class probabilities
+    averaged (dsrl_prob_merge, and dsrl_prob_merge_finish for the last view).  -> (pred uint8 (N,Ho,Wo), ce): pred is the first maximum of the
+    summed probabilities; with `target` (N,Ho,Wo) `ce` is the 0-d mean of -log P[target] over target != ignore_index, `counts` (int64
+    [3*classes+2], optional) gets the dsrl_seg_metrics table of pred ADDED and `confusion` (int64 [classes^2], optional) its confusion matrix;
+    `nan_flag` (int32 scalar, optional): bit 0 a NaN logit in any view, bit 1 a label outside the classes.  Beyond pred the call allocates one
+    accumulator of N * classes * Ho * Wo floats (none for a single view) and the loss workspace."""
+    views = list(views)
+    if not views:
+        raise DsrlHipError('multiscale_merge: no views')
+    first = views[0][0]
+    _need_gpu(*(v[0] for v in views))
+    if first.dim() != 4:
+        raise DsrlHipError(f'4-D (N,C,H,W) tensor expected, got shape {tuple(first.shape)}')
+    merge = ProbMerge(len(views), first.shape[0], first.shape[1], out_size, first.device, target, ignore_index, counts, nan_flag, confusion)
+    out = None
+    for logits, mirrored in views:
+        out = merge.add(logits, mirrored)
+    return out
+
+
 _palettes = {}
 
 

@@ -17,6 +17,9 @@ from .filter_operands import FilterOperands, align as _align, conv_filters
 
 FORMAT, FORMAT_VERSION = 'dsrl-hip-compiled', 1
 STALE_BIT = 4           # bit of the NaN flag word the device-side fingerprint check raises (bit 0: NaN, bit 1: label outside the classes)
+# graph replay of DSRL.predict(scales=...) is not built: a compiled predictor, and the commands asked for one, refuse the combination
+MULTISCALE_NOT_COMPILED = ('multi-scale inference (scales=...) runs through the eager DSRL.predict: a compiled predictor replays the single-scale '
+                           'and flip paths only')
 _private_gen = [1 << 40]
 
 
@@ -192,7 +195,8 @@ class CompiledPredictor:
     replayed from a hipGraph.  `flip` is a call-time option (DSRL.predict(flip=True): the horizontal-flip ensemble), not a property of a compiled model file.
     `confusion` (DSRL.predict_head): the caller's matrix gets exactly this batch's counts added, replayed or eager.  A graph never holds the caller's
     pointer: it fills a static matrix of its own, zeroed by a node of the graph, which the call then adds to the tensor it was given - successive
-    calls may pass different tensors.
+    calls may pass different tensors.  `scales` (DSRL.predict: the multi-scale ensemble) other than "off" raises DsrlHipError before anything else is
+    looked at - its graph replay is not built - and leaves the predictor as it was.
 
     One graph per key (N, H, W, with target, conv arithmetic, flip, with confusion), captured at the key's first use after GRAPH_WARMUP eager calls (the frozen eager path:
     the same kernels), at most MAX_GRAPHS keys; further shapes, and every shape when `graph` is False or a capture failed, run the frozen eager path.
@@ -262,7 +266,9 @@ class CompiledPredictor:
         return c
 
     # ------------------------------------------------------------------ the call
-    def __call__(self, images, target=None, ignore_index=255, nan_flag=None, copy=True, flip=False, confusion=None):
+    def __call__(self, images, target=None, ignore_index=255, nan_flag=None, copy=True, flip=False, confusion=None, scales=None):
+        if HF.multiscale_scales_value(scales) is not None:
+            raise DsrlHipError(MULTISCALE_NOT_COMPILED)
         if self.frozen.released:
             raise DsrlHipError('this CompiledPredictor was released: call compile_predict() again')
         self.frozen.check()

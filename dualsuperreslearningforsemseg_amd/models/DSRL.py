@@ -163,17 +163,25 @@ class DSRL(BaseModel):
         return pred, counts, ce
 
     def predict(self, x: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None, flip: bool = False,
-                confusion: t.Tensor = None):
+                confusion: t.Tensor = None, scales=None):
         """Class map of a batch: (pred, counts or None, ce or None), see predict_head.  Runs under no_grad and raises in train mode.  Without a
         `nan_flag` of the caller's the flag is read back here and a NaN logit or an out-of-range label raises; a caller that passes one reads it when
         it chooses to (command_handlers.benchmark: once, after the last batch).
         `flip=True`: the horizontal-flip ensemble.  The trunk runs once on cat([x, x.flip(3)]) (2N images) and the tail kernel forms the ensemble:
         N class maps, counters and the loss of the averaged class probabilities.
-        `confusion`: see predict_head; with `flip` it is the matrix of the ensemble's class map."""
+        `confusion`: see predict_head; with `flip` it is the matrix of the ensemble's class map.
+        `scales` (a sequence of numbers, functional.multiscale_scales_value; None, () and (1.0,) are "off" and leave every launch as it is): the
+        multi-scale ensemble.  For each scale in turn the images are resized to the multiple of 16 nearest to scale x size (align corners), the SSSR
+        logits of the eval forward path are written (with `flip` for the image and its mirror image in one batch), merged into the ensemble and
+        released before the next scale runs (functional.ProbMerge: the logits of every view resampled to the output grid, softmax, class probabilities
+        averaged); pred, counts, ce, confusion and the NaN flag are those of the ensemble."""
         if self.training:
             raise HF.DsrlHipError('DSRL.predict* is inference: call model.eval() first')
         if confusion is not None and target is None:
             raise HF.DsrlHipError('DSRL.predict: confusion needs a target')
+        scales = HF.multiscale_scales_value(scales)
+        if scales is not None:
+            return self._predict_multiscale(x, target, ignore_index, nan_flag, flip, confusion, scales)
         own = nan_flag is None
         with t.no_grad():
             if own:
@@ -191,6 +199,52 @@ class DSRL(BaseModel):
             if bits:
                 raise HF.DsrlHipError('DSRL.predict: ' + ' and '.join(m for b, m in ((1, 'NaN in the input or the logits'), (2, 'labels outside the classes')) if bits & b))
         return out
+
+    def _eval_sssr_logits(self, x: t.Tensor):
+        """The SSSR logits (N,classes,2H,2W) of the eval-mode forward path on `x`: forward() without the SISR decoder and the feature transformers."""
+        HF.begin_forward(False)
+        fe, dec = self.feature_extractor, self.SSSR_decoder
+        backbone_features, lowlevel_features = fe['backbone'](x)                              # DSRL.py:161
+        aspp_features = fe['aspp'](backbone_features)
+        h, w = aspp_features.shape[-2:]
+        aspp_features = HF.upsample_bilinear_ac(aspp_features, (4 * h, 4 * w))                 # DSRL.py:163
+        cat_features = HF.cat_channels([aspp_features, fe['shortcut_conv'](lowlevel_features)])    # DSRL.py:164-165
+        return dec['upsample16_pred'](dec['cls_conv'](dec['cat_conv'](cat_features)))         # DSRL.py:168-170
+
+    def _predict_multiscale(self, x, target, ignore_index, nan_flag, flip, confusion, scales):
+        HF._need_gpu(x, target, nan_flag, confusion)
+        if x.dim() != 4 or x.shape[2] % 16 or x.shape[3] % 16:
+            raise HF.DsrlHipError(f'DSRL.predict: (N,3,H,W) images with H and W multiples of 16 expected, got shape {tuple(x.shape)}')
+        N, _, H, W = x.shape
+        sizes = HF.multiscale_sizes(H, W, scales)
+        own = nan_flag is None
+        with t.no_grad():
+            if own:
+                nan_flag = t.zeros((), dtype=t.int32, device=x.device)
+            HF.nan_check_(nan_flag, x)          # once, on the images as given: every view is interpolated from them
+            classes = self.SSSR_decoder['upsample16_pred'][6].out_channels
+            counts = t.zeros(3 * classes + 2, dtype=t.int64, device=x.device) if target is not None else None
+            merge = HF.ProbMerge(len(sizes) * (2 if flip else 1), N, classes, (2 * H, 2 * W), x.device, target, ignore_index, counts, nan_flag, confusion)
+            out = None
+            for size in sizes:
+                xk = HF.resize_image_ac(x, size)
+                if flip:
+                    both = t.empty((2 * N,) + tuple(xk.shape[1:]), dtype=xk.dtype, device=xk.device, memory_format=t.channels_last)
+                    both[:N].copy_(xk)
+                    both[N:].copy_(xk.flip(3))
+                    xk = both
+                logits = self._eval_sssr_logits(xk)
+                if flip:
+                    merge.add(logits[:N], False)
+                    out = merge.add(logits[N:], True)
+                else:
+                    out = merge.add(logits, False)
+                del logits, xk                  # one scale's logits at a time
+        if own:
+            bits = int(nan_flag.item())
+            if bits:
+                raise HF.DsrlHipError('DSRL.predict: ' + ' and '.join(m for b, m in ((1, 'NaN in the input or the logits'), (2, 'labels outside the classes')) if bits & b))
+        return out[0], counts, out[1]
 
     def compile_predict(self, batch_size=None, input_size=None, graph=True):
         """-> inference.CompiledPredictor: `predict` on operands prepared once (inference.FrozenOperands: filter amax records, pre-split filters, fp16

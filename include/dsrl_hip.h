@@ -682,6 +682,40 @@ int dsrl_sssr_tail_predict_flip_cm(const float* x, int ldx, int N, int H, int W,
                                    float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes,
                                    unsigned long long* cm /*nullable, [Cout*Cout]*/, dsrl_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * inference: the multi-scale ensemble (csrc/merge.hip) - what follows the eval-mode forward path once it has written a view's logits
+ *   A view v is the logits (N,Hs,Ws,C) of one scale, pixel-major with pixel stride ld >= C, in the plain or (mirror != 0) the horizontally mirrored
+ *   frame; views may differ in Hs, Ws, ld and mirror.  The output grid is (Ho,Wo), the grid of pred and target.
+ *   Resampling: align-corners bilinear interpolation OF THE LOGITS, a mirrored view mirrored back along W first.  The source coordinate of output
+ *   index o on an axis with S source and O output samples is exact: n = o (S - 1), i0 = n / (O - 1), frac = float(n mod (O - 1)) / float(O - 1),
+ *   i1 = min(i0 + 1, S - 1); O = 1: i0 = 0, frac = 0 (32-bit integers, one division per axis: the weight carries one rounding at every size, where
+ *   dsrl_bilinear_ac_fwd's fp32 scale * dst loses accuracy with the coordinate).
+ *   Result over V views: P = (1 / V) sum_v softmax_c(resampled L_v); pred = lowest index among the maxima of sum_v softmax; ce_out[0] = mean of
+ *   -log P[target] over the counted pixels (target != ignore_index), ce_out[1] their number; counts = the dsrl_seg_metrics table of pred, ADDED;
+ *   cm[t*C + p] ADDED under the one convention above; nan_flag |= 1 for a NaN among the sampled logits of ANY view (it travels through the
+ *   accumulator to the last launch), |= 2 for a label >= C that is not ignore_index (which also makes ce_out NaN).  Every pixel ignored: ce_out[0] NaN.
+ *   fp32 limit of ce: it is taken from the accumulated probabilities.  Where the target's probability underflows fp32 in every view (a logit gap above
+ *   about 87) the value is what fp32 gives, +inf; a gap of 60 is still right to an ulp of the logarithm.
+ *   dsrl_prob_merge: one view that is not the last.  first != 0 stores softmax into acc without reading it, otherwise it adds.
+ *   dsrl_prob_merge_finish: the last view: the same resample and softmax plus what acc holds, in registers - acc is never written by this launch and
+ *   is null exactly when views == 1 - then arg-max, counters, loss, NaN flag and confusion matrix.  views = V.  counts, ce_out and cm need a target.
+ *   A view contributes the same bits whichever launch merges it.  Every output is bit-identical run to run: accumulator pixels are owned by one
+ *   thread, counters and bins are 64-bit integer atomics (one per block and non-zero bin), the loss goes through per-block partials in ws reduced in
+ *   a fixed order.  acc is the kernels' own tensor (class-planar) of dsrl_prob_merge_acc_bytes(N, Ho, Wo, C) bytes: callers allocate it and never
+ *   interpret it.  logits and acc 4-byte aligned, ws 8-byte aligned (only used with ce_out); pred and target may start at any byte, Wo may be odd.
+ * _supported: 1 for 1 <= C <= 32 (and C <= dsrl_confusion_matrix_max_classes()), every dimension >= 1 and every 32-bit index in range
+ *   (N*Ho*Wo*C, N*Hs*Ws*C, o*(S-1) <= 2^31 - 1; a launch checks N*Hs*Ws*ld itself), 0 otherwise; pure host code.  _workspace_bytes and _acc_bytes
+ *   depend on the shape only and hold for every launch of that shape.
+ * ---------------------------------------------------------------------------------------------- */
+int dsrl_prob_merge_supported(int N, int Hs, int Ws, int Ho, int Wo, int C);
+size_t dsrl_prob_merge_acc_bytes(int N, int Ho, int Wo, int C);
+size_t dsrl_prob_merge_workspace_bytes(int N, int Ho, int Wo);
+int dsrl_prob_merge(const float* logits, int ld, int N, int Hs, int Ws, int C, int mirror, float* acc, int Ho, int Wo, int first, dsrl_stream_t stream);
+int dsrl_prob_merge_finish(const float* logits, int ld, int N, int Hs, int Ws, int C, int mirror, const float* acc /*nullable: the only view*/, int Ho,
+                           int Wo, int views, uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index,
+                           unsigned long long* counts /*nullable*/, float* ce_out /*nullable, [2]: mean, counted pixels*/, int* nan_flag /*nullable*/,
+                           void* ws, size_t ws_bytes, unsigned long long* cm /*nullable, [C*C]*/, dsrl_stream_t stream);
+
 /* Fingerprint of tensors that must not change while an inference.FrozenOperands holds operands derived from them (a write through `.data` or a
  * raw pointer moves neither a tensor's address nor its version counter).  table: DEVICE array of nseg rows of 2 int64 {pointer (4-byte aligned),
  * number of 32-bit words <= dsrl_fingerprint_segment_words()}, one block per row; a tensor is cut into as many rows as it needs.  Row r gets

@@ -24,6 +24,15 @@ on uniform labels and on labels / predictions that are class 0 on ~90 % of the p
   (e) dsrl_seg_metrics_cm against dsrl_seg_metrics on 8x19x512x1024 logits.
 
     python tools/predict_bench.py --confusion [--baseline] [--out profiles/predict_confusion.txt]
+
+--multiscale measures the multi-scale ensemble (profiles/predict_multiscale.txt) on 256x512 images, batch 1 and 8, scales 0.5 ... 1.75, plain and flip:
+  (a) the merge launches alone (functional.multiscale_merge, all views) against torch interpolate / softmax / add / argmax on the same logits, with
+      the peak memory of each,
+  (b) one dsrl_prob_merge launch against the bytes it must move (accumulator read + write + logits once), beside a dsrl_copy2d of as many bytes,
+  (c) DSRL.predict(scales=...) against the sum of DSRL.predict calls on the same view sizes,
+and lists the registers of the merge kernels.
+
+    python tools/predict_bench.py --multiscale [--out profiles/predict_multiscale.txt]
 """
 import argparse
 import math
@@ -304,6 +313,110 @@ def confusion_main(args):
             f.write('\n'.join(lines) + '\n')
 
 
+MS_SCALES = (0.5, 0.75, 1.0, 1.25, 1.5, 1.75)
+
+
+def multiscale_main(args):
+    import kernel_resources as KR
+    from dualsuperreslearningforsemseg_amd import _lib
+    from dualsuperreslearningforsemseg_amd._lib import call
+    dev = torch.device('cuda:0')
+    lines = []
+
+    def say(s=''):
+        print(s, flush=True)
+        lines.append(s)
+
+    def fmt(ts, scale=1e3, unit='us'):
+        return f'{sum(ts) / len(ts) * scale:9.1f} {unit} [{", ".join(f"{t * scale:.1f}" for t in ts)}]'
+
+    H, W = 256, 512
+    Ho, Wo = 2 * H, 2 * W
+    sizes = HF.multiscale_sizes(H, W, MS_SCALES)
+    say(f'Multi-scale ensemble, {torch.cuda.get_device_name(0)}, images {H}x{W} (class maps {Ho}x{Wo}), scales {MS_SCALES} -> views of '
+        f'{", ".join(f"{h}x{w}" for h, w in sizes)}; windows of >= {args.window} s per side, {args.rounds} alternations A B A B ..; mean [each window]')
+    say()
+    say('(a) the merge alone, on the same logits (random normal, one (N,19,2h,2w) tensor per view; with flip two per scale, the second mirrored): '
+        'A = torch interpolate(align_corners=True) -> softmax -> add per view, then argmax; B = functional.multiscale_merge (dsrl_prob_merge for all but '
+        'the last view, dsrl_prob_merge_finish)')
+    slower = []
+    for flip in (False, True):
+        for N in (1, 8):
+            views = [(torch.randn(N, NC, 2 * h, 2 * w, device=dev).contiguous(memory_format=torch.channels_last), bool(v))
+                     for h, w in sizes for v in range(2 if flip else 1)]
+
+            def a():
+                with torch.no_grad():
+                    total = None
+                    for L, m in views:
+                        p = torch.softmax(torch.nn.functional.interpolate(L.flip(3) if m else L, size=(Ho, Wo), mode='bilinear', align_corners=True), dim=1)
+                        total = p if total is None else total.add_(p)
+                    return torch.argmax(total, dim=1)
+
+            def b():
+                return HF.multiscale_merge(views, (Ho, Wo))[0]
+
+            ta, tb = ab(a, b, args.window, args.rounds)
+            mem_a, mem_b = peak_bytes(a), peak_bytes(b)
+            agree = (a() == b()).float().mean().item()
+            ma, mb = _row(say, f'N={N} {"flip " if flip else "plain"} {len(views):2d} views', ta, tb,
+                          extra=f'   peak memory A {mem_a / 1e6:8.1f} MB  B {mem_b / 1e6:7.1f} MB   class maps agree at {100 * agree:.3f} %')
+            if mb > ma:
+                slower.append((N, flip))
+            del views
+    say('rows where B is slower than A: ' + (', '.join(str(r) for r in slower) if slower else 'none'))
+    say()
+    say('(b) dsrl_prob_merge, one launch that adds a view (first = 0): bytes it must move = accumulator read + write + the view\'s logits once; beside it '
+        'dsrl_copy2d moving the same number of bytes (half read, half written)')
+    for N in (1, 8):
+        acc = torch.zeros(_lib.query('dsrl_prob_merge_acc_bytes', N, Ho, Wo, NC) // 4, device=dev)
+        for h, w in (sizes[0], sizes[2], sizes[5]):
+            L = torch.randn(N, NC, 2 * h, 2 * w, device=dev).contiguous(memory_format=torch.channels_last)
+            nbytes = 2 * acc.numel() * 4 + L.numel() * 4
+            rows = nbytes // (2 * 4 * 64)
+            src, dst = torch.randn(rows * 64, device=dev), torch.empty(rows * 64, device=dev)
+            st = HF._stream()
+            tm, tc = ab(lambda: call('dsrl_prob_merge', L.data_ptr(), NC, N, 2 * h, 2 * w, NC, 0, acc.data_ptr(), Ho, Wo, 0, st),
+                        lambda: call('dsrl_copy2d', src.data_ptr(), 64, dst.data_ptr(), 64, rows, 64, st), args.window, args.rounds)
+            mm, mc = sum(tm) / len(tm), sum(tc) / len(tc)
+            say(f'N={N} view {2 * h}x{2 * w}: {nbytes / 1e6:7.1f} MB   merge {fmt(tm)} = {nbytes / (mm * 1e-3) / 1e12:5.2f} TB/s   copy2d {fmt(tc)} = '
+                f'{nbytes / (mc * 1e-3) / 1e12:5.2f} TB/s   ({100 * mc / mm:.0f} % of the copy\'s rate; HBM {HBM_BPS / 1e12:.2f} TB/s)')
+            acc.zero_()
+            del L, src, dst
+        del acc
+    say()
+    say('(c) whole model (stage 1, random weights, eval, caller-owned nan_flag: no readback): A = the sum of DSRL.predict calls on the same view sizes '
+        '(class maps only; what the trunk and the fused tail cost), B = DSRL.predict(scales=...) (logits written, merged, released per scale)')
+    model = DSRL(1, CS).to(dev).to(memory_format=torch.channels_last).eval()
+    flag = torch.zeros((), dtype=torch.int32, device=dev)
+    for flip in (False, True):
+        for N in (1, 8):
+            img = torch.randn(N, 3, H, W, device=dev).contiguous(memory_format=torch.channels_last)
+            resized = [HF.resize_image_ac(img, s) for s in sizes]
+
+            def a():
+                return [model.predict(r, nan_flag=flag, flip=flip)[0] for r in resized]
+
+            def b():
+                return model.predict(img, nan_flag=flag, flip=flip, scales=MS_SCALES)[0]
+
+            ta, tb = ab(a, b, args.window, args.rounds)
+            _row(say, f'batch {N} {"flip " if flip else "plain"}', ta, tb, 1.0, 'ms',
+                 f'   peak memory A {peak_bytes(a) / 1e6:8.1f} MB  B {peak_bytes(b) / 1e6:8.1f} MB   single-scale predict '
+                 f'{window(lambda: model.predict(img, nan_flag=flag, flip=flip)[0], args.window):7.3f} ms')
+    say()
+    say('kernel resources (tools/kernel_resources.py on libdsrl_hip.so):')
+    ks = KR.kernels(_lib.LIB_PATH)
+    for k, n in zip(ks, KR.demangle([k['name'] for k in ks])):
+        if 'prob_merge' in n:
+            say(f"vgpr {k.get('vgpr', 0):3d} agpr {k.get('agpr', 0):3d} sgpr {k.get('sgpr', 0):3d} scratch {k.get('scratch', 0):5d} B  spills v{k.get('vgpr_spill', 0)} "
+                f"s{k.get('sgpr_spill', 0)}  lds {k.get('lds', 0):6d}  {n[:110]}")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
@@ -312,8 +425,11 @@ def main():
     ap.add_argument('--flip', action='store_true', help='measure the horizontal-flip ensemble (profiles/predict_flip.txt)')
     ap.add_argument('--confusion', action='store_true', help='measure the device confusion matrix (profiles/predict_confusion.txt)')
     ap.add_argument('--baseline', action='store_true', help='with --confusion: only (a), the calls a tree without the feature also has')
+    ap.add_argument('--multiscale', action='store_true', help='measure the multi-scale ensemble (profiles/predict_multiscale.txt)')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'predict_bench.py measures on the GPU only'
+    if args.multiscale:
+        return multiscale_main(args)
     if args.confusion:
         return confusion_main(args)
     if args.flip:
