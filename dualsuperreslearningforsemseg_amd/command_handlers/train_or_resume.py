@@ -88,16 +88,24 @@ class TrainStep:
 
     `label_smoothing` (a number in [0, 1]; 0: off): nn.CrossEntropyLoss(label_smoothing=) for the CE term on the same paths, training and
     `do_train=False` alike, also on the weighted kernels.  Together with `focal_gamma` > 0: ValueError.  The value is fixed for the life of the
-    step, as `focal_gamma` is, so every graph this step captures was captured with it."""
+    step, as `focal_gamma` is, so every graph this step captures was captured with it.
+
+    `ohem` (HF.ohem_value: None / False off, True = (0.7, 100000), (thresh, min_kept) or a mapping): online hard example mining for the CE term of
+    the TRAINING iterations - the hard pixels of the batch are selected on the device and every other label becomes `ignore_index` before the CE paths
+    run (HF.ohem_target), fused and unfused losses, eager and captured.  `do_train=False` keeps the configured CE without mining, so
+    validation losses stay comparable between runs with and without it.  It goes with `class_weights` (the selection is on the unweighted
+    probability) and not with `focal_gamma` > 0 or `label_smoothing` > 0 (ValueError); `ignore_index` must then be a byte value.  With more than one
+    rank each rank mines its own batch.  Fixed for the life of the step, like the other two."""
 
     GRAPH_WARMUP = HF.GRAPH_WARMUP          # eager iterations per batch shape before the capture
 
-    def __init__(self, model, flat, stage, w1, w2, ignore_index, graph=None, class_weights=None, focal_gamma=0.0, label_smoothing=0.0):
+    def __init__(self, model, flat, stage, w1, w2, ignore_index, graph=None, class_weights=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None):
         self.model, self.flat, self.stage, self.w1, self.w2, self.ignore = model, flat, stage, w1, w2, ignore_index
         self.focal_gamma = HF.focal_gamma_value(focal_gamma)                                                          # ValueError on a bad gamma
         self.label_smoothing = HF.label_smoothing_value(label_smoothing)                                              # ValueError on a bad eps
         if self.focal_gamma > 0.0 and self.label_smoothing > 0.0:
             raise ValueError(f'label_smoothing = {label_smoothing!r} together with focal_gamma = {focal_gamma!r}: the combination is not defined')
+        self.ohem = HF._ohem_args(ohem, self.focal_gamma, self.label_smoothing, ignore_index)                        # ValueError on a bad value or combination
         self.class_weight = None if class_weights is None else HF.class_weight_table(class_weights, flat.device)     # ValueError on bad weights
         self.fa = FALoss()
         dev = flat.device
@@ -125,9 +133,10 @@ class TrainStep:
         self.time_collectives = False           # bench.py: bracket the exposed part of the collectives with events
         self.comm_events = []                   # (broadcast start, end, replay end, end of exchange [+ update: one-graph schedule]) per step
 
-    def losses(self, outs, input_org, target):
+    def losses(self, outs, input_org, target, do_train=True):
         SSSR, SISR, SSSR_ft, SISR_ft = outs
-        ce = HF.cross_entropy(SSSR, target, self.ignore, self.class_weight, self.focal_gamma, self.label_smoothing)      # train_or_resume.py:435
+        ce = HF.cross_entropy(SSSR, target, self.ignore, self.class_weight, self.focal_gamma, self.label_smoothing,      # train_or_resume.py:435
+                              self.ohem if do_train else None)
         ms = self.w1 * HF.mse_loss(SISR, input_org) if self.stage > 1 else self.zero       # :436
         fa = self.w2 * self.fa(SSSR_ft, SISR_ft) if self.stage > 2 else self.zero          # :437
         return ce, ms, fa, ce + ms + fa                                                    # :438
@@ -148,24 +157,25 @@ class TrainStep:
                 bb = self.model.feature_extractor['backbone']
                 bb._dsrl_cut = []
         self.flag.zero_()
+        ohem = self.ohem if do_train else None    # validation keeps the configured CE without mining
         cuts = None
         try:
             with t.set_grad_enabled(do_train):
                 if self.fused_losses and do_train:
                     # the layer that produces the logits evaluates the CE value in its own forward kernel (HF.logits_target), :435
                     with HF.logits_target(target if target.dtype == t.uint8 and target.is_contiguous() else None, self.ignore, self.flag,
-                                          self.class_weight, self.focal_gamma, self.label_smoothing):
+                                          self.class_weight, self.focal_gamma, self.label_smoothing, ohem):
                         outs = self.model(input_image)                                     # :420
                 else:
                     outs = self.model(input_image)                                         # :420
                 if self.fused_losses:
                     # CE + MSE + FA, their gradients, the NaN asserts (:426-433) and the loss mix (:435-438) in one launch set
                     vals = HF.fused_losses(outs, target, input_org, self.ignore, self.w1, self.w2, self.stage, self.flag, self.fa.subsample_factor,
-                                           self.class_weight, self.focal_gamma, self.label_smoothing)
+                                           self.class_weight, self.focal_gamma, self.label_smoothing, ohem)
                     total = vals[3]
                 else:
                     HF.nan_check_(self.flag, *[o for o in outs if o.is_cuda])              # the four NaN asserts, :426-433
-                    ce, ms, fa, total = self.losses(outs, input_org, target)
+                    ce, ms, fa, total = self.losses(outs, input_org, target, do_train)
                     vals = t.cat([t.stack([ce, ms, fa, total]).detach().float(), self.flag.float()])
                 if in_graph and HF.knob('DSRL_GRAPH_FAIL_TEST', ''):
                     raise RuntimeError('DSRL_GRAPH_FAIL_TEST: simulated failure in the middle of a capture')      # tests/test_rccl_gpu.py
@@ -237,7 +247,7 @@ class TrainStep:
 
     def _graph_key(self, input_image, input_org, target):
         return (tuple(input_image.shape), tuple(input_org.shape), tuple(target.shape), HF.get_conv_precision(), HF.overlap_wgrad,
-                self.focal_gamma, self.label_smoothing)
+                self.focal_gamma, self.label_smoothing, self.ohem)
 
     def _capture(self, key, input_image, input_org, target, hp):
         """-> the captured step, or None: a capture that fails (a runtime that refuses something inside it) must not end the training run.  This
@@ -435,6 +445,13 @@ def check_label_smoothing(dataset):
     return e
 
 
+def check_ohem(dataset):
+    """dataset['ohem']: absent, None or False -> None (off); True, a pair (thresh, min_kept) or a mapping with these keys -> (thresh, min_kept), as
+    HF.ohem_value; ValueError otherwise, on a value together with dataset['focal_gamma'] > 0 or dataset['label_smoothing'] > 0 (scoped out), and on
+    an ignore label of the dataset that is no byte value.  Touches no device."""
+    return HF._ohem_args(dataset.get('ohem'), check_focal_gamma(dataset), check_label_smoothing(dataset), dataset['settings'].IGNORE_CLASS_LABEL)
+
+
 def train_or_resume(is_resuming_training, device, distributed, mixed_precision, disable_cudnn_benchmark, num_workers, dataset, val_interval,
                     checkpoint_interval, checkpoint_history, init_weights, batch_size, epochs, learning_rate, end_learning_rate, momentum,
                     weights_decay, poly_power, stage, w1, w2, freeze_batch_norm, experiment_id, description, early_stopping, dry_run=False, **other_args):
@@ -447,6 +464,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     class_weights = check_class_weights(dataset, dataset['settings'].NUM_CLASSES)
     focal_gamma = check_focal_gamma(dataset)
     label_smoothing = check_label_smoothing(dataset)
+    ohem = check_ohem(dataset)
     input_size = other_args.get('model_input_size', settings.MODEL_INPUT_SIZE)
     if distributed:
         t.manual_seed(settings.RANDOM_SEED)                                                # identical init on all ranks, :31
@@ -502,7 +520,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
         lut = DeviceBatchPreparation(ds.LABEL_MAPPING_DICT, ds.MEAN, ds.STD, input_size, ds.IGNORE_CLASS_LABEL).lut_host
         class_weights = enet_weights(class_counts(cache_dir_of(dataset), 'train', lut, device_obj)[:ds.NUM_CLASSES])
     step = TrainStep(model, flat, stage, w1, w2, ds.IGNORE_CLASS_LABEL, class_weights=class_weights, focal_gamma=focal_gamma,
-                     label_smoothing=label_smoothing)
+                     label_smoothing=label_smoothing, ohem=ohem)
     train_loader = factory('train', batch_size, device_obj, rank, world)
     val_loader = factory('val', batch_size, device_obj, rank, world) if is_master_rank else None
 

@@ -1380,6 +1380,80 @@ def label_smoothing_value(x):
     return e
 
 
+OHEM_DEFAULT = (0.7, 100000)            # thresh, min_kept of `ohem=True`: the values the published Cityscapes configurations train with
+
+
+def ohem_value(x):
+    """Online hard example mining as (thresh, min_kept), or None when it is off.  None / False: off; True: OHEM_DEFAULT; a pair (thresh, min_kept);
+    a mapping with the keys 'thresh' and / or 'min_kept' (a missing one takes its default).  thresh: a number in [0, 1]; min_kept: an integer >= 0
+    (below 2^63).  ValueError on anything else - a bool where a number belongs, a NaN, a float min_kept, an unknown key.  Touches no device."""
+    if x is None:
+        return None
+    if isinstance(x, (bool, np.bool_)):
+        return OHEM_DEFAULT if x else None
+    if isinstance(x, dict):
+        if not x or set(x) - {'thresh', 'min_kept'}:
+            raise ValueError(f"ohem = {x!r}: expected a mapping with the keys 'thresh' and 'min_kept'")
+        thresh, min_kept = x.get('thresh', OHEM_DEFAULT[0]), x.get('min_kept', OHEM_DEFAULT[1])
+    elif isinstance(x, (tuple, list)) and len(x) == 2:
+        thresh, min_kept = x
+    else:
+        raise ValueError(f'ohem = {x!r}: expected None, a bool, a pair (thresh, min_kept) or a mapping with these keys')
+    if isinstance(thresh, (bool, np.bool_)) or not isinstance(thresh, (int, float, np.integer, np.floating)):
+        raise ValueError(f'ohem: thresh = {thresh!r}: expected a number in [0, 1]')
+    th = float(thresh)
+    if not (0.0 <= th <= 1.0) or float(np.float32(th)) > 1.0:                   # (a NaN fails the comparison; the kernels take it as fp32)
+        raise ValueError(f'ohem: thresh = {thresh!r}: expected a number in [0, 1]')
+    if isinstance(min_kept, (bool, np.bool_)) or not isinstance(min_kept, (int, np.integer)) or not 0 <= int(min_kept) < 2 ** 63:
+        raise ValueError(f'ohem: min_kept = {min_kept!r}: expected an integer >= 0')
+    return th, int(min_kept)
+
+
+def _ohem_args(ohem, gamma, eps, ignore_index):
+    """ohem_value(ohem) of a CE call, after the combinations it does not go with: a focal or label-smoothed loss (scoped out: ValueError) and an
+    ignore_index that is no byte value (it is written into the target: ValueError)."""
+    ohem = ohem_value(ohem)
+    if ohem is not None:
+        if gamma > 0.0 or eps > 0.0:
+            raise ValueError(f'ohem = {ohem!r} together with focal_gamma = {gamma!r} or label_smoothing = {eps!r}: the combination is not supported')
+        if isinstance(ignore_index, (bool, np.bool_)) or not isinstance(ignore_index, (int, np.integer)) or not 0 <= int(ignore_index) <= 255:
+            raise ValueError(f'ohem: ignore_index = {ignore_index!r} must be a byte value 0..255 (it is written into the target)')
+    return ohem
+
+
+def ohem_target(logits, target, ignore_index, thresh, min_kept, flag=None, stats=None):
+    """The target with the label of every easy pixel set to `ignore_index`: logits (N,C,H,W) fp32, target (N,H,W) uint8/long ->
+    a new uint8 tensor of target's shape.  A pixel takes part when its label is neither ignore_index nor >= C; p is the softmax probability of its
+    label; with n such pixels in the call, k = min(min_kept, n - 1) and thr = max(k-th smallest p, thresh), a pixel stays iff p < thr.  The whole
+    selection runs on the device (dsrl_ohem_target) without a host read, so it can be captured.  flag: the int32 NaN flag to OR into (optional);
+    stats: a 4-element int32 tensor that receives {bits of thr, n, number kept, number with p < thresh} (optional).  Not differentiable: nothing is
+    recorded, the logits are read as numbers."""
+    th, mk = ohem_value((thresh, min_kept))
+    if isinstance(ignore_index, (bool, np.bool_)) or not isinstance(ignore_index, (int, np.integer)) or not 0 <= int(ignore_index) <= 255:
+        raise ValueError(f'ohem: ignore_index = {ignore_index!r} must be a byte value 0..255 (it is written into the target)')
+    with torch.no_grad():
+        logits, ld = pm(logits.detach())
+        _need_gpu(target, flag, stats)
+        if target.dtype != torch.uint8:
+            target = target.to(torch.uint8)
+        target = target.contiguous()
+        N, Cc, H, W = logits.shape
+        P = N * H * W
+        if target.numel() != P:
+            raise DsrlHipError(f'ohem_target: target has {target.numel()} pixels, logits {P}')
+        if flag is not None and flag.dtype != torch.int32:
+            raise DsrlHipError(f'ohem_target: the NaN flag must be int32, got {flag.dtype}')
+        if stats is None:
+            stats = torch.empty(4, device=logits.device, dtype=torch.int32)
+        elif stats.dtype != torch.int32 or stats.numel() < 4 or not stats.is_contiguous():
+            raise DsrlHipError('ohem_target: stats must be a contiguous int32 tensor of 4 elements')
+        out = torch.empty_like(target)
+        ws = _ws(cquery('dsrl_ohem_workspace_bytes', P), logits)
+        call('dsrl_ohem_target', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), th, mk, out.data_ptr(), stats.data_ptr(),
+             None if flag is None else flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return out
+
+
 def _focal_args(weight, gamma, device, num_classes, eps=0.0):
     """(class-weight table or None, gamma, eps) of a CE call: the focal and the label-smoothed loss run on the weighted kernels, so gamma > 0 or
     eps > 0 without weights takes the all-ones table of `num_classes` classes.  Both at once: ValueError (the combination has no agreed
@@ -1419,16 +1493,18 @@ class logits_target:
     they will be compared with, so that its forward kernel evaluates nn.CrossEntropyLoss while the output tile is on chip (dsrl_convt2x2_fwd_ce) and
     fused_losses finds the value ready (LogitsGrad.value) instead of reading the logits again.  target: (N,H,W) uint8, contiguous; flag: the int32 NaN
     flag fused_losses will be given; weight: the class weights fused_losses will be given (None: unweighted); focal_gamma: its focal exponent
-    (0: none); label_smoothing: its label smoothing (0: none; not together with focal_gamma > 0).  Outside the block, or when the shape does not
-    qualify, nothing changes."""
+    (0: none); label_smoothing: its label smoothing (0: none; not together with focal_gamma > 0); ohem: its hard-pixel mining (ohem_value; not
+    together with either of the two).  Outside the block, or when the shape does not qualify, nothing changes.  With ohem nothing is engaged either:
+    the target the loss will use does not exist before the logits do, so the plain forward runs and fused_losses evaluates the value itself."""
 
-    def __init__(self, target, ignore_index, flag, weight=None, focal_gamma=0.0, label_smoothing=0.0):
+    def __init__(self, target, ignore_index, flag, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None):
         focal_gamma = focal_gamma_value(focal_gamma)
         label_smoothing = label_smoothing_value(label_smoothing)
         if focal_gamma > 0.0 and label_smoothing > 0.0:
             raise ValueError(f'label_smoothing = {label_smoothing!r} together with focal_gamma = {focal_gamma!r}: the combination is not defined')
+        ohem = _ohem_args(ohem, focal_gamma, label_smoothing, ignore_index)
         ok = (convt_ce_enabled and target is not None and target.is_cuda and target.dtype == torch.uint8 and target.is_contiguous() and target.dim() == 3
-              and flag is not None and flag.dtype == torch.int32)
+              and flag is not None and flag.dtype == torch.int32 and ohem is None)
         if weight is not None and target is not None:
             weight = class_weight_table(weight, target.device)
         self.new = (target, int(ignore_index), flag, weight, focal_gamma, label_smoothing) if ok else None
@@ -1669,12 +1745,17 @@ class _CrossEntropy(torch.autograd.Function):
         return dl, None, None, None, None, None
 
 
-def cross_entropy(logits, target, ignore_index=255, weight=None, focal_gamma=0.0, label_smoothing=0.0):
+def cross_entropy(logits, target, ignore_index=255, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None):
     """nn.CrossEntropyLoss(weight, ignore_index, label_smoothing=) with mean reduction; target (N,H,W) uint8/long; weight: None, one number per
     class, or a class_weight_table.  focal_gamma > 0: the focal loss sum w[t] (1 - p_t)^gamma (-log p_t) / sum w[t]; 0 changes
     nothing.  label_smoothing in (0, 1]: torch's smoothed loss, with one deviation: a class of weight 0 adds nothing to the
-    smoothing sum even where its -log p is +inf (torch forms 0 * inf = NaN there); 0 changes nothing; together with focal_gamma > 0: ValueError."""
+    smoothing sum even where its -log p is +inf (torch forms 0 * inf = NaN there); 0 changes nothing; together with focal_gamma > 0: ValueError.
+    ohem (ohem_value: None, True, (thresh, min_kept) or a mapping): online hard example mining - the loss of ohem_target's rewritten target, with or
+    without weights (the selection is on the unweighted probability); together with focal_gamma > 0 or label_smoothing > 0: ValueError."""
     weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, logits.device, logits.shape[1], label_smoothing)
+    ohem = _ohem_args(ohem, focal_gamma, label_smoothing, ignore_index)
+    if ohem is not None:
+        target = ohem_target(logits, target, ignore_index, *ohem)
     return _CrossEntropy.apply(logits, target, ignore_index, weight, focal_gamma, label_smoothing)
 
 
@@ -1839,13 +1920,19 @@ def fused_losses_backward(vals):
     torch.autograd.backward([vals], [e3])
 
 
-def fused_losses(outs, target, input_org, ignore_index, w1, w2, stage, flag, subsample_factor=8, weight=None, focal_gamma=0.0, label_smoothing=0.0):
+def fused_losses(outs, target, input_org, ignore_index, w1, w2, stage, flag, subsample_factor=8, weight=None, focal_gamma=0.0, label_smoothing=0.0,
+                 ohem=None):
     """-> 5-float device tensor [CE, w1*MSE, w2*FA, total, NaN flag]; `outs` = DSRL.forward's 4-tuple.  vals[3].backward() is the only
     supported backward (the function is the root of the pass); `flag` is the int32 NaN flag the fused kernels OR into.  weight: per-class CE
     weights (None, one number per class, or a class_weight_table): nn.CrossEntropyLoss(weight=).  focal_gamma > 0 makes the CE term the focal loss
-    (as cross_entropy); 0 changes nothing.  label_smoothing in (0, 1] makes it torch's label-smoothed loss (as cross_entropy); 0 changes nothing."""
+    (as cross_entropy); 0 changes nothing.  label_smoothing in (0, 1] makes it torch's label-smoothed loss (as cross_entropy); 0 changes nothing.
+    ohem (as cross_entropy) mines the hard pixels first: the target is rewritten on the device (ohem_target, which ORs into `flag` too) and
+    everything after it - the loss pass, the hand-over to the layer that produced the logits - runs on the rewritten target as it stands."""
     sssr, sisr, ft1, ft2 = outs
     weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, sssr.device, sssr.shape[1], label_smoothing)
+    ohem = _ohem_args(ohem, focal_gamma, label_smoothing, ignore_index)
+    if ohem is not None:
+        target = ohem_target(sssr, target, ignore_index, *ohem, flag=flag)
     dummy = _const1(0.0, sssr.device)            # stands in for the outputs a lower stage does not have (a cached constant: no fill launch per step)
     return _FusedLosses.apply(sssr, sisr if stage > 1 else dummy, ft1 if stage > 2 else dummy, ft2 if stage > 2 else dummy, target,
                               input_org if stage > 1 else dummy, int(ignore_index), float(w1), float(w2), int(stage), flag, int(subsample_factor), weight,

@@ -512,6 +512,34 @@ int dsrl_convt2x2_bwd_ce_s(const float* x, const float* w, const float* logits, 
                            int ft_stride, float* dx, float* dw, float* dbias /*nullable*/, int N, int H, int W, int Cin, int Cout, void* ws,
                            size_t ws_bytes, dsrl_stream_t stream);
 
+/* Online hard example mining (OHEM) for the cross entropy, as a rewrite of the target: the rule of mmseg's OHEMPixelSampler and HRNet's
+ * OhemCrossEntropy.  For one call of P pixels, `thresh` in [0, 1] and min_kept >= 0:
+ *     a pixel is a candidate iff target != ignore_index && target < C; every other pixel takes no part and keeps its label
+ *     p_i = e_t / s of candidate i in fp32, in the arithmetic of the CE kernels (m = max_c v_c, e_c = exp(v_c - m), s = sum e_c, c ascending);
+ *           a NaN p counts as 0 (the pixel is kept) and raises bit 0 of nan_flag, as a NaN sum does in any pixel
+ *     n candidates (n == 0: nothing changes), k = min(min_kept, n - 1), v = the k-th smallest p counting from 0, thr = max(v, thresh)
+ *     a candidate is kept iff p < thr, strictly; every other candidate gets the label ignore_index
+ * The selection is a value threshold found by an exact radix select on the bit patterns of p (non-negative floats order as unsigned integers; four
+ * passes of 8-bit digits, per-block integer partial histograms, no float atomics): no tie-breaking by index, the same bytes on every call.
+ * n, k and thr are formed on the device and every launch is unconditional: the calls can be captured into a graph.
+ *   dsrl_ohem_prob    p_out[i] = p_i, or 2.0f for a pixel that is not a candidate; reads the logits once (ld >= C; 16-byte loads when ld == C and the
+ *                     base is 16-byte aligned).
+ *   dsrl_ohem_select  stats[4] = {bits of thr, n, number kept, number with p < thresh} from p[P] (any 4-byte aligned buffer: a value >= 2.0f is no
+ *                     candidate, a NaN or a value <= 0 counts as 0).  ws: >= dsrl_ohem_workspace_bytes(P), 16-byte aligned.
+ *   dsrl_ohem_apply   target_out[i] = (p[i] >= 2.0f || p[i] < thr) ? target[i] : ignore_index, thr read from stats[0]; target_out may be target.
+ *   dsrl_ohem_target  the three in order, p kept in ws.  dsrl_ohem_workspace_bytes(P) sizes the p buffer, the partial histograms and the state; it
+ *                     depends on P alone (0, with a message, for P <= 0 or P >= 2^31).
+ * Argument errors (DSRL_E_BADARG before any HIP call, nothing written): null pointers, P <= 0 or >= 2^31, C outside 1..60, ld < C, thresh outside
+ * [0, 1] or NaN, min_kept < 0, ignore_index outside 0..255 (it is written into the target); a workspace too small or misaligned is DSRL_E_WORKSPACE. */
+size_t dsrl_ohem_workspace_bytes(int64_t P);
+int dsrl_ohem_prob(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float* p_out, int* nan_flag /*nullable*/,
+                   dsrl_stream_t stream);
+int dsrl_ohem_select(const float* p, int64_t P, float thresh, int64_t min_kept, uint32_t* stats /*[4]*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+int dsrl_ohem_apply(const float* p, const uint8_t* target, int64_t P, int ignore_index, const uint32_t* stats /*[4]*/, uint8_t* target_out,
+                    dsrl_stream_t stream);
+int dsrl_ohem_target(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float thresh, int64_t min_kept,
+                     uint8_t* target_out, uint32_t* stats /*[4]*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+
 /* FALoss (models/losses/FALoss.py:8-34). fm1/fm2 are (B,C,H,W) with element strides (sb,sc,sh,sw).
  * reduction: 0 mean, 1 sum, 2 none (out has B*C*n*n floats, n = (W/k)^2).
  * `saved` (>= dsrl_fa_saved_floats) carries S1,S2,sigma,u1,v1 to the backward. */

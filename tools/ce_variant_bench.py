@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
 """Cost of one cross-entropy variant at the step's shape (N = 8, tail input 256 x 512, 19 -> 19), written to profiles/<variant>_ce.txt
-(class_weighted_ce.txt, focal_ce.txt, label_smoothing_ce.txt):
+(class_weighted_ce.txt, focal_ce.txt, label_smoothing_ce.txt, ohem_ce.txt):
   * kernel-only times through the C ABI, HIP events around back-to-back launches, the variant's entry points against their base:
       weighted   dsrl_convt2x2_fwd_ce_w, dsrl_convt2x2_bwd_ce_w and dsrl_ce_fused_w against the unweighted calls, and the D pre-pass alone
                  (dsrl_ce_weight_sum: label histogram + weight sum);
       focal      dsrl_ce_fwd_f + dsrl_ce_bwd_f, dsrl_ce_fused_f, dsrl_convt2x2_fwd_ce_f, dsrl_convt2x2_bwd_ce_f against their _w siblings, gamma = 2;
       smoothed   the same four _s paths against their _w siblings, eps = 0.1;
+      ohem       dsrl_ohem_prob beside dsrl_ce_fused on the same logits (time and bytes per second), dsrl_ohem_select, dsrl_ohem_apply and the whole
+                 dsrl_ohem_target, thresh = 0.7, min_kept = 100000;
   * the replayed training step (stage 3, batch 8, 256 x 512 input, hipGraph): default, class weights and (focal, smoothed) class weights + gamma
-    or eps, alternating in one process.
+    or eps, alternating in one process (ohem: default against ohem = (0.7, 100000)).
 Everything in that file from the line '## recorded beside the tool' on is kept as it is.
-Usage: python tools/ce_variant_bench.py weighted|focal|smoothed [--steps K] [--no-step] [VAR=value ...]"""
+Usage: python tools/ce_variant_bench.py weighted|focal|smoothed|ohem [--steps K] [--no-step] [VAR=value ...]"""
 import os
 import sys
 import time
@@ -29,7 +31,8 @@ from dualsuperreslearningforsemseg_amd._lib import call, query                  
 #             the TrainStep keyword of the parameter, output file)
 VARIANTS = {'weighted': ('_w', '', None, None, 'weighted', None, 'class_weighted_ce.txt'),
             'focal': ('_f', '_w', 2.0, 'gamma', 'focal', 'focal_gamma', 'focal_ce.txt'),
-            'smoothed': ('_s', '_w', 0.1, 'eps', 'smoothed', 'label_smoothing', 'label_smoothing_ce.txt')}
+            'smoothed': ('_s', '_w', 0.1, 'eps', 'smoothed', 'label_smoothing', 'label_smoothing_ce.txt'),
+            'ohem': ('', '', (0.7, 100000), 'ohem', 'ohem', 'ohem', 'ohem_ce.txt')}
 if not args or args[0] not in VARIANTS:
     sys.exit(__doc__)
 VARIANT = args[0]
@@ -131,6 +134,47 @@ def kernels():
         say(f'  D  dsrl_convt2x2_bwd_ce   weighted {a:7.1f} ({waves:>2} waves)   {WORD} {bb:7.1f} (8 waves, DSRL_CONVT_CE_WAVES={waves})   ({bb - a:+.1f})')
 
 
+def ohem_kernels():
+    N, H, W, C = 8, 256, 512, 19
+    P = N * 4 * H * W
+    thresh, min_kept = PARAM
+    # logits of a few units whose labels follow their own ranking in part: p from about 0 to about 1, as in training after the first epochs
+    y = torch.randn(N, 2 * H, 2 * W, C, device=dev) * 3
+    top = y.argmax(dim=-1).to(torch.uint8)
+    tg = torch.randint(0, C, (N, 2 * H, 2 * W), device=dev, dtype=torch.uint8)
+    tg = torch.where(torch.rand(tg.shape, device=dev) < 0.6, top, tg)
+    tg[torch.rand(tg.shape, device=dev) < 0.1] = 255
+    dl = torch.empty_like(y); out = torch.empty_like(tg)
+    scal = torch.zeros(8, device=dev); flag = torch.zeros(1, dtype=torch.int32, device=dev); stats = torch.zeros(4, dtype=torch.int32, device=dev)
+    st = HF._stream()
+    wsf = torch.empty(query('dsrl_ce_fused_workspace_bytes', P), dtype=torch.uint8, device=dev)
+    wso = torch.empty(query('dsrl_ohem_workspace_bytes', P), dtype=torch.uint8, device=dev)
+    p = torch.empty(P, device=dev)
+    t = {}
+    t['fused'] = timeit(lambda: call('dsrl_ce_fused', y.data_ptr(), C, tg.data_ptr(), P, C, 255, dl.data_ptr(), C, scal.data_ptr(), flag.data_ptr(),
+                                     wsf.data_ptr(), wsf.numel(), st))
+    t['value'] = timeit(lambda: call('dsrl_ce_fused', y.data_ptr(), C, tg.data_ptr(), P, C, 255, None, C, scal.data_ptr(), flag.data_ptr(),
+                                     wsf.data_ptr(), wsf.numel(), st))
+    t['prob'] = timeit(lambda: call('dsrl_ohem_prob', y.data_ptr(), C, tg.data_ptr(), P, C, 255, p.data_ptr(), flag.data_ptr(), st))
+    t['select'] = timeit(lambda: call('dsrl_ohem_select', p.data_ptr(), P, thresh, min_kept, stats.data_ptr(), wso.data_ptr(), wso.numel(), st))
+    t['apply'] = timeit(lambda: call('dsrl_ohem_apply', p.data_ptr(), tg.data_ptr(), P, 255, stats.data_ptr(), out.data_ptr(), st))
+    t['target'] = timeit(lambda: call('dsrl_ohem_target', y.data_ptr(), C, tg.data_ptr(), P, C, 255, thresh, min_kept, out.data_ptr(), stats.data_ptr(),
+                                      flag.data_ptr(), wso.data_ptr(), wso.numel(), st))
+    torch.cuda.synchronize()
+    s4 = stats.cpu().numpy().view(np.uint32)
+    lb = P * C * 4
+    say(f'kernel-only, us per call (N = {N}, tail input {H} x {W}, {P} pixels, {lb / 1e6:.0f} MB of logits; thresh = {thresh}, min_kept = {min_kept}; mean of 20')
+    say(f'back-to-back calls; this batch: {int(s4[1])} candidates, {int(s4[2])} kept, thr = {float(s4[:1].view(np.float32)[0]):.6f}):')
+    rows = (('dsrl_ce_fused, value + gradient (count pre-pass + ce_fused_kernel + finalize)', 'fused', 2 * lb + 2 * P),
+            ('dsrl_ce_fused, value only, as in the hand-over step', 'value', lb + 2 * P),
+            ('dsrl_ohem_prob (ohem_prob_kernel)', 'prob', lb + P + 4 * P),
+            ('dsrl_ohem_select (4 x histogram + pick)', 'select', 4 * 4 * P),
+            ('dsrl_ohem_apply', 'apply', 4 * P + 2 * P),
+            ('dsrl_ohem_target (the three above)', 'target', lb + P + 4 * P + 4 * 4 * P + 4 * P + 2 * P))
+    for label, key, nbytes in rows:
+        say(f'  {label:<78} {t[key]:7.1f}   {nbytes / 1e6:6.1f} MB   {nbytes / t[key] / 1e6:5.2f} TB/s')
+
+
 def replayed_step():
     import dualsuperreslearningforsemseg_amd as D
     from dualsuperreslearningforsemseg_amd import settings
@@ -157,6 +201,8 @@ def replayed_step():
             step.collect()
     if VARIANT == 'weighted':
         kinds = {'unweighted': {}, 'weighted': {'class_weights': w}}
+    elif VARIANT == 'ohem':
+        kinds = {'default': {}, 'ohem': {'ohem': PARAM}}
     else:
         kinds = {'default': {}, 'weighted': {'class_weights': w}, WORD: {'class_weights': w, STEP_KW: PARAM}}
     res, replays = {k: [] for k in kinds}, {}
@@ -177,12 +223,14 @@ def replayed_step():
         say(f'  {k:<{width}} ' + '  '.join(f'{v:.3f}' for v in res[k]) + f'   min {min(res[k]):.3f}  (replays {replays[k]})')
     if VARIANT == 'weighted':
         say(f"  weighted - unweighted (min): {(min(res['weighted']) - min(res['unweighted'])) * 1e3:+.0f} us")
+    elif VARIANT == 'ohem':
+        say(f"  ohem - default (min): {(min(res['ohem']) - min(res['default'])) * 1e3:+.0f} us")
     else:
         say(f"  {WORD} - weighted (min): {(min(res[WORD]) - min(res['weighted'])) * 1e3:+.0f} us;  {WORD} - default (min): "
             f"{(min(res[WORD]) - min(res['default'])) * 1e3:+.0f} us")
 
 
-kernels()
+ohem_kernels() if VARIANT == 'ohem' else kernels()
 if '--no-step' not in args:
     replayed_step()
 out = os.path.join(ROOT, 'profiles', OUT)
