@@ -189,6 +189,12 @@ PROTOTYPES = {
     'dsrl_sgd_step': (i32, [fp, fp, fp, i64, f32, f32, f32, f32, stream_t]),
     'dsrl_sgd_step_dev': (i32, [fp, fp, fp, i64, fp, stream_t]),
     'dsrl_sgd_step_dev_segments': (i32, [fp, fp, fp, fp, i64, fp, stream_t]),
+    'dsrl_sgd_step_ema': (i32, [fp, fp, fp, i64, f32, f32, f32, f32, fp, fp, stream_t]),
+    'dsrl_sgd_step_dev_ema': (i32, [fp, fp, fp, i64, fp, fp, fp, stream_t]),
+    'dsrl_sgd_step_dev_segments_ema': (i32, [fp, fp, fp, fp, i64, fp, fp, fp, stream_t]),
+    'dsrl_ema_update': (i32, [fp, fp, i64, fp, stream_t]),
+    'dsrl_ema_advance': (i32, [fp, stream_t]),
+    'dsrl_arena_swap': (i32, [fp, fp, i64, stream_t]),
     'dsrl_nan_check': (i32, [fp, i64, fp, stream_t]),
     'dsrl_rng_bind_device_key': (i32, [fp]),
     'dsrl_rng_advance_key': (i32, [fp, stream_t]),

@@ -11,6 +11,7 @@ probabilities averaged); benchmark.txt then says so.
 `scales=(0.5, 0.75, ...)` in other_args: every batch is evaluated as the multi-scale ensemble (`DSRL.predict(scales=...)`; combines with `flip`);
 the value is validated before any device work, benchmark.txt names the scales and the view sizes, and with `compiled_model` the command raises
 before it loads anything (graph replay of the multi-scale path is not built).
+`ema=True` in other_args: `weights` names a checkpoint written with dataset['ema'] and its averaged weights ('ema_state_dict') are evaluated.
 Beside the reference's per-batch figures the command accumulates ONE confusion matrix over the split on the device (the kernel that writes the
 class map fills it; it comes back in the same single read) and reports the dataset-level figures from it - intersections and unions summed over the
 split, then IoU per class, then the mean over the classes, as Cityscapes results are published - with a per-class table in benchmark.txt and the
@@ -33,9 +34,10 @@ from .train_or_resume import isCUDAdevice
 NOT_GPU = "this build runs on the MI355X only: use device='gpu' (the reference's --device cpu path is its own)"
 
 
-def load_eval_model(weights, dataset_settings, device_obj):
-    """Stage-1 DSRL in eval mode with the matching entries of the file's state dict (a stage-2/3 file carries more: strict=False, as the reference)."""
-    d = load_checkpoint_or_weights(weights, map_location='cpu')
+def load_eval_model(weights, dataset_settings, device_obj, ema=False):
+    """Stage-1 DSRL in eval mode with the matching entries of the file's state dict (a stage-2/3 file carries more: strict=False, as the reference).
+    `ema`: the averaged weights of a checkpoint written with dataset['ema'] (utils.load_checkpoint_or_weights)."""
+    d = load_checkpoint_or_weights(weights, map_location='cpu', ema=ema)
     if d.get('format') is not None:
         raise RuntimeError(f"'{weights}' is a compiled model file (written by the compile_model command): pass compiled_model=True to read it")
     model = DSRL(stage=1, dataset_settings=dataset_settings).eval()
@@ -71,7 +73,7 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
         from ..inference import load_compiled_model
         model, predictor = load_compiled_model(weights, device_obj)          # frozen operands + hipGraph replay: the same class maps, counters and losses
     else:
-        model = load_eval_model(weights, ds, device_obj)
+        model = load_eval_model(weights, ds, device_obj, ema=other_args.get('ema', False))
     predict = model.predict if predictor is None else predictor
     flip = bool(other_args.get('flip'))
     if scales is not None:

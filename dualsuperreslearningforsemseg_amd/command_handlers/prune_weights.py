@@ -15,7 +15,7 @@ from ..utils import load_checkpoint_or_weights
 @t.no_grad()
 def prune_weights(src_weights, dest_weights, dataset, **other_args):
     model = DSRL(stage=1, dataset_settings=dataset['settings'], init_weights=False).eval()
-    src = load_checkpoint_or_weights(src_weights, map_location='cpu')
+    src = load_checkpoint_or_weights(src_weights, map_location='cpu', ema=other_args.get('ema', False))      # ema=True: the averaged weights of a checkpoint
     missing, _dropped = model.load_state_dict(src['model_state_dict'], strict=False)
     missing = [k for k in missing if not k.endswith('num_batches_tracked')]
     if missing:

@@ -15,8 +15,10 @@ What differs by design:
     (callable(split, batch_size, device, rank, world) -> iterable of ((input_image, input_org), (target, _))), which is used as given;
     `SyntheticCityscapes` below provides device-resident batches of the Cityscapes shapes.
 """
+import contextlib
 import glob
 import os
+import warnings
 from datetime import datetime
 
 import torch as t
@@ -95,7 +97,10 @@ class TrainStep:
     run (HF.ohem_target), fused and unfused losses, eager and captured.  `do_train=False` keeps the configured CE without mining, so
     validation losses stay comparable between runs with and without it.  It goes with `class_weights` (the selection is on the unweighted
     probability) and not with `focal_gamma` > 0 or `label_smoothing` > 0 (ValueError); `ignore_index` must then be a byte value.  With more than one
-    rank each rank mines its own batch.  Fixed for the life of the step, like the other two."""
+    rank each rank mines its own batch.  Fixed for the life of the step, like the other two.
+
+    The weight average (`flat.enable_ema`) needs nothing here: the optimiser pass of the step updates it, eagerly and in the captured
+    graph alike, and whether it is enabled is part of the graph key.  A training iteration inside `flat.ema_weights()` raises DsrlHipError."""
 
     GRAPH_WARMUP = HF.GRAPH_WARMUP          # eager iterations per batch shape before the capture
 
@@ -247,6 +252,7 @@ class TrainStep:
 
     def _graph_key(self, input_image, input_org, target):
         return (tuple(input_image.shape), tuple(input_org.shape), tuple(target.shape), HF.get_conv_precision(), HF.overlap_wgrad,
+                self.flat.e_flat is not None,           # "EMA enabled": a step captured without the weight average has no launch that updates it
                 self.focal_gamma, self.label_smoothing, self.ohem)
 
     def _capture(self, key, input_image, input_org, target, hp):
@@ -346,6 +352,8 @@ class TrainStep:
         import time
         t_host0 = time.perf_counter()
         hp = (lr, momentum, weight_decay)
+        if do_train and self.flat.ema_swapped:
+            raise HF.DsrlHipError('a training step inside FlatParams.ema_weights(): the parameters are the averaged ones')
         if do_train and self.use_graph:
             if self.rng is None:
                 self.rng = HF.DeviceRng(self.flat.device)
@@ -452,6 +460,21 @@ def check_ohem(dataset):
     return HF._ohem_args(dataset.get('ohem'), check_focal_gamma(dataset), check_label_smoothing(dataset), dataset['settings'].IGNORE_CLASS_LABEL)
 
 
+def check_ema(dataset):
+    """dataset['ema']: absent, None or False -> None (off); True, a decay in (0, 1), a pair (decay, warmup) or a mapping with these keys ->
+    (decay, warmup), as HF.ema_value; ValueError otherwise.  Touches no device."""
+    return HF.ema_value(dataset.get('ema'))
+
+
+def checkpoint_dict(have, ema_state_dict=None):
+    """What a checkpoint file holds: every key of settings.VARIABLES_IN_CHECKPOINT out of `have` and nothing else - the reference's layout -, plus
+    'ema_state_dict' (FlatParams.ema_state_dict()) in a run with dataset['ema'].  'model_state_dict' stays the live weights: a resume needs them."""
+    out = {k: have[k] for k in settings.VARIABLES_IN_CHECKPOINT}
+    if ema_state_dict is not None:
+        out['ema_state_dict'] = ema_state_dict
+    return out
+
+
 def train_or_resume(is_resuming_training, device, distributed, mixed_precision, disable_cudnn_benchmark, num_workers, dataset, val_interval,
                     checkpoint_interval, checkpoint_history, init_weights, batch_size, epochs, learning_rate, end_learning_rate, momentum,
                     weights_decay, poly_power, stage, w1, w2, freeze_batch_norm, experiment_id, description, early_stopping, dry_run=False, **other_args):
@@ -465,6 +488,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     focal_gamma = check_focal_gamma(dataset)
     label_smoothing = check_label_smoothing(dataset)
     ohem = check_ohem(dataset)
+    ema = check_ema(dataset)
     input_size = other_args.get('model_input_size', settings.MODEL_INPUT_SIZE)
     if distributed:
         t.manual_seed(settings.RANDOM_SEED)                                                # identical init on all ranks, :31
@@ -504,6 +528,17 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     flat = FlatParams(model)                                                               # DDP wrap, :105-106
     if is_resuming_training and 'optimizer_state_dict' in other_args:
         flat.load_state_dict(other_args['optimizer_state_dict'])
+    if ema is not None:
+        # dataset['ema']: an exponential moving average of the weights and BatchNorm statistics, updated inside the optimiser launches.
+        # Validation - and with it the best checkpoint, early stopping and the dataset-level figures - measures the AVERAGED model, the final weights file
+        # stores it, checkpoints carry it as 'ema_state_dict' beside the live weights a resume needs.  With several ranks every rank averages its own
+        # arenas: the parameters are identical on all of them, the buffers are rank 0's, and only rank 0's average is ever read (validation and files).
+        flat.enable_ema(*ema)             # after the broadcast and the state load: the average starts from the weights training starts from
+        if is_resuming_training:
+            if other_args.get('ema_state_dict') is not None:
+                flat.load_ema_state_dict(other_args['ema_state_dict'])
+            else:
+                warnings.warn("resuming with dataset['ema'] from a checkpoint without 'ema_state_dict': the average starts from the loaded weights at 0 updates")
     factory = dataset.get('loader_factory')
     own_loader = factory is None
     if own_loader:
@@ -542,7 +577,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
                 'MSE_val_avg_loss': MSE_val_avg_loss, 'FA_val_avg_loss': FA_val_avg_loss, 'Avg_val_loss': Avg_val_loss, 'epoch': epoch,
                 'best_validation_dict': best_validation_dict, 'model_state_dict': _get_state_dict(model),
                 'optimizer_state_dict': flat.state_dict(lr, momentum, weights_decay, initial_lr=learning_rate)}
-        t.save({k: have[k] for k in settings.VARIABLES_IN_CHECKPOINT}, os.path.join(ckpt_dir, filename))
+        t.save(checkpoint_dict(have, flat.ema_state_dict() if ema is not None else None), os.path.join(ckpt_dir, filename))
         return ckpt_dir
 
     if conv_arith is not None:
@@ -566,7 +601,8 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
                             os.remove(stale)
                 if val_loader is not None and epoch % val_interval == 0:                                            # :294
                     details = {}
-                    rec['val'] = _do_train_val(False, epoch, model, step, val_loader, lr, momentum, weights_decay, False, True, details)
+                    with flat.ema_weights() if ema is not None else contextlib.nullcontext():      # the averaged model is the one that is measured
+                        rec['val'] = _do_train_val(False, epoch, model, step, val_loader, lr, momentum, weights_decay, False, True, details)
                     rec['val_mIoU_dataset'], rec['val_IoU_per_class'] = rec['val'][6], details['IoU_per_class']
                     CE_val_avg_loss, MSE_val_avg_loss, FA_val_avg_loss, Avg_val_loss, val_mIoU = rec['val'][:5]
                     if val_mIoU > best_validation_dict['best_miou_percent']:                                        # :318-337
@@ -594,8 +630,13 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     if is_master_rank and experiment_id:
         wdir = os.path.join(experiment_id, settings.WEIGHTS_DIR.format(stage=stage))
         os.makedirs(wdir, exist_ok=True)
-        t.save({'model_state_dict': _get_state_dict(model), 'mixed_precision': mixed_precision, 'amp_state_dict': amp_state_dict},
-               os.path.join(wdir, settings.FINAL_WEIGHTS_FILE))                               # utils.py:277-282
+        final = {'model_state_dict': _get_state_dict(model), 'mixed_precision': mixed_precision, 'amp_state_dict': amp_state_dict}
+        if ema is not None:
+            # the averaged weights: the model validation measured, and what the next stage starts from
+            avg = flat.ema_state_dict()
+            final['ema'] = {'decay': avg.pop('ema_decay'), 'updates': avg.pop('ema_updates')}
+            final['model_state_dict'] = avg
+        t.save(final, os.path.join(wdir, settings.FINAL_WEIGHTS_FILE))                        # utils.py:277-282
         history.append({'elapsed': str(datetime.now() - process_start_timestamp)})
     return history
 

@@ -178,6 +178,18 @@ __device__ __forceinline__ void smooth_pixel(const float* v, const float* w, int
 __device__ __forceinline__ float smooth_sub(float eps, int C, float wc, float scale) { return ((eps / (float)C) * wc) * scale; }
 __device__ __forceinline__ float smooth_grad(float e, float inv, bool hit, float sub_t, float sub_c) { return e * inv - (hit ? sub_t : sub_c); }
 
+// ---------------------------------------------------------------- exponential moving average of the weights (ema.hip)
+// The EMA record in device memory (16 bytes, 16-byte aligned).  omd = 1 - d_t of the update ABOUT to run; dsrl_ema_advance rewrites it once per step.
+struct EmaRecord {
+    float omd;          // 1 - d_t: all that the element kernels read
+    float decay_max;    // the configured decay, d_t's limit
+    uint32_t updates;   // averages formed so far (t)
+    uint32_t warmup;    // non-zero: d_t = min(decay_max, (1 + t) / (10 + t))
+};
+// e <- d e + (1 - d) p as e + (1 - d) (p - e): one difference and one fma, so e == p stays e for every d, and the error per step is an ulp of e.
+// Every EMA kernel - fused into an SGD launch or not - goes through this one function, so that the fused and the unfused paths round alike.
+__device__ __forceinline__ float ema_elem(float e, float p_new, float omd) { return fmaf(omd, p_new - e, e); }
+
 // ---------------------------------------------------------------- wave / block reductions
 __device__ inline float wave_sum(float v) {
 #pragma unroll

@@ -16,6 +16,8 @@ One process per GPU; `torch.distributed` backend 'nccl' is RCCL on ROCm.  With w
 collectives are skipped and only the arena + fused optimiser remain.
 """
 
+import contextlib
+
 import torch
 import torch.distributed as dist
 
@@ -99,6 +101,9 @@ class FlatParams:
         self.filters = FilterOperands([w for w in conv_filters(model) if id(w) in mine] if dev.type == 'cuda' else [], dev, transposed=True)
         self.filters.attach()
         self._seg_tables, self._amax_key = {}, None        # segment tables of the optimiser pass by arena range; key under which its filter magnitudes are valid
+        # the weight average (enable_ema): arenas laid out as p_flat / b_flat, the 16-byte device record, and whether ema_weights() has them swapped in
+        self.e_flat = self.eb_flat = self.ema_rec = self.ema_config = None
+        self.ema_swapped = False
         if self.world > 1 and self.device.type == 'cuda' and HF.knob('DSRL_BN_FUSED_BIG', None) is None:
             # RCCL kernels hold CUs while they wait for their peers: a 256-block fused-BN launch (one block on EVERY CU) could stall behind
             # them, the 128-block variant cannot
@@ -106,6 +111,7 @@ class FlatParams:
         if self.world > 1:
             dist.broadcast(self.p_flat, 0, group=self.pg)          # DDP constructor semantics: rank 0's weights win
             dist.broadcast(self.b_flat, 0, group=self.pg)
+            self.invalidate_filter_amax()                          # the collective wrote the parameters behind torch's version counters
             for i, p in enumerate(self.params):
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._make_hook(i)))
 
@@ -176,8 +182,19 @@ class FlatParams:
         return tab
 
     def _sgd_range(self, a, b, hyper, hp):
-        """SGD on arena range [a, b): with device-resident hyper-parameters and the f16 arithmetics, by the segment kernel that also measures the filters."""
-        if hyper is not None and self._fold_amax():
+        """SGD on arena range [a, b): with device-resident hyper-parameters and the f16 arithmetics, by the segment kernel that also measures the filters.
+        With the weight average enabled the same three launches in their _ema forms: e_flat follows in the launch that writes p_flat."""
+        if self.e_flat is not None:
+            e, rec = self.e_flat, self.ema_rec
+            if hyper is not None and self._fold_amax():
+                tab, n = self._segments(a, b)
+                HF.call('dsrl_sgd_step_dev_segments_ema', self.p_flat.data_ptr(), self.g_flat.data_ptr(), self.m_flat.data_ptr(), tab.data_ptr(), n, hyper.data_ptr(),
+                        e.data_ptr(), rec.data_ptr(), HF._stream())
+            elif hyper is not None:
+                HF.sgd_step_dev_ema_(self.p_flat[a:b], self.g_flat[a:b], self.m_flat[a:b], hyper, e[a:b], rec)
+            else:
+                HF.sgd_step_ema_(self.p_flat[a:b], self.g_flat[a:b], self.m_flat[a:b], hp[0], hp[1], hp[2], 1.0 / self.world, e[a:b], rec)
+        elif hyper is not None and self._fold_amax():
             tab, n = self._segments(a, b)
             HF.call('dsrl_sgd_step_dev_segments', self.p_flat.data_ptr(), self.g_flat.data_ptr(), self.m_flat.data_ptr(), tab.data_ptr(), n, hyper.data_ptr(), HF._stream())
         elif hyper is not None:
@@ -319,6 +336,7 @@ class FlatParams:
         single 239.5 MB call of round 4 exposed the whole optimiser pass behind the exchange).  Only element-wise kernels touch the ranges, so they
         need no parameter alignment beyond 16 bytes; no barrier kernel is co-resident with RCCL here - those are all inside the graph that has
         finished.  Bit-identical to reduce_all() + one SGD launch (same element-wise arithmetic).  Returns the chunk ranges (tests)."""
+        self._refuse_swapped('reduce_chunked_and_step')
         n = max(1, HF.knob('DSRL_REDUCE_CHUNKS', 4) if nchunks is None else int(nchunks))
         per = _align(-(-self.numel // n), 1024)
         ranges = [(a, min(a + per, self.numel)) for a in range(0, self.numel, per)]
@@ -338,12 +356,14 @@ class FlatParams:
         """torch.optim.SGD(momentum, weight_decay).step() on the whole arena; gradients are averaged over ranks here.  `hyper`: a
         4-float device tensor (lr, momentum, weight_decay, 1/world) the kernel reads when it runs (graph-replayable) instead of the
         three host values."""
+        self._refuse_swapped('sgd_step')
         if reduce:
             self.finish_reduction()
         self._update([(0, self.numel)], [], hyper, (lr, momentum, weight_decay))
 
     def _update(self, ranges, works, hyper, hp):
         """SGD over `ranges` of the arena, range k as soon as works[k] (its all-reduce, if any) is done; then the step is over."""
+        self._refuse_swapped('the optimiser step')
         fold = hyper is not None and self._fold_amax()
         if fold:
             self.filters.amax.zero_()
@@ -351,6 +371,11 @@ class FlatParams:
             if works:
                 works[i].wait()             # stream-ordered for RCCL: the compute stream waits for this range only
             self._sgd_range(a, b, hyper, hp)
+        if self.e_flat is not None:
+            # every range above read the same omd; the buffers' average follows (the step's forward has left the running statistics), then the
+            # schedule moves on - once per step, on the device
+            HF.ema_update_(self.eb_flat, self.b_flat, self.ema_rec)
+            HF.ema_advance_(self.ema_rec)
         self._amax_key = self._params_key() if fold else None
         if self.device.type == 'cuda':
             HF.amax_end_step(self.device)       # records asked for between steps (validation) come from the loose arena, not from the step's
@@ -379,12 +404,14 @@ class FlatParams:
             if sd['numel'] != self.numel:
                 raise ValueError('optimizer arena size mismatch')
             self.m_flat.copy_(sd['momentum_arena'])
+            self.invalidate_filter_amax()
             return
         ps = self._trainable_in_model_order()
         ids = [i for g in sd['param_groups'] for i in g['params']]
         if len(ids) != len(ps):
             raise ValueError(f'optimizer state has {len(ids)} parameters, the model {len(ps)}')
         self.m_flat.zero_()
+        self.invalidate_filter_amax()           # a restored state: whatever wrote the parameters beside it may not have moved the version counters
         with torch.no_grad():
             for p, i in zip(ps, ids):
                 st = sd['state'].get(i)
@@ -395,3 +422,121 @@ class FlatParams:
                     raise ValueError(f'momentum buffer {tuple(buf.shape)} does not match parameter {tuple(p.shape)}')
                 o = self.offsets[self._index[id(p)]]
                 self.m_flat.as_strided(p.shape, p.stride(), o).copy_(buf.to(self.device))
+
+    # ------------------------------------------------------------------ filter magnitudes left by the optimiser pass: explicit invalidation
+    def invalidate_filter_amax(self):
+        """The magnitudes the optimiser pass left (_amax_key) are trusted while torch's version counters stand still (_params_key); a writer those
+        counters do not see - a collective on the arena, a raw-pointer kernel such as the swap of ema_weights(), `.data` writes - calls this, and
+        the next step measures the filters again.  External code that writes parameters through `.data` must call it too."""
+        self._amax_key = None
+
+    # ------------------------------------------------------------------ exponential moving average of the weights (DESIGN.md 6.1.6)
+    def enable_ema(self, decay, warmup=True):
+        """Starts the weight average from the CURRENT parameters and buffers: e_flat / eb_flat (copies of p_flat / b_flat) and the device record
+        {omd = 1 - d_0, decay, updates = 0, warmup}.  From here every optimiser pass updates e_flat in the launch that writes p_flat, eb_flat
+        behind it, and advances the schedule on the device (d_t = min(decay, (1 + t) / (10 + t)) under warm-up).  Call it after a state load, so
+        that the average starts from the weights training starts from; a second call raises.  With several ranks every rank averages its own
+        arenas: the parameters are identical, the buffers are rank 0's after every broadcast, and only rank 0's average is ever read."""
+        if self.e_flat is not None:
+            raise HF.DsrlHipError('enable_ema: the weight average of this FlatParams is already enabled')
+        cfg = HF.ema_value((decay, warmup))
+        if cfg is None:
+            raise ValueError(f'enable_ema: decay = {decay!r}')
+        self.ema_config = cfg
+        self.e_flat = self.p_flat.detach().clone()
+        self.eb_flat = self.b_flat.detach().clone()
+        self.ema_rec = HF.ema_record(cfg[0], cfg[1], 0, self.device)
+
+    def ema_updates(self):
+        """Averages formed so far, read from the device record (synchronises)."""
+        self._need_ema('ema_updates')
+        return HF.ema_record_read(self.ema_rec)['updates']
+
+    def _need_ema(self, what):
+        if self.e_flat is None:
+            raise HF.DsrlHipError(f'{what}: the weight average is not enabled (enable_ema)')
+
+    def _refuse_swapped(self, what):
+        if self.ema_swapped:
+            raise HF.DsrlHipError(f'{what} inside ema_weights(): the parameters are the averaged ones, a training step would update the average as if it were the model')
+
+    def _swap_ema(self):
+        HF.arena_swap_(self.p_flat, self.e_flat)
+        HF.arena_swap_(self.b_flat, self.eb_flat)
+        # the kernels wrote behind torch's back: drop what was derived from the old values, and move every counter a watcher reads (_params_key,
+        # inference.FrozenOperands).  A parameter's counter is its own, not the arena's
+        self.invalidate_filter_amax()
+        self.filters.invalidate()
+        bump = torch.autograd.graph.increment_version
+        bump(self.p_flat)
+        bump(self.b_flat)
+        for p in self.params:
+            bump(p)
+        for mod, name, _, _ in self.buffers:
+            bump(mod._buffers[name])
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model IS the averaged model: p_flat <-> e_flat and b_flat <-> eb_flat are exchanged in place (two launches, no
+        third buffer) and exchanged back on exit, bit for bit.  For validation and for writing weights; a training step inside raises."""
+        self._need_ema('ema_weights')
+        self._refuse_swapped('ema_weights (nested)')
+        self._swap_ema()
+        self.ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self.ema_swapped = False
+
+    def _ema_sources(self):
+        """state_dict key -> the tensor of the averaged model: views of e_flat / eb_flat for what the arenas hold, the live tensor for the rest
+        (integer buffers such as num_batches_tracked, parameters that do not train)."""
+        src = {}
+        pviews = {id(p): self.e_flat.as_strided(p.shape, p.stride(), o) for p, o in zip(self.params, self.offsets)}
+        bviews = {(id(mod), name): self.eb_flat[o:o + b.numel()].view(b.shape) for mod, name, o, b in self.buffers}
+        for prefix, mod in self.model.named_modules(remove_duplicate=False):
+            dot = prefix + '.' if prefix else ''
+            for name, p in mod._parameters.items():
+                if p is not None:
+                    src[dot + name] = pviews.get(id(p), p)
+            for name, b in mod._buffers.items():
+                if b is not None and name not in mod._non_persistent_buffers_set:
+                    src[dot + name] = bviews.get((id(mod), name), b)
+        return src
+
+    def ema_state_dict(self):
+        """The averaged model in the layout of model.state_dict() - same keys, logical NCHW shapes, tensors on the arena's device -, parameters and
+        float buffers from the EMA arenas, integer buffers from the live model, plus 'ema_updates' (int) and 'ema_decay' (float)."""
+        self._need_ema('ema_state_dict')
+        if self.ema_swapped:
+            raise HF.DsrlHipError('ema_state_dict inside ema_weights(): the arenas are exchanged')
+        src = self._ema_sources()
+        sd = {k: src[k].detach().clone() for k in self.model.state_dict().keys()}
+        rec = HF.ema_record_read(self.ema_rec)
+        sd['ema_updates'], sd['ema_decay'] = rec['updates'], rec['decay_max']
+        return sd
+
+    def load_ema_state_dict(self, sd):
+        """Restores the average from ema_state_dict(): the arenas from the tensors, `updates` from 'ema_updates', and omd recomputed from it under
+        the decay and warm-up this FlatParams was enabled with (the run's setting rules; 'ema_decay' records what the file was written with)."""
+        self._need_ema('load_ema_state_dict')
+        if self.ema_swapped:
+            raise HF.DsrlHipError('load_ema_state_dict inside ema_weights(): the arenas are exchanged')
+        src = self._ema_sources()
+        keys = set(self.model.state_dict().keys())
+        missing = keys - set(sd)
+        if missing or 'ema_updates' not in sd:
+            raise ValueError(f'ema state has no {sorted(missing)[:3] or "ema_updates"!r}: not an ema_state_dict of this model')
+        with torch.no_grad():
+            for k in keys:
+                dst = src[k]
+                if dst.dtype != torch.float32 or not (dst._base is self.e_flat or dst._base is self.eb_flat):
+                    continue                    # lives in the model, not in the average
+                if tuple(sd[k].shape) != tuple(dst.shape):
+                    raise ValueError(f'ema state: {k} is {tuple(sd[k].shape)}, the model {tuple(dst.shape)}')
+                dst.copy_(sd[k].to(self.device))
+        updates = int(sd['ema_updates'])
+        if not 0 <= updates < 2 ** 32:
+            raise ValueError(f'ema state: ema_updates = {updates!r}')
+        self.ema_rec.copy_(HF.ema_record(self.ema_config[0], self.ema_config[1], updates, self.device))

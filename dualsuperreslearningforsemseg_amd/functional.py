@@ -1997,6 +1997,99 @@ def sgd_step_dev_(p, g, buf, hyper):
     call('dsrl_sgd_step_dev', p.data_ptr(), g.data_ptr(), buf.data_ptr(), p.numel(), hyper.data_ptr(), _stream())
 
 
+def sgd_step_ema_(p, g, buf, lr, momentum, weight_decay, grad_scale, ema, record):
+    """sgd_step_ with the weight average `ema` updated from the new p in the same launch (`record`: the 16-byte EMA record, ema_record())."""
+    _need_gpu(p, g, buf, ema, record)
+    call('dsrl_sgd_step_ema', p.data_ptr(), g.data_ptr(), buf.data_ptr(), p.numel(), float(lr), float(momentum), float(weight_decay),
+         float(grad_scale), ema.data_ptr(), record.data_ptr(), _stream())
+
+
+def sgd_step_dev_ema_(p, g, buf, hyper, ema, record):
+    """sgd_step_dev_ with the weight average updated in the same launch."""
+    _need_gpu(p, g, buf, hyper, ema, record)
+    call('dsrl_sgd_step_dev_ema', p.data_ptr(), g.data_ptr(), buf.data_ptr(), p.numel(), hyper.data_ptr(), ema.data_ptr(), record.data_ptr(), _stream())
+
+
+# ------------------------------------------------------------------------------------------------ weight EMA (DESIGN.md 6.1.6)
+EMA_DEFAULT = (0.999, True)             # decay, warmup of `ema=True`
+
+
+def ema_value(x):
+    """The weight average as (decay, warmup), or None when it is off.  None / False: off; True: EMA_DEFAULT; a number d in (0, 1): (d, True); a pair
+    (decay, warmup); a mapping with the keys 'decay' and / or 'warmup' (a missing one takes its default).  decay: a number in (0, 1), also as fp32;
+    warmup: a bool.  ValueError on anything else - a bool where the decay belongs, a NaN, an unknown key.  Touches no device."""
+    if x is None:
+        return None
+    if isinstance(x, (bool, np.bool_)):
+        return EMA_DEFAULT if x else None
+    if isinstance(x, dict):
+        if not x or set(x) - {'decay', 'warmup'}:
+            raise ValueError(f"ema = {x!r}: expected a mapping with the keys 'decay' and 'warmup'")
+        decay, warmup = x.get('decay', EMA_DEFAULT[0]), x.get('warmup', EMA_DEFAULT[1])
+    elif isinstance(x, (tuple, list)) and len(x) == 2:
+        decay, warmup = x
+    elif isinstance(x, (int, float, np.integer, np.floating)):
+        decay, warmup = x, True
+    else:
+        raise ValueError(f'ema = {x!r}: expected None, a bool, a decay in (0, 1), a pair (decay, warmup) or a mapping with these keys')
+    if isinstance(decay, (bool, np.bool_)) or not isinstance(decay, (int, float, np.integer, np.floating)):
+        raise ValueError(f'ema: decay = {decay!r}: expected a number in (0, 1)')
+    d = float(decay)
+    if not (0.0 < d < 1.0) or not (0.0 < float(np.float32(d)) < 1.0):            # (a NaN fails the comparison; the kernels take it as fp32)
+        raise ValueError(f'ema: decay = {decay!r}: expected a number in (0, 1)')
+    if not isinstance(warmup, (bool, np.bool_)):
+        raise ValueError(f'ema: warmup = {warmup!r}: expected a bool')
+    return d, bool(warmup)
+
+
+def ema_decay(t, decay_max, warmup):
+    """d_t, the decay of update number t (0-based), in fp32 as dsrl_ema_advance computes it: min(decay_max, (1 + t) / (10 + t)) under warm-up."""
+    d = np.float32(decay_max)
+    if warmup:
+        tf = np.float32(t)
+        d = min(d, (np.float32(1) + tf) / (np.float32(10) + tf))
+    return np.float32(d)
+
+
+def ema_record(decay_max, warmup, updates, device):
+    """A new EMA record (include/dsrl_hip.h: {omd, decay_max, updates, warmup}) as a 4-word int32 tensor on `device`, omd = 1 - d_updates."""
+    omd = np.float32(1) - ema_decay(updates, decay_max, warmup)
+    words = np.zeros(4, dtype=np.int32)
+    words[:2] = np.array([omd, decay_max], dtype=np.float32).view(np.int32)
+    words[2:] = np.array([updates, 1 if warmup else 0], dtype=np.uint32).view(np.int32)
+    return torch.from_numpy(words).to(device)
+
+
+def ema_record_read(record):
+    """The record's fields on the host (one synchronising read): {'omd', 'decay_max', 'updates', 'warmup'}."""
+    words = record.detach().cpu().numpy()
+    f = words[:2].view(np.float32)
+    u = words[2:].view(np.uint32)
+    return {'omd': float(f[0]), 'decay_max': float(f[1]), 'updates': int(u[0]), 'warmup': bool(u[1])}
+
+
+def ema_update_(ema, p, record):
+    """ema <- ema + omd (p - ema) on flat fp32 arenas, omd read from the record when the kernel runs."""
+    _need_gpu(ema, p, record)
+    if ema.numel() != p.numel():
+        raise DsrlHipError(f'ema_update: {ema.numel()} and {p.numel()} elements')
+    call('dsrl_ema_update', ema.data_ptr(), p.data_ptr(), p.numel(), record.data_ptr(), _stream())
+
+
+def ema_advance_(record):
+    """Once per step behind its last EMA launch: updates += 1 and the next omd, on the device."""
+    _need_gpu(record)
+    call('dsrl_ema_advance', record.data_ptr(), _stream())
+
+
+def arena_swap_(a, b):
+    """Exchanges the contents of two flat fp32 arenas in place (bit patterns)."""
+    _need_gpu(a, b)
+    if a.numel() != b.numel() or a.dtype != torch.float32 or b.dtype != torch.float32 or not (a.is_contiguous() and b.is_contiguous()):
+        raise DsrlHipError('arena_swap: two contiguous fp32 arenas of one size expected')
+    call('dsrl_arena_swap', a.data_ptr(), b.data_ptr(), a.numel(), _stream())
+
+
 class DeviceRng:
     """Device-resident twin of the host dropout key (begin_forward): three 64-bit words {key, step, base}.  While bound, every
     dropout-bearing kernel of the device reads `key` when it runs and advance() enqueues the per-step derivation, so that a step

@@ -3,11 +3,18 @@ import numpy as np
 import torch as t
 
 
-def load_checkpoint_or_weights(filename, map_location='cpu'):
-    """A `.weights` or `.checkpoint` file written by train_or_resume: a dict with at least 'model_state_dict'."""
+def load_checkpoint_or_weights(filename, map_location='cpu', ema=False):
+    """A `.weights` or `.checkpoint` file written by train_or_resume: a dict with at least 'model_state_dict'.  `ema=True`: the averaged weights of
+    a checkpoint written with dataset['ema'] - its 'ema_state_dict' without the two bookkeeping keys - are returned as 'model_state_dict'; a file
+    without one raises.  (A final weights file of such a run already holds the averaged weights as 'model_state_dict'.)"""
     d = t.load(filename, map_location=map_location)
     if not isinstance(d, dict) or 'model_state_dict' not in d:
         raise RuntimeError(f"'{filename}' holds no 'model_state_dict': not a .weights / .checkpoint file of this project")
+    if ema:
+        if not isinstance(d.get('ema_state_dict'), dict):
+            raise RuntimeError(f"'{filename}' holds no 'ema_state_dict': it was not written by a training run with dataset['ema']")
+        d = dict(d)
+        d['model_state_dict'] = {k: v for k, v in d['ema_state_dict'].items() if k not in ('ema_updates', 'ema_decay')}
     return d
 
 

@@ -652,6 +652,25 @@ int dsrl_sgd_step_dev(float* p, const float* g, float* buf, int64_t n, const flo
  * rows with a record the launch also leaves max |p| of the UPDATED values there (same bit patterns as dsrl_conv2d_filters_amax_batched; the records must be zero
  * when the launch starts) - the conv filters' operand magnitudes for the next step come out of the optimiser pass instead of a sweep of their own */
 int dsrl_sgd_step_dev_segments(float* p, const float* g, float* buf, const int64_t* table, int64_t nseg, const float* hyper /*device, 4 floats*/, dsrl_stream_t stream);
+/* Exponential moving average of the weights, e <- e + (1 - d_t) (p_new - e) with p_new the parameter the SGD update has just computed.
+ * ema_record: 16 bytes of device memory, 16-byte aligned: {float omd = 1 - d_t of the update about to run, float decay_max, uint32 updates,
+ * uint32 warmup}.  The element kernels only read omd; dsrl_ema_advance, once per step behind the last of them, does updates += 1 and writes the next
+ * omd: d_t = warmup ? min(decay_max, (1 + t) / (10 + t)) : decay_max with t = updates, in fp32 with a correctly rounded division.  No host write per
+ * step: a captured step advances the schedule on every replay.
+ * The three dsrl_sgd_step*_ema take the arguments of their twins plus the average's arena `ema` (laid out as p, 16-byte aligned) and the record;
+ * p and buf come out bit-identical to the twin's, the amax records of the segment form are published from p_new as before, and ema is bit-identical
+ * to the twin followed by dsrl_ema_update(ema, p, n, ...). */
+int dsrl_sgd_step_ema(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float weight_decay, float grad_scale,
+                      float* ema, const void* ema_record, dsrl_stream_t stream);
+int dsrl_sgd_step_dev_ema(float* p, const float* g, float* buf, int64_t n, const float* hyper /*device, 4 floats*/, float* ema, const void* ema_record,
+                          dsrl_stream_t stream);
+int dsrl_sgd_step_dev_segments_ema(float* p, const float* g, float* buf, const int64_t* table, int64_t nseg, const float* hyper /*device, 4 floats*/,
+                                   float* ema, const void* ema_record, dsrl_stream_t stream);
+/* the unfused update: ema[i] <- ema[i] + omd (p[i] - ema[i]) for i < n (the BatchNorm buffer arena after the step); both 16-byte aligned */
+int dsrl_ema_update(float* ema, const float* p, int64_t n, const void* ema_record, dsrl_stream_t stream);
+int dsrl_ema_advance(void* ema_record, dsrl_stream_t stream);
+/* exchanges n floats of two disjoint 16-byte aligned arenas in place, as bit patterns (NaN payloads, infinities, -0 and denormals survive) */
+int dsrl_arena_swap(float* a, float* b, int64_t n, dsrl_stream_t stream);
 /* flag[0] |= 1 if any element is NaN (the reference's per-output NaN asserts folded into one readback) */
 int dsrl_nan_check(const float* x, int64_t n, int* flag, dsrl_stream_t stream);
 
