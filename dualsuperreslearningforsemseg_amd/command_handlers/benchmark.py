@@ -12,6 +12,11 @@ probabilities averaged); benchmark.txt then says so.
 the value is validated before any device work, benchmark.txt names the scales and the view sizes, and with `compiled_model` the command raises
 before it loads anything (graph replay of the multi-scale path is not built).
 `ema=True` in other_args: `weights` names a checkpoint written with dataset['ema'] and its averaged weights ('ema_state_dict') are evaluated.
+`sisr=True` in other_args: the super-resolution branch is measured too.  The model is built at stage 2 (a file without 'SISR_decoder' entries - a
+stage-1 or pruned file - raises RuntimeError), every batch runs the backbone once and `DSRL.predict_head` and `DSRL.super_resolve_head` on its
+features, and metrices.SRQuality compares the super-resolved image with the loader's original: the result gains 'PSNR' (dB, mean over the images)
+and 'SSIM', benchmark.txt two lines; the records travel in the same single read.  Not with `flip`, `scales` or `compiled_model` (ValueError before
+any device work): the SISR branch has no ensemble, and compiled files are stage-1.
 Beside the reference's per-batch figures the command accumulates ONE confusion matrix over the split on the device (the kernel that writes the
 class map fills it; it comes back in the same single read) and reports the dataset-level figures from it - intersections and unions summed over the
 split, then IoU per class, then the mean over the classes, as Cityscapes results are published - with a per-class table in benchmark.txt and the
@@ -25,8 +30,8 @@ import torch as t
 
 from .. import settings
 from .._lib import DsrlHipError
-from ..functional import multiscale_scales_value, multiscale_sizes
-from ..metrices import Accuracy, AverageMeter, ConfusionMatrix, mIoU
+from ..functional import multiscale_scales_value, multiscale_sizes, nan_check_
+from ..metrices import Accuracy, AverageMeter, ConfusionMatrix, SRQuality, mIoU
 from ..models import DSRL
 from ..utils import load_checkpoint_or_weights
 from .train_or_resume import isCUDAdevice
@@ -34,14 +39,18 @@ from .train_or_resume import isCUDAdevice
 NOT_GPU = "this build runs on the MI355X only: use device='gpu' (the reference's --device cpu path is its own)"
 
 
-def load_eval_model(weights, dataset_settings, device_obj, ema=False):
+def load_eval_model(weights, dataset_settings, device_obj, ema=False, sisr=False):
     """Stage-1 DSRL in eval mode with the matching entries of the file's state dict (a stage-2/3 file carries more: strict=False, as the reference).
-    `ema`: the averaged weights of a checkpoint written with dataset['ema'] (utils.load_checkpoint_or_weights)."""
+    `ema`: the averaged weights of a checkpoint written with dataset['ema'] (utils.load_checkpoint_or_weights).
+    `sisr`: a stage-2 model, SISR decoder included; a file that does not carry the decoder raises RuntimeError naming the first missing key."""
     d = load_checkpoint_or_weights(weights, map_location='cpu', ema=ema)
     if d.get('format') is not None:
         raise RuntimeError(f"'{weights}' is a compiled model file (written by the compile_model command): pass compiled_model=True to read it")
-    model = DSRL(stage=1, dataset_settings=dataset_settings).eval()
-    model.load_state_dict(d['model_state_dict'], strict=False)
+    model = DSRL(stage=2 if sisr else 1, dataset_settings=dataset_settings).eval()
+    loaded = model.load_state_dict(d['model_state_dict'], strict=False)
+    missing = [k for k in loaded.missing_keys if k.startswith('SISR_decoder.')]
+    if sisr and missing:
+        raise RuntimeError(f"'{weights}' carries no '{missing[0]}': sisr=True needs a stage-2 or stage-3 weights file that was not pruned")
     return model.to(device_obj).to(memory_format=t.channels_last)
 
 
@@ -58,6 +67,11 @@ def split_loader(dataset, split, batch_size, device_obj, input_size):
 
 def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
     scales = multiscale_scales_value(other_args.get('scales'))          # ValueError on a bad value, before any device work
+    sisr = bool(other_args.get('sisr'))
+    if sisr:
+        clash = [k for k, on in (('flip', other_args.get('flip')), ('scales', scales is not None), ('compiled_model', other_args.get('compiled_model'))) if on]
+        if clash:
+            raise ValueError(f"benchmark: sisr=True does not combine with {', '.join(clash)} (the SISR branch has no ensemble; compiled files are stage-1)")
     if not isCUDAdevice(device):
         raise RuntimeError(NOT_GPU)
     if scales is not None and other_args.get('compiled_model'):
@@ -73,7 +87,7 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
         from ..inference import load_compiled_model
         model, predictor = load_compiled_model(weights, device_obj)          # frozen operands + hipGraph replay: the same class maps, counters and losses
     else:
-        model = load_eval_model(weights, ds, device_obj, ema=other_args.get('ema', False))
+        model = load_eval_model(weights, ds, device_obj, ema=other_args.get('ema', False), sisr=sisr)
     predict = model.predict if predictor is None else predictor
     flip = bool(other_args.get('flip'))
     if scales is not None:
@@ -84,16 +98,27 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
     ces, tables = [], []
     nc = ds.NUM_CLASSES
     confusion = t.zeros(nc * nc, dtype=t.int64, device=device_obj)
+    quality = SRQuality(ds.MEAN, ds.STD) if sisr else None
     try:
-        for (input_image, _), (target, _) in loader:
-            _, counts, ce = predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag, flip=flip, confusion=confusion)
+        for (input_image, input_org), (target, _) in loader:
+            if sisr:
+                with t.no_grad():       # DSRL.predict with the trunk's features kept for the other branch
+                    nan_check_(nan_flag, input_image)
+                    features = model.feature_extractor['backbone'](input_image)
+                    _, counts, ce = model.predict_head(*features, target, ds.IGNORE_CLASS_LABEL, nan_flag, False, confusion)
+                    quality.update(model.super_resolve_head(*features), input_org)
+            else:
+                _, counts, ce = predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag, flip=flip, confusion=confusion)
             ces.append(ce)
             tables.append(counts)
         if not ces:
             raise RuntimeError(f"the '{split}' split yielded no batch")
         # the one device -> host read: losses, NaN flag, counters and the confusion matrix in a single float64 tensor (counters < 2^53: exact)
         nb = len(ces)
-        host = t.cat([t.stack(ces).double(), nan_flag.double().reshape(1), t.stack(tables).double().reshape(-1), confusion.double()]).cpu()
+        parts = [t.stack(ces).double(), nan_flag.double().reshape(1), t.stack(tables).double().reshape(-1), confusion.double()]
+        if sisr:
+            parts += [b[0].reshape(-1) for b in quality.batches]
+        host = t.cat(parts).cpu()
     finally:
         if predictor is not None:
             predictor.release()             # drops the graphs and restores the conv arithmetic the file selected
@@ -109,7 +134,8 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
         accuracy_mean.update_from_counts(host_tables[i])
     result = {'CE': CE_avg_loss(), 'mIoU': miou(), 'accuracy': accuracy_mean()}
     whole = ConfusionMatrix(nc, ds.IGNORE_CLASS_LABEL)
-    whole.merge(host[nb + 1 + nb * (3 * nc + 2):].to(t.int64))
+    at = nb + 1 + nb * (3 * nc + 2)
+    whole.merge(host[at:at + nc * nc].to(t.int64))
     fig = whole.result()
     result.update({'mIoU_dataset': fig['mIoU'], 'IoU_per_class': [float(v) for v in fig['IoU']], 'pixel_accuracy': fig['pixel_accuracy'],
                    'mean_class_accuracy': fig['mean_class_accuracy'], 'fwIoU': fig['fwIoU'], 'confusion_matrix': fig['matrix'].tolist()})
@@ -124,6 +150,15 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
                   result['pixel_accuracy'], result['mean_class_accuracy'], result['fwIoU']),
               '', '{:<{w}s}  {:>7s}  {:>8s}'.format('class', 'IoU %', 'recall %', w=width)]
     lines += ['{:<{w}s}  {:>7.2f}  {:>8.2f}'.format(n, i, r, w=width) for n, i, r in zip(names, fig['IoU'], fig['class_accuracy'])]
+    if sisr:
+        at, on_host = at + nc * nc, SRQuality()
+        for records, C, H, W in quality.batches:
+            on_host.update_from_records(host[at:at + records.numel()].reshape(-1, 2), C, H, W)
+            at += records.numel()
+        sr = on_host.result()
+        result.update({'PSNR': sr['PSNR'], 'SSIM': sr['SSIM']})
+        lines += ['Super-resolved image against the original, mean over {:d} images, PSNR dB: {:.2f}'.format(sr['images'], sr['PSNR']),
+                  'Super-resolved image against the original, mean over {:d} images, SSIM: {:.4f}'.format(sr['images'], sr['SSIM'])]
     print('-------- RESULTS --------')
     for ln in lines:
         print(ln)

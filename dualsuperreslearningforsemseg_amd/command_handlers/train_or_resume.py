@@ -601,9 +601,14 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
                             os.remove(stale)
                 if val_loader is not None and epoch % val_interval == 0:                                            # :294
                     details = {}
+                    if stage > 1:           # PSNR and SSIM of the SISR output against the 2x original; reported, nothing is decided from them
+                        from ..metrices import SRQuality
+                        details['sr_quality'] = SRQuality(ds.MEAN, ds.STD)
                     with flat.ema_weights() if ema is not None else contextlib.nullcontext():      # the averaged model is the one that is measured
                         rec['val'] = _do_train_val(False, epoch, model, step, val_loader, lr, momentum, weights_decay, False, True, details)
                     rec['val_mIoU_dataset'], rec['val_IoU_per_class'] = rec['val'][6], details['IoU_per_class']
+                    if 'sr_quality' in details:
+                        rec['val_PSNR'], rec['val_SSIM'] = details['PSNR'], details['SSIM']
                     CE_val_avg_loss, MSE_val_avg_loss, FA_val_avg_loss, Avg_val_loss, val_mIoU = rec['val'][:5]
                     if val_mIoU > best_validation_dict['best_miou_percent']:                                        # :318-337
                         best_validation_dict = {'epoch': epoch, 'best_miou_percent': val_mIoU, 'loss': Avg_val_loss}
@@ -645,7 +650,8 @@ def _do_train_val(do_train, epoch, model, step, data_loader, lr, momentum, weigh
     """train_or_resume.py:373-533 without the progress-bar / TensorBoard plumbing. Returns the running means
     (CE, MSE, FA, Total, mIoU %, accuracy %) and, as a last element, the dataset-level mIoU % (metrices.ConfusionMatrix over the whole loader);
     the last three only for validation.  Everything decided from a validation - best checkpoint, early stopping - uses the reference's per-batch
-    mIoU.  `details` (a dict, optional) receives 'IoU_per_class' of the dataset-level figure."""
+    mIoU.  `details` (a dict, optional) receives 'IoU_per_class' of the dataset-level figure; a validation that finds a metrices.SRQuality under
+    details['sr_quality'] feeds it every batch's SISR output and original (two launches per batch, one read at the end) and leaves 'PSNR' and 'SSIM'."""
     model.train(mode=do_train)
     if do_train and freeze_batch_norm:
         for m in model.modules():
@@ -657,6 +663,7 @@ def _do_train_val(do_train, epoch, model, step, data_loader, lr, momentum, weigh
     miou, mean_accuracy = mIoU(num_classes=nc, ignore_index=step.ignore), Accuracy(num_classes=nc, ignore_index=step.ignore)
     whole = ConfusionMatrix(num_classes=nc, ignore_index=step.ignore)
     whole_fits = nc <= ConfusionMatrix.max_classes_from_logits()        # beyond it the one-pass kernel has no room for the matrix: the figure is NaN
+    srq = details.get('sr_quality') if (details is not None and not do_train and is_master_rank) else None
     sizes = []
 
     def drain(keep):
@@ -673,10 +680,15 @@ def _do_train_val(do_train, epoch, model, step, data_loader, lr, momentum, weigh
             mean_accuracy.update_from_logits(outs[0], target)
             if whole_fits:
                 whole.update_from_logits(outs[0], target)
+            if srq is not None:
+                srq.update(outs[1], input_org)
         drain(1)              # the losses of iteration k are read while iteration k+1 is already queued
     drain(0)
     fig = whole.result() if not do_train else None
     if details is not None and fig is not None:
         details['IoU_per_class'] = [float(v) for v in fig['IoU']]
+    if srq is not None:
+        quality = srq.result()
+        details['PSNR'], details['SSIM'] = quality['PSNR'], quality['SSIM']
     return [m() for m in meters] + [miou() if not do_train else 0.0, mean_accuracy() if not do_train else 0.0, fig['mIoU'] if fig is not None else 0.0]
 

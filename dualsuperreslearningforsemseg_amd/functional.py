@@ -2136,6 +2136,66 @@ def nan_check_(flag, *tensors):
         call('dsrl_nan_check', td.data_ptr(), td.numel(), flag.data_ptr(), st)
 
 
+# ------------------------------------------------------------------------------------------------ quality of the super-resolved image
+SR_QUALITY_WINDOW = 11          # the SSIM window of dsrl_sr_quality: 11 x 11 Gaussian, sigma 1.5
+
+
+def _sr_quality_args(pred, ref, mean, std):
+    """The argument checks of sr_quality, all of them host-side: -> (C, mean, std) as ctypes float arrays.  ValueError on anything the kernel cannot take."""
+    if pred.dim() != 4 or ref.dim() != 4:
+        raise ValueError(f'sr_quality: 4-D (N,C,H,W) tensors expected, got shapes {tuple(pred.shape)} and {tuple(ref.shape)}')
+    if tuple(pred.shape) != tuple(ref.shape):
+        raise ValueError(f'sr_quality: pred {tuple(pred.shape)} and ref {tuple(ref.shape)} differ in shape')
+    N, Cc, H, W = pred.shape
+    if N < 1 or Cc < 1 or Cc > 4:
+        raise ValueError(f'sr_quality: at least one image of 1 to 4 channels expected, got shape {tuple(pred.shape)}')
+    if H < SR_QUALITY_WINDOW or W < SR_QUALITY_WINDOW:
+        raise ValueError(f'sr_quality: images of {H} x {W} are smaller than the {SR_QUALITY_WINDOW}x{SR_QUALITY_WINDOW} window of the SSIM')
+    mean = [0.0] * Cc if mean is None else [float(v) for v in mean]
+    std = [1.0] * Cc if std is None else [float(v) for v in std]
+    if len(mean) != Cc or len(std) != Cc:
+        raise ValueError(f'sr_quality: mean and std of {Cc} values expected, got {len(mean)} and {len(std)}')
+    mean32, std32 = (ctypes.c_float * Cc)(*mean), (ctypes.c_float * Cc)(*std)
+    if not all(math.isfinite(v) for v in mean32):
+        raise ValueError(f'sr_quality: mean {mean} is not finite')
+    if not all(math.isfinite(v) and v != 0.0 for v in std32):
+        raise ValueError(f'sr_quality: std {std} must be finite and non-zero (as fp32)')
+    return Cc, mean32, std32
+
+
+def sr_quality(pred, ref, mean=None, std=None, ssim_map=False):
+    """Squared error and SSIM sum of `pred` against `ref`, per image (dsrl_sr_quality, include/dsrl_hip.h): both (N,C,H,W) fp32, C <= 4, H and W >= 11;
+    every value is de-normalised as x * std[c] + mean[c] and clamped to [0, 1] first (`mean`, `std`: C numbers each; None: the tensors are in [0, 1]
+    already).  -> records (N, 2) float64 on the device, row n = {sse, ssim_sum} of image n (sr_quality_figures turns them into PSNR and SSIM); with
+    `ssim_map` also the fp32 map (N, C, H-10, W-10).  Two launches, nothing read back; bit-identical run to run and for an image alone or in a batch.
+    A bad argument is a ValueError before any device work."""
+    Cc, mean32, std32 = _sr_quality_args(pred, ref, mean, std)
+    with torch.no_grad():
+        pred, ldp = pm(pred)
+        ref, ldr = pm(ref)
+        if ref.device != pred.device:
+            raise DsrlHipError(f'sr_quality: pred is on {pred.device}, ref on {ref.device}')
+        N, _, H, W = pred.shape
+        records = torch.empty((N, 2), dtype=torch.float64, device=pred.device)
+        smap = torch.empty((N, Cc, H - SR_QUALITY_WINDOW + 1, W - SR_QUALITY_WINDOW + 1), dtype=torch.float32, device=pred.device) if ssim_map else None
+        nbytes = cquery('dsrl_sr_quality_workspace_bytes', N, Cc, H, W)
+        ws = _ws(nbytes, pred)
+        call('dsrl_sr_quality', pred.data_ptr(), ldp, ref.data_ptr(), ldr, N, Cc, H, W, mean32, std32, records.data_ptr(),
+             None if smap is None else smap.data_ptr(), ws.data_ptr(), nbytes, _stream())
+    return (records, smap) if ssim_map else records
+
+
+def sr_quality_figures(records, C, H, W):
+    """Host side: records (N, 2) {sse, ssim_sum} of (C, H, W) images (a tensor anywhere, or an array) -> (psnr, ssim), float64 arrays of N:
+    psnr = 10 log10(C H W / sse) in dB at data range 1, +inf where sse == 0; ssim = ssim_sum / (C (H-10) (W-10)).  NaN records stay NaN."""
+    r = records.detach().cpu().numpy() if isinstance(records, torch.Tensor) else np.asarray(records)
+    r = r.astype(np.float64).reshape(-1, 2)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        psnr = 10.0 * np.log10(float(C * H * W) / r[:, 0])
+    ssim = r[:, 1] / float(C * (H - SR_QUALITY_WINDOW + 1) * (W - SR_QUALITY_WINDOW + 1))
+    return psnr, ssim
+
+
 # ------------------------------------------------------------------------------------------------ inference
 def _bad_label_bit(nan_flag, target, ignore_index, num_classes):
     """bit 1 of `nan_flag`: a label outside [0, num_classes) that is not the ignore label"""

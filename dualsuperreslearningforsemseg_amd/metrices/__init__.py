@@ -190,6 +190,47 @@ class ConfusionMatrix:
         return figures(m)
 
 
+class SRQuality:
+    """PSNR (dB, data range 1) and SSIM of super-resolved images against their originals over a whole split (functional.sr_quality): `mean` / `std`
+    are the normalisation the tensors carry (dataset settings' MEAN / STD; None: values in [0, 1] already).  Every update leaves one (N, 2) float64
+    record tensor on the device; result() does the one read."""
+
+    def __init__(self, mean=None, std=None):
+        self.mean, self.std = mean, std
+        self.reset()
+
+    def reset(self):
+        self.batches = []           # [(records (N, 2), C, H, W)]
+
+    def update(self, pred, ref):
+        """pred, ref (N,C,H,W) device tensors -> dsrl_sr_quality; nothing is read back"""
+        records = HF.sr_quality(pred, ref, self.mean, self.std)
+        self.batches.append((records,) + tuple(int(v) for v in pred.shape[1:]))
+
+    def update_from_records(self, records, C, H, W):
+        """records (N, 2) {sse, ssim_sum} some call of functional.sr_quality already produced for (C, H, W) images; a host tensor is taken as it is"""
+        if records.dim() != 2 or records.shape[1] != 2:
+            raise ValueError(f'records of shape (N, 2) expected, got {tuple(records.shape)}')
+        self.batches.append((records.to(torch.float64), int(C), int(H), int(W)))
+
+    def result(self):
+        """The one device read -> {'PSNR', 'SSIM', 'images', 'PSNR_per_image', 'SSIM_per_image'}: PSNR the mean over the images of their dB figures
+        (the convention of super-resolution papers, not the dB of the mean error), SSIM the mean over the images.  Nothing fed: NaN figures and 0
+        images.  An image identical to its original has PSNR +inf, and so has the mean."""
+        if not self.batches:
+            nan = float('nan')
+            return {'PSNR': nan, 'SSIM': nan, 'images': 0, 'PSNR_per_image': np.zeros(0), 'SSIM_per_image': np.zeros(0)}
+        devices = {b[0].device for b in self.batches}
+        host = (torch.cat([b[0] for b in self.batches]).cpu() if len(devices) == 1 else torch.cat([b[0].cpu() for b in self.batches])).numpy()
+        psnr, ssim, at = [], [], 0
+        for rec, C, H, W in self.batches:
+            p, s = HF.sr_quality_figures(host[at:at + rec.shape[0]], C, H, W)
+            psnr.append(p); ssim.append(s)
+            at += rec.shape[0]
+        psnr, ssim = np.concatenate(psnr), np.concatenate(ssim)
+        return {'PSNR': float(psnr.mean()), 'SSIM': float(ssim.mean()), 'images': int(psnr.size), 'PSNR_per_image': psnr, 'SSIM_per_image': ssim}
+
+
 def _nanmean(v):
     ok = ~np.isnan(v)
     return float(v[ok].mean()) if ok.any() else float('nan')

@@ -200,6 +200,33 @@ class DSRL(BaseModel):
                 raise HF.DsrlHipError('DSRL.predict: ' + ' and '.join(m for b, m in ((1, 'NaN in the input or the logits'), (2, 'labels outside the classes')) if bits & b))
         return out
 
+    def super_resolve_head(self, backbone_features: t.Tensor, lowlevel_features: t.Tensor):
+        """Inference counterpart of forward_head for the other branch: ASPP, upsample, shortcut, concatenation and `SISR_decoder` in eval mode ->
+        the super-resolved image (N,3,2H,2W), normalised as the input is and bit-identical to `forward(x)[1]`.  Neither the SSSR decoder nor the
+        feature transformers run.  Raises in train mode and at stage 1, which has no SISR decoder."""
+        if self.training:
+            raise HF.DsrlHipError('DSRL.super_resolve* is inference: call model.eval() first')
+        if self.stage < 2:
+            raise HF.DsrlHipError('DSRL.super_resolve*: a stage-1 model has no SISR decoder')
+        with t.no_grad():
+            fe = self.feature_extractor
+            aspp_features = fe['aspp'](backbone_features)
+            h, w = aspp_features.shape[-2:]
+            aspp_features = HF.upsample_bilinear_ac(aspp_features, (4 * h, 4 * w))            # DSRL.py:163
+            cat_features = HF.cat_channels([aspp_features, fe['shortcut_conv'](lowlevel_features)])    # DSRL.py:164-165
+            return self.SISR_decoder(cat_features)                                             # DSRL.py:177
+
+    def super_resolve(self, x: t.Tensor):
+        """The super-resolved image of a batch, see super_resolve_head.  Runs under no_grad."""
+        if self.training:
+            raise HF.DsrlHipError('DSRL.super_resolve* is inference: call model.eval() first')
+        if self.stage < 2:
+            raise HF.DsrlHipError('DSRL.super_resolve*: a stage-1 model has no SISR decoder')
+        with t.no_grad():
+            HF.begin_forward(False)
+            backbone_features, lowlevel_features = self.feature_extractor['backbone'](x)      # DSRL.py:161
+            return self.super_resolve_head(backbone_features, lowlevel_features)
+
     def _eval_sssr_logits(self, x: t.Tensor):
         """The SSSR logits (N,classes,2H,2W) of the eval-mode forward path on `x`: forward() without the SISR decoder and the feature transformers."""
         HF.begin_forward(False)

@@ -787,6 +787,29 @@ int dsrl_fingerprint_segments(const int64_t* table, int64_t nseg, uint64_t* out 
 int dsrl_class_map_visualize(const uint8_t* rgb, const uint8_t* classes, const uint8_t* mask /*nullable*/, const uint8_t* palette /*device, 256 x 3*/,
                              uint8_t* out, int N, int H, int W, int ignore_index, double blend_factor, dsrl_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * quality of the super-resolved image: squared error and SSIM of pred against ref, per image (csrc/sr_quality.hip)
+ *   pred, ref: fp32 (N,H,W,C) pixel-major with pixel strides ld_pred, ld_ref >= C (4-byte aligned; 16-byte aligned rows are loaded as float4),
+ *   1 <= C <= 4, H >= 11 and W >= 11 (DSRL_E_BADARG otherwise).  mean, std: C HOST floats (finite, std != 0), passed on as kernel arguments.
+ *   Every value is de-normalised as v = x * std[c] + mean[c] (a product, then a sum: two roundings) and clamped to [0, 1] by comparisons that a NaN
+ *   fails, so a NaN stays one; mean = 0, std = 1 is "already in [0, 1]".
+ *   sse      = sum over the image's C*H*W values of (vp - vr)^2; difference and square fp32, the sum double.
+ *   SSIM     = the single-scale index of Wang et al. at data range 1: window g[k] = exp(-(k-5)^2 / 4.5), k = 0..10, normalised in double and rounded
+ *              to fp32; applied separably (rows, then columns, taps ascending, fp32 fused multiply-adds) to x, y, x*x, x*y, y*y (single fp32
+ *              products) over the valid region (H-10) x (W-10) of each channel; per pixel ((2 mx my + C1)(2 sxy + C2)) / ((mx^2 + my^2 + C1)
+ *              (sxx + syy + C2)) with sab = E[ab] - ma mb, C1 = 1e-4f, C2 = 9e-4f, a correctly rounded division: bit-equal pred and ref give exactly 1.
+ *   ssim_sum = sum of that map over channels and valid pixels, in double.
+ *   records (N x {sse, ssim_sum}, float64, 8-byte aligned) is WRITTEN.  ssim_map (nullable; fp32, planar (N, C, H-10, W-10)) receives the map.
+ *   Two launches, no allocation, no host synchronisation, no atomics: every block writes its two double partials to its own slot of ws and the second
+ *   launch adds an image's slots in a fixed order.  The tiling of an image does not depend on N or on the image's place in the batch: results are
+ *   bit-identical run to run, and an image's record is the same alone or inside a batch.  ws 8-byte aligned, ws_bytes >= the query
+ *   (DSRL_E_WORKSPACE otherwise); the query depends on the shape only and holds for every launch of that shape (0 for a shape the launch refuses).
+ *   32-bit element indices: N * H * W * max(ld_pred, ld_ref) < 2^31 and N <= 65535, DSRL_E_UNSUPPORTED beyond.
+ * ---------------------------------------------------------------------------------------------- */
+size_t dsrl_sr_quality_workspace_bytes(int N, int C, int H, int W);
+int dsrl_sr_quality(const float* pred, int ld_pred, const float* ref, int ld_ref, int N, int C, int H, int W, const float* mean /*host, C*/,
+                    const float* std /*host, C*/, double* records /*N x 2*/, float* ssim_map /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
