@@ -198,6 +198,10 @@ PROTOTYPES = {
     'dsrl_nan_check': (i32, [fp, i64, fp, stream_t]),
     'dsrl_sr_quality_workspace_bytes': (sz, [i32] * 4),
     'dsrl_sr_quality': (i32, [fp, i32, fp, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), fp, fp, fp, sz, stream_t]),
+    'dsrl_boundary_counts_max_classes': (i32, []),
+    'dsrl_boundary_counts_max_distance': (i32, []),
+    'dsrl_boundary_counts_workspace_bytes': (sz, [i32] * 4),
+    'dsrl_boundary_counts': (i32, [fp, fp, i32, i32, i32, i32, i32, i32, fp, fp, fp, fp, sz, stream_t]),
     'dsrl_rng_bind_device_key': (i32, [fp]),
     'dsrl_rng_advance_key': (i32, [fp, stream_t]),
     'dsrl_prof_enable': (i32, [i32]),

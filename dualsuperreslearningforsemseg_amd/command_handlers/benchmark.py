@@ -17,6 +17,10 @@ stage-1 or pruned file - raises RuntimeError), every batch runs the backbone onc
 features, and metrices.SRQuality compares the super-resolved image with the loader's original: the result gains 'PSNR' (dB, mean over the images)
 and 'SSIM', benchmark.txt two lines; the records travel in the same single read.  Not with `flip`, `scales` or `compiled_model` (ValueError before
 any device work): the SISR branch has no ensemble, and compiled files are stage-1.
+`boundary=True` (ratio 0.02 of the image diagonal) or a positive ratio in other_args: every batch's class map - which every predict variant returns
+anyway - also goes to `functional.boundary_counts_`, and the Boundary IoU counters (metrices.BoundaryIoU) ride in the same single read: the result
+gains 'mBIoU_dataset' and 'BIoU_per_class', the per-class table of benchmark.txt a column and the file one summary line.  Combines with `flip`,
+`scales`, `compiled_model`, `ema` and `sisr`; anything but True, False, None or a finite number > 0 is a ValueError before any device work.
 Beside the reference's per-batch figures the command accumulates ONE confusion matrix over the split on the device (the kernel that writes the
 class map fills it; it comes back in the same single read) and reports the dataset-level figures from it - intersections and unions summed over the
 split, then IoU per class, then the mean over the classes, as Cityscapes results are published - with a per-class table in benchmark.txt and the
@@ -30,8 +34,8 @@ import torch as t
 
 from .. import settings
 from .._lib import DsrlHipError
-from ..functional import multiscale_scales_value, multiscale_sizes, nan_check_
-from ..metrices import Accuracy, AverageMeter, ConfusionMatrix, SRQuality, mIoU
+from ..functional import boundary_counts_, boundary_distance, multiscale_scales_value, multiscale_sizes, nan_check_
+from ..metrices import Accuracy, AverageMeter, BoundaryIoU, ConfusionMatrix, SRQuality, mIoU
 from ..models import DSRL
 from ..utils import load_checkpoint_or_weights
 from .train_or_resume import isCUDAdevice
@@ -65,8 +69,22 @@ def split_loader(dataset, split, batch_size, device_obj, input_size):
     return factory(split, batch_size, device_obj, 0, 1)
 
 
+def boundary_ratio_value(value):
+    """other_args['boundary'] -> the band's share of the image diagonal, or None when the key is absent or off: True is the paper's 0.02, a finite
+    number > 0 is itself; anything else is a ValueError"""
+    if value is None or value is False:
+        return None
+    if value is True:
+        return 0.02
+    if isinstance(value, (int, float, np.integer, np.floating)):
+        boundary_distance(1, 1, value)          # ValueError unless finite and > 0
+        return float(value)
+    raise ValueError(f'benchmark: boundary = {value!r} is neither True nor a positive ratio of the image diagonal')
+
+
 def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
     scales = multiscale_scales_value(other_args.get('scales'))          # ValueError on a bad value, before any device work
+    boundary = boundary_ratio_value(other_args.get('boundary'))
     sisr = bool(other_args.get('sisr'))
     if sisr:
         clash = [k for k, on in (('flip', other_args.get('flip')), ('scales', scales is not None), ('compiled_model', other_args.get('compiled_model'))) if on]
@@ -99,16 +117,21 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
     nc = ds.NUM_CLASSES
     confusion = t.zeros(nc * nc, dtype=t.int64, device=device_obj)
     quality = SRQuality(ds.MEAN, ds.STD) if sisr else None
+    band_counts = t.zeros(3 * nc, dtype=t.int64, device=device_obj) if boundary is not None else None
+    band_distances = []
     try:
         for (input_image, input_org), (target, _) in loader:
             if sisr:
                 with t.no_grad():       # DSRL.predict with the trunk's features kept for the other branch
                     nan_check_(nan_flag, input_image)
                     features = model.feature_extractor['backbone'](input_image)
-                    _, counts, ce = model.predict_head(*features, target, ds.IGNORE_CLASS_LABEL, nan_flag, False, confusion)
+                    pred, counts, ce = model.predict_head(*features, target, ds.IGNORE_CLASS_LABEL, nan_flag, False, confusion)
                     quality.update(model.super_resolve_head(*features), input_org)
             else:
-                _, counts, ce = predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag, flip=flip, confusion=confusion)
+                pred, counts, ce = predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag, flip=flip, confusion=confusion)
+            if boundary is not None:
+                boundary_counts_(band_counts, pred, target, nc, ds.IGNORE_CLASS_LABEL, ratio=boundary, nan_flag=nan_flag)
+                band_distances.append(boundary_distance(pred.shape[-2], pred.shape[-1], boundary))
             ces.append(ce)
             tables.append(counts)
         if not ces:
@@ -116,6 +139,8 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
         # the one device -> host read: losses, NaN flag, counters and the confusion matrix in a single float64 tensor (counters < 2^53: exact)
         nb = len(ces)
         parts = [t.stack(ces).double(), nan_flag.double().reshape(1), t.stack(tables).double().reshape(-1), confusion.double()]
+        if boundary is not None:
+            parts.append(band_counts.double())
         if sisr:
             parts += [b[0].reshape(-1) for b in quality.batches]
         host = t.cat(parts).cpu()
@@ -149,9 +174,22 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
               'Dataset-level pixel accuracy %: {:.2f}, mean class accuracy %: {:.2f}, frequency-weighted IoU %: {:.2f}'.format(
                   result['pixel_accuracy'], result['mean_class_accuracy'], result['fwIoU']),
               '', '{:<{w}s}  {:>7s}  {:>8s}'.format('class', 'IoU %', 'recall %', w=width)]
-    lines += ['{:<{w}s}  {:>7.2f}  {:>8.2f}'.format(n, i, r, w=width) for n, i, r in zip(names, fig['IoU'], fig['class_accuracy'])]
+    at += nc * nc
+    if boundary is None:
+        lines += ['{:<{w}s}  {:>7.2f}  {:>8.2f}'.format(n, i, r, w=width) for n, i, r in zip(names, fig['IoU'], fig['class_accuracy'])]
+    else:
+        band = BoundaryIoU(nc, ds.IGNORE_CLASS_LABEL, ratio=boundary)
+        band.merge(host[at:at + 3 * nc].to(t.int64))
+        at += 3 * nc
+        bfig = band.result()
+        result.update({'mBIoU_dataset': bfig['mBIoU'], 'BIoU_per_class': [float(v) for v in bfig['BIoU']]})
+        lines[-1] += '  {:>15s}'.format('boundary IoU %')
+        lines += ['{:<{w}s}  {:>7.2f}  {:>8.2f}  {:>15.2f}'.format(n, i, r, b, w=width)
+                  for n, i, r, b in zip(names, fig['IoU'], fig['class_accuracy'], bfig['BIoU'])]
+        lines.append('Dataset-level boundary mIoU %: {:.2f} (band of {:g} of the image diagonal: {:s} pixels)'.format(
+            result['mBIoU_dataset'], boundary, ', '.join('{:d}'.format(d) for d in sorted(set(band_distances)))))
     if sisr:
-        at, on_host = at + nc * nc, SRQuality()
+        on_host = SRQuality()
         for records, C, H, W in quality.batches:
             on_host.update_from_records(host[at:at + records.numel()].reshape(-1, 2), C, H, W)
             at += records.numel()

@@ -2241,6 +2241,61 @@ def confusion_matrix_(confusion, pred, target, num_classes, ignore_index=255, na
     return confusion
 
 
+def boundary_distance(H, W, ratio=0.02):
+    """The band distance of Boundary IoU for H x W maps: `ratio` of the image diagonal, rounded, at least 1 (46 at 1024 x 2048 for the paper's 0.02)."""
+    ratio = float(ratio)
+    if not math.isfinite(ratio) or ratio <= 0.0:
+        raise ValueError(f'boundary_distance: ratio = {ratio} is not a finite number > 0')
+    if int(H) < 1 or int(W) < 1:
+        raise ValueError(f'boundary_distance: H = {H}, W = {W} (both >= 1)')
+    return max(1, int(round(ratio * math.hypot(int(H), int(W)))))
+
+
+def boundary_counts_(counts, pred, target, num_classes, ignore_index=255, distance=None, ratio=0.02, nan_flag=None, band=None):
+    """counts[I | G | P] += the Boundary IoU counters of two class maps of the same shape, (N, H, W) or (H, W) (dsrl_boundary_counts,
+    include/dsrl_hip.h): per class the pixels of the target's band (G), of the prediction's band (P) and of both (I), a band being the pixels whose
+    (2d+1) x (2d+1) window leaves the image or holds another label.  `distance` d, or `ratio` of the diagonal (boundary_distance) when None.  Targets
+    equal to `ignore_index` or >= num_classes are void, and so is the prediction under them; a predicted class >= num_classes elsewhere raises bit 1 of
+    `nan_flag` (int32 device scalar, optional) and is in no class's P.  `band` (uint8, the maps' shape, contiguous, optional) receives bit 0 = target
+    band, bit 1 = prediction band, 0 on void pixels.  `counts`: int64, 3 * num_classes elements, accumulated.  Two launches, nothing read back.
+    A bad argument is a ValueError or DsrlHipError before any device work."""
+    C = int(num_classes)
+    maxc = int(query('dsrl_boundary_counts_max_classes'))
+    if C < 1 or C > maxc:
+        raise ValueError(f'boundary_counts_: {C} classes, 1 to {maxc} are possible')
+    if tuple(pred.shape) != tuple(target.shape):
+        raise DsrlHipError(f'boundary_counts_: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape')
+    if pred.dim() not in (2, 3):
+        raise ValueError(f'boundary_counts_: class maps of shape (N, H, W) or (H, W) expected, got {tuple(pred.shape)}')
+    N = int(pred.shape[0]) if pred.dim() == 3 else 1
+    H, W = int(pred.shape[-2]), int(pred.shape[-1])
+    if N < 1 or H < 1 or W < 1:
+        raise ValueError(f'boundary_counts_: empty class maps of shape {tuple(pred.shape)}')
+    if N * H * W >= 2 ** 31:
+        raise ValueError(f'boundary_counts_: maps of {N * H * W} pixels do not fit 32-bit pixel indices')
+    d = boundary_distance(H, W, ratio) if distance is None else int(distance)
+    maxd = int(query('dsrl_boundary_counts_max_distance'))
+    if d < 1 or d > maxd:
+        raise ValueError(f'boundary_counts_: distance {d}, 1 to {maxd} are possible')
+    with torch.no_grad():
+        if nan_flag is not None and (nan_flag.dtype != torch.int32 or nan_flag.numel() != 1 or nan_flag.device != pred.device):
+            raise DsrlHipError('boundary_counts_: nan_flag must be an int32 scalar on the maps\' device')
+        if band is not None and (band.dtype != torch.uint8 or tuple(band.shape) != tuple(pred.shape) or not band.is_contiguous() or band.device != pred.device):
+            raise DsrlHipError(f'boundary_counts_: band must be a contiguous uint8 tensor of shape {tuple(pred.shape)} on the maps\' device')
+        if counts.dtype != torch.int64 or counts.numel() != 3 * C or not counts.is_contiguous():
+            raise DsrlHipError(f'boundary_counts_: counts must be a contiguous int64 tensor of {3 * C} elements (got {counts.dtype}, {counts.numel()} elements)')
+        if target.device != pred.device or counts.device != pred.device:
+            raise DsrlHipError(f'boundary_counts_: pred is on {pred.device}, target on {target.device}, counts on {counts.device}')
+        _need_gpu(pred, target, counts, nan_flag, band)
+        pred = (pred if pred.dtype == torch.uint8 else pred.to(torch.uint8)).contiguous()
+        target = (target if target.dtype == torch.uint8 else target.to(torch.uint8)).contiguous()
+        nbytes = cquery('dsrl_boundary_counts_workspace_bytes', N, H, W, d)
+        ws = _ws(nbytes, pred)
+        call('dsrl_boundary_counts', pred.data_ptr(), target.data_ptr(), N, H, W, C, int(ignore_index), d, counts.data_ptr(),
+             None if band is None else band.data_ptr(), None if nan_flag is None else nan_flag.data_ptr(), ws.data_ptr(), nbytes, _stream())
+    return counts
+
+
 def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, counts=None, nan_flag=None, flip=False, confusion=None):
     """Eval-mode tail of the SSSR decoder after its bilinear x2 (DSRL.py:55-69): ConvTranspose2d k2 s2 `convt1` -> BatchNorm2d `bn` (running statistics)
     -> ReLU -> ConvTranspose2d k2 s2 `convt2` -> arg-max, as one launch that writes class indices and never the logits (dsrl_sssr_tail_predict).

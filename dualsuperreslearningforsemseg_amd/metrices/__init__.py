@@ -231,6 +231,72 @@ class SRQuality:
         return {'PSNR': float(psnr.mean()), 'SSIM': float(ssim.mean()), 'images': int(psnr.size), 'PSNR_per_image': psnr, 'SSIM_per_image': ssim}
 
 
+class BoundaryIoU:
+    """Dataset-level Boundary IoU (Cheng et al., CVPR 2021): the IoU restricted to the pixels within `distance` of a class outline, `ratio` of each
+    batch's image diagonal when `distance` is None (functional.boundary_counts_, dsrl_boundary_counts).  Shaped like ConfusionMatrix: `.counts` is the
+    int64 [I | G | P] buffer of 3 * num_classes elements, allocated on first use on the device of what it is fed; every update adds to it, result()
+    does the one read."""
+
+    def __init__(self, num_classes, ignore_index=255, ratio=0.02, distance=None):
+        self.num_classes, self.ignore_index = int(num_classes), int(ignore_index)
+        self.ratio, self.distance = float(ratio), None if distance is None else int(distance)
+        HF.boundary_distance(1, 1, self.ratio)          # a bad ratio is refused here
+        if self.distance is not None and self.distance < 1:
+            raise ValueError(f'BoundaryIoU: distance {self.distance} below 1')
+        self._counts = None
+
+    def _on(self, device):
+        if self._counts is None:
+            self._counts = torch.zeros(3 * self.num_classes, dtype=torch.int64, device=device)
+        elif self._counts.device != torch.device(device):
+            raise ValueError(f'BoundaryIoU lives on {self._counts.device}, fed from {device}')
+        return self._counts
+
+    @property
+    def counts(self):
+        if self._counts is None:
+            raise ValueError('BoundaryIoU.counts before first use: call on(device), update() or merge() first')
+        return self._counts
+
+    def on(self, device):
+        """-> .counts, allocated on `device` if nothing has been fed yet"""
+        return self._on(torch.device(device))
+
+    def reset(self):
+        if self._counts is not None:
+            self._counts.zero_()
+
+    def update(self, pred, target, valid_labels_mask=None):
+        """class maps (B, H, W) or (H, W) and an optional boolean mask of the pixels that count (device tensors) -> dsrl_boundary_counts"""
+        assert pred.shape == target.shape, "BUG CHECK: 'pred' and 'target' must be of the same shape of (B, H, W)."
+        HF._need_gpu(pred, target, valid_labels_mask)
+        if valid_labels_mask is not None:
+            target = torch.where(valid_labels_mask.bool(), target.long(), torch.full_like(target.long(), self.ignore_index))
+        HF.boundary_counts_(self._on(pred.device), pred, target, self.num_classes, self.ignore_index, distance=self.distance, ratio=self.ratio)
+
+    def merge(self, other):
+        """adds another BoundaryIoU or an int64 tensor of 3 * C elements; a host tensor is taken as it is (and so is its device)"""
+        m = other.counts if isinstance(other, BoundaryIoU) else other
+        if m.dtype != torch.int64 or m.numel() != 3 * self.num_classes:
+            raise ValueError(f'merge: an int64 tensor of {3 * self.num_classes} elements expected, got {m.dtype} of {m.numel()}')
+        self._on(m.device).add_(m.reshape(-1))
+
+    def result(self):
+        """The one device read -> boundary_figures(counts); nothing fed gives NaN figures."""
+        C = self.num_classes
+        return boundary_figures(np.zeros(3 * C, np.int64) if self._counts is None else self._counts.cpu().numpy().astype(np.int64))
+
+
+def boundary_figures(counts):
+    """The figures of BoundaryIoU.result() from the [I | G | P] counters (3 * C integers): {'BIoU': per class I / (G + P - I) in percent, NaN where a
+    class has no band pixel in either map; 'mBIoU': its nan-mean; 'I', 'G', 'P': the int64 counters}."""
+    c = np.asarray(counts).astype(np.int64).reshape(3, -1)
+    inter, union = c[0].astype(np.float64), (c[1] + c[2] - c[0]).astype(np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        biou = np.where(union > 0, inter / union, np.nan)
+    return {'BIoU': 100. * biou, 'mBIoU': 100. * _nanmean(biou), 'I': c[0].copy(), 'G': c[1].copy(), 'P': c[2].copy()}
+
+
 def _nanmean(v):
     ok = ~np.isnan(v)
     return float(v[ok].mean()) if ok.any() else float('nan')

@@ -810,6 +810,32 @@ size_t dsrl_sr_quality_workspace_bytes(int N, int C, int H, int W);
 int dsrl_sr_quality(const float* pred, int ld_pred, const float* ref, int ld_ref, int N, int C, int H, int W, const float* mean /*host, C*/,
                     const float* std /*host, C*/, double* records /*N x 2*/, float* ssim_map /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Boundary IoU (Cheng et al., CVPR 2021) of two class maps: the counters of the IoU restricted to the pixels within distance d of a class outline
+ * (csrc/boundary.hip).  pred, target: uint8 (N,H,W); either may start at any byte and W may be anything (byte loads).
+ *   1. g' = target where target < C and target != ignore_index, else 255 (void).  p' = 255 where g' == 255, else pred where pred < C, else 254 (bad);
+ *      a bad pixel raises bit 1 (|= 2) of nan_flag (nullable), as in dsrl_confusion_matrix.
+ *   2. A pixel is in the band of a map iff the (2d+1) x (2d+1) window centred on it leaves the image or holds a byte other than its own; windows do
+ *      not reach into the batch's next image.  gb: the band of g', pb: the band of p'.  For every class at once this is the paper's
+ *      mask - erode(mask, 3x3, d iterations) on a mask padded by a ring of zeros.
+ *   3. Over the pixels with g' != 255: G[c] += gb && g' == c;  P[c] += pb && p' == c (p' < C only);  I[c] += gb && pb && g' == c && p' == c.
+ *   counts = [I | G | P], 3*C 64-bit counters, ADDED to (8-byte aligned); Boundary IoU of class c = I / (G + P - I).
+ *   band (nullable, N*H*W bytes) is WRITTEN: bit 0 gb, bit 1 pb, 0 on void pixels.
+ *   Two launches (a row pass that leaves one byte per pixel and map in ws - the label where the row window is uniform and inside the image, 253
+ *   otherwise - and a column pass that tests those bytes and counts), O(1) work per pixel and pass whatever d; integer arithmetic, per-block LDS bins
+ *   flushed as 64-bit atomics: exact, order independent, identical run to run, and an image counts the same alone or inside a batch.  No allocation
+ *   and no host synchronisation.
+ *   1 <= C <= dsrl_boundary_counts_max_classes() = 253 and 1 <= d <= dsrl_boundary_counts_max_distance() = 128 (DSRL_E_UNSUPPORTED above, DSRL_E_BADARG
+ *   below, as for a dimension below 1 or a null pred, target or counts); N*H*W < 2^31 - 2^16 (DSRL_E_UNSUPPORTED); ws 2-byte aligned, ws_bytes >= the query
+ *   (DSRL_E_WORKSPACE).  The query depends on its arguments only and holds for every launch of that shape (0 for arguments the launch refuses).
+ * ---------------------------------------------------------------------------------------------- */
+int dsrl_boundary_counts_max_classes(void);
+int dsrl_boundary_counts_max_distance(void);
+size_t dsrl_boundary_counts_workspace_bytes(int N, int H, int W, int d);
+int dsrl_boundary_counts(const uint8_t* pred, const uint8_t* target, int N, int H, int W, int C, int ignore_index, int d,
+                         unsigned long long* counts /*[3*C]: I | G | P, ADDED to*/, uint8_t* band /*nullable*/, int* nan_flag /*nullable*/, void* ws,
+                         size_t ws_bytes, dsrl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
