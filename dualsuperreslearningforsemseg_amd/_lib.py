@@ -156,6 +156,10 @@ PROTOTYPES = {
     'dsrl_ohem_select': (i32, [fp, i64, f32, i64, fp, fp, sz, stream_t]),
     'dsrl_ohem_apply': (i32, [fp, fp, i64, i32, fp, fp, stream_t]),
     'dsrl_ohem_target': (i32, [fp, i32, fp, i64, i32, i32, f32, i64, fp, fp, fp, fp, sz, stream_t]),
+    'dsrl_dice_workspace_bytes': (sz, [i64]),
+    'dsrl_dice_fwd': (i32, [fp, i32, fp, i64, i32, i32, f32, f32, fp, fp, fp, sz, stream_t]),
+    'dsrl_dice_bwd': (i32, [fp, i32, fp, i64, i32, i32, fp, i32, fp, i32, stream_t]),
+    'dsrl_convt2x2_bwd_ce_d': (i32, [fp, fp, fp, fp, i32, fp, fp, fp, fp, fp, i32, fp, fp, fp, i32, i32, i32, i32, i32, fp, sz, stream_t]),
     'dsrl_loss_mix': (i32, [fp, fp, fp, f32, f32, fp, fp, stream_t]),
     'dsrl_fa_saved_floats': (sz, [i32] * 5),
     'dsrl_fa_workspace_bytes': (sz, [i32] * 5),

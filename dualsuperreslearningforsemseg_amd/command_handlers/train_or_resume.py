@@ -99,18 +99,27 @@ class TrainStep:
     probability) and not with `focal_gamma` > 0 or `label_smoothing` > 0 (ValueError); `ignore_index` must then be a byte value.  With more than one
     rank each rank mines its own batch.  Fixed for the life of the step, like the other two.
 
+    `dice` (HF.dice_value: None / False / 0 off, True = (1.0, 1.0), a weight, (weight, smooth) or a mapping): the soft Dice term weight * L_dice is
+    added to the CE term of the TRAINING iterations (HF.dice_loss) - the class sums are formed on the device from the batch of the
+    iteration, the term's gradient joins d(CE)/d(logits) inside the ConvTranspose backward, fused and unfused losses, eager and captured.  The CE
+    figure a training iteration reports is then CE + weight * L_dice.  `do_train=False` keeps the configured CE, so validation losses and checkpoint
+    selection stay comparable between runs with and without it.  It goes with `class_weights` and not with `focal_gamma` > 0, `label_smoothing` > 0
+    or `ohem` (ValueError).  With more than one rank each rank uses the sums of its own batch.  Fixed for the life of the step, like the others.
+
     The weight average (`flat.enable_ema`) needs nothing here: the optimiser pass of the step updates it, eagerly and in the captured
     graph alike, and whether it is enabled is part of the graph key.  A training iteration inside `flat.ema_weights()` raises DsrlHipError."""
 
     GRAPH_WARMUP = HF.GRAPH_WARMUP          # eager iterations per batch shape before the capture
 
-    def __init__(self, model, flat, stage, w1, w2, ignore_index, graph=None, class_weights=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None):
+    def __init__(self, model, flat, stage, w1, w2, ignore_index, graph=None, class_weights=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None,
+                 dice=None):
         self.model, self.flat, self.stage, self.w1, self.w2, self.ignore = model, flat, stage, w1, w2, ignore_index
         self.focal_gamma = HF.focal_gamma_value(focal_gamma)                                                          # ValueError on a bad gamma
         self.label_smoothing = HF.label_smoothing_value(label_smoothing)                                              # ValueError on a bad eps
         if self.focal_gamma > 0.0 and self.label_smoothing > 0.0:
             raise ValueError(f'label_smoothing = {label_smoothing!r} together with focal_gamma = {focal_gamma!r}: the combination is not defined')
         self.ohem = HF._ohem_args(ohem, self.focal_gamma, self.label_smoothing, ignore_index)                        # ValueError on a bad value or combination
+        self.dice = HF._dice_args(dice, self.focal_gamma, self.label_smoothing, self.ohem)                           # ValueError on a bad value or combination
         self.class_weight = None if class_weights is None else HF.class_weight_table(class_weights, flat.device)     # ValueError on bad weights
         self.fa = FALoss()
         dev = flat.device
@@ -141,7 +150,7 @@ class TrainStep:
     def losses(self, outs, input_org, target, do_train=True):
         SSSR, SISR, SSSR_ft, SISR_ft = outs
         ce = HF.cross_entropy(SSSR, target, self.ignore, self.class_weight, self.focal_gamma, self.label_smoothing,      # train_or_resume.py:435
-                              self.ohem if do_train else None)
+                              self.ohem if do_train else None, self.dice if do_train else None)
         ms = self.w1 * HF.mse_loss(SISR, input_org) if self.stage > 1 else self.zero       # :436
         fa = self.w2 * self.fa(SSSR_ft, SISR_ft) if self.stage > 2 else self.zero          # :437
         return ce, ms, fa, ce + ms + fa                                                    # :438
@@ -163,20 +172,21 @@ class TrainStep:
                 bb._dsrl_cut = []
         self.flag.zero_()
         ohem = self.ohem if do_train else None    # validation keeps the configured CE without mining
+        dice = self.dice if do_train else None    # and without the Dice term
         cuts = None
         try:
             with t.set_grad_enabled(do_train):
                 if self.fused_losses and do_train:
                     # the layer that produces the logits evaluates the CE value in its own forward kernel (HF.logits_target), :435
                     with HF.logits_target(target if target.dtype == t.uint8 and target.is_contiguous() else None, self.ignore, self.flag,
-                                          self.class_weight, self.focal_gamma, self.label_smoothing, ohem):
+                                          self.class_weight, self.focal_gamma, self.label_smoothing, ohem, dice):
                         outs = self.model(input_image)                                     # :420
                 else:
                     outs = self.model(input_image)                                         # :420
                 if self.fused_losses:
                     # CE + MSE + FA, their gradients, the NaN asserts (:426-433) and the loss mix (:435-438) in one launch set
                     vals = HF.fused_losses(outs, target, input_org, self.ignore, self.w1, self.w2, self.stage, self.flag, self.fa.subsample_factor,
-                                           self.class_weight, self.focal_gamma, self.label_smoothing, ohem)
+                                           self.class_weight, self.focal_gamma, self.label_smoothing, ohem, dice)
                     total = vals[3]
                 else:
                     HF.nan_check_(self.flag, *[o for o in outs if o.is_cuda])              # the four NaN asserts, :426-433
@@ -253,7 +263,7 @@ class TrainStep:
     def _graph_key(self, input_image, input_org, target):
         return (tuple(input_image.shape), tuple(input_org.shape), tuple(target.shape), HF.get_conv_precision(), HF.overlap_wgrad,
                 self.flat.e_flat is not None,           # "EMA enabled": a step captured without the weight average has no launch that updates it
-                self.focal_gamma, self.label_smoothing, self.ohem)
+                self.focal_gamma, self.label_smoothing, self.dice, self.ohem)
 
     def _capture(self, key, input_image, input_org, target, hp):
         """-> the captured step, or None: a capture that fails (a runtime that refuses something inside it) must not end the training run.  This
@@ -460,6 +470,13 @@ def check_ohem(dataset):
     return HF._ohem_args(dataset.get('ohem'), check_focal_gamma(dataset), check_label_smoothing(dataset), dataset['settings'].IGNORE_CLASS_LABEL)
 
 
+def check_dice(dataset):
+    """dataset['dice']: absent, None, False or 0 -> None (off); True, a weight > 0, a pair (weight, smooth) or a mapping with the keys 'weight' and
+    'smooth' -> (weight, smooth), as HF.dice_value; ValueError otherwise, and on a value together with dataset['focal_gamma'] > 0,
+    dataset['label_smoothing'] > 0 or dataset['ohem'] (scoped out).  Touches no device."""
+    return HF._dice_args(dataset.get('dice'), check_focal_gamma(dataset), check_label_smoothing(dataset), check_ohem(dataset))
+
+
 def check_ema(dataset):
     """dataset['ema']: absent, None or False -> None (off); True, a decay in (0, 1), a pair (decay, warmup) or a mapping with these keys ->
     (decay, warmup), as HF.ema_value; ValueError otherwise.  Touches no device."""
@@ -488,6 +505,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     focal_gamma = check_focal_gamma(dataset)
     label_smoothing = check_label_smoothing(dataset)
     ohem = check_ohem(dataset)
+    dice = check_dice(dataset)
     ema = check_ema(dataset)
     input_size = other_args.get('model_input_size', settings.MODEL_INPUT_SIZE)
     if distributed:
@@ -555,7 +573,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
         lut = DeviceBatchPreparation(ds.LABEL_MAPPING_DICT, ds.MEAN, ds.STD, input_size, ds.IGNORE_CLASS_LABEL).lut_host
         class_weights = enet_weights(class_counts(cache_dir_of(dataset), 'train', lut, device_obj)[:ds.NUM_CLASSES])
     step = TrainStep(model, flat, stage, w1, w2, ds.IGNORE_CLASS_LABEL, class_weights=class_weights, focal_gamma=focal_gamma,
-                     label_smoothing=label_smoothing, ohem=ohem)
+                     label_smoothing=label_smoothing, ohem=ohem, dice=dice)
     train_loader = factory('train', batch_size, device_obj, rank, world)
     val_loader = factory('val', batch_size, device_obj, rank, world) if is_master_rank else None
 
@@ -589,6 +607,8 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
                 train_loader.set_epoch(epoch)     # the sample order and the augmentation draws of this epoch
             means = _do_train_val(True, epoch, model, step, train_loader, lr, momentum, weights_decay, freeze_batch_norm, is_master_rank)
             rec = {'epoch': epoch, 'lr': lr, 'train': means}
+            if dice is not None:
+                rec['train_ce_includes_dice'] = list(dice)      # (weight, smooth): means[0] is CE + weight * L_dice; the validation figures are the CE alone
             stop = False
             if is_master_rank:
                 if checkpoint_history > 0 and epoch % checkpoint_interval == 0 and experiment_id:                 # :264

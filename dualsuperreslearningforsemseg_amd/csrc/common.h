@@ -41,17 +41,21 @@ int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float*
 // weighted() / focal() / smoothed(), and these hold the one normalisation rule: gamma == 0 or eps == 0 IS the weighted form, in every respect
 // (kernels, messages).  Everything below the entry points takes this value and decides by kind.
 struct CeVariant {
-    enum Kind { kPlain, kWeighted, kFocal, kSmoothed };
+    enum Kind { kPlain, kWeighted, kFocal, kSmoothed, kDice };
     const float* weights = nullptr;     // the 256-float class-weight table; the plain form has none
     float gamma = 0.f;                  // > 0: kFocal
     float eps = 0.f;                    // > 0: kSmoothed
     Kind kind = kPlain;
+    const float* dice = nullptr;        // kDice: the record of dsrl_dice_fwd (dsrl_convt2x2_bwd_ce_d only: the weighted row plus the Dice row)
     static CeVariant weighted(const float* w) { return CeVariant{w, 0.f, 0.f, kWeighted}; }
     static CeVariant focal(const float* w, float gamma) { return gamma == 0.f ? weighted(w) : CeVariant{w, gamma, 0.f, kFocal}; }
     static CeVariant smoothed(const float* w, float eps) { return eps == 0.f ? weighted(w) : CeVariant{w, 0.f, eps, kSmoothed}; }
+    static CeVariant diced(const float* w, const float* record) { return CeVariant{w, 0.f, 0.f, kDice, record}; }
     bool plain() const { return kind == kPlain; }
     bool table_ok() const { return plain() || weights != nullptr; }         // part of every entry point's argument check
-    const char* suffix() const { return plain() ? "" : kind == kWeighted ? "_w" : kind == kFocal ? "_f" : "_s"; }       // of the entry point, for its messages
+    const char* suffix() const {        // of the entry point, for its messages
+        return plain() ? "" : kind == kWeighted ? "_w" : kind == kFocal ? "_f" : kind == kSmoothed ? "_s" : "_d";
+    }
 };
 // losses.hip, for the ConvTranspose forms in spatial.hip: the pre-pass of every kind but plain (D = sum n_c w_c into d_out, through `ws` of
 // ce_weight_sum_bytes()) and the finalize (plain: loss / pixel count; the others: loss / D, D read from loss_out[1])
@@ -177,6 +181,31 @@ __device__ __forceinline__ void smooth_pixel(const float* v, const float* w, int
 }
 __device__ __forceinline__ float smooth_sub(float eps, int C, float wc, float scale) { return ((eps / (float)C) * wc) * scale; }
 __device__ __forceinline__ float smooth_grad(float e, float inv, bool hit, float sub_t, float sub_c) { return e * inv - (hit ? sub_t : sub_c); }
+
+// ---------------------------------------------------------------- soft Dice loss term (dice.hip), the gradient row of one pixel
+// The record dsrl_dice_fwd leaves in device memory: kDiceRecordFloats floats {lambda L_dice, |K|, a[0..C), b[0..C), zeros}.  With the per-class
+// coefficients a_c, b_c of the batch (zero for a class without a pixel),
+//     d(lambda L_dice) / d v_k = live p_k (g_k - sum_j p_j g_j),   g_j = b_j + a_j [j == t],   p_j = e_j (1 / s)
+// The caller passes its softmax terms e_c = exp_nonpos(v_c - m) and s = sum_c e_c (c ascending) - what every CE kernel has in hand - the label and
+// the two tables; live = the label is neither ignore_index nor >= C (such a pixel takes no part in Dice: a row of zeros).  dice_pixel forms 1 / s,
+// a_t and the sum over the classes in ascending j; dice_grad is one element of the row.  CT > 0: the class count at compile time (e[] in registers,
+// the loop unrolled); CT == 0: `C` at run time.  The unfused kernel (dice.hip) and the ConvTranspose backward that forms the row itself
+// (convt_dma.hip) both go through these two functions, so that they round alike (the library is built with -ffp-contract=off).
+constexpr int kDiceRecordFloats = 128, kDiceMaxC = 60;
+template <int CT>
+__device__ __forceinline__ void dice_pixel(const float* e, int C, float s, int tg, bool live, const float* a, const float* b, float& inv_s, float& a_t,
+                                           float& dot) {
+    const int n = CT > 0 ? CT : C;
+    inv_s = 1.f / s;
+    a_t = live ? a[tg] : 0.f;
+    float d = 0.f;
+#pragma unroll
+    for (int c = 0; c < n; ++c) d += (e[c] * inv_s) * (b[c] + (c == tg ? a_t : 0.f));
+    dot = d;
+}
+__device__ __forceinline__ float dice_grad(float e, float inv_s, float b_c, bool hit, float a_t, float dot, bool live) {
+    return live ? (e * inv_s) * ((b_c + (hit ? a_t : 0.f)) - dot) : 0.f;
+}
 
 // ---------------------------------------------------------------- exponential moving average of the weights (ema.hip)
 // The EMA record in device memory (16 bytes, 16-byte aligned).  omd = 1 - d_t of the update ABOUT to run; dsrl_ema_advance rewrites it once per step.

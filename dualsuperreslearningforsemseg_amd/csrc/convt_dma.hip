@@ -27,6 +27,7 @@
 #include "common.h"
 #include "lds_dma.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace dsrl {
 
@@ -42,6 +43,10 @@ struct ConvtCeArgs {
     float gamma;                    // FL: the focal exponent (> 0)
     float eps;                      // SM: the label smoothing (0 < eps <= 1)
 };
+// the arguments of the DC build: a type of its own, so that the kernel arguments of every other instantiation keep their size and offsets
+struct ConvtCeDiceArgs : ConvtCeArgs {
+    const float* dice;              // the record of dsrl_dice_fwd {lambda L_dice, |K|, a[0..CO), b[0..CO)}
+};
 
 // CW = true (dsrl_convt2x2_bwd_ce_w): nn.CrossEntropyLoss(weight=).  ce.count points to D = sum n_c w_c and the only change is in transform(): the
 // per-pixel sc = wtab[target] * (1 / D) stands where `scale` stands, as in ce_fused_body<true> (losses.hip).  The 256-float table sits in LDS, already
@@ -53,13 +58,18 @@ struct ConvtCeArgs {
 // SM = true (dsrl_convt2x2_bwd_ce_s): label-smoothed cross entropy.  The table in LDS holds the raw weights (its first CO entries are the per-class w_c
 // of the smoothing term), W = sum_c w_c is summed from it once per block, a second table holds smooth_sub of every class, and the row is smooth_pixel /
 // smooth_grad (common.h) on the e_c in registers, as ce_fused_body<true, false, true> forms it from its tile.  A backward needs no value, hence no log.
-template <int CI, int CO, bool CE, bool TW = false, bool CW = false, bool FL = false, bool SM = false>
+// DC = true (dsrl_convt2x2_bwd_ce_d): the weighted cross entropy plus the soft Dice term.  The coefficient tables a and b of the
+// record sit in LDS beside the weight table (in sub_s, which the label smoothing does not use here), the row is (weighted CE row) + (Dice row) with
+// the Dice row from dice_pixel / dice_grad (common.h) on the e_c in registers, and the transformer's g * w is added after that: the order and the
+// roundings of dsrl_ce_fused_w -> dsrl_dice_bwd(accumulate = 1) -> dsrl_pointwise_strided_bwd.
+template <int CI, int CO, bool CE, bool TW = false, bool CW = false, bool FL = false, bool SM = false, bool DC = false>
 __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ dy,
                                                                  float* __restrict__ dx, float* __restrict__ part, int N, int H, int W,
-                                                                 int nseg_per_row, int nseg, ConvtCeArgs ce) {
+                                                                 int nseg_per_row, int nseg, std::conditional_t<DC, ConvtCeDiceArgs, ConvtCeArgs> ce) {
     static_assert(CE || !CW, "class weights belong to the CE build");
     static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
     static_assert(!SM || (CW && !FL), "label smoothing runs on the weighted machinery and has no focal form");
+    static_assert(!DC || (CW && !FL && !SM && !TW && CO <= 32), "the Dice term runs on the weighted machinery, in the 8-wave build");
     constexpr int TP = 128, COLS = 4 * CO, NK = COLS / 2, NJ = (COLS + 31) / 32, NOUT = CI * COLS;
     constexpr int XB = TP * CI * 4, XP = (XB + 1023) / 1024;               // bytes / 1 KB pieces of an x segment
     constexpr int GB = 2 * TP * CO * 4, GP = GB / 1024;                    // of one dy row segment
@@ -118,8 +128,11 @@ __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(con
         if (tid < 32) ftw_s[tid] = (ce.ft_g && tid < CO) ? ce.ft_w[tid] : 0.f;          // visible after the first barrier below
     }
     __shared__ float wt_s[CW ? 256 : 1];
-    __shared__ float sub_s[SM ? 32 : 1];                                   // SM: ((eps / C) w_c) scale of every class, published with wt_s
+    __shared__ float sub_s[SM ? 32 : DC ? 64 : 1];                         // SM: ((eps / C) w_c) scale of every class; DC: a_c at c, b_c at 32 + c; published with wt_s
     if (SM && tid < 32) sub_s[tid] = tid < CO ? smooth_sub(ce.eps, CO, ce.wtab[tid], scale) : 0.f;
+    if constexpr (DC) {
+        if (tid < 64) sub_s[tid] = (tid & 31) < CO ? ce.dice[2 + (tid >> 5) * CO + (tid & 31)] : 0.f;
+    }
     if (CW) {
         if (tid < 256) wt_s[tid] = (FL || SM) ? ce.wtab[tid] : ce.wtab[tid] * scale;   // sc of a pixel with label tid (FL, SM: its weight; sc is formed per pixel)
         // block_barrier() is a bare s_barrier: it does not wait for this wave's ds_write, so drain the LDS counter before the barrier that publishes the table
@@ -186,6 +199,16 @@ __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(con
                 const float inv = sc / s;
 #pragma unroll
                 for (int c = 0; c < CO; ++c) e[c] = live ? e[c] * inv - (c == tg ? sc : 0.f) : 0.f;
+            } else if (DC) {
+                // (weighted CE row) + (Dice row); a pixel whose label is >= CO takes no part in Dice and has weight 0 in the table
+                const bool dlive = live && tg < CO;
+                float inv_s, a_t, dot;
+                dice_pixel<CO>(e, CO, s, tg, dlive, sub_s, sub_s + 32, inv_s, a_t, dot);
+                const float sc = wt_s[tg];
+                const float inv = sc / s;
+#pragma unroll
+                for (int c = 0; c < CO; ++c)
+                    e[c] = live ? (e[c] * inv - (c == tg ? sc : 0.f)) + dice_grad(e[c], inv_s, sub_s[32 + c], c == tg, a_t, dot, dlive) : 0.f;
             } else if (CW) {
                 // sc = table[target] is per lane where `scale` is uniform: held across the 19 operations beside inv it is one VGPR more than the
                 // 768-thread build has (168, 2 spilled).  So it is read twice: for inv, and again - through a copy of the index the compiler cannot
@@ -373,18 +396,23 @@ bool convt_bwd_dma_supported(const void* x, const void* dy, int W, int Cin, int 
 }
 int convt_bwd_dma_blocks(long long nseg, int cap) { return (int)std::min<long long>(std::min(cap, kNumCU), nseg); }
 
-template <bool CE, bool TW, bool CW = false, bool FL = false, bool SM = false>
-static int launch_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, const ConvtCeArgs& ce, hipStream_t st) {
+template <bool CE, bool TW, bool CW = false, bool FL = false, bool SM = false, bool DC = false>
+static int launch_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, const ConvtCeArgs& ce, hipStream_t st,
+                      const float* dice = nullptr) {
     constexpr int CI = 19, CO = 19;
     constexpr int kLds = 3 * ((128 * CI * 4 + 1023) / 1024 + 2 * (2 * 128 * CO * 4 / 1024) + (CE ? 2 : 0)) * 1024;
-    static_assert(kLds + (CW ? 1024 : 0) + (SM ? 128 : 0) + 128 <= 160 * 1024, "the ring, the transformer's weights and the class-weight tables in LDS");
-    static const hipError_t attr = hipFuncSetAttribute((const void*)convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+    static_assert(kLds + (CW ? 1024 : 0) + (SM ? 128 : 0) + (DC ? 256 : 0) + 128 <= 160 * 1024,
+                  "the ring, the transformer's weights, the class-weight tables and the Dice tables in LDS");
+    static const hipError_t attr = hipFuncSetAttribute((const void*)convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM, DC>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     if (attr != hipSuccess) { set_error("convt2x2_bwd_dma_kernel: %d bytes of LDS refused (%s)", kLds, hipGetErrorString(attr)); return DSRL_E_LAUNCH; }
     const int nseg_per_row = W / 128;
     const long long nseg = (long long)N * H * nseg_per_row;
     if ((long long)N * 4 * H * W * CO * 4 >= (1ll << 32)) { set_error("convt2x2_bwd_dma_kernel: output gradient of 4 GB or more"); return DSRL_E_UNSUPPORTED; }
     if (nseg >= (1ll << 31) || nblocks < 1 || nblocks > nseg) { set_error("convt2x2_bwd_dma_kernel: %lld segments, %d blocks", nseg, nblocks); return DSRL_E_BADARG; }
-    hipLaunchKernelGGL((convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM>), dim3(nblocks), dim3(TW ? 768 : 512), kLds, st, x, w, dy, dx, part, N, H, W, nseg_per_row, (int)nseg, ce);
+    std::conditional_t<DC, ConvtCeDiceArgs, ConvtCeArgs> args{};
+    static_cast<ConvtCeArgs&>(args) = ce;
+    if constexpr (DC) args.dice = dice;
+    hipLaunchKernelGGL((convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM, DC>), dim3(nblocks), dim3(TW ? 768 : 512), kLds, st, x, w, dy, dx, part, N, H, W, nseg_per_row, (int)nseg, args);
     return launch_status("convt2x2_bwd_dma_kernel");
 }
 int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, hipStream_t st) {
@@ -404,6 +432,9 @@ int launch_convt_bwd_dma_ce(const float* x, const float* w, const float* logits,
     if (v.kind == CeVariant::kFocal) return launch_dma<true, false, true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
     // label smoothing: one wave build, the 8-wave one, as focal has
     if (v.kind == CeVariant::kSmoothed) return launch_dma<true, false, true, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
+    // Dice: one wave build, the 8-wave one, as focal and label smoothing have.  The 12-wave build has 168 VGPRs and spills with focal already; the
+    // Dice row keeps 1 / s, a_t and the class sum beside the 19 terms and the weighted row's inv and sc
+    if (v.kind == CeVariant::kDice) return launch_dma<true, false, true, false, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st, v.dice);
     if (v.kind == CeVariant::kWeighted) return w8 ? launch_dma<true, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st)
                         : launch_dma<true, true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
     if (w8) return launch_dma<true, false>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);

@@ -1296,10 +1296,11 @@ class LogitsGrad:
     leaves `target`, `count` (device pointer holder) here and reports no gradient; the stride-8 feature transformer leaves its incoming gradient and
     weights; the ConvTranspose backward then forms d(CE)/d(logits) (+ the transformer's rank-one term) inside its own kernel
     (dsrl_convt2x2_bwd_ce): the 319 MB gradient of the 256x512 step is neither written nor read."""
-    __slots__ = ('y', 'xshape', 'x_ptr', 'armed', 'target', 'ignore_index', 'count', 'ft', 'value', 'value_key', 'weight', 'gamma', 'eps')
+    __slots__ = ('y', 'xshape', 'x_ptr', 'armed', 'target', 'ignore_index', 'count', 'ft', 'value', 'value_key', 'weight', 'gamma', 'eps', 'dice')
 
     def __init__(self):
         self.y = None; self.xshape = None; self.x_ptr = 0; self.armed = False; self.target = None; self.ignore_index = 255; self.count = None; self.ft = None
+        self.dice = None            # the record of dsrl_dice_fwd when the loss has a Dice term (always with a table, like gamma); None: no such term
         self.value = None           # [CE, pixel count, ...] when the producing layer already evaluated the loss (logits_target), and for which
         self.value_key = None       # (target pointer, ignore_index, NaN flag pointer, class-weight table pointer or 0, label smoothing, focal gamma)
         self.weight = None          # the 256-float class-weight table of a weighted loss (class_weight_table); `count` then holds D = sum n_c w_c
@@ -1454,17 +1455,114 @@ def ohem_target(logits, target, ignore_index, thresh, min_kept, flag=None, stats
     return out
 
 
-def _focal_args(weight, gamma, device, num_classes, eps=0.0):
+DICE_DEFAULT = (1.0, 1.0)               # lambda, smooth of `dice=True`: an equal-weight "CE + Dice" with the usual +1 smoothing
+DICE_RECORD_FLOATS = 128                # the record of dsrl_dice_fwd: {lambda L_dice, |K|, a[0..C), b[0..C), zeros}
+
+
+def dice_value(x):
+    """The soft Dice term as (lambda, smooth), or None when it is off.  None / False / 0: off; True: DICE_DEFAULT; a finite number > 0: lambda, with
+    the default smooth; a pair (lambda, smooth); a mapping with the keys 'weight' (lambda) and / or 'smooth' (a missing one takes its default).
+    smooth: a finite number >= 0.  A lambda of 0 inside a pair or a mapping is off too.  ValueError on anything else - a bool where a number belongs,
+    a NaN, an infinity, a negative number, an unknown key.  Touches no device."""
+    if x is None:
+        return None
+    if isinstance(x, (bool, np.bool_)):
+        return DICE_DEFAULT if x else None
+    if isinstance(x, dict):
+        if not x or set(x) - {'weight', 'smooth'}:
+            raise ValueError(f"dice = {x!r}: expected a mapping with the keys 'weight' and 'smooth'")
+        lam, smooth = x.get('weight', DICE_DEFAULT[0]), x.get('smooth', DICE_DEFAULT[1])
+    elif isinstance(x, (tuple, list)) and len(x) == 2:
+        lam, smooth = x
+    elif isinstance(x, (int, float, np.integer, np.floating)):
+        lam, smooth = x, DICE_DEFAULT[1]
+    else:
+        raise ValueError(f'dice = {x!r}: expected None, a bool, a number > 0, a pair (weight, smooth) or a mapping with these keys')
+    for name, v in (('weight', lam), ('smooth', smooth)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f'dice: {name} = {v!r}: expected a finite number >= 0')
+        with np.errstate(over='ignore'):
+            v32 = float(np.float32(float(v)))                                  # (the kernels take both as fp32)
+        if not (0.0 <= float(v) and math.isfinite(v32)):                       # (a NaN fails the comparison)
+            raise ValueError(f'dice: {name} = {v!r}: expected a finite number >= 0')
+    lam, smooth = float(lam), float(smooth)
+    if lam == 0.0:
+        return None
+    if float(np.float32(lam)) == 0.0:
+        raise ValueError(f'dice: weight = {lam!r} is zero as fp32')
+    return lam, smooth
+
+
+def _dice_args(dice, gamma, eps, ohem):
+    """dice_value(dice) of a CE call, after the combinations it does not go with: a focal or label-smoothed loss and hard-pixel mining (scoped out:
+    ValueError).  It goes with class weights."""
+    dice = dice_value(dice)
+    if dice is not None and (gamma > 0.0 or eps > 0.0 or ohem is not None):
+        raise ValueError(f'dice = {dice!r} together with focal_gamma = {gamma!r}, label_smoothing = {eps!r} or ohem = {ohem!r}: '
+                         'the combination is not supported')
+    return dice
+
+
+def _dice_record(logits, ld, target, P, Cc, ignore_index, dice, flag=None):
+    """dsrl_dice_fwd on pixel-major logits and a contiguous uint8 target: -> the 128-float device record {lambda L_dice, |K|, a, b}.
+    No host read: it can be captured."""
+    rec = torch.empty(DICE_RECORD_FLOATS, device=logits.device, dtype=torch.float32)
+    ws = _ws(cquery('dsrl_dice_workspace_bytes', P), logits)
+    call('dsrl_dice_fwd', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), float(dice[0]), float(dice[1]), rec.data_ptr(),
+         None if flag is None else flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return rec
+
+
+class _DiceLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, dice):
+        logits, ld = pm(logits)
+        _need_gpu(target)
+        if target.dtype != torch.uint8:
+            target = target.to(torch.uint8)
+        target = target.contiguous()
+        N, Cc, H, W = logits.shape
+        P = N * H * W
+        if target.numel() != P:
+            raise DsrlHipError(f'dice_loss: target has {target.numel()} pixels, logits {P}')
+        rec = _dice_record(logits, ld, target, P, Cc, ignore_index, dice)
+        ctx.save_for_backward(logits, target, rec)
+        ctx.ignore_index = int(ignore_index)
+        return rec[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, rec = ctx.saved_tensors
+        _, ld = pm(logits)
+        N, Cc, H, W = logits.shape
+        dl = new_cl((N, Cc, H, W), logits)
+        call('dsrl_dice_bwd', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, rec.data_ptr(), 0, dl.data_ptr(), Cc, _stream())
+        dl.mul_(g.reshape(1, 1, 1, 1).float())          # the incoming gradient as a device scalar: no host read (1 leaves every element as it is)
+        return dl, None, None, None
+
+
+def dice_loss(logits, target, ignore_index=255, weight=1.0, smooth=1.0):
+    """weight * L_dice, the soft Dice loss of the softmax of logits (N,C,H,W) against target (N,H,W) uint8/long: L_dice = 1 - the
+    mean over the classes PRESENT among the live pixels of the call of (2 I_c + smooth) / (P_c + G_c + smooth); a pixel is live when its label is
+    neither ignore_index nor >= C.  A class that no live pixel carries adds nothing (it is not counted as a perfect score).  weight: a finite number
+    > 0; smooth: a finite number >= 0.  Differentiable (dsrl_dice_fwd / dsrl_dice_bwd); the class sums are those of this call."""
+    dice = dice_value((weight, smooth))
+    if dice is None:
+        raise ValueError(f'dice_loss: weight = {weight!r}: expected a finite number > 0')
+    return _DiceLoss.apply(logits, target, int(ignore_index), dice)
+
+
+def _focal_args(weight, gamma, device, num_classes, eps=0.0, dice=None):
     """(class-weight table or None, gamma, eps) of a CE call: the focal and the label-smoothed loss run on the weighted kernels, so gamma > 0 or
-    eps > 0 without weights takes the all-ones table of `num_classes` classes.  Both at once: ValueError (the combination has no agreed
-    definition and no kernel)."""
+    eps > 0 without weights takes the all-ones table of `num_classes` classes; so does a Dice term (`dice` not None), whose fused backward is a
+    build of the weighted kernel.  gamma and eps both at once: ValueError (the combination has no agreed definition and no kernel)."""
     gamma = focal_gamma_value(gamma)
     eps = label_smoothing_value(eps)
     if gamma > 0.0 and eps > 0.0:
         raise ValueError(f'label_smoothing = {eps!r} together with focal_gamma = {gamma!r}: the combination is not defined')
     if weight is not None:
         weight = class_weight_table(weight, device, num_classes)
-    elif gamma > 0.0 or eps > 0.0:
+    elif gamma > 0.0 or eps > 0.0 or dice is not None:
         weight = class_weight_table(np.ones(int(num_classes), np.float32), device, num_classes)
     return weight, gamma, eps
 
@@ -1497,17 +1595,20 @@ class logits_target:
     together with either of the two).  Outside the block, or when the shape does not qualify, nothing changes.  With ohem nothing is engaged either:
     the target the loss will use does not exist before the logits do, so the plain forward runs and fused_losses evaluates the value itself."""
 
-    def __init__(self, target, ignore_index, flag, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None):
+    def __init__(self, target, ignore_index, flag, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None, dice=None):
         focal_gamma = focal_gamma_value(focal_gamma)
         label_smoothing = label_smoothing_value(label_smoothing)
         if focal_gamma > 0.0 and label_smoothing > 0.0:
             raise ValueError(f'label_smoothing = {label_smoothing!r} together with focal_gamma = {focal_gamma!r}: the combination is not defined')
         ohem = _ohem_args(ohem, focal_gamma, label_smoothing, ignore_index)
+        # a Dice term leaves the forward as it is: the kernel evaluates the CE value (on the weighted machinery: the all-ones table without weights,
+        # as fused_losses will use) and dsrl_dice_fwd reads the logits once more
+        dice = _dice_args(dice, focal_gamma, label_smoothing, ohem)
         ok = (convt_ce_enabled and target is not None and target.is_cuda and target.dtype == torch.uint8 and target.is_contiguous() and target.dim() == 3
               and flag is not None and flag.dtype == torch.int32 and ohem is None)
         if weight is not None and target is not None:
             weight = class_weight_table(weight, target.device)
-        self.new = (target, int(ignore_index), flag, weight, focal_gamma, label_smoothing) if ok else None
+        self.new = (target, int(ignore_index), flag, weight, focal_gamma, label_smoothing, dice is not None) if ok else None
 
     def __enter__(self):
         global _logits_target
@@ -1537,9 +1638,9 @@ class _ConvT2x2(torch.autograd.Function):
         lt = _logits_target if holder is not None else None
         if (lt is not None and tuple(lt[0].shape) == (N, 2 * H, 2 * W) and lt[0].device == x.device
                 and query('dsrl_convt2x2_fwd_ce_supported', x.data_ptr(), y.data_ptr(), N, H, W, Ci, Co)):       # (pointer arguments: not memoised)
-            tgt, ign, flag, wt, gamma, eps = lt
-            if wt is not None or gamma > 0.0 or eps > 0.0:
-                wt = _focal_args(wt, gamma, x.device, Co, eps)[0]           # (a table of another class count: ValueError)
+            tgt, ign, flag, wt, gamma, eps, diced = lt
+            if wt is not None or gamma > 0.0 or eps > 0.0 or diced:
+                wt = _focal_args(wt, gamma, x.device, Co, eps, True if diced else None)[0]           # (a table of another class count: ValueError)
             sfx, extra = _ce_variant(wt, gamma, eps)
             holder.value = torch.empty(8, device=x.device, dtype=torch.float32)
             holder.value_key = (tgt.data_ptr(), ign, flag.data_ptr(), 0 if wt is None else wt.data_ptr(), eps, gamma)
@@ -1564,8 +1665,9 @@ class _ConvT2x2(torch.autograd.Function):
         h = ctx.holder
         hand = None
         if h is not None and h.armed:           # the loss left d(CE)/d(logits) to this layer: take it over, and disarm the holder whatever happens next
-            hand = (h.y, h.target, int(h.ignore_index), h.count, h.ft, h.weight, h.gamma, h.eps)
+            hand = (h.y, h.target, int(h.ignore_index), h.count, h.ft, h.weight, h.gamma, h.eps, h.dice)
             h.armed = False; h.ft = None; h.target = None; h.count = None; h.y = None; h.value = None; h.weight = None; h.gamma = 0.0; h.eps = 0.0
+            h.dice = None
         fused = dy is None and hand is not None
         if dy is None and not fused:
             raise DsrlHipError('conv_transpose2d_k2s2: backward reached without a gradient for the output')
@@ -1573,9 +1675,9 @@ class _ConvT2x2(torch.autograd.Function):
             dy = pm_dense(dy)
         if hand is not None and not fused:
             # another consumer of the logits sent a gradient too (it is not the loss's: fused_losses returned none): d(CE)/d(logits) and the
-            # transformer's term are written as the unfused step writes them (dsrl_ce_fused, dsrl_pointwise_strided_bwd(accumulate = 1)), dy is
-            # added as autograd would add it, and the plain backward below takes the sum
-            y, target, ign, _, ft, wt, gamma, eps = hand
+            # transformer's term are written as the unfused step writes them (dsrl_ce_fused, dsrl_dice_bwd(accumulate = 1) when the loss has a Dice
+            # term, dsrl_pointwise_strided_bwd(accumulate = 1)), dy is added as autograd would add it, and the plain backward below takes the sum
+            y, target, ign, _, ft, wt, gamma, eps, dice_rec = hand
             P = N * 4 * H * W
             dl = new_cl((N, Co, 2 * H, 2 * W), x)
             scal = torch.empty(8, device=x.device, dtype=torch.float32)
@@ -1583,6 +1685,8 @@ class _ConvT2x2(torch.autograd.Function):
             wsc = _ws(cquery(f'dsrl_ce_fused{sfx}_workspace_bytes', P), x)
             call('dsrl_ce_fused' + sfx, y.data_ptr(), Co, target.data_ptr(), P, Co, ign, *extra, dl.data_ptr(), Co, scal.data_ptr(), None,
                  wsc.data_ptr(), wsc.numel(), _stream())
+            if dice_rec is not None:
+                call('dsrl_dice_bwd', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, dice_rec.data_ptr(), 1, dl.data_ptr(), Co, _stream())
             if ft is not None:
                 ft_g, ft_w, ft_s = ft
                 dwf = torch.empty(Co, device=x.device, dtype=torch.float32)          # the transformer's weight gradient was delivered by its own backward
@@ -1597,9 +1701,11 @@ class _ConvT2x2(torch.autograd.Function):
         db = (bsink if bsink is not None else torch.empty(Co, device=x.device, dtype=torch.float32)) if ctx.has_bias else None
         ws = _ws(cquery('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, Ci, Co), x)
         if fused:
-            y, target, ign, count, ft, wt, gamma, eps = hand
+            y, target, ign, count, ft, wt, gamma, eps, dice_rec = hand
             ft_g, ft_w, ft_s = ft if ft is not None else (None, None, 0)
             sfx, extra = _ce_variant(wt, gamma, eps)
+            if dice_rec is not None:            # the weighted row plus the Dice row (never with gamma or eps: _dice_args)
+                sfx, extra = '_d', (wt.data_ptr(), dice_rec.data_ptr())
             call('dsrl_convt2x2_bwd_ce' + sfx, x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, *extra, count.data_ptr() + 4,
                  None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
                  dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
@@ -1745,18 +1851,22 @@ class _CrossEntropy(torch.autograd.Function):
         return dl, None, None, None, None, None
 
 
-def cross_entropy(logits, target, ignore_index=255, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None):
+def cross_entropy(logits, target, ignore_index=255, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None, dice=None):
     """nn.CrossEntropyLoss(weight, ignore_index, label_smoothing=) with mean reduction; target (N,H,W) uint8/long; weight: None, one number per
     class, or a class_weight_table.  focal_gamma > 0: the focal loss sum w[t] (1 - p_t)^gamma (-log p_t) / sum w[t]; 0 changes
     nothing.  label_smoothing in (0, 1]: torch's smoothed loss, with one deviation: a class of weight 0 adds nothing to the
     smoothing sum even where its -log p is +inf (torch forms 0 * inf = NaN there); 0 changes nothing; together with focal_gamma > 0: ValueError.
     ohem (ohem_value: None, True, (thresh, min_kept) or a mapping): online hard example mining - the loss of ohem_target's rewritten target, with or
-    without weights (the selection is on the unweighted probability); together with focal_gamma > 0 or label_smoothing > 0: ValueError."""
+    without weights (the selection is on the unweighted probability); together with focal_gamma > 0 or label_smoothing > 0: ValueError.
+    dice (dice_value: None, True, a weight, (weight, smooth) or a mapping): adds weight * L_dice (dice_loss) to the CE, with or
+    without class weights; together with focal_gamma > 0, label_smoothing > 0 or ohem: ValueError."""
+    dice = _dice_args(dice, focal_gamma_value(focal_gamma), label_smoothing_value(label_smoothing), ohem_value(ohem))
     weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, logits.device, logits.shape[1], label_smoothing)
     ohem = _ohem_args(ohem, focal_gamma, label_smoothing, ignore_index)
     if ohem is not None:
         target = ohem_target(logits, target, ignore_index, *ohem)
-    return _CrossEntropy.apply(logits, target, ignore_index, weight, focal_gamma, label_smoothing)
+    ce =_CrossEntropy.apply(logits, target, ignore_index, weight, focal_gamma, label_smoothing)
+    return ce if dice is None else ce + _DiceLoss.apply(logits, target, int(ignore_index), dice)
 
 
 class _MSE(torch.autograd.Function):
@@ -1793,7 +1903,7 @@ class _FusedLosses(torch.autograd.Function):
     its incoming gradient is 1 (TrainStep calls vals[3].backward()); the stored gradients are returned as they are."""
 
     @staticmethod
-    def forward(ctx, sssr, sisr, ft1, ft2, target, org, ignore_index, w1, w2, stage, flag, k, weight=None, gamma=0.0, eps=0.0):
+    def forward(ctx, sssr, sisr, ft1, ft2, target, org, ignore_index, w1, w2, stage, flag, k, weight=None, gamma=0.0, eps=0.0, dice=None):
         want = bool(ctx.needs_input_grad[0])          # forward-only (validation, no_grad): no gradient buffers are written
         logits, ld = pm(sssr)
         _need_gpu(target)
@@ -1820,6 +1930,16 @@ class _FusedLosses(torch.autograd.Function):
             ws = _ws(cquery(f'dsrl_ce_fused{sfx}_workspace_bytes', P), logits)
             call('dsrl_ce_fused' + sfx, logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), *extra,
                  None if dl is None else dl.data_ptr(), Cc, scal.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        ce_ptr = scal.data_ptr()
+        rec = None
+        if dice is not None:
+            # the Dice term: one more pass over the logits leaves the record, its value joins the CE in the slot the mix reads, and
+            # without a hand-over its row is added to d(CE)/d(logits) here - before any transformer contribution, as the fused backward orders them
+            rec = _dice_record(logits, ld, target, P, Cc, ignore_index, dice, flag)
+            ce_dice = scal[0:1] + rec[0:1]
+            ce_ptr = ce_dice.data_ptr()
+            if dl is not None:
+                call('dsrl_dice_bwd', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), rec.data_ptr(), 1, dl.data_ptr(), Cc, st)
         da = None
         mse_ptr = fa_ptr = None
         ctx.fa = None
@@ -1846,9 +1966,10 @@ class _FusedLosses(torch.autograd.Function):
                  ws3.data_ptr(), ws3.numel(), st)
             fa_ptr = fa_out.data_ptr()
             ctx.fa = (ft1, ft2, saved, k, fa_out)
-        call('dsrl_loss_mix', scal.data_ptr(), mse_ptr, fa_ptr, float(w1), float(w2), flag.data_ptr(), vals.data_ptr(), st)
+        call('dsrl_loss_mix', ce_ptr, mse_ptr, fa_ptr, float(w1), float(w2), flag.data_ptr(), vals.data_ptr(), st)
         if lg is not None:
             lg.target = target; lg.ignore_index = int(ignore_index); lg.count = scal; lg.ft = None; lg.weight = weight; lg.gamma = gamma; lg.eps = eps; lg.armed = True
+            lg.dice = rec
         ctx.lg = lg
         ctx.grads = (dl, da)
         ctx.w2 = float(w2)
@@ -1888,7 +2009,7 @@ class _FusedLosses(torch.autograd.Function):
             if slot is not None and buf is not None and not slot.closed and slot.buf is None:
                 slot.buf = buf
                 out[i] = None
-        return out[0], out[1], d1, d2, None, None, None, None, None, None, None, None, None, None, None
+        return out[0], out[1], d1, d2, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 _fused_losses_root_checked = False
@@ -1921,22 +2042,26 @@ def fused_losses_backward(vals):
 
 
 def fused_losses(outs, target, input_org, ignore_index, w1, w2, stage, flag, subsample_factor=8, weight=None, focal_gamma=0.0, label_smoothing=0.0,
-                 ohem=None):
+                 ohem=None, dice=None):
     """-> 5-float device tensor [CE, w1*MSE, w2*FA, total, NaN flag]; `outs` = DSRL.forward's 4-tuple.  vals[3].backward() is the only
     supported backward (the function is the root of the pass); `flag` is the int32 NaN flag the fused kernels OR into.  weight: per-class CE
     weights (None, one number per class, or a class_weight_table): nn.CrossEntropyLoss(weight=).  focal_gamma > 0 makes the CE term the focal loss
     (as cross_entropy); 0 changes nothing.  label_smoothing in (0, 1] makes it torch's label-smoothed loss (as cross_entropy); 0 changes nothing.
     ohem (as cross_entropy) mines the hard pixels first: the target is rewritten on the device (ohem_target, which ORs into `flag` too) and
-    everything after it - the loss pass, the hand-over to the layer that produced the logits - runs on the rewritten target as it stands."""
+    everything after it - the loss pass, the hand-over to the layer that produced the logits - runs on the rewritten target as it stands.
+    dice (as cross_entropy) adds the soft Dice term lambda L_dice of this call's pixels: vals[0] = CE + lambda L_dice and vals[3] includes it; the
+    gradient of the term is added to d(CE)/d(logits), inside the ConvTranspose backward when the hand-over engages (dsrl_convt2x2_bwd_ce_d).  The CE
+    then runs on the weighted kernels (all-ones weights when `weight` is None); not together with focal_gamma > 0, label_smoothing > 0 or ohem."""
     sssr, sisr, ft1, ft2 = outs
-    weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, sssr.device, sssr.shape[1], label_smoothing)
+    dice = _dice_args(dice, focal_gamma_value(focal_gamma), label_smoothing_value(label_smoothing), ohem_value(ohem))
+    weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, sssr.device, sssr.shape[1], label_smoothing, dice)
     ohem = _ohem_args(ohem, focal_gamma, label_smoothing, ignore_index)
     if ohem is not None:
         target = ohem_target(sssr, target, ignore_index, *ohem, flag=flag)
     dummy = _const1(0.0, sssr.device)            # stands in for the outputs a lower stage does not have (a cached constant: no fill launch per step)
     return _FusedLosses.apply(sssr, sisr if stage > 1 else dummy, ft1 if stage > 2 else dummy, ft2 if stage > 2 else dummy, target,
                               input_org if stage > 1 else dummy, int(ignore_index), float(w1), float(w2), int(stage), flag, int(subsample_factor), weight,
-                              focal_gamma, label_smoothing)
+                              focal_gamma, label_smoothing, dice)
 
 
 _RED = {'mean': 0, 'sum': 1, 'none': 2}

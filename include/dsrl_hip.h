@@ -540,6 +540,38 @@ int dsrl_ohem_apply(const float* p, const uint8_t* target, int64_t P, int ignore
 int dsrl_ohem_target(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float thresh, int64_t min_kept,
                      uint8_t* target_out, uint32_t* stats /*[4]*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
 
+/* Soft Dice loss term beside the cross entropy: loss = CE + lambda L_dice.  A pixel is live when its label is neither ignore_index
+ * nor >= C; p_ic = e_ic (1 / s_i) is its softmax with the terms of the CE kernels (m = max, e_c = exp(v_c - m), s = sum e_c with c ascending).  Over
+ * the live pixels of the call:
+ *     I_c = sum_i p_ic [t_i == c]     P_c = sum_i p_ic     G_c = sum_i [t_i == c]  (integer)     den_c = P_c + G_c + smooth
+ *     K = {c : G_c > 0}     L_dice = 1 - (1 / |K|) sum_{c in K} (2 I_c + smooth) / den_c          (K empty: L_dice = 0 and every coefficient 0)
+ *     a_c = -(lambda / |K|) 2 / den_c     b_c = (lambda / |K|) (2 I_c + smooth) / den_c^2          (c not in K: 0)
+ *     d(lambda L_dice) / d v_ik = live_i p_ik (g_ik - sum_j p_ij g_ij),   g_ij = b_j + a_j [j == t_i]       (sum over j ascending)
+ * The mean is over the classes PRESENT in the call; an absent class adds nothing.
+ *   dsrl_dice_fwd  one pass over the logits (ld >= C; 16-byte loads when ld == C and the base is 16-byte aligned) leaves partial sums per chunk of
+ *                  pixels (I_c, P_c in double, G_c in integers; the pixel -> chunk mapping depends on P alone), a one-block finish adds them in
+ *                  a fixed ascending order (the chunks of each group of 64, then the groups) and writes record[128] = {lambda L_dice, |K|, a[0..C), b[0..C), zeros}, the coefficients formed in double
+ *                  and rounded once.  No float atomics: the same bits on every call.  A NaN logit in a live pixel ORs 1 into nan_flag and makes the
+ *                  value NaN.  After the call ws begins with the totals {double I[64], double P[64], uint32 G[64]}.
+ *                  ws: >= dsrl_dice_workspace_bytes(P) (depends on P alone; 0, with a message, for P <= 0 or P >= 2^31 - 256), 8-byte aligned.
+ *   dsrl_dice_bwd  dlogits[i][k] = the row above from the logits and the record (accumulate = 0), or dlogits + row (accumulate = 1, one fp32
+ *                  addition per element; a pixel that is not live adds +0).
+ *   dsrl_convt2x2_bwd_ce_d  dsrl_convt2x2_bwd_ce_w with the Dice row added to the weighted CE row inside the kernel (all-ones weights for an
+ *                  unweighted CE): bit-identical to dsrl_ce_fused_w -> dsrl_dice_bwd(accumulate = 1) -> dsrl_pointwise_strided_bwd(accumulate = 1)
+ *                  -> dsrl_convt2x2_bwd.  Same contract and workspace as the _w entry point.
+ * Everything runs on the stream with no host read: the calls can be captured.  Argument errors (DSRL_E_BADARG before any HIP call, nothing written):
+ * null pointers, P <= 0 or >= 2^31 - 256, C outside 1..60, ld or lddl < C, lambda not a finite number > 0, smooth not a finite number >= 0,
+ * accumulate not 0 or 1; a workspace too small or misaligned is DSRL_E_WORKSPACE. */
+size_t dsrl_dice_workspace_bytes(int64_t P);
+int dsrl_dice_fwd(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float lambda, float smooth,
+                  float* record /*[128]*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+int dsrl_dice_bwd(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* record /*[128]*/, int accumulate,
+                  float* dlogits, int lddl, dsrl_stream_t stream);
+int dsrl_convt2x2_bwd_ce_d(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* weights /*[256]*/,
+                           const float* dice_record /*[128]*/, const float* ce_wsum /*D: loss_out + 1*/, const float* ft_g /*nullable*/,
+                           const float* ft_w /*nullable*/, int ft_stride, float* dx, float* dw, float* dbias /*nullable*/, int N, int H, int W, int Cin,
+                           int Cout, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+
 /* FALoss (models/losses/FALoss.py:8-34). fm1/fm2 are (B,C,H,W) with element strides (sb,sc,sh,sw).
  * reduction: 0 mean, 1 sum, 2 none (out has B*C*n*n floats, n = (W/k)^2).
  * `saved` (>= dsrl_fa_saved_floats) carries S1,S2,sigma,u1,v1 to the backward. */

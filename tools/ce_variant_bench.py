@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Cost of one cross-entropy variant at the step's shape (N = 8, tail input 256 x 512, 19 -> 19), written to profiles/<variant>_ce.txt
-(class_weighted_ce.txt, focal_ce.txt, label_smoothing_ce.txt, ohem_ce.txt):
+(class_weighted_ce.txt, focal_ce.txt, label_smoothing_ce.txt, ohem_ce.txt, dice_ce.txt):
   * kernel-only times through the C ABI, HIP events around back-to-back launches, the variant's entry points against their base:
       weighted   dsrl_convt2x2_fwd_ce_w, dsrl_convt2x2_bwd_ce_w and dsrl_ce_fused_w against the unweighted calls, and the D pre-pass alone
                  (dsrl_ce_weight_sum: label histogram + weight sum);
@@ -8,10 +8,12 @@
       smoothed   the same four _s paths against their _w siblings, eps = 0.1;
       ohem       dsrl_ohem_prob beside dsrl_ce_fused on the same logits (time and bytes per second), dsrl_ohem_select, dsrl_ohem_apply and the whole
                  dsrl_ohem_target, thresh = 0.7, min_kept = 100000;
+      dice       dsrl_dice_fwd beside dsrl_copy2d on as many bytes, dsrl_ohem_prob on the same logits and the torch composition (softmax, one-hot,
+                 sums); dsrl_dice_bwd; dsrl_convt2x2_bwd_ce_d against dsrl_convt2x2_bwd_ce_w on the same inputs; five windows each, lambda = smooth = 1;
   * the replayed training step (stage 3, batch 8, 256 x 512 input, hipGraph): default, class weights and (focal, smoothed) class weights + gamma
-    or eps, alternating in one process (ohem: default against ohem = (0.7, 100000)).
+    or eps, alternating in one process (ohem: default against ohem = (0.7, 100000); dice: default, class weights, class weights + dice = True).
 Everything in that file from the line '## recorded beside the tool' on is kept as it is.
-Usage: python tools/ce_variant_bench.py weighted|focal|smoothed|ohem [--steps K] [--no-step] [VAR=value ...]"""
+Usage: python tools/ce_variant_bench.py weighted|focal|smoothed|ohem|dice [--steps K] [--no-step] [VAR=value ...]"""
 import os
 import sys
 import time
@@ -32,7 +34,8 @@ from dualsuperreslearningforsemseg_amd._lib import call, query                  
 VARIANTS = {'weighted': ('_w', '', None, None, 'weighted', None, 'class_weighted_ce.txt'),
             'focal': ('_f', '_w', 2.0, 'gamma', 'focal', 'focal_gamma', 'focal_ce.txt'),
             'smoothed': ('_s', '_w', 0.1, 'eps', 'smoothed', 'label_smoothing', 'label_smoothing_ce.txt'),
-            'ohem': ('', '', (0.7, 100000), 'ohem', 'ohem', 'ohem', 'ohem_ce.txt')}
+            'ohem': ('', '', (0.7, 100000), 'ohem', 'ohem', 'ohem', 'ohem_ce.txt'),
+            'dice': ('_d', '_w', (1.0, 1.0), 'dice', 'dice', 'dice', 'dice_ce.txt')}
 if not args or args[0] not in VARIANTS:
     sys.exit(__doc__)
 VARIANT = args[0]
@@ -175,6 +178,65 @@ def ohem_kernels():
         say(f'  {label:<78} {t[key]:7.1f}   {nbytes / 1e6:6.1f} MB   {nbytes / t[key] / 1e6:5.2f} TB/s')
 
 
+def dice_kernels():
+    N, H, W, C = 8, 256, 512, 19
+    P = N * 4 * H * W
+    lam, smooth = PARAM
+    rs = np.random.RandomState(1)
+    y = torch.randn(N, 2 * H, 2 * W, C, device=dev) * 3
+    top = y.argmax(dim=-1).to(torch.uint8)
+    tg = torch.randint(0, C, (N, 2 * H, 2 * W), device=dev, dtype=torch.uint8)
+    tg = torch.where(torch.rand(tg.shape, device=dev) < 0.5, top, tg)
+    tg[torch.rand(tg.shape, device=dev) < 0.1] = 255
+    x = torch.randn(N, H, W, C, device=dev); w = torch.randn(C, C, 2, 2, device=dev) * 0.2
+    wt = HF.class_weight_table(rs.uniform(0.25, 8.0, C), dev)
+    dx = torch.empty_like(x); dw = torch.empty_like(w); db = torch.empty(C, device=dev); dl = torch.zeros_like(y)
+    scal = torch.zeros(8, device=dev); flag = torch.zeros(1, dtype=torch.int32, device=dev); rec = torch.zeros(128, device=dev)
+    ftg = torch.randn(N, H // 4, W // 4, device=dev); ftw = torch.randn(C, device=dev)
+    p = torch.empty(P, device=dev)
+    st = HF._stream()
+    wb = torch.empty(query('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, C, C), dtype=torch.uint8, device=dev)
+    wsd = torch.empty(query('dsrl_dice_workspace_bytes', P), dtype=torch.uint8, device=dev)
+    wsf = torch.empty(query('dsrl_ce_fused_w_workspace_bytes', P), dtype=torch.uint8, device=dev)
+    call('dsrl_ce_fused_w', y.data_ptr(), C, tg.data_ptr(), P, C, 255, wt.data_ptr(), None, C, scal.data_ptr(), flag.data_ptr(), wsf.data_ptr(), wsf.numel(), st)
+
+    def torch_dice():
+        live = tg != 255
+        pr = torch.softmax(y, dim=-1)[live]
+        oh = torch.nn.functional.one_hot(tg[live].long(), C).float()
+        I, Pc, G = (pr * oh).sum(0), pr.sum(0), oh.sum(0)
+        present = G > 0
+        return lam * (1 - ((2 * I + smooth) / (Pc + G + smooth))[present].sum() / present.sum())
+
+    def bwd(s, extra):
+        call('dsrl_convt2x2_bwd_ce' + s, x.data_ptr(), w.data_ptr(), y.data_ptr(), tg.data_ptr(), 255, *extra, scal.data_ptr() + 4, ftg.data_ptr(),
+             ftw.data_ptr(), 8, dx.data_ptr(), dw.data_ptr(), db.data_ptr(), N, H, W, C, C, wb.data_ptr(), wb.numel(), st)
+
+    lb = P * C * 4
+    rows = [('dsrl_dice_fwd (dice_sums_kernel + dice_finish_kernel)', lb + P,
+             lambda: call('dsrl_dice_fwd', y.data_ptr(), C, tg.data_ptr(), P, C, 255, lam, smooth, rec.data_ptr(), flag.data_ptr(), wsd.data_ptr(), wsd.numel(), st)),
+            ('dsrl_copy2d, half the logits: as many bytes read + written', lb,
+             lambda: call('dsrl_copy2d', y.data_ptr(), C, dl.data_ptr(), C, P // 2, C, st)),
+            ('dsrl_ohem_prob on the same logits', lb + P + 4 * P,
+             lambda: call('dsrl_ohem_prob', y.data_ptr(), C, tg.data_ptr(), P, C, 255, p.data_ptr(), flag.data_ptr(), st)),
+            ('torch: softmax, one-hot, sums', 0, torch_dice),
+            ('dsrl_dice_bwd, accumulate = 1', 3 * lb + P,
+             lambda: call('dsrl_dice_bwd', y.data_ptr(), C, tg.data_ptr(), P, C, 255, rec.data_ptr(), 1, dl.data_ptr(), C, st))]
+    for waves in ('12', '8'):
+        rows.append((f'dsrl_convt2x2_bwd_ce_w (DSRL_CONVT_CE_WAVES={waves})', 0, lambda waves=waves: (os.environ.__setitem__('DSRL_CONVT_CE_WAVES', waves), bwd('_w', (wt.data_ptr(),)))))
+    rows.append(('dsrl_convt2x2_bwd_ce_d (8 waves)', 0, lambda: bwd('_d', (wt.data_ptr(), rec.data_ptr()))))
+    say(f'kernel-only, us per call (N = {N}, tail input {H} x {W}, {P} pixels, {lb / 1e6:.0f} MB of logits; lambda = {lam}, smooth = {smooth}; five windows of 20')
+    say('back-to-back calls each: min / median / max of the windows; bytes and rate at the median):')
+    for label, nbytes, f in rows:
+        wins = sorted(timeit(f) for _ in range(5))
+        rate = f'   {nbytes / 1e6:6.1f} MB   {nbytes / wins[2] / 1e6:5.2f} TB/s' if nbytes else ''
+        say(f'  {label:<62} {wins[0]:7.1f} / {wins[2]:7.1f} / {wins[4]:7.1f}{rate}')
+    os.environ.pop('DSRL_CONVT_CE_WAVES', None)
+    torch.cuda.synchronize()
+    r = rec.cpu().numpy()
+    say(f'  this batch: lambda L_dice = {r[0]:.6f}, |K| = {int(r[1])}, torch composition {float(torch_dice()):.6f}')
+
+
 def replayed_step():
     import dualsuperreslearningforsemseg_amd as D
     from dualsuperreslearningforsemseg_amd import settings
@@ -203,10 +265,12 @@ def replayed_step():
         kinds = {'unweighted': {}, 'weighted': {'class_weights': w}}
     elif VARIANT == 'ohem':
         kinds = {'default': {}, 'ohem': {'ohem': PARAM}}
+    elif VARIANT == 'dice':
+        kinds = {'default': {}, 'weighted': {'class_weights': w}, 'dice': {'class_weights': w, 'dice': PARAM}}
     else:
         kinds = {'default': {}, 'weighted': {'class_weights': w}, WORD: {'class_weights': w, STEP_KW: PARAM}}
     res, replays = {k: [] for k in kinds}, {}
-    for _ in range(2):                          # one captured step at a time (the device-resident dropout key has one binding): build, warm, time, release
+    for _ in range(3 if VARIANT == 'dice' else 2):      # one captured step at a time (the device-resident dropout key has one binding): build, warm, time, release
         for k, kw in kinds.items():
             s = TrainStep(model, flat, 3, 0.1, 1.0, cs.IGNORE_CLASS_LABEL, **kw)
             run(s, s.GRAPH_WARMUP + 6)
@@ -217,7 +281,7 @@ def replayed_step():
             res[k].append((time.perf_counter() - t0) / STEPS * 1e3)
             replays[k] = s.graph_replays
             s.release()
-    say(f'replayed step (stage 3, batch 8, 256 x 512, {STEPS} steps per figure, two alternating rounds in one process), ms per step:')
+    say(f'replayed step (stage 3, batch 8, 256 x 512, {STEPS} steps per figure, {len(next(iter(res.values())))} alternating rounds in one process), ms per step:')
     width = 11 if VARIANT == 'weighted' else 9
     for k in res:
         say(f'  {k:<{width}} ' + '  '.join(f'{v:.3f}' for v in res[k]) + f'   min {min(res[k]):.3f}  (replays {replays[k]})')
@@ -230,7 +294,7 @@ def replayed_step():
             f"{(min(res[WORD]) - min(res['default'])) * 1e3:+.0f} us")
 
 
-ohem_kernels() if VARIANT == 'ohem' else kernels()
+ohem_kernels() if VARIANT == 'ohem' else dice_kernels() if VARIANT == 'dice' else kernels()
 if '--no-step' not in args:
     replayed_step()
 out = os.path.join(ROOT, 'profiles', OUT)
