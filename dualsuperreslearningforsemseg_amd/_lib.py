@@ -200,6 +200,11 @@ PROTOTYPES = {
     'dsrl_ema_advance': (i32, [fp, stream_t]),
     'dsrl_arena_swap': (i32, [fp, fp, i64, stream_t]),
     'dsrl_nan_check': (i32, [fp, i64, fp, stream_t]),
+    'dsrl_sssr_tail_predict_ex': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, fp, fp, i32, fp, stream_t]),
+    'dsrl_sssr_tail_predict_flip_ex': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, fp, fp, i32, fp, stream_t]),
+    'dsrl_prob_merge_finish_ex': (i32, [fp, i32] + [i32] * 5 + [fp, i32, i32, i32, fp, fp, i32, fp, fp, fp, fp, sz, fp, fp, i32, fp, stream_t]),
+    'dsrl_calibration_max_bins': (i32, []),
+    'dsrl_calibration_from_logits': (i32, [fp, i32, fp, i64, i32, i32, i32, fp, fp, fp, stream_t]),
     'dsrl_sr_quality_workspace_bytes': (sz, [i32] * 4),
     'dsrl_sr_quality': (i32, [fp, i32, fp, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), fp, fp, fp, sz, stream_t]),
     'dsrl_boundary_counts_max_classes': (i32, []),

@@ -21,6 +21,12 @@ any device work): the SISR branch has no ensemble, and compiled files are stage-
 anyway - also goes to `functional.boundary_counts_`, and the Boundary IoU counters (metrices.BoundaryIoU) ride in the same single read: the result
 gains 'mBIoU_dataset' and 'BIoU_per_class', the per-class table of benchmark.txt a column and the file one summary line.  Combines with `flip`,
 `scales`, `compiled_model`, `ema` and `sisr`; anything but True, False, None or a finite number > 0 is a ValueError before any device work.
+`calibration=True` (15 bins) or a bin count in other_args: the kernel that writes every batch's class map also fills ONE reliability record over
+the split (metrices.Calibration: the maximum softmax probability of every counted pixel binned against whether its class was right), which rides in
+the same single read: the result gains 'ECE', 'MCE', 'mean_confidence' (fractions in [0, 1]) and 'reliability' (per bin: n, acc, conf),
+benchmark.txt a reliability table and one summary line.  Combines with `flip`, `scales`, `ema`, `boundary` and `sisr`, not with `compiled_model`
+(graphs are keyed on their outputs); anything but True, False, None or an integer from 1 to functional.calibration_max_bins() is a ValueError
+before any device work.
 Beside the reference's per-batch figures the command accumulates ONE confusion matrix over the split on the device (the kernel that writes the
 class map fills it; it comes back in the same single read) and reports the dataset-level figures from it - intersections and unions summed over the
 split, then IoU per class, then the mean over the classes, as Cityscapes results are published - with a per-class table in benchmark.txt and the
@@ -34,8 +40,9 @@ import torch as t
 
 from .. import settings
 from .._lib import DsrlHipError
-from ..functional import boundary_counts_, boundary_distance, multiscale_scales_value, multiscale_sizes, nan_check_
-from ..metrices import Accuracy, AverageMeter, BoundaryIoU, ConfusionMatrix, SRQuality, mIoU
+from ..functional import (CALIBRATION_DEFAULT_BINS, boundary_counts_, boundary_distance, calibration_bins_value, multiscale_scales_value,
+                          multiscale_sizes, nan_check_)
+from ..metrices import Accuracy, AverageMeter, BoundaryIoU, ConfusionMatrix, SRQuality, calibration_figures, mIoU
 from ..models import DSRL
 from ..utils import load_checkpoint_or_weights
 from .train_or_resume import isCUDAdevice
@@ -82,9 +89,22 @@ def boundary_ratio_value(value):
     raise ValueError(f'benchmark: boundary = {value!r} is neither True nor a positive ratio of the image diagonal')
 
 
+def calibration_bins_arg(value):
+    """other_args['calibration'] -> the bin count, or None when the key is absent or off: True is 15 bins, an integer from 1 to
+    functional.calibration_max_bins() is itself; anything else is a ValueError"""
+    if value is None or value is False:
+        return None
+    if value is True:
+        return CALIBRATION_DEFAULT_BINS
+    return calibration_bins_value(value, 'benchmark: calibration')
+
+
 def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
     scales = multiscale_scales_value(other_args.get('scales'))          # ValueError on a bad value, before any device work
     boundary = boundary_ratio_value(other_args.get('boundary'))
+    cal_bins = calibration_bins_arg(other_args.get('calibration'))
+    if cal_bins is not None and other_args.get('compiled_model'):
+        raise ValueError('benchmark: calibration does not combine with compiled_model (compiled graphs are keyed on their outputs)')
     sisr = bool(other_args.get('sisr'))
     if sisr:
         clash = [k for k, on in (('flip', other_args.get('flip')), ('scales', scales is not None), ('compiled_model', other_args.get('compiled_model'))) if on]
@@ -119,16 +139,19 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
     quality = SRQuality(ds.MEAN, ds.STD) if sisr else None
     band_counts = t.zeros(3 * nc, dtype=t.int64, device=device_obj) if boundary is not None else None
     band_distances = []
+    cal_record = t.zeros(3 * cal_bins, dtype=t.int64, device=device_obj) if cal_bins is not None else None
+    cal_kw = {} if cal_record is None else {'calibration': cal_record}          # without the key: the calls of a command that does not know it
     try:
         for (input_image, input_org), (target, _) in loader:
             if sisr:
                 with t.no_grad():       # DSRL.predict with the trunk's features kept for the other branch
                     nan_check_(nan_flag, input_image)
                     features = model.feature_extractor['backbone'](input_image)
-                    pred, counts, ce = model.predict_head(*features, target, ds.IGNORE_CLASS_LABEL, nan_flag, False, confusion)
+                    pred, counts, ce = model.predict_head(*features, target, ds.IGNORE_CLASS_LABEL, nan_flag, False, confusion, **cal_kw)
                     quality.update(model.super_resolve_head(*features), input_org)
             else:
-                pred, counts, ce = predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag, flip=flip, confusion=confusion)
+                pred, counts, ce = predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag, flip=flip, confusion=confusion,
+                                          **cal_kw)
             if boundary is not None:
                 boundary_counts_(band_counts, pred, target, nc, ds.IGNORE_CLASS_LABEL, ratio=boundary, nan_flag=nan_flag)
                 band_distances.append(boundary_distance(pred.shape[-2], pred.shape[-1], boundary))
@@ -143,6 +166,10 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
             parts.append(band_counts.double())
         if sisr:
             parts += [b[0].reshape(-1) for b in quality.batches]
+        if cal_record is not None:
+            # n and hit are < 2^53; q (a sum of up to 2^24 per pixel) travels as its high and low 24-bit halves, each exact in float64
+            q = cal_record[2 * cal_bins:]
+            parts += [cal_record[:2 * cal_bins].double(), (q >> 24).double(), (q & 0xffffff).double()]
         host = t.cat(parts).cpu()
     finally:
         if predictor is not None:
@@ -197,6 +224,21 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
         result.update({'PSNR': sr['PSNR'], 'SSIM': sr['SSIM']})
         lines += ['Super-resolved image against the original, mean over {:d} images, PSNR dB: {:.2f}'.format(sr['images'], sr['PSNR']),
                   'Super-resolved image against the original, mean over {:d} images, SSIM: {:.4f}'.format(sr['images'], sr['SSIM'])]
+    if cal_record is not None:
+        B = cal_bins
+        rec = host[at:at + 4 * B].to(t.int64)
+        at += 4 * B
+        cfig = calibration_figures(t.cat([rec[:2 * B], (rec[2 * B:3 * B] << 24) + rec[3 * B:]]))
+        result.update({'ECE': cfig['ECE'], 'MCE': cfig['MCE'], 'mean_confidence': cfig['mean_confidence'],
+                       'reliability': {'n': [int(v) for v in cfig['bins']['n']], 'acc': [float(v) for v in cfig['bins']['acc']],
+                                       'conf': [float(v) for v in cfig['bins']['conf']]}})
+        lines += ['', 'Reliability of the maximum softmax probability, {:d} bins over {:d} pixels'.format(B, cfig['pixels']),
+                  '{:>15s}  {:>12s}  {:>10s}  {:>12s}'.format('confidence bin', 'pixels', 'accuracy', 'confidence')]
+        lines += ['[{:5.3f}, {:5.3f}{:s}  {:>12d}  {:>10.4f}  {:>12.4f}'.format(b / B, (b + 1) / B, ']' if b == B - 1 else ')', int(n), a, c)
+                  for b, (n, a, c) in enumerate(zip(cfig['bins']['n'], cfig['bins']['acc'], cfig['bins']['conf']))]
+        lines.append('Expected calibration error: {:.4f}, maximum: {:.4f}, mean confidence: {:.4f} against accuracy {:.4f} ({:s})'.format(
+            cfig['ECE'], cfig['MCE'], cfig['mean_confidence'], cfig['accuracy'],
+            'over-confident' if cfig['gap'] > 0 else 'under-confident' if cfig['gap'] < 0 else 'no gap'))
     print('-------- RESULTS --------')
     for ln in lines:
         print(ln)

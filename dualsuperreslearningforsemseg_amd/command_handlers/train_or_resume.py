@@ -624,11 +624,14 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
                     if stage > 1:           # PSNR and SSIM of the SISR output against the 2x original; reported, nothing is decided from them
                         from ..metrices import SRQuality
                         details['sr_quality'] = SRQuality(ds.MEAN, ds.STD)
+                    from ..metrices import Calibration      # ECE / MCE of the validated model; reported, nothing is decided from them
+                    details['calibration'] = Calibration(ignore_index=step.ignore)
                     with flat.ema_weights() if ema is not None else contextlib.nullcontext():      # the averaged model is the one that is measured
                         rec['val'] = _do_train_val(False, epoch, model, step, val_loader, lr, momentum, weights_decay, False, True, details)
                     rec['val_mIoU_dataset'], rec['val_IoU_per_class'] = rec['val'][6], details['IoU_per_class']
                     if 'sr_quality' in details:
                         rec['val_PSNR'], rec['val_SSIM'] = details['PSNR'], details['SSIM']
+                    rec['val_ECE'], rec['val_MCE'] = details['ECE'], details['MCE']
                     CE_val_avg_loss, MSE_val_avg_loss, FA_val_avg_loss, Avg_val_loss, val_mIoU = rec['val'][:5]
                     if val_mIoU > best_validation_dict['best_miou_percent']:                                        # :318-337
                         best_validation_dict = {'epoch': epoch, 'best_miou_percent': val_mIoU, 'loss': Avg_val_loss}
@@ -671,7 +674,9 @@ def _do_train_val(do_train, epoch, model, step, data_loader, lr, momentum, weigh
     (CE, MSE, FA, Total, mIoU %, accuracy %) and, as a last element, the dataset-level mIoU % (metrices.ConfusionMatrix over the whole loader);
     the last three only for validation.  Everything decided from a validation - best checkpoint, early stopping - uses the reference's per-batch
     mIoU.  `details` (a dict, optional) receives 'IoU_per_class' of the dataset-level figure; a validation that finds a metrices.SRQuality under
-    details['sr_quality'] feeds it every batch's SISR output and original (two launches per batch, one read at the end) and leaves 'PSNR' and 'SSIM'."""
+    details['sr_quality'] feeds it every batch's SISR output and original (two launches per batch, one read at the end) and leaves 'PSNR' and 'SSIM';
+    one that finds a metrices.Calibration under details['calibration'] feeds it the logits validation already has (one launch per batch, one read at
+    the end) and leaves 'ECE' and 'MCE' (fractions in [0, 1])."""
     model.train(mode=do_train)
     if do_train and freeze_batch_norm:
         for m in model.modules():
@@ -684,6 +689,7 @@ def _do_train_val(do_train, epoch, model, step, data_loader, lr, momentum, weigh
     whole = ConfusionMatrix(num_classes=nc, ignore_index=step.ignore)
     whole_fits = nc <= ConfusionMatrix.max_classes_from_logits()        # beyond it the one-pass kernel has no room for the matrix: the figure is NaN
     srq = details.get('sr_quality') if (details is not None and not do_train and is_master_rank) else None
+    cal = details.get('calibration') if (details is not None and not do_train and is_master_rank) else None
     sizes = []
 
     def drain(keep):
@@ -702,6 +708,8 @@ def _do_train_val(do_train, epoch, model, step, data_loader, lr, momentum, weigh
                 whole.update_from_logits(outs[0], target)
             if srq is not None:
                 srq.update(outs[1], input_org)
+            if cal is not None:
+                cal.update_from_logits(outs[0], target)
         drain(1)              # the losses of iteration k are read while iteration k+1 is already queued
     drain(0)
     fig = whole.result() if not do_train else None
@@ -710,5 +718,8 @@ def _do_train_val(do_train, epoch, model, step, data_loader, lr, momentum, weigh
     if srq is not None:
         quality = srq.result()
         details['PSNR'], details['SSIM'] = quality['PSNR'], quality['SSIM']
+    if cal is not None:
+        cfig = cal.result()
+        details['ECE'], details['MCE'] = cfig['ECE'], cfig['MCE']
     return [m() for m in meters] + [miou() if not do_train else 0.0, mean_accuracy() if not do_train else 0.0, fig['mIoU'] if fig is not None else 0.0]
 

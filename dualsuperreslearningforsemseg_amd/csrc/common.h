@@ -219,6 +219,61 @@ struct EmaRecord {
 // Every EMA kernel - fused into an SGD launch or not - goes through this one function, so that the fused and the unfused paths round alike.
 __device__ __forceinline__ float ema_elem(float e, float p_new, float omd) { return fmaf(omd, p_new - e, e); }
 
+// ---------------------------------------------------------------- calibration record and confidence (calibration.hip)
+// Confidence of a pixel: the probability of the class the kernel reports (first maximum), fp32, from values the producer already has:
+//     one softmax (dsrl_calibration_from_logits, the single-view tail):  1 / s, s = sum_c exp_nonpos(v_c - m) with c ascending, m the fmaxf chain from v_0
+//                                                                        (the max term is exp(0) = 1, so s >= 1 and the confidence <= 1)
+//     two views (the flip tail):          half the winning entry of e_a / s_a + e_b / s_b, as the kernel formed it for the arg-max
+//     V views (the multi-scale finish):   min(1, winning sum / V)
+// A NaN stays a NaN in all three (the comparison in confidence_views fails for it).  Bin of a confidence among B equal-width bins: one fp32 multiply
+// (the library is built with -ffp-contract=off), conf = 1 goes to the last bin.  The record is int64 [3 B] = [n_b | hit_b | q_b]: counted pixels,
+// those with pred == target, and the sum of rintf(conf 2^24) as an integer - no float is ever added, so a record does not depend on the order of the
+// additions.  A NaN confidence is counted nowhere.  Per block the three rows are LDS integers (CalBins; q is 64-bit there already: 256 pixels of
+// confidence 1 are 2^32), flushed as one 64-bit atomic per non-zero entry.  Every producer goes through these functions, so that they bin alike.
+constexpr int kCalMaxBins = 64;
+constexpr float kCalQScale = 16777216.f;        // 2^24
+template <int CT>
+__device__ __forceinline__ float softmax_denominator(const float* v, int C) {
+    const int n = CT > 0 ? CT : C;
+    float m = v[0];
+#pragma unroll
+    for (int c = 1; c < n; ++c) m = fmaxf(m, v[c]);
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < n; ++c) s += exp_nonpos(v[c] - m);
+    return s;
+}
+__device__ __forceinline__ float confidence_pixel(float s) { return 1.f / s; }
+__device__ __forceinline__ float confidence_flip(float best_sum) { return 0.5f * best_sum; }
+__device__ __forceinline__ float confidence_views(float best_sum, float views) {
+    const float q = best_sum / views;
+    return q > 1.f ? 1.f : q;
+}
+__device__ __forceinline__ int calibration_bin(float conf, int B) { return min(B - 1, (int)(conf * (float)B)); }
+struct CalBins {
+    unsigned n[kCalMaxBins], hit[kCalMaxBins];
+    unsigned long long q[kCalMaxBins];
+    // every thread of the block; the caller synchronises before the first count
+    __device__ __forceinline__ void clear(int B) {
+        for (int b = threadIdx.x; b < B; b += blockDim.x) { n[b] = 0u; hit[b] = 0u; q[b] = 0ull; }
+    }
+    __device__ __forceinline__ void count(float conf, bool is_hit, int B) {
+        if (!(conf >= 0.f && conf <= 1.f)) return;      // a NaN fails the comparison (every producer's confidence is in [0, 1] otherwise)
+        const int b = calibration_bin(conf, B);
+        atomicAdd(&n[b], 1u);
+        if (is_hit) atomicAdd(&hit[b], 1u);
+        atomicAdd(&q[b], (unsigned long long)rintf(conf * kCalQScale));
+    }
+    // every thread of the block, behind a __syncthreads() that follows the last count
+    __device__ __forceinline__ void flush(unsigned long long* __restrict__ rec, int B) {
+        for (int b = threadIdx.x; b < B; b += blockDim.x) {
+            if (n[b]) atomicAdd(&rec[b], (unsigned long long)n[b]);
+            if (hit[b]) atomicAdd(&rec[B + b], (unsigned long long)hit[b]);
+            if (q[b]) atomicAdd(&rec[2 * B + b], q[b]);
+        }
+    }
+};
+
 // ---------------------------------------------------------------- wave / block reductions
 __device__ inline float wave_sum(float v) {
 #pragma unroll

@@ -166,19 +166,25 @@ __global__ __launch_bounds__(256) void prob_merge_kernel(const float* __restrict
 }
 
 // The last view.  target, counts, part (the loss), nan_flag and cm are nullable (counts, part and cm need a target); lnV = ln(views).
-template <int CT>
+// CAL: the calibration record (common.h: CalBins, in LDS beside cmh; needs a target); CONF: the confidence map beside pred, one float per lane.  The
+// confidence is min(1, winning sum / views) (confidence_views); a NaN pixel is in no bin and NaN in the map.
+template <int CT, bool CAL = false, bool CONF = false>
 __global__ __launch_bounds__(256) void prob_merge_finish_kernel(const float* __restrict__ logits, int ld, int Hs, int Ws, int C, int mirror,
                                                                 const float* __restrict__ acc, int Ho, int Wo, float lnV,
                                                                 unsigned char* __restrict__ pred, const unsigned char* __restrict__ target,
                                                                 int ignore_index, unsigned long long* __restrict__ counts, double* __restrict__ part,
                                                                 int* __restrict__ nan_flag, unsigned long long* __restrict__ cm, int nspans, int XC,
-                                                                int rounds) {
+                                                                int rounds, float fV, unsigned long long* __restrict__ cal, int B,
+                                                                float* __restrict__ conf) {
     __shared__ float stage[4][kMergeStageFloats];
     __shared__ unsigned hist[3 * kMergeMaxC + 2];
     __shared__ unsigned cmh[kMergeMaxC * kMergeMaxC];          // cmh[t * C + p]
     __shared__ double shd[4];
+    __shared__ unsigned long long calraw[CAL ? sizeof(CalBins) / 8 : 1];
+    CalBins& calb = *reinterpret_cast<CalBins*>(calraw);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (CAL) calb.clear(B);         // CAL comes with a target: the barrier below covers it
     if (target != nullptr) {
         for (int t = tid; t < 3 * C + 2; t += 256) hist[t] = 0u;
         if (cm != nullptr)
@@ -210,9 +216,13 @@ __global__ __launch_bounds__(256) void prob_merge_finish_kernel(const float* __r
         }
         bad |= !(total == total);               // a NaN logit of any view made every class of the pixel NaN
         pred[pix] = (unsigned char)best;
+        float cf = 0.f;
+        if (CAL || CONF) cf = confidence_views(bestv, fV);
+        if (CONF) conf[pix] = cf;
         if (target != nullptr) {
             const int tg = (int)target[pix];
             const bool counted = tg != ignore_index && tg < C;
+            if (CAL && counted) calb.count(cf, best == tg, B);
             bad_label |= tg != ignore_index && tg >= C;
             if (counts != nullptr && counted) {
                 atomicAdd(&hist[best], 1u);
@@ -241,6 +251,7 @@ __global__ __launch_bounds__(256) void prob_merge_finish_kernel(const float* __r
         if (cm != nullptr)
             for (int t = tid; t < C * C; t += 256)
                 if (cmh[t]) atomicAdd(&cm[t], (unsigned long long)cmh[t]);
+        if (CAL) calb.flush(cal, B);
     }
     if (part != nullptr) {
         if (bad_label) ce_loss = __builtin_nan("");     // as sssr_tail_predict_kernel
@@ -332,14 +343,19 @@ extern "C" int dsrl_prob_merge(const float* logits, int ld, int N, int Hs, int W
     return launch_status("prob_merge_kernel");
 }
 
-extern "C" int dsrl_prob_merge_finish(const float* logits, int ld, int N, int Hs, int Ws, int C, int mirror, const float* acc, int Ho, int Wo, int views,
-                                      uint8_t* pred, const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag,
-                                      void* ws, size_t ws_bytes, unsigned long long* cm, dsrl_stream_t stream) {
+namespace {
+
+int merge_finish_launch(const float* logits, int ld, int N, int Hs, int Ws, int C, int mirror, const float* acc, int Ho, int Wo, int views, uint8_t* pred,
+                        const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag, void* ws, size_t ws_bytes,
+                        unsigned long long* cm, unsigned long long* cal, int bins, float* conf, dsrl_stream_t stream) {
     if (int e = merge_check("prob_merge_finish", logits, ld, N, Hs, Ws, C, Ho, Wo)) return e;
     DSRL_REQUIRE(pred && views >= 1 && ((uintptr_t)acc % 4) == 0, DSRL_E_BADARG, "prob_merge_finish: null pred, views < 1, or acc not 4-byte aligned");
     DSRL_REQUIRE((acc != nullptr) == (views > 1), DSRL_E_BADARG, "prob_merge_finish: acc must be given exactly when there are earlier views (views = %d)",
                  views);
-    DSRL_REQUIRE(target || (!counts && !ce_out && !cm), DSRL_E_BADARG, "prob_merge_finish: counts / ce_out / cm need a target");
+    DSRL_REQUIRE(target || (!counts && !ce_out && !cm && !cal), DSRL_E_BADARG, "prob_merge_finish: counts / ce_out / cm / cal need a target");
+    DSRL_REQUIRE(!cal || (bins >= 1 && bins <= kCalMaxBins && ((uintptr_t)cal % 8) == 0), DSRL_E_BADARG,
+                 "prob_merge_finish: %d calibration bins (1 to %d are possible), or cal not 8-byte aligned", bins, kCalMaxBins);
+    DSRL_REQUIRE(((uintptr_t)conf % 4) == 0, DSRL_E_BADARG, "prob_merge_finish: conf not 4-byte aligned");
     const int nb = merge_blocks(N, Ho, Wo);
     DSRL_REQUIRE(!ce_out || (ws && ws_bytes >= dsrl_prob_merge_workspace_bytes(N, Ho, Wo) && ((uintptr_t)ws % 8) == 0), DSRL_E_WORKSPACE,
                  "prob_merge_finish: workspace too small or misaligned");
@@ -347,17 +363,44 @@ extern "C" int dsrl_prob_merge_finish(const float* logits, int ld, int N, int Hs
     if (int e = bind_stream_device(st)) return e;
     const int XC = merge_spans_per_row(Wo), nspans = N * Ho * XC, rounds = (int)ceil_div(nspans, 4LL * nb);
     double* part = ce_out ? (double*)ws : nullptr;
-    const float lnV = (float)log((double)views);
-    if (C == 19)
-        hipLaunchKernelGGL(prob_merge_finish_kernel<19>, dim3(nb), dim3(256), 0, st, logits, ld, Hs, Ws, C, mirror, acc, Ho, Wo, lnV, pred, target,
-                           ignore_index, counts, part, nan_flag, cm, nspans, XC, rounds);
-    else
-        hipLaunchKernelGGL(prob_merge_finish_kernel<kMergeMaxC>, dim3(nb), dim3(256), 0, st, logits, ld, Hs, Ws, C, mirror, acc, Ho, Wo, lnV, pred,
-                           target, ignore_index, counts, part, nan_flag, cm, nspans, XC, rounds);
+    const float lnV = (float)log((double)views), fV = (float)views;
+#define DSRL_MERGE_FINISH(CT, CAL, CONF)                                                                                                                  \
+    hipLaunchKernelGGL((prob_merge_finish_kernel<CT, CAL, CONF>), dim3(nb), dim3(256), 0, st, logits, ld, Hs, Ws, C, mirror, acc, Ho, Wo, lnV, pred, target, \
+                       ignore_index, counts, part, nan_flag, cm, nspans, XC, rounds, fV, cal, bins, conf)
+#define DSRL_MERGE_FINISH_CT(CT)                                        \
+    do {                                                                \
+        if (cal && conf) DSRL_MERGE_FINISH(CT, true, true);             \
+        else if (cal) DSRL_MERGE_FINISH(CT, true, false);               \
+        else if (conf) DSRL_MERGE_FINISH(CT, false, true);              \
+        else DSRL_MERGE_FINISH(CT, false, false);                       \
+    } while (0)
+    if (C == 19) DSRL_MERGE_FINISH_CT(19);
+    else DSRL_MERGE_FINISH_CT(kMergeMaxC);
+#undef DSRL_MERGE_FINISH_CT
+#undef DSRL_MERGE_FINISH
     if (int e = launch_status("prob_merge_finish_kernel")) return e;
     if (ce_out) {
         hipLaunchKernelGGL(prob_merge_ce_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nb, ce_out);
         return launch_status("prob_merge_ce_finalize_kernel");
     }
     return DSRL_OK;
+}
+
+}  // namespace
+
+extern "C" int dsrl_prob_merge_finish(const float* logits, int ld, int N, int Hs, int Ws, int C, int mirror, const float* acc, int Ho, int Wo, int views,
+                                      uint8_t* pred, const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag,
+                                      void* ws, size_t ws_bytes, unsigned long long* cm, dsrl_stream_t stream) {
+    return merge_finish_launch(logits, ld, N, Hs, Ws, C, mirror, acc, Ho, Wo, views, pred, target, ignore_index, counts, ce_out, nan_flag, ws, ws_bytes, cm,
+                               nullptr, 0, nullptr, stream);
+}
+
+// the same launch with every optional output: cal (the calibration record, int64 [3 * bins], ADDED; needs a target) and conf (the confidence map
+// (N,Ho,Wo) fp32) are nullable; with both null this is dsrl_prob_merge_finish
+extern "C" int dsrl_prob_merge_finish_ex(const float* logits, int ld, int N, int Hs, int Ws, int C, int mirror, const float* acc, int Ho, int Wo, int views,
+                                         uint8_t* pred, const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag,
+                                         void* ws, size_t ws_bytes, unsigned long long* cm, unsigned long long* cal, int bins, float* conf,
+                                         dsrl_stream_t stream) {
+    return merge_finish_launch(logits, ld, N, Hs, Ws, C, mirror, acc, Ho, Wo, views, pred, target, ignore_index, counts, ce_out, nan_flag, ws, ws_bytes, cm,
+                               cal, bins, conf, stream);
 }

@@ -26,17 +26,25 @@ constexpr int kPT = 5;                  // M tiles of 16 rows (80 >= 76) = k-ste
 constexpr int kPredMaxBlocks = 512;     // two blocks of 4 waves per CU
 using f32x4_p = __attribute__((ext_vector_type(4))) float;
 
-template <bool TGT, bool CE, bool CM>
+// CAL: the calibration record of the class map against target (common.h: CalBins, in LDS beside cmh); CONF: the confidence map (N,4H,4W), one aligned
+// 16-byte store per lane - the four columns of a patch row assembled with the lane 16 away, as the class bytes are.  Both take the confidence from the
+// softmax denominator the loss forms (CE) or form it the same way (softmax_denominator); a patch whose input pixel held a NaN in front of the ReLU has
+// NaN confidence (the ReLU hides it from the logits): in no bin, NaN in the map.  Without them the kernel is the one that does not know them.
+template <bool TGT, bool CE, bool CM, bool CAL = false, bool CONF = false>
 __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w1,
                                                                     const float* __restrict__ bn_mean, const float* __restrict__ bn_invstd,
                                                                     const float* __restrict__ bn_gamma, const float* __restrict__ bn_beta,
                                                                     const float* __restrict__ w2, const float* __restrict__ bias2,
                                                                     unsigned char* __restrict__ pred, const unsigned char* __restrict__ target, int ignore_index,
                                                                     unsigned long long* __restrict__ counts, double* __restrict__ part, int* __restrict__ nan_flag,
-                                                                    int H, int W, long long P, int ntiles, unsigned long long* __restrict__ cm) {
+                                                                    int H, int W, long long P, int ntiles, unsigned long long* __restrict__ cm,
+                                                                    unsigned long long* __restrict__ cal, int B, float* __restrict__ conf) {
     static_assert(!CM || TGT, "the confusion matrix needs a target");
+    static_assert(!CAL || TGT, "the calibration record needs a target");
     __shared__ unsigned hist[3 * kPC + 2];
     __shared__ unsigned cmh[CM ? kPC * kPC : 1];           // CM: cmh[t * kPC + p], per block at most what hist[3 * kPC + 1] receives
+    __shared__ unsigned long long calraw[CAL ? sizeof(CalBins) / 8 : 1];
+    CalBins& calb = *reinterpret_cast<CalBins*>(calraw);
     __shared__ double shd[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int px = lane & 15, g = lane >> 4;
@@ -44,6 +52,7 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
         for (int t = tid; t < 3 * kPC + 2; t += 256) hist[t] = 0u;
         if (CM)
             for (int t = tid; t < kPC * kPC; t += 256) cmh[t] = 0u;
+        if (CAL) calb.clear(B);
         __syncthreads();
     }
     // A fragments: A[i = l & 15][k = 4 s + (l >> 4)] of M-tile t
@@ -101,6 +110,8 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
             tw[1] = *reinterpret_cast<const unsigned*>(target + obase + (long long)(2 + i2) * Wo);
         }
         // ---- stage 1: the 2x2 mid pixels
+        unsigned tilebits = 0u;                     // CAL / CONF: a NaN in front of this pixel's ReLU
+        float cf[4] = {0.f, 0.f, 0.f, 0.f};         // CAL / CONF: the confidence of this lane's four output pixels
         f32x4_p mid[kPT];
 #pragma unroll
         for (int t = 0; t < kPT; ++t) mid[t] = f32x4_p{0.f, 0.f, 0.f, 0.f};
@@ -113,20 +124,31 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float z = fmaf(mid[t][r], sc[t], sh[t]);
-                nanbits = max(nanbits, abs_bits(z));        // fmaxf(NaN, 0) = 0: the ReLU would hide a NaN of the input from the logits (lanes past the end hold zeros)
+                // fmaxf(NaN, 0) = 0: the ReLU would hide a NaN of the input from the logits (lanes past the end hold zeros)
+                if (CAL || CONF) tilebits = max(tilebits, abs_bits(z));
+                else nanbits = max(nanbits, abs_bits(z));
                 mid[t][r] = fmaxf(z, 0.f);
             }
         // ---- stage 2: per mid pixel (tap1) the 2x2 logits; this lane's output pixel is (tap1, tap2 = g)
+        // packed: the class of output pixel T in bits 0-4 of byte T.  CAL / CONF keep their flags in the free bits and mask them off below: bit 7 of
+        // byte 0 = a NaN in front of this pixel's ReLU, bits 5 / 6 of byte T = pixel T is counted / is a hit (binned behind the T loop, where few
+        // registers are live)
         unsigned packed = 0u;
+        if (CAL || CONF) { nanbits = max(nanbits, tilebits); packed = tilebits > 0x7f800000u ? 0x80u : 0u; }
 #pragma unroll
         for (int T = 0; T < 4; ++T) {
             f32x4_p acc[kPT];
 #pragma unroll
             for (int t = 0; t < kPT; ++t) acc[t] = f32x4_p{bv[4 * t], bv[4 * t + 1], bv[4 * t + 2], bv[4 * t + 3]};
+            // The map-only build (no target) has no LDS traffic between two output pixels: left alone the compiler runs the next pixel's MFMAs ahead of
+            // this one's softmax arithmetic and spills one register.  An empty asm statement keeps their order, as in the flip kernel: the first k-step's
+            // operand passes through one that needs the class byte of the pixel before.
+            float m0 = mid[0][T];
+            if (CONF && !TGT) asm volatile("" : "+v"(packed), "+v"(m0));
 #pragma unroll
             for (int s = 0; s < kPT; ++s)
 #pragma unroll
-                for (int t = 0; t < kPT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[t][s], mid[s][T], acc[t], 0, 0, 0);
+                for (int t = 0; t < kPT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[t][s], s == 0 ? m0 : mid[s][T], acc[t], 0, 0, 0);
             float v[kPC];
 #pragma unroll
             for (int c = 0; c < kPC; ++c) v[c] = acc[c >> 2][c & 3];
@@ -140,6 +162,8 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
 #pragma unroll
                 for (int c = 0; c < kPC; ++c) nanbits = max(nanbits, valid ? abs_bits(v[c]) : 0u);
             }
+            float csum = 0.f;
+            if ((CAL || CONF) && !CE) csum = softmax_denominator<kPC>(v, kPC);
             if (TGT) {
                 const int tg = (int)((tw[T >> 1] >> (8 * (2 * (T & 1) + j2))) & 0xffu);
                 const bool lab_bad = valid && tg != ignore_index && tg >= kPC;
@@ -164,17 +188,34 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
 #pragma unroll
                     for (int c = 0; c < kPC; ++c) sum += exp_nonpos(v[c] - m);
                     bad |= !(sum == sum);               // any NaN logit poisons the sum (fmaxf alone would skip it)
+                    if (CAL || CONF) csum = sum;
                     if (tg != ignore_index) { ce_loss += (double)(m + logf(sum) - vt); ce_cnt += 1.0; }
                 }
+                if (CAL || CONF) cf[T] = (packed & 0x80u) ? __builtin_nanf("") : confidence_pixel(csum);
+                if (CAL && valid && tg != ignore_index && tg < kPC) packed |= (best == tg ? 0x60u : 0x20u) << (8 * T);
+            } else if (CONF) {
+                cf[T] = (packed & 0x80u) ? __builtin_nanf("") : confidence_pixel(csum);
             }
         }
         // row 2 i1 + i2 of the patch, columns 2 j1 + j2: this lane has j2, the lane 16 further on has the other one; lane j2 writes row i1 = j2
         const unsigned other = (unsigned)__shfl_xor((int)packed, 16, 64);
-        const unsigned b0 = j2 ? (other >> 16) & 0xffu : packed & 0xffu;
-        const unsigned b1 = j2 ? (packed >> 16) & 0xffu : other & 0xffu;
-        const unsigned b2 = j2 ? (other >> 24) & 0xffu : (packed >> 8) & 0xffu;
-        const unsigned b3 = j2 ? (packed >> 24) & 0xffu : (other >> 8) & 0xffu;
+        constexpr unsigned kCls = (CAL || CONF) ? 0x1fu : 0xffu;
+        const unsigned b0 = j2 ? (other >> 16) & kCls : packed & kCls;
+        const unsigned b1 = j2 ? (packed >> 16) & kCls : other & kCls;
+        const unsigned b2 = j2 ? (other >> 24) & kCls : (packed >> 8) & kCls;
+        const unsigned b3 = j2 ? (packed >> 24) & kCls : (other >> 8) & kCls;
         if (valid) *reinterpret_cast<unsigned*>(pred + obase + (long long)(2 * j2 + i2) * Wo) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+        if (CAL) {
+#pragma unroll
+            for (int T = 0; T < 4; ++T)
+                if ((packed >> (8 * T)) & 0x20u) calb.count(cf[T], ((packed >> (8 * T)) & 0x40u) != 0u, B);
+        }
+        if (CONF) {
+            // the same row: this lane's two columns and the two of the lane 16 away, which needs this lane's other pair
+            const float s0 = __shfl_xor(j2 ? cf[0] : cf[2], 16, 64), s1 = __shfl_xor(j2 ? cf[1] : cf[3], 16, 64);
+            const f32x4_p row = j2 ? f32x4_p{s0, cf[2], s1, cf[3]} : f32x4_p{cf[0], s0, cf[1], s1};
+            if (valid) *reinterpret_cast<f32x4_p*>(conf + obase + (long long)(2 * j2 + i2) * Wo) = row;
+        }
 #pragma unroll
         for (int s = 0; s < kPT; ++s) xb[s] = xn[s];
     }
@@ -189,6 +230,7 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
         if (CM)
             for (int t = tid; t < kPC * kPC; t += 256)
                 if (cmh[t]) atomicAdd(&cm[t], (unsigned long long)cmh[t]);
+        if (CAL) calb.flush(cal, B);
     }
     if (CE) {
         if (bad_label) ce_loss = __builtin_nan("");     // torch asserts on such a label; here it poisons the loss, as ce_fused_kernel does
@@ -212,7 +254,7 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
 // ea_c / sa + eb_c / sb, the loss -(logaddexp(la_t, lb_t) - ln 2) of the two log-softmax values in log space (finite where the averaged probability
 // underflows).  View a is reduced to its 19 probabilities before view b's accumulators are formed, so only one set of accumulators is live at a time.
 // Counters, partials, NaN flag and the byte assembly are those of sssr_tail_predict_kernel.
-template <bool TGT, bool CE, bool CM>
+template <bool TGT, bool CE, bool CM, bool CAL = false, bool CONF = false>
 __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w1,
                                                                          const float* __restrict__ bn_mean, const float* __restrict__ bn_invstd,
                                                                          const float* __restrict__ bn_gamma, const float* __restrict__ bn_beta,
@@ -220,10 +262,14 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const fl
                                                                          unsigned char* __restrict__ pred, const unsigned char* __restrict__ target,
                                                                          int ignore_index, unsigned long long* __restrict__ counts, double* __restrict__ part,
                                                                          int* __restrict__ nan_flag, int H, int W, long long P, int ntiles,
-                                                                         unsigned long long* __restrict__ cm) {
+                                                                         unsigned long long* __restrict__ cm, unsigned long long* __restrict__ cal, int B,
+                                                                         float* __restrict__ conf) {
     static_assert(!CM || TGT, "the confusion matrix needs a target");
+    static_assert(!CAL || TGT, "the calibration record needs a target");
     __shared__ unsigned hist[3 * kPC + 2];
     __shared__ unsigned cmh[CM ? kPC * kPC : 1];           // as sssr_tail_predict_kernel
+    __shared__ unsigned long long calraw[CAL ? sizeof(CalBins) / 8 : 1];
+    CalBins& calb = *reinterpret_cast<CalBins*>(calraw);
     __shared__ double shd[4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int px = lane & 15, g = lane >> 4;
@@ -231,6 +277,7 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const fl
         for (int t = tid; t < 3 * kPC + 2; t += 256) hist[t] = 0u;
         if (CM)
             for (int t = tid; t < kPC * kPC; t += 256) cmh[t] = 0u;
+        if (CAL) calb.clear(B);
         __syncthreads();
     }
     // Stage-2 fragments stay in registers (two sets: a2 for view a, a2b with tap2 ^ 1 for view b).  The stage-1 fragments do not fit beside them and
@@ -279,6 +326,7 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const fl
     double ce_loss = 0.0, ce_cnt = 0.0;
     bool bad = false, bad_label = false;
     unsigned nanbits = 0u;
+    unsigned tilebits = 0u;                     // CAL / CONF: a NaN in front of the ReLU of either view of the tile's pixel
 
     // view a: pixel p; view b: the pixel of image N + n at column W - 1 - w, i.e. p + P + (W - 1 - 2 w)
     auto xload = [&](int tile, float (&xa)[kPT], float (&xb)[kPT]) {
@@ -305,7 +353,9 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const fl
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float z = fmaf(mid[t][r], sc[t], sh[t]);
-                nanbits = max(nanbits, abs_bits(z));        // the ReLU would hide a NaN of the input from the logits (lanes past the end hold zeros)
+                // the ReLU would hide a NaN of the input from the logits (lanes past the end hold zeros)
+                if (CAL || CONF) tilebits = max(tilebits, abs_bits(z));
+                else nanbits = max(nanbits, abs_bits(z));
                 mid[t][r] = fmaxf(z, 0.f);
             }
     };
@@ -356,10 +406,13 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const fl
             tw[1] = *reinterpret_cast<const unsigned*>(target + obase + (long long)(2 + i2) * Wo);
         }
         f32x4_p mid_a[kPT], mid_b[kPT];
+        tilebits = 0u;
+        float cf[4] = {0.f, 0.f, 0.f, 0.f};         // CAL / CONF: the confidence of this lane's four output pixels
         stage1(a1, xa, mid_a);
         stage1(a1, xb, mid_b);
         xload(tile + stride, xa, xb);               // the next tile's pixels are in flight while stage 2 of this one is computed
-        unsigned packed = 0u;
+        unsigned packed = 0u;                       // the free bits of its bytes: as in sssr_tail_predict_kernel
+        if (CAL || CONF) { nanbits = max(nanbits, tilebits); packed = tilebits > 0x7f800000u ? 0x80u : 0u; }
 #pragma unroll
         for (int T = 0; T < 4; ++T) {
             int tg = 0, ts = 0;
@@ -391,8 +444,10 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const fl
                 if (e > bestv) { bestv = e; best = c; }                 // first maximum, as seg_metrics_kernel and torch.argmax
             }
             packed |= (unsigned)best << (8 * T);
+            if (CAL || CONF) cf[T] = (packed & 0x80u) ? __builtin_nanf("") : confidence_flip(bestv);
             if (TGT) {
                 const bool lab_bad = valid && tg != ignore_index && tg >= kPC;
+                if (CAL && valid && tg != ignore_index && tg < kPC) packed |= (best == tg ? 0x60u : 0x20u) << (8 * T);
                 bad_label |= lab_bad;
                 if (counts != nullptr && valid && tg != ignore_index && tg < kPC) {
                     atomicAdd(&hist[best], 1u);
@@ -412,11 +467,23 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const fl
         }
         // row 2 i1 + i2 of the patch, columns 2 j1 + j2: this lane has j2, the lane 16 further on has the other one; lane j2 writes row i1 = j2
         const unsigned other = (unsigned)__shfl_xor((int)packed, 16, 64);
-        const unsigned b0 = j2 ? (other >> 16) & 0xffu : packed & 0xffu;
-        const unsigned b1 = j2 ? (packed >> 16) & 0xffu : other & 0xffu;
-        const unsigned b2 = j2 ? (other >> 24) & 0xffu : (packed >> 8) & 0xffu;
-        const unsigned b3 = j2 ? (packed >> 24) & 0xffu : (other >> 8) & 0xffu;
+        constexpr unsigned kCls = (CAL || CONF) ? 0x1fu : 0xffu;
+        const unsigned b0 = j2 ? (other >> 16) & kCls : packed & kCls;
+        const unsigned b1 = j2 ? (packed >> 16) & kCls : other & kCls;
+        const unsigned b2 = j2 ? (other >> 24) & kCls : (packed >> 8) & kCls;
+        const unsigned b3 = j2 ? (packed >> 24) & kCls : (other >> 8) & kCls;
         if (valid) *reinterpret_cast<unsigned*>(pred + obase + (long long)(2 * j2 + i2) * Wo) = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+        if (CAL) {
+#pragma unroll
+            for (int T = 0; T < 4; ++T)
+                if ((packed >> (8 * T)) & 0x20u) calb.count(cf[T], ((packed >> (8 * T)) & 0x40u) != 0u, B);
+        }
+        if (CONF) {
+            // the same row: this lane's two columns and the two of the lane 16 away, which needs this lane's other pair
+            const float s0 = __shfl_xor(j2 ? cf[0] : cf[2], 16, 64), s1 = __shfl_xor(j2 ? cf[1] : cf[3], 16, 64);
+            const f32x4_p row = j2 ? f32x4_p{s0, cf[2], s1, cf[3]} : f32x4_p{cf[0], s0, cf[1], s1};
+            if (valid) *reinterpret_cast<f32x4_p*>(conf + obase + (long long)(2 * j2 + i2) * Wo) = row;
+        }
     }
     bad |= nanbits > 0x7f800000u;
     if (nan_flag != nullptr && __any(bad) && lane == 0) atomicOr(nan_flag, 1);
@@ -429,6 +496,7 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const fl
         if (CM)
             for (int t = tid; t < kPC * kPC; t += 256)
                 if (cmh[t]) atomicAdd(&cm[t], (unsigned long long)cmh[t]);
+        if (CAL) calb.flush(cal, B);
     }
     if (CE) {
         if (bad_label) ce_loss = __builtin_nan("");     // as sssr_tail_predict_kernel
@@ -520,14 +588,17 @@ namespace {
 int tail_predict_launch(bool flip, const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
                         const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2, uint8_t* pred,
                         const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag, void* ws, size_t ws_bytes,
-                        unsigned long long* cm, dsrl_stream_t stream) {
+                        unsigned long long* cm, unsigned long long* cal, int bins, float* conf, dsrl_stream_t stream) {
     DSRL_REQUIRE(x && w1 && bn_mean && bn_invstd && bn_gamma && bn_beta && w2 && pred && N > 0 && H > 0 && W > 0, DSRL_E_BADARG,
                  "sssr_tail_predict: null pointer or empty shape");
     DSRL_REQUIRE(dsrl_sssr_tail_predict_supported(N, H, W, Cin, Cmid, Cout), DSRL_E_UNSUPPORTED,
                  "sssr_tail_predict: needs 19 -> 19 -> 19 channels and N*H*W*16 < 2^31 (got %d -> %d -> %d, %d x %d x %d)", Cin, Cmid, Cout, N, H, W);
     DSRL_REQUIRE(ldx >= Cin && ((uintptr_t)x % 4) == 0 && ((uintptr_t)pred % 4) == 0 && ((uintptr_t)target % 4) == 0, DSRL_E_BADARG,
                  "sssr_tail_predict: ldx < Cin, or x / pred / target not 4-byte aligned");
-    DSRL_REQUIRE(target || (!counts && !ce_out && !cm), DSRL_E_BADARG, "sssr_tail_predict: counts / ce_out / cm need a target");
+    DSRL_REQUIRE(target || (!counts && !ce_out && !cm && !cal), DSRL_E_BADARG, "sssr_tail_predict: counts / ce_out / cm / cal need a target");
+    DSRL_REQUIRE(!cal || (bins >= 1 && bins <= kCalMaxBins && ((uintptr_t)cal % 8) == 0), DSRL_E_BADARG,
+                 "sssr_tail_predict: %d calibration bins (1 to %d are possible), or cal not 8-byte aligned", bins, kCalMaxBins);
+    DSRL_REQUIRE(((uintptr_t)conf % 16) == 0, DSRL_E_BADARG, "sssr_tail_predict: conf not 16-byte aligned");
     const long long P = (long long)N * H * W;
     const int nb = predict_blocks(P);
     DSRL_REQUIRE(!ce_out || (ws && ws_bytes >= dsrl_sssr_tail_predict_workspace_bytes(N, H, W) && ((uintptr_t)ws % 8) == 0), DSRL_E_WORKSPACE,
@@ -536,22 +607,42 @@ int tail_predict_launch(bool flip, const float* x, int ldx, int N, int H, int W,
     if (int e = bind_stream_device(st)) return e;
     const int ntiles = (int)ceil_div(P, 16);
     double* part = (double*)ws;
-#define DSRL_PREDICT_LAUNCH(KERNEL, TGT, CE, CM)                                                                                                       \
-    hipLaunchKernelGGL((KERNEL<TGT, CE, CM>), dim3(nb), dim3(256), 0, st, x, ldx, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, \
-                       ignore_index, counts, part, nan_flag, H, W, P, ntiles, cm)
-    if (flip) {
-        if (!target) DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, false, false, false);
-        else if (cm && !ce_out) DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, true, false, true);
-        else if (cm) DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, true, true, true);
-        else if (!ce_out) DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, true, false, false);
-        else DSRL_PREDICT_LAUNCH(sssr_tail_predict_flip_kernel, true, true, false);
+#define DSRL_PREDICT_LAUNCH(KERNEL, TGT, CE, CM, CAL, CONF)                                                                                             \
+    hipLaunchKernelGGL((KERNEL<TGT, CE, CM, CAL, CONF>), dim3(nb), dim3(256), 0, st, x, ldx, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred,   \
+                       target, ignore_index, counts, part, nan_flag, H, W, P, ntiles, cm, cal, bins, conf)
+    // without a record and a map: the launches of the entry points that do not know them
+#define DSRL_PREDICT_PLAIN(KERNEL)                                                          \
+    do {                                                                                    \
+        if (!target) DSRL_PREDICT_LAUNCH(KERNEL, false, false, false, false, false);        \
+        else if (cm && !ce_out) DSRL_PREDICT_LAUNCH(KERNEL, true, false, true, false, false); \
+        else if (cm) DSRL_PREDICT_LAUNCH(KERNEL, true, true, true, false, false);           \
+        else if (!ce_out) DSRL_PREDICT_LAUNCH(KERNEL, true, false, false, false, false);    \
+        else DSRL_PREDICT_LAUNCH(KERNEL, true, true, false, false, false);                  \
+    } while (0)
+#define DSRL_PREDICT_EX3(KERNEL, CE, CM)                                                    \
+    do {                                                                                    \
+        if (cal && conf) DSRL_PREDICT_LAUNCH(KERNEL, true, CE, CM, true, true);             \
+        else if (cal) DSRL_PREDICT_LAUNCH(KERNEL, true, CE, CM, true, false);               \
+        else DSRL_PREDICT_LAUNCH(KERNEL, true, CE, CM, false, true);                        \
+    } while (0)
+#define DSRL_PREDICT_EX(KERNEL)                                                             \
+    do {                                                                                    \
+        if (!target) DSRL_PREDICT_LAUNCH(KERNEL, false, false, false, false, true);         \
+        else if (cm && !ce_out) DSRL_PREDICT_EX3(KERNEL, false, true);                      \
+        else if (cm) DSRL_PREDICT_EX3(KERNEL, true, true);                                  \
+        else if (!ce_out) DSRL_PREDICT_EX3(KERNEL, false, false);                           \
+        else DSRL_PREDICT_EX3(KERNEL, true, false);                                         \
+    } while (0)
+    if (!cal && !conf) {
+        if (flip) DSRL_PREDICT_PLAIN(sssr_tail_predict_flip_kernel);
+        else DSRL_PREDICT_PLAIN(sssr_tail_predict_kernel);
     } else {
-        if (!target) DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, false, false, false);
-        else if (cm && !ce_out) DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, true, false, true);
-        else if (cm) DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, true, true, true);
-        else if (!ce_out) DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, true, false, false);
-        else DSRL_PREDICT_LAUNCH(sssr_tail_predict_kernel, true, true, false);
+        if (flip) DSRL_PREDICT_EX(sssr_tail_predict_flip_kernel);
+        else DSRL_PREDICT_EX(sssr_tail_predict_kernel);
     }
+#undef DSRL_PREDICT_EX
+#undef DSRL_PREDICT_EX3
+#undef DSRL_PREDICT_PLAIN
 #undef DSRL_PREDICT_LAUNCH
     if (int e = launch_status(flip ? "sssr_tail_predict_flip_kernel" : "sssr_tail_predict_kernel")) return e;
     if (ce_out) {
@@ -568,7 +659,7 @@ extern "C" int dsrl_sssr_tail_predict(const float* x, int ldx, int N, int H, int
                                       const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag, void* ws,
                                       size_t ws_bytes, dsrl_stream_t stream) {
     return tail_predict_launch(false, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
-                               counts, ce_out, nan_flag, ws, ws_bytes, nullptr, stream);
+                               counts, ce_out, nan_flag, ws, ws_bytes, nullptr, nullptr, 0, nullptr, stream);
 }
 
 extern "C" int dsrl_sssr_tail_predict_flip(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
@@ -576,7 +667,7 @@ extern "C" int dsrl_sssr_tail_predict_flip(const float* x, int ldx, int N, int H
                                            uint8_t* pred, const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag,
                                            void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     return tail_predict_launch(true, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
-                               counts, ce_out, nan_flag, ws, ws_bytes, nullptr, stream);
+                               counts, ce_out, nan_flag, ws, ws_bytes, nullptr, nullptr, 0, nullptr, stream);
 }
 
 // the same launches with the confusion matrix beside the counters: cm[t * Cout + p] += pixels with target t and predicted class p
@@ -585,7 +676,7 @@ extern "C" int dsrl_sssr_tail_predict_cm(const float* x, int ldx, int N, int H, 
                                          const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag, void* ws,
                                          size_t ws_bytes, unsigned long long* cm, dsrl_stream_t stream) {
     return tail_predict_launch(false, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
-                               counts, ce_out, nan_flag, ws, ws_bytes, cm, stream);
+                               counts, ce_out, nan_flag, ws, ws_bytes, cm, nullptr, 0, nullptr, stream);
 }
 
 extern "C" int dsrl_sssr_tail_predict_flip_cm(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
@@ -593,7 +684,26 @@ extern "C" int dsrl_sssr_tail_predict_flip_cm(const float* x, int ldx, int N, in
                                               uint8_t* pred, const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag,
                                               void* ws, size_t ws_bytes, unsigned long long* cm, dsrl_stream_t stream) {
     return tail_predict_launch(true, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
-                               counts, ce_out, nan_flag, ws, ws_bytes, cm, stream);
+                               counts, ce_out, nan_flag, ws, ws_bytes, cm, nullptr, 0, nullptr, stream);
+}
+
+// one entry point per kernel for every optional output: cm, cal (the calibration record, int64 [3 * bins], ADDED) and conf (the confidence map) are
+// nullable; with cal and conf null these are the launches above
+extern "C" int dsrl_sssr_tail_predict_ex(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                                         const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2, uint8_t* pred,
+                                         const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag, void* ws,
+                                         size_t ws_bytes, unsigned long long* cm, unsigned long long* cal, int bins, float* conf, dsrl_stream_t stream) {
+    return tail_predict_launch(false, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
+                               counts, ce_out, nan_flag, ws, ws_bytes, cm, cal, bins, conf, stream);
+}
+
+extern "C" int dsrl_sssr_tail_predict_flip_ex(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                                              const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2,
+                                              uint8_t* pred, const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag,
+                                              void* ws, size_t ws_bytes, unsigned long long* cm, unsigned long long* cal, int bins, float* conf,
+                                              dsrl_stream_t stream) {
+    return tail_predict_launch(true, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
+                               counts, ce_out, nan_flag, ws, ws_bytes, cm, cal, bins, conf, stream);
 }
 
 extern "C" int dsrl_fingerprint_segment_words(void) { return kFingerprintSegWords; }

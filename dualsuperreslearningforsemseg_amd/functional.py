@@ -2347,6 +2347,89 @@ def check_confusion(confusion, num_classes, device, what='sssr_tail_predict'):
         raise DsrlHipError(f'{what}: confusion is on {confusion.device}, the batch on {device}')
 
 
+CALIBRATION_DEFAULT_BINS = 15
+
+
+def calibration_max_bins():
+    """the largest bin count of a calibration record (dsrl_calibration_max_bins); pure host code"""
+    return int(query('dsrl_calibration_max_bins'))
+
+
+def calibration_bins_value(bins, what='calibration'):
+    """`bins` as an int in [1, calibration_max_bins()]; ValueError on anything else (bools, floats, strings included).  Touches no device."""
+    maxb = calibration_max_bins()
+    if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)) or not 1 <= int(bins) <= maxb:
+        raise ValueError(f'{what}: bins = {bins!r}, an integer from 1 to {maxb} expected')
+    return int(bins)
+
+
+def check_calibration(record, bins, device, what='sssr_tail_predict'):
+    """`record` as every producer wants it: a contiguous int64 tensor of 3 * bins elements [n_b | hit_b | q_b] on `device`; `bins` from 1 to
+    calibration_max_bins().  -> bins as an int.  Raises before any device work."""
+    bins = calibration_bins_value(bins, what)
+    if not isinstance(record, torch.Tensor) or record.dtype != torch.int64 or record.numel() != 3 * bins or not record.is_contiguous():
+        got = f'{record.dtype}, {record.numel()} elements' if isinstance(record, torch.Tensor) else type(record).__name__
+        raise DsrlHipError(f'{what}: calibration must be a contiguous int64 tensor of {3 * bins} elements (got {got})')
+    _need_gpu(record)
+    if record.device != torch.device(device):
+        raise DsrlHipError(f'{what}: calibration is on {record.device}, the batch on {device}')
+    return bins
+
+
+def _calibration_bins_of(record, what):
+    """the bin count a record tensor implies (its length over 3), checked"""
+    if not isinstance(record, torch.Tensor) or record.numel() % 3 or record.numel() == 0:
+        got = f'{record.numel()} elements' if isinstance(record, torch.Tensor) else type(record).__name__
+        raise DsrlHipError(f'{what}: calibration must be an int64 tensor of 3 * bins elements (got {got})')
+    return record.numel() // 3
+
+
+def calibration_counts_(record, logits, target, ignore_index=255, bins=CALIBRATION_DEFAULT_BINS, confidence=None, nan_flag=None):
+    """record[n_b | hit_b | q_b] += the reliability histogram of logits (N,C,H,W) against target (N,H,W) over `bins` equal-width confidence bins
+    (dsrl_calibration_from_logits, include/dsrl_hip.h "calibration"): the confidence of a pixel is its maximum softmax probability, counted are the
+    pixels the confusion matrix counts (target != ignore_index and < C), q is the sum of rintf(conf * 2^24).  `confidence` (float32, (N,H,W),
+    contiguous, optional) receives the confidence map; `nan_flag` (int32 device scalar, optional): bit 0 a NaN logit, bit 1 a label outside the
+    classes.  One streaming launch, nothing read back.  A bad argument raises before any device work."""
+    with torch.no_grad():
+        if logits.dim() != 4:
+            raise DsrlHipError(f'calibration_counts_: 4-D (N,C,H,W) logits expected, got shape {tuple(logits.shape)}')
+        bins = check_calibration(record, bins, logits.device, 'calibration_counts_')
+        _need_gpu(logits, target, nan_flag, confidence)
+        N, C, H, W = logits.shape
+        if tuple(target.shape) != (N, H, W):
+            raise DsrlHipError(f'calibration_counts_: target {tuple(target.shape)} is not {(N, H, W)}')
+        if nan_flag is not None and (nan_flag.dtype != torch.int32 or nan_flag.numel() != 1):
+            raise DsrlHipError('calibration_counts_: nan_flag must be an int32 scalar')
+        if confidence is not None and (confidence.dtype != torch.float32 or tuple(confidence.shape) != (N, H, W) or not confidence.is_contiguous()
+                                       or confidence.device != logits.device):
+            raise DsrlHipError(f'calibration_counts_: confidence must be a contiguous float32 tensor of shape {(N, H, W)} on the logits\' device')
+        logits, ld = pm(logits)
+        target = (target if target.dtype == torch.uint8 else target.to(torch.uint8)).contiguous()
+        if N * H * W:
+            call('dsrl_calibration_from_logits', logits.data_ptr(), ld, target.data_ptr(), N * H * W, C, int(ignore_index), bins, record.data_ptr(),
+                 None if confidence is None else confidence.data_ptr(), None if nan_flag is None else nan_flag.data_ptr(), _stream())
+    return record
+
+
+def _calibration_of_scores(record, scores, pred, target, ignore_index, num_classes, want_conf):
+    """The fall-back of heads the fused kernels do not implement, from class probabilities `scores` (N,C,H,W) that are NOT a single softmax (the flip
+    and multi-scale ensembles composed from torch ops): the confidence is the winning probability; the record is binned by the definition of
+    include/dsrl_hip.h in integer torch ops (exact, order independent)."""
+    conf = scores.gather(1, pred.long().unsqueeze(1))[:, 0].float().clamp(max=1.0)
+    if record is not None:
+        B = record.numel() // 3
+        counted = (target != ignore_index) & (target < num_classes) & ~torch.isnan(conf)
+        c = conf[counted]
+        b = torch.clamp((c * float(B)).to(torch.int64), max=B - 1)
+        hit = (pred[counted] == target[counted]).to(torch.int64)
+        q = torch.round(c * 16777216.0).to(torch.int64)         # round half to even, as rintf
+        rec = record.view(3, B)
+        rec[0].scatter_add_(0, b, torch.ones_like(b))
+        rec[1].scatter_add_(0, b, hit)
+        rec[2].scatter_add_(0, b, q)
+    return conf.contiguous() if want_conf else None
+
+
 def confusion_matrix_(confusion, pred, target, num_classes, ignore_index=255, nan_flag=None):
     """confusion[t * num_classes + p] += pixels with target t and predicted class p, from two class maps of the same shape (dsrl_confusion_matrix):
     targets equal to `ignore_index` or >= num_classes are not counted; a predicted class >= num_classes on a counted pixel raises bit 1 of `nan_flag`
@@ -2421,7 +2504,8 @@ def boundary_counts_(counts, pred, target, num_classes, ignore_index=255, distan
     return counts
 
 
-def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, counts=None, nan_flag=None, flip=False, confusion=None):
+def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, counts=None, nan_flag=None, flip=False, confusion=None, calibration=None,
+                      confidence=False):
     """Eval-mode tail of the SSSR decoder after its bilinear x2 (DSRL.py:55-69): ConvTranspose2d k2 s2 `convt1` -> BatchNorm2d `bn` (running statistics)
     -> ReLU -> ConvTranspose2d k2 s2 `convt2` -> arg-max, as one launch that writes class indices and never the logits (dsrl_sssr_tail_predict).
     -> (pred uint8 (N,4H,4W), ce): with `target` (N,4H,4W) `ce` is the 0-d device tensor of nn.CrossEntropyLoss(ignore_index) of the logits and
@@ -2432,9 +2516,16 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
     logarithm, `target` (N,4H,4W); the same single launch (dsrl_sssr_tail_predict_flip), still no logits in memory.
     `confusion` (int64 [classes^2], optional, needs a target) gets the confusion matrix of the returned class map ADDED: confusion[t * classes + p] =
     pixels with target t and predicted class p, by the same launch (dsrl_sssr_tail_predict_cm / _flip_cm); heads the kernel does not implement
-    count it from `pred` (dsrl_confusion_matrix).  Without it the launches are those of a call that does not know the argument."""
+    count it from `pred` (dsrl_confusion_matrix).  Without it the launches are those of a call that does not know the argument.
+    `calibration` (int64 [3*bins], optional, needs a target) gets the reliability record [n_b | hit_b | q_b] of the returned class map ADDED (the bin
+    count is its length over 3; include/dsrl_hip.h "calibration"), `confidence=True` appends the confidence map (float32 (N,4H,4W): the probability of
+    the reported class) to the returned tuple; both come from the same single launch (dsrl_sssr_tail_predict_ex / _flip_ex).  Heads the kernel does
+    not implement go modules -> logits -> dsrl_calibration_from_logits.  Without them the launches are those of a call that does not know them."""
     if confusion is not None and target is None:
         raise DsrlHipError('sssr_tail_predict: confusion needs a target')
+    if calibration is not None and target is None:
+        raise DsrlHipError('sssr_tail_predict: calibration needs a target')
+    confidence = bool(confidence)
     with torch.no_grad():
         x, ldx = pm(x)
         w1, w2, b2 = convt1.weight, convt2.weight, convt2.bias
@@ -2461,6 +2552,10 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
             raise DsrlHipError('sssr_tail_predict: counts and confusion need a target')
         if confusion is not None:
             check_confusion(confusion, Co, x.device)
+        bins = 0
+        if calibration is not None:
+            bins = check_calibration(calibration, _calibration_bins_of(calibration, 'sssr_tail_predict'), x.device)
+        ex = calibration is not None or confidence
         if counts is not None and (counts.dtype != torch.int64 or counts.numel() != 3 * Co + 2 or not counts.is_contiguous()):
             raise DsrlHipError(f'sssr_tail_predict: counts must be a contiguous int64 tensor of {3 * Co + 2} elements')
         if nan_flag is not None and (nan_flag.dtype != torch.int32 or nan_flag.numel() != 1):
@@ -2478,13 +2573,18 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
             ws = _ws(cquery('dsrl_sssr_tail_predict_workspace_bytes', N, H, W) if ce is not None else 0, x)
             gamma = bn.weight if bn.weight is not None else torch.ones_like(invstd)
             beta = bn.bias if bn.bias is not None else torch.zeros_like(invstd)
-            name = ('dsrl_sssr_tail_predict_flip' if flip else 'dsrl_sssr_tail_predict') + ('' if confusion is None else '_cm')
+            name = ('dsrl_sssr_tail_predict_flip' if flip else 'dsrl_sssr_tail_predict') + ('_ex' if ex else '' if confusion is None else '_cm')
+            conf = torch.empty((N, 4 * H, 4 * W), device=x.device, dtype=torch.float32) if confidence else None
+            extra = () if confusion is None else (confusion.data_ptr(),)
+            if ex:
+                extra = (None if confusion is None else confusion.data_ptr(), None if calibration is None else calibration.data_ptr(), bins,
+                         None if conf is None else conf.data_ptr())
             call(name, x.data_ptr(), ldx, N, H, W, Ci, Cm, Co, w1.contiguous().data_ptr(), bn.running_mean.data_ptr(),
                  invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w2.contiguous().data_ptr(), None if b2 is None else b2.data_ptr(),
                  pred.data_ptr(), None if target is None else target.data_ptr(), int(ignore_index), None if counts is None else counts.data_ptr(),
                  None if ce is None else ce.data_ptr(), None if nan_flag is None else nan_flag.data_ptr(), ws.data_ptr(), ws.numel(),
-                 *(() if confusion is None else (confusion.data_ptr(),)), st)
-            return pred, (None if ce is None else ce[0])
+                 *extra, st)
+            return (pred, (None if ce is None else ce[0])) + ((conf,) if confidence else ())
         # any other head: the modules as the training forward runs them in eval mode, then the reductions over their logits
         y = batch_norm_act(convt1(x), bn, relu=True)
         logits = convt2(y)
@@ -2493,8 +2593,19 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
         if flip:
             logits = _flip_ensemble(logits)         # the scores of the ensemble stand in for the logits: log_softmax(E) = E
         pred = torch.argmax(logits, dim=1).to(torch.uint8)
+        conf = ()
+        if ex:
+            # softmax(E) = exp(E), so the maximum softmax probability of the scores IS the ensemble's confidence: one producer for both forms
+            cmap = torch.empty((N, 4 * H, 4 * W), device=x.device, dtype=torch.float32) if confidence else None
+            if calibration is not None:
+                calibration_counts_(calibration, logits, target, int(ignore_index), bins, cmap)
+            else:
+                lg, ld = pm(logits)
+                call('dsrl_calibration_from_logits', lg.data_ptr(), ld, None, N * 16 * H * W, Co, int(ignore_index), 1, None, cmap.data_ptr(), None,
+                     _stream())
+            conf = (cmap,) if confidence else ()
         if target is None:
-            return pred, None
+            return (pred, None) + conf
         if nan_flag is not None:
             _bad_label_bit(nan_flag, target, int(ignore_index), Co)
         if counts is not None:
@@ -2502,7 +2613,7 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
             call('dsrl_seg_metrics', lg.data_ptr(), ld, target.data_ptr(), N * 16 * H * W, Co, int(ignore_index), counts.data_ptr(), _stream())
         if confusion is not None:
             confusion_matrix_(confusion, pred, target, Co, int(ignore_index))
-        return pred, cross_entropy(logits, target, int(ignore_index))
+        return (pred, cross_entropy(logits, target, int(ignore_index))) + conf
 
 
 # ------------------------------------------------------------------------------------------------ multi-scale inference
@@ -2586,7 +2697,10 @@ class ProbMerge:
     current stream and nothing else refers to them.  Shapes dsrl_prob_merge_supported refuses for the whole batch are launched image by image; class
     counts it refuses are composed from torch ops under the same definition."""
 
-    def __init__(self, views, N, C, out_size, device, target=None, ignore_index=255, counts=None, nan_flag=None, confusion=None):
+    def __init__(self, views, N, C, out_size, device, target=None, ignore_index=255, counts=None, nan_flag=None, confusion=None, calibration=None,
+                 confidence=False):
+        """`calibration` (int64 [3*bins], needs a target) gets the reliability record of the ensemble's class map ADDED and `confidence=True` appends
+        the confidence map (float32 (N,Ho,Wo): min(1, winning probability sum / views)) to what the last `add` returns (dsrl_prob_merge_finish_ex)."""
         self.V, self.N, self.C = int(views), int(N), int(C)
         self.Ho, self.Wo = int(out_size[0]), int(out_size[1])
         self.device, self.ignore_index = device, int(ignore_index)
@@ -2599,10 +2713,14 @@ class ProbMerge:
             if target.dtype != torch.uint8:
                 target = target.to(torch.uint8)
             target = target.contiguous()
-        elif counts is not None or confusion is not None:
-            raise DsrlHipError('multiscale_merge: counts and confusion need a target')
+        elif counts is not None or confusion is not None or calibration is not None:
+            raise DsrlHipError('multiscale_merge: counts, confusion and calibration need a target')
         if confusion is not None:
             check_confusion(confusion, self.C, device, 'multiscale_merge')
+        self.bins = 0
+        if calibration is not None:
+            self.bins = check_calibration(calibration, _calibration_bins_of(calibration, 'multiscale_merge'), device, 'multiscale_merge')
+        self.calibration, self.confidence = calibration, bool(confidence)
         if counts is not None and (counts.dtype != torch.int64 or counts.numel() != 3 * self.C + 2 or not counts.is_contiguous()):
             raise DsrlHipError(f'multiscale_merge: counts must be a contiguous int64 tensor of {3 * self.C + 2} elements')
         if nan_flag is not None and (nan_flag.dtype != torch.int32 or nan_flag.numel() != 1):
@@ -2647,19 +2765,24 @@ class ProbMerge:
             pred = torch.empty((self.N, Ho, Wo), device=self.device, dtype=torch.uint8)
             ce = torch.empty((self.N // n, 2), device=self.device, dtype=torch.float32) if tgt is not None else None
             ws = _ws(cquery('dsrl_prob_merge_workspace_bytes', n, Ho, Wo) if ce is not None else 0, logits)
+            ex = self.calibration is not None or self.confidence
+            conf = torch.empty((self.N, Ho, Wo), device=self.device, dtype=torch.float32) if self.confidence else None
+            more = (conf,) if self.confidence else ()
             for k, i in enumerate(range(0, self.N, n)):
-                call('dsrl_prob_merge_finish', logits.data_ptr() + i * h * w * ld * 4, ld, n, h, w, C, int(bool(mirrored)),
+                extra = () if not ex else (None if self.calibration is None else self.calibration.data_ptr(), self.bins,
+                                           None if conf is None else conf.data_ptr() + 4 * i * Ho * Wo)
+                call('dsrl_prob_merge_finish_ex' if ex else 'dsrl_prob_merge_finish', logits.data_ptr() + i * h * w * ld * 4, ld, n, h, w, C, int(bool(mirrored)),
                      None if self.acc is None else self.acc.data_ptr() + i * acc_step, Ho, Wo, self.V, pred.data_ptr() + i * Ho * Wo,
                      None if tgt is None else tgt.data_ptr() + i * Ho * Wo, self.ignore_index, None if self.counts is None else self.counts.data_ptr(),
                      None if ce is None else ce.data_ptr() + 8 * k, None if self.nan_flag is None else self.nan_flag.data_ptr(), ws.data_ptr(), ws.numel(),
-                     None if self.confusion is None else self.confusion.data_ptr(), st)
+                     None if self.confusion is None else self.confusion.data_ptr(), *extra, st)
             self.acc = None
             if ce is None:
-                return pred, None
+                return (pred, None) + more
             if ce.shape[0] == 1:
-                return pred, ce[0, 0]
+                return (pred, ce[0, 0]) + more
             mean, cnt = ce[:, 0].double(), ce[:, 1].double()            # per image: a mean over no pixel (NaN) carries no weight
-            return pred, (torch.where(cnt > 0, mean * cnt, torch.zeros_like(mean)).sum() / cnt.sum()).float()
+            return (pred, (torch.where(cnt > 0, mean * cnt, torch.zeros_like(mean)).sum() / cnt.sum()).float()) + more
 
     def _add_torch(self, logits, mirrored, last):
         p = torch.softmax(_resample_exact(logits, mirrored, self.Ho, self.Wo), dim=1)
@@ -2671,8 +2794,12 @@ class ProbMerge:
             nan_check_(self.nan_flag, tot)
         pred = torch.argmax(tot, dim=1).to(torch.uint8)
         tgt = self.target
+        more = ()
+        if self.calibration is not None or self.confidence:
+            conf = _calibration_of_scores(self.calibration, tot / float(self.V), pred, tgt, self.ignore_index, self.C, self.confidence)
+            more = (conf,) if self.confidence else ()
         if tgt is None:
-            return pred, None
+            return (pred, None) + more
         if self.nan_flag is not None:
             _bad_label_bit(self.nan_flag, tgt, self.ignore_index, self.C)
         if self.counts is not None:
@@ -2684,10 +2811,10 @@ class ProbMerge:
         picked = (tot / float(self.V)).gather(1, tgt.long().clamp(max=self.C - 1).unsqueeze(1))[:, 0]
         ce = (-torch.log(picked))[counted].mean()
         bad = (counted & (tgt >= self.C)).any()
-        return pred, torch.where(bad, torch.full_like(ce, float('nan')), ce)
+        return (pred, torch.where(bad, torch.full_like(ce, float('nan')), ce)) + more
 
 
-def multiscale_merge(views, out_size, target=None, ignore_index=255, counts=None, nan_flag=None, confusion=None):
+def multiscale_merge(views, out_size, target=None, ignore_index=255, counts=None, nan_flag=None, confusion=None, calibration=None, confidence=False):
     """The multi-scale (and flip) ensemble of given logits: `views` is a list of (logits (N,C,h,w), mirrored) - the logits of one scale each, in the
     horizontally mirrored frame where `mirrored` is true; sizes may differ from view to view.  Every view is resampled onto the `out_size` = (Ho, Wo)
     grid by align-corners bilinear interpolation of the logits (a mirrored one mirrored back first), its softmax taken and the class probabilities
@@ -2695,7 +2822,9 @@ def multiscale_merge(views, out_size, target=None, ignore_index=255, counts=None
     summed probabilities; with `target` (N,Ho,Wo) `ce` is the 0-d mean of -log P[target] over target != ignore_index, `counts` (int64
     [3*classes+2], optional) gets the dsrl_seg_metrics table of pred ADDED and `confusion` (int64 [classes^2], optional) its confusion matrix;
     `nan_flag` (int32 scalar, optional): bit 0 a NaN logit in any view, bit 1 a label outside the classes.  Beyond pred the call allocates one
-    accumulator of N * classes * Ho * Wo floats (none for a single view) and the loss workspace."""
+    accumulator of N * classes * Ho * Wo floats (none for a single view) and the loss workspace.
+    `calibration` (int64 [3*bins], optional, needs a target) gets the reliability record of pred ADDED, `confidence=True` appends the confidence map
+    (float32 (N,Ho,Wo)) to the returned tuple: both by the last view's launch (dsrl_prob_merge_finish_ex)."""
     views = list(views)
     if not views:
         raise DsrlHipError('multiscale_merge: no views')
@@ -2703,7 +2832,8 @@ def multiscale_merge(views, out_size, target=None, ignore_index=255, counts=None
     _need_gpu(*(v[0] for v in views))
     if first.dim() != 4:
         raise DsrlHipError(f'4-D (N,C,H,W) tensor expected, got shape {tuple(first.shape)}')
-    merge = ProbMerge(len(views), first.shape[0], first.shape[1], out_size, first.device, target, ignore_index, counts, nan_flag, confusion)
+    merge = ProbMerge(len(views), first.shape[0], first.shape[1], out_size, first.device, target, ignore_index, counts, nan_flag, confusion, calibration,
+                      confidence)
     out = None
     for logits, mirrored in views:
         out = merge.add(logits, mirrored)

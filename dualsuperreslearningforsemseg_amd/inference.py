@@ -266,7 +266,11 @@ class CompiledPredictor:
         return c
 
     # ------------------------------------------------------------------ the call
-    def __call__(self, images, target=None, ignore_index=255, nan_flag=None, copy=True, flip=False, confusion=None, scales=None):
+    def __call__(self, images, target=None, ignore_index=255, nan_flag=None, copy=True, flip=False, confusion=None, scales=None, calibration=None,
+                 confidence=False):
+        if calibration is not None or confidence:
+            # graphs are keyed on their outputs: the calibration record and the confidence map are not among the keys
+            raise ValueError('CompiledPredictor: calibration and confidence are outputs of DSRL.predict only, not of a compiled predictor')
         if HF.multiscale_scales_value(scales) is not None:
             raise DsrlHipError(MULTISCALE_NOT_COMPILED)
         if self.frozen.released:

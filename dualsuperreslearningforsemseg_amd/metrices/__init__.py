@@ -190,6 +190,82 @@ class ConfusionMatrix:
         return figures(m)
 
 
+def calibration_figures(record):
+    """The figures of a calibration record [n_b | hit_b | q_b] (3 * bins integers; include/dsrl_hip.h "calibration"), float64, host only:
+    acc_b = hit_b / n_b, conf_b = q_b / (2^24 n_b), ECE = sum_b (n_b / N) |acc_b - conf_b|, MCE the maximum of |acc_b - conf_b| over the non-empty
+    bins, mean_confidence, accuracy (fractions in [0, 1]) and gap = mean_confidence - accuracy (> 0: over-confident).  -> dict with those and `bins`
+    = {'n' int64, 'acc', 'conf'} per bin (NaN where a bin is empty), `pixels` = N.  An empty record gives NaN figures."""
+    if isinstance(record, torch.Tensor):
+        record = record.detach().cpu().numpy()
+    rec = np.asarray(record)
+    if rec.size == 0 or rec.size % 3:
+        raise ValueError(f'calibration_figures: a record of 3 * bins integers expected, got {rec.size} elements')
+    rec = rec.astype(np.int64).reshape(3, -1)
+    n, hit, q = rec[0], rec[1], rec[2]
+    total = int(n.sum())
+    nf = n.astype(np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        acc = hit.astype(np.float64) / nf
+        conf = q.astype(np.float64) / (16777216.0 * nf)
+    bins = {'n': n.copy(), 'acc': acc, 'conf': conf}
+    if total == 0:
+        nan = float('nan')
+        return {'ECE': nan, 'MCE': nan, 'mean_confidence': nan, 'accuracy': nan, 'gap': nan, 'pixels': 0, 'bins': bins}
+    live = n > 0
+    gap = np.abs(acc[live] - conf[live])
+    mean_conf, accuracy = float(q.sum()) / (16777216.0 * total), float(hit.sum()) / total
+    return {'ECE': float((nf[live] / total * gap).sum()), 'MCE': float(gap.max()), 'mean_confidence': mean_conf, 'accuracy': accuracy,
+            'gap': mean_conf - accuracy, 'pixels': total, 'bins': bins}
+
+
+class Calibration:
+    """Expected / Maximum Calibration Error over a whole split (Guo et al. 2017): the reliability histogram of the maximum softmax probability over
+    `bins` equal-width bins.  Shaped like ConfusionMatrix: `.record` is the int64 [n_b | hit_b | q_b] buffer of 3 * bins elements, allocated on first
+    use on the device of what it is fed; every producer adds to it and none clears it, so it can be handed to `DSRL.predict(calibration=cal.record)`
+    batch after batch; result() does the one read."""
+
+    def __init__(self, bins=HF.CALIBRATION_DEFAULT_BINS, ignore_index=255):
+        self.bins, self.ignore_index = HF.calibration_bins_value(bins, 'Calibration'), int(ignore_index)
+        self._record = None
+
+    def _on(self, device):
+        if self._record is None:
+            self._record = torch.zeros(3 * self.bins, dtype=torch.int64, device=device)
+        elif self._record.device != torch.device(device):
+            raise ValueError(f'Calibration lives on {self._record.device}, fed from {device}')
+        return self._record
+
+    @property
+    def record(self):
+        if self._record is None:
+            raise ValueError('Calibration.record before first use: call on(device), update_from_logits() or merge() first')
+        return self._record
+
+    def on(self, device):
+        """-> .record, allocated on `device` if nothing has been fed yet"""
+        return self._on(torch.device(device))
+
+    def reset(self):
+        if self._record is not None:
+            self._record.zero_()
+
+    def update_from_logits(self, logits, target):
+        """logits (N, C, H, W), target (N, H, W): one streaming pass (dsrl_calibration_from_logits), nothing read back"""
+        HF._need_gpu(logits, target)
+        HF.calibration_counts_(self._on(logits.device), logits, target, self.ignore_index, self.bins)
+
+    def merge(self, other):
+        """adds another Calibration or an int64 tensor of 3 * bins elements; a host tensor is taken as it is (and so is its device)"""
+        r = other.record if isinstance(other, Calibration) else other
+        if r.dtype != torch.int64 or r.numel() != 3 * self.bins:
+            raise ValueError(f'merge: an int64 tensor of {3 * self.bins} elements expected, got {r.dtype} of {r.numel()}')
+        self._on(r.device).add_(r.reshape(-1))
+
+    def result(self):
+        """The one device read -> calibration_figures(record); nothing fed: NaN figures"""
+        return calibration_figures(np.zeros(3 * self.bins, np.int64) if self._record is None else self._record)
+
+
 class SRQuality:
     """PSNR (dB, data range 1) and SSIM of super-resolved images against their originals over a whole split (functional.sr_quality): `mean` / `std`
     are the normalisation the tensors carry (dataset settings' MEAN / STD; None: values in [0, 1] already).  Every update leaves one (N, 2) float64

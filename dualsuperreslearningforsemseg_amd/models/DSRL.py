@@ -135,7 +135,7 @@ class DSRL(BaseModel):
             return self.forward_head(backbone_features, lowlevel_features)
 
     def predict_head(self, backbone_features: t.Tensor, lowlevel_features: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None,
-                     flip: bool = False, confusion: t.Tensor = None):
+                     flip: bool = False, confusion: t.Tensor = None, calibration: t.Tensor = None, confidence: bool = False):
         """Inference counterpart of forward_head: the SSSR branch in eval mode down to the bilinear x2 of `upsample16_pred`, then its ConvTranspose ->
         BatchNorm -> ReLU -> ConvTranspose tail and the arg-max as one kernel (functional.sssr_tail_predict) -> (pred uint8 (N,H,W), counts, ce).
         With `target` (N,H,W): `counts` is the int64 table of dsrl_seg_metrics of this batch (metrices.mIoU / Accuracy.update_from_counts), a fresh
@@ -144,7 +144,10 @@ class DSRL(BaseModel):
         cleared here: one buffer collects a whole split.  `nan_flag` (int32 device scalar) collects bit 0 = NaN logit, bit 1 = label outside
         the classes; nothing is read back here.  Neither the SISR decoder nor the feature transformers run, whatever the stage.
         `flip=True`: the features are those of 2N images, the second half from the horizontally mirrored images; the tail kernel mirrors that half back
-        and averages the two views' class probabilities -> N class maps (functional.sssr_tail_predict(flip=True)), `target` (N,H,W)."""
+        and averages the two views' class probabilities -> N class maps (functional.sssr_tail_predict(flip=True)), `target` (N,H,W).
+        `calibration` (int64 device tensor of 3 * bins elements, needs a target; metrices.Calibration.record) gets this batch's reliability record
+        ADDED by the same kernel; `confidence=True` appends the confidence map (float32 (N,H,W): the probability of the reported class) to the
+        returned tuple.  Without them every launch is the one of a call that does not know them."""
         if self.training:
             raise HF.DsrlHipError('DSRL.predict* is inference: call model.eval() first')
         with t.no_grad():
@@ -158,12 +161,12 @@ class DSRL(BaseModel):
             counts = None
             if target is not None:
                 counts = t.zeros(3 * up[6].out_channels + 2, dtype=t.int64, device=y.device)
-            pred, ce = HF.sssr_tail_predict(y, up[2], up[3], up[6], target=target, ignore_index=ignore_index, counts=counts, nan_flag=nan_flag, flip=flip,
-                                            confusion=confusion)
-        return pred, counts, ce
+            out = HF.sssr_tail_predict(y, up[2], up[3], up[6], target=target, ignore_index=ignore_index, counts=counts, nan_flag=nan_flag, flip=flip,
+                                       confusion=confusion, calibration=calibration, confidence=confidence)
+        return (out[0], counts, out[1]) + tuple(out[2:])
 
     def predict(self, x: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None, flip: bool = False,
-                confusion: t.Tensor = None, scales=None):
+                confusion: t.Tensor = None, scales=None, calibration: t.Tensor = None, confidence: bool = False):
         """Class map of a batch: (pred, counts or None, ce or None), see predict_head.  Runs under no_grad and raises in train mode.  Without a
         `nan_flag` of the caller's the flag is read back here and a NaN logit or an out-of-range label raises; a caller that passes one reads it when
         it chooses to (command_handlers.benchmark: once, after the last batch).
@@ -174,14 +177,17 @@ class DSRL(BaseModel):
         multi-scale ensemble.  For each scale in turn the images are resized to the multiple of 16 nearest to scale x size (align corners), the SSSR
         logits of the eval forward path are written (with `flip` for the image and its mirror image in one batch), merged into the ensemble and
         released before the next scale runs (functional.ProbMerge: the logits of every view resampled to the output grid, softmax, class probabilities
-        averaged); pred, counts, ce, confusion and the NaN flag are those of the ensemble."""
+        averaged); pred, counts, ce, confusion and the NaN flag are those of the ensemble.
+        `calibration`, `confidence`: see predict_head; with `flip` and `scales` they are the record and the confidence map of the ensemble."""
         if self.training:
             raise HF.DsrlHipError('DSRL.predict* is inference: call model.eval() first')
         if confusion is not None and target is None:
             raise HF.DsrlHipError('DSRL.predict: confusion needs a target')
+        if calibration is not None and target is None:
+            raise HF.DsrlHipError('DSRL.predict: calibration needs a target')
         scales = HF.multiscale_scales_value(scales)
         if scales is not None:
-            return self._predict_multiscale(x, target, ignore_index, nan_flag, flip, confusion, scales)
+            return self._predict_multiscale(x, target, ignore_index, nan_flag, flip, confusion, scales, calibration, confidence)
         own = nan_flag is None
         with t.no_grad():
             if own:
@@ -193,7 +199,7 @@ class DSRL(BaseModel):
                 both[x.shape[0]:].copy_(x.flip(3))          # 3 channels at input size: torch ops
                 x = both
             backbone_features, lowlevel_features = self.feature_extractor['backbone'](x)
-            out = self.predict_head(backbone_features, lowlevel_features, target, ignore_index, nan_flag, flip, confusion)
+            out = self.predict_head(backbone_features, lowlevel_features, target, ignore_index, nan_flag, flip, confusion, calibration, confidence)
         if own:
             bits = int(nan_flag.item())
             if bits:
@@ -238,8 +244,8 @@ class DSRL(BaseModel):
         cat_features = HF.cat_channels([aspp_features, fe['shortcut_conv'](lowlevel_features)])    # DSRL.py:164-165
         return dec['upsample16_pred'](dec['cls_conv'](dec['cat_conv'](cat_features)))         # DSRL.py:168-170
 
-    def _predict_multiscale(self, x, target, ignore_index, nan_flag, flip, confusion, scales):
-        HF._need_gpu(x, target, nan_flag, confusion)
+    def _predict_multiscale(self, x, target, ignore_index, nan_flag, flip, confusion, scales, calibration=None, confidence=False):
+        HF._need_gpu(x, target, nan_flag, confusion, calibration)
         if x.dim() != 4 or x.shape[2] % 16 or x.shape[3] % 16:
             raise HF.DsrlHipError(f'DSRL.predict: (N,3,H,W) images with H and W multiples of 16 expected, got shape {tuple(x.shape)}')
         N, _, H, W = x.shape
@@ -251,7 +257,8 @@ class DSRL(BaseModel):
             HF.nan_check_(nan_flag, x)          # once, on the images as given: every view is interpolated from them
             classes = self.SSSR_decoder['upsample16_pred'][6].out_channels
             counts = t.zeros(3 * classes + 2, dtype=t.int64, device=x.device) if target is not None else None
-            merge = HF.ProbMerge(len(sizes) * (2 if flip else 1), N, classes, (2 * H, 2 * W), x.device, target, ignore_index, counts, nan_flag, confusion)
+            merge = HF.ProbMerge(len(sizes) * (2 if flip else 1), N, classes, (2 * H, 2 * W), x.device, target, ignore_index, counts, nan_flag, confusion,
+                                 calibration, confidence)
             out = None
             for size in sizes:
                 xk = HF.resize_image_ac(x, size)
@@ -271,7 +278,7 @@ class DSRL(BaseModel):
             bits = int(nan_flag.item())
             if bits:
                 raise HF.DsrlHipError('DSRL.predict: ' + ' and '.join(m for b, m in ((1, 'NaN in the input or the logits'), (2, 'labels outside the classes')) if bits & b))
-        return out[0], counts, out[1]
+        return (out[0], counts, out[1]) + tuple(out[2:])
 
     def compile_predict(self, batch_size=None, input_size=None, graph=True):
         """-> inference.CompiledPredictor: `predict` on operands prepared once (inference.FrozenOperands: filter amax records, pre-split filters, fp16

@@ -795,6 +795,49 @@ int dsrl_prob_merge_finish(const float* logits, int ld, int N, int Hs, int Ws, i
                            unsigned long long* counts /*nullable*/, float* ce_out /*nullable, [2]: mean, counted pixels*/, int* nan_flag /*nullable*/,
                            void* ws, size_t ws_bytes, unsigned long long* cm /*nullable, [C*C]*/, dsrl_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * calibration: the reliability record and the confidence map (csrc/calibration.hip; the arithmetic is written once in csrc/common.h)
+ *   Confidence of a pixel: the probability of the class the producer reports (first maximum), fp32, from values it already has -
+ *     from logits and the single-view tail: 1 / sum_c exp(v_c - max) (the sum the cross entropy forms, c ascending);
+ *     the flip tail: the winning entry of (ea_c / sa + eb_c / sb) / 2;   the multi-scale finish: min(1, winning sum / views).
+ *   Bin: B equal-width bins, 1 <= B <= dsrl_calibration_max_bins() = 64; b = min(B - 1, (int)(conf * (float)B)), one fp32 multiply.
+ *   Record: int64 [3 B] = [n_b | hit_b | q_b], ADDED: counted pixels of bin b (target != ignore_index and target < C: the pixels of the confusion
+ *   matrix), those with pred == target, and sum rintf(conf * 2^24) as an integer.  A pixel whose confidence is NaN is counted nowhere (it raises
+ *   bit 0 of nan_flag).  Integers only: per-block LDS counters (q in 64 bits), one 64-bit atomic per block and non-zero entry - a record is
+ *   bit-identical run to run and, up to the summation of records, for an image alone or in a batch.
+ *   Figures (host, float64): acc_b = hit_b / n_b, conf_b = q_b / (2^24 n_b), ECE = sum_b (n_b / N) |acc_b - conf_b|, MCE = the maximum over
+ *   the non-empty bins.
+ * dsrl_calibration_from_logits: logits (P, C) pixel-major with pixel stride ld, C <= 60 (the addressing of dsrl_seg_metrics), one streaming
+ *   launch.  record (nullable, needs target) and conf_map (nullable, P floats, written for every pixel) - at least one; nan_flag (nullable):
+ *   |= 1 for a NaN logit, |= 2 for a label >= C that is not ignore_index (record only).  logits and conf_map 4-byte, record 8-byte aligned.
+ * dsrl_sssr_tail_predict_ex / _flip_ex / dsrl_prob_merge_finish_ex: the launches of dsrl_sssr_tail_predict_cm / _flip_cm /
+ *   dsrl_prob_merge_finish with every optional output: cm, cal (the record, [3 * bins]; needs a target) and conf (the confidence map, the shape
+ *   of pred, fp32; needs no target; 16-byte aligned for the tails, 4-byte for the finish) are nullable.  With cal and conf null they ARE those
+ *   launches; with them pred, counts, ce_out, cm and nan_flag are bit-identical to theirs.  In the tails a NaN in front of the ReLU (which hides
+ *   it from the logits) makes the confidence of the input pixel's 4x4 patch NaN.
+ * ---------------------------------------------------------------------------------------------- */
+int dsrl_calibration_max_bins(void);
+int dsrl_calibration_from_logits(const float* logits, int ld, const uint8_t* target /*nullable*/, int64_t P, int C, int ignore_index, int bins,
+                                 unsigned long long* record /*nullable, [3*bins]*/, float* conf_map /*nullable, [P]*/, int* nan_flag /*nullable*/,
+                                 dsrl_stream_t stream);
+int dsrl_sssr_tail_predict_ex(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                              const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2 /*nullable*/,
+                              uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index, unsigned long long* counts /*nullable*/,
+                              float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes,
+                              unsigned long long* cm /*nullable, [Cout*Cout]*/, unsigned long long* cal /*nullable, [3*bins]*/, int bins,
+                              float* conf /*nullable, (N,4H,4W)*/, dsrl_stream_t stream);
+int dsrl_sssr_tail_predict_flip_ex(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                                   const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2 /*nullable*/,
+                                   uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index, unsigned long long* counts /*nullable*/,
+                                   float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes,
+                                   unsigned long long* cm /*nullable, [Cout*Cout]*/, unsigned long long* cal /*nullable, [3*bins]*/, int bins,
+                                   float* conf /*nullable, (N,4H,4W)*/, dsrl_stream_t stream);
+int dsrl_prob_merge_finish_ex(const float* logits, int ld, int N, int Hs, int Ws, int C, int mirror, const float* acc /*nullable: the only view*/, int Ho,
+                              int Wo, int views, uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index,
+                              unsigned long long* counts /*nullable*/, float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes,
+                              unsigned long long* cm /*nullable, [C*C]*/, unsigned long long* cal /*nullable, [3*bins]*/, int bins,
+                              float* conf /*nullable, (N,Ho,Wo)*/, dsrl_stream_t stream);
+
 /* Fingerprint of tensors that must not change while an inference.FrozenOperands holds operands derived from them (a write through `.data` or a
  * raw pointer moves neither a tensor's address nor its version counter).  table: DEVICE array of nseg rows of 2 int64 {pointer (4-byte aligned),
  * number of 32-bit words <= dsrl_fingerprint_segment_words()}, one block per row; a tensor is cut into as many rows as it needs.  Row r gets
