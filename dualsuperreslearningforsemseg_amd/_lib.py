@@ -205,6 +205,12 @@ PROTOTYPES = {
     'dsrl_prob_merge_finish_ex': (i32, [fp, i32] + [i32] * 5 + [fp, i32, i32, i32, fp, fp, i32, fp, fp, fp, fp, sz, fp, fp, i32, fp, stream_t]),
     'dsrl_calibration_max_bins': (i32, []),
     'dsrl_calibration_from_logits': (i32, [fp, i32, fp, i64, i32, i32, i32, fp, fp, fp, stream_t]),
+    'dsrl_temperature_max_points': (i32, []),
+    'dsrl_temperature_workspace_bytes': (sz, [i64, i32]),
+    'dsrl_temperature_stats': (i32, [fp, i32, fp, i64, i32, i32, fp, i32, fp, fp, fp, sz, stream_t]),
+    'dsrl_sssr_tail_predict_t': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, fp, fp, i32, fp, f32, stream_t]),
+    'dsrl_sssr_tail_predict_flip_t': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, fp, fp, i32, fp, f32, stream_t]),
+    'dsrl_calibration_from_logits_t': (i32, [fp, i32, fp, i64, i32, i32, i32, fp, fp, fp, f32, stream_t]),
     'dsrl_sr_quality_workspace_bytes': (sz, [i32] * 4),
     'dsrl_sr_quality': (i32, [fp, i32, fp, i32, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), fp, fp, fp, sz, stream_t]),
     'dsrl_boundary_counts_max_classes': (i32, []),

@@ -27,6 +27,13 @@ the same single read: the result gains 'ECE', 'MCE', 'mean_confidence' (fraction
 benchmark.txt a reliability table and one summary line.  Combines with `flip`, `scales`, `ema`, `boundary` and `sisr`, not with `compiled_model`
 (graphs are keyed on their outputs); anything but True, False, None or an integer from 1 to functional.calibration_max_bins() is a ValueError
 before any device work.
+`temperature=<number>`, `temperature=<path of a temperature.json>` (command_handlers.fit_temperature) or `temperature='fit'` in other_args:
+temperature scaling - every batch is evaluated as `DSRL.predict(temperature=T)`, the model that reports softmax(logits / T).  'CE', 'ECE', 'MCE' and
+'mean_confidence' are then those of the scaled model (the class maps and every figure counted from them do not change), the result gains
+'temperature' and benchmark.txt one line naming T.  `'fit'` first fits T on the evaluated split itself (the two passes of fit_temperature), and
+benchmark.txt says that the figure is in-sample.  Combines with `flip`, `ema`, `boundary`, `calibration` and `sisr`, not with `scales` or
+`compiled_model`; a clash, a bad number or a file that is not a temperature.json is a ValueError before any device work.  Without the key the
+command makes exactly the calls it makes without it.
 Beside the reference's per-batch figures the command accumulates ONE confusion matrix over the split on the device (the kernel that writes the
 class map fills it; it comes back in the same single read) and reports the dataset-level figures from it - intersections and unions summed over the
 split, then IoU per class, then the mean over the classes, as Cityscapes results are published - with a per-class table in benchmark.txt and the
@@ -41,7 +48,7 @@ import torch as t
 from .. import settings
 from .._lib import DsrlHipError
 from ..functional import (CALIBRATION_DEFAULT_BINS, boundary_counts_, boundary_distance, calibration_bins_value, multiscale_scales_value,
-                          multiscale_sizes, nan_check_)
+                          multiscale_sizes, nan_check_, temperature_value)
 from ..metrices import Accuracy, AverageMeter, BoundaryIoU, ConfusionMatrix, SRQuality, calibration_figures, mIoU
 from ..models import DSRL
 from ..utils import load_checkpoint_or_weights
@@ -99,10 +106,29 @@ def calibration_bins_arg(value):
     return calibration_bins_value(value, 'benchmark: calibration')
 
 
+def temperature_arg(value):
+    """other_args['temperature'] -> None when the key is absent, 'fit', or the temperature as a float: a number is itself (1 included: the model as
+    it is), any other string names a temperature.json of fit_temperature, which is read here; anything else is a ValueError"""
+    if value is None:
+        return None
+    if isinstance(value, (str, os.PathLike)):
+        if value == 'fit':
+            return 'fit'
+        from .fit_temperature import read_temperature_file
+        value = read_temperature_file(value)
+    T = temperature_value(value, 'benchmark')
+    return 1.0 if T is None else T
+
+
 def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
     scales = multiscale_scales_value(other_args.get('scales'))          # ValueError on a bad value, before any device work
     boundary = boundary_ratio_value(other_args.get('boundary'))
     cal_bins = calibration_bins_arg(other_args.get('calibration'))
+    temperature = temperature_arg(other_args.get('temperature'))
+    if temperature is not None:
+        clash = [k for k, on in (('scales', scales is not None), ('compiled_model', other_args.get('compiled_model'))) if on]
+        if clash:
+            raise ValueError(f"benchmark: temperature does not combine with {', '.join(clash)} (the multi-scale merge and compiled graphs take no temperature)")
     if cal_bins is not None and other_args.get('compiled_model'):
         raise ValueError('benchmark: calibration does not combine with compiled_model (compiled graphs are keyed on their outputs)')
     sisr = bool(other_args.get('sisr'))
@@ -130,6 +156,12 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
     flip = bool(other_args.get('flip'))
     if scales is not None:
         predict = functools.partial(predict, scales=scales)
+    fitted = None
+    if temperature == 'fit':
+        from .fit_temperature import fit_passes
+        fitted = fit_passes(model, lambda: split_loader(dataset, split, batch_size, device_obj, input_size), ds.IGNORE_CLASS_LABEL, device_obj)
+        temperature = fitted['temperature']
+    temp_kw = {} if temperature is None or temperature == 1.0 else {'temperature': temperature}     # without the key: the calls of a command that does not know it
     loader = split_loader(dataset, split, batch_size, device_obj, input_size)
 
     nan_flag = t.zeros((), dtype=t.int32, device=device_obj)
@@ -147,11 +179,11 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
                 with t.no_grad():       # DSRL.predict with the trunk's features kept for the other branch
                     nan_check_(nan_flag, input_image)
                     features = model.feature_extractor['backbone'](input_image)
-                    pred, counts, ce = model.predict_head(*features, target, ds.IGNORE_CLASS_LABEL, nan_flag, False, confusion, **cal_kw)
+                    pred, counts, ce = model.predict_head(*features, target, ds.IGNORE_CLASS_LABEL, nan_flag, False, confusion, **cal_kw, **temp_kw)
                     quality.update(model.super_resolve_head(*features), input_org)
             else:
                 pred, counts, ce = predict(input_image, target, ignore_index=ds.IGNORE_CLASS_LABEL, nan_flag=nan_flag, flip=flip, confusion=confusion,
-                                          **cal_kw)
+                                          **cal_kw, **temp_kw)
             if boundary is not None:
                 boundary_counts_(band_counts, pred, target, nc, ds.IGNORE_CLASS_LABEL, ratio=boundary, nan_flag=nan_flag)
                 band_distances.append(boundary_distance(pred.shape[-2], pred.shape[-1], boundary))
@@ -239,6 +271,13 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
         lines.append('Expected calibration error: {:.4f}, maximum: {:.4f}, mean confidence: {:.4f} against accuracy {:.4f} ({:s})'.format(
             cfig['ECE'], cfig['MCE'], cfig['mean_confidence'], cfig['accuracy'],
             'over-confident' if cfig['gap'] > 0 else 'under-confident' if cfig['gap'] < 0 else 'no gap'))
+    if temperature is not None:
+        result['temperature'] = float(temperature)
+        lines += ['', 'Temperature scaling: T = {:.4f}{:s}; cross entropy{:s} of softmax(logits / T)'.format(
+            float(temperature),
+            '' if fitted is None else ', fitted on this {:s} split itself (in-sample: NLL {:.4f} -> {:.4f} over {:d} pixels{:s})'.format(
+                split, fitted['nll_before'], fitted['nll_after'], fitted['pixels'], ', at a bound of the search interval' if fitted['at_bound'] else ''),
+            '' if cal_record is None else ', calibration errors and confidence')]
     print('-------- RESULTS --------')
     for ln in lines:
         print(ln)

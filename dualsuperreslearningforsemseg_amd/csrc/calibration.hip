@@ -17,10 +17,13 @@ namespace {
 constexpr int kCalMaxC = 60;            // 256 * C staged floats within the default 64 KB of LDS, as dsrl_seg_metrics
 constexpr int kCalBlocks = 1024;
 
+// TEMP (dsrl_calibration_from_logits_t): behind the first-maximum search the pixel's logits become v_c * beta in place (temperature_scale), and the
+// confidence is that of softmax(beta v) through the same arithmetic - what the TEMP builds of the fused tail (predict.hip) report, bit for bit.
+template <bool TEMP>
 __global__ __launch_bounds__(256) void calibration_from_logits_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target,
                                                                       int nchunks, int last_np, int C, int ignore_index, int B,
                                                                       unsigned long long* __restrict__ record, float* __restrict__ conf_map,
-                                                                      int* __restrict__ nan_flag) {
+                                                                      int* __restrict__ nan_flag, float beta) {
     extern __shared__ float tile[];                     // [256][C] logits
     __shared__ CalBins bins;
     const int tid = threadIdx.x;
@@ -39,11 +42,13 @@ __global__ __launch_bounds__(256) void calibration_from_logits_kernel(const floa
         }
         __syncthreads();
         if (tid < np) {
-            const float* v = tile + tid * C;
+            float* v = tile + tid * C;
             int best = 0;
             float bv = v[0];
             for (int c = 1; c < C; ++c)
                 if (v[c] > bv) { bv = v[c]; best = c; }             // first maximum, as seg_metrics_kernel and torch.argmax
+            if (TEMP)
+                for (int c = 0; c < C; ++c) v[c] = temperature_scale(v[c], beta);
             const float conf = confidence_pixel(softmax_denominator<0>(v, C));
             bad |= !(conf == conf);                                 // any NaN logit poisons the sum
             if (conf_map != nullptr) (conf_map + p0)[tid] = conf;
@@ -70,8 +75,9 @@ using namespace dsrl;
 
 extern "C" int dsrl_calibration_max_bins(void) { return kCalMaxBins; }
 
-extern "C" int dsrl_calibration_from_logits(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, int B,
-                                            unsigned long long* record, float* conf_map, int* nan_flag, dsrl_stream_t stream) {
+// both entry points: `temp` selects the build that scales the logits by beta
+static int calibration_launch(bool temp, float beta, const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, int B,
+                              unsigned long long* record, float* conf_map, int* nan_flag, dsrl_stream_t stream) {
     DSRL_REQUIRE(logits && P > 0 && C > 0 && ld >= C && (record || conf_map), DSRL_E_BADARG,
                  "calibration_from_logits: null logits, empty shape, ld < C, or neither a record nor a confidence map (C=%d)", C);
     DSRL_REQUIRE(!record || target, DSRL_E_BADARG, "calibration_from_logits: the record needs a target");
@@ -85,7 +91,23 @@ extern "C" int dsrl_calibration_from_logits(const float* logits, int ld, const u
     if (int e = bind_stream_device(st)) return e;
     const int nchunks = (int)ceil_div(P, 256), last_np = (int)(P - (int64_t)(nchunks - 1) * 256);
     const int nb = std::min(kCalBlocks, nchunks);
-    hipLaunchKernelGGL(calibration_from_logits_kernel, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, nchunks, last_np, C,
-                       ignore_index, record ? B : 1, record, conf_map, nan_flag);
+    if (temp)
+        hipLaunchKernelGGL(calibration_from_logits_kernel<true>, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, nchunks,
+                           last_np, C, ignore_index, record ? B : 1, record, conf_map, nan_flag, beta);
+    else
+        hipLaunchKernelGGL(calibration_from_logits_kernel<false>, dim3(nb), dim3(256), (size_t)256 * C * sizeof(float), st, logits, ld, target, nchunks,
+                           last_np, C, ignore_index, record ? B : 1, record, conf_map, nan_flag, 1.f);
     return launch_status("calibration_from_logits_kernel");
+}
+
+extern "C" int dsrl_calibration_from_logits(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, int B,
+                                            unsigned long long* record, float* conf_map, int* nan_flag, dsrl_stream_t stream) {
+    return calibration_launch(false, 1.f, logits, ld, target, P, C, ignore_index, B, record, conf_map, nan_flag, stream);
+}
+
+// the record and the map of softmax(beta v), beta = 1 / T a finite number > 0 (include/dsrl_hip.h, "temperature")
+extern "C" int dsrl_calibration_from_logits_t(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, int B,
+                                              unsigned long long* record, float* conf_map, int* nan_flag, float beta, dsrl_stream_t stream) {
+    DSRL_TEMPERATURE_BETA(beta, "calibration_from_logits_t");
+    return calibration_launch(true, beta, logits, ld, target, P, C, ignore_index, B, record, conf_map, nan_flag, stream);
 }

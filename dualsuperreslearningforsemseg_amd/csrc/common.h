@@ -274,6 +274,61 @@ struct CalBins {
     }
 };
 
+// ---------------------------------------------------------------- temperature scaling (temperature.hip)
+// The NLL of softmax(beta v) at the label t of one live pixel, with its first and second derivative in beta = 1 / T, fp32, c ascending.  The caller
+// passes d_c = v_c - m (m the fmaxf chain from v_0, so d_c <= 0) and dt = d_t:
+//     e_c = exp_nonpos(beta d_c), s = sum e_c, a = sum e_c d_c, q = sum (e_c d_c) d_c
+//     L = log_ge1(s) - beta dt,  mu = a / s,  G = mu - dt = dL/dbeta,  H = q / s - mu mu = d2L/dbeta2 (the variance of d under softmax(beta v), >= 0)
+// Every producer of a temperature record goes through this function, so that they round alike (no contraction: -ffp-contract=off).
+// The logarithm is log_ge1, not logf: the device's logf (v_log_f32 underneath) came out 3.1e-8 relative LOW on average when measured alone (sum of
+// logf(m), m = 1..19, over 30720 pixels against float64; numpy's float32 log: +8e-9), and a sum over 10^5 - 10^6 pixels keeps such a bias where it
+// averages rounding out: the L entries were 1.9e-9 - 2.3e-8 off against 2e-10 - 1.6e-9 for a float32 restatement.  log_ge1 is the float32 polynomial
+// of the Cephes logf (s = m 2^e with m in [sqrt(1/2), sqrt(2)), degree 9 in m - 1, ln 2 in two parts): about 25 instructions, within 8.1e-8 relative
+// for s >= 1.1 and 4.1e-9 absolute below, mean error 8e-10 (2.4 M samples of [1, 19] against float64).  s >= 1 here: the maximum's term is exp(0).
+__device__ __forceinline__ float log_ge1(float s) {
+    int ei;
+    float m = frexpf(s, &ei);                   // s = m 2^ei, m in [0.5, 1)
+    float e = (float)ei;
+    const bool lo = m < 0.707106769084930419921875f;
+    e = lo ? e - 1.f : e;
+    const float x = lo ? (m + m) - 1.f : m - 1.f;
+    const float z = x * x;
+    float y = 7.0376836292e-2f;
+    y = y * x + -1.1514610310e-1f;
+    y = y * x + 1.1676998740e-1f;
+    y = y * x + -1.2420140846e-1f;
+    y = y * x + 1.4249322787e-1f;
+    y = y * x + -1.6668057665e-1f;
+    y = y * x + 2.0000714765e-1f;
+    y = y * x + -2.4999993993e-1f;
+    y = y * x + 3.3333331174e-1f;
+    y = y * x * z;
+    y = y + -2.12194440e-4f * e;
+    y = y + -0.5f * z;
+    return (x + y) + 0.693359375f * e;
+}
+__device__ __forceinline__ void temperature_terms(const float* d, int C, float dt, float beta, float& L, float& G, float& H) {
+    float s = 0.f, a = 0.f, q = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float dc = d[c];
+        const float e = exp_nonpos(beta * dc);
+        const float ed = e * dc;
+        s += e;
+        a += ed;
+        q += ed * dc;
+    }
+    const float mu = a / s;
+    L = log_ge1(s) - beta * dt;
+    G = mu - dt;
+    H = q / s - mu * mu;
+}
+// Applying a temperature in a producer: behind its arg-max every logit becomes v_c * beta (one fp32 multiply), then the softmax arithmetic that is
+// already there runs on the result.  A positive beta is monotone under rounding, so the first maximum - the class map - does not move.
+__device__ __forceinline__ float temperature_scale(float v, float beta) { return v * beta; }
+// beta as every entry point that applies one wants it: a finite number > 0 (a NaN fails the comparison)
+#define DSRL_TEMPERATURE_BETA(beta, what) \
+    DSRL_REQUIRE((beta) > 0.f && (beta) <= 3.402823466e+38f, DSRL_E_BADARG, what ": beta = %g is not a finite number > 0", (double)(beta))
+
 // ---------------------------------------------------------------- wave / block reductions
 __device__ inline float wave_sum(float v) {
 #pragma unroll

@@ -30,7 +30,10 @@ using f32x4_p = __attribute__((ext_vector_type(4))) float;
 // 16-byte store per lane - the four columns of a patch row assembled with the lane 16 away, as the class bytes are.  Both take the confidence from the
 // softmax denominator the loss forms (CE) or form it the same way (softmax_denominator); a patch whose input pixel held a NaN in front of the ReLU has
 // NaN confidence (the ReLU hides it from the logits): in no bin, NaN in the map.  Without them the kernel is the one that does not know them.
-template <bool TGT, bool CE, bool CM, bool CAL = false, bool CONF = false>
+// TEMP: temperature scaling (common.h: temperature_scale) - behind the arg-max the 19 logits in registers become v_c * beta, and the loss, the
+// confidence and the calibration bins come from the scaled values through the code that is there; the class map and the counters do not change.
+// (In the flip kernel each view's logits are scaled in front of that view's max / exp: the ensemble is that of the scaled model.)
+template <bool TGT, bool CE, bool CM, bool CAL = false, bool CONF = false, bool TEMP = false>
 __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w1,
                                                                     const float* __restrict__ bn_mean, const float* __restrict__ bn_invstd,
                                                                     const float* __restrict__ bn_gamma, const float* __restrict__ bn_beta,
@@ -38,7 +41,7 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
                                                                     unsigned char* __restrict__ pred, const unsigned char* __restrict__ target, int ignore_index,
                                                                     unsigned long long* __restrict__ counts, double* __restrict__ part, int* __restrict__ nan_flag,
                                                                     int H, int W, long long P, int ntiles, unsigned long long* __restrict__ cm,
-                                                                    unsigned long long* __restrict__ cal, int B, float* __restrict__ conf) {
+                                                                    unsigned long long* __restrict__ cal, int B, float* __restrict__ conf, float beta) {
     static_assert(!CM || TGT, "the confusion matrix needs a target");
     static_assert(!CAL || TGT, "the calibration record needs a target");
     __shared__ unsigned hist[3 * kPC + 2];
@@ -144,7 +147,11 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
             // this one's softmax arithmetic and spills one register.  An empty asm statement keeps their order, as in the flip kernel: the first k-step's
             // operand passes through one that needs the class byte of the pixel before.
             float m0 = mid[0][T];
-            if (CONF && !TGT) asm volatile("" : "+v"(packed), "+v"(m0));
+            // (The TEMP build holds one value more per pixel, beta, and spilled again: there the operand also waits for the confidence of the pixel before.)
+            if (CONF && !TGT) {
+                if (TEMP && T > 0) asm volatile("" : "+v"(packed), "+v"(m0), "+v"(cf[T - 1]));
+                else asm volatile("" : "+v"(packed), "+v"(m0));
+            }
 #pragma unroll
             for (int s = 0; s < kPT; ++s)
 #pragma unroll
@@ -161,6 +168,10 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
             if (!CE) {
 #pragma unroll
                 for (int c = 0; c < kPC; ++c) nanbits = max(nanbits, valid ? abs_bits(v[c]) : 0u);
+            }
+            if (TEMP) {         // softmax(beta v): the class above is that of v (beta > 0 is monotone under rounding); loss and confidence below are the scaled model's
+#pragma unroll
+                for (int c = 0; c < kPC; ++c) v[c] = temperature_scale(v[c], beta);
             }
             float csum = 0.f;
             if ((CAL || CONF) && !CE) csum = softmax_denominator<kPC>(v, kPC);
@@ -254,7 +265,7 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_kernel(const float* 
 // ea_c / sa + eb_c / sb, the loss -(logaddexp(la_t, lb_t) - ln 2) of the two log-softmax values in log space (finite where the averaged probability
 // underflows).  View a is reduced to its 19 probabilities before view b's accumulators are formed, so only one set of accumulators is live at a time.
 // Counters, partials, NaN flag and the byte assembly are those of sssr_tail_predict_kernel.
-template <bool TGT, bool CE, bool CM, bool CAL = false, bool CONF = false>
+template <bool TGT, bool CE, bool CM, bool CAL = false, bool CONF = false, bool TEMP = false>
 __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w1,
                                                                          const float* __restrict__ bn_mean, const float* __restrict__ bn_invstd,
                                                                          const float* __restrict__ bn_gamma, const float* __restrict__ bn_beta,
@@ -263,7 +274,7 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const fl
                                                                          int ignore_index, unsigned long long* __restrict__ counts, double* __restrict__ part,
                                                                          int* __restrict__ nan_flag, int H, int W, long long P, int ntiles,
                                                                          unsigned long long* __restrict__ cm, unsigned long long* __restrict__ cal, int B,
-                                                                         float* __restrict__ conf) {
+                                                                         float* __restrict__ conf, float beta) {
     static_assert(!CM || TGT, "the confusion matrix needs a target");
     static_assert(!CAL || TGT, "the calibration record needs a target");
     __shared__ unsigned hist[3 * kPC + 2];
@@ -369,7 +380,7 @@ __global__ __launch_bounds__(256, 2) void sssr_tail_predict_flip_kernel(const fl
 #pragma unroll
             for (int t = 0; t < kPT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[t][s], mid[s][T], acc[t], 0, 0, 0);
 #pragma unroll
-        for (int c = 0; c < kPC; ++c) v[c] = acc[c >> 2][c & 3];
+        for (int c = 0; c < kPC; ++c) v[c] = TEMP ? temperature_scale(acc[c >> 2][c & 3], beta) : acc[c >> 2][c & 3];
         float m = v[0], vt = v[0];
 #pragma unroll
         for (int c = 1; c < kPC; ++c) {
@@ -588,7 +599,8 @@ namespace {
 int tail_predict_launch(bool flip, const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
                         const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2, uint8_t* pred,
                         const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag, void* ws, size_t ws_bytes,
-                        unsigned long long* cm, unsigned long long* cal, int bins, float* conf, dsrl_stream_t stream) {
+                        unsigned long long* cm, unsigned long long* cal, int bins, float* conf, dsrl_stream_t stream, bool temp = false,
+                        float beta = 1.f) {
     DSRL_REQUIRE(x && w1 && bn_mean && bn_invstd && bn_gamma && bn_beta && w2 && pred && N > 0 && H > 0 && W > 0, DSRL_E_BADARG,
                  "sssr_tail_predict: null pointer or empty shape");
     DSRL_REQUIRE(dsrl_sssr_tail_predict_supported(N, H, W, Cin, Cmid, Cout), DSRL_E_UNSUPPORTED,
@@ -607,9 +619,15 @@ int tail_predict_launch(bool flip, const float* x, int ldx, int N, int H, int W,
     if (int e = bind_stream_device(st)) return e;
     const int ntiles = (int)ceil_div(P, 16);
     double* part = (double*)ws;
-#define DSRL_PREDICT_LAUNCH(KERNEL, TGT, CE, CM, CAL, CONF)                                                                                             \
-    hipLaunchKernelGGL((KERNEL<TGT, CE, CM, CAL, CONF>), dim3(nb), dim3(256), 0, st, x, ldx, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred,   \
-                       target, ignore_index, counts, part, nan_flag, H, W, P, ntiles, cm, cal, bins, conf)
+    // the _t entry points (temp) launch the TEMP builds; every other entry point launches the builds it always did
+#define DSRL_PREDICT_LAUNCH_T(KERNEL, TGT, CE, CM, CAL, CONF, TEMP)                                                                                     \
+    hipLaunchKernelGGL((KERNEL<TGT, CE, CM, CAL, CONF, TEMP>), dim3(nb), dim3(256), 0, st, x, ldx, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2,  \
+                       pred, target, ignore_index, counts, part, nan_flag, H, W, P, ntiles, cm, cal, bins, conf, beta)
+#define DSRL_PREDICT_LAUNCH(KERNEL, TGT, CE, CM, CAL, CONF)                         \
+    do {                                                                            \
+        if (temp) DSRL_PREDICT_LAUNCH_T(KERNEL, TGT, CE, CM, CAL, CONF, true);      \
+        else DSRL_PREDICT_LAUNCH_T(KERNEL, TGT, CE, CM, CAL, CONF, false);          \
+    } while (0)
     // without a record and a map: the launches of the entry points that do not know them
 #define DSRL_PREDICT_PLAIN(KERNEL)                                                          \
     do {                                                                                    \
@@ -644,6 +662,7 @@ int tail_predict_launch(bool flip, const float* x, int ldx, int N, int H, int W,
 #undef DSRL_PREDICT_EX3
 #undef DSRL_PREDICT_PLAIN
 #undef DSRL_PREDICT_LAUNCH
+#undef DSRL_PREDICT_LAUNCH_T
     if (int e = launch_status(flip ? "sssr_tail_predict_flip_kernel" : "sssr_tail_predict_kernel")) return e;
     if (ce_out) {
         hipLaunchKernelGGL(predict_ce_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nb, ce_out);
@@ -704,6 +723,27 @@ extern "C" int dsrl_sssr_tail_predict_flip_ex(const float* x, int ldx, int N, in
                                               dsrl_stream_t stream) {
     return tail_predict_launch(true, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
                                counts, ce_out, nan_flag, ws, ws_bytes, cm, cal, bins, conf, stream);
+}
+
+// temperature scaling applied in the tail (include/dsrl_hip.h, "temperature"): the argument list of _ex plus beta = 1 / T
+extern "C" int dsrl_sssr_tail_predict_t(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                                        const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2, uint8_t* pred,
+                                        const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag, void* ws,
+                                        size_t ws_bytes, unsigned long long* cm, unsigned long long* cal, int bins, float* conf, float beta,
+                                        dsrl_stream_t stream) {
+    DSRL_TEMPERATURE_BETA(beta, "sssr_tail_predict_t");
+    return tail_predict_launch(false, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
+                               counts, ce_out, nan_flag, ws, ws_bytes, cm, cal, bins, conf, stream, true, beta);
+}
+
+extern "C" int dsrl_sssr_tail_predict_flip_t(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                                             const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2,
+                                             uint8_t* pred, const uint8_t* target, int ignore_index, unsigned long long* counts, float* ce_out, int* nan_flag,
+                                             void* ws, size_t ws_bytes, unsigned long long* cm, unsigned long long* cal, int bins, float* conf, float beta,
+                                             dsrl_stream_t stream) {
+    DSRL_TEMPERATURE_BETA(beta, "sssr_tail_predict_flip_t");
+    return tail_predict_launch(true, x, ldx, N, H, W, Cin, Cmid, Cout, w1, bn_mean, bn_invstd, bn_gamma, bn_beta, w2, bias2, pred, target, ignore_index,
+                               counts, ce_out, nan_flag, ws, ws_bytes, cm, cal, bins, conf, stream, true, beta);
 }
 
 extern "C" int dsrl_fingerprint_segment_words(void) { return kFingerprintSegWords; }

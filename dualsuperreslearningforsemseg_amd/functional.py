@@ -2384,12 +2384,15 @@ def _calibration_bins_of(record, what):
     return record.numel() // 3
 
 
-def calibration_counts_(record, logits, target, ignore_index=255, bins=CALIBRATION_DEFAULT_BINS, confidence=None, nan_flag=None):
+def calibration_counts_(record, logits, target, ignore_index=255, bins=CALIBRATION_DEFAULT_BINS, confidence=None, nan_flag=None, temperature=None):
     """record[n_b | hit_b | q_b] += the reliability histogram of logits (N,C,H,W) against target (N,H,W) over `bins` equal-width confidence bins
     (dsrl_calibration_from_logits, include/dsrl_hip.h "calibration"): the confidence of a pixel is its maximum softmax probability, counted are the
     pixels the confusion matrix counts (target != ignore_index and < C), q is the sum of rintf(conf * 2^24).  `confidence` (float32, (N,H,W),
     contiguous, optional) receives the confidence map; `nan_flag` (int32 device scalar, optional): bit 0 a NaN logit, bit 1 a label outside the
-    classes.  One streaming launch, nothing read back.  A bad argument raises before any device work."""
+    classes.  One streaming launch, nothing read back.  A bad argument raises before any device work.
+    `temperature` (temperature_value: None and 1 are "off" and the launch is today's): the record and the map of softmax(logits / T)
+    (dsrl_calibration_from_logits_t: the class is that of the logits as they are, the confidence that of the scaled ones)."""
+    temperature = temperature_value(temperature, 'calibration_counts_')
     with torch.no_grad():
         if logits.dim() != 4:
             raise DsrlHipError(f'calibration_counts_: 4-D (N,C,H,W) logits expected, got shape {tuple(logits.shape)}')
@@ -2405,9 +2408,13 @@ def calibration_counts_(record, logits, target, ignore_index=255, bins=CALIBRATI
             raise DsrlHipError(f'calibration_counts_: confidence must be a contiguous float32 tensor of shape {(N, H, W)} on the logits\' device')
         logits, ld = pm(logits)
         target = (target if target.dtype == torch.uint8 else target.to(torch.uint8)).contiguous()
-        if N * H * W:
+        if N * H * W and temperature is None:
             call('dsrl_calibration_from_logits', logits.data_ptr(), ld, target.data_ptr(), N * H * W, C, int(ignore_index), bins, record.data_ptr(),
                  None if confidence is None else confidence.data_ptr(), None if nan_flag is None else nan_flag.data_ptr(), _stream())
+        elif N * H * W:
+            call('dsrl_calibration_from_logits_t', logits.data_ptr(), ld, target.data_ptr(), N * H * W, C, int(ignore_index), bins, record.data_ptr(),
+                 None if confidence is None else confidence.data_ptr(), None if nan_flag is None else nan_flag.data_ptr(),
+                 temperature_beta(temperature), _stream())
     return record
 
 
@@ -2428,6 +2435,196 @@ def _calibration_of_scores(record, scores, pred, target, ignore_index, num_class
         rec[1].scatter_add_(0, b, hit)
         rec[2].scatter_add_(0, b, q)
     return conf.contiguous() if want_conf else None
+
+
+# ------------------------------------------------------------------------------------------------ temperature scaling
+def temperature_max_points():
+    """the largest number of temperatures of one dsrl_temperature_stats call; pure host code"""
+    return int(query('dsrl_temperature_max_points'))
+
+
+def temperature_value(x, what='temperature'):
+    """`x` as a temperature T: None (absent) and 1 are "off" -> None, and every launch is then the one of a call that does not know the argument;
+    a finite number > 0 -> float(T).  ValueError on anything else (bools, strings, NaN, inf, 0, negatives).  Touches no device."""
+    if x is None:
+        return None
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+        raise ValueError(f'{what}: temperature = {x!r}, None or a finite number > 0 expected')
+    T = float(x)
+    with np.errstate(over='ignore', under='ignore'):
+        b32 = float(np.float32(1.0 / T)) if math.isfinite(T) and T > 0.0 else 0.0
+    if not math.isfinite(b32) or b32 <= 0.0:
+        raise ValueError(f'{what}: temperature = {x!r}, None or a finite number > 0 (with a finite fp32 inverse) expected')
+    return None if T == 1.0 else T
+
+
+def temperature_beta(T):
+    """beta = 1 / T as the kernels receive it: rounded to fp32 once, here (a Python float that is exactly an fp32 value)"""
+    return float(np.float32(1.0 / float(T)))
+
+
+def temperature_betas_value(betas, what='temperature'):
+    """`betas` (a sequence of numbers or a host tensor) as a float64 array of fp32 values - what the device receives, so that a solve on the host
+    uses the very numbers the kernel used: 1 to temperature_max_points() of them, each a finite number > 0.  ValueError on anything else."""
+    if isinstance(betas, torch.Tensor):
+        betas = betas.detach().cpu().numpy()
+    try:
+        b = np.asarray(betas, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f'{what}: betas = {betas!r}, a sequence of numbers expected') from None
+    maxk = temperature_max_points()
+    if not 1 <= b.size <= maxk:
+        raise ValueError(f'{what}: {b.size} betas, 1 to {maxk} are possible')
+    with np.errstate(over='ignore'):
+        b = b.astype(np.float32).astype(np.float64)
+    if not np.all(np.isfinite(b) & (b > 0.0)):
+        raise ValueError(f'{what}: betas = {b.tolist()}, every one must be a finite number > 0 (in fp32)')
+    return b
+
+
+def temperature_grid(lo, hi, K, log=True):
+    """The K values of beta = 1 / T of one pass over [lo, hi], ends included, log-spaced (the first pass: a ratio is what matters) or linearly
+    spaced (the second pass, across one bracket); fp32 values as a float64 array (temperature_betas_value).  K = 1 needs lo == hi.  ValueError on
+    a K outside 1..temperature_max_points(), on bounds that are not finite numbers > 0 and on lo > hi (or lo == hi with K > 1)."""
+    if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= temperature_max_points():
+        raise ValueError(f'temperature_grid: K = {K!r}, an integer from 1 to {temperature_max_points()} expected')
+    K = int(K)
+    for v in (lo, hi):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)) or float(v) <= 0.0:
+            raise ValueError(f'temperature_grid: bounds ({lo!r}, {hi!r}) must be finite numbers > 0')
+    lo, hi = float(lo), float(hi)
+    if lo > hi or (lo == hi) != (K == 1):
+        raise ValueError(f'temperature_grid: {K} points over [{lo}, {hi}] (lo < hi for K > 1, lo == hi for K == 1)')
+    if K == 1:
+        g = np.array([lo])
+    elif log:
+        g = np.exp(np.linspace(math.log(lo), math.log(hi), K))
+    else:
+        g = np.linspace(lo, hi, K)
+    g[0], g[-1] = lo, hi
+    g = temperature_betas_value(g, 'temperature_grid')
+    if np.any(np.diff(g) <= 0.0):
+        raise ValueError(f'temperature_grid: [{lo}, {hi}] is too narrow for {K} distinct fp32 values')
+    return g
+
+
+def _temperature_record_value(betas, record, what):
+    """-> (betas float64 [K], record float64 [1 + 3 K]) on the host, checked against each other"""
+    if isinstance(record, torch.Tensor):
+        record = record.detach().cpu().numpy()
+    b = np.asarray(betas.detach().cpu().numpy() if isinstance(betas, torch.Tensor) else betas, dtype=np.float64).reshape(-1)
+    r = np.asarray(record, dtype=np.float64).reshape(-1)
+    if b.size < 1 or r.size != 1 + 3 * b.size:
+        raise ValueError(f'{what}: a record of 1 + 3 K = {1 + 3 * b.size} numbers expected for {b.size} betas, got {r.size}')
+    if b.size > 1 and np.any(np.diff(b) <= 0.0):
+        raise ValueError(f'{what}: the betas must ascend')
+    return b, r
+
+
+def _hermite(x0, x1, f0, f1, g0, g1, x):
+    """the cubic through (x0, f0), (x1, f1) with slopes g0, g1, at x"""
+    h = x1 - x0
+    t = (x - x0) / h
+    t2, t3 = t * t, t * t * t
+    return (2 * t3 - 3 * t2 + 1) * f0 + (t3 - 2 * t2 + t) * h * g0 + (-2 * t3 + 3 * t2) * f1 + (t3 - t2) * h * g1
+
+
+def temperature_bracket(betas, record):
+    """-> (i, at_bound): the grid interval [betas[i], betas[i + 1]] that holds the root of sum G (G is monotone in beta: L is convex), or the end
+    the minimum lies beyond: (0, True) when G[0] >= 0, (K - 1, True) when G[-1] <= 0.  Pure host code on a float64 record."""
+    b, r = _temperature_record_value(betas, record, 'temperature_bracket')
+    G = r[2::3]
+    if not np.all(np.isfinite(G)):
+        raise ValueError('temperature_bracket: the record holds a NaN or an infinite sum (a NaN logit, or a bad beta)')
+    if G[0] >= 0.0:
+        return 0, True
+    if G[-1] <= 0.0:
+        return b.size - 1, True
+    i = int(np.nonzero(G > 0.0)[0][0]) - 1          # G[i] <= 0 < G[i + 1]
+    return i, False
+
+
+def temperature_solve(betas, record):
+    """The fitted beta = 1 / T from one record of dsrl_temperature_stats (float64 [1 + 3 K], the sums of L, G = dL/dbeta and H = d2L/dbeta2 at the
+    ascending `betas`) -> (beta, at_bound).  G is monotone in beta.  If G[0] >= 0 or G[-1] <= 0 the minimum is at or beyond that end of the grid:
+    that end, at_bound=True.  Otherwise the root of the cubic Hermite interpolant of G between the two bracketing grid points (G the values, H the
+    slopes), found by bisection.  Pure host code."""
+    b, r = _temperature_record_value(betas, record, 'temperature_solve')
+    i, at_bound = temperature_bracket(b, r)
+    if at_bound:
+        return float(b[i]), True
+    G, H = r[2::3], r[3::3]
+    lo, hi = float(b[i]), float(b[i + 1])
+    if G[i] == 0.0:
+        return lo, False
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if mid <= lo or mid >= hi:
+            break
+        if _hermite(b[i], b[i + 1], G[i], G[i + 1], H[i], H[i + 1], mid) > 0.0:
+            hi = mid
+        else:
+            lo = mid
+    return 0.5 * (lo + hi), False
+
+
+def temperature_nll_at(betas, record, beta):
+    """The mean NLL over the live pixels at `beta` from a record: a grid point's own value, otherwise the cubic Hermite interpolant between the two
+    grid points around it (L the values, G the slopes); NaN outside the grid or for an empty record.  Pure host code."""
+    b, r = _temperature_record_value(betas, record, 'temperature_nll_at')
+    n, L, G = r[0], r[1::3], r[2::3]
+    beta = float(beta)
+    if n <= 0 or not b[0] <= beta <= b[-1]:
+        return float('nan')
+    j = int(np.searchsorted(b, beta))
+    if b[j] == beta:
+        return float(L[j] / n)
+    return float(_hermite(b[j - 1], b[j], L[j - 1], L[j], G[j - 1], G[j], beta) / n)
+
+
+def temperature_stats_(record, logits, target, betas, ignore_index=255, nan_flag=None):
+    """record[0] += live pixels, record[1 + 3 k ..] += the sums of L, G, H at betas[k] (dsrl_temperature_stats, include/dsrl_hip.h "temperature"):
+    the NLL of softmax(beta v) of logits (N,C,H,W) against target (N,H,W) with its first and second derivative in beta = 1 / T, at up to 16 values of
+    beta in one streaming pass.  `record`: float64, 1 + 3 K elements, contiguous, accumulated.  `betas`: a sequence of numbers or a host tensor -
+    each checked here as a finite number > 0, at most temperature_max_points() of them - or a float32 tensor on the logits' device, which is taken as
+    it is (its length is checked; a bad value makes its own three entries NaN): a caller that feeds many batches uploads it once
+    (metrices.TemperatureFit).  `nan_flag` (int32 device scalar, optional): bit 0 a NaN logit of a live pixel, bit 1 a label outside the classes.
+    Two launches, nothing read back.  A bad argument raises before any device work."""
+    with torch.no_grad():
+        if logits.dim() != 4:
+            raise DsrlHipError(f'temperature_stats_: 4-D (N,C,H,W) logits expected, got shape {tuple(logits.shape)}')
+        on_device = isinstance(betas, torch.Tensor) and betas.device.type != 'cpu'
+        if on_device:
+            if betas.dtype != torch.float32 or betas.dim() != 1 or not betas.is_contiguous() or not 1 <= betas.numel() <= temperature_max_points():
+                raise ValueError(f'temperature_stats_: device betas must be a contiguous float32 vector of 1 to {temperature_max_points()} elements')
+            if betas.device != logits.device:
+                raise DsrlHipError(f'temperature_stats_: betas are on {betas.device}, the logits on {logits.device}')
+            K = betas.numel()
+        else:
+            host = temperature_betas_value(betas, 'temperature_stats_')
+            K = host.size
+        if not isinstance(record, torch.Tensor) or record.dtype != torch.float64 or record.numel() != 1 + 3 * K or not record.is_contiguous():
+            got = f'{record.dtype}, {record.numel()} elements' if isinstance(record, torch.Tensor) else type(record).__name__
+            raise DsrlHipError(f'temperature_stats_: record must be a contiguous float64 tensor of {1 + 3 * K} elements (got {got})')
+        _need_gpu(logits, target, record, nan_flag)
+        if record.device != logits.device:
+            raise DsrlHipError(f'temperature_stats_: record is on {record.device}, the logits on {logits.device}')
+        N, C, H, W = logits.shape
+        if tuple(target.shape) != (N, H, W):
+            raise DsrlHipError(f'temperature_stats_: target {tuple(target.shape)} is not {(N, H, W)}')
+        if nan_flag is not None and (nan_flag.dtype != torch.int32 or nan_flag.numel() != 1):
+            raise DsrlHipError('temperature_stats_: nan_flag must be an int32 scalar')
+        if not on_device:
+            betas = torch.tensor(host, dtype=torch.float32).to(logits.device)
+        logits, ld = pm(logits)
+        target = (target if target.dtype == torch.uint8 else target.to(torch.uint8)).contiguous()
+        P = N * H * W
+        if P:
+            nbytes = cquery('dsrl_temperature_workspace_bytes', P, K)
+            ws = _ws(nbytes, logits)
+            call('dsrl_temperature_stats', logits.data_ptr(), ld, target.data_ptr(), P, C, int(ignore_index), betas.data_ptr(), K, record.data_ptr(),
+                 None if nan_flag is None else nan_flag.data_ptr(), ws.data_ptr(), nbytes, _stream())
+    return record
 
 
 def confusion_matrix_(confusion, pred, target, num_classes, ignore_index=255, nan_flag=None):
@@ -2505,7 +2702,7 @@ def boundary_counts_(counts, pred, target, num_classes, ignore_index=255, distan
 
 
 def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, counts=None, nan_flag=None, flip=False, confusion=None, calibration=None,
-                      confidence=False):
+                      confidence=False, temperature=None):
     """Eval-mode tail of the SSSR decoder after its bilinear x2 (DSRL.py:55-69): ConvTranspose2d k2 s2 `convt1` -> BatchNorm2d `bn` (running statistics)
     -> ReLU -> ConvTranspose2d k2 s2 `convt2` -> arg-max, as one launch that writes class indices and never the logits (dsrl_sssr_tail_predict).
     -> (pred uint8 (N,4H,4W), ce): with `target` (N,4H,4W) `ce` is the 0-d device tensor of nn.CrossEntropyLoss(ignore_index) of the logits and
@@ -2520,7 +2717,14 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
     `calibration` (int64 [3*bins], optional, needs a target) gets the reliability record [n_b | hit_b | q_b] of the returned class map ADDED (the bin
     count is its length over 3; include/dsrl_hip.h "calibration"), `confidence=True` appends the confidence map (float32 (N,4H,4W): the probability of
     the reported class) to the returned tuple; both come from the same single launch (dsrl_sssr_tail_predict_ex / _flip_ex).  Heads the kernel does
-    not implement go modules -> logits -> dsrl_calibration_from_logits.  Without them the launches are those of a call that does not know them."""
+    not implement go modules -> logits -> dsrl_calibration_from_logits.  Without them the launches are those of a call that does not know them.
+    `temperature` (temperature_value: None and 1 are "off" and every launch is then today's; a finite number T > 0): the model reports
+    softmax(logits / T).  Behind the arg-max the kernel multiplies the logits by beta = 1 / T (dsrl_sssr_tail_predict_t / _flip_t), so `ce`, the
+    calibration record and the confidence map are those of the scaled model while `pred`, `counts` and `confusion` of a single view keep their bits;
+    with `flip` each view is scaled in front of its softmax and the ensemble is that of the scaled model.  Heads the kernel does not implement
+    multiply their logits by beta and run the reductions they run today."""
+    temperature = temperature_value(temperature, 'sssr_tail_predict')
+    tbeta = None if temperature is None else temperature_beta(temperature)          # (`beta` is the BatchNorm's below)
     if confusion is not None and target is None:
         raise DsrlHipError('sssr_tail_predict: confusion needs a target')
     if calibration is not None and target is None:
@@ -2576,9 +2780,12 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
             name = ('dsrl_sssr_tail_predict_flip' if flip else 'dsrl_sssr_tail_predict') + ('_ex' if ex else '' if confusion is None else '_cm')
             conf = torch.empty((N, 4 * H, 4 * W), device=x.device, dtype=torch.float32) if confidence else None
             extra = () if confusion is None else (confusion.data_ptr(),)
-            if ex:
+            if ex or tbeta is not None:
                 extra = (None if confusion is None else confusion.data_ptr(), None if calibration is None else calibration.data_ptr(), bins,
                          None if conf is None else conf.data_ptr())
+            if tbeta is not None:
+                name = 'dsrl_sssr_tail_predict_flip_t' if flip else 'dsrl_sssr_tail_predict_t'
+                extra = extra + (tbeta,)
             call(name, x.data_ptr(), ldx, N, H, W, Ci, Cm, Co, w1.contiguous().data_ptr(), bn.running_mean.data_ptr(),
                  invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w2.contiguous().data_ptr(), None if b2 is None else b2.data_ptr(),
                  pred.data_ptr(), None if target is None else target.data_ptr(), int(ignore_index), None if counts is None else counts.data_ptr(),
@@ -2591,18 +2798,29 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
         if nan_flag is not None:
             nan_check_(nan_flag, logits)
         if flip:
+            if tbeta is not None:
+                logits = logits * tbeta             # each view's softmax is that of the scaled model (beta is an fp32 value: one fp32 multiply)
             logits = _flip_ensemble(logits)         # the scores of the ensemble stand in for the logits: log_softmax(E) = E
         pred = torch.argmax(logits, dim=1).to(torch.uint8)
+        # a single view's temperature: the class map and the counters come from the logits as they are, the confidence from dsrl_calibration_from_logits_t
+        # (which scales behind its own first-maximum search), the loss from the scaled logits
+        cal_t = temperature if not flip else None
         conf = ()
         if ex:
             # softmax(E) = exp(E), so the maximum softmax probability of the scores IS the ensemble's confidence: one producer for both forms
             cmap = torch.empty((N, 4 * H, 4 * W), device=x.device, dtype=torch.float32) if confidence else None
-            if calibration is not None:
+            if calibration is not None and cal_t is None:
                 calibration_counts_(calibration, logits, target, int(ignore_index), bins, cmap)
-            else:
+            elif calibration is not None:
+                calibration_counts_(calibration, logits, target, int(ignore_index), bins, cmap, temperature=cal_t)
+            elif cal_t is None:
                 lg, ld = pm(logits)
                 call('dsrl_calibration_from_logits', lg.data_ptr(), ld, None, N * 16 * H * W, Co, int(ignore_index), 1, None, cmap.data_ptr(), None,
                      _stream())
+            else:
+                lg, ld = pm(logits)
+                call('dsrl_calibration_from_logits_t', lg.data_ptr(), ld, None, N * 16 * H * W, Co, int(ignore_index), 1, None, cmap.data_ptr(), None,
+                     tbeta, _stream())
             conf = (cmap,) if confidence else ()
         if target is None:
             return (pred, None) + conf
@@ -2613,6 +2831,8 @@ def sssr_tail_predict(x, convt1, bn, convt2, target=None, ignore_index=255, coun
             call('dsrl_seg_metrics', lg.data_ptr(), ld, target.data_ptr(), N * 16 * H * W, Co, int(ignore_index), counts.data_ptr(), _stream())
         if confusion is not None:
             confusion_matrix_(confusion, pred, target, Co, int(ignore_index))
+        if cal_t is not None:
+            logits = logits * tbeta
         return (pred, cross_entropy(logits, target, int(ignore_index))) + conf
 
 

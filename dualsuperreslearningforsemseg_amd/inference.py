@@ -267,10 +267,13 @@ class CompiledPredictor:
 
     # ------------------------------------------------------------------ the call
     def __call__(self, images, target=None, ignore_index=255, nan_flag=None, copy=True, flip=False, confusion=None, scales=None, calibration=None,
-                 confidence=False):
+                 confidence=False, temperature=None):
         if calibration is not None or confidence:
             # graphs are keyed on their outputs: the calibration record and the confidence map are not among the keys
             raise ValueError('CompiledPredictor: calibration and confidence are outputs of DSRL.predict only, not of a compiled predictor')
+        if HF.temperature_value(temperature, 'CompiledPredictor') is not None:
+            # a graph bakes its kernel arguments in: a temperature would have to be one more key
+            raise ValueError('CompiledPredictor: temperature is an option of DSRL.predict only, not of a compiled predictor')
         if HF.multiscale_scales_value(scales) is not None:
             raise DsrlHipError(MULTISCALE_NOT_COMPILED)
         if self.frozen.released:

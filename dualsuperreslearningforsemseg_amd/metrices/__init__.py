@@ -266,6 +266,74 @@ class Calibration:
         return calibration_figures(np.zeros(3 * self.bins, np.int64) if self._record is None else self._record)
 
 
+def temperature_figures(betas, record):
+    """The figures of a temperature record (float64 [1 + 3 K]: live pixels, then the sums of L, G, H at each of the ascending `betas`;
+    include/dsrl_hip.h "temperature"), host only: `beta` = the fitted 1 / T (functional.temperature_solve), `temperature` = 1 / beta, `at_bound`
+    (the minimum lies at or beyond an end of the grid: the end is reported), `nll` = the mean NLL over the live pixels at each beta, `betas`,
+    `pixels`.  An empty record gives NaN figures."""
+    b, r = HF._temperature_record_value(betas, record, 'temperature_figures')
+    n = int(r[0])
+    if n == 0:
+        nan = float('nan')
+        return {'temperature': nan, 'beta': nan, 'at_bound': False, 'nll': np.full(b.size, nan), 'betas': b, 'pixels': 0}
+    beta, at_bound = HF.temperature_solve(b, r)
+    return {'temperature': 1.0 / beta, 'beta': beta, 'at_bound': bool(at_bound), 'nll': r[1::3] / float(n), 'betas': b, 'pixels': n}
+
+
+class TemperatureFit:
+    """One pass of a temperature fit over a whole split (Guo et al. 2017): the NLL of softmax(beta logits), beta = 1 / T, with its first and second
+    derivative at the K <= 16 values `betas` (functional.temperature_grid).  Shaped like Calibration: `.record` is the float64 buffer of 1 + 3 K
+    elements, allocated on first use on the device of what it is fed; update_from_logits adds to it and nothing clears it; result() does the one
+    read.  The betas travel to the device once, beside the record."""
+
+    def __init__(self, betas, ignore_index=255):
+        self.betas, self.ignore_index = HF.temperature_betas_value(betas, 'TemperatureFit'), int(ignore_index)
+        if np.any(np.diff(self.betas) <= 0.0):
+            raise ValueError(f'TemperatureFit: the betas must ascend, got {self.betas.tolist()}')
+        self._record = self._betas_dev = None
+
+    def _on(self, device):
+        if self._record is None:
+            self._record = torch.zeros(1 + 3 * self.betas.size, dtype=torch.float64, device=device)
+            self._betas_dev = torch.tensor(self.betas, dtype=torch.float32).to(device)
+        elif self._record.device != torch.device(device):
+            raise ValueError(f'TemperatureFit lives on {self._record.device}, fed from {device}')
+        return self._record
+
+    @property
+    def record(self):
+        if self._record is None:
+            raise ValueError('TemperatureFit.record before first use: call on(device), update_from_logits() or merge() first')
+        return self._record
+
+    def on(self, device):
+        """-> .record, allocated on `device` if nothing has been fed yet"""
+        return self._on(torch.device(device))
+
+    def reset(self):
+        if self._record is not None:
+            self._record.zero_()
+
+    def update_from_logits(self, logits, target, nan_flag=None):
+        """logits (N, C, H, W), target (N, H, W): one streaming pass and its finish (dsrl_temperature_stats), nothing read back"""
+        HF._need_gpu(logits, target)
+        rec = self._on(logits.device)
+        HF.temperature_stats_(rec, logits, target, self._betas_dev if self._betas_dev.device.type != 'cpu' else self.betas, self.ignore_index, nan_flag)
+
+    def merge(self, other):
+        """adds another TemperatureFit over the same betas, or a float64 tensor of 1 + 3 K elements; a host tensor is taken as it is"""
+        if isinstance(other, TemperatureFit) and not np.array_equal(other.betas, self.betas):
+            raise ValueError('merge: the two fits are over different betas')
+        r = other.record if isinstance(other, TemperatureFit) else other
+        if r.dtype != torch.float64 or r.numel() != 1 + 3 * self.betas.size:
+            raise ValueError(f'merge: a float64 tensor of {1 + 3 * self.betas.size} elements expected, got {r.dtype} of {r.numel()}')
+        self._on(r.device).add_(r.reshape(-1))
+
+    def result(self):
+        """The one device read -> temperature_figures(betas, record); nothing fed: NaN figures"""
+        return temperature_figures(self.betas, np.zeros(1 + 3 * self.betas.size) if self._record is None else self._record)
+
+
 class SRQuality:
     """PSNR (dB, data range 1) and SSIM of super-resolved images against their originals over a whole split (functional.sr_quality): `mean` / `std`
     are the normalisation the tensors carry (dataset settings' MEAN / STD; None: values in [0, 1] already).  Every update leaves one (N, 2) float64

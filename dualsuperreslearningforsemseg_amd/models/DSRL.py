@@ -135,7 +135,7 @@ class DSRL(BaseModel):
             return self.forward_head(backbone_features, lowlevel_features)
 
     def predict_head(self, backbone_features: t.Tensor, lowlevel_features: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None,
-                     flip: bool = False, confusion: t.Tensor = None, calibration: t.Tensor = None, confidence: bool = False):
+                     flip: bool = False, confusion: t.Tensor = None, calibration: t.Tensor = None, confidence: bool = False, temperature=None):
         """Inference counterpart of forward_head: the SSSR branch in eval mode down to the bilinear x2 of `upsample16_pred`, then its ConvTranspose ->
         BatchNorm -> ReLU -> ConvTranspose tail and the arg-max as one kernel (functional.sssr_tail_predict) -> (pred uint8 (N,H,W), counts, ce).
         With `target` (N,H,W): `counts` is the int64 table of dsrl_seg_metrics of this batch (metrices.mIoU / Accuracy.update_from_counts), a fresh
@@ -147,9 +147,13 @@ class DSRL(BaseModel):
         and averages the two views' class probabilities -> N class maps (functional.sssr_tail_predict(flip=True)), `target` (N,H,W).
         `calibration` (int64 device tensor of 3 * bins elements, needs a target; metrices.Calibration.record) gets this batch's reliability record
         ADDED by the same kernel; `confidence=True` appends the confidence map (float32 (N,H,W): the probability of the reported class) to the
-        returned tuple.  Without them every launch is the one of a call that does not know them."""
+        returned tuple.  Without them every launch is the one of a call that does not know them.
+        `temperature` (functional.temperature_value: None and 1 are "off" and leave every launch as it is; a finite number T > 0): the model reports
+        softmax(logits / T) - `ce`, the calibration record and the confidence map are those of the scaled model, the class map and the counters of a
+        single view do not change (functional.sssr_tail_predict(temperature=))."""
         if self.training:
             raise HF.DsrlHipError('DSRL.predict* is inference: call model.eval() first')
+        temperature = HF.temperature_value(temperature, 'DSRL.predict_head')
         with t.no_grad():
             fe, dec = self.feature_extractor, self.SSSR_decoder
             aspp_features = fe['aspp'](backbone_features)
@@ -161,12 +165,13 @@ class DSRL(BaseModel):
             counts = None
             if target is not None:
                 counts = t.zeros(3 * up[6].out_channels + 2, dtype=t.int64, device=y.device)
+            more = {} if temperature is None else {'temperature': temperature}
             out = HF.sssr_tail_predict(y, up[2], up[3], up[6], target=target, ignore_index=ignore_index, counts=counts, nan_flag=nan_flag, flip=flip,
-                                       confusion=confusion, calibration=calibration, confidence=confidence)
+                                       confusion=confusion, calibration=calibration, confidence=confidence, **more)
         return (out[0], counts, out[1]) + tuple(out[2:])
 
     def predict(self, x: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None, flip: bool = False,
-                confusion: t.Tensor = None, scales=None, calibration: t.Tensor = None, confidence: bool = False):
+                confusion: t.Tensor = None, scales=None, calibration: t.Tensor = None, confidence: bool = False, temperature=None):
         """Class map of a batch: (pred, counts or None, ce or None), see predict_head.  Runs under no_grad and raises in train mode.  Without a
         `nan_flag` of the caller's the flag is read back here and a NaN logit or an out-of-range label raises; a caller that passes one reads it when
         it chooses to (command_handlers.benchmark: once, after the last batch).
@@ -178,14 +183,19 @@ class DSRL(BaseModel):
         logits of the eval forward path are written (with `flip` for the image and its mirror image in one batch), merged into the ensemble and
         released before the next scale runs (functional.ProbMerge: the logits of every view resampled to the output grid, softmax, class probabilities
         averaged); pred, counts, ce, confusion and the NaN flag are those of the ensemble.
-        `calibration`, `confidence`: see predict_head; with `flip` and `scales` they are the record and the confidence map of the ensemble."""
+        `calibration`, `confidence`: see predict_head; with `flip` and `scales` they are the record and the confidence map of the ensemble.
+        `temperature`: see predict_head (a T fitted by command_handlers.fit_temperature); combines with flip, target, confusion, calibration and
+        confidence.  With `scales` it is a ValueError before any device work: the multi-scale merge takes no temperature."""
         if self.training:
             raise HF.DsrlHipError('DSRL.predict* is inference: call model.eval() first')
         if confusion is not None and target is None:
             raise HF.DsrlHipError('DSRL.predict: confusion needs a target')
         if calibration is not None and target is None:
             raise HF.DsrlHipError('DSRL.predict: calibration needs a target')
+        temperature = HF.temperature_value(temperature, 'DSRL.predict')
         scales = HF.multiscale_scales_value(scales)
+        if temperature is not None and scales is not None:
+            raise ValueError('DSRL.predict: temperature does not combine with scales (the multi-scale merge takes no temperature)')
         if scales is not None:
             return self._predict_multiscale(x, target, ignore_index, nan_flag, flip, confusion, scales, calibration, confidence)
         own = nan_flag is None
@@ -199,7 +209,8 @@ class DSRL(BaseModel):
                 both[x.shape[0]:].copy_(x.flip(3))          # 3 channels at input size: torch ops
                 x = both
             backbone_features, lowlevel_features = self.feature_extractor['backbone'](x)
-            out = self.predict_head(backbone_features, lowlevel_features, target, ignore_index, nan_flag, flip, confusion, calibration, confidence)
+            more = {} if temperature is None else {'temperature': temperature}
+            out = self.predict_head(backbone_features, lowlevel_features, target, ignore_index, nan_flag, flip, confusion, calibration, confidence, **more)
         if own:
             bits = int(nan_flag.item())
             if bits:

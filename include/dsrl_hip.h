@@ -838,6 +838,51 @@ int dsrl_prob_merge_finish_ex(const float* logits, int ld, int N, int Hs, int Ws
                               unsigned long long* cm /*nullable, [C*C]*/, unsigned long long* cal /*nullable, [3*bins]*/, int bins,
                               float* conf /*nullable, (N,Ho,Wo)*/, dsrl_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * temperature: post-hoc temperature scaling (Guo et al. 2017) - fit one scalar T on a held-out split, report softmax(v / T)
+ * (csrc/temperature.hip; the arithmetic is written once in csrc/common.h: temperature_terms, temperature_scale).  beta = 1 / T.
+ *   The fit.  A live pixel is one whose label t is neither ignore_index nor >= C.  For its logits v_0..v_{C-1}: m = the fmaxf chain from v_0,
+ *   d_c = v_c - m <= 0, and for each beta_k of the call, in fp32 with c ascending:
+ *     e_c = exp(beta_k d_c), s = sum e_c, a = sum e_c d_c, q = sum (e_c d_c) d_c,
+ *     L = log(s) - beta_k d_t  (the NLL of softmax(beta_k v) at t; the log is a float32 polynomial without the device logf's half-ulp bias),  mu = a / s,  G = mu - d_t = dL/dbeta,  H = q / s - mu mu = d2L/dbeta2 >= 0.
+ *   Record: float64 [1 + 3 K], ADDED by every call: [0] the number of live pixels, then for each k the sums of L, G and H over the live pixels.
+ *   L is convex in beta, so the root of sum G is the fitted 1 / T; G and H at K points give it by Hermite interpolation (functional.temperature_solve).
+ * dsrl_temperature_stats: logits (P, C) pixel-major with pixel stride ld >= C, C <= 60; betas: DEVICE array of K floats, 1 <= K <=
+ *   dsrl_temperature_max_points() = 16.  One streaming launch (256 pixels x C floats per tile through LDS, one thread per pixel, per-block partial
+ *   sums in double) and a one-block finish that adds the partials in a fixed order and then adds the totals to record: no float atomics, the
+ *   pixel -> block mapping depends on P alone, so a record has the same bits on every call.  ws: >= dsrl_temperature_workspace_bytes(P, K) (a
+ *   function of P and K alone; 0, with a message, for bad arguments), 8-byte aligned.  nan_flag (nullable): |= 1 for a NaN logit of a live pixel
+ *   (its NaN reaches the sums), |= 2 for a label >= C that is not ignore_index (not counted).  A beta that is not a finite number > 0 makes its own
+ *   three entries NaN and leaves the others right.  logits / betas 4-byte, record 8-byte aligned.  No host reads; capturable.
+ *   Argument errors, before any launch and with nothing written: null pointers, P <= 0, K outside 1..16, ld < C, a misaligned pointer
+ *   (DSRL_E_BADARG); C > 60, or P / ld beyond the 32-bit tile indices (DSRL_E_UNSUPPORTED); a workspace too small or misaligned (DSRL_E_WORKSPACE).
+ *   Applying a temperature: every producer, behind its arg-max, replaces each logit by v_c * beta (one fp32 multiply) and runs the softmax
+ *   arithmetic it has on the result.  A positive beta is monotone under rounding: the class map and the counters of a single view are
+ *   bit-identical with and without a temperature, and dsrl_calibration_from_logits_t reproduces the fused tail's confidence exactly.
+ * dsrl_sssr_tail_predict_t / _flip_t: dsrl_sssr_tail_predict_ex / _flip_ex plus beta (a finite number > 0, DSRL_E_BADARG otherwise): ce_out, cal and
+ *   conf are those of the scaled model; in the flip form each view is scaled in front of its softmax.
+ * dsrl_calibration_from_logits_t: dsrl_calibration_from_logits plus beta.
+ * ---------------------------------------------------------------------------------------------- */
+int dsrl_temperature_max_points(void);
+size_t dsrl_temperature_workspace_bytes(int64_t P, int K);
+int dsrl_temperature_stats(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* betas /*device, K floats*/,
+                           int K, double* record /*[1 + 3K], accumulated*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+int dsrl_sssr_tail_predict_t(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                             const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2 /*nullable*/,
+                             uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index, unsigned long long* counts /*nullable*/,
+                             float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes,
+                             unsigned long long* cm /*nullable, [Cout*Cout]*/, unsigned long long* cal /*nullable, [3*bins]*/, int bins,
+                             float* conf /*nullable, (N,4H,4W)*/, float beta, dsrl_stream_t stream);
+int dsrl_sssr_tail_predict_flip_t(const float* x, int ldx, int N, int H, int W, int Cin, int Cmid, int Cout, const float* w1, const float* bn_mean,
+                                  const float* bn_invstd, const float* bn_gamma, const float* bn_beta, const float* w2, const float* bias2 /*nullable*/,
+                                  uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index, unsigned long long* counts /*nullable*/,
+                                  float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes,
+                                  unsigned long long* cm /*nullable, [Cout*Cout]*/, unsigned long long* cal /*nullable, [3*bins]*/, int bins,
+                                  float* conf /*nullable, (N,4H,4W)*/, float beta, dsrl_stream_t stream);
+int dsrl_calibration_from_logits_t(const float* logits, int ld, const uint8_t* target /*nullable*/, int64_t P, int C, int ignore_index, int bins,
+                                   unsigned long long* record /*nullable, [3*bins]*/, float* conf_map /*nullable, [P]*/, int* nan_flag /*nullable*/,
+                                   float beta, dsrl_stream_t stream);
+
 /* Fingerprint of tensors that must not change while an inference.FrozenOperands holds operands derived from them (a write through `.data` or a
  * raw pointer moves neither a tensor's address nor its version counter).  table: DEVICE array of nseg rows of 2 int64 {pointer (4-byte aligned),
  * number of 32-bit words <= dsrl_fingerprint_segment_words()}, one block per row; a tensor is cut into as many rows as it needs.  Row r gets
