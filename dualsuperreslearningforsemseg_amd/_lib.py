@@ -181,6 +181,13 @@ PROTOTYPES = {
     'dsrl_prob_merge_workspace_bytes': (sz, [i32] * 3),
     'dsrl_prob_merge': (i32, [fp, i32] + [i32] * 5 + [fp, i32, i32, i32, stream_t]),
     'dsrl_prob_merge_finish': (i32, [fp, i32] + [i32] * 5 + [fp, i32, i32, i32, fp, fp, i32, fp, fp, fp, fp, sz, fp, stream_t]),
+    'dsrl_window_merge_supported': (i32, [i32] * 6),
+    'dsrl_window_merge_workspace_bytes': (sz, [i32] * 3),
+    'dsrl_window_merge': (i32, [fp, i32] + [i32] * 5 + [fp] + [i32] * 6 + [stream_t]),
+    'dsrl_window_merge_finish': (i32, [fp] + [i32] * 4 + [C.POINTER(i32), i32, C.POINTER(i32), i32, i32, i32, i32, fp, fp, i32, fp, fp, fp, fp, sz, fp,
+                                       stream_t]),          # ys / xs: host arrays (ctypes)
+    'dsrl_window_merge_finish_ex': (i32, [fp] + [i32] * 4 + [C.POINTER(i32), i32, C.POINTER(i32), i32, i32, i32, i32, fp, fp, i32, fp, fp, fp, fp, sz, fp,
+                                          fp, i32, fp, stream_t]),
     'dsrl_fingerprint_segment_words': (i32, []),
     'dsrl_fingerprint_segments': (i32, [fp, i64, fp, fp, fp, i32, stream_t]),
     'dsrl_class_map_visualize': (i32, [fp, fp, fp, fp, fp, i32, i32, i32, i32, C.c_double, stream_t]),

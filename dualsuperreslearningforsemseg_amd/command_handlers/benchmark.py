@@ -34,6 +34,11 @@ temperature scaling - every batch is evaluated as `DSRL.predict(temperature=T)`,
 benchmark.txt says that the figure is in-sample.  Combines with `flip`, `ema`, `boundary`, `calibration` and `sisr`, not with `scales` or
 `compiled_model`; a clash, a bad number or a file that is not a temperature.json is a ValueError before any device work.  Without the key the
 command makes exactly the calls it makes without it.
+`window=<side or (rows, columns)>` and optionally `stride=` in other_args, in pixels of `model_input_size`: sliding-window inference - every batch is
+evaluated as `DSRL.predict(window=..., stride=...)`, overlapping windows of the training size whose class probabilities are averaged (a missing
+stride is 2/3 of the window).  Validated against `model_input_size` before any device work; benchmark.txt gets one line naming the window, the
+stride and the positions per axis.  Combines with `flip`, `ema`, `boundary`, `calibration` and `confusion`; with `scales`, `temperature`,
+`compiled_model` or `sisr` it is a ValueError before any device work.  A window that is the whole input is "off".
 Beside the reference's per-batch figures the command accumulates ONE confusion matrix over the split on the device (the kernel that writes the
 class map fills it; it comes back in the same single read) and reports the dataset-level figures from it - intersections and unions summed over the
 split, then IoU per class, then the mean over the classes, as Cityscapes results are published - with a per-class table in benchmark.txt and the
@@ -48,7 +53,7 @@ import torch as t
 from .. import settings
 from .._lib import DsrlHipError
 from ..functional import (CALIBRATION_DEFAULT_BINS, boundary_counts_, boundary_distance, calibration_bins_value, multiscale_scales_value,
-                          multiscale_sizes, nan_check_, temperature_value)
+                          multiscale_sizes, nan_check_, temperature_value, window_plan, window_value)
 from ..metrices import Accuracy, AverageMeter, BoundaryIoU, ConfusionMatrix, SRQuality, calibration_figures, mIoU
 from ..models import DSRL
 from ..utils import load_checkpoint_or_weights
@@ -136,6 +141,16 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
         clash = [k for k, on in (('flip', other_args.get('flip')), ('scales', scales is not None), ('compiled_model', other_args.get('compiled_model'))) if on]
         if clash:
             raise ValueError(f"benchmark: sisr=True does not combine with {', '.join(clash)} (the SISR branch has no ensemble; compiled files are stage-1)")
+    window, positions = window_value(other_args.get('window'), other_args.get('stride')), None
+    if window is not None:
+        clash = [k for k, on in (('scales', scales is not None), ('temperature', temperature is not None), ('compiled_model', other_args.get('compiled_model')),
+                                 ('sisr', sisr)) if on]
+        if clash:
+            raise ValueError(f"benchmark: window does not combine with {', '.join(clash)} (the windows run through the eager single-scale DSRL.predict)")
+        size = tuple(other_args.get('model_input_size', settings.MODEL_INPUT_SIZE))
+        positions = window_plan(size[0], size[1], *window)       # ValueError on a window the input cannot take; None: the whole input, "off"
+        if positions is None:
+            window = None
     if not isCUDAdevice(device):
         raise RuntimeError(NOT_GPU)
     if scales is not None and other_args.get('compiled_model'):
@@ -156,6 +171,8 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
     flip = bool(other_args.get('flip'))
     if scales is not None:
         predict = functools.partial(predict, scales=scales)
+    if window is not None:
+        predict = functools.partial(predict, window=window[0], stride=window[1])
     fitted = None
     if temperature == 'fit':
         from .fit_temperature import fit_passes
@@ -293,6 +310,10 @@ def benchmark(weights, dataset, device, num_workers, batch_size, **other_args):
             f.write('Multi-scale ensemble: scales {:s} of the {:d} x {:d} input -> views of {:s}\n'.format(
                 ', '.join('{:g}'.format(s) for s in scales), int(input_size[0]), int(input_size[1]),
                 ', '.join('{:d} x {:d}'.format(h, w) for h, w in multiscale_sizes(input_size[0], input_size[1], scales))))
+        if window is not None:
+            f.write('Sliding-window ensemble: windows of {:d} x {:d} at stride {:d} x {:d} over the {:d} x {:d} input -> {:d} x {:d} positions, '
+                    'class probabilities averaged where they overlap\n'.format(window[0][0], window[0][1], window[1][0], window[1][1], int(input_size[0]),
+                                                                               int(input_size[1]), len(positions[0]), len(positions[1])))
         f.write('\n')
         f.write('\n'.join(lines) + '\n')
     np.save(os.path.join(output_dir, 'confusion_matrix.npy'), fig['matrix'])

@@ -8,7 +8,9 @@ was trained with (the reference's torchvision Resize here is a different one); t
 way the input | class colours | overlay panels are built on the device (utils.make_input_output_visualization_device): what crosses to the host
 per image is the finished uint8 panel, which PIL encodes.  `flip=True` in other_args: the class maps are those of the horizontal-flip ensemble
 (`DSRL.predict(flip=True)`).  `scales=(...)` in other_args: those of the multi-scale ensemble (`DSRL.predict(scales=...)`; combines with `flip`);
-the value is validated before any device work, and with `compiled_model` the command raises before it reads the file."""
+the value is validated before any device work, and with `compiled_model` the command raises before it reads the file.  `window=` / `stride=` in
+other_args (an integer or a pair, in pixels of `model_input_size`): those of sliding-window inference (`DSRL.predict(window=...)`; combines with
+`flip`); validated against `model_input_size` before any device work, a ValueError with `scales` or `compiled_model`."""
 import functools
 import os
 
@@ -17,7 +19,7 @@ import torch as t
 
 from .. import consts, settings
 from .._lib import DsrlHipError
-from ..functional import multiscale_scales_value
+from ..functional import multiscale_scales_value, window_plan, window_value
 from ..models.transforms import DeviceBatchPreparation
 from ..utils import make_input_output_visualization_device
 from .benchmark import NOT_GPU, load_eval_model, split_loader
@@ -35,6 +37,14 @@ def _save_png(hwc, filename):
 @t.no_grad()
 def test(image_file, images_dir, dataset, output_dir, weights, device, compiled_model, **other_args):
     scales = multiscale_scales_value(other_args.get('scales'))          # ValueError on a bad value, before any device work
+    window = window_value(other_args.get('window'), other_args.get('stride'))
+    if window is not None:
+        clash = [k for k, on in (('scales', scales is not None), ('compiled_model', compiled_model)) if on]
+        if clash:
+            raise ValueError(f"test: window does not combine with {', '.join(clash)} (the windows run through the eager single-scale DSRL.predict)")
+        size = tuple(other_args.get('model_input_size', settings.MODEL_INPUT_SIZE))
+        if window_plan(size[0], size[1], *window) is None:       # ValueError on a window the input cannot take; the whole input is "off"
+            window = None
     if not isCUDAdevice(device):
         raise RuntimeError(NOT_GPU)
     data = None
@@ -62,6 +72,8 @@ def test(image_file, images_dir, dataset, output_dir, weights, device, compiled_
             predict = functools.partial(predict, flip=True)
         if scales is not None:
             predict = functools.partial(predict, scales=scales)
+        if window is not None:
+            predict = functools.partial(predict, window=window[0], stride=window[1])
         return _run(predict, image_file, images_dir, dataset, ds, output_dir, device_obj, input_size, output_size)
     finally:
         if predictor is not None:

@@ -24,18 +24,13 @@
 //
 // fp32 limit of ce: it is the logarithm of the ACCUMULATED probability.  Where the probability of the target underflows fp32 in every view (a logit gap
 // above about 87) the pixel's term, and with it ce, is +inf - the value fp32 gives - while a gap of 60 (p = 9e-27) is exact to an ulp of the logarithm.
-#include "common.h"
-#include <algorithm>
+#include "merge_common.h"
 #include <limits.h>
 #include <math.h>
 
 namespace dsrl {
 
 namespace {
-
-constexpr int kMergeMaxC = 32;
-constexpr int kMergeMaxBlocks = 2048;       // eight blocks of 4 waves per CU
-constexpr int kMergeStageFloats = 2304;     // per wave: 121 source columns of 19 floats
 
 // i0, i1, frac of output index o (see the header comment)
 __device__ __forceinline__ void merge_coord(int o, int S, int O, int& i0, int& i1, float& frac) {
@@ -126,16 +121,7 @@ __device__ __forceinline__ void merge_pixel(const float* __restrict__ logits, in
         m = 0.f;
     }
     __syncthreads();            // the next round overwrites the staged rows
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        if (CT == kMergeMaxC && c >= C) { p[c] = 0.f; continue; }
-        p[c] = exp_nonpos(p[c] - m);
-        sum += p[c];
-    }
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int c = 0; c < CT; ++c) p[c] *= inv;
+    merge_softmax<CT>(p, C, m);         // merge_common.h: the sliding-window ensemble takes the same softmax
 }
 
 template <int CT>
@@ -284,12 +270,6 @@ __global__ __launch_bounds__(256) void prob_merge_ce_finalize_kernel(const doubl
     }
 }
 
-int merge_spans_per_row(int Wo) { return (int)ceil_div(Wo, 64); }
-int merge_blocks(int N, int Ho, int Wo) {
-    const long long spans = (long long)N * Ho * merge_spans_per_row(Wo);
-    return (int)std::max<long long>(1, std::min<long long>(kMergeMaxBlocks, ceil_div(spans, 4)));
-}
-
 // every 32-bit index of a launch with pixel stride ld (the span index runs to the end of the last round: < nspans + 4 * kMergeMaxBlocks)
 bool merge_indices_fit(int N, int Hs, int Ws, int ld, int Ho, int Wo, int C) {
     const long long lim = INT_MAX;
@@ -308,6 +288,11 @@ int merge_check(const char* what, const float* logits, int ld, int N, int Hs, in
 }
 
 }  // namespace
+
+int launch_merge_ce_finalize(const double* part, int nb, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(prob_merge_ce_finalize_kernel, dim3(1), dim3(256), 0, st, part, nb, out);
+    return launch_status("prob_merge_ce_finalize_kernel");
+}
 
 }  // namespace dsrl
 
@@ -379,10 +364,7 @@ int merge_finish_launch(const float* logits, int ld, int N, int Hs, int Ws, int 
 #undef DSRL_MERGE_FINISH_CT
 #undef DSRL_MERGE_FINISH
     if (int e = launch_status("prob_merge_finish_kernel")) return e;
-    if (ce_out) {
-        hipLaunchKernelGGL(prob_merge_ce_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nb, ce_out);
-        return launch_status("prob_merge_ce_finalize_kernel");
-    }
+    if (ce_out) return launch_merge_ce_finalize(part, nb, ce_out, st);
     return DSRL_OK;
 }
 

@@ -3060,6 +3060,270 @@ def multiscale_merge(views, out_size, target=None, ignore_index=255, counts=None
     return out
 
 
+# ------------------------------------------------------------------------------------------------ sliding-window inference
+WINDOW_MAX_POSITIONS = 32           # per axis: the positions travel in the finish launch's argument struct (csrc/window.hip)
+
+
+def _window_pair(value, what):
+    """an integer >= 1 or a pair of them -> (int, int); ValueError on bools, strings, tensors, non-integers and values < 1"""
+    msg = f'{what} = {value!r}: expected an integer >= 1 or a pair (rows, columns) of them'
+    if isinstance(value, (str, bytes, torch.Tensor, bool, np.bool_)):
+        raise ValueError(msg)
+    if isinstance(value, (int, np.integer)):
+        value = (value, value)
+    try:
+        seq = tuple(value)
+    except TypeError:
+        raise ValueError(msg) from None
+    if len(seq) != 2:
+        raise ValueError(msg)
+    for v in seq:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+            raise ValueError(msg)
+    return int(seq[0]), int(seq[1])
+
+
+def window_value(window, stride=None):
+    """The window of sliding-window inference as ((h, w), (sy, sx)) in input pixels, or None for "off" (window None).  `window` and `stride`: an
+    integer or a pair (rows, columns) of integers >= 1; a missing stride is ceil(2 side / 3) per axis (mmseg's stride of 2/3 of the crop).
+    ValueError on bools, strings, tensors, non-integers, values < 1 and a stride without a window.  Touches no device."""
+    if window is None:
+        if stride is not None:
+            raise ValueError(f'stride = {stride!r} without a window: expected window = an integer >= 1 or a pair of them')
+        return None
+    size = _window_pair(window, 'window')
+    step = tuple(-(-2 * v // 3) for v in size) if stride is None else _window_pair(stride, 'stride')
+    return size, step
+
+
+def window_positions(S, w, s):
+    """The window positions along an axis of S pixels, window side w, stride s (mmseg's slide rule): n = max(S - w + s - 1, 0) // s + 1 of them,
+    a_i = max(min(i s + w, S) - w, 0) - the last window is pulled back to end at S.  Strictly increasing for 1 <= s and w <= S.  Pure host code."""
+    S, w, s = int(S), int(w), int(s)
+    n = max(S - w + s - 1, 0) // s + 1
+    return tuple(max(min(i * s + w, S) - w, 0) for i in range(n))
+
+
+def window_plan(H, W, window, stride=None):
+    """(ys, xs): the window positions of an (H, W) input in input pixels, their product visited row-major; None when the window is "off" (None, or
+    the whole image).  `window` / `stride` as window_value takes them.  ValueError on a window larger than the image, a stride larger
+    than the window (it would leave pixels uncovered), an image or window side that is not a multiple of 16 (the head concatenates the 4x upsampled
+    OS16 features with the OS4 features) and more than 32 positions on an axis.  Pure host code."""
+    value = window_value(window, stride)
+    if value is None:
+        return None
+    (h, w), (sy, sx) = value
+    H, W = int(H), int(W)
+    what = f'window = {h} x {w}, stride = {sy} x {sx} on a {H} x {W} input'
+    if h > H or w > W:
+        raise ValueError(f'{what}: the window is larger than the image')
+    if sy > h or sx > w:
+        raise ValueError(f'{what}: a stride larger than the window leaves pixels uncovered')
+    if H % 16 or W % 16 or h % 16 or w % 16:
+        raise ValueError(f'{what}: every side of the image and of the window must be a multiple of 16')
+    if (h, w) == (H, W):
+        return None
+    ys, xs = window_positions(H, h, sy), window_positions(W, w, sx)
+    if len(ys) > WINDOW_MAX_POSITIONS or len(xs) > WINDOW_MAX_POSITIONS:
+        raise ValueError(f'{what}: {len(ys)} x {len(xs)} positions, at most {WINDOW_MAX_POSITIONS} per axis are possible')
+    return ys, xs
+
+
+def window_fresh(positions, side, i):
+    """fresh_y (or fresh_x) of the first view of position i along an axis (include/dsrl_hip.h, dsrl_window_merge): the window's rows from this one on
+    were not covered by position i - 1"""
+    return 0 if i == 0 else positions[i - 1] + side - positions[i]
+
+
+def _window_axis(positions, side, size, what):
+    """positions along one axis of the output grid as a tuple of ints: 1 to 32, from 0, strictly increasing, no gap, the last one ending at `size`"""
+    msg = f'{what} = {positions!r}: expected 1 to {WINDOW_MAX_POSITIONS} integers that start at 0, increase, leave no gap between windows of side {side} and end at {size - side}'
+    if isinstance(positions, (str, bytes, torch.Tensor)):
+        raise ValueError(msg)
+    try:
+        seq = tuple(positions)
+    except TypeError:
+        raise ValueError(msg) from None
+    if not 1 <= len(seq) <= WINDOW_MAX_POSITIONS or any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in seq):
+        raise ValueError(msg)
+    seq = tuple(int(v) for v in seq)
+    if seq[0] != 0 or seq[-1] + side != size or any(b <= a or b > a + side for a, b in zip(seq, seq[1:])):
+        raise ValueError(msg)
+    return seq
+
+
+class WindowMerge:
+    """The sliding-window ensemble one view at a time (include/dsrl_hip.h, "sliding-window ensemble"): `add(logits)` once per view in plan order -
+    positions `ys` x `xs` (offsets on the OUTPUT grid) row-major, with `flip` the plain and then the mirrored-frame view of each position; the call
+    with the last view returns (pred, ce[, conf]), every earlier one None.  Every view goes through dsrl_window_merge into one accumulator, which the
+    launches fill without a zero fill (this class owns the order and the store-or-add offsets: callers hand it logits only), and the last call ends
+    in dsrl_window_merge_finish(_ex).  A view's logits may be freed as soon as its `add` returns.  Shapes dsrl_window_merge_supported refuses for
+    the whole batch are launched image by image; class counts it refuses are composed from torch ops under the same definition.  Bad positions are
+    a ValueError before any device work."""
+
+    def __init__(self, ys, xs, window_out, N, C, out_size, device, target=None, ignore_index=255, counts=None, nan_flag=None, confusion=None,
+                 calibration=None, confidence=False, flip=False):
+        self.N, self.C = int(N), int(C)
+        self.Ho, self.Wo = int(out_size[0]), int(out_size[1])
+        self.hw, self.ww = int(window_out[0]), int(window_out[1])
+        self.device, self.ignore_index = device, int(ignore_index)
+        if self.N < 1 or self.C < 1 or self.hw < 1 or self.ww < 1 or self.hw > self.Ho or self.ww > self.Wo:
+            raise ValueError(f'window_merge: {self.N} x {self.C} x {self.hw} x {self.ww} windows on a {self.Ho} x {self.Wo} grid: every count must be at '
+                             'least 1 and the window inside the grid')
+        self.ys, self.xs = _window_axis(ys, self.hw, self.Ho, 'ys'), _window_axis(xs, self.ww, self.Wo, 'xs')
+        self.vpp = 2 if flip else 1
+        self.V = len(self.ys) * len(self.xs) * self.vpp
+        _need_gpu(target, counts, nan_flag, confusion)
+        if target is not None:
+            if tuple(target.shape) != (self.N, self.Ho, self.Wo):
+                raise DsrlHipError(f'window_merge: target {tuple(target.shape)} is not {(self.N, self.Ho, self.Wo)}')
+            if target.dtype != torch.uint8:
+                target = target.to(torch.uint8)
+            target = target.contiguous()
+        elif counts is not None or confusion is not None or calibration is not None:
+            raise DsrlHipError('window_merge: counts, confusion and calibration need a target')
+        if confusion is not None:
+            check_confusion(confusion, self.C, device, 'window_merge')
+        self.bins = 0
+        if calibration is not None:
+            self.bins = check_calibration(calibration, _calibration_bins_of(calibration, 'window_merge'), device, 'window_merge')
+        self.calibration, self.confidence = calibration, bool(confidence)
+        if counts is not None and (counts.dtype != torch.int64 or counts.numel() != 3 * self.C + 2 or not counts.is_contiguous()):
+            raise DsrlHipError(f'window_merge: counts must be a contiguous int64 tensor of {3 * self.C + 2} elements')
+        if nan_flag is not None and (nan_flag.dtype != torch.int32 or nan_flag.numel() != 1):
+            raise DsrlHipError('window_merge: nan_flag must be an int32 scalar')
+        self.target, self.counts, self.nan_flag, self.confusion = target, counts, nan_flag, confusion
+        self.kernel = bool(cquery('dsrl_window_merge_supported', 1, 1, 1, 1, 1, self.C))
+        self.acc = None             # the kernels' accumulator (or, without the kernels, the canvas of summed probabilities)
+        self.done = 0
+
+    def _chunk(self, ld):
+        """images per launch: the batch, or one where the batch's indices leave 32 bits"""
+        for n in (self.N, 1):
+            if cquery('dsrl_window_merge_supported', n, self.hw, self.ww, self.Ho, self.Wo, self.C) and n * self.hw * self.ww * ld < 2 ** 31:
+                return n
+        raise DsrlHipError(f'window_merge: a single {self.C} x {self.hw} x {self.ww} window on a {self.Ho} x {self.Wo} grid is beyond the 32-bit '
+                           'indices of dsrl_window_merge')
+
+    def add(self, logits):
+        if self.done >= self.V:
+            raise DsrlHipError(f'window_merge: all {self.V} views were merged already')
+        with torch.no_grad():
+            logits, ld = pm(logits)
+            if tuple(logits.shape) != (self.N, self.C, self.hw, self.ww) or logits.device != self.device:
+                raise DsrlHipError(f'window_merge: view {self.done} is {tuple(logits.shape)} on {logits.device}, expected '
+                                   f'{(self.N, self.C, self.hw, self.ww)} on {self.device}')
+            position, view = divmod(self.done, self.vpp)
+            i, j = divmod(position, len(self.xs))
+            mirrored = view == 1
+            self.done += 1
+            last = self.done == self.V
+            if not self.kernel:
+                return self._add_torch(logits, i, j, mirrored, last)
+            C, Ho, Wo, hw, ww = self.C, self.Ho, self.Wo, self.hw, self.ww
+            n, st = self._chunk(ld), _stream()
+            if self.acc is None:
+                self.acc = torch.empty(self.N * (cquery('dsrl_prob_merge_acc_bytes', 1, Ho, Wo, C) // 4), device=self.device, dtype=torch.float32)
+            acc_step = C * Ho * Wo * 4          # bytes per image (dsrl_prob_merge_acc_bytes is linear in N)
+            # a mirrored view is never the first one of its pixels: nothing of it is stored
+            fresh = (hw, 0) if mirrored else (window_fresh(self.ys, hw, i), window_fresh(self.xs, ww, j))
+            for k in range(0, self.N, n):
+                call('dsrl_window_merge', logits.data_ptr() + k * hw * ww * ld * 4, ld, n, hw, ww, C, int(mirrored), self.acc.data_ptr() + k * acc_step,
+                     Ho, Wo, self.ys[i], self.xs[j], fresh[0], fresh[1], st)
+            if not last:
+                return None
+            tgt = self.target
+            pred = torch.empty((self.N, Ho, Wo), device=self.device, dtype=torch.uint8)
+            ce = torch.empty((self.N // n, 2), device=self.device, dtype=torch.float32) if tgt is not None else None
+            ws = _ws(cquery('dsrl_window_merge_workspace_bytes', n, Ho, Wo) if ce is not None else 0, logits)
+            ex = self.calibration is not None or self.confidence
+            conf = torch.empty((self.N, Ho, Wo), device=self.device, dtype=torch.float32) if self.confidence else None
+            more = (conf,) if self.confidence else ()
+            ys, xs = (ctypes.c_int * len(self.ys))(*self.ys), (ctypes.c_int * len(self.xs))(*self.xs)
+            for q, k in enumerate(range(0, self.N, n)):
+                extra = () if not ex else (None if self.calibration is None else self.calibration.data_ptr(), self.bins,
+                                           None if conf is None else conf.data_ptr() + 4 * k * Ho * Wo)
+                call('dsrl_window_merge_finish_ex' if ex else 'dsrl_window_merge_finish', self.acc.data_ptr() + k * acc_step, n, C, Ho, Wo, ys, len(self.ys),
+                     xs, len(self.xs), hw, ww, self.vpp, pred.data_ptr() + k * Ho * Wo, None if tgt is None else tgt.data_ptr() + k * Ho * Wo,
+                     self.ignore_index, None if self.counts is None else self.counts.data_ptr(), None if ce is None else ce.data_ptr() + 8 * q,
+                     None if self.nan_flag is None else self.nan_flag.data_ptr(), ws.data_ptr(), ws.numel(),
+                     None if self.confusion is None else self.confusion.data_ptr(), *extra, st)
+            self.acc = None
+            if ce is None:
+                return (pred, None) + more
+            if ce.shape[0] == 1:
+                return (pred, ce[0, 0]) + more
+            mean, cnt = ce[:, 0].double(), ce[:, 1].double()            # per image: a mean over no pixel (NaN) carries no weight
+            return (pred, (torch.where(cnt > 0, mean * cnt, torch.zeros_like(mean)).sum() / cnt.sum()).float()) + more
+
+    def _add_torch(self, logits, i, j, mirrored, last):
+        if self.acc is None:
+            self.acc = torch.zeros((self.N, self.C, self.Ho, self.Wo), device=self.device, dtype=torch.float32)
+        p = torch.softmax(logits.flip(3) if mirrored else logits, dim=1)
+        self.acc[:, :, self.ys[i]:self.ys[i] + self.hw, self.xs[j]:self.xs[j] + self.ww] += p
+        if not last:
+            return None
+        tot, self.acc = self.acc, None
+        cover = []
+        for positions, side, size in ((self.ys, self.hw, self.Ho), (self.xs, self.ww, self.Wo)):
+            o = torch.arange(size, device=self.device).unsqueeze(0)
+            a = torch.tensor(positions, device=self.device).unsqueeze(1)
+            cover.append(((o >= a) & (o < a + side)).sum(0))
+        cnt = (cover[0].unsqueeze(1) * cover[1].unsqueeze(0) * self.vpp).to(torch.float32)
+        if self.nan_flag is not None:
+            nan_check_(self.nan_flag, tot)
+        pred = torch.argmax(tot, dim=1).to(torch.uint8)
+        tgt = self.target
+        prob = tot / cnt
+        more = ()
+        if self.calibration is not None or self.confidence:
+            conf = _calibration_of_scores(self.calibration, prob, pred, tgt, self.ignore_index, self.C, self.confidence)
+            more = (conf,) if self.confidence else ()
+        if tgt is None:
+            return (pred, None) + more
+        if self.nan_flag is not None:
+            _bad_label_bit(self.nan_flag, tgt, self.ignore_index, self.C)
+        if self.counts is not None:
+            lg, ld = pm(tot)
+            call('dsrl_seg_metrics', lg.data_ptr(), ld, tgt.data_ptr(), tgt.numel(), self.C, self.ignore_index, self.counts.data_ptr(), _stream())
+        if self.confusion is not None:
+            confusion_matrix_(self.confusion, pred, tgt, self.C, self.ignore_index)
+        counted = tgt != self.ignore_index
+        picked = prob.gather(1, tgt.long().clamp(max=self.C - 1).unsqueeze(1))[:, 0]
+        ce = (-torch.log(picked))[counted].mean()
+        bad = (counted & (tgt >= self.C)).any()
+        return (pred, torch.where(bad, torch.full_like(ce, float('nan')), ce)) + more
+
+
+def window_merge(views, ys, xs, out_size, target=None, ignore_index=255, counts=None, nan_flag=None, confusion=None, calibration=None, confidence=False,
+                 flip=False):
+    """The sliding-window (and flip) ensemble of given logits: `views` is the list of the windows' logits (N,C,hw,ww), all of one size, in plan
+    order - positions `ys` x `xs` (offsets on the `out_size` = (Ho, Wo) grid: any integers that start at 0, increase, leave no gap and end at the
+    grid's end) row-major, with `flip` two per position, the second in the horizontally mirrored frame.  Every view's softmax is added where the
+    window lies (a mirrored one mirrored back first) and the sum divided by the number of views covering the pixel (dsrl_window_merge,
+    dsrl_window_merge_finish).  -> (pred uint8 (N,Ho,Wo), ce): pred is the first maximum of the summed probabilities; with `target` (N,Ho,Wo)
+    `ce` is the 0-d mean of -log P[target] over target != ignore_index, `counts` (int64 [3*classes+2], optional) gets the dsrl_seg_metrics table of
+    pred ADDED and `confusion` (int64 [classes^2], optional) its confusion matrix; `nan_flag` (int32 scalar, optional): bit 0 a NaN logit in any
+    view, bit 1 a label outside the classes; `calibration` (int64 [3*bins], optional, needs a target) gets the reliability record of pred ADDED,
+    `confidence=True` appends the confidence map (float32 (N,Ho,Wo): min(1, winning sum / views covering the pixel)).  Beyond pred the call
+    allocates one accumulator of N * classes * Ho * Wo floats, which is never filled, and the loss workspace."""
+    views = list(views)
+    if not views:
+        raise DsrlHipError('window_merge: no views')
+    first = views[0]
+    _need_gpu(*views)
+    if first.dim() != 4:
+        raise DsrlHipError(f'4-D (N,C,H,W) tensor expected, got shape {tuple(first.shape)}')
+    merge = WindowMerge(ys, xs, first.shape[2:], first.shape[0], first.shape[1], out_size, first.device, target, ignore_index, counts, nan_flag, confusion,
+                        calibration, confidence, flip)
+    if len(views) != merge.V:
+        raise DsrlHipError(f'window_merge: {len(views)} views for {len(merge.ys)} x {len(merge.xs)} positions of {merge.vpp}: {merge.V} expected')
+    out = None
+    for logits in views:
+        out = merge.add(logits)
+    return out
+
+
 _palettes = {}
 
 

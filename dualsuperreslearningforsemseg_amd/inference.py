@@ -196,7 +196,8 @@ class CompiledPredictor:
     `confusion` (DSRL.predict_head): the caller's matrix gets exactly this batch's counts added, replayed or eager.  A graph never holds the caller's
     pointer: it fills a static matrix of its own, zeroed by a node of the graph, which the call then adds to the tensor it was given - successive
     calls may pass different tensors.  `scales` (DSRL.predict: the multi-scale ensemble) other than "off" raises DsrlHipError before anything else is
-    looked at - its graph replay is not built - and leaves the predictor as it was.
+    looked at - its graph replay is not built - and leaves the predictor as it was; so does `window` (DSRL.predict: sliding-window inference), with a
+    ValueError.
 
     One graph per key (N, H, W, with target, conv arithmetic, flip, with confusion), captured at the key's first use after GRAPH_WARMUP eager calls (the frozen eager path:
     the same kernels), at most MAX_GRAPHS keys; further shapes, and every shape when `graph` is False or a capture failed, run the frozen eager path.
@@ -267,7 +268,7 @@ class CompiledPredictor:
 
     # ------------------------------------------------------------------ the call
     def __call__(self, images, target=None, ignore_index=255, nan_flag=None, copy=True, flip=False, confusion=None, scales=None, calibration=None,
-                 confidence=False, temperature=None):
+                 confidence=False, temperature=None, window=None, stride=None):
         if calibration is not None or confidence:
             # graphs are keyed on their outputs: the calibration record and the confidence map are not among the keys
             raise ValueError('CompiledPredictor: calibration and confidence are outputs of DSRL.predict only, not of a compiled predictor')
@@ -276,6 +277,9 @@ class CompiledPredictor:
             raise ValueError('CompiledPredictor: temperature is an option of DSRL.predict only, not of a compiled predictor')
         if HF.multiscale_scales_value(scales) is not None:
             raise DsrlHipError(MULTISCALE_NOT_COMPILED)
+        if HF.window_value(window, stride) is not None:
+            # a graph is keyed on the batch's shape: the windows of an image would be a loop of replays with a merge between them, which is not built
+            raise ValueError('CompiledPredictor: window is an option of DSRL.predict only, not of a compiled predictor')
         if self.frozen.released:
             raise DsrlHipError('this CompiledPredictor was released: call compile_predict() again')
         self.frozen.check()

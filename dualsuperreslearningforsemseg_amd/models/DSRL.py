@@ -171,7 +171,8 @@ class DSRL(BaseModel):
         return (out[0], counts, out[1]) + tuple(out[2:])
 
     def predict(self, x: t.Tensor, target: t.Tensor = None, ignore_index: int = 255, nan_flag: t.Tensor = None, flip: bool = False,
-                confusion: t.Tensor = None, scales=None, calibration: t.Tensor = None, confidence: bool = False, temperature=None):
+                confusion: t.Tensor = None, scales=None, calibration: t.Tensor = None, confidence: bool = False, temperature=None, window=None,
+                stride=None):
         """Class map of a batch: (pred, counts or None, ce or None), see predict_head.  Runs under no_grad and raises in train mode.  Without a
         `nan_flag` of the caller's the flag is read back here and a NaN logit or an out-of-range label raises; a caller that passes one reads it when
         it chooses to (command_handlers.benchmark: once, after the last batch).
@@ -185,7 +186,15 @@ class DSRL(BaseModel):
         averaged); pred, counts, ce, confusion and the NaN flag are those of the ensemble.
         `calibration`, `confidence`: see predict_head; with `flip` and `scales` they are the record and the confidence map of the ensemble.
         `temperature`: see predict_head (a T fitted by command_handlers.fit_temperature); combines with flip, target, confusion, calibration and
-        confidence.  With `scales` it is a ValueError before any device work: the multi-scale merge takes no temperature."""
+        confidence.  With `scales` it is a ValueError before any device work: the multi-scale merge takes no temperature.
+        `window`, `stride` (functional.window_value: an integer or a pair (rows, columns) of input pixels; None, and a window that is the whole image,
+        are "off" and leave every launch as it is; a missing stride is 2/3 of the window): sliding-window inference.  The ASPP's global-average-pool
+        branch makes the network depend on the input size, so an image larger than the training crop is evaluated in overlapping windows of the
+        training size: for each position of functional.window_plan in turn the crop goes through the eval forward path (with `flip` the crop and its
+        mirror image in one batch), its SSSR logits are merged into the ensemble where the window lies and released before the next position runs
+        (functional.WindowMerge: softmax per view, class probabilities averaged over the views covering a pixel - mmseg's slide mode averages
+        logits); pred, counts, ce, confusion, calibration, confidence and the NaN flag are those of the ensemble.  With `scales` or `temperature`
+        it is a ValueError before any device work."""
         if self.training:
             raise HF.DsrlHipError('DSRL.predict* is inference: call model.eval() first')
         if confusion is not None and target is None:
@@ -196,6 +205,15 @@ class DSRL(BaseModel):
         scales = HF.multiscale_scales_value(scales)
         if temperature is not None and scales is not None:
             raise ValueError('DSRL.predict: temperature does not combine with scales (the multi-scale merge takes no temperature)')
+        window = HF.window_value(window, stride)
+        if window is not None:
+            if scales is not None or temperature is not None:
+                raise ValueError('DSRL.predict: window does not combine with scales or temperature (the window merge resamples nothing and takes no temperature)')
+            if x.dim() != 4:
+                raise HF.DsrlHipError(f'DSRL.predict: (N,3,H,W) images expected, got shape {tuple(x.shape)}')
+            plan = HF.window_plan(x.shape[2], x.shape[3], *window)           # None: the window is the whole image, "off"
+            if plan is not None:
+                return self._predict_windows(x, target, ignore_index, nan_flag, flip, confusion, window, plan, calibration, confidence)
         if scales is not None:
             return self._predict_multiscale(x, target, ignore_index, nan_flag, flip, confusion, scales, calibration, confidence)
         own = nan_flag is None
@@ -285,6 +303,42 @@ class DSRL(BaseModel):
                 else:
                     out = merge.add(logits, False)
                 del logits, xk                  # one scale's logits at a time
+        if own:
+            bits = int(nan_flag.item())
+            if bits:
+                raise HF.DsrlHipError('DSRL.predict: ' + ' and '.join(m for b, m in ((1, 'NaN in the input or the logits'), (2, 'labels outside the classes')) if bits & b))
+        return (out[0], counts, out[1]) + tuple(out[2:])
+
+    def _predict_windows(self, x, target, ignore_index, nan_flag, flip, confusion, window, plan, calibration=None, confidence=False):
+        HF._need_gpu(x, target, nan_flag, confusion, calibration)
+        N, _, H, W = x.shape
+        (h, w), (ys, xs) = window[0], plan
+        own = nan_flag is None
+        with t.no_grad():
+            if own:
+                nan_flag = t.zeros((), dtype=t.int32, device=x.device)
+            HF.nan_check_(nan_flag, x)          # once, on the images as given: every window is a crop of them
+            classes = self.SSSR_decoder['upsample16_pred'][6].out_channels
+            counts = t.zeros(3 * classes + 2, dtype=t.int64, device=x.device) if target is not None else None
+            merge = HF.WindowMerge(tuple(2 * y for y in ys), tuple(2 * v for v in xs), (2 * h, 2 * w), N, classes, (2 * H, 2 * W), x.device, target,
+                                   ignore_index, counts, nan_flag, confusion, calibration, confidence, flip)
+            out = None
+            for y0 in ys:
+                for x0 in xs:
+                    crop = x[:, :, y0:y0 + h, x0:x0 + w]
+                    if flip:
+                        xk = t.empty((2 * N, x.shape[1], h, w), dtype=x.dtype, device=x.device, memory_format=t.channels_last)
+                        xk[:N].copy_(crop)
+                        xk[N:].copy_(crop.flip(3))
+                    else:
+                        xk = crop.contiguous(memory_format=t.channels_last)
+                    logits = self._eval_sssr_logits(xk)
+                    if flip:
+                        merge.add(logits[:N])
+                        out = merge.add(logits[N:])
+                    else:
+                        out = merge.add(logits)
+                    del logits, xk              # one position's logits at a time
         if own:
             bits = int(nan_flag.item())
             if bits:

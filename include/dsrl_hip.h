@@ -796,6 +796,50 @@ int dsrl_prob_merge_finish(const float* logits, int ld, int N, int Hs, int Ws, i
                            void* ws, size_t ws_bytes, unsigned long long* cm /*nullable, [C*C]*/, dsrl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * inference: the sliding-window ensemble (csrc/window.hip) - "slide" evaluation: the image in overlapping windows of the training size
+ *   Plan (pure host code, functional.window_plan).  Along an axis of S input pixels with window side w and stride s (1 <= s <= w <= S) the positions
+ *   are n = max(S - w + s - 1, 0) / s + 1 and a_i = max(min(i s + w, S) - w, 0): the last window is pulled back to end at S, positions are strictly
+ *   increasing.  The 2-D plan is the product ys x xs, visited row-major.  On the model path H, W, h, w are multiples of 16, 16 <= h <= H,
+ *   16 <= w <= W, and there are at most 32 positions per axis.
+ *   Ensemble.  A window's crop goes through the eval forward path (with flip the crop and its mirror image in one batch); its SSSR logits
+ *   (N,C,2h,2w) sit at (2 y0, 2 x0) on the (2H,2W) grid.  On the grid (Ho,Wo): tot = sum over the views covering a pixel of softmax_c(logits), a
+ *   mirrored view mirrored back along W first; cnt = (y-positions covering the row) x (x-positions covering the column) x views_per_position;
+ *   P = tot / cnt; pred = lowest index among the maxima of tot; ce_out[0] = mean of -log P[target] over the counted pixels (target !=
+ *   ignore_index), ce_out[1] their number; confidence = min(1, tot[pred] / cnt); counts, cm, cal, conf and nan_flag exactly as
+ *   dsrl_prob_merge_finish_ex defines them for its ensemble (bit 0: a NaN logit in ANY covering view, bit 1: a label >= C that is not ignore_index,
+ *   which also makes ce_out NaN).  Class PROBABILITIES are averaged, as in the flip and multi-scale modes; mmseg's slide mode averages logits.
+ *   The softmax is the function of the multi-scale ensemble (csrc/merge_common.h): one whole-image window gives the bits of one identity view of
+ *   dsrl_prob_merge_finish.
+ * dsrl_window_merge: one view of one position.  logits (N,hw,ww,C) pixel-major with pixel stride ld >= C, in the plain or (mirror != 0) the mirrored
+ *   frame; the window's pixel (wy, wx) is pixel (oy + wy, ox + wx) of acc (class-planar, dsrl_prob_merge_acc_bytes(N, Ho, Wo, C) bytes, the
+ *   kernels' own).  It is STORED without reading acc iff wy >= fresh_y && wx >= fresh_x, otherwise ADDED: acc needs no fill.  With the positions
+ *   visited row-major a pixel of window (i, j) has been covered before iff it lies above grid row ys[i-1] + hw or left of grid column xs[j-1] + ww,
+ *   so the first view of position (i, j) takes fresh_y = i ? ys[i-1] + hw - ys[i] : 0, fresh_x likewise, and a view that is never the first one of
+ *   its pixels (the mirrored one) fresh_y = hw.  0 <= fresh_y <= hw, 0 <= fresh_x <= ww; the window must lie inside the grid (DSRL_E_BADARG).
+ *   functional.WindowMerge owns the order and the offsets: callers hand it logits only.
+ * dsrl_window_merge_finish(_ex): one pass over acc after the last view.  ys / xs: HOST arrays of ny / nx grid offsets (at most 32 each), copied into
+ *   the launch's arguments - no device table, no copy, capturable.  DSRL_E_BADARG unless each axis starts at 0, increases strictly, leaves no gap
+ *   (a_i <= a_{i-1} + side) and ends at the grid's end.  counts, ce_out, cm and cal need a target; _ex adds cal (the record, [3 * bins]) and conf
+ *   (the confidence map (N,Ho,Wo)), both nullable.  Every output is bit-identical run to run: integer atomics for the counters, per-block loss
+ *   partials in ws reduced in block order, no float atomics.  acc and conf 4-byte, ws and cal 8-byte aligned; pred and target any byte, any Wo.
+ * _supported: 1 for 1 <= C <= 32 (and C <= dsrl_confusion_matrix_max_classes()), hw <= Ho, ww <= Wo and every 32-bit index in range
+ *   (N*Ho*Wo*C, N*hw*ww*C <= 2^31 - 1; a launch checks N*hw*ww*ld itself), 0 otherwise; pure host code.  _workspace_bytes depends on the shape only.
+ * ---------------------------------------------------------------------------------------------- */
+int dsrl_window_merge_supported(int N, int hw, int ww, int Ho, int Wo, int C);
+size_t dsrl_window_merge_workspace_bytes(int N, int Ho, int Wo);
+int dsrl_window_merge(const float* logits, int ld, int N, int hw, int ww, int C, int mirror, float* acc, int Ho, int Wo, int oy, int ox, int fresh_y,
+                      int fresh_x, dsrl_stream_t stream);
+int dsrl_window_merge_finish(const float* acc, int N, int C, int Ho, int Wo, const int* ys /*host, ny*/, int ny, const int* xs /*host, nx*/, int nx, int hw,
+                             int ww, int views_per_position, uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index,
+                             unsigned long long* counts /*nullable*/, float* ce_out /*nullable, [2]: mean, counted pixels*/, int* nan_flag /*nullable*/,
+                             void* ws, size_t ws_bytes, unsigned long long* cm /*nullable, [C*C]*/, dsrl_stream_t stream);
+int dsrl_window_merge_finish_ex(const float* acc, int N, int C, int Ho, int Wo, const int* ys /*host, ny*/, int ny, const int* xs /*host, nx*/, int nx,
+                                int hw, int ww, int views_per_position, uint8_t* pred, const uint8_t* target /*nullable*/, int ignore_index,
+                                unsigned long long* counts /*nullable*/, float* ce_out /*nullable*/, int* nan_flag /*nullable*/, void* ws, size_t ws_bytes,
+                                unsigned long long* cm /*nullable, [C*C]*/, unsigned long long* cal /*nullable, [3*bins]*/, int bins,
+                                float* conf /*nullable, (N,Ho,Wo)*/, dsrl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * calibration: the reliability record and the confidence map (csrc/calibration.hip; the arithmetic is written once in csrc/common.h)
  *   Confidence of a pixel: the probability of the class the producer reports (first maximum), fp32, from values it already has -
  *     from logits and the single-view tail: 1 / sum_c exp(v_c - max) (the sum the cross entropy forms, c ascending);

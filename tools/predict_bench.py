@@ -33,6 +33,18 @@ on uniform labels and on labels / predictions that are class 0 on ~90 % of the p
 and lists the registers of the merge kernels.
 
     python tools/predict_bench.py --multiscale [--out profiles/predict_multiscale.txt]
+
+--window WITHOUT a value measures sliding-window inference (profiles/predict_window.txt) on 512x1024 images, batch 1 and 8, window 256x512 at the default
+stride (3 x 3 positions), plain and flip (timing windows of --seconds, default 0.5):
+  (a) the merge and finish launches (functional.window_merge, all views) against the torch composition on the same logits (softmax, add into a canvas,
+      divide by a count map, argmax), alternating in one call, with the peak memory of each,
+  (b) one dsrl_window_merge launch and the dsrl_window_merge_finish launch against the bytes they must move, beside a dsrl_copy2d of as many bytes,
+  (c) DSRL.predict(window=...) against the nine DSRL.predict calls on the crops,
+  (d) the default DSRL.predict (256x512, batch 8) and the default train step (bench.py --gpus 1) of this tree against the parent commit in its own
+      tree with its own library under ab/prev_tree (as tools/ab_tree.sh), each round parent, this, parent again; skipped, and said so, without it,
+and lists the registers of the window kernels.
+
+    python tools/predict_bench.py --window [--out profiles/predict_window.txt]
 """
 import argparse
 import math
@@ -417,10 +429,194 @@ def multiscale_main(args):
             f.write('\n'.join(lines) + '\n')
 
 
+WIN_IMAGE, WIN_SIZE = (512, 1024), (256, 512)
+# (d): what a fresh process runs in each tree: the default predict on a 256x512 batch of 8, ms per call over three windows
+_PREDICT_PROBE = '''
+import sys, torch
+sys.path.insert(0, "tools"); sys.path.insert(0, ".")
+import predict_bench as PB
+from dualsuperreslearningforsemseg_amd.datasets.Cityscapes import settings as CS
+from dualsuperreslearningforsemseg_amd.models.DSRL import DSRL
+torch.manual_seed(7)
+dev = torch.device("cuda:0")
+model = DSRL(1, CS).to(dev).to(memory_format=torch.channels_last).eval()
+flag = torch.zeros((), dtype=torch.int32, device=dev)
+img = torch.randn(8, 3, 256, 512, device=dev).contiguous(memory_format=torch.channels_last)
+fn = lambda: model.predict(img, nan_flag=flag)[0]
+for _ in range(5):
+    fn()
+print("PREDICT_MS", min(PB.window(fn, 0.5) for _ in range(3)), int(fn().sum().item()))
+'''
+
+
+def window_against_parent(say, steps=30, rounds=2):
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    prev = os.path.join(root, 'ab', 'prev_tree')
+    say(f'(d) this tree against the parent commit (its own tree and library under ab/prev_tree), fresh processes, each round parent, this, parent again: '
+        f'the default DSRL.predict (stage 1, 256x512, batch 8, best of three windows, ms per call) and the default replayed train step '
+        f'(bench.py --gpus 1 --steps {steps} --warmup 8, ms per step)')
+    if not os.path.isfile(os.path.join(prev, 'bench.py')):
+        say('    NOT MEASURED: no parent tree under ab/prev_tree')
+        return
+
+    def predict_ms(tree):
+        r = subprocess.run([sys.executable, '-c', _PREDICT_PROBE], cwd=tree, capture_output=True, text=True, timeout=300)
+        if r.returncode != 0:
+            raise RuntimeError(f'the predict probe in {tree} ended with {r.returncode}: {r.stderr[-400:]}')
+        w = [ln for ln in r.stdout.splitlines() if ln.startswith('PREDICT_MS')][-1].split()
+        return float(w[1]), w[2]
+
+    def step_ms(tree):
+        r = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', str(steps), '--warmup', '8'], cwd=tree, capture_output=True, text=True,
+                           timeout=300)
+        if r.returncode != 0:
+            raise RuntimeError(f'bench.py in {tree} ended with {r.returncode}: {r.stderr[-400:]}')
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+        return float(d['ms_per_step']), json.dumps(d['config']['losses_last_step'])
+
+    for name, probe in (('default predict', predict_ms), ('default train step', step_ms)):
+        parent, this, marks = [], [], set()
+        for r in range(rounds):
+            (a, ma), (b, mb), (c, mc) = probe(prev), probe(root), probe(prev)
+            parent += [a, c]; this.append(b)
+            marks |= {ma, mb, mc}
+            say(f'    {name}, round {r + 1}: parent {a:.3f}  this {b:.3f}  parent-again {c:.3f}')
+        pm, tm = sum(parent) / len(parent), sum(this) / len(this)
+        say(f'    {name}: parent {min(parent):.3f} .. {max(parent):.3f} (spread {max(parent) - min(parent):.3f}, mean {pm:.3f}); this {min(this):.3f} .. '
+            f'{max(this):.3f} (mean {tm:.3f}); this - parent mean {tm - pm:+.3f} ms: '
+            + ('inside' if min(parent) <= tm <= max(parent) else 'BELOW (faster than)' if tm < min(parent) else 'ABOVE (slower than)')
+            + " the parent's own spread; results (class-map checksum / losses of the last step) "
+            + ('identical in all runs' if len(marks) == 1 else 'DIFFERENT: ' + ' '.join(sorted(marks))))
+
+
+def window_main(args):
+    lines = []
+
+    def say(s=''):
+        print(s, flush=True)
+        lines.append(s)
+
+    seconds = args.seconds
+    say(f'Sliding-window inference: images {WIN_IMAGE[0]}x{WIN_IMAGE[1]}, window {WIN_SIZE[0]}x{WIN_SIZE[1]}, default stride; timing windows of >= '
+        f'{seconds} s per side, {args.rounds} alternations A B A B ..; mean [each window]')
+    say()
+    window_against_parent(say)              # before this process opens the device: one bench at a time has it to itself
+    say()
+    import kernel_resources as KR
+    from dualsuperreslearningforsemseg_amd import _lib
+    from dualsuperreslearningforsemseg_amd._lib import call
+    import ctypes
+    dev = torch.device('cuda:0')
+
+    def fmt(ts, scale=1e3, unit='us'):
+        return f'{sum(ts) / len(ts) * scale:9.1f} {unit} [{", ".join(f"{t * scale:.1f}" for t in ts)}]'
+
+    H, W = WIN_IMAGE
+    (h, w), stride = HF.window_value(WIN_SIZE)
+    ys, xs = HF.window_plan(H, W, WIN_SIZE)
+    Ho, Wo, hw, ww = 2 * H, 2 * W, 2 * h, 2 * w
+    oys, oxs = tuple(2 * y for y in ys), tuple(2 * x for x in xs)
+    say(f'{torch.cuda.get_device_name(0)}; stride {stride[0]}x{stride[1]} -> positions y {ys} x {xs}: {len(ys)} x {len(xs)}; class maps {Ho}x{Wo}, a window\'s logits '
+        f'{hw}x{ww}')
+    say()
+    say('(a) the merge alone, on the same logits (random normal, one (N,19,2h,2w) tensor per view; with flip two per position, the second mirrored): '
+        'A = torch softmax -> add into a zeroed canvas per view, divide by the count map, argmax; B = functional.window_merge (dsrl_window_merge per '
+        'view, dsrl_window_merge_finish)')
+    slower = []
+    for flip in (False, True):
+        vpp = 2 if flip else 1
+        for N in (1, 8):
+            views = [torch.randn(N, NC, hw, ww, device=dev).contiguous(memory_format=torch.channels_last) for _ in range(len(ys) * len(xs) * vpp)]
+            cnt = torch.zeros(Ho, Wo, device=dev)
+            for y in oys:
+                for x in oxs:
+                    cnt[y:y + hw, x:x + ww] += vpp
+
+            def a():
+                with torch.no_grad():
+                    canvas = torch.zeros(N, NC, Ho, Wo, device=dev)
+                    for k, L in enumerate(views):
+                        pos, v = divmod(k, vpp)
+                        i, j = divmod(pos, len(oxs))
+                        canvas[:, :, oys[i]:oys[i] + hw, oxs[j]:oxs[j] + ww] += torch.softmax(L.flip(3) if v else L, dim=1)
+                    return torch.argmax(canvas / cnt, dim=1)
+
+            def b():
+                return HF.window_merge(views, oys, oxs, (Ho, Wo), flip=flip)[0]
+
+            ta, tb = ab(a, b, seconds, args.rounds)
+            mem_a, mem_b = peak_bytes(a), peak_bytes(b)
+            agree = (a() == b()).float().mean().item()
+            ma, mb = _row(say, f'N={N} {"flip " if flip else "plain"} {len(views):2d} views', ta, tb,
+                          extra=f'   peak memory A {mem_a / 1e6:8.1f} MB  B {mem_b / 1e6:7.1f} MB   class maps agree at {100 * agree:.3f} %')
+            if mb > ma:
+                slower.append((N, flip))
+            del views
+    say('rows where B is slower than A: ' + (', '.join(str(r) for r in slower) if slower else 'none'))
+    say()
+    say('(b) bytes per launch.  dsrl_window_merge that ADDS a whole window (fresh_y = window rows): window area of the accumulator read + written + the '
+        'logits once; one that STORES it (fresh 0, 0): written + logits; dsrl_window_merge_finish: the accumulator read + one byte of class map per pixel.  '
+        'Beside each a dsrl_copy2d moving the same number of bytes (half read, half written)')
+    cy, cx = (ctypes.c_int * len(oys))(*oys), (ctypes.c_int * len(oxs))(*oxs)
+    for N in (1, 8):
+        acc = torch.zeros(_lib.query('dsrl_prob_merge_acc_bytes', N, Ho, Wo, NC) // 4, device=dev)
+        pred = torch.empty((N, Ho, Wo), device=dev, dtype=torch.uint8)
+        L = torch.randn(N, NC, hw, ww, device=dev).contiguous(memory_format=torch.channels_last)
+        st = HF._stream()
+        for label, nbytes, fn in (
+                ('merge, add  ', 3 * L.numel() * 4, lambda: call('dsrl_window_merge', L.data_ptr(), NC, N, hw, ww, NC, 0, acc.data_ptr(), Ho, Wo, oys[1], oxs[1], hw, 0, st)),
+                ('merge, store', 2 * L.numel() * 4, lambda: call('dsrl_window_merge', L.data_ptr(), NC, N, hw, ww, NC, 0, acc.data_ptr(), Ho, Wo, oys[1], oxs[1], 0, 0, st)),
+                ('finish      ', acc.numel() * 4 + pred.numel(), lambda: call('dsrl_window_merge_finish', acc.data_ptr(), N, NC, Ho, Wo, cy, len(oys), cx, len(oxs),
+                                                                              hw, ww, 1, pred.data_ptr(), None, 255, None, None, None, None, 0, None, st))):
+            rows = nbytes // (2 * 4 * 64)
+            src, dst = torch.randn(rows * 64, device=dev), torch.empty(rows * 64, device=dev)
+            tm, tc = ab(fn, lambda: call('dsrl_copy2d', src.data_ptr(), 64, dst.data_ptr(), 64, rows, 64, st), seconds, args.rounds)
+            mm, mc = sum(tm) / len(tm), sum(tc) / len(tc)
+            say(f'N={N} {label}: {nbytes / 1e6:7.1f} MB   launch {fmt(tm)} = {nbytes / (mm * 1e-3) / 1e12:5.2f} TB/s   copy2d {fmt(tc)} = '
+                f'{nbytes / (mc * 1e-3) / 1e12:5.2f} TB/s   ({100 * mc / mm:.0f} % of the copy\'s rate; HBM {HBM_BPS / 1e12:.2f} TB/s)')
+            del src, dst
+        del acc, L, pred
+    say()
+    say('(c) whole model (stage 1, random weights, eval, caller-owned nan_flag: no readback): A = the nine DSRL.predict calls on the crops (class maps '
+        'only: what the trunk and the fused tail cost), B = DSRL.predict(window=...) (logits written, merged, released per position)')
+    model = DSRL(1, CS).to(dev).to(memory_format=torch.channels_last).eval()
+    flag = torch.zeros((), dtype=torch.int32, device=dev)
+    for flip in (False, True):
+        for N in (1, 8):
+            img = torch.randn(N, 3, H, W, device=dev).contiguous(memory_format=torch.channels_last)
+            crops = [img[:, :, y:y + h, x:x + w].contiguous(memory_format=torch.channels_last) for y in ys for x in xs]
+
+            def a():
+                return [model.predict(c, nan_flag=flag, flip=flip)[0] for c in crops]
+
+            def b():
+                return model.predict(img, nan_flag=flag, flip=flip, window=WIN_SIZE)[0]
+
+            ta, tb = ab(a, b, seconds, args.rounds)
+            _row(say, f'batch {N} {"flip " if flip else "plain"}', ta, tb, 1.0, 'ms',
+                 f'   peak memory A {peak_bytes(a) / 1e6:8.1f} MB  B {peak_bytes(b) / 1e6:8.1f} MB   whole-image predict '
+                 f'{window(lambda: model.predict(img, nan_flag=flag, flip=flip)[0], seconds):7.3f} ms')
+    say()
+    say('kernel resources (tools/kernel_resources.py on libdsrl_hip.so):')
+    ks = KR.kernels(_lib.LIB_PATH)
+    for k, n in zip(ks, KR.demangle([k['name'] for k in ks])):
+        if 'window_merge' in n or 'window_finish' in n:
+            say(f"vgpr {k.get('vgpr', 0):3d} agpr {k.get('agpr', 0):3d} sgpr {k.get('sgpr', 0):3d} scratch {k.get('scratch', 0):5d} B  spills v{k.get('vgpr_spill', 0)} "
+                f"s{k.get('sgpr_spill', 0)}  lds {k.get('lds', 0):6d}  {n[:110]}")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
-    ap.add_argument('--window', type=float, default=0.5)
+    ap.add_argument('--window', type=float, nargs='?', default=0.5, const=None,
+                    help='seconds of device work per timing window; WITHOUT a value: measure sliding-window inference (profiles/predict_window.txt)')
+    ap.add_argument('--seconds', type=float, default=0.5, help='with a bare --window: seconds of device work per timing window')
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--flip', action='store_true', help='measure the horizontal-flip ensemble (profiles/predict_flip.txt)')
     ap.add_argument('--confusion', action='store_true', help='measure the device confusion matrix (profiles/predict_confusion.txt)')
@@ -428,6 +624,8 @@ def main():
     ap.add_argument('--multiscale', action='store_true', help='measure the multi-scale ensemble (profiles/predict_multiscale.txt)')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'predict_bench.py measures on the GPU only'
+    if args.window is None:
+        return window_main(args)
     if args.multiscale:
         return multiscale_main(args)
     if args.confusion:
