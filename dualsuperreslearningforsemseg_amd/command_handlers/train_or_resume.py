@@ -107,7 +107,11 @@ class TrainStep:
     or `ohem` (ValueError).  With more than one rank each rank uses the sums of its own batch.  Fixed for the life of the step, like the others.
 
     The weight average (`flat.enable_ema`) needs nothing here: the optimiser pass of the step updates it, eagerly and in the captured
-    graph alike, and whether it is enabled is part of the graph key.  A training iteration inside `flat.ema_weights()` raises DsrlHipError."""
+    graph alike, and whether it is enabled is part of the graph key.  A training iteration inside `flat.ema_weights()` raises DsrlHipError.
+
+    Gradient-norm clipping (`flat.enable_grad_clip`) needs nothing here either: the optimiser pass forms the norm and folds the
+    coefficient into the device hyper-parameters, eagerly and in the captured graph alike; whether it is enabled is part of the graph key.  It does
+    not go with the two-graph schedule (DSRL_GRAPH_SPLIT): a training iteration then raises DsrlHipError."""
 
     GRAPH_WARMUP = HF.GRAPH_WARMUP          # eager iterations per batch shape before the capture
 
@@ -263,6 +267,7 @@ class TrainStep:
     def _graph_key(self, input_image, input_org, target):
         return (tuple(input_image.shape), tuple(input_org.shape), tuple(target.shape), HF.get_conv_precision(), HF.overlap_wgrad,
                 self.flat.e_flat is not None,           # "EMA enabled": a step captured without the weight average has no launch that updates it
+                self.flat.clip_rec is not None,         # "clip enabled": a step captured without it has neither the norm launches nor hyper_eff
                 self.focal_gamma, self.label_smoothing, self.dice, self.ohem)
 
     def _capture(self, key, input_image, input_org, target, hp):
@@ -364,6 +369,8 @@ class TrainStep:
         hp = (lr, momentum, weight_decay)
         if do_train and self.flat.ema_swapped:
             raise HF.DsrlHipError('a training step inside FlatParams.ema_weights(): the parameters are the averaged ones')
+        if do_train and self.split and self.flat.clip_rec is not None:
+            raise HF.DsrlHipError('gradient clipping (grad_clip) is not supported in the two-graph schedule: unset DSRL_GRAPH_SPLIT')
         if do_train and self.use_graph:
             if self.rng is None:
                 self.rng = HF.DeviceRng(self.flat.device)
@@ -483,6 +490,12 @@ def check_ema(dataset):
     return HF.ema_value(dataset.get('ema'))
 
 
+def check_grad_clip(dataset):
+    """dataset['grad_clip']: absent, None or False -> None (off); a number > 0 (inf: monitor only) or {'max_norm': such a number} -> that float,
+    as HF.grad_clip_value; ValueError otherwise.  Touches no device."""
+    return HF.grad_clip_value(dataset.get('grad_clip'))
+
+
 def checkpoint_dict(have, ema_state_dict=None):
     """What a checkpoint file holds: every key of settings.VARIABLES_IN_CHECKPOINT out of `have` and nothing else - the reference's layout -, plus
     'ema_state_dict' (FlatParams.ema_state_dict()) in a run with dataset['ema'].  'model_state_dict' stays the live weights: a resume needs them."""
@@ -507,6 +520,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     ohem = check_ohem(dataset)
     dice = check_dice(dataset)
     ema = check_ema(dataset)
+    grad_clip = check_grad_clip(dataset)
     input_size = other_args.get('model_input_size', settings.MODEL_INPUT_SIZE)
     if distributed:
         t.manual_seed(settings.RANDOM_SEED)                                                # identical init on all ranks, :31
@@ -557,6 +571,10 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
                 flat.load_ema_state_dict(other_args['ema_state_dict'])
             else:
                 warnings.warn("resuming with dataset['ema'] from a checkpoint without 'ema_state_dict': the average starts from the loaded weights at 0 updates")
+    if grad_clip is not None:
+        # dataset['grad_clip']: torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) inside the optimiser pass, on the device;
+        # every epoch record carries the gradient-norm figures of its training iterations.  inf reports the figures and changes nothing else.
+        flat.enable_grad_clip(grad_clip)
     factory = dataset.get('loader_factory')
     own_loader = factory is None
     if own_loader:
@@ -609,6 +627,11 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
             rec = {'epoch': epoch, 'lr': lr, 'train': means}
             if dice is not None:
                 rec['train_ce_includes_dice'] = list(dice)      # (weight, smooth): means[0] is CE + weight * L_dice; the validation figures are the CE alone
+            if grad_clip is not None:
+                gc = flat.grad_clip_stats(reset=True)           # one device read per epoch: the norms of this epoch's training iterations
+                rec['grad_norm_mean'], rec['grad_norm_max'] = gc['norm_mean'], gc['norm_max']
+                rec['grad_clipped_fraction'] = gc['clipped'] / gc['steps'] if gc['steps'] else 0.0
+                rec['grad_nonfinite_steps'] = gc['nonfinite']
             stop = False
             if is_master_rank:
                 if checkpoint_history > 0 and epoch % checkpoint_interval == 0 and experiment_id:                 # :264

@@ -219,6 +219,23 @@ struct EmaRecord {
 // Every EMA kernel - fused into an SGD launch or not - goes through this one function, so that the fused and the unfused paths round alike.
 __device__ __forceinline__ float ema_elem(float e, float p_new, float omd) { return fmaf(omd, p_new - e, e); }
 
+// ---------------------------------------------------------------- gradient-norm clipping (gradclip.hip)
+// The clip record in device memory (64 bytes, 16-byte aligned).  dsrl_grad_clip_finish reads max_norm when it runs - a new value needs no re-capture -
+// and writes everything else: the figures of the step it finished, then the running fields (since the record was made or last reset by the host).
+struct GradClipRecord {
+    double sumsq;       // S of the last step: the sum of squares of the gradient arena, before grad_scale
+    double norm_sum;    // running: sum of the finite norms
+    float norm;         // last step: grad_scale * sqrt(S), the norm of the rank-averaged gradient
+    float coef;         // last step: min(1, max_norm / (norm + 1e-6)); NaN for a NaN norm
+    float max_norm;     // the threshold; +inf monitors only
+    float norm_max;     // running: largest finite norm
+    uint32_t steps;     // running: finishes
+    uint32_t clipped;   // running: finishes with a finite norm and coef < 1
+    uint32_t nonfinite; // running: finishes with a NaN or infinite norm (left out of norm_sum and norm_max)
+    uint32_t pad[5];
+};
+static_assert(sizeof(GradClipRecord) == 64, "GradClipRecord is 64 bytes");
+
 // ---------------------------------------------------------------- calibration record and confidence (calibration.hip)
 // Confidence of a pixel: the probability of the class the kernel reports (first maximum), fp32, from values the producer already has:
 //     one softmax (dsrl_calibration_from_logits, the single-view tail):  1 / s, s = sum_c exp_nonpos(v_c - m) with c ascending, m the fmaxf chain from v_0

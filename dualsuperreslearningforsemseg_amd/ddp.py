@@ -104,6 +104,9 @@ class FlatParams:
         # the weight average (enable_ema): arenas laid out as p_flat / b_flat, the 16-byte device record, and whether ema_weights() has them swapped in
         self.e_flat = self.eb_flat = self.ema_rec = self.ema_config = None
         self.ema_swapped = False
+        # gradient-norm clipping (enable_grad_clip): the 64-byte device record, the tile sums at the start of their workspace, the hyper-parameters the
+        # optimiser launches read once the coefficient is folded into grad_scale
+        self.clip_rec = self.clip_ws = self.clip_tiles = self.hyper_eff = None
         if self.world > 1 and self.device.type == 'cuda' and HF.knob('DSRL_BN_FUSED_BIG', None) is None:
             # RCCL kernels hold CUs while they wait for their peers: a 256-block fused-BN launch (one block on EVERY CU) could stall behind
             # them, the 128-block variant cannot
@@ -335,7 +338,10 @@ class FlatParams:
         SGD kernel of range k runs on the compute stream as soon as ITS all-reduce is done - under the all-reduces of ranges k+1 .. (round 5; the
         single 239.5 MB call of round 4 exposed the whole optimiser pass behind the exchange).  Only element-wise kernels touch the ranges, so they
         need no parameter alignment beyond 16 bytes; no barrier kernel is co-resident with RCCL here - those are all inside the graph that has
-        finished.  Bit-identical to reduce_all() + one SGD launch (same element-wise arithmetic).  Returns the chunk ranges (tests)."""
+        finished.  Bit-identical to reduce_all() + one SGD launch (same element-wise arithmetic).  Returns the chunk ranges (tests).
+        With gradient clipping enabled (enable_grad_clip) the update of EVERY range needs the norm of the WHOLE arena: what runs under the all-reduces
+        of ranges k+1 .. is then the sum-of-squares pass of range k (ranges start at multiples of 1024, the tile of dsrl_grad_sumsq), and the SGD
+        launches follow the last all-reduce and the finish - they no longer overlap the exchange.  Still bit-identical to the single-range step."""
         self._refuse_swapped('reduce_chunked_and_step')
         n = max(1, HF.knob('DSRL_REDUCE_CHUNKS', 4) if nchunks is None else int(nchunks))
         per = _align(-(-self.numel // n), 1024)
@@ -364,6 +370,9 @@ class FlatParams:
     def _update(self, ranges, works, hyper, hp):
         """SGD over `ranges` of the arena, range k as soon as works[k] (its all-reduce, if any) is done; then the step is over."""
         self._refuse_swapped('the optimiser step')
+        if self.clip_rec is not None:
+            hyper = self._clip(ranges, works, hyper, hp)        # waits for every range; the launches below read grad_scale * coef
+            works = []
         fold = hyper is not None and self._fold_amax()
         if fold:
             self.filters.amax.zero_()
@@ -429,6 +438,62 @@ class FlatParams:
         counters do not see - a collective on the arena, a raw-pointer kernel such as the swap of ema_weights(), `.data` writes - calls this, and
         the next step measures the filters again.  External code that writes parameters through `.data` must call it too."""
         self._amax_key = None
+
+    # ------------------------------------------------------------------ gradient-norm clipping (DESIGN.md 6.1.13)
+    def enable_grad_clip(self, max_norm):
+        """torch.nn.utils.clip_grad_norm_(parameters, max_norm) inside every optimiser pass from here on, on the device: a sum-of-squares pass over
+        the gradient arena, one finish that forms coef = min(1, max_norm / (norm + 1e-6)) from the norm of the rank-averaged gradient and writes
+        {lr, momentum, weight_decay, coef / world} to `hyper_eff`, and the usual SGD launches reading that.  No host read or write per step, so a
+        captured step clips on every replay; the record holds max_norm (write a new value into it and the next step uses it) and the figures
+        grad_clip_stats() reports.  max_norm = inf monitors only: the step is bit-identical to one without clipping.  A second call raises."""
+        if self.clip_rec is not None:
+            raise HF.DsrlHipError('enable_grad_clip: gradient clipping of this FlatParams is already enabled')
+        v = HF.grad_clip_value(max_norm)
+        if v is None:
+            raise ValueError(f'enable_grad_clip: max_norm = {max_norm!r}')
+        self.clip_ws = HF.grad_clip_workspace(self.numel, self.device)
+        self.clip_tiles = self.clip_ws[:-(-self.numel // HF.GRAD_CLIP_TILE)]
+        self.hyper_eff = torch.zeros(4, device=self.device, dtype=torch.float32)
+        self.clip_rec = HF.grad_clip_record(v, self.device)
+
+    def set_grad_clip_max_norm(self, max_norm):
+        """A new threshold, written into the device record behind what the stream holds: captured steps follow it without a re-capture."""
+        self._need_clip('set_grad_clip_max_norm')
+        v = HF.grad_clip_value(max_norm)
+        if v is None:
+            raise ValueError(f'set_grad_clip_max_norm: max_norm = {max_norm!r}')
+        self.clip_rec[6:7].copy_(HF.grad_clip_record(v, 'cpu')[6:7])
+
+    def grad_clip_stats(self, reset=False):
+        """One device read (synchronises): {'norm_mean', 'norm_max' over the steps with a finite norm since the last reset (NaN / 0 when there
+        was none), 'norm', 'coef' of the last step, 'steps', 'clipped', 'nonfinite', 'max_norm'}.  reset=True starts the running figures again
+        (max_norm stays)."""
+        self._need_clip('grad_clip_stats')
+        r = HF.grad_clip_record_read(self.clip_rec)
+        finite = r['steps'] - r['nonfinite']
+        out = {'norm_mean': r['norm_sum'] / finite if finite else float('nan'), 'norm_max': r['norm_max'], 'norm': r['norm'], 'coef': r['coef'],
+               'steps': r['steps'], 'clipped': r['clipped'], 'nonfinite': r['nonfinite'], 'max_norm': r['max_norm']}
+        if reset:
+            self.clip_rec[2:4].zero_()          # norm_sum
+            self.clip_rec[7:11].zero_()         # norm_max, steps, clipped, nonfinite; max_norm and the last step's figures stay
+        return out
+
+    def _need_clip(self, what):
+        if self.clip_rec is None:
+            raise HF.DsrlHipError(f'{what}: gradient clipping is not enabled (enable_grad_clip)')
+
+    def _clip(self, ranges, works, hyper, hp):
+        """The clipping part of an optimiser pass: the tile sums of range k as soon as works[k] (its all-reduce, if any) is done - under the
+        all-reduces of ranges k+1 .. -, then one finish.  -> hyper_eff, the device hyper-parameters of every SGD launch of the pass."""
+        for i, (a, b) in enumerate(ranges):
+            if works:
+                works[i].wait()
+            HF.grad_sumsq_(self.g_flat[a:b], a, self.clip_tiles)
+        if hyper is not None:
+            HF.grad_clip_finish_(self.clip_tiles, self.clip_rec, self.hyper_eff, hyper=hyper)
+        else:
+            HF.grad_clip_finish_(self.clip_tiles, self.clip_rec, self.hyper_eff, hp=(hp[0], hp[1], hp[2], 1.0 / self.world))
+        return self.hyper_eff
 
     # ------------------------------------------------------------------ exponential moving average of the weights (DESIGN.md 6.1.6)
     def enable_ema(self, decay, warmup=True):

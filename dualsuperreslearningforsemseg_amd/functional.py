@@ -2215,6 +2215,87 @@ def arena_swap_(a, b):
     call('dsrl_arena_swap', a.data_ptr(), b.data_ptr(), a.numel(), _stream())
 
 
+# ------------------------------------------------------------------------------------------------ gradient-norm clipping
+GRAD_CLIP_TILE = 1024                   # floats per tile of dsrl_grad_sumsq, anchored at the arena's first float
+GRAD_CLIP_RECORD_WORDS = 16             # include/dsrl_hip.h: the 64-byte clip record
+
+
+def grad_clip_value(x):
+    """The clipping threshold as a float, or None when clipping is off.  None / False: off; a number > 0 (inf: monitor only) or a mapping
+    {'max_norm': such a number}: that float.  ValueError on anything else - True, 0, a negative number, a NaN, an unknown key.  Touches no device."""
+    if x is None:
+        return None
+    if isinstance(x, (bool, np.bool_)):
+        if x:
+            raise ValueError('grad_clip = True: expected the threshold itself, a number > 0')
+        return None
+    if isinstance(x, dict):
+        if set(x) != {'max_norm'}:
+            raise ValueError(f"grad_clip = {x!r}: expected a mapping with the key 'max_norm'")
+        x = x['max_norm']
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+        raise ValueError(f'grad_clip: max_norm = {x!r}: expected a number > 0')
+    v = float(x)
+    if not (v > 0.0) or not (float(np.float32(v)) > 0.0):          # (a NaN fails the comparison; the kernel takes it as fp32)
+        raise ValueError(f'grad_clip: max_norm = {x!r}: expected a number > 0')
+    return v
+
+
+def grad_clip_record(max_norm, device):
+    """A new clip record (include/dsrl_hip.h) as a 16-word int32 tensor on `device`: max_norm set, everything else zero."""
+    words = np.zeros(GRAD_CLIP_RECORD_WORDS, dtype=np.int32)
+    words[6:7] = np.array([max_norm], dtype=np.float32).view(np.int32)
+    return torch.from_numpy(words).to(device)
+
+
+def grad_clip_record_read(rec):
+    """The record's fields on the host (one synchronising read)."""
+    words = rec.detach().cpu().numpy()
+    d = words[:4].view(np.float64)
+    f = words[4:8].view(np.float32)
+    u = words[8:11].view(np.uint32)
+    return {'sumsq': float(d[0]), 'norm_sum': float(d[1]), 'norm': float(f[0]), 'coef': float(f[1]), 'max_norm': float(f[2]), 'norm_max': float(f[3]),
+            'steps': int(u[0]), 'clipped': int(u[1]), 'nonfinite': int(u[2])}
+
+
+def grad_clip_workspace(n, device):
+    """The float64 workspace of an n-float arena: its ceil(n / 1024) tile sums first, the scratch of the finish behind them."""
+    return torch.empty(int(query('dsrl_grad_clip_workspace_bytes', int(n))) // 8, dtype=torch.float64, device=device)
+
+
+def _room_behind(t):
+    return t.untyped_storage().nbytes() - t.storage_offset() * t.element_size()
+
+
+def grad_sumsq_(g, first, tiles):
+    """Sums of squares of the 1024-float tiles of `g`, a range of a flat fp32 arena that starts at the arena's float `first` (a multiple of 1024),
+    into tiles[first / 1024 ...] (float64, indexed from the arena's first tile).  Only the tiles of the range are written."""
+    _need_gpu(g, tiles)
+    first = int(first)
+    if g.dtype != torch.float32 or tiles.dtype != torch.float64 or not (g.is_contiguous() and tiles.is_contiguous()):
+        raise DsrlHipError('grad_sumsq: a contiguous fp32 range and a contiguous float64 tile array expected')
+    if first >= 0 and first // GRAD_CLIP_TILE + -(-g.numel() // GRAD_CLIP_TILE) > tiles.numel():
+        raise DsrlHipError(f'grad_sumsq: {g.numel()} floats from {first} need more than the {tiles.numel()} tiles given')
+    call('dsrl_grad_sumsq', g.data_ptr() - 4 * first, first, g.numel(), tiles.data_ptr(), _stream())
+
+
+def grad_clip_finish_(tiles, record, hyper_out, hyper=None, hp=None):
+    """Behind the grad_sumsq_ launches of a step: S = the sum of `tiles` (the first tiles.numel() doubles of a grad_clip_workspace), the clip
+    coefficient from it and record['max_norm'], hyper_out = {lr, momentum, weight_decay, grad_scale * coef} and the record's figures.  The four
+    hyper-parameters come from the device tensor `hyper`, or from the host values `hp` = (lr, momentum, weight_decay, grad_scale)."""
+    _need_gpu(tiles, record, hyper_out, hyper)
+    if (hyper is None) == (hp is None):
+        raise DsrlHipError('grad_clip_finish: exactly one of hyper (device) and hp (host values) expected')
+    if tiles.dtype != torch.float64 or not tiles.is_contiguous() or _room_behind(tiles) < int(cquery('dsrl_grad_clip_workspace_bytes', tiles.numel() * GRAD_CLIP_TILE)):
+        raise DsrlHipError('grad_clip_finish: `tiles` must be the tile sums at the start of a grad_clip_workspace')
+    if record.numel() * record.element_size() != 4 * GRAD_CLIP_RECORD_WORDS or hyper_out.dtype != torch.float32 or hyper_out.numel() != 4 or \
+            (hyper is not None and (hyper.dtype != torch.float32 or hyper.numel() != 4 or hyper.data_ptr() == hyper_out.data_ptr())):
+        raise DsrlHipError('grad_clip_finish: a 64-byte record and 4-float hyper-parameter tensors (two different ones) expected')
+    h = (0.0, 0.0, 0.0, 0.0) if hp is None else tuple(float(v) for v in hp)
+    call('dsrl_grad_clip_finish', tiles.data_ptr(), tiles.numel(), None if hyper is None else hyper.data_ptr(), h[0], h[1], h[2], h[3], record.data_ptr(),
+         hyper_out.data_ptr(), _stream())
+
+
 class DeviceRng:
     """Device-resident twin of the host dropout key (begin_forward): three 64-bit words {key, step, base}.  While bound, every
     dropout-bearing kernel of the device reads `key` when it runs and advance() enqueues the per-step derivation, so that a step

@@ -703,6 +703,26 @@ int dsrl_ema_update(float* ema, const float* p, int64_t n, const void* ema_recor
 int dsrl_ema_advance(void* ema_record, dsrl_stream_t stream);
 /* exchanges n floats of two disjoint 16-byte aligned arenas in place, as bit patterns (NaN payloads, infinities, -0 and denormals survive) */
 int dsrl_arena_swap(float* a, float* b, int64_t n, dsrl_stream_t stream);
+/* Gradient-norm clipping on the gradient arena: torch.nn.utils.clip_grad_norm_(parameters, max_norm) with the coefficient folded into the
+ * optimiser's grad_scale, everything on the device.
+ * dsrl_grad_sumsq: one pass over g[first, first + n) of the arena `g`.  The arena is cut into tiles of 1024 floats anchored at g[0];
+ * tiles[first / 1024 + k] receives the sum of squares of tile k of the range, in double (a float square is exact there), in an order fixed inside
+ * the tile.  first must be a multiple of 1024 and g 16-byte aligned (DSRL_E_BADARG otherwise, nothing is written); the last tile of a range may be
+ * short.  No atomics and no zero fill: only the tiles of the range are written, each once, and they do not depend on how the arena is cut into calls.
+ * dsrl_grad_clip_workspace_bytes(n): the bytes of the tile array of an n-float arena plus the scratch the finish keeps BEHIND it.
+ * dsrl_grad_clip_finish: `tiles` is the start of such a workspace and ntiles = ceil(n / 1024).  S = the sum of the tiles in a fixed order (two
+ * launches).  {lr, momentum, weight_decay, gs} come from the four device floats `hyper_in`, or from the host arguments when hyper_in is null.  In double:
+ * norm = gs sqrt(S), coef = min(1, max_norm / (norm + 1e-6)) - torch's formula; a NaN norm gives a NaN coefficient, an infinite one 0.
+ * hyper_out (device, 4 floats, may not alias hyper_in) = {lr, momentum, weight_decay, (float)(gs coef)}, bit-equal to gs when coef == 1: the
+ * `hyper` of the dsrl_sgd_step_dev* launches that follow.
+ * record: 64 bytes of device memory, 16-byte aligned: {double sumsq, double norm_sum, float norm, float coef, float max_norm, float norm_max,
+ * uint32 steps, uint32 clipped, uint32 nonfinite, 20 bytes of padding}.  max_norm is READ when the finish runs (+inf: monitor only), so a captured
+ * step follows a new threshold without being re-captured; sumsq, norm and coef are those of this call; steps += 1; a finite norm is added to
+ * norm_sum, raises norm_max and counts in `clipped` when coef < 1; a NaN or infinite norm counts in `nonfinite` alone. */
+int dsrl_grad_sumsq(const float* g, int64_t first, int64_t n, double* tiles, dsrl_stream_t stream);
+size_t dsrl_grad_clip_workspace_bytes(int64_t n);
+int dsrl_grad_clip_finish(const double* tiles, int64_t ntiles, const float* hyper_in /*device, 4 floats, or null*/, float lr, float momentum,
+                          float weight_decay, float grad_scale, void* record, float* hyper_out /*device, 4 floats*/, dsrl_stream_t stream);
 /* flag[0] |= 1 if any element is NaN (the reference's per-output NaN asserts folded into one readback) */
 int dsrl_nan_check(const float* x, int64_t n, int* flag, dsrl_stream_t stream);
 
