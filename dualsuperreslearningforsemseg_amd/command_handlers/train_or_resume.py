@@ -106,6 +106,14 @@ class TrainStep:
     selection stay comparable between runs with and without it.  It goes with `class_weights` and not with `focal_gamma` > 0, `label_smoothing` > 0
     or `ohem` (ValueError).  With more than one rank each rank uses the sums of its own batch.  Fixed for the life of the step, like the others.
 
+    `lovasz` (HF.lovasz_value: None / False / 0 off, True = (1.0, 1024), a weight, (weight, bins) or a mapping): the quantised Lovasz-Softmax term
+    weight * L_lovasz is added to the CE term of the TRAINING iterations (HF.lovasz_softmax_loss) - the error histograms are
+    formed on the device from the batch of the iteration (classes = 'present' over the batch), the term's gradient joins d(CE)/d(logits) inside the
+    ConvTranspose backward, fused and unfused losses, eager and captured.  The CE figure a training iteration reports is then CE + weight * L_lovasz.
+    `do_train=False` keeps the configured CE, so validation losses and checkpoint selection are unchanged.  It goes with `class_weights` and not
+    with `focal_gamma` > 0, `label_smoothing` > 0, `ohem` or `dice` (ValueError).  With more than one rank each rank uses the histograms of its own
+    batch.  Fixed for the life of the step, like the others.
+
     The weight average (`flat.enable_ema`) needs nothing here: the optimiser pass of the step updates it, eagerly and in the captured
     graph alike, and whether it is enabled is part of the graph key.  A training iteration inside `flat.ema_weights()` raises DsrlHipError.
 
@@ -116,7 +124,7 @@ class TrainStep:
     GRAPH_WARMUP = HF.GRAPH_WARMUP          # eager iterations per batch shape before the capture
 
     def __init__(self, model, flat, stage, w1, w2, ignore_index, graph=None, class_weights=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None,
-                 dice=None):
+                 dice=None, lovasz=None):
         self.model, self.flat, self.stage, self.w1, self.w2, self.ignore = model, flat, stage, w1, w2, ignore_index
         self.focal_gamma = HF.focal_gamma_value(focal_gamma)                                                          # ValueError on a bad gamma
         self.label_smoothing = HF.label_smoothing_value(label_smoothing)                                              # ValueError on a bad eps
@@ -124,6 +132,7 @@ class TrainStep:
             raise ValueError(f'label_smoothing = {label_smoothing!r} together with focal_gamma = {focal_gamma!r}: the combination is not defined')
         self.ohem = HF._ohem_args(ohem, self.focal_gamma, self.label_smoothing, ignore_index)                        # ValueError on a bad value or combination
         self.dice = HF._dice_args(dice, self.focal_gamma, self.label_smoothing, self.ohem)                           # ValueError on a bad value or combination
+        self.lovasz = HF._lovasz_args(lovasz, self.focal_gamma, self.label_smoothing, self.ohem, self.dice)          # ValueError on a bad value or combination
         self.class_weight = None if class_weights is None else HF.class_weight_table(class_weights, flat.device)     # ValueError on bad weights
         self.fa = FALoss()
         dev = flat.device
@@ -154,7 +163,7 @@ class TrainStep:
     def losses(self, outs, input_org, target, do_train=True):
         SSSR, SISR, SSSR_ft, SISR_ft = outs
         ce = HF.cross_entropy(SSSR, target, self.ignore, self.class_weight, self.focal_gamma, self.label_smoothing,      # train_or_resume.py:435
-                              self.ohem if do_train else None, self.dice if do_train else None)
+                              self.ohem if do_train else None, self.dice if do_train else None, self.lovasz if do_train else None)
         ms = self.w1 * HF.mse_loss(SISR, input_org) if self.stage > 1 else self.zero       # :436
         fa = self.w2 * self.fa(SSSR_ft, SISR_ft) if self.stage > 2 else self.zero          # :437
         return ce, ms, fa, ce + ms + fa                                                    # :438
@@ -177,20 +186,21 @@ class TrainStep:
         self.flag.zero_()
         ohem = self.ohem if do_train else None    # validation keeps the configured CE without mining
         dice = self.dice if do_train else None    # and without the Dice term
+        lovasz = self.lovasz if do_train else None      # or the Lovasz-Softmax term
         cuts = None
         try:
             with t.set_grad_enabled(do_train):
                 if self.fused_losses and do_train:
                     # the layer that produces the logits evaluates the CE value in its own forward kernel (HF.logits_target), :435
                     with HF.logits_target(target if target.dtype == t.uint8 and target.is_contiguous() else None, self.ignore, self.flag,
-                                          self.class_weight, self.focal_gamma, self.label_smoothing, ohem, dice):
+                                          self.class_weight, self.focal_gamma, self.label_smoothing, ohem, dice, lovasz):
                         outs = self.model(input_image)                                     # :420
                 else:
                     outs = self.model(input_image)                                         # :420
                 if self.fused_losses:
                     # CE + MSE + FA, their gradients, the NaN asserts (:426-433) and the loss mix (:435-438) in one launch set
                     vals = HF.fused_losses(outs, target, input_org, self.ignore, self.w1, self.w2, self.stage, self.flag, self.fa.subsample_factor,
-                                           self.class_weight, self.focal_gamma, self.label_smoothing, ohem, dice)
+                                           self.class_weight, self.focal_gamma, self.label_smoothing, ohem, dice, lovasz)
                     total = vals[3]
                 else:
                     HF.nan_check_(self.flag, *[o for o in outs if o.is_cuda])              # the four NaN asserts, :426-433
@@ -268,7 +278,7 @@ class TrainStep:
         return (tuple(input_image.shape), tuple(input_org.shape), tuple(target.shape), HF.get_conv_precision(), HF.overlap_wgrad,
                 self.flat.e_flat is not None,           # "EMA enabled": a step captured without the weight average has no launch that updates it
                 self.flat.clip_rec is not None,         # "clip enabled": a step captured without it has neither the norm launches nor hyper_eff
-                self.focal_gamma, self.label_smoothing, self.dice, self.ohem)
+                self.focal_gamma, self.label_smoothing, self.dice, self.lovasz, self.ohem)
 
     def _capture(self, key, input_image, input_org, target, hp):
         """-> the captured step, or None: a capture that fails (a runtime that refuses something inside it) must not end the training run.  This
@@ -484,6 +494,13 @@ def check_dice(dataset):
     return HF._dice_args(dataset.get('dice'), check_focal_gamma(dataset), check_label_smoothing(dataset), check_ohem(dataset))
 
 
+def check_lovasz(dataset):
+    """dataset['lovasz']: absent, None, False or 0 -> None (off); True, a weight > 0, a pair (weight, bins) or a mapping with the keys 'weight' and
+    'bins' -> (weight, bins), as HF.lovasz_value; ValueError otherwise, and on a value together with dataset['focal_gamma'] > 0,
+    dataset['label_smoothing'] > 0, dataset['ohem'] or dataset['dice'] (scoped out).  Touches no device."""
+    return HF._lovasz_args(dataset.get('lovasz'), check_focal_gamma(dataset), check_label_smoothing(dataset), check_ohem(dataset), check_dice(dataset))
+
+
 def check_ema(dataset):
     """dataset['ema']: absent, None or False -> None (off); True, a decay in (0, 1), a pair (decay, warmup) or a mapping with these keys ->
     (decay, warmup), as HF.ema_value; ValueError otherwise.  Touches no device."""
@@ -519,6 +536,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     label_smoothing = check_label_smoothing(dataset)
     ohem = check_ohem(dataset)
     dice = check_dice(dataset)
+    lovasz = check_lovasz(dataset)
     ema = check_ema(dataset)
     grad_clip = check_grad_clip(dataset)
     input_size = other_args.get('model_input_size', settings.MODEL_INPUT_SIZE)
@@ -591,7 +609,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
         lut = DeviceBatchPreparation(ds.LABEL_MAPPING_DICT, ds.MEAN, ds.STD, input_size, ds.IGNORE_CLASS_LABEL).lut_host
         class_weights = enet_weights(class_counts(cache_dir_of(dataset), 'train', lut, device_obj)[:ds.NUM_CLASSES])
     step = TrainStep(model, flat, stage, w1, w2, ds.IGNORE_CLASS_LABEL, class_weights=class_weights, focal_gamma=focal_gamma,
-                     label_smoothing=label_smoothing, ohem=ohem, dice=dice)
+                     label_smoothing=label_smoothing, ohem=ohem, dice=dice, lovasz=lovasz)
     train_loader = factory('train', batch_size, device_obj, rank, world)
     val_loader = factory('val', batch_size, device_obj, rank, world) if is_master_rank else None
 
@@ -627,6 +645,8 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
             rec = {'epoch': epoch, 'lr': lr, 'train': means}
             if dice is not None:
                 rec['train_ce_includes_dice'] = list(dice)      # (weight, smooth): means[0] is CE + weight * L_dice; the validation figures are the CE alone
+            if lovasz is not None:
+                rec['train_ce_includes_lovasz'] = True          # means[0] is CE + weight * L_lovasz; the validation figures are the CE alone
             if grad_clip is not None:
                 gc = flat.grad_clip_stats(reset=True)           # one device read per epoch: the norms of this epoch's training iterations
                 rec['grad_norm_mean'], rec['grad_norm_max'] = gc['norm_mean'], gc['norm_max']

@@ -41,7 +41,7 @@ int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float*
 // weighted() / focal() / smoothed(), and these hold the one normalisation rule: gamma == 0 or eps == 0 IS the weighted form, in every respect
 // (kernels, messages).  Everything below the entry points takes this value and decides by kind.
 struct CeVariant {
-    enum Kind { kPlain, kWeighted, kFocal, kSmoothed, kDice };
+    enum Kind { kPlain, kWeighted, kFocal, kSmoothed, kDice, kLovasz };
     const float* weights = nullptr;     // the 256-float class-weight table; the plain form has none
     float gamma = 0.f;                  // > 0: kFocal
     float eps = 0.f;                    // > 0: kSmoothed
@@ -50,11 +50,14 @@ struct CeVariant {
     static CeVariant weighted(const float* w) { return CeVariant{w, 0.f, 0.f, kWeighted}; }
     static CeVariant focal(const float* w, float gamma) { return gamma == 0.f ? weighted(w) : CeVariant{w, gamma, 0.f, kFocal}; }
     static CeVariant smoothed(const float* w, float eps) { return eps == 0.f ? weighted(w) : CeVariant{w, 0.f, eps, kSmoothed}; }
+    const float* lovasz = nullptr;      // kLovasz: the record of dsrl_lovasz_fwd (dsrl_convt2x2_bwd_ce_l only: the weighted row plus the Lovasz row)
+    int bins = 0;                       // kLovasz: K, the levels of that record
     static CeVariant diced(const float* w, const float* record) { return CeVariant{w, 0.f, 0.f, kDice, record}; }
+    static CeVariant lovasz_of(const float* w, const float* record, int bins) { return CeVariant{w, 0.f, 0.f, kLovasz, nullptr, record, bins}; }
     bool plain() const { return kind == kPlain; }
     bool table_ok() const { return plain() || weights != nullptr; }         // part of every entry point's argument check
     const char* suffix() const {        // of the entry point, for its messages
-        return plain() ? "" : kind == kWeighted ? "_w" : kind == kFocal ? "_f" : kind == kSmoothed ? "_s" : "_d";
+        return plain() ? "" : kind == kWeighted ? "_w" : kind == kFocal ? "_f" : kind == kSmoothed ? "_s" : kind == kDice ? "_d" : "_l";
     }
 };
 // losses.hip, for the ConvTranspose forms in spatial.hip: the pre-pass of every kind but plain (D = sum n_c w_c into d_out, through `ws` of
@@ -206,6 +209,45 @@ __device__ __forceinline__ void dice_pixel(const float* e, int C, float s, int t
 __device__ __forceinline__ float dice_grad(float e, float inv_s, float b_c, bool hit, float a_t, float dot, bool live) {
     return live ? (e * inv_s) * ((b_c + (hit ? a_t : 0.f)) - dot) : 0.f;
 }
+
+// ---------------------------------------------------------------- Lovasz-Softmax loss term (lovasz.hip), the gradient row of one pixel
+// The quantised form: the error err_c = |[c == t] - p_c| of a live pixel falls in level b = lovasz_bin(err_c, K) of K, and the loss and a valid
+// subgradient follow from the integer histograms of the levels (dsrl_hip.h).  The record dsrl_lovasz_fwd leaves in device memory:
+//     {lambda L, |Present|, 0, 0, gf[C][K], gb[C][K]}      gf = -(lambda / |Present|) wf,  gb = +(lambda / |Present|) wb,  zeros for an absent class
+//     d(lambda L) / d v_k = live p_k (g_k - sum_j p_j g_j),   g_j = (j == t ? gf : gb)[j][b_j],   p_j = e_j (1 / s)          (j ascending)
+// lovasz_bin is the ONE function that turns an error into a level: the histogram pass and every gradient path call it on the same fp32 p, so a
+// pixel looks up the level it was counted in.  It returns an index in [0, K) for ANY bit pattern: x = err K; fmaxf(x, 0) is 0 for a NaN (maxnum
+// returns the operand that is a number) and for every negative value or -inf; fminf(., K - 1) bounds +inf and everything above; the conversion of
+// a number in [0, K - 1] is exact arithmetic; and the final & (K - 1) (K is a power of two) holds the range whatever the three steps before it gave.
+// lovasz_coef is g_j of one class (one gather from the record, global memory / L2); lovasz_pixel forms 1 / s and the sum over the classes in
+// ascending j, and with CT > 0 (class count at compile time, e[] in registers) keeps the C coefficients in g[] so that the row needs no second
+// gather; CT == 0: `C` at run time, g unused, the caller gathers again through lovasz_coef.  A pixel that is not live reads nothing.  The unfused
+// kernel (lovasz.hip) and the ConvTranspose backward (convt_dma.hip) both go through these functions, so that they round alike.
+constexpr int kLovaszHeadFloats = 4, kLovaszMaxC = 60, kLovaszMinBins = 16, kLovaszMaxBins = 4096;
+__host__ __device__ __forceinline__ int lovasz_bin(float err, int K) {
+    const float x = fminf(fmaxf(err * (float)K, 0.f), (float)(K - 1));
+    return (int)x & (K - 1);
+}
+__device__ __forceinline__ float lovasz_err(float p, bool hit) { return hit ? fabsf(1.f - p) : fabsf(p); }
+__device__ __forceinline__ float lovasz_coef(float p, bool hit, int c, const float* __restrict__ gf, const float* __restrict__ gb, int K) {
+    return (hit ? gf : gb)[c * K + lovasz_bin(lovasz_err(p, hit), K)];
+}
+template <int CT>
+__device__ __forceinline__ void lovasz_pixel(const float* e, int C, float s, int tg, bool live, const float* __restrict__ gf, const float* __restrict__ gb,
+                                             int K, float& inv_s, float* g, float& dot) {
+    const int n = CT > 0 ? CT : C;
+    inv_s = 1.f / s;
+    float d = 0.f;
+#pragma unroll
+    for (int c = 0; c < n; ++c) {
+        const float p = e[c] * inv_s;
+        const float gc = live ? lovasz_coef(p, c == tg, c, gf, gb, K) : 0.f;
+        if (CT > 0) g[c] = gc;
+        d += p * gc;
+    }
+    dot = d;
+}
+__device__ __forceinline__ float lovasz_grad(float e, float inv_s, float g_c, float dot, bool live) { return live ? (e * inv_s) * (g_c - dot) : 0.f; }
 
 // ---------------------------------------------------------------- exponential moving average of the weights (ema.hip)
 // The EMA record in device memory (16 bytes, 16-byte aligned).  omd = 1 - d_t of the update ABOUT to run; dsrl_ema_advance rewrites it once per step.

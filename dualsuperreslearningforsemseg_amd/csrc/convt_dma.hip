@@ -47,6 +47,12 @@ struct ConvtCeArgs {
 struct ConvtCeDiceArgs : ConvtCeArgs {
     const float* dice;              // the record of dsrl_dice_fwd {lambda L_dice, |K|, a[0..CO), b[0..CO)}
 };
+// and of the LV build, for the same reason
+struct ConvtCeLovaszArgs : ConvtCeArgs {
+    const float* lovasz;            // the record of dsrl_lovasz_fwd {lambda L, |Present|, 0, 0, gf[CO][bins], gb[CO][bins]}
+    int bins;                       // K, a power of two in [16, 4096]
+};
+template <bool DC, bool LV> using ConvtCeArgsOf = std::conditional_t<DC, ConvtCeDiceArgs, std::conditional_t<LV, ConvtCeLovaszArgs, ConvtCeArgs>>;
 
 // CW = true (dsrl_convt2x2_bwd_ce_w): nn.CrossEntropyLoss(weight=).  ce.count points to D = sum n_c w_c and the only change is in transform(): the
 // per-pixel sc = wtab[target] * (1 / D) stands where `scale` stands, as in ce_fused_body<true> (losses.hip).  The 256-float table sits in LDS, already
@@ -62,14 +68,19 @@ struct ConvtCeDiceArgs : ConvtCeArgs {
 // record sit in LDS beside the weight table (in sub_s, which the label smoothing does not use here), the row is (weighted CE row) + (Dice row) with
 // the Dice row from dice_pixel / dice_grad (common.h) on the e_c in registers, and the transformer's g * w is added after that: the order and the
 // roundings of dsrl_ce_fused_w -> dsrl_dice_bwd(accumulate = 1) -> dsrl_pointwise_strided_bwd.
-template <int CI, int CO, bool CE, bool TW = false, bool CW = false, bool FL = false, bool SM = false, bool DC = false>
+// LV = true (dsrl_convt2x2_bwd_ce_l): the weighted cross entropy plus the Lovasz-Softmax term.  The record's tables (155 KB at
+// 19 classes and 1024 levels) do not fit LDS beside the ring: lovasz_pixel (common.h) gathers the 19 coefficients of a pixel from global memory /
+// L2 with the e_c in registers and keeps them there, the row is (weighted CE row) + (Lovasz row) through lovasz_grad, and the transformer's g * w is
+// added after that: the order and the roundings of dsrl_ce_fused_w -> dsrl_lovasz_bwd(accumulate = 1) -> dsrl_pointwise_strided_bwd.
+template <int CI, int CO, bool CE, bool TW = false, bool CW = false, bool FL = false, bool SM = false, bool DC = false, bool LV = false>
 __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ dy,
                                                                  float* __restrict__ dx, float* __restrict__ part, int N, int H, int W,
-                                                                 int nseg_per_row, int nseg, std::conditional_t<DC, ConvtCeDiceArgs, ConvtCeArgs> ce) {
+                                                                 int nseg_per_row, int nseg, ConvtCeArgsOf<DC, LV> ce) {
     static_assert(CE || !CW, "class weights belong to the CE build");
     static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
     static_assert(!SM || (CW && !FL), "label smoothing runs on the weighted machinery and has no focal form");
     static_assert(!DC || (CW && !FL && !SM && !TW && CO <= 32), "the Dice term runs on the weighted machinery, in the 8-wave build");
+    static_assert(!LV || (CW && !FL && !SM && !TW && !DC), "the Lovasz term runs on the weighted machinery, in the 8-wave build");
     constexpr int TP = 128, COLS = 4 * CO, NK = COLS / 2, NJ = (COLS + 31) / 32, NOUT = CI * COLS;
     constexpr int XB = TP * CI * 4, XP = (XB + 1023) / 1024;               // bytes / 1 KB pieces of an x segment
     constexpr int GB = 2 * TP * CO * 4, GP = GB / 1024;                    // of one dy row segment
@@ -209,6 +220,17 @@ __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(con
 #pragma unroll
                 for (int c = 0; c < CO; ++c)
                     e[c] = live ? (e[c] * inv - (c == tg ? sc : 0.f)) + dice_grad(e[c], inv_s, sub_s[32 + c], c == tg, a_t, dot, dlive) : 0.f;
+            } else if (LV) {
+                // (weighted CE row) + (Lovasz row); a pixel whose label is >= CO takes no part in the term and has weight 0 in the table
+                if constexpr (LV) {
+                    const bool llive = live && tg < CO;
+                    float inv_s, dot, g[CO];
+                    lovasz_pixel<CO>(e, CO, s, tg, llive, ce.lovasz + kLovaszHeadFloats, ce.lovasz + kLovaszHeadFloats + CO * ce.bins, ce.bins, inv_s, g, dot);
+                    const float sc = wt_s[tg];
+                    const float inv = sc / s;
+#pragma unroll
+                    for (int c = 0; c < CO; ++c) e[c] = live ? (e[c] * inv - (c == tg ? sc : 0.f)) + lovasz_grad(e[c], inv_s, g[c], dot, llive) : 0.f;
+                }
             } else if (CW) {
                 // sc = table[target] is per lane where `scale` is uniform: held across the 19 operations beside inv it is one VGPR more than the
                 // 768-thread build has (168, 2 spilled).  So it is read twice: for inv, and again - through a copy of the index the compiler cannot
@@ -396,23 +418,24 @@ bool convt_bwd_dma_supported(const void* x, const void* dy, int W, int Cin, int 
 }
 int convt_bwd_dma_blocks(long long nseg, int cap) { return (int)std::min<long long>(std::min(cap, kNumCU), nseg); }
 
-template <bool CE, bool TW, bool CW = false, bool FL = false, bool SM = false, bool DC = false>
+template <bool CE, bool TW, bool CW = false, bool FL = false, bool SM = false, bool DC = false, bool LV = false>
 static int launch_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, const ConvtCeArgs& ce, hipStream_t st,
-                      const float* dice = nullptr) {
+                      const float* dice = nullptr, int bins = 0) {
     constexpr int CI = 19, CO = 19;
     constexpr int kLds = 3 * ((128 * CI * 4 + 1023) / 1024 + 2 * (2 * 128 * CO * 4 / 1024) + (CE ? 2 : 0)) * 1024;
     static_assert(kLds + (CW ? 1024 : 0) + (SM ? 128 : 0) + (DC ? 256 : 0) + 128 <= 160 * 1024,
                   "the ring, the transformer's weights, the class-weight tables and the Dice tables in LDS");
-    static const hipError_t attr = hipFuncSetAttribute((const void*)convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM, DC>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+    static const hipError_t attr = hipFuncSetAttribute((const void*)convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM, DC, LV>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     if (attr != hipSuccess) { set_error("convt2x2_bwd_dma_kernel: %d bytes of LDS refused (%s)", kLds, hipGetErrorString(attr)); return DSRL_E_LAUNCH; }
     const int nseg_per_row = W / 128;
     const long long nseg = (long long)N * H * nseg_per_row;
     if ((long long)N * 4 * H * W * CO * 4 >= (1ll << 32)) { set_error("convt2x2_bwd_dma_kernel: output gradient of 4 GB or more"); return DSRL_E_UNSUPPORTED; }
     if (nseg >= (1ll << 31) || nblocks < 1 || nblocks > nseg) { set_error("convt2x2_bwd_dma_kernel: %lld segments, %d blocks", nseg, nblocks); return DSRL_E_BADARG; }
-    std::conditional_t<DC, ConvtCeDiceArgs, ConvtCeArgs> args{};
+    ConvtCeArgsOf<DC, LV> args{};
     static_cast<ConvtCeArgs&>(args) = ce;
     if constexpr (DC) args.dice = dice;
-    hipLaunchKernelGGL((convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM, DC>), dim3(nblocks), dim3(TW ? 768 : 512), kLds, st, x, w, dy, dx, part, N, H, W, nseg_per_row, (int)nseg, args);
+    if constexpr (LV) { args.lovasz = dice; args.bins = bins; }
+    hipLaunchKernelGGL((convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM, DC, LV>), dim3(nblocks), dim3(TW ? 768 : 512), kLds, st, x, w, dy, dx, part, N, H, W, nseg_per_row, (int)nseg, args);
     return launch_status("convt2x2_bwd_dma_kernel");
 }
 int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, hipStream_t st) {
@@ -435,6 +458,9 @@ int launch_convt_bwd_dma_ce(const float* x, const float* w, const float* logits,
     // Dice: one wave build, the 8-wave one, as focal and label smoothing have.  The 12-wave build has 168 VGPRs and spills with focal already; the
     // Dice row keeps 1 / s, a_t and the class sum beside the 19 terms and the weighted row's inv and sc
     if (v.kind == CeVariant::kDice) return launch_dma<true, false, true, false, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st, v.dice);
+    // Lovasz: the 8-wave build as well: 19 gathered coefficients beside the 19 terms
+    if (v.kind == CeVariant::kLovasz)
+        return launch_dma<true, false, true, false, false, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st, v.lovasz, v.bins);
     if (v.kind == CeVariant::kWeighted) return w8 ? launch_dma<true, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st)
                         : launch_dma<true, true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
     if (w8) return launch_dma<true, false>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);

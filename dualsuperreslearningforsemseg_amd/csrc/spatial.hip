@@ -1436,6 +1436,14 @@ extern "C" int dsrl_convt2x2_bwd_ce_d(const float* x, const float* w, const floa
     return convt_bwd_ce_any(CeVariant::diced(weights, dice_record), x, w, logits, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, dx, dw, dbias, N, H, W, Cin,
                             Cout, ws, ws_bytes, stream);
 }
+extern "C" int dsrl_convt2x2_bwd_ce_l(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* weights,
+                                      const float* lovasz_record, int bins, const float* ce_wsum, const float* ft_g, const float* ft_w, int ft_stride, float* dx,
+                                      float* dw, float* dbias, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    DSRL_REQUIRE(lovasz_record && ((uintptr_t)lovasz_record % 4) == 0 && bins >= kLovaszMinBins && bins <= kLovaszMaxBins && (bins & (bins - 1)) == 0, DSRL_E_BADARG,
+                 "convt2x2_bwd_ce_l: bad arguments (no Lovasz record, or bins = %d not a power of two in [16, 4096])", bins);
+    return convt_bwd_ce_any(CeVariant::lovasz_of(weights, lovasz_record, bins), x, w, logits, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, dx, dw, dbias, N,
+                            H, W, Cin, Cout, ws, ws_bytes, stream);
+}
 
 static size_t pixel_shuffle_tile_bytes(int c, int r) { return (size_t)kPsTile * c * (r * r + 1) * sizeof(float); }
 static bool pixel_shuffle_tiled_ok(int N, int H, int W, int c, int r) {

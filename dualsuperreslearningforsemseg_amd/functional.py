@@ -1296,11 +1296,12 @@ class LogitsGrad:
     leaves `target`, `count` (device pointer holder) here and reports no gradient; the stride-8 feature transformer leaves its incoming gradient and
     weights; the ConvTranspose backward then forms d(CE)/d(logits) (+ the transformer's rank-one term) inside its own kernel
     (dsrl_convt2x2_bwd_ce): the 319 MB gradient of the 256x512 step is neither written nor read."""
-    __slots__ = ('y', 'xshape', 'x_ptr', 'armed', 'target', 'ignore_index', 'count', 'ft', 'value', 'value_key', 'weight', 'gamma', 'eps', 'dice')
+    __slots__ = ('y', 'xshape', 'x_ptr', 'armed', 'target', 'ignore_index', 'count', 'ft', 'value', 'value_key', 'weight', 'gamma', 'eps', 'dice', 'lovasz')
 
     def __init__(self):
         self.y = None; self.xshape = None; self.x_ptr = 0; self.armed = False; self.target = None; self.ignore_index = 255; self.count = None; self.ft = None
         self.dice = None            # the record of dsrl_dice_fwd when the loss has a Dice term (always with a table, like gamma); None: no such term
+        self.lovasz = None          # (record of dsrl_lovasz_fwd, bins) when the loss has a Lovasz-Softmax term (always with a table too); None: no such term
         self.value = None           # [CE, pixel count, ...] when the producing layer already evaluated the loss (logits_target), and for which
         self.value_key = None       # (target pointer, ignore_index, NaN flag pointer, class-weight table pointer or 0, label smoothing, focal gamma)
         self.weight = None          # the 256-float class-weight table of a weighted loss (class_weight_table); `count` then holds D = sum n_c w_c
@@ -1552,17 +1553,124 @@ def dice_loss(logits, target, ignore_index=255, weight=1.0, smooth=1.0):
     return _DiceLoss.apply(logits, target, int(ignore_index), dice)
 
 
-def _focal_args(weight, gamma, device, num_classes, eps=0.0, dice=None):
+LOVASZ_DEFAULT = (1.0, 1024)            # lambda, bins of `lovasz=True`: an equal-weight "CE + Lovasz-Softmax" within 1 / 2048 of the unquantised loss
+LOVASZ_BINS = (16, 4096)                # bins: a power of two in this range
+
+
+def lovasz_value(x):
+    """The Lovasz-Softmax term as (lambda, bins), or None when it is off.  None / False / 0: off; True: LOVASZ_DEFAULT; a finite number > 0: lambda,
+    with the default bins; a pair (lambda, bins); a mapping with the keys 'weight' (lambda) and / or 'bins' (a missing one takes its default).
+    bins: an integer power of two in [16, 4096].  A lambda of 0 inside a pair or a mapping is off too.  ValueError on anything else - a bool where a
+    number belongs, a NaN, an infinity, a negative number, an unknown key, bins that are not such a power of two.  Touches no device."""
+    if x is None:
+        return None
+    if isinstance(x, (bool, np.bool_)):
+        return LOVASZ_DEFAULT if x else None
+    if isinstance(x, dict):
+        if not x or set(x) - {'weight', 'bins'}:
+            raise ValueError(f"lovasz = {x!r}: expected a mapping with the keys 'weight' and 'bins'")
+        lam, bins = x.get('weight', LOVASZ_DEFAULT[0]), x.get('bins', LOVASZ_DEFAULT[1])
+    elif isinstance(x, (tuple, list)) and len(x) == 2:
+        lam, bins = x
+    elif isinstance(x, (int, float, np.integer, np.floating)):
+        lam, bins = x, LOVASZ_DEFAULT[1]
+    else:
+        raise ValueError(f'lovasz = {x!r}: expected None, a bool, a number > 0, a pair (weight, bins) or a mapping with these keys')
+    if isinstance(lam, (bool, np.bool_)) or not isinstance(lam, (int, float, np.integer, np.floating)):
+        raise ValueError(f'lovasz: weight = {lam!r}: expected a finite number >= 0')
+    with np.errstate(over='ignore'):
+        lam32 = float(np.float32(float(lam)))                                  # (the kernels take it as fp32)
+    if not (0.0 <= float(lam) and math.isfinite(lam32)):                       # (a NaN fails the comparison)
+        raise ValueError(f'lovasz: weight = {lam!r}: expected a finite number >= 0')
+    if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)):
+        raise ValueError(f'lovasz: bins = {bins!r}: expected an integer power of two in [{LOVASZ_BINS[0]}, {LOVASZ_BINS[1]}]')
+    bins = int(bins)
+    if not (LOVASZ_BINS[0] <= bins <= LOVASZ_BINS[1]) or bins & (bins - 1):
+        raise ValueError(f'lovasz: bins = {bins!r}: expected an integer power of two in [{LOVASZ_BINS[0]}, {LOVASZ_BINS[1]}]')
+    lam = float(lam)
+    if lam == 0.0:
+        return None
+    if lam32 == 0.0:
+        raise ValueError(f'lovasz: weight = {lam!r} is zero as fp32')
+    return lam, bins
+
+
+def _lovasz_args(lovasz, gamma, eps, ohem, dice):
+    """lovasz_value(lovasz) of a CE call, after the combinations it does not go with: a focal or label-smoothed loss, hard-pixel mining and the Dice
+    term (scoped out - each would be one more build of the backward kernel: ValueError).  It goes with class weights."""
+    lovasz = lovasz_value(lovasz)
+    if lovasz is not None and (gamma > 0.0 or eps > 0.0 or ohem is not None or dice is not None):
+        raise ValueError(f'lovasz = {lovasz!r} together with focal_gamma = {gamma!r}, label_smoothing = {eps!r}, ohem = {ohem!r} or dice = {dice!r}: '
+                         'the combination is not supported')
+    return lovasz
+
+
+def _lovasz_record(logits, ld, target, P, Cc, ignore_index, lovasz, flag=None):
+    """dsrl_lovasz_fwd on pixel-major logits and a contiguous uint8 target: -> the device record {lambda L, |Present|, 0, 0, gf[C][bins], gb[C][bins]}
+    (DESIGN.md 6.1.14).  No host read: it can be captured."""
+    lam, bins = lovasz
+    rec = torch.empty(cquery('dsrl_lovasz_record_floats', Cc, bins), device=logits.device, dtype=torch.float32)
+    ws = _ws(cquery('dsrl_lovasz_workspace_bytes', P, Cc, bins), logits)
+    call('dsrl_lovasz_fwd', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), float(lam), int(bins), rec.data_ptr(),
+         None if flag is None else flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return rec
+
+
+class _LovaszLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, lovasz):
+        logits, ld = pm(logits)
+        _need_gpu(target)
+        if target.dtype != torch.uint8:
+            target = target.to(torch.uint8)
+        target = target.contiguous()
+        N, Cc, H, W = logits.shape
+        P = N * H * W
+        if target.numel() != P:
+            raise DsrlHipError(f'lovasz_softmax_loss: target has {target.numel()} pixels, logits {P}')
+        rec = _lovasz_record(logits, ld, target, P, Cc, ignore_index, lovasz)
+        ctx.save_for_backward(logits, target, rec)
+        ctx.ignore_index = int(ignore_index)
+        ctx.bins = int(lovasz[1])
+        return rec[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, rec = ctx.saved_tensors
+        _, ld = pm(logits)
+        N, Cc, H, W = logits.shape
+        dl = new_cl((N, Cc, H, W), logits)
+        call('dsrl_lovasz_bwd', logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, rec.data_ptr(), ctx.bins, 0, dl.data_ptr(), Cc,
+             _stream())
+        dl.mul_(g.reshape(1, 1, 1, 1).float())          # the incoming gradient as a device scalar: no host read (1 leaves every element as it is)
+        return dl, None, None, None
+
+
+def lovasz_softmax_loss(logits, target, ignore_index=255, weight=1.0, bins=1024):
+    """weight * L, the Lovasz-Softmax loss (Berman et al., CVPR 2018) of the softmax of logits (N,C,H,W) against target (N,H,W) uint8/long in its
+    QUANTISED form: the errors |[t == c] - p_c| of the live pixels are put into `bins` levels and the Lovasz extension of the
+    Jaccard loss is evaluated at the level centres, exactly, from integer histograms - within 1 / (2 bins) of the sorted, unquantised loss, with no
+    sort.  classes = 'present' over the whole call (per_image = False): the mean runs over the classes some live pixel carries; a pixel is live when
+    its label is neither ignore_index nor >= C.  The gradient keeps the ranking constant, as autograd does in the sorted form.  weight: a finite
+    number > 0; bins: a power of two in [16, 4096].  Differentiable (dsrl_lovasz_fwd / dsrl_lovasz_bwd); the histograms are those of this call."""
+    lovasz = lovasz_value((weight, bins))
+    if lovasz is None:
+        raise ValueError(f'lovasz_softmax_loss: weight = {weight!r}: expected a finite number > 0')
+    return _LovaszLoss.apply(logits, target, int(ignore_index), lovasz)
+
+
+def _focal_args(weight, gamma, device, num_classes, eps=0.0, dice=None, lovasz=None):
     """(class-weight table or None, gamma, eps) of a CE call: the focal and the label-smoothed loss run on the weighted kernels, so gamma > 0 or
-    eps > 0 without weights takes the all-ones table of `num_classes` classes; so does a Dice term (`dice` not None), whose fused backward is a
-    build of the weighted kernel.  gamma and eps both at once: ValueError (the combination has no agreed definition and no kernel)."""
+    eps > 0 without weights takes the all-ones table of `num_classes` classes; so do a Dice term (`dice` not None) and a Lovasz-Softmax term
+    (`lovasz` not None), whose fused backwards are builds of the weighted kernel.  gamma and eps both at once: ValueError (the combination has no
+    agreed definition and no kernel)."""
     gamma = focal_gamma_value(gamma)
     eps = label_smoothing_value(eps)
     if gamma > 0.0 and eps > 0.0:
         raise ValueError(f'label_smoothing = {eps!r} together with focal_gamma = {gamma!r}: the combination is not defined')
     if weight is not None:
         weight = class_weight_table(weight, device, num_classes)
-    elif gamma > 0.0 or eps > 0.0 or dice is not None:
+    elif gamma > 0.0 or eps > 0.0 or dice is not None or lovasz is not None:
         weight = class_weight_table(np.ones(int(num_classes), np.float32), device, num_classes)
     return weight, gamma, eps
 
@@ -1595,7 +1703,7 @@ class logits_target:
     together with either of the two).  Outside the block, or when the shape does not qualify, nothing changes.  With ohem nothing is engaged either:
     the target the loss will use does not exist before the logits do, so the plain forward runs and fused_losses evaluates the value itself."""
 
-    def __init__(self, target, ignore_index, flag, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None, dice=None):
+    def __init__(self, target, ignore_index, flag, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None, dice=None, lovasz=None):
         focal_gamma = focal_gamma_value(focal_gamma)
         label_smoothing = label_smoothing_value(label_smoothing)
         if focal_gamma > 0.0 and label_smoothing > 0.0:
@@ -1604,11 +1712,12 @@ class logits_target:
         # a Dice term leaves the forward as it is: the kernel evaluates the CE value (on the weighted machinery: the all-ones table without weights,
         # as fused_losses will use) and dsrl_dice_fwd reads the logits once more
         dice = _dice_args(dice, focal_gamma, label_smoothing, ohem)
+        lovasz = _lovasz_args(lovasz, focal_gamma, label_smoothing, ohem, dice)        # the same holds for a Lovasz-Softmax term (dsrl_lovasz_fwd)
         ok = (convt_ce_enabled and target is not None and target.is_cuda and target.dtype == torch.uint8 and target.is_contiguous() and target.dim() == 3
               and flag is not None and flag.dtype == torch.int32 and ohem is None)
         if weight is not None and target is not None:
             weight = class_weight_table(weight, target.device)
-        self.new = (target, int(ignore_index), flag, weight, focal_gamma, label_smoothing, dice is not None) if ok else None
+        self.new = (target, int(ignore_index), flag, weight, focal_gamma, label_smoothing, dice is not None or lovasz is not None) if ok else None
 
     def __enter__(self):
         global _logits_target
@@ -1665,9 +1774,9 @@ class _ConvT2x2(torch.autograd.Function):
         h = ctx.holder
         hand = None
         if h is not None and h.armed:           # the loss left d(CE)/d(logits) to this layer: take it over, and disarm the holder whatever happens next
-            hand = (h.y, h.target, int(h.ignore_index), h.count, h.ft, h.weight, h.gamma, h.eps, h.dice)
+            hand = (h.y, h.target, int(h.ignore_index), h.count, h.ft, h.weight, h.gamma, h.eps, h.dice, h.lovasz)
             h.armed = False; h.ft = None; h.target = None; h.count = None; h.y = None; h.value = None; h.weight = None; h.gamma = 0.0; h.eps = 0.0
-            h.dice = None
+            h.dice = None; h.lovasz = None
         fused = dy is None and hand is not None
         if dy is None and not fused:
             raise DsrlHipError('conv_transpose2d_k2s2: backward reached without a gradient for the output')
@@ -1677,7 +1786,7 @@ class _ConvT2x2(torch.autograd.Function):
             # another consumer of the logits sent a gradient too (it is not the loss's: fused_losses returned none): d(CE)/d(logits) and the
             # transformer's term are written as the unfused step writes them (dsrl_ce_fused, dsrl_dice_bwd(accumulate = 1) when the loss has a Dice
             # term, dsrl_pointwise_strided_bwd(accumulate = 1)), dy is added as autograd would add it, and the plain backward below takes the sum
-            y, target, ign, _, ft, wt, gamma, eps, dice_rec = hand
+            y, target, ign, _, ft, wt, gamma, eps, dice_rec, lov = hand
             P = N * 4 * H * W
             dl = new_cl((N, Co, 2 * H, 2 * W), x)
             scal = torch.empty(8, device=x.device, dtype=torch.float32)
@@ -1687,6 +1796,8 @@ class _ConvT2x2(torch.autograd.Function):
                  wsc.data_ptr(), wsc.numel(), _stream())
             if dice_rec is not None:
                 call('dsrl_dice_bwd', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, dice_rec.data_ptr(), 1, dl.data_ptr(), Co, _stream())
+            if lov is not None:             # (or dsrl_lovasz_bwd(accumulate = 1) when it has a Lovasz-Softmax term)
+                call('dsrl_lovasz_bwd', y.data_ptr(), Co, target.data_ptr(), P, Co, ign, lov[0].data_ptr(), lov[1], 1, dl.data_ptr(), Co, _stream())
             if ft is not None:
                 ft_g, ft_w, ft_s = ft
                 dwf = torch.empty(Co, device=x.device, dtype=torch.float32)          # the transformer's weight gradient was delivered by its own backward
@@ -1701,11 +1812,13 @@ class _ConvT2x2(torch.autograd.Function):
         db = (bsink if bsink is not None else torch.empty(Co, device=x.device, dtype=torch.float32)) if ctx.has_bias else None
         ws = _ws(cquery('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, Ci, Co), x)
         if fused:
-            y, target, ign, count, ft, wt, gamma, eps, dice_rec = hand
+            y, target, ign, count, ft, wt, gamma, eps, dice_rec, lov = hand
             ft_g, ft_w, ft_s = ft if ft is not None else (None, None, 0)
             sfx, extra = _ce_variant(wt, gamma, eps)
             if dice_rec is not None:            # the weighted row plus the Dice row (never with gamma or eps: _dice_args)
                 sfx, extra = '_d', (wt.data_ptr(), dice_rec.data_ptr())
+            if lov is not None:                 # the weighted row plus the Lovasz row (never with gamma, eps or Dice: _lovasz_args)
+                sfx, extra = '_l', (wt.data_ptr(), lov[0].data_ptr(), lov[1])
             call('dsrl_convt2x2_bwd_ce' + sfx, x.data_ptr(), w.data_ptr(), y.data_ptr(), target.data_ptr(), ign, *extra, count.data_ptr() + 4,
                  None if ft_g is None else ft_g.data_ptr(), None if ft_w is None else ft_w.data_ptr(), int(ft_s),
                  dx.data_ptr(), dw.data_ptr(), None if db is None else db.data_ptr(), N, H, W, Ci, Co, ws.data_ptr(), ws.numel(), _stream())
@@ -1851,7 +1964,7 @@ class _CrossEntropy(torch.autograd.Function):
         return dl, None, None, None, None, None
 
 
-def cross_entropy(logits, target, ignore_index=255, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None, dice=None):
+def cross_entropy(logits, target, ignore_index=255, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None, dice=None, lovasz=None):
     """nn.CrossEntropyLoss(weight, ignore_index, label_smoothing=) with mean reduction; target (N,H,W) uint8/long; weight: None, one number per
     class, or a class_weight_table.  focal_gamma > 0: the focal loss sum w[t] (1 - p_t)^gamma (-log p_t) / sum w[t]; 0 changes
     nothing.  label_smoothing in (0, 1]: torch's smoothed loss, with one deviation: a class of weight 0 adds nothing to the
@@ -1859,13 +1972,19 @@ def cross_entropy(logits, target, ignore_index=255, weight=None, focal_gamma=0.0
     ohem (ohem_value: None, True, (thresh, min_kept) or a mapping): online hard example mining - the loss of ohem_target's rewritten target, with or
     without weights (the selection is on the unweighted probability); together with focal_gamma > 0 or label_smoothing > 0: ValueError.
     dice (dice_value: None, True, a weight, (weight, smooth) or a mapping): adds weight * L_dice (dice_loss) to the CE, with or
-    without class weights; together with focal_gamma > 0, label_smoothing > 0 or ohem: ValueError."""
+    without class weights; together with focal_gamma > 0, label_smoothing > 0 or ohem: ValueError.
+    lovasz (lovasz_value: None, True, a weight, (weight, bins) or a mapping): adds weight * L_lovasz, the quantised Lovasz-Softmax loss
+    (lovasz_softmax_loss), with or without class weights; together with focal_gamma > 0, label_smoothing > 0, ohem or dice:
+    ValueError."""
     dice = _dice_args(dice, focal_gamma_value(focal_gamma), label_smoothing_value(label_smoothing), ohem_value(ohem))
+    lovasz = _lovasz_args(lovasz, focal_gamma_value(focal_gamma), label_smoothing_value(label_smoothing), ohem_value(ohem), dice)
     weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, logits.device, logits.shape[1], label_smoothing)
     ohem = _ohem_args(ohem, focal_gamma, label_smoothing, ignore_index)
     if ohem is not None:
         target = ohem_target(logits, target, ignore_index, *ohem)
     ce =_CrossEntropy.apply(logits, target, ignore_index, weight, focal_gamma, label_smoothing)
+    if lovasz is not None:
+        return ce + _LovaszLoss.apply(logits, target, int(ignore_index), lovasz)
     return ce if dice is None else ce + _DiceLoss.apply(logits, target, int(ignore_index), dice)
 
 
@@ -1903,7 +2022,7 @@ class _FusedLosses(torch.autograd.Function):
     its incoming gradient is 1 (TrainStep calls vals[3].backward()); the stored gradients are returned as they are."""
 
     @staticmethod
-    def forward(ctx, sssr, sisr, ft1, ft2, target, org, ignore_index, w1, w2, stage, flag, k, weight=None, gamma=0.0, eps=0.0, dice=None):
+    def forward(ctx, sssr, sisr, ft1, ft2, target, org, ignore_index, w1, w2, stage, flag, k, weight=None, gamma=0.0, eps=0.0, dice=None, lovasz=None):
         want = bool(ctx.needs_input_grad[0])          # forward-only (validation, no_grad): no gradient buffers are written
         logits, ld = pm(sssr)
         _need_gpu(target)
@@ -1940,6 +2059,15 @@ class _FusedLosses(torch.autograd.Function):
             ce_ptr = ce_dice.data_ptr()
             if dl is not None:
                 call('dsrl_dice_bwd', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), rec.data_ptr(), 1, dl.data_ptr(), Cc, st)
+        lrec = None
+        if lovasz is not None:
+            # the Lovasz-Softmax term, wired as the Dice term is: one more pass leaves the record, record[0] joins the CE value,
+            # and without a hand-over the row is added to d(CE)/d(logits) here
+            lrec = _lovasz_record(logits, ld, target, P, Cc, ignore_index, lovasz, flag)
+            ce_lov = scal[0:1] + lrec[0:1]
+            ce_ptr = ce_lov.data_ptr()
+            if dl is not None:
+                call('dsrl_lovasz_bwd', logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), lrec.data_ptr(), lovasz[1], 1, dl.data_ptr(), Cc, st)
         da = None
         mse_ptr = fa_ptr = None
         ctx.fa = None
@@ -1970,6 +2098,7 @@ class _FusedLosses(torch.autograd.Function):
         if lg is not None:
             lg.target = target; lg.ignore_index = int(ignore_index); lg.count = scal; lg.ft = None; lg.weight = weight; lg.gamma = gamma; lg.eps = eps; lg.armed = True
             lg.dice = rec
+            lg.lovasz = None if lrec is None else (lrec, lovasz[1])
         ctx.lg = lg
         ctx.grads = (dl, da)
         ctx.w2 = float(w2)
@@ -2009,7 +2138,7 @@ class _FusedLosses(torch.autograd.Function):
             if slot is not None and buf is not None and not slot.closed and slot.buf is None:
                 slot.buf = buf
                 out[i] = None
-        return out[0], out[1], d1, d2, None, None, None, None, None, None, None, None, None, None, None, None
+        return out[0], out[1], d1, d2, None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 _fused_losses_root_checked = False
@@ -2042,7 +2171,7 @@ def fused_losses_backward(vals):
 
 
 def fused_losses(outs, target, input_org, ignore_index, w1, w2, stage, flag, subsample_factor=8, weight=None, focal_gamma=0.0, label_smoothing=0.0,
-                 ohem=None, dice=None):
+                 ohem=None, dice=None, lovasz=None):
     """-> 5-float device tensor [CE, w1*MSE, w2*FA, total, NaN flag]; `outs` = DSRL.forward's 4-tuple.  vals[3].backward() is the only
     supported backward (the function is the root of the pass); `flag` is the int32 NaN flag the fused kernels OR into.  weight: per-class CE
     weights (None, one number per class, or a class_weight_table): nn.CrossEntropyLoss(weight=).  focal_gamma > 0 makes the CE term the focal loss
@@ -2051,17 +2180,20 @@ def fused_losses(outs, target, input_org, ignore_index, w1, w2, stage, flag, sub
     everything after it - the loss pass, the hand-over to the layer that produced the logits - runs on the rewritten target as it stands.
     dice (as cross_entropy) adds the soft Dice term lambda L_dice of this call's pixels: vals[0] = CE + lambda L_dice and vals[3] includes it; the
     gradient of the term is added to d(CE)/d(logits), inside the ConvTranspose backward when the hand-over engages (dsrl_convt2x2_bwd_ce_d).  The CE
-    then runs on the weighted kernels (all-ones weights when `weight` is None); not together with focal_gamma > 0, label_smoothing > 0 or ohem."""
+    then runs on the weighted kernels (all-ones weights when `weight` is None); not together with focal_gamma > 0, label_smoothing > 0 or ohem.
+    lovasz (as cross_entropy) adds the quantised Lovasz-Softmax term in the same way (dsrl_convt2x2_bwd_ce_l when the hand-over engages); not
+    together with any of the others but `weight`."""
     sssr, sisr, ft1, ft2 = outs
     dice = _dice_args(dice, focal_gamma_value(focal_gamma), label_smoothing_value(label_smoothing), ohem_value(ohem))
-    weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, sssr.device, sssr.shape[1], label_smoothing, dice)
+    lovasz = _lovasz_args(lovasz, focal_gamma_value(focal_gamma), label_smoothing_value(label_smoothing), ohem_value(ohem), dice)
+    weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, sssr.device, sssr.shape[1], label_smoothing, dice, lovasz)
     ohem = _ohem_args(ohem, focal_gamma, label_smoothing, ignore_index)
     if ohem is not None:
         target = ohem_target(sssr, target, ignore_index, *ohem, flag=flag)
     dummy = _const1(0.0, sssr.device)            # stands in for the outputs a lower stage does not have (a cached constant: no fill launch per step)
     return _FusedLosses.apply(sssr, sisr if stage > 1 else dummy, ft1 if stage > 2 else dummy, ft2 if stage > 2 else dummy, target,
                               input_org if stage > 1 else dummy, int(ignore_index), float(w1), float(w2), int(stage), flag, int(subsample_factor), weight,
-                              focal_gamma, label_smoothing, dice)
+                              focal_gamma, label_smoothing, dice, lovasz)
 
 
 _RED = {'mean': 0, 'sum': 1, 'none': 2}

@@ -572,6 +572,48 @@ int dsrl_convt2x2_bwd_ce_d(const float* x, const float* w, const float* logits, 
                            const float* ft_w /*nullable*/, int ft_stride, float* dx, float* dw, float* dbias /*nullable*/, int N, int H, int W, int Cin,
                            int Cout, void* ws, size_t ws_bytes, dsrl_stream_t stream);
 
+/* Lovasz-Softmax loss term beside the cross entropy (Berman et al., CVPR 2018), in its QUANTISED form: loss = CE + lambda L.  A pixel
+ * is live when its label is neither ignore_index nor >= C; p_ic = e_ic (1 / s_i) is its softmax with the terms of the CE kernels (m = max,
+ * e_c = exp(v_c - m), s = sum e_c with c ascending).  K = bins levels:
+ *     err_ic = |[t_i == c] - p_ic|     b_ic = min(K - 1, max(0, floor(err_ic K)))     e^_b = (b + 1/2) / K
+ * Per class c over the live pixels of the call: nf_c[b] / nb_c[b] = the foreground (t_i == c) / background pixels in level b, G_c = sum_b nf_c[b], and
+ * from the top level down NFincl_c[b] = sum_{b' >= b} nf_c[b'], NBincl_c[b] = sum_{b' >= b} nb_c[b'], NBabove_c[b] = NBincl_c[b] - nb_c[b]:
+ *     wf_c[b] = 1 / (G_c + NBabove_c[b])          wb_c[b] = (G_c - NFincl_c[b]) / ((G_c + NBabove_c[b]) (G_c + NBincl_c[b]))
+ *     L_c = sum_b e^_b (nf_c[b] wf_c[b] + nb_c[b] wb_c[b])
+ *     Present = {c : G_c > 0}     L = (1 / |Present|) sum_{c in Present} L_c          (Present empty: L = 0 and every table entry 0)
+ * This is the exact Lovasz extension of the Jaccard loss at the quantised errors (ties: foreground first; the value does not depend on the order
+ * among ties), within 1 / (2 K) of the unquantised loss; classes = 'present', over the batch (per_image = False).  The gradient treats the ranking
+ * as constant, as autograd does in the sorted implementation (straight-through over the quantisation):
+ *     g_ic = (c == t_i ? gf_c : gb_c)[b_ic],   gf = -(lambda / |Present|) wf,   gb = +(lambda / |Present|) wb          (c not in Present: 0)
+ *     d(lambda L) / d v_ik = live_i p_ik (g_ik - sum_j p_ij g_ij)          (sum over j ascending)
+ *   dsrl_lovasz_record_floats(C, bins) = 4 + 2 C bins: record = {lambda L, |Present|, 0, 0, gf[C][bins], gb[C][bins]}, the tables formed in double and
+ *                  rounded once.  dsrl_lovasz_workspace_bytes(P, C, bins) = 2 C bins uint32 + 784.  Both depend on their arguments alone (0, with a
+ *                  message, for arguments out of range).
+ *   dsrl_lovasz_fwd  clears its workspace on the stream, makes one pass over the logits (ld >= C; 16-byte loads when ld == C and the base is 16-byte
+ *                  aligned; one pass per group of classes when C x bins packed words do not fit LDS beside the tile: 19 x 1024 do, 19 x 4096 take
+ *                  three) into per-block LDS histograms flushed with 32-bit integer atomics, scans every class from the top level down and writes
+ *                  the record.  Integers only up to the tables, no float atomics: the same bits on every call.  After the call ws begins with
+ *                  uint32 nf[C][bins], nb[C][bins].  A NaN logit in a live pixel ORs 1 into nan_flag and makes record[0] NaN (its levels are still in
+ *                  range).  ws: 16-byte aligned.
+ *   dsrl_lovasz_bwd  dlogits[i][k] = the row above from the logits and the record (accumulate = 0), or dlogits + row (accumulate = 1, one fp32
+ *                  addition per element; a pixel that is not live adds +0).
+ *   dsrl_convt2x2_bwd_ce_l  dsrl_convt2x2_bwd_ce_w with the Lovasz row added to the weighted CE row inside the kernel (all-ones weights for an
+ *                  unweighted CE), the tables gathered from global memory: bit-identical to dsrl_ce_fused_w -> dsrl_lovasz_bwd(accumulate = 1) ->
+ *                  dsrl_pointwise_strided_bwd(accumulate = 1) -> dsrl_convt2x2_bwd.  Same contract and workspace as the _w entry point.
+ * Everything runs on the stream with no host read: the calls can be captured.  Argument errors (DSRL_E_BADARG before any HIP call, nothing written):
+ * null pointers, P <= 0 or >= 2^31 - 256, C outside 1..60, ld or lddl < C, lambda not a finite number > 0, bins not a power of two in [16, 4096],
+ * accumulate not 0 or 1; a workspace too small or misaligned is DSRL_E_WORKSPACE. */
+size_t dsrl_lovasz_workspace_bytes(int64_t P, int C, int bins);
+size_t dsrl_lovasz_record_floats(int C, int bins);
+int dsrl_lovasz_fwd(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float lambda, int bins, float* record,
+                    int* nan_flag /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+int dsrl_lovasz_bwd(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* record, int bins, int accumulate,
+                    float* dlogits, int lddl, dsrl_stream_t stream);
+int dsrl_convt2x2_bwd_ce_l(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* weights /*[256]*/,
+                           const float* lovasz_record, int bins, const float* ce_wsum /*D: loss_out + 1*/, const float* ft_g /*nullable*/,
+                           const float* ft_w /*nullable*/, int ft_stride, float* dx, float* dw, float* dbias /*nullable*/, int N, int H, int W, int Cin,
+                           int Cout, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+
 /* FALoss (models/losses/FALoss.py:8-34). fm1/fm2 are (B,C,H,W) with element strides (sb,sc,sh,sw).
  * reduction: 0 mean, 1 sum, 2 none (out has B*C*n*n floats, n = (W/k)^2).
  * `saved` (>= dsrl_fa_saved_floats) carries S1,S2,sigma,u1,v1 to the backward. */

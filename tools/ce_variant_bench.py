@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Cost of one cross-entropy variant at the step's shape (N = 8, tail input 256 x 512, 19 -> 19), written to profiles/<variant>_ce.txt
-(class_weighted_ce.txt, focal_ce.txt, label_smoothing_ce.txt, ohem_ce.txt, dice_ce.txt):
+(class_weighted_ce.txt, focal_ce.txt, label_smoothing_ce.txt, ohem_ce.txt, dice_ce.txt, lovasz_ce.txt):
   * kernel-only times through the C ABI, HIP events around back-to-back launches, the variant's entry points against their base:
       weighted   dsrl_convt2x2_fwd_ce_w, dsrl_convt2x2_bwd_ce_w and dsrl_ce_fused_w against the unweighted calls, and the D pre-pass alone
                  (dsrl_ce_weight_sum: label histogram + weight sum);
@@ -10,10 +10,14 @@
                  dsrl_ohem_target, thresh = 0.7, min_kept = 100000;
       dice       dsrl_dice_fwd beside dsrl_copy2d on as many bytes, dsrl_ohem_prob on the same logits and the torch composition (softmax, one-hot,
                  sums); dsrl_dice_bwd; dsrl_convt2x2_bwd_ce_d against dsrl_convt2x2_bwd_ce_w on the same inputs; five windows each, lambda = smooth = 1;
+      lovasz     dsrl_lovasz_fwd at K = 1024 and K = 4096, on random logits and on near-one-hot logits (almost every background error in level 0: the
+                 contended case), each with the per-wave aggregation of levels 0 and K - 1 and without it (DSRL_LOVASZ_AGG=0), beside dsrl_dice_fwd
+                 and dsrl_copy2d on as many bytes; dsrl_lovasz_bwd; dsrl_convt2x2_bwd_ce_l against _d and _w; the torch composition (softmax, 19 x
+                 torch.sort, cumsum); five windows each, lambda = 1;
   * the replayed training step (stage 3, batch 8, 256 x 512 input, hipGraph): default, class weights and (focal, smoothed) class weights + gamma
-    or eps, alternating in one process (ohem: default against ohem = (0.7, 100000); dice: default, class weights, class weights + dice = True).
+    or eps, alternating in one process (ohem: default against ohem = (0.7, 100000); dice / lovasz: default, class weights, class weights + the term).
 Everything in that file from the line '## recorded beside the tool' on is kept as it is.
-Usage: python tools/ce_variant_bench.py weighted|focal|smoothed|ohem|dice [--steps K] [--no-step] [VAR=value ...]"""
+Usage: python tools/ce_variant_bench.py weighted|focal|smoothed|ohem|dice|lovasz [--steps K] [--no-step] [VAR=value ...]"""
 import os
 import sys
 import time
@@ -35,7 +39,8 @@ VARIANTS = {'weighted': ('_w', '', None, None, 'weighted', None, 'class_weighted
             'focal': ('_f', '_w', 2.0, 'gamma', 'focal', 'focal_gamma', 'focal_ce.txt'),
             'smoothed': ('_s', '_w', 0.1, 'eps', 'smoothed', 'label_smoothing', 'label_smoothing_ce.txt'),
             'ohem': ('', '', (0.7, 100000), 'ohem', 'ohem', 'ohem', 'ohem_ce.txt'),
-            'dice': ('_d', '_w', (1.0, 1.0), 'dice', 'dice', 'dice', 'dice_ce.txt')}
+            'dice': ('_d', '_w', (1.0, 1.0), 'dice', 'dice', 'dice', 'dice_ce.txt'),
+            'lovasz': ('_l', '_w', (1.0, 1024), 'lovasz', 'lovasz', 'lovasz', 'lovasz_ce.txt')}
 if not args or args[0] not in VARIANTS:
     sys.exit(__doc__)
 VARIANT = args[0]
@@ -237,6 +242,103 @@ def dice_kernels():
     say(f'  this batch: lambda L_dice = {r[0]:.6f}, |K| = {int(r[1])}, torch composition {float(torch_dice()):.6f}')
 
 
+def lovasz_kernels():
+    N, H, W, C = 8, 256, 512, 19
+    P = N * 4 * H * W
+    lam = PARAM[0]
+    rs = np.random.RandomState(1)
+    y = torch.randn(N, 2 * H, 2 * W, C, device=dev) * 3
+    top = y.argmax(dim=-1).to(torch.uint8)
+    tg = torch.randint(0, C, (N, 2 * H, 2 * W), device=dev, dtype=torch.uint8)
+    tg = torch.where(torch.rand(tg.shape, device=dev) < 0.5, top, tg)
+    tg[torch.rand(tg.shape, device=dev) < 0.1] = 255
+    # a confident model: the label's logit 12 above noise of 0.5 on 97 % of the pixels - p of the others about 6e-6, level 0 at either K
+    hot = torch.randn(N, 2 * H, 2 * W, C, device=dev) * 0.5
+    lab = torch.where(tg == 255, torch.zeros_like(tg), tg).long()
+    right = torch.rand(tg.shape, device=dev) < 0.97
+    hot.scatter_add_(3, torch.where(right, lab, (lab + 1) % C).unsqueeze(-1), torch.full((N, 2 * H, 2 * W, 1), 12.0, device=dev))
+    x = torch.randn(N, H, W, C, device=dev); w = torch.randn(C, C, 2, 2, device=dev) * 0.2
+    wt = HF.class_weight_table(rs.uniform(0.25, 8.0, C), dev)
+    dx = torch.empty_like(x); dw = torch.empty_like(w); db = torch.empty(C, device=dev); dl = torch.zeros_like(y)
+    scal = torch.zeros(8, device=dev); flag = torch.zeros(1, dtype=torch.int32, device=dev); drec = torch.zeros(128, device=dev)
+    ftg = torch.randn(N, H // 4, W // 4, device=dev); ftw = torch.randn(C, device=dev)
+    st = HF._stream()
+    wb = torch.empty(query('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, C, C), dtype=torch.uint8, device=dev)
+    wsd = torch.empty(query('dsrl_dice_workspace_bytes', P), dtype=torch.uint8, device=dev)
+    wsf = torch.empty(query('dsrl_ce_fused_w_workspace_bytes', P), dtype=torch.uint8, device=dev)
+    recs = {K: torch.zeros(query('dsrl_lovasz_record_floats', C, K), device=dev) for K in (1024, 4096)}
+    wsl = {K: torch.empty(query('dsrl_lovasz_workspace_bytes', P, C, K), dtype=torch.uint8, device=dev) for K in (1024, 4096)}
+    call('dsrl_ce_fused_w', y.data_ptr(), C, tg.data_ptr(), P, C, 255, wt.data_ptr(), None, C, scal.data_ptr(), flag.data_ptr(), wsf.data_ptr(), wsf.numel(), st)
+    call('dsrl_dice_fwd', y.data_ptr(), C, tg.data_ptr(), P, C, 255, 1.0, 1.0, drec.data_ptr(), flag.data_ptr(), wsd.data_ptr(), wsd.numel(), st)
+
+    def fwd(lg, K, agg):
+        os.environ['DSRL_LOVASZ_AGG'] = agg
+        call('dsrl_lovasz_fwd', lg.data_ptr(), C, tg.data_ptr(), P, C, 255, lam, K, recs[K].data_ptr(), flag.data_ptr(), wsl[K].data_ptr(), wsl[K].numel(), st)
+
+    def torch_lovasz(lg):
+        live = tg != 255
+        pr = torch.softmax(lg, dim=-1)[live]
+        lab = tg[live].long()
+        losses = []
+        for c in range(C):
+            fg = (lab == c).float()
+            if fg.sum() == 0:
+                continue
+            es, perm = torch.sort((fg - pr[:, c]).abs(), descending=True)
+            fs = fg[perm]
+            gts = fs.sum()
+            jac = 1.0 - (gts - fs.cumsum(0)) / (gts + (1.0 - fs).cumsum(0))
+            jac[1:] = jac[1:] - jac[:-1]
+            losses.append(torch.dot(es, jac))
+        return lam * torch.stack(losses).mean()
+
+    def bwd(s, extra):
+        call('dsrl_convt2x2_bwd_ce' + s, x.data_ptr(), w.data_ptr(), y.data_ptr(), tg.data_ptr(), 255, *extra, scal.data_ptr() + 4, ftg.data_ptr(),
+             ftw.data_ptr(), 8, dx.data_ptr(), dw.data_ptr(), db.data_ptr(), N, H, W, C, C, wb.data_ptr(), wb.numel(), st)
+
+    lb = P * C * 4
+    rows = []
+    for K in (1024, 4096):
+        npass = 1 if K == 1024 else 3
+        for name, lg in (('random logits', y), ('near-one-hot logits', hot)):
+            for agg in ('1', '0'):
+                rows.append((f'dsrl_lovasz_fwd K = {K}, {name}, {"aggregated" if agg == "1" else "plain LDS atomics"}', npass * (lb + P),
+                             lambda lg=lg, K=K, agg=agg: fwd(lg, K, agg)))
+    rows += [('dsrl_dice_fwd on the random logits', lb + P,
+              lambda: call('dsrl_dice_fwd', y.data_ptr(), C, tg.data_ptr(), P, C, 255, 1.0, 1.0, drec.data_ptr(), flag.data_ptr(), wsd.data_ptr(), wsd.numel(), st)),
+             ('dsrl_copy2d, half the logits: as many bytes read + written', lb,
+              lambda: call('dsrl_copy2d', y.data_ptr(), C, dl.data_ptr(), C, P // 2, C, st)),
+             ('torch: softmax, 19 x torch.sort, cumsum (random logits)', 0, lambda: torch_lovasz(y))]
+    say(f'kernel-only, us per call (N = {N}, tail input {H} x {W}, {P} pixels, {lb / 1e6:.0f} MB of logits; lambda = {lam}; five windows of 20 back-to-back')
+    say('calls each: min / median / max of the windows; bytes (the logits once per class group: 1 pass at K = 1024, 3 at K = 4096) and rate at the median):')
+
+    def table(rows):
+        for label, nbytes, f in rows:
+            wins = sorted(timeit(f, 5 if label.startswith('torch') else 20) for _ in range(5))
+            rate = f'   {nbytes / 1e6:6.1f} MB   {nbytes / wins[2] / 1e6:5.2f} TB/s' if nbytes else ''
+            say(f'  {label:<72} {wins[0]:8.1f} / {wins[2]:8.1f} / {wins[4]:8.1f}{rate}')
+    table(rows)
+    os.environ.pop('DSRL_LOVASZ_AGG', None)
+    fwd(y, 1024, '1'); os.environ.pop('DSRL_LOVASZ_AGG', None)
+    rows = [('dsrl_lovasz_bwd K = 1024, accumulate = 1', 3 * lb + P,
+             lambda: call('dsrl_lovasz_bwd', y.data_ptr(), C, tg.data_ptr(), P, C, 255, recs[1024].data_ptr(), 1024, 1, dl.data_ptr(), C, st))]
+    for waves in ('12', '8'):
+        rows.append((f'dsrl_convt2x2_bwd_ce_w (DSRL_CONVT_CE_WAVES={waves})', 0, lambda waves=waves: (os.environ.__setitem__('DSRL_CONVT_CE_WAVES', waves), bwd('_w', (wt.data_ptr(),)))))
+    rows.append(('dsrl_convt2x2_bwd_ce_d (8 waves)', 0, lambda: bwd('_d', (wt.data_ptr(), drec.data_ptr()))))
+    rows.append(('dsrl_convt2x2_bwd_ce_l (8 waves), K = 1024', 0, lambda: bwd('_l', (wt.data_ptr(), recs[1024].data_ptr(), 1024))))
+    table(rows)
+    os.environ.pop('DSRL_CONVT_CE_WAVES', None)
+    torch.cuda.synchronize()
+    r = recs[1024].cpu().numpy()
+    say(f'  random logits: lambda L = {r[0]:.6f} at K = 1024, |Present| = {int(r[1])}, torch (sorted, unquantised) {float(torch_lovasz(y)):.6f}')
+    fwd(hot, 1024, '1'); os.environ.pop('DSRL_LOVASZ_AGG', None)
+    torch.cuda.synchronize()
+    r = recs[1024].cpu().numpy()
+    h = wsl[1024][:2 * C * 1024 * 4].cpu().numpy().view(np.uint32).reshape(2, C, 1024)
+    say(f'  near-one-hot logits: lambda L = {r[0]:.6f}, torch {float(torch_lovasz(hot)):.6f}; {h[1][:, 0].sum() / h[1].sum():.4f} of the background and '
+        f'{h[0][:, 0].sum() / h[0].sum():.4f} of the foreground errors in level 0')
+
+
 def replayed_step():
     import dualsuperreslearningforsemseg_amd as D
     from dualsuperreslearningforsemseg_amd import settings
@@ -265,12 +367,12 @@ def replayed_step():
         kinds = {'unweighted': {}, 'weighted': {'class_weights': w}}
     elif VARIANT == 'ohem':
         kinds = {'default': {}, 'ohem': {'ohem': PARAM}}
-    elif VARIANT == 'dice':
-        kinds = {'default': {}, 'weighted': {'class_weights': w}, 'dice': {'class_weights': w, 'dice': PARAM}}
+    elif VARIANT in ('dice', 'lovasz'):
+        kinds = {'default': {}, 'weighted': {'class_weights': w}, VARIANT: {'class_weights': w, VARIANT: PARAM}}
     else:
         kinds = {'default': {}, 'weighted': {'class_weights': w}, WORD: {'class_weights': w, STEP_KW: PARAM}}
     res, replays = {k: [] for k in kinds}, {}
-    for _ in range(3 if VARIANT == 'dice' else 2):      # one captured step at a time (the device-resident dropout key has one binding): build, warm, time, release
+    for _ in range(3 if VARIANT in ('dice', 'lovasz') else 2):      # one captured step at a time (the device-resident dropout key has one binding): build, warm, time, release
         for k, kw in kinds.items():
             s = TrainStep(model, flat, 3, 0.1, 1.0, cs.IGNORE_CLASS_LABEL, **kw)
             run(s, s.GRAPH_WARMUP + 6)
@@ -294,7 +396,7 @@ def replayed_step():
             f"{(min(res[WORD]) - min(res['default'])) * 1e3:+.0f} us")
 
 
-ohem_kernels() if VARIANT == 'ohem' else dice_kernels() if VARIANT == 'dice' else kernels()
+ohem_kernels() if VARIANT == 'ohem' else dice_kernels() if VARIANT == 'dice' else lovasz_kernels() if VARIANT == 'lovasz' else kernels()
 if '--no-step' not in args:
     replayed_step()
 out = os.path.join(ROOT, 'profiles', OUT)
