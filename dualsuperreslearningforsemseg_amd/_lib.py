@@ -214,6 +214,14 @@ PROTOTYPES = {
     'dsrl_grad_sumsq': (i32, [fp, i64, i64, fp, stream_t]),
     'dsrl_grad_clip_workspace_bytes': (sz, [i64]),
     'dsrl_grad_clip_finish': (i32, [fp, i64, fp, f32, f32, f32, f32, fp, fp, stream_t]),
+    'dsrl_adamw_step': (i32, [fp, fp, fp, fp, i64, f32, f32, f32, fp, stream_t]),
+    'dsrl_adamw_step_dev': (i32, [fp, fp, fp, fp, i64, fp, fp, stream_t]),
+    'dsrl_adamw_step_dev_segments': (i32, [fp, fp, fp, fp, fp, i64, fp, fp, stream_t]),
+    'dsrl_adamw_step_ema': (i32, [fp, fp, fp, fp, i64, f32, f32, f32, fp, fp, fp, stream_t]),
+    'dsrl_adamw_step_dev_ema': (i32, [fp, fp, fp, fp, i64, fp, fp, fp, fp, stream_t]),
+    'dsrl_adamw_step_dev_segments_ema': (i32, [fp, fp, fp, fp, fp, i64, fp, fp, fp, fp, stream_t]),
+    'dsrl_adamw_advance': (i32, [fp, stream_t]),
+    'dsrl_adamw_set_step': (i32, [fp, i64, stream_t]),
     'dsrl_nan_check': (i32, [fp, i64, fp, stream_t]),
     'dsrl_sssr_tail_predict_ex': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, fp, fp, i32, fp, stream_t]),
     'dsrl_sssr_tail_predict_flip_ex': (i32, [fp, i32] + [i32] * 6 + [fp] * 9 + [i32, fp, fp, fp, fp, sz, fp, fp, i32, fp, stream_t]),

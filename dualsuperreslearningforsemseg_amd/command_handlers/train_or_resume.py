@@ -13,7 +13,11 @@ What differs by design:
   * the input pipeline (torchvision Cityscapes + PIL transforms) reads a pre-decoded uint8 cache of the Cityscapes tree and runs the random
     augmentations as HIP kernels (datasets/Cityscapes/loader.py, models/transforms/augment.py).  `dataset` may instead carry a 'loader_factory'
     (callable(split, batch_size, device, rank, world) -> iterable of ((input_image, input_org), (target, _))), which is used as given;
-    `SyntheticCityscapes` below provides device-resident batches of the Cityscapes shapes.
+    `SyntheticCityscapes` below provides device-resident batches of the Cityscapes shapes;
+  * `dataset['optimizer'] = 'adamw'` (or {'name': 'adamw', 'betas': (b1, b2), 'eps': e}) replaces SGD by torch.optim.AdamW(lr, betas, eps,
+    weight_decay) semantics inside the same optimiser pass (ddp.FlatParams.enable_adamw): `learning_rate`, `end_learning_rate`,
+    `poly_power` and `weights_decay` keep their meaning, `momentum` is unused (stored in checkpoints as given; one warning), the checkpoint's
+    `optimizer_state_dict` has torch.optim.AdamW's layout and every epoch record carries 'optimizer': 'adamw'.  Absent, None or 'sgd': SGD, as ever.
 """
 import contextlib
 import glob
@@ -119,7 +123,11 @@ class TrainStep:
 
     Gradient-norm clipping (`flat.enable_grad_clip`) needs nothing here either: the optimiser pass forms the norm and folds the
     coefficient into the device hyper-parameters, eagerly and in the captured graph alike; whether it is enabled is part of the graph key.  It does
-    not go with the two-graph schedule (DSRL_GRAPH_SPLIT): a training iteration then raises DsrlHipError."""
+    not go with the two-graph schedule (DSRL_GRAPH_SPLIT): a training iteration then raises DsrlHipError.
+
+    AdamW (`flat.enable_adamw`) is the optimiser pass's business as well: the same launches in their AdamW forms, the step counter
+    advanced on the device, eagerly and in the captured graph alike; whether it is enabled is part of the graph key.  The momentum a step is called
+    with is then not read.  Like clipping it does not go with the two-graph schedule: a training iteration then raises DsrlHipError."""
 
     GRAPH_WARMUP = HF.GRAPH_WARMUP          # eager iterations per batch shape before the capture
 
@@ -278,6 +286,7 @@ class TrainStep:
         return (tuple(input_image.shape), tuple(input_org.shape), tuple(target.shape), HF.get_conv_precision(), HF.overlap_wgrad,
                 self.flat.e_flat is not None,           # "EMA enabled": a step captured without the weight average has no launch that updates it
                 self.flat.clip_rec is not None,         # "clip enabled": a step captured without it has neither the norm launches nor hyper_eff
+                self.flat.v_flat is not None,           # "AdamW enabled": a step captured without it holds the SGD launches and no advance of t
                 self.focal_gamma, self.label_smoothing, self.dice, self.lovasz, self.ohem)
 
     def _capture(self, key, input_image, input_org, target, hp):
@@ -381,6 +390,8 @@ class TrainStep:
             raise HF.DsrlHipError('a training step inside FlatParams.ema_weights(): the parameters are the averaged ones')
         if do_train and self.split and self.flat.clip_rec is not None:
             raise HF.DsrlHipError('gradient clipping (grad_clip) is not supported in the two-graph schedule: unset DSRL_GRAPH_SPLIT')
+        if do_train and self.split and self.flat.v_flat is not None:
+            raise HF.DsrlHipError("AdamW (optimizer='adamw') is not supported in the two-graph schedule: unset DSRL_GRAPH_SPLIT")
         if do_train and self.use_graph:
             if self.rng is None:
                 self.rng = HF.DeviceRng(self.flat.device)
@@ -507,6 +518,12 @@ def check_ema(dataset):
     return HF.ema_value(dataset.get('ema'))
 
 
+def check_optimizer(dataset):
+    """dataset['optimizer']: absent, None or 'sgd' -> None (SGD); 'adamw' or {'name': 'adamw', 'betas': (b1, b2), 'eps': e} -> (beta1, beta2, eps),
+    as HF.adamw_value; ValueError otherwise.  Touches no device."""
+    return HF.adamw_value(dataset.get('optimizer'))
+
+
 def check_grad_clip(dataset):
     """dataset['grad_clip']: absent, None or False -> None (off); a number > 0 (inf: monitor only) or {'max_norm': such a number} -> that float,
     as HF.grad_clip_value; ValueError otherwise.  Touches no device."""
@@ -539,6 +556,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     lovasz = check_lovasz(dataset)
     ema = check_ema(dataset)
     grad_clip = check_grad_clip(dataset)
+    adamw = check_optimizer(dataset)
     input_size = other_args.get('model_input_size', settings.MODEL_INPUT_SIZE)
     if distributed:
         t.manual_seed(settings.RANDOM_SEED)                                                # identical init on all ranks, :31
@@ -576,6 +594,12 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
                 model.initialize_with_pretrained_weights(settings.WEIGHTS_ROOT_DIR)
     model = model.to(device_obj).to(memory_format=t.channels_last)                        # :103 (+ kernel weight layout)
     flat = FlatParams(model)                                                               # DDP wrap, :105-106
+    if adamw is not None:
+        # dataset['optimizer']: AdamW inside the optimiser pass, its step counter and bias corrections on the device.  In front of the
+        # state load - which then expects torch.optim.AdamW's layout and refuses SGD's - and of the average and the clipping.
+        flat.enable_adamw(adamw[:2], adamw[2])
+        if momentum:
+            warnings.warn(f"dataset['optimizer'] = 'adamw': momentum = {momentum!r} is not used (betas = {adamw[:2]!r}); it is stored in checkpoints as given")
     if is_resuming_training and 'optimizer_state_dict' in other_args:
         flat.load_state_dict(other_args['optimizer_state_dict'])
     if ema is not None:
@@ -643,6 +667,8 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
                 train_loader.set_epoch(epoch)     # the sample order and the augmentation draws of this epoch
             means = _do_train_val(True, epoch, model, step, train_loader, lr, momentum, weights_decay, freeze_batch_norm, is_master_rank)
             rec = {'epoch': epoch, 'lr': lr, 'train': means}
+            if adamw is not None:
+                rec['optimizer'] = 'adamw'
             if dice is not None:
                 rec['train_ce_includes_dice'] = list(dice)      # (weight, smooth): means[0] is CE + weight * L_dice; the validation figures are the CE alone
             if lovasz is not None:

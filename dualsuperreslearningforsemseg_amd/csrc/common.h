@@ -278,6 +278,44 @@ struct GradClipRecord {
 };
 static_assert(sizeof(GradClipRecord) == 64, "GradClipRecord is 64 bytes");
 
+// ---------------------------------------------------------------- AdamW (adamw.hip)
+// The AdamW record in device memory (64 bytes, 16-byte aligned).  The host writes the configuration once (the floats as the kernels use them, 1 - beta
+// formed from the DOUBLE beta as torch forms it: 1 - 0.999f is 4.7e-5 off 0.001; the doubles for the bias corrections, which amplify a beta error by
+// t); dsrl_adamw_advance / dsrl_adamw_set_step write t and the two factors of step t, in double from t, and nothing else ever does.
+struct AdamwRecord {
+    float beta1, beta2;     // as float: beta2 multiplies v
+    float eps;
+    float ss_factor;        // 1 / (1 - beta1^t): the step size is lr times this
+    float isq;              // 1 / sqrt(1 - beta2^t)
+    float omb1, omb2;       // (float)(1 - beta1), (float)(1 - beta2) of the double betas
+    uint32_t pad0;
+    long long t;            // optimiser passes begun: the launches of a pass read the factors of THIS t (0 in a fresh record: nothing may launch yet)
+    double beta1_d, beta2_d;
+    uint32_t pad1[2];
+};
+static_assert(sizeof(AdamwRecord) == 64, "AdamwRecord is 64 bytes");
+// what every element of a launch shares, formed the same way by every entry point
+struct AdamwCoef { float dk, b1, w1, b2, w2, eps, ss, isq, gscale; };
+__device__ __forceinline__ AdamwCoef adamw_coef(float lr, float wd, float gscale, const AdamwRecord* __restrict__ r) {
+    AdamwCoef c;
+    c.dk = 1.f - lr * wd;               // decoupled decay, torch's p.mul_(1 - lr * wd)
+    c.b1 = r->beta1; c.w1 = r->omb1; c.b2 = r->beta2; c.w2 = r->omb2; c.eps = r->eps;
+    c.ss = lr * r->ss_factor; c.isq = r->isq; c.gscale = gscale;
+    return c;
+}
+// One element of torch.optim.AdamW (one group, no amsgrad, no maximize) on gh = g * grad_scale - scaled BEFORE the moments: eps makes the update depend
+// on the gradient's scale.  m as torch's lerp - from m for a weight 1 - beta1 below 1/2, from gh above, so that beta1 = 0 gives gh itself; the choice is
+// uniform over the launch -, v and both p updates with one rounding each (explicit fma: the library is built with -ffp-contract=off); square root and
+// division correctly rounded: sqrtf, which hipcc lowers to v_sqrt_f32 plus the two-fma +-1 ulp correction (NOT __fsqrt_rn - without
+// OCML_BASIC_ROUNDED_OPERATIONS the header maps it to the bare native instruction), and __fdiv_rn, the full div_scale / div_fmas / div_fixup sequence.  Every AdamW kernel goes through this one function, so that all forms round alike.
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, const AdamwCoef& c) {
+    const float gh = g * c.gscale;
+    p = p * c.dk;
+    m = c.w1 < 0.5f ? fmaf(c.w1, gh - m, m) : fmaf(-c.b1, gh - m, gh);
+    v = fmaf(c.b2, v, (c.w2 * gh) * gh);
+    p = fmaf(-c.ss, __fdiv_rn(m, fmaf(sqrtf(v), c.isq, c.eps)), p);
+}
+
 // ---------------------------------------------------------------- calibration record and confidence (calibration.hip)
 // Confidence of a pixel: the probability of the class the kernel reports (first maximum), fp32, from values the producer already has:
 //     one softmax (dsrl_calibration_from_logits, the single-view tail):  1 / s, s = sum_c exp_nonpos(v_c - m) with c ascending, m the fmaxf chain from v_0

@@ -25,6 +25,24 @@ from . import functional as HF
 from .filter_operands import FilterOperands, align as _align, conv_filters, segment_rows
 
 
+def optimizer_state_kind(sd):
+    """'sgd', 'adamw' or None (no per-parameter state to tell by) for an optimiser state_dict, from the keys of its per-parameter entries."""
+    for st in (sd.get('state') or {}).values():
+        if 'momentum_buffer' in st:
+            return 'sgd'
+        if 'exp_avg' in st or 'exp_avg_sq' in st:
+            return 'adamw'
+    return 'sgd' if 'momentum_arena' in sd else None
+
+
+def adamw_param_group(lr, betas, eps, weight_decay, nparams):
+    """The one param group of torch.optim.AdamW.state_dict() with the keys the installed torch writes (a one-scalar CPU optimiser is asked)."""
+    probe = torch.optim.AdamW([torch.zeros(1)], lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False)
+    group = dict(probe.state_dict()['param_groups'][0])
+    group['params'] = list(range(nparams))
+    return group
+
+
 class FlatParams:
     def __init__(self, model, chunk_bytes=32 << 20, process_group=None, broadcast_buffers=True):
         self.model = model
@@ -107,6 +125,8 @@ class FlatParams:
         # gradient-norm clipping (enable_grad_clip): the 64-byte device record, the tile sums at the start of their workspace, the hyper-parameters the
         # optimiser launches read once the coefficient is folded into grad_scale
         self.clip_rec = self.clip_ws = self.clip_tiles = self.hyper_eff = None
+        # AdamW (enable_adamw): the second-moment arena laid out as p_flat (m_flat is the first moment), the 64-byte device record, (beta1, beta2, eps)
+        self.v_flat = self.adamw_rec = self.adamw_config = None
         if self.world > 1 and self.device.type == 'cuda' and HF.knob('DSRL_BN_FUSED_BIG', None) is None:
             # RCCL kernels hold CUs while they wait for their peers: a 256-block fused-BN launch (one block on EVERY CU) could stall behind
             # them, the 128-block variant cannot
@@ -187,6 +207,8 @@ class FlatParams:
     def _sgd_range(self, a, b, hyper, hp):
         """SGD on arena range [a, b): with device-resident hyper-parameters and the f16 arithmetics, by the segment kernel that also measures the filters.
         With the weight average enabled the same three launches in their _ema forms: e_flat follows in the launch that writes p_flat."""
+        if self.v_flat is not None:
+            return self._adamw_range(a, b, hyper, hp)
         if self.e_flat is not None:
             e, rec = self.e_flat, self.ema_rec
             if hyper is not None and self._fold_amax():
@@ -204,6 +226,24 @@ class FlatParams:
             HF.sgd_step_dev_(self.p_flat[a:b], self.g_flat[a:b], self.m_flat[a:b], hyper)
         else:
             HF.sgd_step_(self.p_flat[a:b], self.g_flat[a:b], self.m_flat[a:b], hp[0], hp[1], hp[2], 1.0 / self.world)
+
+    def _adamw_range(self, a, b, hyper, hp):
+        """AdamW on arena range [a, b): the launch of the form _sgd_range would have picked (host / device hyper-parameters / segment table, with or
+        without the average), at the t the record holds.  `hyper` and `hp` are the SGD ones; the momentum in them is not read."""
+        p, g, m, v, rec = self.p_flat, self.g_flat, self.m_flat, self.v_flat, self.adamw_rec
+        ema = () if self.e_flat is None else (self.e_flat.data_ptr(), self.ema_rec.data_ptr())
+        if hyper is not None and self._fold_amax():
+            tab, n = self._segments(a, b)
+            HF.call('dsrl_adamw_step_dev_segments_ema' if ema else 'dsrl_adamw_step_dev_segments', p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
+                    tab.data_ptr(), n, hyper.data_ptr(), rec.data_ptr(), *ema, HF._stream())
+        elif hyper is not None and ema:
+            HF.adamw_step_dev_ema_(p[a:b], g[a:b], m[a:b], v[a:b], hyper, rec, self.e_flat[a:b], self.ema_rec)
+        elif hyper is not None:
+            HF.adamw_step_dev_(p[a:b], g[a:b], m[a:b], v[a:b], hyper, rec)
+        elif ema:
+            HF.adamw_step_ema_(p[a:b], g[a:b], m[a:b], v[a:b], hp[0], hp[2], 1.0 / self.world, rec, self.e_flat[a:b], self.ema_rec)
+        else:
+            HF.adamw_step_(p[a:b], g[a:b], m[a:b], v[a:b], hp[0], hp[2], 1.0 / self.world, rec)
 
     def ensure_filter_amax(self):
         """In front of a REPLAYED step: a graph captured while the optimiser's magnitudes were valid contains no measuring sweep and relies on the
@@ -361,7 +401,7 @@ class FlatParams:
     def sgd_step(self, lr, momentum, weight_decay, hyper=None, reduce=True):
         """torch.optim.SGD(momentum, weight_decay).step() on the whole arena; gradients are averaged over ranks here.  `hyper`: a
         4-float device tensor (lr, momentum, weight_decay, 1/world) the kernel reads when it runs (graph-replayable) instead of the
-        three host values."""
+        three host values.  After enable_adamw() the pass is torch.optim.AdamW's at the same lr and weight decay; the momentum is not read."""
         self._refuse_swapped('sgd_step')
         if reduce:
             self.finish_reduction()
@@ -376,6 +416,8 @@ class FlatParams:
         fold = hyper is not None and self._fold_amax()
         if fold:
             self.filters.amax.zero_()
+        if self.v_flat is not None:
+            HF.adamw_advance_(self.adamw_rec)       # once per pass, on the device: every range below reads the factors of the same t (the first pass: 1)
         for i, (a, b) in enumerate(ranges):
             if works:
                 works[i].wait()             # stream-ordered for RCCL: the compute stream waits for this range only
@@ -397,6 +439,8 @@ class FlatParams:
         """The optimiser state in torch.optim.SGD's state_dict layout (what the reference saves as `optimizer_state_dict`,
         train_or_resume.py:276, and loads back at main.py:51-52): one param group over model.parameters() order, per-parameter
         `momentum_buffer` tensors (copies of the arena views, channels-last parameters returned in their logical NCHW shape)."""
+        if self.v_flat is not None:
+            return self._adamw_state_dict(lr, weight_decay, initial_lr)
         ps = self._trainable_in_model_order()
         state = {}
         for i, p in enumerate(ps):
@@ -408,7 +452,15 @@ class FlatParams:
         return {'state': state, 'param_groups': [group]}
 
     def load_state_dict(self, sd):
-        """Accepts torch.optim.SGD's layout (a reference checkpoint or our own) and the round-1 arena dump."""
+        """Accepts torch.optim.SGD's layout (a reference checkpoint or our own) and the round-1 arena dump; with AdamW enabled torch.optim.AdamW's.
+        State of the other optimiser raises ValueError."""
+        kind = optimizer_state_kind(sd)
+        if self.v_flat is not None:
+            if kind == 'sgd':
+                raise ValueError('optimizer state mix-up: the state is SGD\'s (momentum_buffer), this run uses AdamW (exp_avg, exp_avg_sq)')
+            return self._load_adamw_state_dict(sd)
+        if kind == 'adamw':
+            raise ValueError('optimizer state mix-up: the state is AdamW\'s (exp_avg, exp_avg_sq), this run uses SGD (momentum_buffer)')
         if 'momentum_arena' in sd:
             if sd['numel'] != self.numel:
                 raise ValueError('optimizer arena size mismatch')
@@ -431,6 +483,75 @@ class FlatParams:
                     raise ValueError(f'momentum buffer {tuple(buf.shape)} does not match parameter {tuple(p.shape)}')
                 o = self.offsets[self._index[id(p)]]
                 self.m_flat.as_strided(p.shape, p.stride(), o).copy_(buf.to(self.device))
+
+    # ------------------------------------------------------------------ AdamW
+    def enable_adamw(self, betas=(0.9, 0.999), eps=1e-8):
+        """torch.optim.AdamW(lr, betas, eps, weight_decay) - one group, decoupled decay, no amsgrad - in every optimiser pass from here on instead of
+        SGD: v_flat (zeros, laid out as p_flat) beside m_flat (zeroed: it is the first moment now) and the 64-byte device record, t = 0.  lr, weight
+        decay and grad_scale arrive as they do for SGD (the momentum among them is ignored), the launches keep their form - host / device
+        hyper-parameters / segment table, with or without the average - and the step counter and its bias corrections live on the device, so a
+        captured step advances them on every replay.  Call it once the weights are loaded, in front of load_state_dict (which then expects AdamW's
+        layout and refuses SGD's) and of enable_ema / enable_grad_clip; a second call raises."""
+        if self.v_flat is not None:
+            raise HF.DsrlHipError('enable_adamw: AdamW of this FlatParams is already enabled')
+        cfg = HF.adamw_value({'name': 'adamw', 'betas': tuple(betas), 'eps': eps})
+        self.adamw_config = cfg
+        self.m_flat.zero_()
+        self.v_flat = torch.zeros_like(self.p_flat)
+        self.adamw_rec = HF.adamw_record(cfg[0], cfg[1], cfg[2], self.device)
+
+    def adamw_step_count(self):
+        """Optimiser passes done so far (t), read from the device record (synchronises)."""
+        if self.v_flat is None:
+            raise HF.DsrlHipError('adamw_step_count: AdamW is not enabled (enable_adamw)')
+        return HF.adamw_record_read(self.adamw_rec)['t']
+
+    def _adamw_state_dict(self, lr, weight_decay, initial_lr):
+        """torch.optim.AdamW's state_dict layout: per parameter `step` (a float tensor, the same t for all), `exp_avg`, `exp_avg_sq` (copies of the
+        arena views in logical NCHW shape); one param group with the keys the installed torch writes."""
+        ps = self._trainable_in_model_order()
+        t = self.adamw_step_count()
+        state = {}
+        for i, p in enumerate(ps):
+            o = self.offsets[self._index[id(p)]]
+            state[i] = {'step': torch.tensor(float(t), dtype=torch.float32),
+                        'exp_avg': self.m_flat.as_strided(p.shape, p.stride(), o).detach().clone().contiguous().cpu(),
+                        'exp_avg_sq': self.v_flat.as_strided(p.shape, p.stride(), o).detach().clone().contiguous().cpu()}
+        b1, b2, eps = self.adamw_config
+        group = adamw_param_group(lr, (b1, b2), eps, weight_decay, len(ps))
+        if initial_lr is not None:
+            group['initial_lr'] = initial_lr
+        return {'state': state, 'param_groups': [group]}
+
+    def _load_adamw_state_dict(self, sd):
+        ps = self._trainable_in_model_order()
+        ids = [i for g in sd['param_groups'] for i in g['params']]
+        if len(ids) != len(ps):
+            raise ValueError(f'optimizer state has {len(ids)} parameters, the model {len(ps)}')
+        steps = set()
+        todo = []
+        for p, i in zip(ps, ids):
+            st = sd['state'].get(i)
+            if not st:
+                continue                              # torch creates the state lazily: a parameter that never stepped has none and stays zero
+            m, v = st.get('exp_avg'), st.get('exp_avg_sq')
+            if m is None or v is None or 'step' not in st:
+                raise ValueError(f'AdamW state of parameter {i} lacks step, exp_avg or exp_avg_sq')
+            if tuple(m.shape) != tuple(p.shape) or tuple(v.shape) != tuple(p.shape):
+                raise ValueError(f'AdamW moments {tuple(m.shape)} / {tuple(v.shape)} do not match parameter {tuple(p.shape)}')
+            steps.add(int(float(st['step'])))
+            todo.append((p, m, v))
+        if len(steps) > 1 or any(s < 0 for s in steps):
+            raise ValueError(f'AdamW state with step counts {sorted(steps)}: one count >= 0 for all parameters expected (one group, one arena)')
+        self.m_flat.zero_()
+        self.v_flat.zero_()
+        self.invalidate_filter_amax()
+        with torch.no_grad():
+            for p, m, v in todo:
+                o = self.offsets[self._index[id(p)]]
+                self.m_flat.as_strided(p.shape, p.stride(), o).copy_(m.to(self.device))
+                self.v_flat.as_strided(p.shape, p.stride(), o).copy_(v.to(self.device))
+        HF.adamw_set_step_(self.adamw_rec, steps.pop() if steps else 0)
 
     # ------------------------------------------------------------------ filter magnitudes left by the optimiser pass: explicit invalidation
     def invalidate_filter_amax(self):

@@ -2428,6 +2428,112 @@ def grad_clip_finish_(tiles, record, hyper_out, hyper=None, hp=None):
          hyper_out.data_ptr(), _stream())
 
 
+# ------------------------------------------------------------------------------------------------ AdamW
+ADAMW_DEFAULT = (0.9, 0.999, 1e-8)      # beta1, beta2, eps of `optimizer='adamw'`: torch.optim.AdamW's
+ADAMW_RECORD_WORDS = 16                 # include/dsrl_hip.h: the 64-byte AdamW record
+
+
+def adamw_value(x):
+    """dataset['optimizer'] as (beta1, beta2, eps) for AdamW, or None for SGD.  None / 'sgd' / {'name': 'sgd'}: None; 'adamw': ADAMW_DEFAULT; a mapping
+    {'name': 'adamw', 'betas': (b1, b2), 'eps': e} ('betas' and 'eps' optional) with 0 <= b < 1 (also as fp32) and a finite e >= 0: those values.
+    ValueError on anything else - an unknown name or key, a bool or NaN where a number belongs, a beta of 1.  Touches no device."""
+    def number(v, what):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f'optimizer: {what} = {v!r}: expected a number')
+        return float(v)
+
+    if x is None:
+        return None
+    if isinstance(x, str):
+        x = {'name': x}
+    if not isinstance(x, dict) or 'name' not in x or set(x) - {'name', 'betas', 'eps'}:
+        raise ValueError(f"optimizer = {x!r}: expected None, 'sgd', 'adamw' or a mapping with the keys 'name', 'betas' and 'eps'")
+    name = x['name']
+    if name == 'sgd' and set(x) == {'name'}:
+        return None
+    if name != 'adamw':
+        raise ValueError(f"optimizer = {x!r}: expected the name 'sgd' (without options) or 'adamw'")
+    betas, eps = x.get('betas', ADAMW_DEFAULT[:2]), number(x.get('eps', ADAMW_DEFAULT[2]), 'eps')
+    if not isinstance(betas, (tuple, list)) or len(betas) != 2:
+        raise ValueError(f'optimizer: betas = {betas!r}: expected a pair (beta1, beta2)')
+    b1, b2 = (number(b, 'beta') for b in betas)
+    for b in (b1, b2):
+        if not (0.0 <= b < 1.0) or not (float(np.float32(b)) < 1.0):           # (a NaN fails the comparison; the kernels multiply v by beta2 as fp32)
+            raise ValueError(f'optimizer: betas = {betas!r}: expected 0 <= beta < 1')
+    if not (0.0 <= eps < float('inf')):
+        raise ValueError(f'optimizer: eps = {eps!r}: expected a finite number >= 0')
+    return b1, b2, eps
+
+
+def adamw_record(beta1, beta2, eps, device):
+    """A fresh AdamW record (include/dsrl_hip.h) as a 16-word int32 tensor on `device`: the betas as float and as double, 1 - beta rounded from the
+    double difference, eps, t = 0.  The two bias-correction factors are the device's to write (adamw_advance_, adamw_set_step_); no launch may read
+    the record before one of them ran."""
+    words = np.zeros(ADAMW_RECORD_WORDS, dtype=np.int32)
+    words[:3] = np.array([beta1, beta2, eps], dtype=np.float32).view(np.int32)
+    words[5:7] = np.array([1.0 - float(beta1), 1.0 - float(beta2)], dtype=np.float32).view(np.int32)
+    words[10:14] = np.array([beta1, beta2], dtype=np.float64).view(np.int32)
+    return torch.from_numpy(words).to(device)
+
+
+def adamw_record_read(record):
+    """The record's fields on the host (one synchronising read)."""
+    words = record.detach().cpu().numpy()
+    f = words[:7].view(np.float32)
+    return {'beta1': float(words[10:12].view(np.float64)[0]), 'beta2': float(words[12:14].view(np.float64)[0]), 'eps': float(f[2]),
+            'ss_factor': float(f[3]), 'isq': float(f[4]), 't': int(words[8:10].view(np.int64)[0])}
+
+
+def _adamw_check(record, *arenas):
+    _need_gpu(record, *arenas)
+    if record.numel() * record.element_size() != 4 * ADAMW_RECORD_WORDS:
+        raise DsrlHipError('adamw: a 64-byte AdamW record (adamw_record) expected')
+    if any(a.numel() != arenas[0].numel() or a.dtype != torch.float32 or not a.is_contiguous() for a in arenas):
+        raise DsrlHipError('adamw: contiguous fp32 arenas of one size expected')
+
+
+def adamw_advance_(record):
+    """Once per optimiser pass, in front of its launches: t += 1 and the factors of the new t, on the device."""
+    _adamw_check(record)
+    call('dsrl_adamw_advance', record.data_ptr(), _stream())
+
+
+def adamw_set_step_(record, t):
+    """t (optimiser passes done so far) and its factors into the record, through the device code of adamw_advance_."""
+    _adamw_check(record)
+    call('dsrl_adamw_set_step', record.data_ptr(), int(t), _stream())
+
+
+def adamw_step_(p, g, m, v, lr, weight_decay, grad_scale, record):
+    """In-place torch.optim.AdamW step on flat fp32 arenas (m: exp_avg, v: exp_avg_sq) at the t the record holds."""
+    _adamw_check(record, p, g, m, v)
+    call('dsrl_adamw_step', p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(weight_decay), float(grad_scale),
+         record.data_ptr(), _stream())
+
+
+def adamw_step_dev_(p, g, m, v, hyper, record):
+    """The same update with {lr, -, weight_decay, grad_scale} read from the 4-float device tensor `hyper` (the SGD launches' record) at run time."""
+    _adamw_check(record, p, g, m, v)
+    _need_gpu(hyper)
+    call('dsrl_adamw_step_dev', p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), hyper.data_ptr(), record.data_ptr(), _stream())
+
+
+def adamw_step_ema_(p, g, m, v, lr, weight_decay, grad_scale, record, ema, ema_record):
+    """adamw_step_ with the weight average `ema` updated from the new p in the same launch."""
+    _adamw_check(record, p, g, m, v, ema)
+    _need_gpu(ema_record)
+    call('dsrl_adamw_step_ema', p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(weight_decay), float(grad_scale),
+         record.data_ptr(), ema.data_ptr(), ema_record.data_ptr(), _stream())
+
+
+def adamw_step_dev_ema_(p, g, m, v, hyper, record, ema, ema_record):
+    """adamw_step_dev_ with the weight average updated in the same launch."""
+    _adamw_check(record, p, g, m, v, ema)
+    _need_gpu(hyper, ema_record)
+    call('dsrl_adamw_step_dev_ema', p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), hyper.data_ptr(), record.data_ptr(), ema.data_ptr(),
+         ema_record.data_ptr(), _stream())
+
+
 class DeviceRng:
     """Device-resident twin of the host dropout key (begin_forward): three 64-bit words {key, step, base}.  While bound, every
     dropout-bearing kernel of the device reads `key` when it runs and advance() enqueues the per-step derivation, so that a step

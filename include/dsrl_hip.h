@@ -765,6 +765,34 @@ int dsrl_grad_sumsq(const float* g, int64_t first, int64_t n, double* tiles, dsr
 size_t dsrl_grad_clip_workspace_bytes(int64_t n);
 int dsrl_grad_clip_finish(const double* tiles, int64_t ntiles, const float* hyper_in /*device, 4 floats, or null*/, float lr, float momentum,
                           float weight_decay, float grad_scale, void* record, float* hyper_out /*device, 4 floats*/, dsrl_stream_t stream);
+/* torch.optim.AdamW(lr, betas, eps, weight_decay) - one parameter group, decoupled decay, no amsgrad, no maximize - on the flat arenas p, g, m
+ * (exp_avg), v (exp_avg_sq), all 16-byte aligned.  Per element, in fp32, with gh = g * grad_scale (scaled before the moments: eps makes the update
+ * depend on the gradient's scale):
+ *     p <- p (1 - lr wd);  m <- m + (1 - b1)(gh - m);  v <- b2 v + (1 - b2) gh gh;  p <- p - ss m / (sqrt(v) isq + eps)
+ *     ss = lr / (1 - b1^t), isq = 1 / sqrt(1 - b2^t); square root and division correctly rounded.
+ * record: 64 bytes of device memory, 16-byte aligned: {float beta1, float beta2, float eps, float ss_factor = 1 / (1 - b1^t), float isq,
+ * float (1 - beta1), float (1 - beta2) (of the double betas), 4 bytes of padding, int64 t, double beta1, double beta2, 8 bytes of padding}.  The host
+ * writes the betas and eps once; t and the two factors are written by dsrl_adamw_advance (t += 1; once per optimiser pass, BEFORE its launches: a
+ * fresh record holds t = 0, the first pass runs with t = 1) and dsrl_adamw_set_step (a resume), both of which form the factors in double from t
+ * itself - the same bits whichever way t was reached - and never by the host.  The element launches only read the record.
+ * The entry points mirror dsrl_sgd_step*: host hyper-parameters; `hyper` = the 4 device floats {lr, unused, weight_decay, grad_scale} the SGD
+ * launches read (slot 1, SGD's momentum, is ignored: dsrl_grad_clip_finish serves both optimisers); the segment table of
+ * dsrl_sgd_step_dev_segments, with max |p_new| published to the rows' amax records in the same way.  The _ema forms add the average's arena and the
+ * EMA record and update the average from the p they have just computed.  All six give the same bits in p, m and v. */
+int dsrl_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float weight_decay, float grad_scale, const void* record,
+                    dsrl_stream_t stream);
+int dsrl_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper /*device, 4 floats*/, const void* record,
+                        dsrl_stream_t stream);
+int dsrl_adamw_step_dev_segments(float* p, const float* g, float* m, float* v, const int64_t* table, int64_t nseg, const float* hyper /*device, 4 floats*/,
+                                 const void* record, dsrl_stream_t stream);
+int dsrl_adamw_step_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, float weight_decay, float grad_scale, const void* record,
+                        float* ema, const void* ema_record, dsrl_stream_t stream);
+int dsrl_adamw_step_dev_ema(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper /*device, 4 floats*/, const void* record,
+                            float* ema, const void* ema_record, dsrl_stream_t stream);
+int dsrl_adamw_step_dev_segments_ema(float* p, const float* g, float* m, float* v, const int64_t* table, int64_t nseg,
+                                     const float* hyper /*device, 4 floats*/, const void* record, float* ema, const void* ema_record, dsrl_stream_t stream);
+int dsrl_adamw_advance(void* record, dsrl_stream_t stream);
+int dsrl_adamw_set_step(void* record, int64_t t, dsrl_stream_t stream);
 /* flag[0] |= 1 if any element is NaN (the reference's per-output NaN asserts folded into one readback) */
 int dsrl_nan_check(const float* x, int64_t n, int* flag, dsrl_stream_t stream);
 
