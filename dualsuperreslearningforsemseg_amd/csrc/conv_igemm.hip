@@ -1481,6 +1481,11 @@ extern "C" int dsrl_conv2d_fwd_stats_parts(int N, int H, int W, int C, int K, in
 static bool planes_usable(int C, int ld, const void* a_planes, const void* b_planes) {
     return C % 8 == 0 && ld % 8 == 0 && ((uintptr_t)a_planes % 16) == 0 && ((uintptr_t)b_planes % 16) == 0 && knob("DSRL_PLANES", 1) != 0;
 }
+// does conv_planes_kernel run this plan?  Not a cooperative split-K plan (it keeps its kernel whatever the caller offers, see fwd_impl), and not K groups
+// together with split-K slabs (DSRL_FORCE_SPLITS on a K-group plan): the planes launch has no slab dimension under K groups
+static bool planes_plan_ok(const FwdPlan& p) {
+    return planes_cfg_supported((int)p.cfg, p.kg) && !(p.coop && p.splits > 1) && !(p.kg > 1 && p.splits > 1);
+}
 static int fwd_impl(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy,
                     int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil,
                     void* ws, size_t ws_bytes, dsrl_stream_t stream, float* stats, int stats_parts,
@@ -1516,8 +1521,7 @@ static int fwd_impl(const float* x, int ldx, const float* w, const float* bias, 
         // on offer, so that the launch, its BatchNorm partials (dsrl_conv2d_fwd_stats_parts) and the bits of its result do not depend on which step first
         // had the planes (round 5: with the planes taking precedence the step-1 and step-2 plans differed, and the slab reduce wrote ceil(M/64) rows of
         // partials into a buffer sized for the cooperative launch's M/128).
-        if (x_planes != nullptr && w_planes != nullptr && x_amax != nullptr && w_amax != nullptr && planes_usable(C, ldx, x_planes, w_planes) &&
-            planes_cfg_supported((int)p.cfg, p.kg) && !(p.coop && p.splits > 1)) {
+        if (x_planes != nullptr && w_planes != nullptr && x_amax != nullptr && w_amax != nullptr && planes_usable(C, ldx, x_planes, w_planes) && planes_plan_ok(p)) {
             const long long pe = (long long)N * H * W * ldx, we = (long long)K * R * S * C;
             a.planes = conv_planes(PASS_FWD); a.w_split = 0;
             a.x = (const float*)x_planes; a.w = (const float*)w_planes;
@@ -1653,7 +1657,7 @@ static int dgrad_impl(const float* dy, int lddy, const float* w, const float* wt
     const float* wt = wt_in;
     float* slabs = (float*)((char*)ws + wtb);
     const bool use_planes = conv_f16() && dy_planes != nullptr && wt_planes != nullptr && dy_amax != nullptr && w_amax != nullptr && stride == 1 && K % 8 == 0 &&
-                            planes_usable(K, lddy, dy_planes, wt_planes) && planes_cfg_supported((int)p.cfg, p.kg) && !(p.coop && p.splits > 1);    // see fwd_impl
+                            planes_usable(K, lddy, dy_planes, wt_planes) && planes_plan_ok(p);    // see fwd_impl
     const bool use_split = conv_f16() && wt_split != nullptr && w_amax != nullptr;
     if (wt == nullptr && use_planes) wt = (const float*)wt_planes;       // replaced below; no fp32 transpose is built for it
     if (wt == nullptr && use_split) wt = (const float*)wt_split;         // replaced below; no fp32 transpose is built for it

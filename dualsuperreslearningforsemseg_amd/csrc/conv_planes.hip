@@ -686,6 +686,9 @@ __global__ __launch_bounds__(256) void filter_planes_batched_kernel(const long l
 // cfg: enum TileCfg of conv_igemm.hip {T128x128, T256x64, T256x32, T64x64, T128x64, T64x128, T128x32, T256x128, T256x256}
 template <bool DGRAD>
 static int launch_planes_t(const ConvArgs& a, int cfg, hipStream_t st) {
+    // K groups AND split-K slabs (only DSRL_FORCE_SPLITS asks for both): this grid has no slab dimension under K groups, so slabs 1.. would stay unwritten
+    // and the reduce would sum whatever the workspace held.  The hosts keep such a plan on the register-staged kernel (conv_igemm.hip: planes_plan_ok).
+    if (a.kg > 1 && a.splits > 1) { set_error("conv_planes_kernel: no launch for %d K groups with %d split-K slabs", a.kg, a.splits); return DSRL_E_UNSUPPORTED; }
     const dim3 grid((unsigned)(a.mtiles * a.ntiles), 1u, (unsigned)(a.kg > 1 ? 1 : a.splits));
     const int kg = a.kg > 1 ? a.kg : 1;
     switch (cfg) {
