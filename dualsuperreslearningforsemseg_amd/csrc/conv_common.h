@@ -87,6 +87,10 @@ struct ConvArgs {
     int bn_ldx, bn_ldy, bn_relu;          // bn_relu == 2: bn_y addresses the sign mask uint32 [K / 32][bn_ldy] of that output (bn.hip: bn_stats_apply_kernel), not y itself
     float bn_gscale;                      // factor on the masked gradient: 1 / (1 - p) when a Dropout sits behind the BatchNorm's ReLU (round 5), else 1
     int bn_fast;                          // KG == 1 builds: the BatchNorm-backward sums through LDS with 16-byte loads of x / y (host: alignment, K % 4 == 0, no parity order)
+    // KG == 1 data-gradient builds: the whole epilogue by float4 rows of the LDS-parked tile (RowEpilogue below; host: row_epilogue_ok).  bn_x_bytes / bn_y_bytes:
+    // extents of bn_x and of bn_y (the output or its sign mask) for that epilogue's bounds-checked loads
+    int row_epi;
+    unsigned bn_x_bytes, bn_y_bytes;
     // split kernels, dgrad of a strided conv (par = stride > 1, else 0): the GEMM rows are ordered by parity class - M-tile t (pbm rows) holds
     // rows (t / par^2) * pbm ... of class (ph, pw) = t % par^2, a class row j being pixel (n, hh*par + ph, wh*par + pw), (n, hh, wh) = j over the
     // Hh x Wh grid of the class - so that all rows of a tile share the taps that divide evenly (a row-major tile multiplies zeros for the
@@ -138,6 +142,132 @@ __device__ inline float4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned off) {
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
+
+// ------------------------------------------------------------------------------------------------ row epilogue (one-group data-gradient builds)
+// The accumulator layout (lane = column, register = row) makes every epilogue access 4 bytes wide, and the scalar epilogue of an accumulating launch
+// pays one full memory round trip per 32x32 piece of the wave tile (load the old values, wait, add, store, next piece), then bn_fast's round trip for
+// x / y of the BatchNorm - all of it on cold lines behind the last MFMA.  None of these operands depends on the accumulators.  Here a wave
+//   fetch():  requests EVERYTHING the epilogue reads - the old y rows, the first NB rows of the BatchNorm's x and y (or sign-mask words), mean / invstd -
+//             as float4 rows with unconditional buffer loads (dead rows: out-of-range offsets), before its tile is parked;
+//   park():   writes its finished 32 MR x 32 NR tile to its private region of the idle LDS stages (where bn_fast parks it);
+//   pass():   one pass over the float4 rows: y = (acc + old) + bias with one 16-byte store, and the BatchNorm-backward sums of the same values in
+//             bn_fast's row and shuffle order.
+// Every floating-point operation and its order are those of the scalar epilogue followed by bn_fast: the results are bit-identical.
+// Shared by conv_igemm_split_kernel and conv_planes_kernel.  Row it of lane l: tile row l / CQ + RSTEP * it, channels 4 * (l % CQ) .. + 3.
+template <int MR, int NR>
+struct RowEpilogue {
+    static constexpr int TR = 32 * MR, TC = 32 * NR, CQ = TC / 4, RSTEP = 64 / CQ, NIT = TR / RSTEP, NB = NIT < 8 ? NIT : 8;
+    int c4, r0, kk, mrow0;
+    bool kok4;
+    u32x4 old[NIT];
+    u32x4 xv[NB], yv[NB];
+    unsigned mw[NB];
+    float4 mu4, is4;
+
+    // BatchNorm operands of rows b0 .. b0 + NB - 1: x, y (bn_relu == 1) and the sign-mask word (bn_relu == 2); what the launch does not read is out of range
+    __device__ __forceinline__ void fetch_bn(const ConvArgs& a, __amdgpu_buffer_rsrc_t bx, __amdgpu_buffer_rsrc_t by, int b0) {
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+            const int m = mrow0 + r0 + RSTEP * (b0 + u);
+            const bool ok = kok4 && m < a.M && a.bstats != nullptr;
+            xv[u] = __builtin_amdgcn_raw_buffer_load_b128(bx, (int)(ok ? ((unsigned)m * (unsigned)a.bn_ldx + (unsigned)kk) * 4u : kOOB), 0, 0);
+            yv[u] = __builtin_amdgcn_raw_buffer_load_b128(by, (int)((ok && a.bn_relu == 1) ? ((unsigned)m * (unsigned)a.bn_ldy + (unsigned)kk) * 4u : kOOB), 0, 0);
+            mw[u] = __builtin_amdgcn_raw_buffer_load_b32(by, (int)((ok && a.bn_relu == 2) ? ((unsigned)(kk >> 5) * (unsigned)a.bn_ldy + (unsigned)m) * 4u : kOOB), 0, 0);
+        }
+    }
+    // mrow0_: first GEMM row of the wave tile, kcol0: its first output channel
+    __device__ __forceinline__ void fetch(const ConvArgs& a, __amdgpu_buffer_rsrc_t yr, __amdgpu_buffer_rsrc_t bx, __amdgpu_buffer_rsrc_t by, int lane, int mrow0_, int kcol0) {
+        c4 = lane % CQ; r0 = lane / CQ; mrow0 = mrow0_;
+        kk = kcol0 + 4 * c4;
+        kok4 = kk < a.K;
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {          // all old rows of the tile are requested before the first store
+            const int m = mrow0 + r0 + RSTEP * it;
+            old[it] = __builtin_amdgcn_raw_buffer_load_b128(yr, (int)((kok4 && m < a.M && a.accumulate) ? ((unsigned)m * (unsigned)a.ldy + (unsigned)kk) * 4u : kOOB), 0, 0);
+        }
+        fetch_bn(a, bx, by, 0);
+        const bool st = kok4 && a.bstats != nullptr;
+        mu4 = st ? *reinterpret_cast<const float4*>(a.bn_mean + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+        is4 = st ? *reinterpret_cast<const float4*>(a.bn_invstd + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __device__ __forceinline__ void park(float* wt, const f32x16 (&acc)[MR][NR], int lane) const {
+#pragma unroll
+        for (int i = 0; i < MR; ++i)
+#pragma unroll
+            for (int j = 0; j < NR; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    wt[(i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)) * TC + j * 32 + (lane & 31)] = acc[i][j][e];
+    }
+    // part / nparts: the wave row's block of BatchNorm partials [2][nparts][K]
+    __device__ __forceinline__ void pass(const ConvArgs& a, __amdgpu_buffer_rsrc_t yr, __amdgpu_buffer_rsrc_t bx, __amdgpu_buffer_rsrc_t by, const float* wt, int lane,
+                                         int part, int nparts) {
+        float bv[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) bv[e] = (a.bias != nullptr && kok4) ? a.bias[kk + e] : 0.f;
+        const bool sums = a.bstats != nullptr;
+        float sg[4] = {0.f, 0.f, 0.f, 0.f}, sgx[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int b0 = 0; b0 < NIT; b0 += NB) {
+            if (b0 > 0) fetch_bn(a, bx, by, b0);
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                const int row = r0 + RSTEP * (b0 + u), m = mrow0 + row;
+                const bool ok = kok4 && m < a.M;
+                float4 gv = *reinterpret_cast<const float4*>(wt + row * TC + 4 * c4);
+                if (a.accumulate) {
+                    const u32x4 o = old[b0 + u];
+                    gv.x += __uint_as_float(o.x); gv.y += __uint_as_float(o.y); gv.z += __uint_as_float(o.z); gv.w += __uint_as_float(o.w);
+                }
+                const u32x4 q = {__float_as_uint(gv.x + bv[0]), __float_as_uint(gv.y + bv[1]), __float_as_uint(gv.z + bv[2]), __float_as_uint(gv.w + bv[3])};
+                __builtin_amdgcn_raw_buffer_store_b128(q, yr, (int)(ok ? ((unsigned)m * (unsigned)a.ldy + (unsigned)kk) * 4u : kOOB), 0, 0);
+                if (sums && ok) {
+                    float4 y4 = make_float4(1.f, 1.f, 1.f, 1.f);
+                    if (a.bn_relu == 2) y4 = bn_mask4(mw[u] >> (kk & 31));          // the lane's four channels: one nibble of the sign mask
+                    else if (a.bn_relu) y4 = make_float4(__uint_as_float(yv[u].x), __uint_as_float(yv[u].y), __uint_as_float(yv[u].z), __uint_as_float(yv[u].w));
+                    const float4 x4 = make_float4(__uint_as_float(xv[u].x), __uint_as_float(xv[u].y), __uint_as_float(xv[u].z), __uint_as_float(xv[u].w));
+                    const float gs = a.bn_gscale;            // 1 / (1 - p) of a Dropout behind the ReLU (its mask is y > 0 as well), else 1: exact
+                    const float g0 = (a.bn_relu && !(y4.x > 0.f)) ? 0.f : gv.x * gs, g1 = (a.bn_relu && !(y4.y > 0.f)) ? 0.f : gv.y * gs;
+                    const float g2 = (a.bn_relu && !(y4.z > 0.f)) ? 0.f : gv.z * gs, g3 = (a.bn_relu && !(y4.w > 0.f)) ? 0.f : gv.w * gs;
+                    sg[0] += g0; sgx[0] += g0 * ((x4.x - mu4.x) * is4.x);
+                    sg[1] += g1; sgx[1] += g1 * ((x4.y - mu4.y) * is4.y);
+                    sg[2] += g2; sgx[2] += g2 * ((x4.z - mu4.z) * is4.z);
+                    sg[3] += g3; sgx[3] += g3 * ((x4.w - mu4.w) * is4.w);
+                }
+            }
+        }
+        if (!sums) return;
+#pragma unroll
+        for (int sft = CQ; sft < 64; sft <<= 1)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { sg[q] += __shfl_xor(sg[q], sft); sgx[q] += __shfl_xor(sgx[q], sft); }
+        if (lane < CQ && kok4) {
+            float* o = a.bstats + (long long)part * a.K + kk;
+            *reinterpret_cast<float4*>(o) = make_float4(sg[0], sg[1], sg[2], sg[3]);
+            *reinterpret_cast<float4*>(o + (long long)nparts * a.K) = make_float4(sgx[0], sgx[1], sgx[2], sgx[3]);
+        }
+    }
+};
+
+// Row epilogue for this pass / tile / arguments?  The ONE answer behind ConvArgs::row_epi and the dynamic-LDS size of every launcher (launch_igemm,
+// launch_sk_igemm, the planes launch), so the flag and the LDS cannot disagree.  a: the launch's arguments with bn_fast already decided for the tile.
+//   * stride-1 data gradient of an fp16 arithmetic on a one-group build, writing finished values (no slabs: splits == 1, or the cooperative launch);
+//   * output channels and ldy multiples of 4, y 16-byte aligned, no parity order; the block tile fits 128 KiB of LDS (bn_fast's rule: up to 256x128);
+//   * BatchNorm sums asked for: bn_fast's own conditions hold, and x / y of the BatchNorm lie inside a buffer descriptor's 2 GiB;
+//   * the launch has epilogue operands to fetch (it accumulates or takes the sums).  Plain data gradients and every forward launch keep the scalar
+//     epilogue: a row store with no loads to hide has to earn its LDS round trip, and that was not measured (docs/next_round_notes.md §3, item 5).
+// DSRL_ROW_EPILOGUE=0: never.  Changes no size query.
+inline bool row_epilogue_ok(const ConvArgs& a, bool dgrad, bool f16, int bm, int bn) {
+    if (!dgrad || !f16 || a.kg > 1 || a.stride != 1 || a.par != 0) return false;
+    if (a.splits > 1 && a.tickets == nullptr) return false;
+    if (a.K % 4 != 0 || a.ldy % 4 != 0 || ((uintptr_t)a.y % 16) != 0 || (size_t)bm * bn * 4 > 128 * 1024) return false;
+    if (a.bstats != nullptr && !(a.bn_fast && a.bn_x_bytes != 0 && (a.bn_relu == 0 || a.bn_y_bytes != 0))) return false;
+    if (!a.accumulate && a.bstats == nullptr) return false;
+    if (a.accumulate && a.stats != nullptr) return false;       // forward statistics are taken from the registers, which the row pass leaves without the old values
+    return knob("DSRL_ROW_EPILOGUE", 1) != 0;
+}
+// bytes of dynamic LDS the epilogue of this launch parks its tile in (0: the scalar epilogue, nothing parked)
+inline size_t epilogue_tile_bytes(const ConvArgs& a, int bm, int bn) { return (a.kg <= 1 && (a.bn_fast || a.row_epi)) ? (size_t)bm * bn * 4 : (size_t)0; }
 
 struct WgradArgs {
     const float* x; const float* dy; float* dw;     // dw or slabs

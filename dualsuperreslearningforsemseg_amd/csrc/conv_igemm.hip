@@ -1242,6 +1242,8 @@ static int launch_igemm(const ConvArgs& a_in, TileCfg cfg, hipStream_t st) {
     a.xcd_remap = knob("DSRL_XCD_REMAP", 1);
     // the fast BatchNorm-sum epilogue of the one-group builds parks the block's fp32 tile in LDS (conv_split_kernel.h): fp16 arithmetics, tiles up to 256x128
     if (a.bn_fast && !(DGRAD && conv_f16() && (size_t)bm * bn * 4 <= 128 * 1024)) a.bn_fast = 0;
+    // the row epilogue (conv_common.h: RowEpilogue) parks the same tile: one helper decides the flag, epilogue_tile_bytes() sizes the LDS of all three launchers from it
+    a.row_epi = row_epilogue_ok(a, DGRAD, conv_f16(), bm, bn) ? 1 : 0;
     if (a.planes) return launch_planes_igemm(a, (int)cfg, DGRAD, st);          // both operands as fp16 planes, staged by LDS-DMA (conv_planes.hip)
     dim3 grid((unsigned)(a.mtiles * a.ntiles), 1u, (unsigned)a.splits);
     const int npl = conv_planes(DGRAD ? PASS_DGRAD : PASS_FWD);
@@ -1282,7 +1284,7 @@ static int launch_igemm(const ConvArgs& a_in, TileCfg cfg, hipStream_t st) {
 #undef DSRL_LAUNCH_KG
             return launch_status("conv_igemm_split_kernel<K groups>");
         }
-        const size_t lds2 = std::max(stages, a.bn_fast ? (size_t)bm * bn * 4 : (size_t)0);
+        const size_t lds2 = std::max(stages, epilogue_tile_bytes(a, bm, bn));
         if (cfg == T256x128 || cfg == T256x256) {               // 8 waves; f16x3 with or without pre-split filters, and bf16x6
 #define DSRL_LAUNCH_BIG(a_, b_, c_, d_)                                                                                                   \
             {                                                                                                                              \
@@ -1719,6 +1721,11 @@ static int dgrad_impl(const float* dy, int lddy, const float* w, const float* wt
         const bool y4 = bn->relu != 1 || (bn->ldy % 4 == 0 && ((uintptr_t)bn->y % 16) == 0);        // float4 rows of y (the sign mask is read by words)
         a.bn_fast = a.par == 0 && C % 4 == 0 && bn->ldx % 4 == 0 && y4 && ((uintptr_t)bn->x % 16) == 0 &&
                     ((uintptr_t)bn->mean % 16) == 0 && ((uintptr_t)bn->invstd % 16) == 0 && ((uintptr_t)bn->stats % 16) == 0;
+        // extents of x and of y (or its sign mask [C / 32][ldy] words) for the row epilogue's bounds-checked loads; 0: beyond a descriptor's range, scalar epilogue
+        const long long bxb = span_bytes(p.M, bn->ldx, C);
+        const long long byb = bn->relu == 2 ? span_bytes(C / 32, bn->ldy, (int)std::min<long long>(p.M, bn->ldy)) : (bn->relu == 1 ? span_bytes(p.M, bn->ldy, C) : 0);
+        a.bn_x_bytes = bxb < (1ll << 31) ? (unsigned)bxb : 0u;
+        a.bn_y_bytes = byb < (1ll << 31) ? (unsigned)byb : 0u;
     }
     return launch_igemm<true>(a, p.cfg, st);
 }
@@ -1727,6 +1734,18 @@ extern "C" int dsrl_conv2d_dgrad(const float* dy, int lddy, const float* w, cons
                                  int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil,
                                  void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     return dgrad_impl(dy, lddy, w, wt_in, dx, lddx, N, H, W, C, K, R, S, stride, pad, dil, ws, ws_bytes, stream, 0);
+}
+// row_epilogue_ok() for a launch described by its properties (tests, tools): the rule launch_igemm applies, in the current arithmetic mode
+extern "C" int dsrl_conv2d_row_epilogue_supported(int dgrad, int bm, int bn, int kg, int stride, int parity, int splits, int coop, int channels, int ldy,
+                                                  size_t y_addr, int accumulate, int bn_sums, int bn_fast, int fwd_stats) {
+    static unsigned word;                       // stands for any non-null pointer: the rule only asks whether sums / statistics / tickets are present
+    ConvArgs a{};
+    a.kg = kg; a.stride = stride; a.par = parity ? stride : 0; a.splits = splits > 1 ? splits : 1;
+    a.tickets = (a.splits > 1 && coop) ? &word : nullptr;
+    a.K = channels; a.ldy = ldy; a.y = (float*)y_addr; a.accumulate = accumulate ? 1 : 0;
+    a.bstats = bn_sums ? (float*)&word : nullptr; a.bn_fast = (bn_sums && bn_fast) ? 1 : 0; a.bn_x_bytes = a.bn_fast ? 4u : 0u; a.bn_relu = 0;
+    a.stats = fwd_stats ? (float*)&word : nullptr;
+    return row_epilogue_ok(a, dgrad != 0, conv_f16(), bm, bn) ? 1 : 0;
 }
 // row blocks of BatchNorm-backward partials a dgrad launch of this shape writes in the current arithmetic mode (0 = it cannot)
 extern "C" int dsrl_conv2d_dgrad_stats_parts(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil) {

@@ -32,7 +32,7 @@ static int launch_one_kg(const ConvArgs& a, hipStream_t st) {
     (void)attr;
     const dim3 grid((unsigned)(a.mtiles * a.ntiles), 1u, (unsigned)a.splits);
     // one K group: the LDS of the ordinary 128x128 launch (two stages of 256 rows x NPL planes x 64 B, or the tile parked for the fast BatchNorm-sum epilogue)
-    const size_t lds = KG > 1 ? kSkLds : std::max((size_t)2 * (128 + 128) * NPL * 64, a.bn_fast ? (size_t)128 * 128 * 4 : (size_t)0);
+    const size_t lds = KG > 1 ? kSkLds : std::max((size_t)2 * (128 + 128) * NPL * 64, epilogue_tile_bytes(a, 128, 128));
     hipLaunchKernelGGL(k, grid, dim3(256 * KG), lds, st, a);
     return launch_status("conv_igemm_split_kernel<128x128, cooperative split-K>");
 }

@@ -522,6 +522,23 @@ void conv_igemm_split_kernel(const ConvArgs a) {
     float* yout = a.y + (!single ? (long long)z * a.slab : 0ll);
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc((void*)yout, 0, (int)a.y_bytes, 0x00020000);
     const int col = lane & 31, rq = (lane >> 5) * 4 + rowg;
+    bool row_done = false;
+    if constexpr (DGRAD && KG == 1 && BM * BN * 4 <= 128 * 1024) {      // the host's tile rule (row_epilogue_ok): larger tiles have no such path
+        if (a.row_epi && single) {
+            // the whole epilogue by float4 rows (conv_common.h: RowEpilogue): every operand requested before the tile is parked, one pass, 16-byte stores
+            using RE = RowEpilogue<MR, NR>;
+            RE re;
+            const __amdgpu_buffer_rsrc_t bxr = __builtin_amdgcn_make_buffer_rsrc((void*)a.bn_x, 0, (int)a.bn_x_bytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t byr = __builtin_amdgcn_make_buffer_rsrc((void*)a.bn_y, 0, (int)a.bn_y_bytes, 0x00020000);
+            re.fetch(a, yr, bxr, byr, lane, m0 + wm * RE::TR, n0 + wn * RE::TC);
+            float* wt = reinterpret_cast<float*>(smem) + (size_t)wave * RE::TR * RE::TC;
+            __syncthreads();                                            // every wave is done with the LDS stages
+            re.park(wt, acc, lane);
+            re.pass(a, yr, bxr, byr, wt, lane, tile_m * WGM + wm, a.mtiles * WGM);
+            row_done = true;
+        }
+    }
+    if (!row_done)
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
         const int k = n0 + (wn * NR + j) * 32 + col;
@@ -551,9 +568,9 @@ void conv_igemm_split_kernel(const ConvArgs a) {
             }
         }
     }
-    bool bstats_done = false;
+    bool bstats_done = row_done;
     if constexpr (DGRAD && KG == 1) {
-        if (a.bstats != nullptr && single && a.bn_fast) {
+        if (a.bstats != nullptr && single && a.bn_fast && !row_done) {
             // Round 5: the same sums with 16-byte accesses.  The accumulator layout (lane = column, register = row) forces one 4-byte load per element of x
             // and y - 64 (128x64 tile) or 128 (128x128) dependent-ish loads per lane, 11-17 us behind the K loop of the wide 1x1 data gradients.  Here a wave
             // parks its 32 MR x 32 NR tile in LDS (wave-private region of the idle stages, row-major), reads it back as float4 rows, and meets x / y with

@@ -101,6 +101,14 @@ int dsrl_conv2d_dgrad_bnstats(const float* dy, int lddy, const float* w, const f
                               void* ws, size_t ws_bytes, const float* bn_x, int bn_ldx, const float* bn_y /*nullable*/, int bn_ldy,
                               const float* bn_mean, const float* bn_invstd, int bn_relu, float* bstats, int stats_parts,
                               int accumulate /* dx += ..., the sums are taken of the accumulated values */, dsrl_stream_t stream);
+/* Does a conv launch with these properties run the row epilogue (float4 rows of the LDS-parked tile, csrc/conv_common.h: RowEpilogue) in the
+ * current arithmetic mode?  The host rule every launcher uses, for tests and tools; it changes no size query.  dgrad: 1 data gradient, 0 forward;
+ * bm x bn: block tile; kg: K groups; parity: 1 = rows in parity order (strided data gradients); splits / coop: split-K plan and whether it reduces
+ * inside the launch; channels, ldy, y_addr: output channels, row stride (floats) and address of the tensor written; accumulate: y += ...;
+ * bn_sums: BatchNorm-backward sums asked for, bn_fast: the 16-byte conditions of those sums hold (multiples of 4, 16-byte aligned operands, extents
+ * below 2 GiB); fwd_stats: forward BatchNorm partials asked for.  DSRL_ROW_EPILOGUE=0: always 0. */
+int dsrl_conv2d_row_epilogue_supported(int dgrad, int bm, int bn, int kg, int stride, int parity, int splits, int coop, int channels, int ldy,
+                                       size_t y_addr, int accumulate, int bn_sums, int bn_fast, int fwd_stats);
 /* dx += dgrad(dy, w): the same computation accumulated onto the existing contents of dx (a tensor that feeds two branches receives
  * both gradient contributions in one buffer, e.g. the input of a ResNet bottleneck: ResNet101.py residual add + conv1). */
 int dsrl_conv2d_dgrad_accumulate(const float* dy, int lddy, const float* w, const float* wt /*nullable*/, float* dx, int lddx,
