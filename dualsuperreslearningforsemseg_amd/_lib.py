@@ -166,6 +166,15 @@ PROTOTYPES = {
     'dsrl_lovasz_fwd': (i32, [fp, i32, fp, i64, i32, i32, f32, i32, fp, fp, fp, sz, stream_t]),
     'dsrl_lovasz_bwd': (i32, [fp, i32, fp, i64, i32, i32, fp, i32, i32, fp, i32, stream_t]),
     'dsrl_convt2x2_bwd_ce_l': (i32, [fp, fp, fp, fp, i32, fp, fp, i32, fp, fp, fp, i32, fp, fp, fp, i32, i32, i32, i32, i32, fp, sz, stream_t]),
+    'dsrl_relax_mask': (i32, [fp, i32, i32, i32, i32, i32, i32, fp, fp, stream_t]),
+    'dsrl_ce_r_workspace_bytes': (sz, [i64]),
+    'dsrl_ce_fwd_r': (i32, [fp, i32, fp, i64, i32, i32, fp, fp, fp, fp, sz, stream_t]),
+    'dsrl_ce_bwd_r': (i32, [fp, i32, fp, i64, i32, i32, fp, fp, fp, fp, fp, i32, stream_t]),
+    'dsrl_ce_fused_r_workspace_bytes': (sz, [i64]),
+    'dsrl_ce_fused_r': (i32, [fp, i32, fp, i64, i32, i32, fp, fp, fp, i32, fp, fp, fp, sz, stream_t]),
+    'dsrl_convt2x2_fwd_ce_r_workspace_bytes': (sz, [i32, i32, i32]),
+    'dsrl_convt2x2_fwd_ce_r': (i32, [fp, fp, fp, fp, i32, i32, i32, i32, i32, fp, i32, fp, fp, fp, fp, fp, sz, stream_t]),
+    'dsrl_convt2x2_bwd_ce_r': (i32, [fp, fp, fp, fp, i32, fp, fp, fp, fp, fp, i32, fp, fp, fp, i32, i32, i32, i32, i32, fp, sz, stream_t]),
     'dsrl_loss_mix': (i32, [fp, fp, fp, f32, f32, fp, fp, stream_t]),
     'dsrl_fa_saved_floats': (sz, [i32] * 5),
     'dsrl_fa_workspace_bytes': (sz, [i32] * 5),

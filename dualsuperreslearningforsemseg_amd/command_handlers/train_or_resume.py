@@ -118,6 +118,14 @@ class TrainStep:
     with `focal_gamma` > 0, `label_smoothing` > 0, `ohem` or `dice` (ValueError).  With more than one rank each rank uses the histograms of its own
     batch.  Fixed for the life of the step, like the others.
 
+    `label_relax` (HF.label_relax_value: None / False / 0 off, True = radius 1, a radius in [1, 4] or {'radius': r}): boundary label relaxation
+     in the TRAINING iterations - the class-set mask of the batch's labels is formed on the device in front of the model's forward
+    (HF.relax_mask, one launch, captured with the step), the logits layer evaluates the relaxed CE in its forward kernel and forms its gradient in
+    its backward, fused and unfused losses, eager and captured.  `do_train=False` keeps the configured CE, so validation losses and checkpoint
+    selection are unchanged.  It goes with `class_weights` and with none of the other loss options (ValueError).  With more than one rank each rank
+    uses the masks of its own batch.  `relax_stats` (int64 {live pixels, pixels with more than one class in their set}) accumulates on the device;
+    `relax_fraction(reset=True)` reads it - one device read.  Fixed for the life of the step, like the others.
+
     The weight average (`flat.enable_ema`) needs nothing here: the optimiser pass of the step updates it, eagerly and in the captured
     graph alike, and whether it is enabled is part of the graph key.  A training iteration inside `flat.ema_weights()` raises DsrlHipError.
 
@@ -132,7 +140,7 @@ class TrainStep:
     GRAPH_WARMUP = HF.GRAPH_WARMUP          # eager iterations per batch shape before the capture
 
     def __init__(self, model, flat, stage, w1, w2, ignore_index, graph=None, class_weights=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None,
-                 dice=None, lovasz=None):
+                 dice=None, lovasz=None, label_relax=None):
         self.model, self.flat, self.stage, self.w1, self.w2, self.ignore = model, flat, stage, w1, w2, ignore_index
         self.focal_gamma = HF.focal_gamma_value(focal_gamma)                                                          # ValueError on a bad gamma
         self.label_smoothing = HF.label_smoothing_value(label_smoothing)                                              # ValueError on a bad eps
@@ -142,6 +150,18 @@ class TrainStep:
         self.dice = HF._dice_args(dice, self.focal_gamma, self.label_smoothing, self.ohem)                           # ValueError on a bad value or combination
         self.lovasz = HF._lovasz_args(lovasz, self.focal_gamma, self.label_smoothing, self.ohem, self.dice)          # ValueError on a bad value or combination
         self.class_weight = None if class_weights is None else HF.class_weight_table(class_weights, flat.device)     # ValueError on bad weights
+        if isinstance(label_relax, t.Tensor):
+            raise ValueError('label_relax: a TrainStep takes the setting (a radius), not a mask: the mask is that of each batch')
+        self.label_relax = HF._label_relax_args(label_relax, self.focal_gamma, self.label_smoothing, self.ohem, self.dice, self.lovasz)   # likewise
+        self.relax_stats = self.relax_classes = None
+        if self.label_relax is not None:
+            layers = [m for m in model.modules() if getattr(m, 'logits_layer', False)]
+            if not layers:
+                raise ValueError('label_relax: the model has no logits layer to take the class count from')
+            self.relax_classes = int(layers[0].weight.shape[1])
+            if self.relax_classes > 32:
+                raise ValueError(f'label_relax: {self.relax_classes} classes, a class set is one 32-bit word')
+            self.relax_stats = t.zeros(2, dtype=t.int64, device=flat.device)
         self.fa = FALoss()
         dev = flat.device
         self.flag = t.zeros(1, dtype=t.int32, device=dev)
@@ -168,10 +188,28 @@ class TrainStep:
         self.time_collectives = False           # bench.py: bracket the exposed part of the collectives with events
         self.comm_events = []                   # (broadcast start, end, replay end, end of exchange [+ update: one-graph schedule]) per step
 
-    def losses(self, outs, input_org, target, do_train=True):
+    def relax_fraction(self, reset=False):
+        """pixels with more than one class in their set over live pixels, of the training iterations since the record was made or last reset: one
+        device read.  None without label_relax; 0.0 before the first live pixel."""
+        if self.relax_stats is None:
+            return None
+        live, multi = (int(v) for v in self.relax_stats.cpu())
+        if reset:
+            self.relax_stats.zero_()
+        return multi / live if live else 0.0
+
+    def _relax_mask(self, target, do_train):
+        """the class-set mask of this iteration's labels (training iterations with label_relax only), with the counts added to relax_stats"""
+        if not do_train or self.label_relax is None:
+            return None
+        tg = target if target.dtype == t.uint8 else target.to(t.uint8)
+        return HF.relax_mask(tg, self.relax_classes, self.ignore, self.label_relax, self.relax_stats)
+
+    def losses(self, outs, input_org, target, do_train=True, relax=None):
         SSSR, SISR, SSSR_ft, SISR_ft = outs
+        extra = {} if relax is None else {'label_relax': relax}
         ce = HF.cross_entropy(SSSR, target, self.ignore, self.class_weight, self.focal_gamma, self.label_smoothing,      # train_or_resume.py:435
-                              self.ohem if do_train else None, self.dice if do_train else None, self.lovasz if do_train else None)
+                              self.ohem if do_train else None, self.dice if do_train else None, self.lovasz if do_train else None, **extra)
         ms = self.w1 * HF.mse_loss(SISR, input_org) if self.stage > 1 else self.zero       # :436
         fa = self.w2 * self.fa(SSSR_ft, SISR_ft) if self.stage > 2 else self.zero          # :437
         return ce, ms, fa, ce + ms + fa                                                    # :438
@@ -195,24 +233,26 @@ class TrainStep:
         ohem = self.ohem if do_train else None    # validation keeps the configured CE without mining
         dice = self.dice if do_train else None    # and without the Dice term
         lovasz = self.lovasz if do_train else None      # or the Lovasz-Softmax term
+        relax = self._relax_mask(target, do_train)      # or the relaxation: the mask launch sits in front of the model's forward
+        rx = {} if relax is None else {'label_relax': relax}
         cuts = None
         try:
             with t.set_grad_enabled(do_train):
                 if self.fused_losses and do_train:
                     # the layer that produces the logits evaluates the CE value in its own forward kernel (HF.logits_target), :435
                     with HF.logits_target(target if target.dtype == t.uint8 and target.is_contiguous() else None, self.ignore, self.flag,
-                                          self.class_weight, self.focal_gamma, self.label_smoothing, ohem, dice, lovasz):
+                                          self.class_weight, self.focal_gamma, self.label_smoothing, ohem, dice, lovasz, **rx):
                         outs = self.model(input_image)                                     # :420
                 else:
                     outs = self.model(input_image)                                         # :420
                 if self.fused_losses:
                     # CE + MSE + FA, their gradients, the NaN asserts (:426-433) and the loss mix (:435-438) in one launch set
                     vals = HF.fused_losses(outs, target, input_org, self.ignore, self.w1, self.w2, self.stage, self.flag, self.fa.subsample_factor,
-                                           self.class_weight, self.focal_gamma, self.label_smoothing, ohem, dice, lovasz)
+                                           self.class_weight, self.focal_gamma, self.label_smoothing, ohem, dice, lovasz, **rx)
                     total = vals[3]
                 else:
                     HF.nan_check_(self.flag, *[o for o in outs if o.is_cuda])              # the four NaN asserts, :426-433
-                    ce, ms, fa, total = self.losses(outs, input_org, target, do_train)
+                    ce, ms, fa, total = self.losses(outs, input_org, target, do_train, relax)
                     vals = t.cat([t.stack([ce, ms, fa, total]).detach().float(), self.flag.float()])
                 if in_graph and HF.knob('DSRL_GRAPH_FAIL_TEST', ''):
                     raise RuntimeError('DSRL_GRAPH_FAIL_TEST: simulated failure in the middle of a capture')      # tests/test_rccl_gpu.py
@@ -287,7 +327,7 @@ class TrainStep:
                 self.flat.e_flat is not None,           # "EMA enabled": a step captured without the weight average has no launch that updates it
                 self.flat.clip_rec is not None,         # "clip enabled": a step captured without it has neither the norm launches nor hyper_eff
                 self.flat.v_flat is not None,           # "AdamW enabled": a step captured without it holds the SGD launches and no advance of t
-                self.focal_gamma, self.label_smoothing, self.dice, self.lovasz, self.ohem)
+                self.focal_gamma, self.label_smoothing, self.dice, self.lovasz, self.label_relax, self.ohem)
 
     def _capture(self, key, input_image, input_org, target, hp):
         """-> the captured step, or None: a capture that fails (a runtime that refuses something inside it) must not end the training run.  This
@@ -524,6 +564,17 @@ def check_optimizer(dataset):
     return HF.adamw_value(dataset.get('optimizer'))
 
 
+def check_label_relax(dataset):
+    """dataset['label_relax']: absent, None, False or 0 -> None (off); True (radius 1), an integer radius in [1, 4] or {'radius': r} -> the radius, as
+    HF.label_relax_value; ValueError otherwise, and on a value together with dataset['focal_gamma'] > 0, dataset['label_smoothing'] > 0,
+    dataset['ohem'], dataset['dice'] or dataset['lovasz'].  Touches no device."""
+    value = dataset.get('label_relax')
+    if isinstance(value, t.Tensor):
+        raise ValueError("dataset['label_relax']: expected a setting (a radius), not a tensor")
+    return HF._label_relax_args(value, check_focal_gamma(dataset), check_label_smoothing(dataset), check_ohem(dataset), check_dice(dataset),
+                                check_lovasz(dataset))
+
+
 def check_grad_clip(dataset):
     """dataset['grad_clip']: absent, None or False -> None (off); a number > 0 (inf: monitor only) or {'max_norm': such a number} -> that float,
     as HF.grad_clip_value; ValueError otherwise.  Touches no device."""
@@ -554,6 +605,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
     ohem = check_ohem(dataset)
     dice = check_dice(dataset)
     lovasz = check_lovasz(dataset)
+    label_relax = check_label_relax(dataset)
     ema = check_ema(dataset)
     grad_clip = check_grad_clip(dataset)
     adamw = check_optimizer(dataset)
@@ -633,7 +685,7 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
         lut = DeviceBatchPreparation(ds.LABEL_MAPPING_DICT, ds.MEAN, ds.STD, input_size, ds.IGNORE_CLASS_LABEL).lut_host
         class_weights = enet_weights(class_counts(cache_dir_of(dataset), 'train', lut, device_obj)[:ds.NUM_CLASSES])
     step = TrainStep(model, flat, stage, w1, w2, ds.IGNORE_CLASS_LABEL, class_weights=class_weights, focal_gamma=focal_gamma,
-                     label_smoothing=label_smoothing, ohem=ohem, dice=dice, lovasz=lovasz)
+                     label_smoothing=label_smoothing, ohem=ohem, dice=dice, lovasz=lovasz, **({} if label_relax is None else {'label_relax': label_relax}))
     train_loader = factory('train', batch_size, device_obj, rank, world)
     val_loader = factory('val', batch_size, device_obj, rank, world) if is_master_rank else None
 
@@ -673,6 +725,9 @@ def train_or_resume(is_resuming_training, device, distributed, mixed_precision, 
                 rec['train_ce_includes_dice'] = list(dice)      # (weight, smooth): means[0] is CE + weight * L_dice; the validation figures are the CE alone
             if lovasz is not None:
                 rec['train_ce_includes_lovasz'] = True          # means[0] is CE + weight * L_lovasz; the validation figures are the CE alone
+            if label_relax is not None:
+                rec['train_ce_is_relaxed'] = True               # means[0] is the relaxed CE at this radius; the validation figures are the configured CE
+                rec['relaxed_fraction'] = step.relax_fraction(reset=True)       # one device read per epoch: border pixels over live pixels
             if grad_clip is not None:
                 gc = flat.grad_clip_stats(reset=True)           # one device read per epoch: the norms of this epoch's training iterations
                 rec['grad_norm_mean'], rec['grad_norm_max'] = gc['norm_mean'], gc['norm_max']

@@ -37,11 +37,11 @@ bool convt_bwd_dma_supported(const void* x, const void* dy, int W, int Cin, int 
 int convt_bwd_dma_blocks(long long nseg, int cap);
 int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, hipStream_t st);
 
-// Which cross entropy a host call asks for: plain, class-weighted, focal or label-smoothed.  The dsrl_*_w / _f / _s entry points make theirs with
-// weighted() / focal() / smoothed(), and these hold the one normalisation rule: gamma == 0 or eps == 0 IS the weighted form, in every respect
+// Which cross entropy a host call asks for: plain, class-weighted, focal, label-smoothed or relaxed.  The dsrl_*_w / _f / _s / _r entry points make
+// theirs with weighted() / focal() / smoothed() / relaxed(), and these hold the one normalisation rule: gamma == 0 or eps == 0 IS the weighted form, in every respect
 // (kernels, messages).  Everything below the entry points takes this value and decides by kind.
 struct CeVariant {
-    enum Kind { kPlain, kWeighted, kFocal, kSmoothed, kDice, kLovasz };
+    enum Kind { kPlain, kWeighted, kFocal, kSmoothed, kDice, kLovasz, kRelaxed };
     const float* weights = nullptr;     // the 256-float class-weight table; the plain form has none
     float gamma = 0.f;                  // > 0: kFocal
     float eps = 0.f;                    // > 0: kSmoothed
@@ -54,10 +54,17 @@ struct CeVariant {
     int bins = 0;                       // kLovasz: K, the levels of that record
     static CeVariant diced(const float* w, const float* record) { return CeVariant{w, 0.f, 0.f, kDice, record}; }
     static CeVariant lovasz_of(const float* w, const float* record, int bins) { return CeVariant{w, 0.f, 0.f, kLovasz, nullptr, record, bins}; }
+    const uint32_t* mask = nullptr;     // kRelaxed: one class-set word per pixel (dsrl_relax_mask, or any words: the consumers clean them with relax_set)
+    static CeVariant relaxed(const float* w, const uint32_t* mask) {
+        CeVariant v{w, 0.f, 0.f, kRelaxed};
+        v.mask = mask;
+        return v;
+    }
     bool plain() const { return kind == kPlain; }
-    bool table_ok() const { return plain() || weights != nullptr; }         // part of every entry point's argument check
+    int max_classes() const { return kind == kRelaxed ? 32 : 60; }          // a class set is one 32-bit word
+    bool table_ok() const { return plain() || (weights != nullptr && (kind != kRelaxed || mask != nullptr)); }   // part of every entry point's argument check
     const char* suffix() const {        // of the entry point, for its messages
-        return plain() ? "" : kind == kWeighted ? "_w" : kind == kFocal ? "_f" : kind == kSmoothed ? "_s" : kind == kDice ? "_d" : "_l";
+        return plain() ? "" : kind == kWeighted ? "_w" : kind == kFocal ? "_f" : kind == kSmoothed ? "_s" : kind == kDice ? "_d" : kind == kLovasz ? "_l" : "_r";
     }
 };
 // losses.hip, for the ConvTranspose forms in spatial.hip: the pre-pass of every kind but plain (D = sum n_c w_c into d_out, through `ws` of
@@ -248,6 +255,45 @@ __device__ __forceinline__ void lovasz_pixel(const float* e, int C, float s, int
     dot = d;
 }
 __device__ __forceinline__ float lovasz_grad(float e, float inv_s, float g_c, float dot, bool live) { return live ? (e * inv_s) * (g_c - dot) : 0.f; }
+
+// ---------------------------------------------------------------- boundary label relaxation (relax.hip), the arithmetic of one live pixel
+// The loss of a pixel asks for the probability of a SET of classes S (the classes of the labels around it, dsrl_relax_mask) instead of one label:
+//     term = w[t] ((m + log s) - (m_S + log z)) = -w[t] log sum_{c in S} p_c,      d loss / d v_c = (w[t] / D) (e_c / s - g_c / z)
+//     m_S = max_{c in S} v_c,   g_c = [c in S] exp_nonpos(v_c - m_S),   z = sum_{c in S} g_c (c ascending)
+// The set softmax is taken relative to its OWN maximum: a set whose logits all lie 87 below the largest one has e_c = 0 for every member, and a
+// -log(sum_S e_c / s) on the shared terms would be infinite where plain CE is about 100.
+// relax_set is the one place a mask word becomes a set: bits of classes that do not exist are dropped and the pixel's own label is added, so no
+// caller-supplied word can drop the label or name a class >= C (a label >= C has no bit: its weight is 0 and the entry point poisons the loss).
+// relax_pixel gets the pixel's C raw logits `v`, m = max_c v_c, s = sum_c exp_nonpos(v_c - m) (c ascending) and sc = w[t] (1 / D) and gives m_S,
+// inv = sc / s, invz = sc / z and (VAL builds) the fp32 term without its weight; relax_grad is one element of the row, e inv - g invz, with g
+// recomputed from the logit (the second exp_nonpos of a logit has the bits of the first).  A member equal to m_S takes the argument 0 whatever its
+// value, so that a set whose maximum is -inf has g = 1 there instead of exp(-inf + inf).  For S = {t}: m_S = v_t, g_t = exp_nonpos(0) = 1, z = 1,
+// log z = 0, invz = sc: the term is (m + log s) - v_t and the row e_c (sc / s) - [c == t] sc - the operations and the bits of the weighted form.
+// CT > 0: the class count at compile time (loops unrolled); CT == 0: `C` at run time.  Every relaxed kernel (losses.hip, spatial.hip, convt_dma.hip)
+// goes through these functions, so that the fused and the unfused paths round alike (the library is built with -ffp-contract=off).
+constexpr int kRelaxMaxC = 32, kRelaxMaxRadius = 4;
+__host__ __device__ __forceinline__ unsigned relax_set(unsigned word, int tg, int C) {
+    const unsigned all = C >= 32 ? 0xffffffffu : (1u << C) - 1u;
+    return (word & all) | ((tg >= 0 && tg < C) ? 1u << tg : 0u);
+}
+__device__ __forceinline__ float relax_arg(float vc, float mS) { return vc == mS ? 0.f : vc - mS; }
+template <int CT, bool VAL>
+__device__ __forceinline__ void relax_pixel(const float* v, int C, unsigned S, float m, float s, float sc, float& mS, float& inv, float& invz, float& term) {
+    const int n = CT > 0 ? CT : C;
+    float ms = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < n; ++c) ms = ((S >> c) & 1u) ? fmaxf(ms, v[c]) : ms;
+    float z = 0.f;
+#pragma unroll
+    for (int c = 0; c < n; ++c) z += ((S >> c) & 1u) ? exp_nonpos(relax_arg(v[c], ms)) : 0.f;
+    mS = ms;
+    inv = sc / s;
+    invz = sc / z;
+    term = VAL ? (m + logf(s)) - (ms + logf(z)) : 0.f;
+}
+__device__ __forceinline__ float relax_grad(float e, float inv, bool in_set, float vc, float mS, float invz) {
+    return e * inv - (in_set ? exp_nonpos(relax_arg(vc, mS)) * invz : 0.f);
+}
 
 // ---------------------------------------------------------------- exponential moving average of the weights (ema.hip)
 // The EMA record in device memory (16 bytes, 16-byte aligned).  omd = 1 - d_t of the update ABOUT to run; dsrl_ema_advance rewrites it once per step.

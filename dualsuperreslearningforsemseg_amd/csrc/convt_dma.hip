@@ -52,7 +52,12 @@ struct ConvtCeLovaszArgs : ConvtCeArgs {
     const float* lovasz;            // the record of dsrl_lovasz_fwd {lambda L, |Present|, 0, 0, gf[CO][bins], gb[CO][bins]}
     int bins;                       // K, a power of two in [16, 4096]
 };
-template <bool DC, bool LV> using ConvtCeArgsOf = std::conditional_t<DC, ConvtCeDiceArgs, std::conditional_t<LV, ConvtCeLovaszArgs, ConvtCeArgs>>;
+// and of the RX build
+struct ConvtCeRelaxArgs : ConvtCeArgs {
+    const unsigned* mask;           // (N, 2H, 2W) class-set words (dsrl_relax_mask, or any words: relax_set cleans them)
+};
+template <bool DC, bool LV, bool RX = false>
+using ConvtCeArgsOf = std::conditional_t<DC, ConvtCeDiceArgs, std::conditional_t<LV, ConvtCeLovaszArgs, std::conditional_t<RX, ConvtCeRelaxArgs, ConvtCeArgs>>>;
 
 // CW = true (dsrl_convt2x2_bwd_ce_w): nn.CrossEntropyLoss(weight=).  ce.count points to D = sum n_c w_c and the only change is in transform(): the
 // per-pixel sc = wtab[target] * (1 / D) stands where `scale` stands, as in ce_fused_body<true> (losses.hip).  The 256-float table sits in LDS, already
@@ -72,15 +77,20 @@ template <bool DC, bool LV> using ConvtCeArgsOf = std::conditional_t<DC, ConvtCe
 // 19 classes and 1024 levels) do not fit LDS beside the ring: lovasz_pixel (common.h) gathers the 19 coefficients of a pixel from global memory /
 // L2 with the e_c in registers and keeps them there, the row is (weighted CE row) + (Lovasz row) through lovasz_grad, and the transformer's g * w is
 // added after that: the order and the roundings of dsrl_ce_fused_w -> dsrl_lovasz_bwd(accumulate = 1) -> dsrl_pointwise_strided_bwd.
-template <int CI, int CO, bool CE, bool TW = false, bool CW = false, bool FL = false, bool SM = false, bool DC = false, bool LV = false>
+// RX = true (dsrl_convt2x2_bwd_ce_r): boundary label relaxation.  The label bytes arrive through the ring as ever; the pixel's
+// class-set word is fetched from global memory at the top of transform(), where the transformer's gradient is fetched, so that the softmax covers its
+// latency.  The row is relax_pixel / relax_grad (common.h) on the e_c in registers and the raw logits still in the stage, as
+// ce_fused_body<true, false, false, true> forms it from its tile: m_S, inv, invz and the set word beside the 19 terms, g_c recomputed per class.
+template <int CI, int CO, bool CE, bool TW = false, bool CW = false, bool FL = false, bool SM = false, bool DC = false, bool LV = false, bool RX = false>
 __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ dy,
                                                                  float* __restrict__ dx, float* __restrict__ part, int N, int H, int W,
-                                                                 int nseg_per_row, int nseg, ConvtCeArgsOf<DC, LV> ce) {
+                                                                 int nseg_per_row, int nseg, ConvtCeArgsOf<DC, LV, RX> ce) {
     static_assert(CE || !CW, "class weights belong to the CE build");
     static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
     static_assert(!SM || (CW && !FL), "label smoothing runs on the weighted machinery and has no focal form");
     static_assert(!DC || (CW && !FL && !SM && !TW && CO <= 32), "the Dice term runs on the weighted machinery, in the 8-wave build");
     static_assert(!LV || (CW && !FL && !SM && !TW && !DC), "the Lovasz term runs on the weighted machinery, in the 8-wave build");
+    static_assert(!RX || (CW && !FL && !SM && !TW && !DC && !LV && CO <= kRelaxMaxC), "label relaxation runs on the weighted machinery, in the 8-wave build");
     constexpr int TP = 128, COLS = 4 * CO, NK = COLS / 2, NJ = (COLS + 31) / 32, NOUT = CI * COLS;
     constexpr int XB = TP * CI * 4, XP = (XB + 1023) / 1024;               // bytes / 1 KB pieces of an x segment
     constexpr int GB = 2 * TP * CO * 4, GP = GB / 1024;                    // of one dy row segment
@@ -159,6 +169,13 @@ __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(con
 #pragma unroll
         for (int u = 0; u < (TW ? 2 : 1); ++u) { gft[u] = 0.f; gon[u] = false; }
         bool any_grid = false;
+        unsigned mword = 0u;                                                // RX: the class-set word of this lane's pixel, requested before anything else
+        if constexpr (RX) {
+            const int row = seg / nseg_per_row;
+            const int w0 = (seg - row * nseg_per_row) * TP;
+            const int n = row / H, h = row - n * H;
+            mword = ce.mask[(long long)(n * 2 * H + 2 * h + r) * (2 * W) + 2 * w0 + wq * 64 + lane];
+        }
         if (ce.ft_g && r == 0) {
             const int row = seg / nseg_per_row;
             const int w0 = (seg - row * nseg_per_row) * TP;
@@ -230,6 +247,14 @@ __global__ __launch_bounds__(TW ? 768 : 512, 1) void convt2x2_bwd_dma_kernel(con
                     const float inv = sc / s;
 #pragma unroll
                     for (int c = 0; c < CO; ++c) e[c] = live ? (e[c] * inv - (c == tg ? sc : 0.f)) + lovasz_grad(e[c], inv_s, g[c], dot, llive) : 0.f;
+                }
+            } else if (RX) {
+                if constexpr (RX) {
+                    const unsigned S = relax_set(mword, tg, CO);
+                    float mS, inv, invz, term;
+                    relax_pixel<CO, false>(v, CO, S, m, s, wt_s[tg], mS, inv, invz, term);
+#pragma unroll
+                    for (int c = 0; c < CO; ++c) e[c] = live ? relax_grad(e[c], inv, (S >> c) & 1u, v[c], mS, invz) : 0.f;
                 }
             } else if (CW) {
                 // sc = table[target] is per lane where `scale` is uniform: held across the 19 operations beside inv it is one VGPR more than the
@@ -418,24 +443,25 @@ bool convt_bwd_dma_supported(const void* x, const void* dy, int W, int Cin, int 
 }
 int convt_bwd_dma_blocks(long long nseg, int cap) { return (int)std::min<long long>(std::min(cap, kNumCU), nseg); }
 
-template <bool CE, bool TW, bool CW = false, bool FL = false, bool SM = false, bool DC = false, bool LV = false>
+template <bool CE, bool TW, bool CW = false, bool FL = false, bool SM = false, bool DC = false, bool LV = false, bool RX = false>
 static int launch_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, const ConvtCeArgs& ce, hipStream_t st,
-                      const float* dice = nullptr, int bins = 0) {
+                      const float* dice = nullptr, int bins = 0, const unsigned* mask = nullptr) {
     constexpr int CI = 19, CO = 19;
     constexpr int kLds = 3 * ((128 * CI * 4 + 1023) / 1024 + 2 * (2 * 128 * CO * 4 / 1024) + (CE ? 2 : 0)) * 1024;
     static_assert(kLds + (CW ? 1024 : 0) + (SM ? 128 : 0) + (DC ? 256 : 0) + 128 <= 160 * 1024,
                   "the ring, the transformer's weights, the class-weight tables and the Dice tables in LDS");
-    static const hipError_t attr = hipFuncSetAttribute((const void*)convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM, DC, LV>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+    static const hipError_t attr = hipFuncSetAttribute((const void*)convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM, DC, LV, RX>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     if (attr != hipSuccess) { set_error("convt2x2_bwd_dma_kernel: %d bytes of LDS refused (%s)", kLds, hipGetErrorString(attr)); return DSRL_E_LAUNCH; }
     const int nseg_per_row = W / 128;
     const long long nseg = (long long)N * H * nseg_per_row;
     if ((long long)N * 4 * H * W * CO * 4 >= (1ll << 32)) { set_error("convt2x2_bwd_dma_kernel: output gradient of 4 GB or more"); return DSRL_E_UNSUPPORTED; }
     if (nseg >= (1ll << 31) || nblocks < 1 || nblocks > nseg) { set_error("convt2x2_bwd_dma_kernel: %lld segments, %d blocks", nseg, nblocks); return DSRL_E_BADARG; }
-    ConvtCeArgsOf<DC, LV> args{};
+    ConvtCeArgsOf<DC, LV, RX> args{};
     static_cast<ConvtCeArgs&>(args) = ce;
     if constexpr (DC) args.dice = dice;
     if constexpr (LV) { args.lovasz = dice; args.bins = bins; }
-    hipLaunchKernelGGL((convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM, DC, LV>), dim3(nblocks), dim3(TW ? 768 : 512), kLds, st, x, w, dy, dx, part, N, H, W, nseg_per_row, (int)nseg, args);
+    if constexpr (RX) args.mask = mask;
+    hipLaunchKernelGGL((convt2x2_bwd_dma_kernel<CI, CO, CE, TW, CW, FL, SM, DC, LV, RX>), dim3(nblocks), dim3(TW ? 768 : 512), kLds, st, x, w, dy, dx, part, N, H, W, nseg_per_row, (int)nseg, args);
     return launch_status("convt2x2_bwd_dma_kernel");
 }
 int launch_convt_bwd_dma(const float* x, const float* w, const float* dy, float* dx, float* part, int N, int H, int W, int nblocks, hipStream_t st) {
@@ -461,6 +487,9 @@ int launch_convt_bwd_dma_ce(const float* x, const float* w, const float* logits,
     // Lovasz: the 8-wave build as well: 19 gathered coefficients beside the 19 terms
     if (v.kind == CeVariant::kLovasz)
         return launch_dma<true, false, true, false, false, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st, v.lovasz, v.bins);
+    // label relaxation: the 8-wave build as well: m_S, inv, invz and the set word beside the 19 terms, and a second exponential per set class
+    if (v.kind == CeVariant::kRelaxed)
+        return launch_dma<true, false, true, false, false, false, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st, nullptr, 0, v.mask);
     if (v.kind == CeVariant::kWeighted) return w8 ? launch_dma<true, false, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st)
                         : launch_dma<true, true, true>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);
     if (w8) return launch_dma<true, false>(x, w, logits, dx, part, N, H, W, nblocks, ce, st);

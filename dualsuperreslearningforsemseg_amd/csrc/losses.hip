@@ -23,11 +23,15 @@ __device__ inline double block_sum_d(double v, double* sh) {     // sh: 4 double
 // (w[t] * mod) * (1 / D), both from focal_pixel (common.h) on exp_nonpos terms; D, the flags and the staging are those of the weighted bodies.
 // SM = true (the *_s_kernel entries): label-smoothed cross entropy, a pixel's term and its gradient row come from smooth_pixel / smooth_grad (common.h),
 // which read all C logits and all C weights of the pixel; W = sum_{c < C} w_c is summed once per block, c ascending, before the pixel loop.
-template <bool CW, bool FL = false, bool SM = false>
+// RX = true (the *_r_kernel entries): boundary label relaxation: the pixel's class-set word is read beside its label byte, cleaned
+// by relax_set, and the term and the gradient row come from relax_pixel / relax_grad (common.h) on exp_nonpos terms.
+template <bool CW, bool FL = false, bool SM = false, bool RX = false>
 __device__ __forceinline__ void ce_fwd_body(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
-                                            int ignore_index, const float* __restrict__ wtab, double* __restrict__ part, float gamma = 0.f, float eps = 0.f) {
+                                            int ignore_index, const float* __restrict__ wtab, double* __restrict__ part, float gamma = 0.f, float eps = 0.f,
+                                            const unsigned* __restrict__ mask = nullptr) {
     static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
     static_assert(!SM || (CW && !FL), "label smoothing runs on the weighted machinery and has no focal form");
+    static_assert(!RX || (CW && !FL && !SM), "label relaxation runs on the weighted machinery alone");
     extern __shared__ float tile[];         // [256][C]
     __shared__ double shd[4];
     double loss = 0.0, cnt = 0.0;
@@ -50,6 +54,12 @@ __device__ __forceinline__ void ce_fwd_body(const float* __restrict__ logits, in
                     double val; float sub_t, inv;
                     smooth_pixel<true>(v, wtab, C, tg, m, s, eps, Wsum, 0.f, val, sub_t, inv);
                     loss += tg < C ? val : __builtin_nan("");
+                } else if (RX) {
+                    float s = 0.f;
+                    for (int c = 0; c < C; ++c) s += exp_nonpos(v[c] - m);
+                    float mS, inv, invz, term;
+                    relax_pixel<0, true>(v, C, relax_set(mask[p0 + threadIdx.x], tg, C), m, s, 0.f, mS, inv, invz, term);
+                    loss += (double)wtab[tg] * (double)(tg < C ? term : __builtin_nanf(""));
                 } else if (FL) {
                     float s = 0.f, so = 0.f;
                     for (int c = 0; c < C; ++c) { const float e = exp_nonpos(v[c] - m); s += e; so += c == tg ? 0.f : e; }
@@ -89,6 +99,11 @@ __global__ __launch_bounds__(256) void ce_fwd_s_kernel(const float* __restrict__
                                                         int ignore_index, const float* __restrict__ wtab, float eps, double* __restrict__ part) {
     ce_fwd_body<true, false, true>(logits, ld, target, P, C, ignore_index, wtab, part, 0.f, eps);
 }
+__global__ __launch_bounds__(256) void ce_fwd_r_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                        int ignore_index, const float* __restrict__ wtab, const unsigned* __restrict__ mask,
+                                                        double* __restrict__ part) {
+    ce_fwd_body<true, false, false, true>(logits, ld, target, P, C, ignore_index, wtab, part, 0.f, 0.f, mask);
+}
 __global__ __launch_bounds__(256) void ce_finalize_kernel(const double* __restrict__ part, int nb, float* __restrict__ out) {
     __shared__ double shd[4];
     double l = 0, n = 0;
@@ -107,12 +122,14 @@ __global__ __launch_bounds__(256) void ce_finalize_w_kernel(const double* __rest
     l = block_sum_d(l, shd);
     if (threadIdx.x == 0) out[0] = (float)(l / (double)out[1]);
 }
-template <bool CW, bool FL = false, bool SM = false>
+template <bool CW, bool FL = false, bool SM = false, bool RX = false>
 __device__ __forceinline__ void ce_bwd_body(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
                                             int ignore_index, const float* __restrict__ wtab, const float* __restrict__ loss_out,
-                                            const float* __restrict__ grad_out, float* __restrict__ dl, int lddl, float gamma = 0.f, float eps = 0.f) {
+                                            const float* __restrict__ grad_out, float* __restrict__ dl, int lddl, float gamma = 0.f, float eps = 0.f,
+                                            const unsigned* __restrict__ mask = nullptr) {
     static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
     static_assert(!SM || (CW && !FL), "label smoothing runs on the weighted machinery and has no focal form");
+    static_assert(!RX || (CW && !FL && !SM), "label relaxation runs on the weighted machinery alone");
     extern __shared__ float tile[];
     const float scale = grad_out[0] / loss_out[1];
     float Wsum = 0.f;
@@ -139,6 +156,14 @@ __device__ __forceinline__ void ce_bwd_body(const float* __restrict__ logits, in
                     double val; float sub_t, inv;
                     smooth_pixel<false>(v, wtab, C, tg, m, s, eps, Wsum, scale, val, sub_t, inv);
                     for (int c = 0; c < C; ++c) v[c] = bad ? __builtin_nanf("") : smooth_grad(exp_nonpos(v[c] - m), inv, c == tg, sub_t, sub_s[c]);
+                } else if (RX) {
+                    float s = 0.f;
+                    for (int c = 0; c < C; ++c) s += exp_nonpos(v[c] - m);
+                    const unsigned S = relax_set(mask[p0 + threadIdx.x], tg, C);
+                    float mS, inv, invz, term;
+                    relax_pixel<0, false>(v, C, S, m, s, wtab[tg] * scale, mS, inv, invz, term);
+                    for (int c = 0; c < C; ++c)
+                        v[c] = bad ? __builtin_nanf("") : relax_grad(exp_nonpos(v[c] - m), inv, (S >> c) & 1u, v[c], mS, invz);
                 } else if (FL) {
                     const float vt = v[min(tg, C - 1)];
                     float s = 0.f, so = 0.f;
@@ -182,6 +207,11 @@ __global__ __launch_bounds__(256) void ce_bwd_s_kernel(const float* __restrict__
                                                         int ignore_index, const float* __restrict__ wtab, float eps, const float* __restrict__ loss_out,
                                                         const float* __restrict__ grad_out, float* __restrict__ dl, int lddl) {
     ce_bwd_body<true, false, true>(logits, ld, target, P, C, ignore_index, wtab, loss_out, grad_out, dl, lddl, 0.f, eps);
+}
+__global__ __launch_bounds__(256) void ce_bwd_r_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                        int ignore_index, const float* __restrict__ wtab, const unsigned* __restrict__ mask,
+                                                        const float* __restrict__ loss_out, const float* __restrict__ grad_out, float* __restrict__ dl, int lddl) {
+    ce_bwd_body<true, false, false, true>(logits, ld, target, P, C, ignore_index, wtab, loss_out, grad_out, dl, lddl, 0.f, 0.f, mask);
 }
 
 // ---------------------------------------------------------------------------------------------- fused loss pass
@@ -267,14 +297,15 @@ __global__ __launch_bounds__(256) void ce_weight_sum_kernel(const unsigned* __re
     }
 }
 
-template <bool CW, bool FL = false, bool SM = false>
+template <bool CW, bool FL = false, bool SM = false, bool RX = false>
 __device__ __forceinline__ void ce_fused_body(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
                                               int ignore_index, const unsigned* __restrict__ cnt_part, const float* __restrict__ wtab,
                                               const float* __restrict__ wsum, float* __restrict__ dl, int lddl,
                                               double* __restrict__ part, int* __restrict__ nan_flag, int vec_in, int vec_out, float gamma = 0.f,
-                                              float eps = 0.f) {
+                                              float eps = 0.f, const unsigned* __restrict__ mask = nullptr) {
     static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
     static_assert(!SM || (CW && !FL), "label smoothing runs on the weighted machinery and has no focal form");
+    static_assert(!RX || (CW && !FL && !SM), "label relaxation runs on the weighted machinery alone");
     extern __shared__ __attribute__((aligned(16))) float tile[];         // [256][C]
     __shared__ double shd[4];
     __shared__ float sh_scale;
@@ -313,7 +344,7 @@ __device__ __forceinline__ void ce_fused_body(const float* __restrict__ logits, 
             for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
             const float vt = v[max(min(tg == ignore_index ? 0 : tg, C - 1), 0)];
             float s = 0.f, so = 0.f;
-            if (SM) {                           // the tile keeps the logits: smooth_pixel reads every one of them once s is known
+            if (SM || RX) {                     // the tile keeps the logits: smooth_pixel / relax_pixel read them once s is known
                 for (int c = 0; c < C; ++c) s += exp_nonpos(v[c] - m);
             } else if (FL) {                    // so: the sum without the target's term, in the same order
                 for (int c = 0; c < C; ++c) { const float e = exp_nonpos(v[c] - m); s += e; so += c == tg ? 0.f : e; v[c] = e; }
@@ -329,6 +360,18 @@ __device__ __forceinline__ void ce_fused_body(const float* __restrict__ logits, 
                     cnt += 1.0;
                     // the second exp_nonpos of a logit has the bits of the first: the row equals the one convt2x2_bwd_dma_kernel forms from registers
                     if (dl) for (int c = 0; c < C; ++c) v[c] = smooth_grad(exp_nonpos(v[c] - m), inv, c == tg, sub_t, sub_s[c]);
+                } else if (dl) {
+                    for (int c = 0; c < C; ++c) v[c] = 0.f;
+                }
+            } else if (RX) {
+                if (tg != ignore_index) {
+                    const unsigned S = relax_set(mask[p0 + threadIdx.x], tg, C);
+                    float mS, inv, invz, term;
+                    const float wt = wtab[tg];
+                    relax_pixel<0, true>(v, C, S, m, s, wt * scale, mS, inv, invz, term);
+                    loss += (double)wt * (double)term;
+                    cnt += 1.0;
+                    if (dl) for (int c = 0; c < C; ++c) v[c] = relax_grad(exp_nonpos(v[c] - m), inv, (S >> c) & 1u, v[c], mS, invz);
                 } else if (dl) {
                     for (int c = 0; c < C; ++c) v[c] = 0.f;
                 }
@@ -392,6 +435,12 @@ __global__ __launch_bounds__(256) void ce_fused_s_kernel(const float* __restrict
                                                           float* __restrict__ dl, int lddl, double* __restrict__ part, int* __restrict__ nan_flag,
                                                           int vec_in, int vec_out) {
     ce_fused_body<true, false, true>(logits, ld, target, P, C, ignore_index, nullptr, wtab, wsum, dl, lddl, part, nan_flag, vec_in, vec_out, 0.f, eps);
+}
+__global__ __launch_bounds__(256) void ce_fused_r_kernel(const float* __restrict__ logits, int ld, const unsigned char* __restrict__ target, long long P, int C,
+                                                          int ignore_index, const float* __restrict__ wtab, const unsigned* __restrict__ mask,
+                                                          const float* __restrict__ wsum, float* __restrict__ dl, int lddl, double* __restrict__ part,
+                                                          int* __restrict__ nan_flag, int vec_in, int vec_out) {
+    ce_fused_body<true, false, false, true>(logits, ld, target, P, C, ignore_index, nullptr, wtab, wsum, dl, lddl, part, nan_flag, vec_in, vec_out, 0.f, 0.f, mask);
 }
 // MSE forward and backward in one pass: partial sums of (a-b)^2 and da = (a-b) * 2 * grad_scale / n; NaN check of `a`
 __global__ __launch_bounds__(256) void mse_fused_kernel(const float* __restrict__ a, const float* __restrict__ b, long long n, float sc, float* __restrict__ da,
@@ -972,15 +1021,17 @@ extern "C" size_t dsrl_ce_workspace_bytes(int64_t P) { return ce_ws_bytes(P, tru
 extern "C" size_t dsrl_ce_w_workspace_bytes(int64_t P) { return ce_ws_bytes(P, false); }
 extern "C" size_t dsrl_ce_f_workspace_bytes(int64_t P) { return ce_ws_bytes(P, false); }
 extern "C" size_t dsrl_ce_s_workspace_bytes(int64_t P) { return ce_ws_bytes(P, false); }
+extern "C" size_t dsrl_ce_r_workspace_bytes(int64_t P) { return ce_ws_bytes(P, false); }
 extern "C" size_t dsrl_ce_fused_workspace_bytes(int64_t P) { return ce_fused_ws_bytes(P, true); }
 extern "C" size_t dsrl_ce_fused_w_workspace_bytes(int64_t P) { return ce_fused_ws_bytes(P, false); }
 extern "C" size_t dsrl_ce_fused_f_workspace_bytes(int64_t P) { return ce_fused_ws_bytes(P, false); }
 extern "C" size_t dsrl_ce_fused_s_workspace_bytes(int64_t P) { return ce_fused_ws_bytes(P, false); }
+extern "C" size_t dsrl_ce_fused_r_workspace_bytes(int64_t P) { return ce_fused_ws_bytes(P, false); }
 
 static int ce_fwd_any(const CeVariant& v, const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float* loss_out,
                       void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     const char* sfx = v.suffix();
-    DSRL_REQUIRE(logits && target && v.table_ok() && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C, DSRL_E_BADARG,
+    DSRL_REQUIRE(logits && target && v.table_ok() && loss_out && ws && P > 0 && C > 0 && C <= v.max_classes() && ld >= C, DSRL_E_BADARG,
                  "ce_fwd%s: bad arguments (C=%d)", sfx, C);
     if (v.plain()) DSRL_REQUIRE(ws_bytes >= ce_ws_bytes(P, true), DSRL_E_WORKSPACE, "ce_fwd: workspace too small");
     else DSRL_REQUIRE(ws_bytes >= ce_ws_bytes(P, false) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fwd%s: workspace too small or misaligned", sfx);
@@ -997,14 +1048,16 @@ static int ce_fwd_any(const CeVariant& v, const float* logits, int ld, const uin
     case CeVariant::kWeighted: hipLaunchKernelGGL(ce_fwd_w_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, part); break;
     case CeVariant::kFocal: hipLaunchKernelGGL(ce_fwd_f_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, v.gamma, part); break;
     case CeVariant::kSmoothed: hipLaunchKernelGGL(ce_fwd_s_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, v.eps, part); break;
+    case CeVariant::kRelaxed: hipLaunchKernelGGL(ce_fwd_r_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, v.mask, part); break;
+    default: break;         // (kDice, kLovasz: no entry point of this family makes them)
     }
-    static const char* const kernel[] = {"ce_fwd_kernel", "ce_fwd_w_kernel", "ce_fwd_f_kernel", "ce_fwd_s_kernel"};
+    static const char* const kernel[] = {"ce_fwd_kernel", "ce_fwd_w_kernel", "ce_fwd_f_kernel", "ce_fwd_s_kernel", "", "", "ce_fwd_r_kernel"};
     if (int e = launch_status(kernel[v.kind])) return e;
     return launch_ce_finalize(v.kind, part, nb, loss_out, st);
 }
 static int ce_bwd_any(const CeVariant& v, const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* loss_out,
                       const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
-    DSRL_REQUIRE(logits && target && v.table_ok() && loss_out && grad_out && dlogits && P > 0 && C > 0 && C <= 60 && ld >= C && lddl >= C, DSRL_E_BADARG,
+    DSRL_REQUIRE(logits && target && v.table_ok() && loss_out && grad_out && dlogits && P > 0 && C > 0 && C <= v.max_classes() && ld >= C && lddl >= C, DSRL_E_BADARG,
                  "ce_bwd%s: bad arguments", v.suffix());
     hipStream_t st = (hipStream_t)stream;
     if (int e = bind_stream_device(st)) return e;
@@ -1025,14 +1078,19 @@ static int ce_bwd_any(const CeVariant& v, const float* logits, int ld, const uin
         hipLaunchKernelGGL(ce_bwd_s_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, v.eps, loss_out, grad_out,
                            dlogits, lddl);
         break;
+    case CeVariant::kRelaxed:
+        hipLaunchKernelGGL(ce_bwd_r_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, v.mask, loss_out, grad_out,
+                           dlogits, lddl);
+        break;
+    default: break;
     }
-    static const char* const kernel[] = {"ce_bwd_kernel", "ce_bwd_w_kernel", "ce_bwd_f_kernel", "ce_bwd_s_kernel"};
+    static const char* const kernel[] = {"ce_bwd_kernel", "ce_bwd_w_kernel", "ce_bwd_f_kernel", "ce_bwd_s_kernel", "", "", "ce_bwd_r_kernel"};
     return launch_status(kernel[v.kind]);
 }
 static int ce_fused_any(const CeVariant& v, const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float* dlogits, int lddl,
                         float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     const char* sfx = v.suffix();
-    DSRL_REQUIRE(logits && target && v.table_ok() && loss_out && ws && P > 0 && C > 0 && C <= 60 && ld >= C && (!dlogits || lddl >= C), DSRL_E_BADARG,
+    DSRL_REQUIRE(logits && target && v.table_ok() && loss_out && ws && P > 0 && C > 0 && C <= v.max_classes() && ld >= C && (!dlogits || lddl >= C), DSRL_E_BADARG,
                  "ce_fused%s: bad arguments (C=%d)", sfx, C);
     DSRL_REQUIRE(ws_bytes >= ce_fused_ws_bytes(P, v.plain()) && ((uintptr_t)ws % 8) == 0, DSRL_E_WORKSPACE, "ce_fused%s: workspace too small or misaligned", sfx);
     hipStream_t st = (hipStream_t)stream;
@@ -1066,8 +1124,13 @@ static int ce_fused_any(const CeVariant& v, const float* logits, int ld, const u
         hipLaunchKernelGGL(ce_fused_s_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, v.eps, wsum, dlogits, lddl,
                            part, nan_flag, vec_in, vec_out);
         break;
+    case CeVariant::kRelaxed:
+        hipLaunchKernelGGL(ce_fused_r_kernel, grid, block, lds, st, logits, ld, target, (long long)P, C, ignore_index, v.weights, v.mask, wsum, dlogits, lddl,
+                           part, nan_flag, vec_in, vec_out);
+        break;
+    default: break;
     }
-    static const char* const kernel[] = {"ce_fused_kernel", "ce_fused_w_kernel", "ce_fused_f_kernel", "ce_fused_s_kernel"};
+    static const char* const kernel[] = {"ce_fused_kernel", "ce_fused_w_kernel", "ce_fused_f_kernel", "ce_fused_s_kernel", "", "", "ce_fused_r_kernel"};
     if (int e = launch_status(kernel[v.kind])) return e;
     return launch_ce_finalize(v.kind, part, nb, loss_out, st);
 }
@@ -1091,6 +1154,10 @@ extern "C" int dsrl_ce_fwd_s(const float* logits, int ld, const uint8_t* target,
     DSRL_LABEL_SMOOTHING(eps, "ce_fwd_s");
     return ce_fwd_any(CeVariant::smoothed(weights, eps), logits, ld, target, P, C, ignore_index, loss_out, ws, ws_bytes, stream);
 }
+extern "C" int dsrl_ce_fwd_r(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, const uint32_t* mask,
+                             float* loss_out, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    return ce_fwd_any(CeVariant::relaxed(weights, mask), logits, ld, target, P, C, ignore_index, loss_out, ws, ws_bytes, stream);
+}
 extern "C" int dsrl_ce_bwd(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* loss_out,
                            const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
     return ce_bwd_any(CeVariant{}, logits, ld, target, P, C, ignore_index, loss_out, grad_out, dlogits, lddl, stream);
@@ -1109,6 +1176,10 @@ extern "C" int dsrl_ce_bwd_s(const float* logits, int ld, const uint8_t* target,
     DSRL_LABEL_SMOOTHING(eps, "ce_bwd_s");
     return ce_bwd_any(CeVariant::smoothed(weights, eps), logits, ld, target, P, C, ignore_index, loss_out, grad_out, dlogits, lddl, stream);
 }
+extern "C" int dsrl_ce_bwd_r(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, const uint32_t* mask,
+                             const float* loss_out, const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream) {
+    return ce_bwd_any(CeVariant::relaxed(weights, mask), logits, ld, target, P, C, ignore_index, loss_out, grad_out, dlogits, lddl, stream);
+}
 extern "C" int dsrl_ce_fused(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, float* dlogits, int lddl,
                              float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     return ce_fused_any(CeVariant{}, logits, ld, target, P, C, ignore_index, dlogits, lddl, loss_out, nan_flag, ws, ws_bytes, stream);
@@ -1126,6 +1197,10 @@ extern "C" int dsrl_ce_fused_s(const float* logits, int ld, const uint8_t* targe
                                float* dlogits, int lddl, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     DSRL_LABEL_SMOOTHING(eps, "ce_fused_s");
     return ce_fused_any(CeVariant::smoothed(weights, eps), logits, ld, target, P, C, ignore_index, dlogits, lddl, loss_out, nan_flag, ws, ws_bytes, stream);
+}
+extern "C" int dsrl_ce_fused_r(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights, const uint32_t* mask,
+                               float* dlogits, int lddl, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    return ce_fused_any(CeVariant::relaxed(weights, mask), logits, ld, target, P, C, ignore_index, dlogits, lddl, loss_out, nan_flag, ws, ws_bytes, stream);
 }
 
 extern "C" int dsrl_class_histogram(const uint8_t* labels, int64_t P, const uint8_t* lut, unsigned long long* counts, dsrl_stream_t stream) {

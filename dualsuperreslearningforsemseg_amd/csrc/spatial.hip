@@ -3,6 +3,7 @@
 // transformers and the NCHW->pixel-major import.  Consecutive lanes always touch consecutive channels / pixels.
 #include "common.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace dsrl {
 
@@ -388,6 +389,8 @@ __global__ __launch_bounds__(256) void convt2x2_fwd_kernel(const float* __restri
 // [0, CO) -> NaN loss + flag bit 1) while the tile is being stored: the 319 MB read of a loss pass of its own disappears.  Per-block partials
 // (sum of the pixel losses, number of pixels that count) as two doubles in ce.part; ce_finalize_kernel merges them.
 struct ConvtFwdCe { const unsigned char* target; double* part; int* nan_flag; int ignore_index; const float* wtab; float gamma; float eps; };
+// the arguments of the RLX build: a type of its own, so that the kernel arguments of every other instantiation keep their size and offsets
+struct ConvtFwdCeRelax : ConvtFwdCe { const unsigned* mask; };
 using f32x16_f = __attribute__((ext_vector_type(16))) float;
 // CW = true (dsrl_convt2x2_fwd_ce_w): nn.CrossEntropyLoss(weight=): a pixel's term is (double)ce.wtab[target] * (double)nll, wtab the 256-float
 // class-weight table (ce_fwd_body in losses.hip).  A template parameter, so that the CW = false instantiations compile to the code they were.
@@ -395,12 +398,16 @@ using f32x16_f = __attribute__((ext_vector_type(16))) float;
 // more pass over the pixel's 19 words in LDS for the sum without the target's term.
 // SM = true (dsrl_convt2x2_fwd_ce_s): label-smoothed cross entropy, the term comes from smooth_pixel (common.h), which reads the pixel's 19 words in LDS
 // once more and all 19 weights; W = sum_c w_c is summed once per block.
-template <int CI, int CO, bool CE = false, bool CW = false, bool FL = false, bool SM = false>
+// RLX = true (dsrl_convt2x2_fwd_ce_r): boundary label relaxation: the pixel's class-set word is read beside its label byte and the
+// term comes from relax_pixel (common.h), which reads the pixel's 19 words in LDS once more for the set's own maximum and sum.
+template <int CI, int CO, bool CE = false, bool CW = false, bool FL = false, bool SM = false, bool RLX = false>
 __global__ __launch_bounds__(256, 2) void convt2x2_fwd_mfma_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                                 float* __restrict__ y, int N, int H, int W, int nseg_per_row, int nseg, ConvtFwdCe ce) {
+                                                                 float* __restrict__ y, int N, int H, int W, int nseg_per_row, int nseg,
+                                                                 std::conditional_t<RLX, ConvtFwdCeRelax, ConvtFwdCe> ce) {
     static_assert(CE || !CW, "class weights belong to the CE build");
     static_assert(!FL || CW, "the focal loss runs on the weighted machinery");
     static_assert(!SM || (CW && !FL), "label smoothing runs on the weighted machinery and has no focal form");
+    static_assert(!RLX || (CW && !FL && !SM && CO <= kRelaxMaxC), "label relaxation runs on the weighted machinery alone");
     constexpr int TP = 128, COLS = 4 * CO, GS = COLS + 1, NK = (CI + 2) / 2, XS = 2 * NK, NJ = (COLS + 31) / 32;
     static_assert(CI + 1 <= XS && NJ <= 3 && (TP * CI) % 4 == 0 && (2 * TP * CO) % 4 == 0, "tile does not fit");
     constexpr int XV = TP * CI / 4, DV = 2 * TP * CO / 4;                   // float4 per x segment / per output row segment
@@ -485,7 +492,10 @@ __global__ __launch_bounds__(256, 2) void convt2x2_fwd_mfma_kernel(const float* 
             for (int u = 0; u < 2; ++u) {
                 const int o = tid + 256 * u, px = o >> 2, tap = o & 3;             // output pixel (2h + (tap >> 1), 2 (w0 + px) + (tap & 1))
                 if (px >= npx) continue;
-                const int tg = ce.target[((long long)(n * 2 * H + 2 * h + (tap >> 1))) * (2 * W) + 2 * (w0 + px) + (tap & 1)];
+                const long long opix = ((long long)(n * 2 * H + 2 * h + (tap >> 1))) * (2 * W) + 2 * (w0 + px) + (tap & 1);
+                const int tg = ce.target[opix];
+                unsigned mword = 0u;
+                if constexpr (RLX) mword = ce.mask[opix];
                 const float* v = buf + px * GS + tap * CO;
                 ce_bad_label |= tg != ce.ignore_index && tg >= CO;
                 float m = v[0];
@@ -501,6 +511,11 @@ __global__ __launch_bounds__(256, 2) void convt2x2_fwd_mfma_kernel(const float* 
                         double val; float sub_t, inv;
                         smooth_pixel<true>(v, ce.wtab, CO, tg, m, sum, ce.eps, Wsum, 0.f, val, sub_t, inv);
                         ce_loss += val;
+                    }
+                    else if (RLX) {
+                        float mS, inv, invz, term;
+                        relax_pixel<CO, true>(v, CO, relax_set(mword, tg, CO), m, sum, 0.f, mS, inv, invz, term);
+                        ce_loss += (double)ce.wtab[tg] * (double)term;
                     }
                     else if (FL) {
                         float so = 0.f, fl, mod;
@@ -1279,6 +1294,7 @@ extern "C" size_t dsrl_convt2x2_fwd_ce_workspace_bytes(int N, int H, int W) {
 extern "C" size_t dsrl_convt2x2_fwd_ce_w_workspace_bytes(int N, int H, int W) { return dsrl_convt2x2_fwd_ce_workspace_bytes(N, H, W) + ce_weight_sum_bytes(); }
 extern "C" size_t dsrl_convt2x2_fwd_ce_f_workspace_bytes(int N, int H, int W) { return dsrl_convt2x2_fwd_ce_w_workspace_bytes(N, H, W); }
 extern "C" size_t dsrl_convt2x2_fwd_ce_s_workspace_bytes(int N, int H, int W) { return dsrl_convt2x2_fwd_ce_w_workspace_bytes(N, H, W); }
+extern "C" size_t dsrl_convt2x2_fwd_ce_r_workspace_bytes(int N, int H, int W) { return dsrl_convt2x2_fwd_ce_w_workspace_bytes(N, H, W); }
 // the one host body of dsrl_convt2x2_fwd_ce, _w, _f and _s (CeVariant, common.h: focal and smoothed are the weighted form plus gamma or eps)
 static int convt_fwd_ce_any(const CeVariant& v, const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
                             const uint8_t* target, int ignore_index, float* loss_out, int* nan_flag, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
@@ -1304,6 +1320,14 @@ static int convt_fwd_ce_any(const CeVariant& v, const float* x, const float* w, 
     case CeVariant::kWeighted: hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true, true>), grid, block, 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce); break;
     case CeVariant::kFocal: hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true, true, true>), grid, block, 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce); break;
     case CeVariant::kSmoothed: hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true, true, false, true>), grid, block, 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, ce); break;
+    case CeVariant::kRelaxed: {
+        ConvtFwdCeRelax cer{};
+        static_cast<ConvtFwdCe&>(cer) = ce;
+        cer.mask = v.mask;
+        hipLaunchKernelGGL((convt2x2_fwd_mfma_kernel<19, 19, true, true, false, false, true>), grid, block, 0, st, x, w, bias, y, N, H, W, nseg_per_row, (int)nseg, cer);
+        break;
+    }
+    default: break;         // (kDice, kLovasz: forward values of their own kernels)
     }
     if (int e = launch_status("convt2x2_fwd_mfma_kernel")) return e;
     return launch_ce_finalize(v.kind, (const double*)ws, nb, loss_out, st);
@@ -1328,6 +1352,11 @@ extern "C" int dsrl_convt2x2_fwd_ce_s(const float* x, const float* w, const floa
                                       void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     DSRL_LABEL_SMOOTHING(eps, "convt2x2_fwd_ce_s");
     return convt_fwd_ce_any(CeVariant::smoothed(weights, eps), x, w, bias, y, N, H, W, Cin, Cout, target, ignore_index, loss_out, nan_flag, ws, ws_bytes, stream);
+}
+extern "C" int dsrl_convt2x2_fwd_ce_r(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                                      const uint8_t* target, int ignore_index, const float* weights, const uint32_t* mask, float* loss_out, int* nan_flag,
+                                      void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    return convt_fwd_ce_any(CeVariant::relaxed(weights, mask), x, w, bias, y, N, H, W, Cin, Cout, target, ignore_index, loss_out, nan_flag, ws, ws_bytes, stream);
 }
 static int convt_dw_blocks(int N, int H, int W) { return (int)std::min<long long>(convt_block_cap(1024), (long long)N * H * ceil_div(W, 64)); }
 extern "C" size_t dsrl_convt2x2_bwd_workspace_bytes(int N, int H, int W, int Cin, int Cout) {
@@ -1427,6 +1456,12 @@ extern "C" int dsrl_convt2x2_bwd_ce_s(const float* x, const float* w, const floa
                                       int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
     DSRL_LABEL_SMOOTHING(eps, "convt2x2_bwd_ce_s");
     return convt_bwd_ce_any(CeVariant::smoothed(weights, eps), x, w, logits, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, dx, dw, dbias, N, H, W, Cin, Cout,
+                            ws, ws_bytes, stream);
+}
+extern "C" int dsrl_convt2x2_bwd_ce_r(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* weights,
+                                      const uint32_t* mask, const float* ce_wsum, const float* ft_g, const float* ft_w, int ft_stride, float* dx, float* dw,
+                                      float* dbias, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, dsrl_stream_t stream) {
+    return convt_bwd_ce_any(CeVariant::relaxed(weights, mask), x, w, logits, target, ignore_index, ce_wsum, ft_g, ft_w, ft_stride, dx, dw, dbias, N, H, W, Cin, Cout,
                             ws, ws_bytes, stream);
 }
 extern "C" int dsrl_convt2x2_bwd_ce_d(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* weights,

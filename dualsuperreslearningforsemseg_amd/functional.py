@@ -1296,14 +1296,16 @@ class LogitsGrad:
     leaves `target`, `count` (device pointer holder) here and reports no gradient; the stride-8 feature transformer leaves its incoming gradient and
     weights; the ConvTranspose backward then forms d(CE)/d(logits) (+ the transformer's rank-one term) inside its own kernel
     (dsrl_convt2x2_bwd_ce): the 319 MB gradient of the 256x512 step is neither written nor read."""
-    __slots__ = ('y', 'xshape', 'x_ptr', 'armed', 'target', 'ignore_index', 'count', 'ft', 'value', 'value_key', 'weight', 'gamma', 'eps', 'dice', 'lovasz')
+    __slots__ = ('y', 'xshape', 'x_ptr', 'armed', 'target', 'ignore_index', 'count', 'ft', 'value', 'value_key', 'weight', 'gamma', 'eps', 'dice', 'lovasz',
+                 'relax')
 
     def __init__(self):
         self.y = None; self.xshape = None; self.x_ptr = 0; self.armed = False; self.target = None; self.ignore_index = 255; self.count = None; self.ft = None
         self.dice = None            # the record of dsrl_dice_fwd when the loss has a Dice term (always with a table, like gamma); None: no such term
         self.lovasz = None          # (record of dsrl_lovasz_fwd, bins) when the loss has a Lovasz-Softmax term (always with a table too); None: no such term
+        self.relax = None           # the class-set mask (relax_mask) of a relaxed loss (always with a table too); None: the label alone
         self.value = None           # [CE, pixel count, ...] when the producing layer already evaluated the loss (logits_target), and for which
-        self.value_key = None       # (target pointer, ignore_index, NaN flag pointer, class-weight table pointer or 0, label smoothing, focal gamma)
+        self.value_key = None       # (target pointer, ignore_index, NaN flag pointer, class-weight table pointer or 0, class-set mask pointer or 0, label smoothing, focal gamma)
         self.weight = None          # the 256-float class-weight table of a weighted loss (class_weight_table); `count` then holds D = sum n_c w_c
         self.gamma = 0.0            # > 0: the focal loss (always with a table: all ones when the caller gave no weights)
         self.eps = 0.0              # > 0: label smoothing (likewise always with a table; never together with gamma > 0)
@@ -1659,10 +1661,90 @@ def lovasz_softmax_loss(logits, target, ignore_index=255, weight=1.0, bins=1024)
     return _LovaszLoss.apply(logits, target, int(ignore_index), lovasz)
 
 
-def _focal_args(weight, gamma, device, num_classes, eps=0.0, dice=None, lovasz=None):
+LABEL_RELAX_RADIUS = (1, 4)             # the window radii dsrl_relax_mask has
+
+
+def label_relax_value(x):
+    """Boundary label relaxation as a setting -> the window radius, or None for none.  None, False and 0 turn it off; True is radius 1; an integer
+    in [1, 4] (also as an integral float) is that radius; a mapping {'radius': r} likewise.  Anything else (a bool is not a radius, a float that is
+    not integral, an unknown key, a radius outside the range) is a ValueError."""
+    lo, hi = LABEL_RELAX_RADIUS
+    if isinstance(x, np.bool_):
+        x = bool(x)
+    if x is None or x is False:
+        return None
+    if x is True:
+        return 1
+    keyed = isinstance(x, dict)
+    if keyed:
+        if set(x) != {'radius'}:
+            raise ValueError(f"label_relax = {x!r}: expected a mapping with the key 'radius'")
+        x = x['radius']
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+        raise ValueError(f"label_relax = {x!r}: expected None, a bool, an integer radius in [{lo}, {hi}] or a mapping {{'radius': r}}")
+    if not np.isfinite(x) or x != int(x):
+        raise ValueError(f'label_relax = {x!r}: the radius is not an integer')
+    r = int(x)
+    if r == 0 and not keyed:
+        return None
+    if not lo <= r <= hi:
+        raise ValueError(f'label_relax = {x!r}: expected a radius in [{lo}, {hi}]')
+    return r
+
+
+def _label_relax_args(label_relax, gamma, eps, ohem, dice, lovasz):
+    """label_relax of a CE call - label_relax_value(label_relax), or a ready class-set mask (an int32 tensor from relax_mask) as it is - after the
+    combinations it does not go with: everything but class weights."""
+    if not isinstance(label_relax, torch.Tensor):
+        label_relax = label_relax_value(label_relax)
+    elif label_relax.dtype != torch.int32:
+        raise ValueError(f'label_relax: a mask of dtype {label_relax.dtype}, expected the int32 tensor of relax_mask')
+    if label_relax is not None and (gamma > 0.0 or eps > 0.0 or ohem is not None or dice is not None or lovasz is not None):
+        shown = 'a mask' if isinstance(label_relax, torch.Tensor) else repr(label_relax)
+        raise ValueError(f'label_relax = {shown} together with focal_gamma = {gamma!r}, label_smoothing = {eps!r}, ohem = {ohem!r}, dice = {dice!r} '
+                         f'or lovasz = {lovasz!r}: the combination is not built')
+    return label_relax
+
+
+def relax_mask(target, num_classes, ignore_index=255, radius=1, stats=None):
+    """The class-set mask of boundary label relaxation (dsrl_relax_mask): target (N, H, W) uint8 on the GPU -> (N, H, W) int32 whose
+    bit c says that class c occurs among the live labels < num_classes in the (2 radius + 1)^2 window around the pixel, clipped at the borders of
+    its own image; 0 for a pixel that is ignored or whose label is >= num_classes.  stats: an int64 tensor of 2 on the same device that receives
+    ADDED counts {live pixels, pixels with more than one class in their set}, or None.  One launch, no host read (graph-capturable)."""
+    _need_gpu(target)
+    if target.dtype != torch.uint8 or target.dim() != 3:
+        raise DsrlHipError(f'relax_mask: target must be a (N, H, W) uint8 tensor, got {tuple(target.shape)} {target.dtype}')
+    target = target.contiguous()
+    N, H, W = target.shape
+    if stats is not None and (stats.dtype != torch.int64 or stats.numel() < 2 or stats.device != target.device or not stats.is_contiguous()):
+        raise DsrlHipError('relax_mask: stats must be a contiguous int64 tensor of 2 on the device of the target')
+    mask = torch.empty((N, H, W), device=target.device, dtype=torch.int32)
+    call('dsrl_relax_mask', target.data_ptr(), N, H, W, int(num_classes), int(ignore_index), int(radius), mask.data_ptr(),
+         None if stats is None else stats.data_ptr(), _stream())
+    return mask
+
+
+def _relax_mask_of(label_relax, target, num_classes, ignore_index):
+    """the mask a CE call uses: the given one, or dsrl_relax_mask of its own target at the given radius (label_relax went through _label_relax_args)"""
+    if label_relax is None:
+        return None
+    if target.dtype != torch.uint8:
+        target = target.to(torch.uint8)
+    target = target.contiguous()
+    if isinstance(label_relax, torch.Tensor):
+        _need_gpu(label_relax)
+        if label_relax.numel() != target.numel() or not label_relax.is_contiguous() or label_relax.device != target.device:
+            raise DsrlHipError(f'label_relax: a mask of {label_relax.numel()} words for a target of {target.numel()} pixels (contiguous, on its device)')
+        return label_relax
+    if num_classes > 32:
+        raise ValueError(f'label_relax: {num_classes} classes, a class set is one 32-bit word')
+    return relax_mask(target if target.dim() == 3 else target.reshape(-1, 1, target.shape[-1]), num_classes, ignore_index, label_relax)
+
+
+def _focal_args(weight, gamma, device, num_classes, eps=0.0, dice=None, lovasz=None, relax=None):
     """(class-weight table or None, gamma, eps) of a CE call: the focal and the label-smoothed loss run on the weighted kernels, so gamma > 0 or
     eps > 0 without weights takes the all-ones table of `num_classes` classes; so do a Dice term (`dice` not None) and a Lovasz-Softmax term
-    (`lovasz` not None), whose fused backwards are builds of the weighted kernel.  gamma and eps both at once: ValueError (the combination has no
+    (`lovasz` not None), whose fused backwards are builds of the weighted kernel, and the relaxed loss (`relax` not None).  gamma and eps both at once: ValueError (the combination has no
     agreed definition and no kernel)."""
     gamma = focal_gamma_value(gamma)
     eps = label_smoothing_value(eps)
@@ -1670,15 +1752,18 @@ def _focal_args(weight, gamma, device, num_classes, eps=0.0, dice=None, lovasz=N
         raise ValueError(f'label_smoothing = {eps!r} together with focal_gamma = {gamma!r}: the combination is not defined')
     if weight is not None:
         weight = class_weight_table(weight, device, num_classes)
-    elif gamma > 0.0 or eps > 0.0 or dice is not None or lovasz is not None:
+    elif gamma > 0.0 or eps > 0.0 or dice is not None or lovasz is not None or relax is not None:
         weight = class_weight_table(np.ones(int(num_classes), np.float32), device, num_classes)
     return weight, gamma, eps
 
 
-def _ce_variant(weight, gamma, eps):
+def _ce_variant(weight, gamma, eps, relax=None):
     """(suffix of the entry point, the arguments that follow ignore_index in its call) of a CE call whose (class-weight table, gamma, eps) went
     through _focal_args: '' plain, '_w' class-weighted, '_f' focal, '_s' label-smoothed.  Every family (dsrl_ce_fwd, dsrl_ce_bwd, dsrl_ce_fused,
-    dsrl_convt2x2_fwd_ce, dsrl_convt2x2_bwd_ce) and every workspace query names its four forms with these suffixes."""
+    dsrl_convt2x2_fwd_ce, dsrl_convt2x2_bwd_ce) and every workspace query names its four forms with these suffixes.  relax: the class-set mask of
+    a relaxed loss (relax_mask; never with gamma or eps: _label_relax_args), the fifth form '_r'."""
+    if relax is not None:
+        return '_r', (weight.data_ptr(), relax.data_ptr())
     if eps > 0.0:
         return '_s', (weight.data_ptr(), eps)
     if gamma > 0.0:
@@ -1701,9 +1786,12 @@ class logits_target:
     flag fused_losses will be given; weight: the class weights fused_losses will be given (None: unweighted); focal_gamma: its focal exponent
     (0: none); label_smoothing: its label smoothing (0: none; not together with focal_gamma > 0); ohem: its hard-pixel mining (ohem_value; not
     together with either of the two).  Outside the block, or when the shape does not qualify, nothing changes.  With ohem nothing is engaged either:
-    the target the loss will use does not exist before the logits do, so the plain forward runs and fused_losses evaluates the value itself."""
+    the target the loss will use does not exist before the logits do, so the plain forward runs and fused_losses evaluates the value itself.
+    label_relax: its boundary label relaxation (a radius, or the ready mask of relax_mask; with class weights only).  Unlike OHEM's target the mask
+    exists before the logits do, so the forward kernel IS engaged (dsrl_convt2x2_fwd_ce_r); fused_losses finds the value ready when it is given
+    the SAME mask tensor - a step computes the mask once and passes it to both (a radius here makes a mask of the layer's own)."""
 
-    def __init__(self, target, ignore_index, flag, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None, dice=None, lovasz=None):
+    def __init__(self, target, ignore_index, flag, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None, dice=None, lovasz=None, label_relax=None):
         focal_gamma = focal_gamma_value(focal_gamma)
         label_smoothing = label_smoothing_value(label_smoothing)
         if focal_gamma > 0.0 and label_smoothing > 0.0:
@@ -1713,11 +1801,14 @@ class logits_target:
         # as fused_losses will use) and dsrl_dice_fwd reads the logits once more
         dice = _dice_args(dice, focal_gamma, label_smoothing, ohem)
         lovasz = _lovasz_args(lovasz, focal_gamma, label_smoothing, ohem, dice)        # the same holds for a Lovasz-Softmax term (dsrl_lovasz_fwd)
+        relax = _label_relax_args(label_relax, focal_gamma, label_smoothing, ohem, dice, lovasz)
         ok = (convt_ce_enabled and target is not None and target.is_cuda and target.dtype == torch.uint8 and target.is_contiguous() and target.dim() == 3
               and flag is not None and flag.dtype == torch.int32 and ohem is None)
         if weight is not None and target is not None:
             weight = class_weight_table(weight, target.device)
-        self.new = (target, int(ignore_index), flag, weight, focal_gamma, label_smoothing, dice is not None or lovasz is not None) if ok else None
+        if ok and isinstance(relax, torch.Tensor):
+            relax = _relax_mask_of(relax, target, 0, ignore_index)         # (a ready mask: checked against the target; a radius waits for the class count)
+        self.new = (target, int(ignore_index), flag, weight, focal_gamma, label_smoothing, dice is not None or lovasz is not None, relax) if ok else None
 
     def __enter__(self):
         global _logits_target
@@ -1747,12 +1838,14 @@ class _ConvT2x2(torch.autograd.Function):
         lt = _logits_target if holder is not None else None
         if (lt is not None and tuple(lt[0].shape) == (N, 2 * H, 2 * W) and lt[0].device == x.device
                 and query('dsrl_convt2x2_fwd_ce_supported', x.data_ptr(), y.data_ptr(), N, H, W, Ci, Co)):       # (pointer arguments: not memoised)
-            tgt, ign, flag, wt, gamma, eps, diced = lt
-            if wt is not None or gamma > 0.0 or eps > 0.0 or diced:
-                wt = _focal_args(wt, gamma, x.device, Co, eps, True if diced else None)[0]           # (a table of another class count: ValueError)
-            sfx, extra = _ce_variant(wt, gamma, eps)
+            tgt, ign, flag, wt, gamma, eps, diced, rmask = lt
+            if rmask is not None:
+                rmask = _relax_mask_of(rmask, tgt, Co, ign)
+            if wt is not None or gamma > 0.0 or eps > 0.0 or diced or rmask is not None:
+                wt = _focal_args(wt, gamma, x.device, Co, eps, True if diced else None, None, rmask)[0]           # (a table of another class count: ValueError)
+            sfx, extra = _ce_variant(wt, gamma, eps, rmask)
             holder.value = torch.empty(8, device=x.device, dtype=torch.float32)
-            holder.value_key = (tgt.data_ptr(), ign, flag.data_ptr(), 0 if wt is None else wt.data_ptr(), eps, gamma)
+            holder.value_key = (tgt.data_ptr(), ign, flag.data_ptr(), 0 if wt is None else wt.data_ptr(), 0 if rmask is None else rmask.data_ptr(), eps, gamma)
             ws = _ws(cquery(f'dsrl_convt2x2_fwd_ce{sfx}_workspace_bytes', N, H, W), x)
             call('dsrl_convt2x2_fwd_ce' + sfx, x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), N, H, W, Ci, Co,
                  tgt.data_ptr(), ign, *extra, holder.value.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
@@ -1774,9 +1867,9 @@ class _ConvT2x2(torch.autograd.Function):
         h = ctx.holder
         hand = None
         if h is not None and h.armed:           # the loss left d(CE)/d(logits) to this layer: take it over, and disarm the holder whatever happens next
-            hand = (h.y, h.target, int(h.ignore_index), h.count, h.ft, h.weight, h.gamma, h.eps, h.dice, h.lovasz)
+            hand = (h.y, h.target, int(h.ignore_index), h.count, h.ft, h.weight, h.gamma, h.eps, h.dice, h.lovasz, h.relax)
             h.armed = False; h.ft = None; h.target = None; h.count = None; h.y = None; h.value = None; h.weight = None; h.gamma = 0.0; h.eps = 0.0
-            h.dice = None; h.lovasz = None
+            h.dice = None; h.lovasz = None; h.relax = None
         fused = dy is None and hand is not None
         if dy is None and not fused:
             raise DsrlHipError('conv_transpose2d_k2s2: backward reached without a gradient for the output')
@@ -1786,11 +1879,11 @@ class _ConvT2x2(torch.autograd.Function):
             # another consumer of the logits sent a gradient too (it is not the loss's: fused_losses returned none): d(CE)/d(logits) and the
             # transformer's term are written as the unfused step writes them (dsrl_ce_fused, dsrl_dice_bwd(accumulate = 1) when the loss has a Dice
             # term, dsrl_pointwise_strided_bwd(accumulate = 1)), dy is added as autograd would add it, and the plain backward below takes the sum
-            y, target, ign, _, ft, wt, gamma, eps, dice_rec, lov = hand
+            y, target, ign, _, ft, wt, gamma, eps, dice_rec, lov, rmask = hand
             P = N * 4 * H * W
             dl = new_cl((N, Co, 2 * H, 2 * W), x)
             scal = torch.empty(8, device=x.device, dtype=torch.float32)
-            sfx, extra = _ce_variant(wt, gamma, eps)
+            sfx, extra = _ce_variant(wt, gamma, eps, rmask)          # (dsrl_ce_fused_r writes the relaxed row)
             wsc = _ws(cquery(f'dsrl_ce_fused{sfx}_workspace_bytes', P), x)
             call('dsrl_ce_fused' + sfx, y.data_ptr(), Co, target.data_ptr(), P, Co, ign, *extra, dl.data_ptr(), Co, scal.data_ptr(), None,
                  wsc.data_ptr(), wsc.numel(), _stream())
@@ -1812,9 +1905,9 @@ class _ConvT2x2(torch.autograd.Function):
         db = (bsink if bsink is not None else torch.empty(Co, device=x.device, dtype=torch.float32)) if ctx.has_bias else None
         ws = _ws(cquery('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, Ci, Co), x)
         if fused:
-            y, target, ign, count, ft, wt, gamma, eps, dice_rec, lov = hand
+            y, target, ign, count, ft, wt, gamma, eps, dice_rec, lov, rmask = hand
             ft_g, ft_w, ft_s = ft if ft is not None else (None, None, 0)
-            sfx, extra = _ce_variant(wt, gamma, eps)
+            sfx, extra = _ce_variant(wt, gamma, eps, rmask)          # (dsrl_convt2x2_bwd_ce_r with a mask: never with gamma, eps, Dice or Lovasz)
             if dice_rec is not None:            # the weighted row plus the Dice row (never with gamma or eps: _dice_args)
                 sfx, extra = '_d', (wt.data_ptr(), dice_rec.data_ptr())
             if lov is not None:                 # the weighted row plus the Lovasz row (never with gamma, eps or Dice: _lovasz_args)
@@ -1929,7 +2022,7 @@ def pointwise_strided(x, weight, stride, out_slot=None):
 # ------------------------------------------------------------------------------------------------ losses
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, ignore_index, weight=None, gamma=0.0, eps=0.0):
+    def forward(ctx, logits, target, ignore_index, weight=None, gamma=0.0, eps=0.0, relax=None):
         logits, ld = pm(logits)
         _need_gpu(target)
         if target.dtype != torch.uint8:
@@ -1940,7 +2033,8 @@ class _CrossEntropy(torch.autograd.Function):
         if target.numel() != P:
             raise DsrlHipError(f'cross_entropy: target has {target.numel()} pixels, logits {P}')
         out = torch.empty(2, device=logits.device, dtype=torch.float32)
-        sfx, extra = _ce_variant(weight, gamma, eps)
+        relax = _relax_mask_of(relax, target.view(N, H, W), Cc, ignore_index)
+        sfx, extra = _ce_variant(weight, gamma, eps, relax)
         ws = _ws(cquery(f'dsrl_ce{sfx}_workspace_bytes', P), logits)
         call('dsrl_ce_fwd' + sfx, logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), *extra, out.data_ptr(),
              ws.data_ptr(), ws.numel(), _stream())
@@ -1949,6 +2043,7 @@ class _CrossEntropy(torch.autograd.Function):
         ctx.weight = weight
         ctx.gamma = gamma
         ctx.eps = eps
+        ctx.relax = relax
         return out[0].clone()
 
     @staticmethod
@@ -1958,13 +2053,13 @@ class _CrossEntropy(torch.autograd.Function):
         N, Cc, H, W = logits.shape
         g = g.reshape(1).contiguous().float()
         dl = new_cl((N, Cc, H, W), logits)
-        sfx, extra = _ce_variant(ctx.weight, ctx.gamma, ctx.eps)
+        sfx, extra = _ce_variant(ctx.weight, ctx.gamma, ctx.eps, ctx.relax)
         call('dsrl_ce_bwd' + sfx, logits.data_ptr(), ld, target.data_ptr(), N * H * W, Cc, ctx.ignore_index, *extra, out.data_ptr(), g.data_ptr(),
              dl.data_ptr(), Cc, _stream())
-        return dl, None, None, None, None, None
+        return dl, None, None, None, None, None, None
 
 
-def cross_entropy(logits, target, ignore_index=255, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None, dice=None, lovasz=None):
+def cross_entropy(logits, target, ignore_index=255, weight=None, focal_gamma=0.0, label_smoothing=0.0, ohem=None, dice=None, lovasz=None, label_relax=None):
     """nn.CrossEntropyLoss(weight, ignore_index, label_smoothing=) with mean reduction; target (N,H,W) uint8/long; weight: None, one number per
     class, or a class_weight_table.  focal_gamma > 0: the focal loss sum w[t] (1 - p_t)^gamma (-log p_t) / sum w[t]; 0 changes
     nothing.  label_smoothing in (0, 1]: torch's smoothed loss, with one deviation: a class of weight 0 adds nothing to the
@@ -1975,13 +2070,19 @@ def cross_entropy(logits, target, ignore_index=255, weight=None, focal_gamma=0.0
     without class weights; together with focal_gamma > 0, label_smoothing > 0 or ohem: ValueError.
     lovasz (lovasz_value: None, True, a weight, (weight, bins) or a mapping): adds weight * L_lovasz, the quantised Lovasz-Softmax loss
     (lovasz_softmax_loss), with or without class weights; together with focal_gamma > 0, label_smoothing > 0, ohem or dice:
-    ValueError."""
+    ValueError.
+    label_relax (label_relax_value: None, True, a radius in [1, 4] or {'radius': r}; or a ready mask from relax_mask): boundary label relaxation
+     - a pixel's term is -w[t] log of the summed probability of the classes in the window around it, at most 32 classes, with
+    or without class weights; together with any of the other options: ValueError."""
     dice = _dice_args(dice, focal_gamma_value(focal_gamma), label_smoothing_value(label_smoothing), ohem_value(ohem))
     lovasz = _lovasz_args(lovasz, focal_gamma_value(focal_gamma), label_smoothing_value(label_smoothing), ohem_value(ohem), dice)
-    weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, logits.device, logits.shape[1], label_smoothing)
+    label_relax = _label_relax_args(label_relax, focal_gamma_value(focal_gamma), label_smoothing_value(label_smoothing), ohem_value(ohem), dice, lovasz)
+    weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, logits.device, logits.shape[1], label_smoothing, relax=label_relax)
     ohem = _ohem_args(ohem, focal_gamma, label_smoothing, ignore_index)
     if ohem is not None:
         target = ohem_target(logits, target, ignore_index, *ohem)
+    if label_relax is not None:
+        return _CrossEntropy.apply(logits, target, ignore_index, weight, focal_gamma, label_smoothing, label_relax)
     ce =_CrossEntropy.apply(logits, target, ignore_index, weight, focal_gamma, label_smoothing)
     if lovasz is not None:
         return ce + _LovaszLoss.apply(logits, target, int(ignore_index), lovasz)
@@ -2022,7 +2123,8 @@ class _FusedLosses(torch.autograd.Function):
     its incoming gradient is 1 (TrainStep calls vals[3].backward()); the stored gradients are returned as they are."""
 
     @staticmethod
-    def forward(ctx, sssr, sisr, ft1, ft2, target, org, ignore_index, w1, w2, stage, flag, k, weight=None, gamma=0.0, eps=0.0, dice=None, lovasz=None):
+    def forward(ctx, sssr, sisr, ft1, ft2, target, org, ignore_index, w1, w2, stage, flag, k, weight=None, gamma=0.0, eps=0.0, dice=None, lovasz=None,
+                relax=None):
         want = bool(ctx.needs_input_grad[0])          # forward-only (validation, no_grad): no gradient buffers are written
         logits, ld = pm(sssr)
         _need_gpu(target)
@@ -2042,10 +2144,11 @@ class _FusedLosses(torch.autograd.Function):
             lg = None
         dl = new_cl((N, Cc, H, W), logits) if (want and lg is None) else None      # lg: the producer of the logits forms this gradient in its own backward
         if lg is not None and lg.value is not None and lg.value_key == (target.data_ptr(), int(ignore_index), flag.data_ptr(),
-                                                                        0 if weight is None else weight.data_ptr(), eps, gamma):
+                                                                        0 if weight is None else weight.data_ptr(),
+                                                                        0 if relax is None else relax.data_ptr(), eps, gamma):
             scal = lg.value                                             # the producer's forward kernel evaluated the loss (logits_target)
         else:
-            sfx, extra = _ce_variant(weight, gamma, eps)
+            sfx, extra = _ce_variant(weight, gamma, eps, relax)
             ws = _ws(cquery(f'dsrl_ce_fused{sfx}_workspace_bytes', P), logits)
             call('dsrl_ce_fused' + sfx, logits.data_ptr(), ld, target.data_ptr(), P, Cc, int(ignore_index), *extra,
                  None if dl is None else dl.data_ptr(), Cc, scal.data_ptr(), flag.data_ptr(), ws.data_ptr(), ws.numel(), st)
@@ -2099,6 +2202,7 @@ class _FusedLosses(torch.autograd.Function):
             lg.target = target; lg.ignore_index = int(ignore_index); lg.count = scal; lg.ft = None; lg.weight = weight; lg.gamma = gamma; lg.eps = eps; lg.armed = True
             lg.dice = rec
             lg.lovasz = None if lrec is None else (lrec, lovasz[1])
+            lg.relax = relax
         ctx.lg = lg
         ctx.grads = (dl, da)
         ctx.w2 = float(w2)
@@ -2138,7 +2242,7 @@ class _FusedLosses(torch.autograd.Function):
             if slot is not None and buf is not None and not slot.closed and slot.buf is None:
                 slot.buf = buf
                 out[i] = None
-        return out[0], out[1], d1, d2, None, None, None, None, None, None, None, None, None, None, None, None, None
+        return out[0], out[1], d1, d2, None, None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 _fused_losses_root_checked = False
@@ -2171,7 +2275,7 @@ def fused_losses_backward(vals):
 
 
 def fused_losses(outs, target, input_org, ignore_index, w1, w2, stage, flag, subsample_factor=8, weight=None, focal_gamma=0.0, label_smoothing=0.0,
-                 ohem=None, dice=None, lovasz=None):
+                 ohem=None, dice=None, lovasz=None, label_relax=None):
     """-> 5-float device tensor [CE, w1*MSE, w2*FA, total, NaN flag]; `outs` = DSRL.forward's 4-tuple.  vals[3].backward() is the only
     supported backward (the function is the root of the pass); `flag` is the int32 NaN flag the fused kernels OR into.  weight: per-class CE
     weights (None, one number per class, or a class_weight_table): nn.CrossEntropyLoss(weight=).  focal_gamma > 0 makes the CE term the focal loss
@@ -2182,18 +2286,23 @@ def fused_losses(outs, target, input_org, ignore_index, w1, w2, stage, flag, sub
     gradient of the term is added to d(CE)/d(logits), inside the ConvTranspose backward when the hand-over engages (dsrl_convt2x2_bwd_ce_d).  The CE
     then runs on the weighted kernels (all-ones weights when `weight` is None); not together with focal_gamma > 0, label_smoothing > 0 or ohem.
     lovasz (as cross_entropy) adds the quantised Lovasz-Softmax term in the same way (dsrl_convt2x2_bwd_ce_l when the hand-over engages); not
-    together with any of the others but `weight`."""
+    together with any of the others but `weight`.
+    label_relax (as cross_entropy: a radius, or the ready mask of relax_mask) makes the CE term the relaxed loss: dsrl_ce_fused_r, or the value of
+    the logits layer's forward (logits_target given the same mask) and dsrl_convt2x2_bwd_ce_r when the hand-over engages; likewise with `weight`
+    only."""
     sssr, sisr, ft1, ft2 = outs
     dice = _dice_args(dice, focal_gamma_value(focal_gamma), label_smoothing_value(label_smoothing), ohem_value(ohem))
     lovasz = _lovasz_args(lovasz, focal_gamma_value(focal_gamma), label_smoothing_value(label_smoothing), ohem_value(ohem), dice)
-    weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, sssr.device, sssr.shape[1], label_smoothing, dice, lovasz)
+    label_relax = _label_relax_args(label_relax, focal_gamma_value(focal_gamma), label_smoothing_value(label_smoothing), ohem_value(ohem), dice, lovasz)
+    weight, focal_gamma, label_smoothing = _focal_args(weight, focal_gamma, sssr.device, sssr.shape[1], label_smoothing, dice, lovasz, label_relax)
     ohem = _ohem_args(ohem, focal_gamma, label_smoothing, ignore_index)
     if ohem is not None:
         target = ohem_target(sssr, target, ignore_index, *ohem, flag=flag)
+    relax_arg = () if label_relax is None else (_relax_mask_of(label_relax, target.reshape(-1, *target.shape[-2:]), sssr.shape[1], ignore_index),)
     dummy = _const1(0.0, sssr.device)            # stands in for the outputs a lower stage does not have (a cached constant: no fill launch per step)
     return _FusedLosses.apply(sssr, sisr if stage > 1 else dummy, ft1 if stage > 2 else dummy, ft2 if stage > 2 else dummy, target,
                               input_org if stage > 1 else dummy, int(ignore_index), float(w1), float(w2), int(stage), flag, int(subsample_factor), weight,
-                              focal_gamma, label_smoothing, dice, lovasz)
+                              focal_gamma, label_smoothing, dice, lovasz, *relax_arg)
 
 
 _RED = {'mean': 0, 'sum': 1, 'none': 2}

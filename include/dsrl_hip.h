@@ -520,6 +520,40 @@ int dsrl_convt2x2_bwd_ce_s(const float* x, const float* w, const float* logits, 
                            int ft_stride, float* dx, float* dw, float* dbias /*nullable*/, int N, int H, int W, int Cin, int Cout, void* ws,
                            size_t ws_bytes, dsrl_stream_t stream);
 
+/* Boundary label relaxation (Zhu et al., CVPR 2019).  dsrl_relax_mask writes one class-set word per pixel of a (N, H, W) label map:
+ *     mask[i] = OR of (1 << t_j) over the pixels j of the (2 radius + 1)^2 window around i, clipped at the borders of i's own image, whose label is
+ *               neither ignore_index nor >= C;   0 when t_i itself is ignore_index or >= C
+ * radius in [1, 4] and C in [1, 32], checked first: anything else is DSRL_E_BADARG and nothing is launched or written.  Integer work, one launch, no
+ * workspace, no host read (graph-capturable).  `stats` (nullable, 8-byte aligned) receives ADDED counts {pixels with t != ignore_index, pixels whose
+ * set holds more than one class}: integer atomics, identical run to run.
+ * The relaxed cross entropy asks for the probability of the set S_i = (mask_i & ((1 << C) - 1)) | bit(t_i) instead of the label (a caller's word can
+ * neither drop the own label nor name a class that does not exist; a word of zeros IS the weighted form, bit for bit).  With m, e_c, s, w and D as
+ * for the _w entry points, m_S = max_{c in S} v_c, g_c = [c in S] exp(v_c - m_S), z = sum_{c in S} g_c (c ascending):
+ *     loss  = sum_live w[t_i] ((m + log s) - (m_S + log z)) / D          dl_ic = live_i (w[t_i] / D) (e_c / s - g_c / z)
+ * Each _r entry point is its _w sibling with `const uint32_t* mask` (P words, or N * 2H * 2W) after `weights` (all-ones weights for an unweighted
+ * relaxed loss) and C <= 32: same contracts, flags and workspaces (the _r size queries are those of the _w siblings); dsrl_ce_fused_r and
+ * dsrl_ce_fwd_r / dsrl_ce_bwd_r(grad_out = 1) give the same bits, and dsrl_convt2x2_bwd_ce_r is bit-identical to
+ * dsrl_ce_fused_r -> dsrl_pointwise_strided_bwd(accumulate = 1) -> dsrl_convt2x2_bwd. */
+int dsrl_relax_mask(const uint8_t* target, int N, int H, int W, int C, int ignore_index, int radius, uint32_t* mask,
+                    unsigned long long* stats /*[2], nullable*/, dsrl_stream_t stream);
+size_t dsrl_ce_r_workspace_bytes(int64_t P);
+int dsrl_ce_fwd_r(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights /*[256]*/,
+                  const uint32_t* mask, float* loss_out /*[2]*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+int dsrl_ce_bwd_r(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights /*[256]*/,
+                  const uint32_t* mask, const float* loss_out, const float* grad_out, float* dlogits, int lddl, dsrl_stream_t stream);
+size_t dsrl_ce_fused_r_workspace_bytes(int64_t P);
+int dsrl_ce_fused_r(const float* logits, int ld, const uint8_t* target, int64_t P, int C, int ignore_index, const float* weights /*[256]*/,
+                    const uint32_t* mask, float* dlogits /*nullable*/, int lddl, float* loss_out /*[2]*/, int* nan_flag /*nullable*/, void* ws,
+                    size_t ws_bytes, dsrl_stream_t stream);
+size_t dsrl_convt2x2_fwd_ce_r_workspace_bytes(int N, int H, int W);
+int dsrl_convt2x2_fwd_ce_r(const float* x, const float* w, const float* bias /*nullable*/, float* y, int N, int H, int W, int Cin, int Cout,
+                           const uint8_t* target, int ignore_index, const float* weights /*[256]*/, const uint32_t* mask, float* loss_out,
+                           int* nan_flag /*nullable*/, void* ws, size_t ws_bytes, dsrl_stream_t stream);
+int dsrl_convt2x2_bwd_ce_r(const float* x, const float* w, const float* logits, const uint8_t* target, int ignore_index, const float* weights /*[256]*/,
+                           const uint32_t* mask, const float* ce_wsum /*D: loss_out + 1*/, const float* ft_g /*nullable*/, const float* ft_w /*nullable*/,
+                           int ft_stride, float* dx, float* dw, float* dbias /*nullable*/, int N, int H, int W, int Cin, int Cout, void* ws,
+                           size_t ws_bytes, dsrl_stream_t stream);
+
 /* Online hard example mining (OHEM) for the cross entropy, as a rewrite of the target: the rule of mmseg's OHEMPixelSampler and HRNet's
  * OhemCrossEntropy.  For one call of P pixels, `thresh` in [0, 1] and min_kept >= 0:
  *     a pixel is a candidate iff target != ignore_index && target < C; every other pixel takes no part and keeps its label

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Cost of one cross-entropy variant at the step's shape (N = 8, tail input 256 x 512, 19 -> 19), written to profiles/<variant>_ce.txt
-(class_weighted_ce.txt, focal_ce.txt, label_smoothing_ce.txt, ohem_ce.txt, dice_ce.txt, lovasz_ce.txt):
+(class_weighted_ce.txt, focal_ce.txt, label_smoothing_ce.txt, ohem_ce.txt, dice_ce.txt, lovasz_ce.txt, label_relax_ce.txt):
   * kernel-only times through the C ABI, HIP events around back-to-back launches, the variant's entry points against their base:
       weighted   dsrl_convt2x2_fwd_ce_w, dsrl_convt2x2_bwd_ce_w and dsrl_ce_fused_w against the unweighted calls, and the D pre-pass alone
                  (dsrl_ce_weight_sum: label histogram + weight sum);
@@ -14,10 +14,14 @@
                  contended case), each with the per-wave aggregation of levels 0 and K - 1 and without it (DSRL_LOVASZ_AGG=0), beside dsrl_dice_fwd
                  and dsrl_copy2d on as many bytes; dsrl_lovasz_bwd; dsrl_convt2x2_bwd_ce_l against _d and _w; the torch composition (softmax, 19 x
                  torch.sort, cumsum); five windows each, lambda = 1;
+      relaxed    dsrl_relax_mask (radius 1, 2 and 4) beside dsrl_copy2d of as many bytes; dsrl_convt2x2_fwd_ce_r, dsrl_convt2x2_bwd_ce_r and
+                 dsrl_ce_fused_r against their _w siblings on the same logits, with the masks of labels on an 8 x 8 block grid and with all-singleton
+                 masks (zeros); five windows each;
   * the replayed training step (stage 3, batch 8, 256 x 512 input, hipGraph): default, class weights and (focal, smoothed) class weights + gamma
-    or eps, alternating in one process (ohem: default against ohem = (0.7, 100000); dice / lovasz: default, class weights, class weights + the term).
+    or eps, alternating in one process (ohem: default against ohem = (0.7, 100000); dice / lovasz: default, class weights, class weights + the term;
+    relaxed: default, class weights, class weights + label_relax = 1, on labels of an 8 x 8 block grid, three rounds).
 Everything in that file from the line '## recorded beside the tool' on is kept as it is.
-Usage: python tools/ce_variant_bench.py weighted|focal|smoothed|ohem|dice|lovasz [--steps K] [--no-step] [VAR=value ...]"""
+Usage: python tools/ce_variant_bench.py weighted|focal|smoothed|ohem|dice|lovasz|relaxed [--steps K] [--no-step] [VAR=value ...]"""
 import os
 import sys
 import time
@@ -40,7 +44,8 @@ VARIANTS = {'weighted': ('_w', '', None, None, 'weighted', None, 'class_weighted
             'smoothed': ('_s', '_w', 0.1, 'eps', 'smoothed', 'label_smoothing', 'label_smoothing_ce.txt'),
             'ohem': ('', '', (0.7, 100000), 'ohem', 'ohem', 'ohem', 'ohem_ce.txt'),
             'dice': ('_d', '_w', (1.0, 1.0), 'dice', 'dice', 'dice', 'dice_ce.txt'),
-            'lovasz': ('_l', '_w', (1.0, 1024), 'lovasz', 'lovasz', 'lovasz', 'lovasz_ce.txt')}
+            'lovasz': ('_l', '_w', (1.0, 1024), 'lovasz', 'lovasz', 'lovasz', 'lovasz_ce.txt'),
+            'relaxed': ('_r', '_w', 1, 'radius', 'relaxed', 'label_relax', 'label_relax_ce.txt')}
 if not args or args[0] not in VARIANTS:
     sys.exit(__doc__)
 VARIANT = args[0]
@@ -339,6 +344,75 @@ def lovasz_kernels():
         f'{h[0][:, 0].sum() / h[0].sum():.4f} of the foreground errors in level 0')
 
 
+def block_labels(N, H, W, C, b, ignore=0.08):
+    """(N, H, W) uint8 labels on the device: one class per b x b block, some blocks ignored"""
+    g = torch.randint(0, C, (N, H // b, W // b), device=dev, dtype=torch.uint8)
+    g[torch.rand(g.shape, device=dev) < ignore] = 255
+    return g.repeat_interleave(b, 1).repeat_interleave(b, 2).contiguous()
+
+
+def relaxed_kernels():
+    N, H, W, C = 8, 256, 512, 19
+    P = N * 4 * H * W
+    rs = np.random.RandomState(1)
+    x = torch.randn(N, H, W, C, device=dev); w = torch.randn(C, C, 2, 2, device=dev) * 0.2; b = torch.randn(C, device=dev)
+    y = torch.empty(N, 2 * H, 2 * W, C, device=dev)
+    tg = block_labels(N, 2 * H, 2 * W, C, 8)
+    wt = HF.class_weight_table(rs.uniform(0.25, 8.0, C), dev)
+    dx = torch.empty_like(x); dw = torch.empty_like(w); db = torch.empty(C, device=dev); dl = torch.empty_like(y)
+    scal = torch.zeros(8, device=dev); flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    ftg = torch.randn(N, H // 4, W // 4, device=dev); ftw = torch.randn(C, device=dev)
+    stats = torch.zeros(2, dtype=torch.int64, device=dev)
+    st = HF._stream()
+    wb = torch.empty(query('dsrl_convt2x2_bwd_workspace_bytes', N, H, W, C, C), dtype=torch.uint8, device=dev)
+    masks = {'block-8 masks': HF.relax_mask(tg, C, 255, 1, stats), 'singleton masks': torch.zeros(N, 2 * H, 2 * W, dtype=torch.int32, device=dev)}
+    live, multi = stats.cpu().tolist()
+    wsp = {}
+
+    def ws(name, *a):
+        if (name, a) not in wsp:
+            wsp[name, a] = torch.empty(query(name, *a), dtype=torch.uint8, device=dev)
+        return wsp[name, a].data_ptr(), wsp[name, a].numel()
+
+    def extra(s, m):
+        return (wt.data_ptr(),) if s == '_w' else (wt.data_ptr(), m.data_ptr())
+
+    def fwd_ce(s, m):
+        call('dsrl_convt2x2_fwd_ce' + s, x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), N, H, W, C, C, tg.data_ptr(), 255, *extra(s, m),
+             scal.data_ptr(), flag.data_ptr(), *ws(f'dsrl_convt2x2_fwd_ce{s}_workspace_bytes', N, H, W), st)
+
+    def bwd_ce(s, m):
+        call('dsrl_convt2x2_bwd_ce' + s, x.data_ptr(), w.data_ptr(), y.data_ptr(), tg.data_ptr(), 255, *extra(s, m), scal.data_ptr() + 4,
+             ftg.data_ptr(), ftw.data_ptr(), 8, dx.data_ptr(), dw.data_ptr(), db.data_ptr(), N, H, W, C, C, wb.data_ptr(), wb.numel(), st)
+
+    def ce_fused(s, m):
+        call('dsrl_ce_fused' + s, y.data_ptr(), C, tg.data_ptr(), P, C, 255, *extra(s, m), dl.data_ptr(), C, scal.data_ptr(), flag.data_ptr(),
+             *ws(f'dsrl_ce_fused{s}_workspace_bytes', P), st)
+
+    mk = torch.empty(N, 2 * H, 2 * W, dtype=torch.int32, device=dev)
+    rows = [(f'dsrl_relax_mask, radius {r}, with the counters', 5 * P,
+             lambda r=r: call('dsrl_relax_mask', tg.data_ptr(), N, 2 * H, 2 * W, C, 255, r, mk.data_ptr(), stats.data_ptr(), st)) for r in (1, 2, 4)]
+    rows.append(('dsrl_relax_mask, radius 1, no counters', 5 * P,
+                 lambda: call('dsrl_relax_mask', tg.data_ptr(), N, 2 * H, 2 * W, C, 255, 1, mk.data_ptr(), None, st)))
+    nf = 5 * P // 8                                 # floats whose read + write is as many bytes as P labels read + P words written
+    rows.append(('dsrl_copy2d of as many bytes', 5 * P, lambda: call('dsrl_copy2d', y.data_ptr(), C, dl.data_ptr(), C, nf // C, C, st)))
+    fwd_ce('_w', None)                              # the logits, and D in scal[1]
+    for name, f in (('dsrl_convt2x2_fwd_ce', fwd_ce), ('dsrl_convt2x2_bwd_ce', bwd_ce), ('dsrl_ce_fused', ce_fused)):
+        for waves in (('12', '8') if f is bwd_ce else (None,)):
+            tag = f' (DSRL_CONVT_CE_WAVES={waves})' if waves else ''
+            rows.append((f'{name}_w{tag}', 0, lambda f=f, waves=waves: (waves and os.environ.__setitem__('DSRL_CONVT_CE_WAVES', waves), f('_w', None))))
+        for label, m in masks.items():
+            rows.append((f'{name}_r, {label}' + (' (8 waves)' if f is bwd_ce else ''), 0, lambda f=f, m=m: f('_r', m)))
+    say(f'kernel-only, us per call (N = {N}, tail input {H} x {W}, {P} pixels; labels on an 8 x 8 block grid: {multi / live:.3f} of the live pixels have')
+    say('more than one class in their set at radius 1; five windows of 20 back-to-back calls each: min / median / max of the windows; bytes and rate at')
+    say('the median):')
+    for label, nbytes, f in rows:
+        wins = sorted(timeit(f) for _ in range(5))
+        rate = f'   {nbytes / 1e6:6.1f} MB   {nbytes / wins[2] / 1e6:5.2f} TB/s' if nbytes else ''
+        say(f'  {label:<58} {wins[0]:7.1f} / {wins[2]:7.1f} / {wins[4]:7.1f}{rate}')
+    os.environ.pop('DSRL_CONVT_CE_WAVES', None)
+
+
 def replayed_step():
     import dualsuperreslearningforsemseg_amd as D
     from dualsuperreslearningforsemseg_amd import settings
@@ -354,6 +428,8 @@ def replayed_step():
     model = model.to(dev).to(memory_format=torch.channels_last).train()
     flat = FlatParams(model)
     (img, org), (tgt, _) = next(iter(SyntheticCityscapes(8, (256, 512), torch.device(dev), length=1)))
+    if VARIANT == 'relaxed':
+        tgt = block_labels(*tgt.shape, cs.NUM_CLASSES, 8)          # labels with borders: the synthetic ones are noise, every set would be full
     w = np.random.RandomState(2).uniform(0.25, 8.0, cs.NUM_CLASSES)
 
     def run(step, n):
@@ -372,7 +448,7 @@ def replayed_step():
     else:
         kinds = {'default': {}, 'weighted': {'class_weights': w}, WORD: {'class_weights': w, STEP_KW: PARAM}}
     res, replays = {k: [] for k in kinds}, {}
-    for _ in range(3 if VARIANT in ('dice', 'lovasz') else 2):      # one captured step at a time (the device-resident dropout key has one binding): build, warm, time, release
+    for _ in range(3 if VARIANT in ('dice', 'lovasz', 'relaxed') else 2):      # one captured step at a time (the device-resident dropout key has one binding): build, warm, time, release
         for k, kw in kinds.items():
             s = TrainStep(model, flat, 3, 0.1, 1.0, cs.IGNORE_CLASS_LABEL, **kw)
             run(s, s.GRAPH_WARMUP + 6)
@@ -394,9 +470,12 @@ def replayed_step():
     else:
         say(f"  {WORD} - weighted (min): {(min(res[WORD]) - min(res['weighted'])) * 1e3:+.0f} us;  {WORD} - default (min): "
             f"{(min(res[WORD]) - min(res['default'])) * 1e3:+.0f} us")
+        if VARIANT == 'relaxed':
+            say('  spread (max - min) per kind, us: ' + '  '.join(f'{k} {(max(v) - min(v)) * 1e3:.0f}' for k, v in res.items()))
 
 
-ohem_kernels() if VARIANT == 'ohem' else dice_kernels() if VARIANT == 'dice' else lovasz_kernels() if VARIANT == 'lovasz' else kernels()
+(ohem_kernels() if VARIANT == 'ohem' else dice_kernels() if VARIANT == 'dice' else lovasz_kernels() if VARIANT == 'lovasz' else
+ relaxed_kernels() if VARIANT == 'relaxed' else kernels())
 if '--no-step' not in args:
     replayed_step()
 out = os.path.join(ROOT, 'profiles', OUT)
